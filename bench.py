@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — configuration collision checks/sec (Panda, 64-primitive environment) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts its N ranks itself, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                               (N > 1: starts its N ranks itself, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path (vmv_validate_batch: FK + environment + self-collision, one validity bit per
@@ -9,13 +10,16 @@ configuration) over one batch of synthetic Panda configurations already resident
 
   weak scaling (the line's `value`): 1,048,576 configurations PER GPU per step; with N > 1 every step ends with the
       RCCL all-gather of the packed validity bitmasks (the path's only exchange step), overlapped with the next step.
-  strong scaling (the line's `strong` object): ONE 1,048,576-configuration batch per step, cut into 64-aligned
+  strong scaling (the line's `strong` object, --full): ONE 1,048,576-configuration batch per step, cut into 64-aligned
       contiguous shards (vamp_mvt_amd.sharding.shard_range), all-gathered the same way.  At N = 1 both are the same job.
 
-Prints ONE JSON line (rank 0).  `roofline` is computed from HIP events recorded on the launch stream around each
-kernel launch inside the timed region; its `valu` / `traffic` parts quote the rocprofv3 PMC summary under profiles/
-only if that summary was measured on this very build (source hash); `cpu_baseline` times the CPU oracle (test
-infrastructure) on a bounded sample of the same workload on this box's host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the weak-scaling steps and prints the headline
+figure; --dump-outputs DIR also writes the validity booleans of the last timed step (DIR/valid.npy, float32).
+Everything else is measured only with --full: `strong`, `roofline` (from HIP events recorded on the launch stream
+around each kernel launch inside the timed region; its `valu` / `traffic` parts quote the rocprofv3 PMC summary under
+profiles/ only if that summary was measured on this very build, by source hash), the N = 2, 4, 8 `shard_probe`, the
+informational `two_streams` leg, and `cpu_baseline`, which times the CPU oracle (test infrastructure) on a bounded
+sample of the same workload on the host's cores.
 """
 from __future__ import annotations
 
@@ -36,6 +40,8 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 N_SIMD = 256 * 4           # 256 CUs x 4 SIMDs
 VALU_CYCLES_PER_INST = 2   # MI355X_MICROARCH.md: wave64 v_fma/v_add on the SIMD-32 = 2 cycles
 CLOCK_GHZ = 2.4
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: larger outputs are written as a fixed, seeded sample
+DUMP_SAMPLE = 1 << 22        # float32 booleans + float64 positions: 48 MiB
 
 
 def _load_by_path(name, path):
@@ -108,6 +114,23 @@ def _cpu_model():
     return "unknown"
 
 
+def dump_outputs(path, words, n, ranks):
+    """The validity booleans of the last timed step (1.0 = valid) as DIR/valid.npy: n per rank, in rank order, from
+    `ranks` consecutive blocks of (n + 63) // 64 validity words.  Above DUMP_LIMIT_BYTES a seeded sample of DUMP_SAMPLE
+    of them, with their positions in the full output as DIR/valid_index.npy."""
+    import numpy as np
+    from vamp_mvt_amd import unpack_bits
+
+    per = (n + 63) // 64
+    v = np.concatenate([unpack_bits(words[r * per:(r + 1) * per], n) for r in range(ranks)]).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    if v.nbytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(path, "valid_index.npy"), idx.astype(np.float64))
+        v = v[idx]
+    np.save(os.path.join(path, "valid.npy"), v)
+
+
 def pmc_profile():
     """profiles/r03_pmc.json (tools/profile.sh + tools/make_pmc_profile.py) if it was measured on THIS build"""
     path = os.path.join(ROOT, "profiles", "r03_pmc.json")
@@ -129,10 +152,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--configs", type=int, default=CONFIGS_PER_GPU, help="configurations per GPU per step (weak) and "
                     "per job per step (strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shard-probe", action="store_true", help="skip the timing of the N = 2, 4, 8 shard sizes on this GPU")
+    ap.add_argument("--full", action="store_true", help="also measure the strong-scaling leg, the per-kernel roofline, "
+                    "the shard probe, the two-stream leg and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the validity booleans of the last timed step as "
+                    "DIR/valid.npy (float32, 1.0 = valid)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-shard-probe", action="store_true",
+                    help="with --full: skip the timing of the N = 2, 4, 8 shard sizes on this GPU")
     ap.add_argument("--no-two-streams", action="store_true",
-                    help="skip the informational two-stream leg (profiling runs: its overlapping launches would mix into the per-kernel averages)")
+                    help="with --full: skip the informational two-stream leg (profiling runs: its overlapping launches "
+                         "would mix into the per-kernel averages)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 21)
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="development only: run the N-rank control flow with every rank on cuda:0 and the exchange "
@@ -140,6 +169,8 @@ def main():
     ap.add_argument("--env", default="shell64", choices=["shell64", "empty", "cage"],
                     help="diagnostics only: the metric is defined on shell64 (BASELINE config 2)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -252,17 +283,22 @@ def main():
     q = torch.empty((n, 7), dtype=torch.float32, device=dev)
     check(lib.vmv_fill_uniform_configs(panda._id, ctypes.c_void_p(q.data_ptr()), n, 1234 + rank, sptr),
           "vmv_fill_uniform_configs")
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
-    elapsed, words_w = run(q, n, (n + 63) // 64, args.steps, args.warmup, evs)
-    kernel_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))  # dominant kernel: environment half
-    self_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)] if args.full else None
+    per_w = (n + 63) // 64
+    elapsed, words_w = run(q, n, per_w, args.steps, args.warmup, evs)
+    if args.full:
+        kernel_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))  # dominant kernel: environment half
+        self_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
     valid_frac = None
     if rank == 0:
-        host_bits = words_w[: (n + 63) // 64].cpu().numpy().view(np.uint64)
-        valid_frac = float(vamp.unpack_bits(host_bits, n).mean())
+        host_words = words_w.cpu().numpy().view(np.uint64)
+        valid_frac = float(vamp.unpack_bits(host_words[:per_w], n).mean())
+        if args.dump_outputs:
+            # every rank's n booleans when the words were all-gathered on the device, else this rank's
+            dump_outputs(args.dump_outputs, host_words, n, world if world > 1 and not cpu_exchange else 1)
 
     # ---- strong scaling: ONE n-configuration batch cut into 64-aligned shards --------------------------------------
-    if world > 1:
+    if world > 1 and args.full:
         check(lib.vmv_fill_uniform_configs(panda._id, ctypes.c_void_p(q.data_ptr()), n, 1234, sptr),
               "vmv_fill_uniform_configs")  # the same batch on every rank; each rank validates its own shard of it
         lo, hi = shard_range(n, rank, world)
@@ -277,7 +313,7 @@ def main():
 
     # ---- shard probe (N = 1 only): the shards the strong-scaling leg gives each GPU at N = 2, 4, 8, timed on this one -----
     shard_probe = None
-    if world == 1 and not args.no_shard_probe:
+    if world == 1 and args.full and not args.no_shard_probe:
         shard_probe = {"note": "pipelined steps of vmv_validate_batch over the first n/N configurations of the batch: what "
                                "ONE rank of the N-GPU strong-scaling leg executes per step (no exchange).  ceiling = the "
                                "1-GPU step time / the shard's step time = the most N GPUs can gain on the 1M job before "
@@ -291,7 +327,7 @@ def main():
 
     # ---- informational: independent batches on two streams (N = 1 only; never `value`) ------------------------------
     two_streams = None
-    if world == 1 and not args.no_two_streams:
+    if world == 1 and args.full and not args.no_two_streams:
         # the same job with consecutive steps submitted on alternating streams (each step = one vmv_validate_batch call
         # over the whole batch, its own result buffer): the next step's kernels fill the tail of the previous step's
         side = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
@@ -319,29 +355,9 @@ def main():
                                "(and the roofline above) do not apply to this figure"}
 
     if rank == 0:
-        value = float(n) * world * args.steps / elapsed
-        achieved = ALGO_BYTES_PER_CHECK * n / (kernel_ms * 1e-3) / 1e9
-        prof, why = pmc_profile()
-        traffic, valu, traffic_step = None, None, None
-        if prof is not None:
-            ke, ks = prof["kernels"]["validate_env_kernel"], prof["kernels"]["validate_self_kernel"]
-            traffic = ke["hbm_bytes"]
-            traffic_step = {"bytes": ke["hbm_bytes"] + ks["hbm_bytes"],
-                            "x_algorithmic": (ke["hbm_bytes"] + ks["hbm_bytes"]) / (ALGO_BYTES_PER_CHECK * prof["configs"]),
-                            "note": "both kernels of one step (the self-collision kernel reads the configurations again)"}
-
-            def valu_of(k, ms):
-                cycles = k["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / N_SIMD
-                return {"wave_instructions_per_launch": k["SQ_INSTS_VALU"], "per_wave": k["SQ_INSTS_VALU"] / k["SQ_WAVES"],
-                        "issue_cycles_per_simd": cycles, "issue_time_ms_at_2.4GHz": cycles / (CLOCK_GHZ * 1e6),
-                        "frac_of_kernel_time": cycles / (CLOCK_GHZ * 1e6) / ms,
-                        "lane_utilisation": k["SQ_THREAD_CYCLES_VALU"] / (k["SQ_ACTIVE_INST_VALU"] * 64.0)}
-            valu = {"peak": "1 wave64 VALU instruction per 2 cycles per SIMD, 1,024 SIMDs at 2.4 GHz (157 TFLOP/s fp32 vector)",
-                    "validate_env_kernel": valu_of(ke, kernel_ms), "validate_self_kernel": valu_of(ks, self_ms),
-                    "source": prof.get("source", "profiles/r03_pmc.json")}
         out = {
             "metric": "config collision checks/sec (Panda, 64-prim env)",
-            "value": value,
+            "value": float(n) * world * args.steps / elapsed,
             "unit": "checks/s",
             "n_gpus": world,
             "steps": args.steps,
@@ -357,25 +373,45 @@ def main():
                        "configs_per_gpu": n, "primitives": len(spec), "env": args.env, "valid_fraction": valid_frac,
                        "exchange": "RCCL all_gather of packed validity bitmasks, overlapped with the next step" if world > 1 else "none",
                        "parallelism": f"shard{world}"},
-            "strong": {"value": float(n) * args.steps / elapsed_s, "unit": "checks/s", "ms_per_step": elapsed_s / args.steps * 1e3,
-                       "configs_per_job": n, "valid_fraction": strong_valid,
-                       "note": "ONE 1,048,576-configuration batch per step in 64-aligned contiguous shards over the GPUs, "
-                               "validity words all-gathered (at 1 GPU: the same job as the weak line)"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": lib.vmv_kernel_name(panda._id, b"validate_batch").decode(),
-                         "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": ALGO_BYTES_PER_CHECK * n,
-                         "other_kernels_ms": {"validate_self_kernel": self_ms},
-                         "traffic_per_step": traffic_step, "valu": valu, "pmc_note": why,
-                         "note": "the path does ~10^4 fp32 operations per 28 B: it is VALU-issue bound, the HBM fraction "
-                                 "is reported because the metric asks for it (DESIGN.md §5)"},
-            "kernel_checks_per_s": n / ((kernel_ms + self_ms) * 1e-3),
         }
+        if args.full:
+            achieved = ALGO_BYTES_PER_CHECK * n / (kernel_ms * 1e-3) / 1e9
+            prof, why = pmc_profile()
+            traffic, valu, traffic_step = None, None, None
+            if prof is not None:
+                ke, ks = prof["kernels"]["validate_env_kernel"], prof["kernels"]["validate_self_kernel"]
+                traffic = ke["hbm_bytes"]
+                traffic_step = {"bytes": ke["hbm_bytes"] + ks["hbm_bytes"],
+                                "x_algorithmic": (ke["hbm_bytes"] + ks["hbm_bytes"]) / (ALGO_BYTES_PER_CHECK * prof["configs"]),
+                                "note": "both kernels of one step (the self-collision kernel reads the configurations again)"}
+
+                def valu_of(k, ms):
+                    cycles = k["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / N_SIMD
+                    return {"wave_instructions_per_launch": k["SQ_INSTS_VALU"], "per_wave": k["SQ_INSTS_VALU"] / k["SQ_WAVES"],
+                            "issue_cycles_per_simd": cycles, "issue_time_ms_at_2.4GHz": cycles / (CLOCK_GHZ * 1e6),
+                            "frac_of_kernel_time": cycles / (CLOCK_GHZ * 1e6) / ms,
+                            "lane_utilisation": k["SQ_THREAD_CYCLES_VALU"] / (k["SQ_ACTIVE_INST_VALU"] * 64.0)}
+                valu = {"peak": "1 wave64 VALU instruction per 2 cycles per SIMD, 1,024 SIMDs at 2.4 GHz (157 TFLOP/s fp32 vector)",
+                        "validate_env_kernel": valu_of(ke, kernel_ms), "validate_self_kernel": valu_of(ks, self_ms),
+                        "source": prof.get("source", "profiles/r03_pmc.json")}
+            out["strong"] = {"value": float(n) * args.steps / elapsed_s, "unit": "checks/s",
+                             "ms_per_step": elapsed_s / args.steps * 1e3, "configs_per_job": n, "valid_fraction": strong_valid,
+                             "note": "ONE 1,048,576-configuration batch per step in 64-aligned contiguous shards over the GPUs, "
+                                     "validity words all-gathered (at 1 GPU: the same job as the weak line)"}
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "kernel": lib.vmv_kernel_name(panda._id, b"validate_batch").decode(),
+                               "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": ALGO_BYTES_PER_CHECK * n,
+                               "other_kernels_ms": {"validate_self_kernel": self_ms},
+                               "traffic_per_step": traffic_step, "valu": valu, "pmc_note": why,
+                               "note": "the path does ~10^4 fp32 operations per 28 B: it is VALU-issue bound, the HBM "
+                                       "fraction is reported because the metric asks for it (DESIGN.md §5)"}
+            out["kernel_checks_per_s"] = n / ((kernel_ms + self_ms) * 1e-3)
         if shard_probe is not None:
             out["shard_probe"] = shard_probe
         if two_streams is not None:
             out["two_streams"] = two_streams
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             threads = max(1, min(len(os.sched_getaffinity(0)), 16))  # the box's CPU share for one GPU
             out["cpu_baseline"] = cpu_baseline(spec, args.cpu_sample, threads)
         print(json.dumps(out), flush=True)

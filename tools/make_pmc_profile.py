@@ -26,7 +26,7 @@ for name, c in raw.items():
             k["hbm_bytes"] = c.get("FETCH_SIZE", 0.0) * 1024.0 * 2.0 + c.get("WRITE_SIZE", 0.0) * 1024.0
             kernels[key] = k
 out = {"source_hash": source_hash(), "configs": configs, "kernels": kernels,
-       "source": f"rocprofv3 --pmc passes over `python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline` ({src}); "
+       "source": f"rocprofv3 --pmc passes over `python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline` ({src}); "
                  "SQ_* are per launch (averaged over the launches of the run), *_CYCLES in quad-cycles; "
                  "hbm_bytes = FETCH_SIZE KiB x 1024 x 2 (gfx950 correction) + WRITE_SIZE KiB x 1024"}
 dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r03_pmc.json")

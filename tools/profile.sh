@@ -5,9 +5,11 @@
 #   3. tools/pmc_summary.py over the passes                           -> gpurun_out/$TAG/pmc.json
 # usage (from the repo root, under gpurun):  bash tools/profile.sh TAG [bench args...]
 # Copy the summaries you want judged from gpurun_out/$TAG into profiles/.
+# Bench arguments given here replace the default ones, --full included: pass --full to keep the bench line's
+# roofline and per-kernel times (the traces and counters are the same without it).
 set -o pipefail
 TAG=${1:-prof}; shift
-ARGS=${@:---steps 30 --warmup 5 --no-cpu-baseline --no-two-streams --no-shard-probe}
+ARGS=${@:---full --steps 30 --warmup 5 --no-cpu-baseline --no-two-streams --no-shard-probe}
 PROG=${PROFILE_PROG:-bench.py}   # e.g. PROFILE_PROG=tools/bench_configs.py bash tools/profile.sh r02_config3 config3
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
