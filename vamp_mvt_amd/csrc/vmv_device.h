@@ -1463,4 +1463,85 @@ namespace vmv
     {
         return ((lds_u32 *) scratch)[kWave + __lane_id()] != 0u;
     }
+    // ------------------------------------------------------------------------
+    // Self-collision passes shared by the waves of a workgroup (vmv_robot_tu.inc, validate_self_kernel).  A workgroup
+    // owns a share of up to kSelfShareWords consecutive validity words; its waves claim 64-configuration passes over the
+    // configurations still valid in them from an LDS counter.
+
+    // position of the j-th set bit of v (j < popcount(v))
+    __device__ __forceinline__ uint32_t nth_set_bit(const uint64_t v, uint32_t j)
+    {
+        uint32_t w = (uint32_t) v, base = 0u;
+        const uint32_t c32 = (uint32_t) __popc(w);
+        if (j >= c32) j -= c32, w = (uint32_t) (v >> 32), base = 32u;
+#pragma unroll
+        for (int half = 16; half >= 1; half >>= 1)
+        {
+            const uint32_t lowmask = (1u << half) - 1u;
+            const uint32_t c = (uint32_t) __popc(w & lowmask);
+            const bool up = j >= c;
+            j = up ? j - c : j;
+            w = up ? (w >> half) : (w & lowmask);
+            base += up ? (uint32_t) half : 0u;
+        }
+        return base;
+    }
+
+    constexpr uint32_t kSelfShareWords = 32;  // words of the largest share: 4 waves x 8 words
+    struct SelfShare                          // (one per workgroup, in LDS)
+    {
+        unsigned long long read[kSelfShareWords];    // the share's words as read: what the passes enumerate
+        unsigned long long result[kSelfShareWords];  // ... and as edited (one LDS atomicAnd per collision)
+        uint32_t before[kSelfShareWords + 1];        // popcount prefix of `read`
+        uint32_t next_pass;                          // passes claimed so far
+    };
+
+    // One wave (lane = its lane number): reads words [w0, w0 + nw) of `bits`, clears the bits at or beyond n in the batch's
+    // last word `last` (tail = n % 64), stores the words as read and as to be edited, builds their prefix and resets the
+    // pass counter.  The caller makes the workgroup wait for it.
+    __device__ __forceinline__ void self_share_load(SelfShare &S, const uint64_t *__restrict__ bits, const uint32_t w0,
+                                                    const uint32_t nw, const uint32_t last, const uint32_t tail,
+                                                    const uint32_t lane)
+    {
+        uint64_t mine = (lane < nw) ? bits[w0 + lane] : 0ull;
+        // vmv_validate_batch_self is an entry point of its own: a caller's words may have bits set at or beyond n (all-ones
+        // words); they are cleared here, so no configuration past the end of the batch is ever read
+        if (w0 + lane == last && tail != 0u) mine = (mine << (64u - tail)) >> (64u - tail);
+        uint32_t incl = (uint32_t) __popcll(mine);
+#pragma unroll
+        for (uint32_t d = 1; d < kSelfShareWords; d <<= 1)
+        {
+            const uint32_t up = (uint32_t) __shfl_up((int) incl, d);
+            incl += (lane >= d) ? up : 0u;
+        }
+        if (lane < kSelfShareWords)
+        {
+            S.read[lane] = mine;
+            S.result[lane] = mine;
+            S.before[lane + 1u] = incl;
+        }
+        if (lane == 0u) S.before[0] = 0u, S.next_pass = 0u;
+    }
+
+    // The calling wave's next pass: the index, among the share's valid configurations, of its first lane (all lanes alike;
+    // at or beyond the share's total when the share is used up).  One LDS atomic per wave and pass, nothing waits.
+    __device__ __forceinline__ uint32_t self_share_claim(SelfShare &S, const uint32_t lane)
+    {
+        uint32_t claim = 0u;
+        if (lane == 0u) claim = atomicAdd(&S.next_pass, 1u);
+        return (uint32_t) __builtin_amdgcn_readfirstlane((int) claim) * (uint32_t) kWave;
+    }
+
+    // word x 64 + bit of the share's j-th valid configuration; ~0 for j >= total (an idle lane).  The word is the last
+    // k < nw with before[k] <= j (binary search over the prefix).  One register: all that has to stay live across the FK.
+    __device__ __forceinline__ uint32_t self_share_locate(const SelfShare &S, const uint32_t nw, const uint32_t j,
+                                                          const uint32_t total)
+    {
+        if (j >= total) return ~0u;
+        uint32_t k = 0u;
+#pragma unroll
+        for (uint32_t step = kSelfShareWords / 2u; step >= 1u; step >>= 1)
+            k = (k + step < nw && S.before[k + step] <= j) ? k + step : k;
+        return k * (uint32_t) kWave + nth_set_bit(S.read[k], j - S.before[k]);
+    }
 }  // namespace vmv

@@ -6,6 +6,10 @@
 #include "vmv_common.h"
 
 #include <cstdlib>
+#ifdef VMV_SELF_STAMP
+#include <cstdio>
+#include <vector>
+#endif
 
 // workgroups per CU the edge kernels are compiled for (tuning knobs; tools/build_variant.py)
 #ifndef VMV_MOTION_ENV_BLOCKS
@@ -308,36 +312,95 @@ namespace VMV_ROBOT_NS
         o[15] = 1.0f;
     }
 
-    // position of the j-th set bit of v (j < popcount(v))
-    __device__ __forceinline__ uint32_t nth_set_bit(const uint64_t v, uint32_t j)
+#ifdef VMV_SELF_STAMP
+    // Measurement build only (tools/build_variant.py NAME -DVMV_SELF_STAMP; never in the default library): every wave of
+    // the self-collision kernels writes one record of 4 words to self_stamp[global wave]: s_memrealtime (100 MHz) at
+    // entry, at the end of its last pass and at exit; passes | XCC_ID << 16 | HW_ID << 32 (tools/self_stamp_summary.py).
+    __device__ uint64_t *self_stamp;
+    __device__ __forceinline__ uint64_t stamp_now() { return __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void stamp_write(const uint64_t t0, const uint64_t t1, const uint32_t passes)
     {
-        uint32_t w = (uint32_t) v, base = 0u;
-        const uint32_t c32 = (uint32_t) __popc(w);
-        if (j >= c32) j -= c32, w = (uint32_t) (v >> 32), base = 32u;
-#pragma unroll
-        for (int half = 16; half >= 1; half >>= 1)
+        const uint64_t t2 = stamp_now();
+        uint32_t hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        uint64_t *r = self_stamp + 4 * ((size_t) blockIdx.x * kWavesPerBlock + threadIdx.x / kWave);
+        const uint32_t lane = __lane_id();
+        if (lane < 4u)
+            r[lane] = lane == 0u ? t0 : lane == 1u ? t1 : lane == 2u ? t2 :
+                      ((uint64_t) (passes & 0xffffu) | (uint64_t) (xcc & 0xfu) << 16 | (uint64_t) hw << 32);
+    }
+#define VMV_STAMP_START const uint64_t stamp_t0_ = stamp_now(); uint64_t stamp_t1_ = 0; uint32_t stamp_passes_ = 0
+#define VMV_STAMP_PASS ++stamp_passes_
+#define VMV_STAMP_WORK_DONE stamp_t1_ = stamp_now()
+#define VMV_STAMP_END stamp_write(stamp_t0_, stamp_t1_, stamp_passes_)
+#else
+#define VMV_STAMP_START
+#define VMV_STAMP_PASS
+#define VMV_STAMP_WORK_DONE
+#define VMV_STAMP_END
+#endif
+
+    // The self-collision half ANDs into the validity words the environment kernel wrote.  A workgroup owns
+    // kWavesPerBlock x `group` (group 1..8) consecutive words and its waves work through the configurations that are
+    // still valid in them, 64 per pass: with 62.5 % of a 16-word share valid that is 10 passes of FK + self-collision
+    // groups instead of 16 (12 with 4-word shares per wave) — what the environment half already rejected costs nothing.  Passes are
+    // claimed from an LDS counter, so a wave whose passes ran long does not hold up the workgroup's other waves, and only
+    // the last pass of the share runs partly empty (per-wave shares of 4 words left every wave a part-empty third pass,
+    // and the kernel lasted 1.6 mean wave lives: profiles/r04_self_stamp_summary.txt).  Nothing is exchanged but the
+    // words themselves (no list in memory, no device-scope atomics: the words are edited in LDS and stored once).  The
+    // launcher picks `group` so that the grid is one round of resident workgroups.
+    static_assert(kSelfShareWords == (uint32_t) kWavesPerBlock * 8u, "a share holds group <= 8 words per wave");
+    __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_kernel(const float *__restrict__ q, const uint32_t n,
+                                                                    uint64_t *__restrict__ bits, const uint32_t group)
+    {
+        VMV_STAMP_START;
+        __shared__ __align__(16) float stage[kSelfRadiiFloats + kWavesPerBlock * self_slab_floats()];
+        __shared__ SelfShare S;
+        stage_radii(stage);
+        const uint32_t wave = uniform(threadIdx.x / kWave);
+        lds_ptr wave_slab = (lds_ptr) stage + kSelfRadiiFloats + wave * self_slab_floats();
+        const uint32_t words = (n + (uint32_t) kWave - 1u) / (uint32_t) kWave;
+        const uint32_t share = group * (uint32_t) kWavesPerBlock;  // <= kSelfShareWords (the launcher clamps group)
+        const uint32_t tail = n % (uint32_t) kWave;
+        for (uint32_t w0 = blockIdx.x * share; w0 < words; w0 += gridDim.x * share)  // workgroup-uniform
         {
-            const uint32_t lowmask = (1u << half) - 1u;
-            const uint32_t c = (uint32_t) __popc(w & lowmask);
-            const bool up = j >= c;
-            j = up ? j - c : j;
-            w = up ? (w >> half) : (w & lowmask);
-            base += up ? (uint32_t) half : 0u;
+            const uint32_t nw = (words - w0 < share) ? words - w0 : share;
+            // (lane numbers re-derived opaquely: the table addresses built from threadIdx were hoisted out of the loop and
+            // spilled)
+            if (wave == 0u) self_share_load(S, bits, w0, nw, words - 1u, tail, opaque_lane_id());
+            __syncthreads();
+            const uint32_t total = uniform(S.before[nw]);
+            for (;;)
+            {
+                const uint32_t pass = self_share_claim(S, opaque_lane_id());
+                if (pass >= total) break;  // wave-uniform: the share is used up
+                VMV_STAMP_PASS;
+                const uint32_t lane = opaque_lane_id();
+                const uint32_t at = self_share_locate(S, nw, pass + lane, total);
+                const uint32_t idx = w0 * (uint32_t) kWave + (at != ~0u ? at : 0u);  // (a valid bit always lies below n <= 2^31)
+                float cfg[R::kDim];
+#pragma unroll
+                for (int d = 0; d < R::kDim; ++d) cfg[d] = q[(size_t) idx * R::kDim + d];
+                const bool bad = R::template fkcc_self<1>(cfg, wave_slab + lane, (lds_cptr) stage, at == ~0u);
+                if (bad && at != ~0u) atomicAnd(&S.result[at / (uint32_t) kWave], ~(1ull << (at % (uint32_t) kWave)));  // LDS atomic
+            }
+            VMV_STAMP_WORK_DONE;
+            __syncthreads();
+            if (wave == 0u && opaque_lane_id() < nw) bits[w0 + opaque_lane_id()] = S.result[opaque_lane_id()];
+            __syncthreads();  // (the next share rewrites the tables)
         }
-        return base;
+        VMV_STAMP_END;
     }
 
-    // The self-collision half ANDs into the validity words the environment kernel wrote.  A wave owns `group` (1..8)
-    // consecutive words and works through the configurations that are still valid in them, 64 per pass: with 62.5 % of a
-    // 4-word group valid that is 3 passes of FK + self-collision groups instead of 4, with a third valid 2 instead of
-    // 4 — the share the environment half already rejected costs nothing, whatever it is, and nothing is exchanged but the
-    // words themselves (no list in memory, no atomics: the words of a group are edited in LDS and stored once).  The
-    // launcher picks `group` so that the grid is one round of resident waves.
-    __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_kernel(const float *__restrict__ q, const uint32_t n,
+    // The self-collision half as before the shared passes (VMV_SELF_BALANCE=0, A/B only): a wave owns `group` words of
+    // its own and works through their valid configurations alone.
+    __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_wave_kernel(const float *__restrict__ q, const uint32_t n,
                                                                     uint64_t *__restrict__ bits, const uint32_t group)
     {
         // (32-bit counts, a scalar wave index and a lane number re-derived per group: as in validate_env_kernel, what is
         // invariant across the loop would otherwise be hoisted into VGPRs and spilled — 60 B of scratch per lane before)
+        VMV_STAMP_START;
         __shared__ __align__(16) float stage[kSelfRadiiFloats + kWavesPerBlock * self_slab_floats()];
         __shared__ unsigned long long result[kWavesPerBlock][8];
         stage_radii(stage);
@@ -369,11 +432,14 @@ namespace VMV_ROBOT_NS
                 before[k + 1] = before[k] + (uint32_t) __popcll(W[k]);
             }
             const uint32_t total = before[8];
-            if (total == 0u) continue;  // wave-uniform: nothing left to check in this group
+            // wave-uniform: nothing left to check in this group (the batch's last group goes on all the same: it stores the
+            // tail bits it cleared)
+            if (total == 0u && (w0 + nw != words || tail == 0u)) continue;
             if (lane < 8u) result[wave][lane] = mine;
             wave_lds_sync();
             for (uint32_t pass = 0; pass < total; pass += kWave)
             {
+                VMV_STAMP_PASS;
                 const uint32_t j = pass + lane;
                 const bool todo = j < total;
                 uint32_t k = 0u;
@@ -399,6 +465,8 @@ namespace VMV_ROBOT_NS
             if (opaque_lane_id() < nw) bits[w0 + opaque_lane_id()] = result[wave][opaque_lane_id()];
             wave_lds_sync();
         }
+        VMV_STAMP_WORK_DONE;
+        VMV_STAMP_END;
     }
 
     // hsum + exact sqrt of a configuration-sized vector (vector/avx.hh:441-452, interface.hh:397-410)
@@ -934,31 +1002,65 @@ namespace VMV_ROBOT_NS
             }
             if (stages & 2)
             {
+                // VMV_SELF_BALANCE=0 (A/B only): the per-wave kernel; read per call (the parity tests switch it)
+                const char *balance = getenv("VMV_SELF_BALANCE");
+                const bool shared = !(balance && balance[0] == '0');
+                auto kernel = shared ? validate_self_kernel : validate_self_wave_kernel;
+                // words per wave: one round of resident workgroups (the hardware's count: 256 CUs x kSelfBlocks workgroups
+                // x 4 waves on the MI355X) covers the batch, at most 8 (VMV_SELF_GROUP overrides: measurement aid)
+                const size_t words = (n + kWave - 1) / kWave;
+                auto resident_waves = [](const void *k)
                 {
-                    // words per wave: one round of resident waves (256 CUs x kSelfBlocks workgroups x 4 waves) covers the
-                    // batch, at most 8 (VMV_SELF_GROUP overrides: measurement aid)
-                    const size_t words = (n + kWave - 1) / kWave;
-                    static const size_t resident = []
+                    int per_cu = 0, dev = 0, cus = 256;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0) != hipSuccess || per_cu < 1)
+                        per_cu = R::kSelfBlocks;
+                    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+                        cus < 1)
+                        cus = 256;
+                    return (size_t) cus * (size_t) per_cu * kWavesPerBlock;
+                };
+                static const size_t resident_shared = resident_waves((const void *) validate_self_kernel);
+                static const size_t resident_wave = resident_waves((const void *) validate_self_wave_kernel);
+                const size_t resident = shared ? resident_shared : resident_wave;
+                uint32_t group = (uint32_t) ((words + resident - 1) / resident);
+                if (const char *e = getenv("VMV_SELF_GROUP")) group = (uint32_t) strtoul(e, nullptr, 10);
+                group = group < 1u ? 1u : (group > 8u ? 8u : group);
+                constexpr size_t kSlice = size_t{1} << 31;  // 32-bit counts inside the kernel; slices own whole words
+                for (size_t lo = 0; lo < n; lo += kSlice)
+                {
+                    const uint32_t m = (uint32_t) (n - lo < kSlice ? n - lo : kSlice);
+                    const size_t waves = (((size_t) m + kWave - 1) / kWave + group - 1) / group;
+                    const size_t blocks = grid_for(waves * kWave, kBlock);
+#ifdef VMV_SELF_STAMP
+                    static uint64_t *d_stamp = nullptr;
+                    static size_t stamp_cap = 0;
+                    if (blocks * kWavesPerBlock > stamp_cap)
                     {
-                        int per_cu = 0, dev = 0, cus = 256;
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, validate_self_kernel, kBlock, 0) != hipSuccess || per_cu < 1)
-                            per_cu = R::kSelfBlocks;
-                        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-                            cus < 1)
-                            cus = 256;
-                        return (size_t) cus * (size_t) per_cu * kWavesPerBlock;
-                    }();
-                    uint32_t group = (uint32_t) ((words + resident - 1) / resident);
-                    if (const char *e = getenv("VMV_SELF_GROUP")) group = (uint32_t) strtoul(e, nullptr, 10);
-                    group = group < 1u ? 1u : (group > 8u ? 8u : group);
-                    constexpr size_t kSlice = size_t{1} << 31;  // 32-bit counts inside the kernel; slices own whole words
-                    for (size_t lo = 0; lo < n; lo += kSlice)
-                    {
-                        const uint32_t m = (uint32_t) (n - lo < kSlice ? n - lo : kSlice);
-                        const size_t waves = (((size_t) m + kWave - 1) / kWave + group - 1) / group;
-                        hipLaunchKernelGGL(validate_self_kernel, dim3(grid_for(waves * kWave, kBlock)), dim3(kBlock), 0, stream,
-                                           d_q + lo * R::kDim, m, d_bits + lo / kWave, group);
+                        if (d_stamp) VMV_HIP_TU(hipFree(d_stamp));
+                        stamp_cap = blocks * kWavesPerBlock;
+                        VMV_HIP_TU(hipMalloc(&d_stamp, stamp_cap * 4 * sizeof(uint64_t)));
+                        VMV_HIP_TU(hipMemcpyToSymbol(HIP_SYMBOL(self_stamp), &d_stamp, sizeof(d_stamp)));
                     }
+                    VMV_HIP_TU(hipMemsetAsync(d_stamp, 0, blocks * kWavesPerBlock * 4 * sizeof(uint64_t), stream));
+#endif
+                    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, d_q + lo * R::kDim, m,
+                                       d_bits + lo / kWave, group);
+#ifdef VMV_SELF_STAMP
+                    // header: n, group, workgroups, shared (1) or per-wave (0); then 4 words per wave.  Overwritten per launch.
+                    if (const char *path = getenv("VMV_SELF_STAMP_OUT"))
+                    {
+                        std::vector<uint64_t> rec(4 + blocks * kWavesPerBlock * 4);
+                        rec[0] = m, rec[1] = group, rec[2] = blocks, rec[3] = shared ? 1u : 0u;
+                        VMV_HIP_TU(hipMemcpyAsync(rec.data() + 4, d_stamp, blocks * kWavesPerBlock * 4 * sizeof(uint64_t),
+                                                  hipMemcpyDeviceToHost, stream));
+                        VMV_HIP_TU(hipStreamSynchronize(stream));
+                        if (FILE *f = fopen(path, "wb"))
+                        {
+                            fwrite(rec.data(), sizeof(uint64_t), rec.size(), f);
+                            fclose(f);
+                        }
+                    }
+#endif
                 }
                 VMV_HIP_TU(hipGetLastError());
             }
