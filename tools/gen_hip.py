@@ -519,6 +519,8 @@ def emit_robot(m):
     L.append(f"    constexpr int kResolution = {m['resolution']};")
     L.append(f"    constexpr int kSlabSpheres = {slab_spheres};  // environment kernels: one chunk of fine spheres")
     L.append(f"    constexpr int kSelfSlabSpheres = {self_slab_spheres};  // self-collision kernels: one chunk of B spheres")
+    L.append("    constexpr int kPackSlots = kSlabSpheres * vmv::kWave;  // packed fine items of one link (vmv::env_fine_packed)")
+    L.append("    static_assert(3 * kPackSlots <= kSlabSpheres * 3 * vmv::kRow, \"the item buffer fits the slab\");")
     L.append(f"    constexpr int kNRadii = {len(radii_tab)};")
     L.append(f"    __constant__ float kRadii[{len(radii_tab)}] = {{" + ", ".join(flit(v) for v in radii_tab) + "};")
     L.append("    struct Tab")
@@ -532,11 +534,13 @@ def emit_robot(m):
     static = set(static_links(m))
     reach = link_samples(m)
 
-    def emit_env_link(em, ln, lazy=LAZY_FINE_FK, no_skip=False, pair_with=None, pre=None, order=None):
+    def emit_env_link(em, ln, lazy=LAZY_FINE_FK, no_skip=False, pair_with=None, pre=None, order=None, packed=False):
         """one link of the environment half: FK ops, slab staging, gate, fine chunks (appends to em.lines).
         lazy: the FK ops only this link's fine spheres need, and the staging of its first chunk, are emitted inside
         `if (wave_any(gate))` - links whose bounding sphere never reaches an obstacle (the base links in a shell-shaped
-        scene) then cost their chain ops and one cell lookup, nothing else."""
+        scene) then cost their chain ops and one cell lookup, nothing else.
+        packed: under #if VMV_PACKED_FINE the passing lanes' fine spheres of all chunks are packed into the slab as items
+        and run in full rounds (vmv::env_fine_flush / env_fine_packed); #else the per-chunk env_fine calls."""
         order = links if order is None else order  # the groups of this walk, in chain order
         g = env_by_link[ln]
         fine = g["fine"]
@@ -573,6 +577,27 @@ def emit_robot(m):
             for k in range(3):
                 em.lines.append(f"{indent}slab[{3 * slot + k} * vmv::kRow] = {em.coord(s, k)};")
 
+        def emit_packed_fine(em, ln, chunks, private):
+            # (vmv_device.h, "packed fine phase": lane of rank j writes fine sphere s of the link to slot s * k + j - done)
+            I = "                "
+            em.lines.append(f"{I}const int rank = vmv::lane_rank(gate);  // this lane's position in the gate's lane list")
+            em.lines.append(f"{I}int pk_fill = 0, pk_done = 0;  // items staged in the slab / already run, wave-uniform")
+            for ci, ch in enumerate(chunks):
+                if ci > 0:
+                    em.lines.append(f"{I}vmv::env_fine_flush<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_done, "
+                                    f"n_gate, {len(ch)} * n_gate, {radii_off[ln] + 1});")
+                em.emit_ops(private & em.closure(ch), indent=I)
+                em.lines.append(f"{I}if (gate)")
+                em.lines.append(f"{I}{{")
+                for si, s in enumerate(ch):
+                    slot = "pk_fill + rank" + (f" + {si} * n_gate" if si else "")
+                    em.lines.append(f"{I}    vmv::pack_stage<kPackSlots>(pk_items, {slot}, "
+                                    + ", ".join(em.coord(s, k) for k in range(3)) + ");")
+                em.lines.append(f"{I}}}")
+                em.lines.append(f"{I}pk_fill += {len(ch)} * n_gate;")
+            em.lines.append(f"{I}vmv::env_fine_packed<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_fill, pk_done, "
+                            f"n_gate, {radii_off[ln] + 1});")
+
         # (the bounding sphere goes to the gate in registers: no slab row, no LDS round trip between caller and gate)
         bc = ", ".join(em.coord(g["bound"], k) for k in range(3))
         if not lazy:
@@ -600,6 +625,14 @@ def emit_robot(m):
         em.lines.append("            if (VMV_ABLATE_ENV >= 1) bad |= gate;  // measurement aid: no fine phase (wrong answers)")
         em.lines.append("            else if (n_gate != 0)")
         em.lines.append("            {")
+        packed = packed and lazy  # (the packed form stages after the gate: lanes write at their rank among passing lanes)
+        done_before = list(em.done)
+        if packed:
+            # both forms emit the same private FK ops inside this block, so the emitter leaves either in the same state
+            em.lines.append("#if VMV_PACKED_FINE")
+            emit_packed_fine(em, ln, chunks, private)
+            em.lines.append("#else")
+            em.done[:] = done_before
         if lazy:
             # (chunk by chunk: the FK of a later chunk's spheres is emitted right before that chunk is staged, so the
             # coordinates of a 27-sphere group are never all live across the fine calls)
@@ -615,6 +648,8 @@ def emit_robot(m):
                     stage(si, s, "                ")
             em.lines.append(f"                vmv::env_fine<G, Tab, V>(E, slab, scratch, {len(ch)}, {radii_off[ln] + 1 + done}, 0, n_gate);")
             done += len(ch)
+        if packed:
+            em.lines.append("#endif")
         em.lines.append("                bad |= gate && vmv::group_any<G>(vmv::env_flag(scratch));")
         em.lines.append("            }")
         em.lines.append("        }")
@@ -635,13 +670,16 @@ def emit_robot(m):
         L.append("        const vmv::lds_ptr scratch = slab - __lane_id() + kSlabSpheres * 3 * vmv::kRow;")
         if not paired:
             L.append("        const unsigned long long skip_links = E.dev->link_skip;  // reach certificates (vmv_api.hip), wave-uniform")
+            L.append("#if VMV_PACKED_FINE")
+            L.append("        const vmv::lds_ptr pk_items = slab - __lane_id();  // the slab as an SoA item buffer of kPackSlots slots")
+            L.append("#endif")
         em = Emitter(m)
         skipped = os.environ.get("VMV_ABLATE_SKIP_LINKS", "").split(",")
         movable = [ln for ln in links if ln not in static and ln not in skipped]
         if not paired:
             # primitive-only variants: rigidly connected links share one gate (merged_groups)
             for ln in prim_order:
-                emit_env_link(em, ln, order=prim_order)
+                emit_env_link(em, ln, order=prim_order, packed=True)
         for ln in (links if paired else []):
             if ln not in movable:
                 emit_env_link(em, ln)

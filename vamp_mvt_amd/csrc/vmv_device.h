@@ -1431,6 +1431,94 @@ namespace vmv
         wave_lds_sync();
     }
 
+    // ---- packed fine phase (generated fkcc_env of the primitive-only walks; VMV_PACKED_FINE=0 restores env_fine) ----
+    // One link's fine items, packed across its slab chunks.  The wave's slab region is viewed as an SoA item buffer of
+    // C = kSlabSpheres * 64 slots (x at [0, C), y at [C, 2C), z at [2C, 3C): 3C <= kSlabSpheres * 3 * kRow floats, so the
+    // LDS per wave stays what it was).  With k lanes through the gate, the lane of rank j (its position in the gate's
+    // lane list) writes fine sphere s of the link — s counted from the link's first fine sphere, across chunks — as item
+    // i = s * k + j, at slot i - done, where `done` counts the link's items already run.  Only passing lanes write, so the
+    // buffer holds live items only; a chunk's FK is still emitted right before its staging (VMV_LAZY_FINE_FK).
+    // The generated code runs the rounds (env_fine_flush) only when the next chunk would not fit, and once at the end of
+    // the link; where env_fine paid a call, a sync and a candidate walk per chunk, a link now pays them per flush.
+    // Rakes (G = 8): k is a multiple of 8 (whole rakes pass), and `done` and every round's first slot are multiples of 8
+    // (a flush runs whole 64-item rounds or everything staged, k * s items), so the 8 lanes of a round that hold one
+    // rake's items for one sphere stay adjacent and 8-aligned for group_max.
+#ifndef VMV_PACKED_FINE
+#define VMV_PACKED_FINE 1
+#endif
+    __device__ __forceinline__ int lane_rank(const bool pred)
+    {
+        const uint64_t mask = __ballot(pred);
+        return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
+    }
+    template <int C>
+    __device__ __forceinline__ void pack_stage(lds_ptr items, const int slot, const float x, const float y, const float z)
+    {
+        items[slot] = x;
+        items[C + slot] = y;
+        items[2 * C + slot] = z;
+    }
+
+    // Runs the first `run_` of the `fill_` staged items (run_ is a multiple of 64, or all of them), then moves the rest
+    // (fewer than 64) to the front of the buffer.  items = the wave's slab base; done_ = link items run before slot 0.
+    template <int G, typename Tab, int V, int C>
+    __device__ __noinline__ void
+    env_fine_packed(const EnvView E_, lds_ptr items_, lds_ptr scratch_, const int fill_, const int run_, const int done_,
+                    const int k_, const int radii_offset_)
+    {
+        static_assert(C % kWave == 0 && kWave % G == 0, "rounds cover whole rakes: 64-slot rounds, 8-aligned rakes");
+        const uint32_t lane = __lane_id();
+        const EnvView E{uniform(E_.dev), uniform(E_.lds), uniform(E_.capt0_planes_in_lds), uniform(E_.radii)};
+        lds_u32 *list = (lds_u32 *) uniform((lds_cptr) scratch_);
+        lds_u32 *flags = list + kWave;
+        const lds_ptr items = (lds_ptr) uniform((lds_cptr) items_);
+        const int fill = uniform(fill_), run = uniform(run_), done = uniform(done_), k = uniform(k_);
+        const int radii_offset = uniform(radii_offset_);
+        const bool masked = E.dev->masked_fine != 0u;
+        const float inv_k = 1.0f / (float) k;
+        for (int base = 0; base < run; base += kWave)
+        {
+            const int t = base + (int) lane;
+            const bool act = t < run;
+            const int slot = act ? t : 0;
+            const int i = done + slot;
+            // s = i / k (exact: i < 28 * 64 < 2^24 converts exactly, and (i + 0.5) / k lies at least 0.5 / 64 from an
+            // integer while the two roundings move it by under 28 * 2^-23, far less)
+            const int s = (int) (((float) i + 0.5f) * inv_k);
+            const int j = i - s * k;
+            const uint32_t src = list[j];
+            const float x = items[slot], y = items[C + slot], z = items[2 * C + slot];
+            bool hit;
+            if (masked)
+                hit = env_hit<G, 2, V>(E, x, y, z, E.radii[radii_offset + s], act, list + 2 * kWave + 4 + src);
+            else
+                hit = env_hit<G, 0, V>(E, x, y, z, E.radii[radii_offset + s], act, nullptr);
+            if (hit) flags[src] = 1u;
+        }
+        // (source [run, fill) and target [0, fill - run) do not overlap: run >= 64 > fill - run, or run == fill)
+        const int rest = fill - run;
+        if ((int) lane < rest)
+        {
+            const float x = items[run + lane], y = items[C + run + lane], z = items[2 * C + run + lane];
+            pack_stage<C>(items, (int) lane, x, y, z);
+        }
+        wave_lds_sync();
+    }
+
+    // Before staging `need` more items: run the whole rounds staged so far if they would not fit (and everything if the
+    // carried remainder still would not), keeping fill + need <= C.  fill, done and need are wave-uniform.
+    template <int G, typename Tab, int V, int C>
+    __device__ __forceinline__ void env_fine_flush(const EnvView &E, lds_ptr items, lds_ptr scratch, int &fill, int &done,
+                                                   const int k, const int need, const int radii_offset)
+    {
+        if (fill + need <= C) return;
+        int run = fill & ~(kWave - 1);
+        if (fill - run + need > C) run = fill;
+        env_fine_packed<G, Tab, V, C>(E, items, scratch, fill, run, done, k, radii_offset);
+        fill -= run;
+        done += run;
+    }
+
     // Re-dealing support for the self-collision groups: list the lanes whose predicate holds; returns how many.
     __device__ __forceinline__ int deal_list(lds_u32 *list, const bool pred)
     {
