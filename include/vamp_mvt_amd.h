@@ -154,6 +154,21 @@ int vmv_validate_batch(int robot, const vmv_env *env, const float *d_q, size_t n
  * into words already written.  vmv_validate_batch == _env then _self on the same stream. */
 int vmv_validate_batch_env(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream);
 int vmv_validate_batch_self(int robot, const float *d_q, size_t n, uint64_t *d_bits, void *stream);
+/* Many environments in one call: configurations [offsets[k], offsets[k+1]) against envs[k]; offsets: host array of
+ * n_envs + 1, offsets[0] == 0, non-decreasing, offsets[n_envs] == n.  Bit i of d_bits = configuration i is collision
+ * free (flat layout: the same words as concatenating one vmv_validate_batch per environment, and the same bits).  Empty
+ * ranges and repeated handles are allowed.  Every environment must be finalized on the current device.
+ * Limits: n < 2^31 and n_envs < 2^31 (the kernels count in 32 bits), else VMV_ERR_INVALID_ARGUMENT.
+ * Every argument is checked before anything is launched: a call that fails a check launches nothing and writes nothing.
+ * The checks that need no device (robot, NULL pointers and handles, offsets, limits, unfinalized environments) come
+ * first.  The device entry point does not synchronise with the host: its tables go through pinned host staging and
+ * device scratch kept per (device, stream) (freed by vmv_release_staging) and are copied on `stream`.  The launches:
+ * one environment kernel per variant class present (each segment runs the variant its environment runs alone), the
+ * self-collision kernel once over all n, the attachment kernel over the segments with an attachment. */
+int vmv_validate_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                             const float *d_q, uint64_t *d_bits, void *stream);
+int vmv_validate_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                  const float *q, uint64_t *bits);
 /* validate_motion<Robot, 8, Robot::resolution>(start, goal, env) — planning/validate.hh:24-77, the call every
  * planner makes per edge (rrtc.hh:136-140, prm.hh:59, fcit.hh:238 ...).  One bit per edge.
  * A sequence of kernels on `stream` (rake 0 of every edge, a scan, the remaining rakes of the surviving edges), with 8
@@ -199,8 +214,8 @@ int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *s
                                    uint64_t *bits);
 /* The host-buffer variants stage through a per-thread device arena that is reused between calls (requests above 64 MiB
  * are not kept), and vmv_validate_motion_batch keeps 8 bytes of device scratch per edge per (device, stream) for its task
- * lists.  Frees the calling thread's arena and every stream's scratch (waits for edge batches in flight); optional — none
- * of this memory is touched at thread or process exit. */
+ * lists, vmv_validate_batch_multi its tables.  Frees the calling thread's arena and every stream's scratch and tables
+ * (waits for the batches in flight); optional — none of this memory is touched at thread or process exit. */
 int vmv_release_staging(void);
 
 /* ---- multi-GPU: one process per GPU, every unit independent given the read-only environment ------- */

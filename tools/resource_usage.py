@@ -21,7 +21,7 @@ def report(robot):
                        capture_output=True, text=True)
     rows, cur = [], None
     for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|"
+        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|"
                       r"ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
@@ -39,6 +39,6 @@ if __name__ == "__main__":
         for robot, rows, rc in ex.map(report, robots):
             print(f"== {robot} (hipcc rc {rc})")
             for k in rows:
-                print(f"  {k['name']:34s} vgpr {k.get('VGPRs'):>4s} agpr {k.get('AGPRs'):>3s} sspill {k.get('SGPRs Spill'):>4s} "
+                print(f"  {k['name']:34s} sgpr {k.get('TotalSGPRs'):>4s} vgpr {k.get('VGPRs'):>4s} agpr {k.get('AGPRs'):>3s} sspill {k.get('SGPRs Spill'):>4s} "
                       f"vspill {k.get('VGPRs Spill'):>3s} scratch {k.get('ScratchSize [bytes/lane]'):>4s} "
                       f"lds {k.get('LDS Size [bytes/block]'):>6s} occ {k.get('Occupancy [waves/SIMD]')}")

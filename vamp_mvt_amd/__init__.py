@@ -608,6 +608,51 @@ class _Robot(types.ModuleType):
                                           bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_host")
         return unpack_bits(bits, n)
 
+    def validate_batch_multi(self, configurations, environments, counts):
+        """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty
+        environment), in one call.  The same answers as one validate_batch per environment, concatenated.  numpy in ->
+        numpy out; torch CUDA tensor in -> torch.bool CUDA tensor out, launched on torch's current stream."""
+        environments = list(environments)
+        counts = np.asarray(counts)
+        if counts.ndim != 1 or len(counts) != len(environments):
+            raise ValueError(f"expected one count per environment, got {counts.shape} counts for {len(environments)}")
+        if counts.size and (not np.issubdtype(counts.dtype, np.integer) or (counts < 0).any()):
+            raise ValueError("counts must be non-negative integers")
+        for e in environments:
+            if e is not None and not isinstance(e, Environment):
+                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
+        torch_in = _is_torch_cuda(configurations)
+        if torch_in:
+            shape = tuple(configurations.shape)
+        else:
+            q = _f32(configurations)
+            shape = q.shape
+        if len(shape) != 2 or shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] configurations")
+        n = shape[0]
+        if int(offsets[-1]) != n:
+            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
+        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
+        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        offs = offsets.ctypes.data_as(_lib.c_size_p)
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(configurations.device):
+                qt = configurations.contiguous().float()
+                bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=qt.device)
+                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
+                check(lib.vmv_validate_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(qt.data_ptr()),
+                                                   ctypes.c_void_p(bits.data_ptr()), stream), "vmv_validate_batch_multi")
+                shifts = torch.arange(64, device=qt.device, dtype=torch.int64)
+                return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+        bits = np.zeros((n + 63) // 64, np.uint64)
+        check(lib.vmv_validate_batch_multi_host(self._id, handles, offs, len(envs), _fp(q),
+                                                bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_multi_host")
+        return unpack_bits(bits, n)
+
     def validate_motion_batch(self, starts, goals, environment: Environment | None = None):
         if _is_torch_cuda(starts):
             return self._torch_bits(starts, goals, environment)

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -87,6 +88,86 @@ namespace
 namespace vmv
 {
     int hip_status(hipError_t e, const char *what) { return hip_fail(e, what); }
+
+    // ---- per-(device, stream) tables of vmv_validate_batch_multi (vmv_common.h: MultiTableLease) ----
+    namespace
+    {
+        struct MultiHostSlot
+        {
+            void *p = nullptr;
+            size_t bytes = 0;
+            hipEvent_t copied = nullptr;  // recorded after the slot's last copy
+        };
+        struct MultiTables
+        {
+            void *dev = nullptr;
+            size_t bytes = 0;
+            std::vector<MultiHostSlot> host;
+        };
+        std::mutex g_multi_mutex;
+        std::map<std::pair<int, hipStream_t>, MultiTables> g_multi;  // never freed at exit (see vmv_release_staging)
+    }  // namespace
+
+    MultiTableLease::MultiTableLease() : lock_(g_multi_mutex, std::defer_lock) {}
+
+    int MultiTableLease::acquire(hipStream_t stream, size_t bytes)
+    {
+        int dev = -1;
+        VMV_HIP(hipGetDevice(&dev));
+        const size_t want = std::max<size_t>(bytes, size_t{1} << 16);
+        lock_.lock();
+        MultiTables &m = g_multi[{dev, stream}];
+        entry_ = &m;
+        if (m.bytes < bytes)
+        {
+            if (m.dev) (void) hipFree(m.dev);  // (waits for the calls still using it)
+            m.dev = nullptr, m.bytes = 0;
+            VMV_HIP(hipMalloc(&m.dev, want));
+            m.bytes = want;
+        }
+        // a host slot whose last copy has run (hipEventQuery: never waits), else a new one
+        slot_ = m.host.size();
+        for (size_t i = 0; i < m.host.size() && slot_ == m.host.size(); ++i)
+            if (m.host[i].bytes >= bytes && hipEventQuery(m.host[i].copied) == hipSuccess) slot_ = i;
+        if (slot_ == m.host.size())
+        {
+            MultiHostSlot s;
+            VMV_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+            if (hipError_t e = hipHostMalloc(&s.p, want, hipHostMallocDefault); e != hipSuccess)
+            {
+                (void) hipEventDestroy(s.copied);
+                return hip_fail(e, "hipHostMalloc(multi-environment tables)");
+            }
+            s.bytes = want;
+            m.host.push_back(s);
+        }
+        host = m.host[slot_].p;
+        this->dev = m.dev;
+        return VMV_OK;
+    }
+
+    int MultiTableLease::upload(hipStream_t stream, size_t bytes)
+    {
+        VMV_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+        VMV_HIP(hipEventRecord(static_cast<MultiTables *>(entry_)->host[slot_].copied, stream));
+        return VMV_OK;
+    }
+
+    void release_multi_tables()
+    {
+        std::lock_guard<std::mutex> g(g_multi_mutex);
+        for (auto &kv : g_multi)
+        {
+            if (kv.second.dev) (void) hipFree(kv.second.dev);
+            for (MultiHostSlot &s : kv.second.host)
+            {
+                (void) hipEventSynchronize(s.copied);
+                (void) hipHostFree(s.p);
+                (void) hipEventDestroy(s.copied);
+            }
+        }
+        g_multi.clear();
+    }
 
     // uniform configurations inside the joint bounds (bench input generator, counter based)
     __global__ void fill_uniform_kernel(float *q, size_t total, int dim, uint64_t seed, const float *lower,
@@ -946,6 +1027,40 @@ namespace
         if (env->robot_status[r] != VMV_OK) g_last_error = env->robot_error[r];
         return env->robot_status[r];
     }
+
+    // the checks of vmv_validate_batch_multi(_host) that need no device, in the header's order; *n = offsets[n_envs]
+    int multi_args(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const void *q,
+                   const void *bits, size_t *n)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        std::string err;
+        if (!envs || !offsets || !q || !bits)
+            err = "null pointer";
+        else if (n_envs >= vmv::kMultiMaxConfigs)
+            err = "n_envs must be below 2^31";
+        else if (offsets[0] != 0)
+            err = "offsets[0] must be 0";
+        else if (offsets[n_envs] >= vmv::kMultiMaxConfigs)
+            err = "offsets[n_envs] (the batch size) must be below 2^31";
+        for (size_t k = 0; err.empty() && k < n_envs; ++k)
+            if (offsets[k + 1] < offsets[k])
+                err = "offsets must be non-decreasing (offsets[" + std::to_string(k + 1) + "] < offsets[" + std::to_string(k) + "])";
+            else if (!envs[k])
+                err = "envs[" + std::to_string(k) + "] is NULL";
+        if (!err.empty())
+        {
+            g_last_error = err;
+            return VMV_ERR_INVALID_ARGUMENT;
+        }
+        for (size_t k = 0; k < n_envs; ++k)
+            if (!envs[k]->finalized)
+            {
+                g_last_error = "envs[" + std::to_string(k) + "] is not finalized";
+                return VMV_ERR_NOT_FINALIZED;
+            }
+        *n = offsets[n_envs];
+        return VMV_OK;
+    }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
@@ -993,6 +1108,23 @@ extern "C"
         if (int rc = check_device(env); rc != VMV_OK) return rc;
         if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
         return kLaunchers[robot]->validate_motion(env->launch[robot], d_a, d_b, n, d_bits, static_cast<hipStream_t>(stream));
+    }
+
+    int vmv_validate_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                 const float *d_q, uint64_t *d_bits, void *stream)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_bits, &n); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        std::vector<const vmv::EnvLaunch *> launch(n_envs);
+        for (size_t k = 0; k < n_envs; ++k)
+        {
+            if (int rc = ensure_robot(envs[k], robot); rc != VMV_OK) return rc;  // (once per environment and robot)
+            launch[k] = &envs[k]->launch[robot];
+        }
+        return kLaunchers[robot]->validate_multi(launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
     }
 
     int vmv_fk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
@@ -1183,7 +1315,26 @@ extern "C"
     {
         g_staging.release();
         vmv::release_edge_scratch();  // (waits for the edge batches still in flight: hipFree synchronizes)
+        vmv::release_multi_tables();
         return VMV_OK;
+    }
+    int vmv_validate_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                      const float *q, uint64_t *bits)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, q, bits, &n); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
+        char *arena = static_cast<char *>(g_staging.get(qb + wb));
+        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
+        float *dq = reinterpret_cast<float *>(arena);
+        uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + qb);
+        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
+        int rc = vmv_validate_batch_multi(robot, envs, offsets, n_envs, dq, dbits, nullptr);
+        if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        g_staging.trim();
+        return rc;
     }
     int vmv_validate_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint64_t *bits)
     {

@@ -23,12 +23,48 @@ namespace vmv
         EnvDev host;          // host copy (sizes)
     };
 
+    // ---- vmv_validate_batch_multi: configurations [lo, hi) of one batch against one environment each ----
+    struct MultiSeg  // one segment (device table written by the launcher)
+    {
+        const EnvDev *env;
+        uint32_t lo, hi;        // the segment's configurations [lo, hi) of the whole batch
+        uint32_t tests_in_lds;  // the environment's LDS plan, as its single-environment launch makes it
+        uint32_t slab;          // LDS float offset of wave 0's slab
+    };
+    struct MultiTile  // one workgroup's kWavesPerBlock validity words [word, word + 4) of segment `seg`
+    {
+        uint32_t seg, word;
+    };
+    constexpr size_t kMultiMaxConfigs = size_t{1} << 31;  // the kernels count configurations and segments in 32 bits
+
+    // Tables of one vmv_validate_batch_multi call: pinned host staging and device scratch per (device, stream), copied with
+    // hipMemcpyAsync on the stream.  Calls on one stream run in order, so they share the device buffer; a host buffer whose
+    // previous copy has not yet run is not rewritten (another one is taken), so the host never waits.  The lease holds the
+    // pool's lock until the call is enqueued.
+    class MultiTableLease
+    {
+        std::unique_lock<std::mutex> lock_;
+        void *entry_ = nullptr;  // the (device, stream) entry
+        size_t slot_ = 0;        // its host buffer in use
+
+    public:
+        void *host = nullptr, *dev = nullptr;
+        MultiTableLease();
+        int acquire(hipStream_t stream, size_t bytes);
+        int upload(hipStream_t stream, size_t bytes);  // host -> dev on `stream`
+    };
+    void release_multi_tables();
+
     // status codes are the VMV_* values of include/vamp_mvt_amd.h
     struct RobotLaunchers
     {
         // stage bit 1 = environment kernel (writes the words), bit 2 = self-collision kernel, bit 4 = attachment kernel
         // (both AND into them; the attachment kernel only runs for environments with an attachment)
         int (*validate)(const EnvLaunch &, const float *d_q, size_t n, uint64_t *d_bits, hipStream_t, int stages);
+        // vmv_validate_batch_multi: configurations [offsets[k], offsets[k + 1]) against *envs[k], n = offsets[n_envs] <
+        // kMultiMaxConfigs; every environment finalized on the current device with this robot's part built
+        int (*validate_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                              uint64_t *d_bits, hipStream_t);
         int (*validate_motion)(const EnvLaunch &, const float *d_a, const float *d_b, size_t n, uint64_t *d_bits,
                                hipStream_t);
         int (*fk)(const float *d_q, size_t n, float *d_out, hipStream_t);

@@ -5,10 +5,12 @@
 #include "../../include/vamp_mvt_amd.h"
 #include "vmv_common.h"
 
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 #ifdef VMV_SELF_STAMP
 #include <cstdio>
-#include <vector>
 #endif
 
 // workgroups per CU the edge kernels are compiled for (tuning knobs; tools/build_variant.py)
@@ -254,6 +256,88 @@ namespace VMV_ROBOT_NS
             const bool bad = R::template fkcc_attach<1>(E, cfg, wave_slab + lane, !todo);
             const uint64_t word = __ballot(todo && !bad);
             if (lane == 0) bits[first / kWave] = word;
+        }
+    }
+
+    // vmv_validate_batch_multi: the segmented twins of validate_env_kernel / validate_attach_kernel.  Workgroup b takes
+    // tile b of its launch's table and stages that tile's environment; wave w owns the GLOBAL validity word tile.word + w,
+    // and the lanes of that word outside the tile's segment are out of range, as lanes beyond n are in the
+    // single-environment kernels (zeroed joints, skipped).  The per-lane body is the single-environment one, so every bit
+    // is the one a call for that environment alone computes.  A word that holds configurations of two segments is shared:
+    // the launcher zeroed it and each segment ORs (environment half) or ANDs (attachment) its bits in with a 64-bit
+    // atomic, possibly from two launches; every other word has one writer and is stored as in the single-environment
+    // kernels.  (One tile per workgroup, no loop: a loop over tiles that restages on a change of segment carried enough
+    // scalar state across the body to spill on every robot.)
+    __device__ __forceinline__ bool multi_shared_word(const uint32_t first, const uint32_t lo, const uint32_t hi, const uint32_t n)
+    {
+        return first < lo || (hi < n && first + (uint32_t) kWave > hi);
+    }
+
+    template <int V>
+    __global__ __launch_bounds__(kBlock, (V == kEnvFull) ? 4 : (V == kEnvClouds) ? VMV_CLOUDS_BLOCKS : (V == kEnvPrims) ? VMV_PRIMS_BLOCKS : R::kEnvBlocks) void validate_env_multi_kernel(
+        const MultiSeg *__restrict__ segs, const MultiTile *__restrict__ tiles, const float *__restrict__ q, const uint32_t n,
+        uint64_t *__restrict__ bits)
+    {
+        extern __shared__ __align__(16) float smem[];
+        const MultiTile tile = tiles[blockIdx.x];
+        const MultiSeg S = segs[tile.seg];
+        const EnvView E = stage_environment(S.env, S.tests_in_lds, smem);
+        const uint32_t wave = uniform(threadIdx.x / kWave);
+        const uint32_t word = tile.word + wave, first = word * (uint32_t) kWave;
+        if (first >= S.hi) return;  // wave-uniform
+        lds_ptr wave_slab = (lds_ptr) smem + S.slab + wave * slab_floats();
+        const uint32_t lane = opaque_lane_id();
+        float cfg[R::kDim];
+        load_configs<R::kDim>(q, first, n, wave_slab, cfg, lane);
+        const bool in_seg = first + lane >= S.lo && first + lane < S.hi;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cfg[j] = in_seg ? cfg[j] : 0.0f;
+        const bool finite = sanitize_config<R::kDim>(cfg);
+        const bool in_range = in_seg && finite;
+        const bool bad = R::template fkcc_env<1, V>(E, cfg, wave_slab + lane, !in_range);
+        const uint64_t w = __ballot(in_range && !bad);
+        if (opaque_lane_id() == 0u)
+        {
+            if (multi_shared_word(first, S.lo, S.hi, n))
+                atomicOr(reinterpret_cast<unsigned long long *>(bits + word), (unsigned long long) w);
+            else
+                bits[word] = w;
+        }
+    }
+
+    __global__ __launch_bounds__(kBlock, 2) void validate_attach_multi_kernel(const MultiSeg *__restrict__ segs,
+                                                                             const MultiTile *__restrict__ tiles,
+                                                                             const float *__restrict__ q, const uint32_t n,
+                                                                             uint64_t *__restrict__ bits)
+    {
+        extern __shared__ __align__(16) float smem[];
+        const MultiTile tile = tiles[blockIdx.x];
+        const MultiSeg S = segs[tile.seg];
+        const EnvView E = stage_environment(S.env, S.tests_in_lds, smem);
+        const uint32_t lane = __lane_id();
+        const uint32_t wave = threadIdx.x / kWave;
+        const uint32_t word = tile.word + wave, first = word * (uint32_t) kWave;
+        if (first >= S.hi) return;  // wave-uniform
+        // (a shared word's bits of the other segment may change meanwhile; this segment's bits are this wave's alone)
+        const uint64_t before = bits[word];
+        if (before == 0ull) return;
+        lds_ptr wave_slab = (lds_ptr) smem + S.slab + wave * slab_floats();
+        float cfg[R::kDim];
+        load_configs<R::kDim>(q, first, n, wave_slab, cfg);
+        const bool in_seg = first + lane >= S.lo && first + lane < S.hi;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cfg[j] = in_seg ? cfg[j] : 0.0f;
+        const bool todo = in_seg && ((before >> lane) & 1ull);
+        const bool bad = R::template fkcc_attach<1>(E, cfg, wave_slab + lane, !todo);
+        if (multi_shared_word(first, S.lo, S.hi, n))
+        {
+            const uint64_t keep = __ballot(!(todo && bad));  // lanes outside the segment keep their bits
+            if (lane == 0) atomicAnd(reinterpret_cast<unsigned long long *>(bits + word), (unsigned long long) keep);
+        }
+        else
+        {
+            const uint64_t w = __ballot(todo && !bad);
+            if (lane == 0) bits[word] = w;
         }
     }
 
@@ -1079,6 +1163,109 @@ namespace VMV_ROBOT_NS
             return VMV_OK;
         }
 
+        // vmv_validate_batch_multi.  Every segment runs the variant its environment runs alone (the classes below: the
+        // choice of launch_validate), one launch per class present, each with its own tile table; then the self-collision
+        // kernel once over the whole batch (it does not depend on the environment), then the attachment kernel over the
+        // segments whose environment has an attachment.  Table: [segments | tiles of class 0 | .. | class 3 | attachment
+        // tiles], one workgroup per tile.
+        int launch_validate_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                  uint64_t *d_bits, hipStream_t stream)
+        {
+            constexpr int kClasses = 4, kAttach = kClasses;  // kEnvZOnly, kEnvPrims, kEnvFull, kEnvClouds | attachments
+            constexpr size_t kMaxGrid = size_t{1} << 20;      // workgroups per launch (grids of up to 2^24 are legal)
+            const size_t n = offsets[n_envs];
+            if (n == 0) return VMV_OK;
+            auto class_of = [](const EnvLaunch &e)
+            {
+                if (prims_only(e)) return (e.host.n_capsule + e.host.n_cuboid == 0) ? 0 : 1;
+                return clouds_only(e) ? 3 : 2;
+            };
+            std::vector<MultiSeg> segs(n_envs);
+            size_t n_tiles[kClasses + 1] = {}, at[kClasses + 1];
+            uint32_t shmem[kClasses + 1] = {};
+            bool any_shared = false;
+            for (size_t k = 0; k < n_envs; ++k)
+            {
+                const EnvLaunch &e = *envs[k];
+                uint32_t tests_in_lds = 0, bytes = 0;
+                if (offsets[k] < offsets[k + 1])
+                    if (int rc = plan_lds(e, tests_in_lds, bytes); rc != VMV_OK) return rc;
+                segs[k] = MultiSeg{e.d_env, (uint32_t) offsets[k], (uint32_t) offsets[k + 1], tests_in_lds,
+                                   ((e.host.n_floats + tests_in_lds + 3u) & ~3u) + kEnvRadiiFloats};
+                if (offsets[k] == offsets[k + 1]) continue;
+                const size_t tiles = ((offsets[k + 1] - 1) / kWave - offsets[k] / kWave) / kWavesPerBlock + 1;
+                any_shared |= offsets[k] % kWave != 0;
+                for (const int c : {class_of(e), e.host.n_attach > 0 ? kAttach : -1})
+                    if (c >= 0)
+                    {
+                        n_tiles[c] += tiles;
+                        shmem[c] = bytes > shmem[c] ? bytes : shmem[c];
+                    }
+            }
+            const size_t seg_bytes = (n_envs * sizeof(MultiSeg) + 15u) & ~size_t{15};
+            size_t total = 0;
+            for (int c = 0; c <= kClasses; ++c) at[c] = total, total += n_tiles[c];
+            MultiTableLease lease;
+            if (int rc = lease.acquire(stream, seg_bytes + total * sizeof(MultiTile)); rc != VMV_OK) return rc;
+            std::memcpy(lease.host, segs.data(), n_envs * sizeof(MultiSeg));
+            MultiTile *tiles = reinterpret_cast<MultiTile *>(static_cast<char *>(lease.host) + seg_bytes);
+            size_t fill[kClasses + 1];
+            std::copy(at, at + kClasses + 1, fill);
+            for (size_t k = 0; k < n_envs; ++k)
+            {
+                if (offsets[k] == offsets[k + 1]) continue;
+                const int cls = class_of(*envs[k]);
+                const bool attach = envs[k]->host.n_attach > 0;
+                for (size_t w = offsets[k] / kWave; w <= (offsets[k + 1] - 1) / kWave; w += kWavesPerBlock)
+                {
+                    tiles[fill[cls]++] = MultiTile{(uint32_t) k, (uint32_t) w};
+                    if (attach) tiles[fill[kAttach]++] = MultiTile{(uint32_t) k, (uint32_t) w};
+                }
+            }
+            const MultiSeg *d_segs = static_cast<const MultiSeg *>(lease.dev);
+            const MultiTile *d_tiles = reinterpret_cast<const MultiTile *>(static_cast<const char *>(lease.dev) + seg_bytes);
+            if (any_shared) VMV_HIP_TU(hipMemsetAsync(d_bits, 0, (n + kWave - 1) / kWave * sizeof(uint64_t), stream));
+            if (int rc = lease.upload(stream, seg_bytes + total * sizeof(MultiTile)); rc != VMV_OK) return rc;
+            auto launch = [&](const void *kernel, int c) -> int
+            {
+                if (n_tiles[c] == 0) return VMV_OK;
+                if (shmem[c] > 64u * 1024u)
+                    VMV_HIP_TU(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) shmem[c]));
+                const uint32_t m = (uint32_t) n;
+                for (size_t t0 = 0; t0 < n_tiles[c]; t0 += kMaxGrid)  // one workgroup per tile
+                {
+                    const dim3 grid((uint32_t) std::min(n_tiles[c] - t0, kMaxGrid));
+                    const MultiTile *t = d_tiles + at[c] + t0;
+                    if (c == kAttach)
+                        hipLaunchKernelGGL(validate_attach_multi_kernel, grid, dim3(kBlock), shmem[c], stream, d_segs, t, d_q, m,
+                                           d_bits);
+                    else if (c == 0)
+                        hipLaunchKernelGGL(validate_env_multi_kernel<kEnvZOnly>, grid, dim3(kBlock), shmem[c], stream, d_segs, t,
+                                           d_q, m, d_bits);
+                    else if (c == 1)
+                        hipLaunchKernelGGL(validate_env_multi_kernel<kEnvPrims>, grid, dim3(kBlock), shmem[c], stream, d_segs, t,
+                                           d_q, m, d_bits);
+                    else if (c == 2)
+                        hipLaunchKernelGGL(validate_env_multi_kernel<kEnvFull>, grid, dim3(kBlock), shmem[c], stream, d_segs, t,
+                                           d_q, m, d_bits);
+                    else
+                        hipLaunchKernelGGL(validate_env_multi_kernel<kEnvClouds>, grid, dim3(kBlock), shmem[c], stream, d_segs, t,
+                                           d_q, m, d_bits);
+                }
+                VMV_HIP_TU(hipGetLastError());
+                return VMV_OK;
+            };
+            const void *kernels[kClasses + 1] = {(const void *) validate_env_multi_kernel<kEnvZOnly>,
+                                                 (const void *) validate_env_multi_kernel<kEnvPrims>,
+                                                 (const void *) validate_env_multi_kernel<kEnvFull>,
+                                                 (const void *) validate_env_multi_kernel<kEnvClouds>,
+                                                 (const void *) validate_attach_multi_kernel};
+            for (int c = 0; c < kClasses; ++c)
+                if (int rc = launch(kernels[c], c); rc != VMV_OK) return rc;
+            if (int rc = launch_validate(EnvLaunch{}, d_q, n, d_bits, stream, 2); rc != VMV_OK) return rc;
+            return launch(kernels[kAttach], kAttach);
+        }
+
         // vmv_validate_motion_batch as (edge, rake) tasks: pass 0 = rake 0 of every edge, then the passes `bounds` lists
         // (rakes [bounds[p], bounds[p + 1]) of the edges still valid; the last bound is "no limit").
         int launch_rake_tasks(const EnvLaunch &env, uint32_t tests_in_lds, uint32_t shmem, const float *d_a, const float *d_b,
@@ -1263,7 +1450,8 @@ namespace VMV_ROBOT_NS
 }  // namespace VMV_ROBOT_NS
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-    extern const RobotLaunchers VMV_ROBOT_LAUNCH = {VMV_ROBOT_NS::launch_validate, VMV_ROBOT_NS::launch_validate_motion,
+    extern const RobotLaunchers VMV_ROBOT_LAUNCH = {VMV_ROBOT_NS::launch_validate, VMV_ROBOT_NS::launch_validate_multi,
+                                                    VMV_ROBOT_NS::launch_validate_motion,
                                                     VMV_ROBOT_NS::launch_fk, VMV_ROBOT_NS::launch_prepare,
                                                     VMV_ROBOT_NS::launch_eefk, VMV_ROBOT_NS::launch_contacts,
                                                     VMV_ROBOT_NS::R::kNSelfPairs};
