@@ -1,5 +1,5 @@
-"""The self-collision kernel with passes shared by the waves of a workgroup (default) against the per-wave kernel it
-replaced (VMV_SELF_BALANCE=0) and the oracle, word for word."""
+"""The self-collision kernel with passes shared by the waves of a workgroup against the oracle, word for word, at every
+share size (VMV_SELF_GROUP)."""
 import ctypes
 
 import numpy as np
@@ -60,24 +60,20 @@ def test_shared_passes_match_oracle_and_per_wave_kernel(vamp, oracle, monkeypatc
         want = np.zeros(n_words * 64, bool)
         want[:n] = caller[:n] & self_valid
         want_words = np.packbits(want, bitorder="little").view(np.uint64)
-        for balance in ("1", "0"):
-            monkeypatch.setenv("VMV_SELF_BALANCE", balance)
-            for group in [None] + [str(g) for g in range(1, 9)]:
-                if group is None:
-                    monkeypatch.delenv("VMV_SELF_GROUP", raising=False)
-                else:
-                    monkeypatch.setenv("VMV_SELF_GROUP", group)
-                got = _self_stage(vamp, name, q, words)
-                assert np.array_equal(got, want_words), (n, balance, group)
+        for group in [None] + [str(g) for g in range(1, 9)]:
+            if group is None:
+                monkeypatch.delenv("VMV_SELF_GROUP", raising=False)
+            else:
+                monkeypatch.setenv("VMV_SELF_GROUP", group)
+            got = _self_stage(vamp, name, q, words)
+            assert np.array_equal(got, want_words), (n, group)
 
 
 @pytest.mark.parametrize("name", ROBOTS)
 @pytest.mark.parametrize("kind", ["shell64", "cage"])
-def test_validate_batch_same_with_either_self_kernel(vamp, oracle, monkeypatch, name, kind):
+def test_validate_batch_same_with_either_self_kernel(vamp, oracle, name, kind):
     env, oenv = make_env(kind, oracle, name)
     n = 20000 - 27
     rid, q = _configs(oracle, name, n, seed=case_seed(name, kind, "self_balance_batch") % 100000)
     want = oracle.validate_batch(rid, oenv, q, threads=8)
-    for balance in ("1", "0"):
-        monkeypatch.setenv("VMV_SELF_BALANCE", balance)
-        assert np.array_equal(getattr(vamp, name).validate_batch(q, env), want), balance
+    assert np.array_equal(getattr(vamp, name).validate_batch(q, env), want)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Offline study (oracle = test infrastructure): fine-phase calls and rounds of the environment kernel per wave of 64
-configurations — one env_fine call per slab chunk (VMV_PACKED_FINE=0) vs each link's items packed into the slab and run
-in full rounds (vmv::env_fine_flush / env_fine_packed), vs one queue across links (built once and removed).
+configurations — one env_fine call per slab chunk (the form the packed phase replaced) vs each link's items packed into
+the slab and run in full rounds (vmv::env_fine_flush / env_fine_packed), vs one queue across links (built once and
+removed).
 Merged gates of gen_hip.merged_groups (what the primitive-only kernels walk), uniform configurations, shell_spec(0).
     python tools/experiments/packed_fine_study.py [waves]"""
 import ctypes

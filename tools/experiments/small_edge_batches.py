@@ -26,7 +26,9 @@ ua = (lo + (hi - lo) * torch.rand((N, len(lo)), generator=g, device="cuda")).con
 d = torch.randn((N, len(lo)), generator=g, device="cuda")
 ub = (ua + d / d.norm(dim=1, keepdim=True) * (0.2 + 1.3 * torch.rand((N, 1), generator=g, device="cuda"))).contiguous()
 sizes = [int(x) for x in sys.argv[1:]] or [256, 2048, 16384, 131072, 262144, 524288, N]
-modes = os.environ.get("EDGE_MODES", "default").split(",")  # VMV_EDGE_TASKS values to compare (default = by batch size)
+# VMV_EDGE_TASKS values to compare: default (by batch size), 1 (the two task kernels), 3 (the fused one where it exists)
+modes = os.environ.get("EDGE_MODES", "default").split(",")
+assert set(modes) <= {"default", "1", "3"}, modes
 for shape, A, B, mode in ((s, x, y, m) for (s, x, y) in (("prm", pa, pb), ("uniform", ua, ub)) for m in modes):
     if mode == "default":
         os.environ.pop("VMV_EDGE_TASKS", None)

@@ -114,8 +114,8 @@ def main():
             os.environ["VMV_SELF_GROUP"] = str(group)
         else:
             os.environ.pop("VMV_SELF_GROUP", None)
-        # the edge schedule (vmv_robot_tu.inc: launch_validate_motion): the default most of the time, the others too
-        sched = rng.choice(["", "", "", "0", "1", "2", "3"])
+        # the edge task kernels (vmv_robot_tu.inc: launch_validate_motion): chosen by batch size, or either one forced
+        sched = rng.choice(["", "1", "3"])
         if sched:
             os.environ["VMV_EDGE_TASKS"] = str(sched)
         else:

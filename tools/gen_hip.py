@@ -240,7 +240,7 @@ def gate_rates(m, n=4096, seed=0, tables=()):
     return [float(f.mean()) for f in fire]
 
 
-SELF_TABLE_N = int(os.environ.get("VMV_SELF_TABLE_N", 256))  # cells per joint of the two-joint clearance tables (0: none)
+SELF_TABLE_N = 256  # cells per joint of the two-joint clearance tables
 SELF_TABLE_MARGIN = 1e-4  # metres, on top of the Lipschitz slack of a cell (fp32 effects at metre scale are ~1e-6)
 
 
@@ -257,8 +257,6 @@ def self_tables(m, N=SELF_TABLE_N):
     whose bit is 0 for a configuration's cell has no colliding fine pair there, so skipping it cannot change the answer;
     outside the joint bounds (and for NaN) every bit is 1.  -> [dict(joints=(i, j), groups=[index into self_groups...],
     table=uint8[N][N] (bit g = group g of this table must be tested), lo=(..), inv=(..))]"""
-    if N <= 0:
-        return []
     dim = m["dimension"]
     lo, span = np.array(m["lower"], float), np.array(m["span"], float)
     r = np.array(m["radii"], float)
@@ -336,23 +334,11 @@ MOTION_SELF_BLOCKS = {"ur5": 5}
 # fused one-FK kernels (the task kernel of planner-sized edge batches, n < 16,384): at 3 workgroups per CU (168 VGPRs) Panda's
 # body spills 28 VGPRs instead of 77 at 4, and such batches never fill more than 2 - 3 waves per SIMD: 256 edges 0.104 ->
 # 0.096 ms, 2,048 0.133 -> 0.126, 8,192 0.148 -> 0.135 (at 2: 0.094 / 0.123 / 0.148); UR5 (no spill at 3) unchanged
-FUSED_BLOCKS = {r: int(os.environ.get("VMV_FUSED_BLOCKS", 3)) for r in ("panda", "ur5")}
-for _r in ("panda", "ur5", "fetch", "baxter"):  # tuning knobs: VMV_{SELF,ENV}_BLOCKS_<ROBOT>, VMV_{SELF,ENV}_CHUNK_<ROBOT>
-    if f"VMV_ENV_BLOCKS_{_r.upper()}" in os.environ:
-        ENV_BLOCKS[_r] = int(os.environ[f"VMV_ENV_BLOCKS_{_r.upper()}"])
-    if f"VMV_ENV_CHUNK_{_r.upper()}" in os.environ:
-        ENV_CHUNK[_r] = int(os.environ[f"VMV_ENV_CHUNK_{_r.upper()}"])
-    if f"VMV_SELF_BLOCKS_{_r.upper()}" in os.environ:
-        SELF_BLOCKS[_r] = int(os.environ[f"VMV_SELF_BLOCKS_{_r.upper()}"])
-    if f"VMV_SELF_CHUNK_{_r.upper()}" in os.environ:
-        SELF_CHUNK[_r] = int(os.environ[f"VMV_SELF_CHUNK_{_r.upper()}"])
-    if f"VMV_MOTION_SELF_BLOCKS_{_r.upper()}" in os.environ:
-        MOTION_SELF_BLOCKS[_r] = int(os.environ[f"VMV_MOTION_SELF_BLOCKS_{_r.upper()}"])
-SELF_DENSE_RATE = float(os.environ.get('VMV_SELF_DENSE_RATE', 0.5))   # groups whose bounding-pair gate fires for at least this share of uniform configurations ...
+FUSED_BLOCKS = {"panda": 3, "ur5": 3}
+SELF_DENSE_RATE = 0.5   # groups whose bounding-pair gate fires for at least this share of uniform configurations ...
 SELF_DENSE_MIN_A = 3    # ... and whose A side is at least this large use the pre-test + compaction form
 SPARSE_BATCH = 8        # sparse groups merged per item list (the list holds SPARSE_BATCH * 64 entries = CHUNK * 64)
 SELF_MARGIN = 1e-4      # metres; enclosure of fine spheres by bounding spheres is asserted to 2e-6 by tools/robot_trace.py
-LAZY_FINE_FK = os.environ.get("VMV_LAZY_FINE_FK", "1") == "1"  # see emit_env_link
 DEFAULT_CHUNK = 8  # fine spheres staged in the LDS slab at a time
 assert SPARSE_BATCH <= 8 and DEFAULT_CHUNK <= 8  # vmv::kSelfScratchWords holds 8 * 64 list entries
 
@@ -360,7 +346,6 @@ assert SPARSE_BATCH <= 8 and DEFAULT_CHUNK <= 8  # vmv::kSelfScratchWords holds 
 GRID_CLASSES = 4  # vmv::kGridClasses
 
 
-MERGE_RIGID_LINKS = os.environ.get("VMV_NO_MERGED_GROUPS") is None  # (A/B knob at generation time)
 # distances inside a rigid cluster still vary by a few 1e-9 m over the configurations (the tape's fixed-joint rotations
 # are 15-digit constants, not exactly orthonormal); anything a joint moves varies by millimetres and more
 RIGID_TOL = 1e-7
@@ -396,7 +381,7 @@ def merged_groups(m):
     out, cur = [], None
     for ln in m["links"]:
         g = env_by_link[ln]
-        if ln in static or not MERGE_RIGID_LINKS:
+        if ln in static:
             cur = None
             out.append(dict(link=ln, members=[ln], bound=g["bound"], fine=list(g["fine"]), radius=m["radii"][g["bound"]]))
             continue
@@ -534,13 +519,13 @@ def emit_robot(m):
     static = set(static_links(m))
     reach = link_samples(m)
 
-    def emit_env_link(em, ln, lazy=LAZY_FINE_FK, no_skip=False, pair_with=None, pre=None, order=None, packed=False):
+    def emit_env_link(em, ln, lazy=True, no_skip=False, pair_with=None, pre=None, order=None, packed=False):
         """one link of the environment half: FK ops, slab staging, gate, fine chunks (appends to em.lines).
         lazy: the FK ops only this link's fine spheres need, and the staging of its first chunk, are emitted inside
         `if (wave_any(gate))` - links whose bounding sphere never reaches an obstacle (the base links in a shell-shaped
-        scene) then cost their chain ops and one cell lookup, nothing else.
-        packed: under #if VMV_PACKED_FINE the passing lanes' fine spheres of all chunks are packed into the slab as items
-        and run in full rounds (vmv::env_fine_flush / env_fine_packed); #else the per-chunk env_fine calls."""
+        scene) then cost their chain ops and one cell lookup, nothing else (the fused body stages eagerly: lazy=False).
+        packed: the passing lanes' fine spheres of all chunks are packed into the slab as items and run in full rounds
+        (vmv::env_fine_flush / env_fine_packed) instead of one env_fine call per chunk (profiles/r05_packed_fine_ab.txt)."""
         order = links if order is None else order  # the groups of this walk, in chain order
         g = env_by_link[ln]
         fine = g["fine"]
@@ -548,8 +533,6 @@ def emit_robot(m):
         assert all(len(ch) <= slab_spheres for ch in chunks), (ln, slab_spheres)  # a chunk never outgrows the slab
         if ln in static:
             em.lines.append(f"        // ---- {ln}: static, evaluated once per environment (static_env_hit)")
-            return
-        if ln in os.environ.get("VMV_ABLATE_SKIP_LINKS", "").split(","):  # measurement aid (wrong answers)
             return
         em.lines.append(f"        // ---- {ln}: {len(fine)} spheres")
         gi_env = m["env_groups"].index(g) if g in m["env_groups"] else -1  # (merged gates carry no reach certificate)
@@ -625,31 +608,24 @@ def emit_robot(m):
         em.lines.append("            if (VMV_ABLATE_ENV >= 1) bad |= gate;  // measurement aid: no fine phase (wrong answers)")
         em.lines.append("            else if (n_gate != 0)")
         em.lines.append("            {")
-        packed = packed and lazy  # (the packed form stages after the gate: lanes write at their rank among passing lanes)
-        done_before = list(em.done)
-        if packed:
-            # both forms emit the same private FK ops inside this block, so the emitter leaves either in the same state
-            em.lines.append("#if VMV_PACKED_FINE")
+        if packed:  # (the packed form stages after the gate: lanes write at their rank among passing lanes)
             emit_packed_fine(em, ln, chunks, private)
-            em.lines.append("#else")
-            em.done[:] = done_before
-        if lazy:
-            # (chunk by chunk: the FK of a later chunk's spheres is emitted right before that chunk is staged, so the
-            # coordinates of a 27-sphere group are never all live across the fine calls)
-            em.emit_ops(private & em.closure(chunks[0]), indent="                ")
-            for si, s in enumerate(chunks[0]):
-                stage(si, s, "                ")
-        done = 0
-        for ci, ch in enumerate(chunks):
-            if ci > 0:
-                if lazy:
-                    em.emit_ops(private & em.closure(ch), indent="                ")
-                for si, s in enumerate(ch):
+        else:
+            if lazy:
+                # (chunk by chunk: the FK of a later chunk's spheres is emitted right before that chunk is staged, so the
+                # coordinates of a 27-sphere group are never all live across the fine calls)
+                em.emit_ops(private & em.closure(chunks[0]), indent="                ")
+                for si, s in enumerate(chunks[0]):
                     stage(si, s, "                ")
-            em.lines.append(f"                vmv::env_fine<G, Tab, V>(E, slab, scratch, {len(ch)}, {radii_off[ln] + 1 + done}, 0, n_gate);")
-            done += len(ch)
-        if packed:
-            em.lines.append("#endif")
+            done = 0
+            for ci, ch in enumerate(chunks):
+                if ci > 0:
+                    if lazy:
+                        em.emit_ops(private & em.closure(ch), indent="                ")
+                    for si, s in enumerate(ch):
+                        stage(si, s, "                ")
+                em.lines.append(f"                vmv::env_fine<G, Tab, V>(E, slab, scratch, {len(ch)}, {radii_off[ln] + 1 + done}, 0, n_gate);")
+                done += len(ch)
         em.lines.append("                bad |= gate && vmv::group_any<G>(vmv::env_flag(scratch));")
         em.lines.append("            }")
         em.lines.append("        }")
@@ -662,20 +638,15 @@ def emit_robot(m):
         L.append(f"    {name}(const vmv::EnvView &E, const float (&q)[kDim], vmv::lds_ptr slab, const bool skip)")
         L.append("    {")
         if not paired:
-            L.append("#ifndef VMV_NO_CAPT_PAIR  // (A/B knob, tools/build_variant.py: every gate queries the clouds on its own)")
             L.append("        if constexpr (V == vmv::kEnvFull || V == vmv::kEnvClouds) return fkcc_env_paired<G, V>(E, q, slab, skip);")
-            L.append("#endif")
         L.append("        bool bad = skip || (E.dev->static_hit != 0u);")
         L.append("        // per-wave scratch words live right behind the sphere slab")
         L.append("        const vmv::lds_ptr scratch = slab - __lane_id() + kSlabSpheres * 3 * vmv::kRow;")
         if not paired:
             L.append("        const unsigned long long skip_links = E.dev->link_skip;  // reach certificates (vmv_api.hip), wave-uniform")
-            L.append("#if VMV_PACKED_FINE")
             L.append("        const vmv::lds_ptr pk_items = slab - __lane_id();  // the slab as an SoA item buffer of kPackSlots slots")
-            L.append("#endif")
         em = Emitter(m)
-        skipped = os.environ.get("VMV_ABLATE_SKIP_LINKS", "").split(",")
-        movable = [ln for ln in links if ln not in static and ln not in skipped]
+        movable = [ln for ln in links if ln not in static]
         if not paired:
             # primitive-only variants: rigidly connected links share one gate (merged_groups)
             for ln in prim_order:

@@ -18,8 +18,7 @@ configs = int(sys.argv[2]) if len(sys.argv) > 2 else 1 << 20
 raw = json.load(open(src))
 kernels = {}
 for name, c in raw.items():
-    for key in ("validate_env_kernel", "validate_self_kernel", "validate_kernel", "validate_motion_env_kernel",
-                "validate_motion_self_kernel"):
+    for key in ("validate_env_kernel", "validate_self_kernel", "rake_tasks_env_kernel", "rake_tasks_self_kernel"):
         if name.split("<")[0] == key:
             k = dict(c)
             k["name"] = name

@@ -1528,7 +1528,7 @@ extern "C"
         // the environment kernel dominates
         std::string ep(entry_point);
         if (ep == "validate_batch") ep = "validate_env";
-        if (ep == "validate_motion_batch") ep = "validate_motion_env";
+        if (ep == "validate_motion_batch") ep = "rake_tasks_env";
         name = std::string("vmv::") + kRobots[robot].name + "::" + ep + "_kernel";
         return name.c_str();
     }

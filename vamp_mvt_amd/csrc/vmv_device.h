@@ -1065,12 +1065,11 @@ namespace vmv
             H.n[kSphere] = D->n_sphere, H.off[kSphere] = D->off_sphere, H.wbase[kSphere] = D->wbase_sphere;
             H.n[kZCapsule] = D->n_zcapsule, H.off[kZCapsule] = D->off_zcapsule, H.wbase[kZCapsule] = D->wbase_zcapsule;
             H.n[kZCuboid] = D->n_zcuboid, H.off[kZCuboid] = D->off_zcuboid, H.wbase[kZCuboid] = D->wbase_zcuboid;
-#ifndef VMV_NO_HDR_HOIST  // (A/B knob, tools/build_variant.py: without the pin every field is fetched where it is used;
-                          // measured on the Panda bench: environment kernel 0.1559 -> 0.1534 ms, profiles/r03_hdr_hoist_ab.txt)
+            // (without the pin every field is fetched where it is used; measured on the Panda bench: environment kernel
+            // 0.1559 -> 0.1534 ms with it, profiles/r03_hdr_hoist_ab.txt)
             if constexpr (PIN)
                 asm volatile("" ::"s"(H.n[kSphere]), "s"(H.n[kZCapsule]), "s"(H.n[kZCuboid]), "s"(H.off[kSphere]), "s"(H.off[kZCapsule]),
                              "s"(H.off[kZCuboid]), "s"(H.wbase[kSphere]), "s"(H.wbase[kZCapsule]), "s"(H.wbase[kZCuboid]));
-#endif
         }
         return H;
     }
@@ -1431,21 +1430,18 @@ namespace vmv
         wave_lds_sync();
     }
 
-    // ---- packed fine phase (generated fkcc_env of the primitive-only walks; VMV_PACKED_FINE=0 restores env_fine) ----
+    // ---- packed fine phase (generated fkcc_env of the primitive-only walks; profiles/r05_packed_fine_ab.txt) ----
     // One link's fine items, packed across its slab chunks.  The wave's slab region is viewed as an SoA item buffer of
     // C = kSlabSpheres * 64 slots (x at [0, C), y at [C, 2C), z at [2C, 3C): 3C <= kSlabSpheres * 3 * kRow floats, so the
     // LDS per wave stays what it was).  With k lanes through the gate, the lane of rank j (its position in the gate's
     // lane list) writes fine sphere s of the link — s counted from the link's first fine sphere, across chunks — as item
     // i = s * k + j, at slot i - done, where `done` counts the link's items already run.  Only passing lanes write, so the
-    // buffer holds live items only; a chunk's FK is still emitted right before its staging (VMV_LAZY_FINE_FK).
+    // buffer holds live items only; a chunk's FK is still emitted right before its staging (tools/gen_hip.py: emit_env_link).
     // The generated code runs the rounds (env_fine_flush) only when the next chunk would not fit, and once at the end of
     // the link; where env_fine paid a call, a sync and a candidate walk per chunk, a link now pays them per flush.
     // Rakes (G = 8): k is a multiple of 8 (whole rakes pass), and `done` and every round's first slot are multiples of 8
     // (a flush runs whole 64-item rounds or everything staged, k * s items), so the 8 lanes of a round that hold one
     // rake's items for one sphere stay adjacent and 8-aligned for group_max.
-#ifndef VMV_PACKED_FINE
-#define VMV_PACKED_FINE 1
-#endif
     __device__ __forceinline__ int lane_rank(const bool pred)
     {
         const uint64_t mask = __ballot(pred);

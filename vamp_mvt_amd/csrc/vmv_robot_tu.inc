@@ -32,13 +32,6 @@
 // 262,144 roadmap-shaped edges 1.455 -> 1.38 ms)
 #define VMV_MOTION_SELF_BLOCKS R::kMotionSelfBlocks  // (UR5: 5, tools/gen_hip.py MOTION_SELF_BLOCKS)
 #endif
-// default schedule of vmv_validate_motion_batch (launch_validate_motion): 0 edge walk, 1 (edge, rake) tasks in two passes,
-// 2 tasks in doubling passes.  Measured on one MI355X (profiles/r03_edge_schedules.txt): the two-pass tasks win at every
-// batch size and on every workload (UR5 2,048 edges 0.54 -> 0.17 ms, 131,072 edges 1.37 -> 0.90 ms, 1M edges 8.2 -> 6.3 ms;
-// Baxter + CAPT 262,144 edges 26.3 -> 18.9 ms)
-#ifndef VMV_EDGE_SCHEDULE
-#define VMV_EDGE_SCHEDULE 1
-#endif
 // batches below this many edges take the fused task kernel where the robot has one (Panda, UR5; primitives only).  Measured
 // (profiles/r03_edge_schedules.txt, UR5): 256 edges 0.148 -> 0.128 ms, 2,048: 0.165 -> 0.144, 8,192: 0.179 -> 0.158, level at
 // 16,384, slower beyond (32,768: 0.29 -> 0.36)
@@ -189,38 +182,11 @@ namespace VMV_ROBOT_NS
         }
     }
 
-    // Both halves of Robot::fkcc in ONE kernel, one FK per configuration (robots with R::kHasFused; the launcher uses it
-    // for vmv_validate_batch when the environment has no attachment).  The per-wave LDS region is the larger of the two
-    // halves' (they use it one after the other).
+    // Per-wave LDS region of the fused task kernel (both halves of Robot::fkcc along one FK, robots with R::kHasFused):
+    // the larger of the two halves' (they use it one after the other).
     __host__ __device__ constexpr uint32_t fused_slab_floats()
     {
         return slab_floats() > self_slab_floats() ? slab_floats() : self_slab_floats();
-    }
-    template <int V>
-    __global__ __launch_bounds__(kBlock, R::kFusedBlocks) void validate_kernel(const EnvDev *__restrict__ env,
-                                                                               const uint32_t tests_in_lds,
-                                                                               const float *__restrict__ q, const size_t n,
-                                                                               uint64_t *__restrict__ bits)
-    {
-        extern __shared__ __align__(16) float smem[];
-        const EnvView E = stage_environment(env, tests_in_lds, smem);
-        const uint32_t lane = __lane_id();
-        const uint32_t wave = threadIdx.x / kWave;
-        lds_ptr wave_slab =
-            (lds_ptr) smem + ((env->n_floats + tests_in_lds + 3u) & ~3u) + kEnvRadiiFloats + wave * fused_slab_floats();
-        lds_ptr slab = wave_slab + lane;
-        for (size_t base = (size_t) blockIdx.x * kBlock; base < n; base += (size_t) gridDim.x * kBlock)
-        {
-            const size_t first = base + (size_t) wave * kWave;
-            if (first >= n) continue;  // wave-uniform
-            float cfg[R::kDim];
-            load_configs<R::kDim>(q, first, n, wave_slab, cfg);
-            const bool finite = sanitize_config<R::kDim>(cfg);
-            const bool in_range = first + lane < n && finite;
-            const bool bad = R::template fkcc_fused<1, V>(E, cfg, slab, !in_range);
-            const uint64_t word = __ballot(in_range && !bad);
-            if (lane == 0) bits[first / kWave] = word;
-        }
     }
 
     // One workgroup, every lane alike: the environment groups of the robot's static links (gen: static_env_hit).
@@ -477,82 +443,6 @@ namespace VMV_ROBOT_NS
         VMV_STAMP_END;
     }
 
-    // The self-collision half as before the shared passes (VMV_SELF_BALANCE=0, A/B only): a wave owns `group` words of
-    // its own and works through their valid configurations alone.
-    __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_wave_kernel(const float *__restrict__ q, const uint32_t n,
-                                                                    uint64_t *__restrict__ bits, const uint32_t group)
-    {
-        // (32-bit counts, a scalar wave index and a lane number re-derived per group: as in validate_env_kernel, what is
-        // invariant across the loop would otherwise be hoisted into VGPRs and spilled — 60 B of scratch per lane before)
-        VMV_STAMP_START;
-        __shared__ __align__(16) float stage[kSelfRadiiFloats + kWavesPerBlock * self_slab_floats()];
-        __shared__ unsigned long long result[kWavesPerBlock][8];
-        stage_radii(stage);
-        __syncthreads();
-        const uint32_t wave = uniform(threadIdx.x / kWave);
-        lds_ptr wave_slab = (lds_ptr) stage + kSelfRadiiFloats + wave * self_slab_floats();
-        const uint32_t words = (n + (uint32_t) kWave - 1u) / (uint32_t) kWave;
-        const uint32_t groups = (words + group - 1u) / group;
-        for (uint32_t g = blockIdx.x * (uint32_t) kWavesPerBlock + wave; g < groups; g += gridDim.x * (uint32_t) kWavesPerBlock)
-        {
-            const uint32_t lane = opaque_lane_id();
-            const uint32_t w0 = g * group;
-            const uint32_t nw = (words - w0 < group) ? words - w0 : group;  // wave-uniform
-            uint64_t mine = (lane < nw) ? bits[w0 + lane] : 0ull;
-            // vmv_validate_batch_self is an entry point of its own: a caller's words may have bits set at or beyond n
-            // (all-ones words); they are cleared here, so no configuration past the end of d_q is ever read
-            const uint32_t tail = n % (uint32_t) kWave;
-            if (w0 + lane == words - 1u && tail != 0u) mine = (mine << (64u - tail)) >> (64u - tail);
-            // the group's words as wave-uniform values + their popcount prefix
-            uint64_t W[8];
-            uint32_t before[9];
-            before[0] = 0u;
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-            {
-                const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) mine, k);
-                const uint32_t hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (mine >> 32), k);
-                W[k] = ((uint64_t) hi << 32) | lo;
-                before[k + 1] = before[k] + (uint32_t) __popcll(W[k]);
-            }
-            const uint32_t total = before[8];
-            // wave-uniform: nothing left to check in this group (the batch's last group goes on all the same: it stores the
-            // tail bits it cleared)
-            if (total == 0u && (w0 + nw != words || tail == 0u)) continue;
-            if (lane < 8u) result[wave][lane] = mine;
-            wave_lds_sync();
-            for (uint32_t pass = 0; pass < total; pass += kWave)
-            {
-                VMV_STAMP_PASS;
-                const uint32_t j = pass + lane;
-                const bool todo = j < total;
-                uint32_t k = 0u;
-#pragma unroll
-                for (int t = 1; t < 8; ++t) k += (todo && j >= before[t]) ? 1u : 0u;  // word of the j-th valid configuration
-                uint64_t v = W[0];
-                uint32_t skip = 0u;
-#pragma unroll
-                for (int t = 1; t < 8; ++t)
-                {
-                    v = (k == (uint32_t) t) ? W[t] : v;
-                    skip = (k == (uint32_t) t) ? before[t] : skip;
-                }
-                const uint32_t b = todo ? nth_set_bit(v, j - skip) : 0u;
-                const uint32_t idx = (w0 + (todo ? k : 0u)) * (uint32_t) kWave + b;  // (a valid bit always lies below n <= 2^31)
-                float cfg[R::kDim];
-#pragma unroll
-                for (int d = 0; d < R::kDim; ++d) cfg[d] = q[(size_t) idx * R::kDim + d];
-                const bool bad = R::template fkcc_self<1>(cfg, wave_slab + lane, (lds_cptr) stage, !todo);
-                if (todo && bad) atomicAnd(&result[wave][k], ~(1ull << b));  // LDS atomic
-            }
-            wave_lds_sync();
-            if (opaque_lane_id() < nw) bits[w0 + opaque_lane_id()] = result[wave][opaque_lane_id()];
-            wave_lds_sync();
-        }
-        VMV_STAMP_WORK_DONE;
-        VMV_STAMP_END;
-    }
-
     // hsum + exact sqrt of a configuration-sized vector (vector/avx.hh:441-452, interface.hh:397-410)
     template <int DIM>
     __device__ __forceinline__ float l2_norm(const float (&v)[DIM])
@@ -568,7 +458,10 @@ namespace VMV_ROBOT_NS
         return sqrtf(a + b);
     }
 
-    // validate_motion<Robot, 8, Robot::resolution> over a batch of edges (planning/validate.hh:24-77).
+    // Attachment part of validate_motion<Robot, 8, Robot::resolution> over a batch of edges (planning/validate.hh:24-77),
+    // after the (edge, rake) task passes: an edge is valid iff fkcc and fkcc_attach are clear on every rake (the
+    // reference's early-out only skips work, so the parts may walk the edge independently); this walk continues only the
+    // edges the task passes left valid and clears the bit of an edge one of whose rakes collides.
     //
     // Lanes 8g..8g+7 of a wave are the 8 lanes of one reference rake (G = 8: the reference's "any lane of the rake"
     // gating is reproduced with ballots).  Edges have very different lengths (n = ceil(distance * resolution / 8)
@@ -577,23 +470,18 @@ namespace VMV_ROBOT_NS
     // counter as soon as its current edge is decided.  Per edge the arithmetic is the reference's, in its order:
     // block = start + vector * percent for the first rake, then block -= backstep, n and backstep from the
     // hsum-ordered l2 norm.  Validity bits of the chunk are assembled in LDS and stored once.
-    // SELF selects which half of fkcc the kernel evaluates; an edge is valid iff both halves are clear on every
-    // rake (the reference's early-out only skips work, so the halves may walk the edge independently); the
-    // self-collision pass only walks edges the environment pass left valid.
 #ifndef VMV_CHUNK_EDGES
 #define VMV_CHUNK_EDGES 512
 #endif
     constexpr uint32_t kChunkEdges = VMV_CHUNK_EDGES;     // multiple of 64: chunks own whole validity words
     constexpr uint32_t kCtrlWords = 4 + kChunkEdges / 32; // [0] next edge, [4..] validity bits of the chunk
 
-    template <int PART, int V = kEnvFull>  // 0 environment half (writes the bits), 1 self-collision half, 2 attachment part (AND into them)
     __device__ __forceinline__ void motion_body(const EnvView &E, lds_ptr slab, lds_u32 *ctrl,
                                                 const float *__restrict__ start, const float *__restrict__ goal,
                                                 const size_t n, uint32_t *__restrict__ bits32, const uint32_t chunk)
     {
         // chunk: edges per workgroup pass, a multiple of 64 and at most kChunkEdges (the launcher shrinks it for small
         // batches so that the grid still fills the chip: a 2,000-edge planner batch is 32 workgroups at 64, 4 at 512)
-        constexpr bool SELF = PART != 0;  // continues only edges that are still valid
         const uint32_t lane = __lane_id();
         const uint32_t tid = threadIdx.x;
         const uint32_t group = tid / 8;  // rake group within the workgroup
@@ -610,7 +498,7 @@ namespace VMV_ROBOT_NS
             if (tid < chunk / 32)
             {
                 const size_t w = begin / 32 + tid;
-                uint32_t in = (SELF && w < n_words) ? bits32[w] : 0u;
+                uint32_t in = (w < n_words) ? bits32[w] : 0u;
                 const size_t first_edge = w * 32;  // bits at or beyond n are never continued (and come back as 0)
                 if (first_edge + 32 > n) in &= (first_edge < n) ? ((1u << (uint32_t) (n - first_edge)) - 1u) : 0u;
                 chunk_bits[tid] = in;
@@ -622,7 +510,6 @@ namespace VMV_ROBOT_NS
             size_t e = begin + group;
             bool fresh = true;  // e was just assigned and has not been set up yet
             uint32_t step = 0, steps = 1;
-            bool poison = false;  // the current edge has a non-finite endpoint: invalid by the boundary rule
             float block[R::kDim], backstep[R::kDim];
 #pragma unroll
             for (int j = 0; j < R::kDim; ++j) block[j] = backstep[j] = 0.0f;
@@ -630,17 +517,14 @@ namespace VMV_ROBOT_NS
             while (true)
             {
                 // (re)assign: groups whose edge is decided, or dead on arrival, pull the next edge of the chunk
-                if constexpr (SELF)
+                while (true)
                 {
-                    while (true)
-                    {
-                        const bool dead = fresh && e < end &&
-                                          ((chunk_bits[(e - begin) / 32] >> ((e - begin) % 32)) & 1u) == 0u;
-                        if (!wave_any(dead)) break;
-                        uint32_t ne = (dead && k == 0) ? atomicAdd((uint32_t *) ctrl, 1u) : 0u;
-                        ne = (uint32_t) __shfl((int) ne, (int) leader);
-                        if (dead) e = ne;
-                    }
+                    const bool dead = fresh && e < end &&
+                                      ((chunk_bits[(e - begin) / 32] >> ((e - begin) % 32)) & 1u) == 0u;
+                    if (!wave_any(dead)) break;
+                    uint32_t ne = (dead && k == 0) ? atomicAdd((uint32_t *) ctrl, 1u) : 0u;
+                    ne = (uint32_t) __shfl((int) ne, (int) leader);
+                    if (dead) e = ne;
                 }
                 const bool work = e < end;
                 if (!wave_any(work)) break;
@@ -660,7 +544,7 @@ namespace VMV_ROBOT_NS
 #pragma unroll
                     for (int j = 0; j < R::kDim; ++j)
                     {
-                        s[j] = finite ? s[j] : 0.0f;  // a poisoned edge is one rake at the zero configuration, then invalid
+                        s[j] = finite ? s[j] : 0.0f;  // (an edge with a non-finite endpoint is already invalid)
                         v[j] = finite ? v[j] - s[j] : 0.0f;
                     }
                     const float distance = l2_norm<R::kDim>(v);
@@ -677,17 +561,10 @@ namespace VMV_ROBOT_NS
                     }
                     steps = take ? st : steps;
                     step = take ? 0u : step;
-                    poison = take ? !finite : poison;
                     fresh = false;
                 }
 
-                bool bad;
-                if constexpr (PART == 1)
-                    bad = R::template fkcc_self<8>(block, slab, E.radii, !work);
-                else if constexpr (PART == 2)
-                    bad = R::template fkcc_attach<8>(E, block, slab, !work);
-                else
-                    bad = R::template fkcc_env<8, V>(E, block, slab, !work) || poison;
+                const bool bad = R::template fkcc_attach<8>(E, block, slab, !work);
 
                 // advance (validate.hh:43-64)
                 const bool decided = work && (bad || step + 1 >= steps);
@@ -702,14 +579,7 @@ namespace VMV_ROBOT_NS
                     if (decided && k == 0)
                     {
                         const uint32_t bit = 1u << ((e - begin) % 32);
-                        if constexpr (SELF)
-                        {
-                            if (bad) atomicAnd((uint32_t *) &chunk_bits[(e - begin) / 32], ~bit);
-                        }
-                        else
-                        {
-                            if (!bad) atomicOr((uint32_t *) &chunk_bits[(e - begin) / 32], bit);
-                        }
+                        if (bad) atomicAnd((uint32_t *) &chunk_bits[(e - begin) / 32], ~bit);
                     }
                     uint32_t ne = (decided && k == 0) ? atomicAdd((uint32_t *) ctrl, 1u) : 0u;
                     ne = (uint32_t) __shfl((int) ne, (int) leader);
@@ -921,23 +791,6 @@ namespace VMV_ROBOT_NS
         rake_task_body<1>(E, wave_slab + __lane_id(), start, goal, n, bits8, nullptr, excl, tasks, lo_i, first != 0u);
     }
 
-    template <int V>
-    __global__ __launch_bounds__(kBlock, 3) void validate_motion_env_kernel(const EnvDev *__restrict__ env,
-                                                                             const uint32_t tests_in_lds,
-                                                                             const float *__restrict__ start,
-                                                                             const float *__restrict__ goal,
-                                                                             const size_t n, uint32_t *__restrict__ bits,
-                                                                             const uint32_t chunk)
-    {
-        extern __shared__ __align__(16) float smem[];
-        const EnvView E = stage_environment(env, tests_in_lds, smem);
-        const uint32_t wave = threadIdx.x / kWave;
-        const uint32_t head = ((env->n_floats + tests_in_lds + 3u) & ~3u) + kEnvRadiiFloats;
-        lds_ptr wave_slab = (lds_ptr) smem + head + wave * slab_floats();
-        lds_u32 *ctrl = (lds_u32 *) ((lds_ptr) smem + head + kWavesPerBlock * slab_floats());
-        motion_body<0, V>(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk);
-    }
-
     __global__ __launch_bounds__(kBlock, 2) void validate_motion_attach_kernel(const EnvDev *__restrict__ env,
                                                                               const uint32_t tests_in_lds,
                                                                               const float *__restrict__ start,
@@ -951,21 +804,7 @@ namespace VMV_ROBOT_NS
         const uint32_t head = ((env->n_floats + tests_in_lds + 3u) & ~3u) + kEnvRadiiFloats;
         lds_ptr wave_slab = (lds_ptr) smem + head + wave * slab_floats();
         lds_u32 *ctrl = (lds_u32 *) ((lds_ptr) smem + head + kWavesPerBlock * slab_floats());
-        motion_body<2>(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk);
-    }
-
-    __global__ __launch_bounds__(kBlock, 2) void validate_motion_self_kernel(const float *__restrict__ start,
-                                                                           const float *__restrict__ goal,
-                                                                           const size_t n, uint32_t *__restrict__ bits,
-                                                                           const uint32_t chunk)
-    {
-        __shared__ __align__(16) float stage[kSelfRadiiFloats + kWavesPerBlock * self_slab_floats() + kCtrlWords];
-        stage_radii(stage);
-        __syncthreads();
-        const EnvView E{nullptr, nullptr, 0u, (lds_cptr) stage};
-        lds_ptr wave_slab = (lds_ptr) stage + kSelfRadiiFloats + (threadIdx.x / kWave) * self_slab_floats();
-        lds_u32 *ctrl = (lds_u32 *) ((lds_ptr) stage + kSelfRadiiFloats + kWavesPerBlock * self_slab_floats());
-        motion_body<1>(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk);
+        motion_body(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk);
     }
 
     __global__ __launch_bounds__(kBlock) void fk_batch_kernel(const float *__restrict__ q, const size_t n,
@@ -991,12 +830,11 @@ namespace VMV_ROBOT_NS
         }
 
         // The top levels of point cloud 0's split-plane tree go to LDS (every query walks them); the budget keeps
-        // four workgroups per CU resident.  VMV_CAPT_PLANES_LDS_BYTES overrides the budget (tuning knob).
+        // four workgroups per CU resident.
         int plan_lds(const EnvLaunch &env, uint32_t &tests_in_lds, uint32_t &shmem)
         {
             const EnvDev &D = env.host;
-            uint32_t budget = 2u * 1024u;  // measured: 2 KiB beats 0, 4, 8, 16 KiB (occupancy outweighs the deeper LDS levels)
-            if (const char *o = getenv("VMV_CAPT_PLANES_LDS_BYTES")) budget = (uint32_t) strtoul(o, nullptr, 10);
+            const uint32_t budget = 2u * 1024u;  // measured: 2 KiB beats 0, 4, 8, 16 KiB (occupancy outweighs the deeper LDS levels)
             tests_in_lds = 0;  // floats: whole 3-level groups of the blocked plane copy, from the root down
             if (D.n_capt > 0) tests_in_lds = capt_plane_floats(D.capt[0].nlog2, budget / (uint32_t) sizeof(float));
             shmem = lds_bytes(D, tests_in_lds);
@@ -1034,35 +872,9 @@ namespace VMV_ROBOT_NS
         if (e_ != hipSuccess) return hip_status(e_, #call);        \
     } while (0)
 
-        // VMV_FUSED_KERNEL=1 (opt-in, A/B only): one fused kernel instead of the environment and self-collision kernels
-        // back to back.  Measured slower on every robot it exists for (Panda 0.326 vs 0.295 ms per 1M configurations: the
-        // fused body needs 128 VGPRs with 61 spilled), so the two-kernel path stays the default.
-        bool use_fused(const EnvLaunch &env, int stages)
-        {
-            static const bool on = getenv("VMV_FUSED_KERNEL") != nullptr;
-            return R::kHasFused && on && (stages & 3) == 3 && prims_only(env);
-        }
-
         int launch_validate(const EnvLaunch &env, const float *d_q, size_t n, uint64_t *d_bits, hipStream_t stream,
                             int stages)
         {
-            if (use_fused(env, stages))
-            {
-                uint32_t tests_in_lds, shmem;
-                int rc = plan_lds(env, tests_in_lds, shmem);
-                if (rc != VMV_OK) return rc;
-                const uint32_t head = ((env.host.n_floats + tests_in_lds + 3u) & ~3u) + kEnvRadiiFloats;
-                shmem = (head + (uint32_t) kWavesPerBlock * fused_slab_floats()) * (uint32_t) sizeof(float);
-                if (shmem > kMaxLdsBytes) return VMV_ERR_CAPACITY;
-                auto kernel = (env.host.n_capsule + env.host.n_cuboid == 0) ? validate_kernel<kEnvZOnly> : validate_kernel<kEnvPrims>;
-                if (shmem > 64u * 1024u)
-                    VMV_HIP_TU(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int) shmem));
-                hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), shmem, stream, env.d_env, tests_in_lds,
-                                   d_q, n, d_bits);
-                VMV_HIP_TU(hipGetLastError());
-                stages &= ~3;
-            }
             if (stages & 1)
             {
                 uint32_t tests_in_lds, shmem;
@@ -1086,26 +898,20 @@ namespace VMV_ROBOT_NS
             }
             if (stages & 2)
             {
-                // VMV_SELF_BALANCE=0 (A/B only): the per-wave kernel; read per call (the parity tests switch it)
-                const char *balance = getenv("VMV_SELF_BALANCE");
-                const bool shared = !(balance && balance[0] == '0');
-                auto kernel = shared ? validate_self_kernel : validate_self_wave_kernel;
                 // words per wave: one round of resident workgroups (the hardware's count: 256 CUs x kSelfBlocks workgroups
                 // x 4 waves on the MI355X) covers the batch, at most 8 (VMV_SELF_GROUP overrides: measurement aid)
                 const size_t words = (n + kWave - 1) / kWave;
-                auto resident_waves = [](const void *k)
+                static const size_t resident = []
                 {
                     int per_cu = 0, dev = 0, cus = 256;
+                    const void *k = (const void *) validate_self_kernel;
                     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0) != hipSuccess || per_cu < 1)
                         per_cu = R::kSelfBlocks;
                     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
                         cus < 1)
                         cus = 256;
                     return (size_t) cus * (size_t) per_cu * kWavesPerBlock;
-                };
-                static const size_t resident_shared = resident_waves((const void *) validate_self_kernel);
-                static const size_t resident_wave = resident_waves((const void *) validate_self_wave_kernel);
-                const size_t resident = shared ? resident_shared : resident_wave;
+                }();
                 uint32_t group = (uint32_t) ((words + resident - 1) / resident);
                 if (const char *e = getenv("VMV_SELF_GROUP")) group = (uint32_t) strtoul(e, nullptr, 10);
                 group = group < 1u ? 1u : (group > 8u ? 8u : group);
@@ -1127,14 +933,15 @@ namespace VMV_ROBOT_NS
                     }
                     VMV_HIP_TU(hipMemsetAsync(d_stamp, 0, blocks * kWavesPerBlock * 4 * sizeof(uint64_t), stream));
 #endif
-                    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, d_q + lo * R::kDim, m,
+                    hipLaunchKernelGGL(validate_self_kernel, dim3(blocks), dim3(kBlock), 0, stream, d_q + lo * R::kDim, m,
                                        d_bits + lo / kWave, group);
 #ifdef VMV_SELF_STAMP
-                    // header: n, group, workgroups, shared (1) or per-wave (0); then 4 words per wave.  Overwritten per launch.
+                    // header: n, group, workgroups, 1 (the shared-pass kernel; files of older builds may hold 0, the per-wave
+                    // kernel); then 4 words per wave.  Overwritten per launch.
                     if (const char *path = getenv("VMV_SELF_STAMP_OUT"))
                     {
                         std::vector<uint64_t> rec(4 + blocks * kWavesPerBlock * 4);
-                        rec[0] = m, rec[1] = group, rec[2] = blocks, rec[3] = shared ? 1u : 0u;
+                        rec[0] = m, rec[1] = group, rec[2] = blocks, rec[3] = 1u;
                         VMV_HIP_TU(hipMemcpyAsync(rec.data() + 4, d_stamp, blocks * kWavesPerBlock * 4 * sizeof(uint64_t),
                                                   hipMemcpyDeviceToHost, stream));
                         VMV_HIP_TU(hipStreamSynchronize(stream));
@@ -1266,11 +1073,13 @@ namespace VMV_ROBOT_NS
             return launch(kernels[kAttach], kAttach);
         }
 
-        // vmv_validate_motion_batch as (edge, rake) tasks: pass 0 = rake 0 of every edge, then the passes `bounds` lists
-        // (rakes [bounds[p], bounds[p + 1]) of the edges still valid; the last bound is "no limit").
+        // vmv_validate_motion_batch as (edge, rake) tasks in two passes: rake 0 of every edge, then all the other rakes of
+        // the edges still valid.  Measured on one MI355X against the edge walk (one rake group walks one edge) and against
+        // passes of doubling width (profiles/r03_edge_schedules.txt): the two passes won at every batch size and on every
+        // workload (UR5 2,048 edges 0.54 -> 0.17 ms, 131,072 edges 1.37 -> 0.90 ms, 1M edges 8.2 -> 6.3 ms; Baxter + CAPT
+        // 262,144 edges 26.3 -> 18.9 ms).  fused: both halves in rake_tasks_fused_kernel, one FK and one launch per pass.
         int launch_rake_tasks(const EnvLaunch &env, uint32_t tests_in_lds, uint32_t shmem, const float *d_a, const float *d_b,
-                              size_t n_all, uint64_t *d_bits, hipStream_t stream, const uint32_t *bounds, uint32_t n_bounds,
-                              bool fused = false)
+                              size_t n_all, uint64_t *d_bits, hipStream_t stream, bool fused)
         {
             auto env_kernel = clouds_only(env) ? rake_tasks_env_kernel<kEnvClouds> : rake_tasks_env_kernel<kEnvFull>;
             if (prims_only(env))
@@ -1303,22 +1112,17 @@ namespace VMV_ROBOT_NS
                     hipLaunchKernelGGL(rake_tasks_self_kernel, dim3(grid_for(n, per_block)), dim3(kBlock), 0, stream, a, b, n, bits8,
                                        (const uint32_t *) nullptr, (const uint32_t *) nullptr, 0u, 1u);
                 VMV_HIP_TU(hipGetLastError());
-                // later passes: the task count is only known on the device, so the grid is sized for the batch (a
-                // workgroup without a task leaves before it stages anything) and strides over the tasks
+                // second pass (rakes 1 and up): the task count is only known on the device, so the grid is sized for the
+                // batch (a workgroup without a task leaves before it stages anything) and strides over the tasks
                 const size_t guess = (size_t) n * 8u < 8192u ? 8192u : (size_t) n * 8u;
                 const int later_grid = grid_for(guess, per_block) < 8192 ? grid_for(guess, per_block) : 8192;
-                for (uint32_t p = 0; p + 1 < n_bounds; ++p)
-                {
-                    if (int rc = launch_edge_pass_scan(S, d_bits + base / 64, n, bounds[p], bounds[p + 1], p, stream); rc != VMV_OK)
-                        return rc;
-                    hipLaunchKernelGGL(env_kernel, dim3(later_grid), dim3(kBlock), shmem, stream, env.d_env, tests_in_lds, a, b,
-                                       n, bits8, (uint32_t *) nullptr, (const uint32_t *) S.excl, (const uint32_t *) (S.total + p),
-                                       bounds[p], 0u);
-                    if (!fused)
-                        hipLaunchKernelGGL(rake_tasks_self_kernel, dim3(later_grid), dim3(kBlock), 0, stream, a, b, n, bits8,
-                                           (const uint32_t *) S.excl, (const uint32_t *) (S.total + p), bounds[p], 0u);
-                    VMV_HIP_TU(hipGetLastError());
-                }
+                if (int rc = launch_edge_pass_scan(S, d_bits + base / 64, n, 1u, 0xffffffffu, 0u, stream); rc != VMV_OK) return rc;
+                hipLaunchKernelGGL(env_kernel, dim3(later_grid), dim3(kBlock), shmem, stream, env.d_env, tests_in_lds, a, b, n,
+                                   bits8, (uint32_t *) nullptr, (const uint32_t *) S.excl, (const uint32_t *) S.total, 1u, 0u);
+                if (!fused)
+                    hipLaunchKernelGGL(rake_tasks_self_kernel, dim3(later_grid), dim3(kBlock), 0, stream, a, b, n, bits8,
+                                       (const uint32_t *) S.excl, (const uint32_t *) S.total, 1u, 0u);
+                VMV_HIP_TU(hipGetLastError());
             }
             return VMV_OK;
         }
@@ -1329,58 +1133,26 @@ namespace VMV_ROBOT_NS
             uint32_t tests_in_lds, shmem;
             int rc = plan_lds(env, tests_in_lds, shmem);
             if (rc != VMV_OK) return rc;
-            // VMV_EDGE_TASKS (measurement / test aid): 0 = the edge walk below, 1 = (edge, rake) tasks in two passes (rake 0,
-            // then all the others), 2 = tasks in doubling passes (rake 0, 1, 2-3, 4-7, 8-15, the rest); unset: VMV_EDGE_SCHEDULE
-            const char *forced = getenv("VMV_EDGE_TASKS");  // (read per call: the parity tests switch it)
-            int mode = forced ? atoi(forced) : VMV_EDGE_SCHEDULE;
-            // 3 = two-pass tasks through the fused kernel (one FK, one launch per pass): where it exists, by default for
-            // batches too small to fill the chip (VMV_EDGE_FUSED_BELOW); elsewhere 3 means 1
-            const bool can_fuse = R::kHasFused && prims_only(env) &&
-                                  env.host.n_attach == 0;
-            if (!forced && mode == 1 && can_fuse && n < (size_t) VMV_EDGE_FUSED_BELOW) mode = 3;
-            if (mode == 3 && !can_fuse) mode = 1;
-            if (mode != 0)
+            // the fused task kernel where it exists, for batches too small to fill the chip (VMV_EDGE_FUSED_BELOW).
+            // VMV_EDGE_TASKS (test aid, read per call: the parity tests switch it) forces one side: 1 = the two task
+            // kernels, 3 = the fused one where it exists; any other value is ignored
+            const bool can_fuse = R::kHasFused && prims_only(env) && env.host.n_attach == 0;
+            const char *forced = getenv("VMV_EDGE_TASKS");
+            const bool force_two = forced && strcmp(forced, "1") == 0, force_fused = forced && strcmp(forced, "3") == 0;
+            const bool fused = can_fuse && (force_fused || (!force_two && n < (size_t) VMV_EDGE_FUSED_BELOW));
+            rc = launch_rake_tasks(env, tests_in_lds, shmem, d_a, d_b, n, d_bits, stream, fused);
+            if (rc != VMV_OK) return rc;
+            if (env.host.n_attach > 0)  // the attachment part continues the edges still valid (motion_body)
             {
-                static const uint32_t two[] = {1u, 0xffffffffu}, doubling[] = {1u, 2u, 4u, 8u, 16u, 0xffffffffu};
-                rc = mode == 2 ? launch_rake_tasks(env, tests_in_lds, shmem, d_a, d_b, n, d_bits, stream, doubling, 6) :
-                                 launch_rake_tasks(env, tests_in_lds, shmem, d_a, d_b, n, d_bits, stream, two, 2, mode == 3);
-                if (rc != VMV_OK) return rc;
-                if (env.host.n_attach > 0)  // the attachment part continues the edges still valid, as below
-                {
-                    uint32_t chunk = kChunkEdges;
-                    while (chunk > 64u && (n + chunk - 1) / chunk < 2048u) chunk /= 2u;
-                    if (shmem > 64u * 1024u)
-                        VMV_HIP_TU(hipFuncSetAttribute((const void *) validate_motion_attach_kernel,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int) shmem));
-                    hipLaunchKernelGGL(validate_motion_attach_kernel, dim3(grid_for(n, chunk)), dim3(kBlock), shmem, stream,
-                                       env.d_env, tests_in_lds, d_a, d_b, n, reinterpret_cast<uint32_t *>(d_bits), chunk);
-                    VMV_HIP_TU(hipGetLastError());
-                }
-                return VMV_OK;
-            }
-            // edges per workgroup pass: as large as kChunkEdges while the grid still has >= 2,048 workgroups (2.7 rounds
-            // of the resident ones), never below one validity word
-            uint32_t chunk = kChunkEdges;
-            while (chunk > 64u && (n + chunk - 1) / chunk < 2048u) chunk /= 2u;
-            auto kernel = validate_motion_env_kernel<kEnvFull>;
-            if (prims_only(env))
-                kernel = (env.host.n_capsule + env.host.n_cuboid == 0) ? validate_motion_env_kernel<kEnvZOnly> :
-                                                                           validate_motion_env_kernel<kEnvPrims>;
-            if (shmem > 64u * 1024u)
-                VMV_HIP_TU(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) shmem));
-            hipLaunchKernelGGL(kernel, dim3(grid_for(n, chunk)), dim3(kBlock), shmem, stream, env.d_env, tests_in_lds,
-                               d_a, d_b, n, reinterpret_cast<uint32_t *>(d_bits), chunk);
-            VMV_HIP_TU(hipGetLastError());
-            hipLaunchKernelGGL(validate_motion_self_kernel, dim3(grid_for(n, chunk)), dim3(kBlock), 0, stream, d_a,
-                               d_b, n, reinterpret_cast<uint32_t *>(d_bits), chunk);
-            VMV_HIP_TU(hipGetLastError());
-            if (env.host.n_attach > 0)
-            {
+                // edges per workgroup pass: as large as kChunkEdges while the grid still has >= 2,048 workgroups (2.7
+                // rounds of the resident ones), never below one validity word
+                uint32_t chunk = kChunkEdges;
+                while (chunk > 64u && (n + chunk - 1) / chunk < 2048u) chunk /= 2u;
                 if (shmem > 64u * 1024u)
                     VMV_HIP_TU(hipFuncSetAttribute((const void *) validate_motion_attach_kernel,
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int) shmem));
-                hipLaunchKernelGGL(validate_motion_attach_kernel, dim3(grid_for(n, chunk)), dim3(kBlock), shmem,
-                                   stream, env.d_env, tests_in_lds, d_a, d_b, n, reinterpret_cast<uint32_t *>(d_bits), chunk);
+                hipLaunchKernelGGL(validate_motion_attach_kernel, dim3(grid_for(n, chunk)), dim3(kBlock), shmem, stream,
+                                   env.d_env, tests_in_lds, d_a, d_b, n, reinterpret_cast<uint32_t *>(d_bits), chunk);
                 VMV_HIP_TU(hipGetLastError());
             }
             return VMV_OK;
