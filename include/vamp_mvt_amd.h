@@ -177,6 +177,18 @@ int vmv_validate_batch_multi_host(int robot, const vmv_env *const *envs, const s
  * resolution 64 — far beyond any joint range; the reference's walk of such an edge would not end either). */
 int vmv_validate_motion_batch(int robot, const vmv_env *env, const float *d_start, const float *d_goal, size_t n,
                               uint64_t *d_bits, void *stream);
+/* Many environments in one call, for edges: edge i = d_start[i] -> d_goal[i], edges [offsets[k], offsets[k+1]) against
+ * envs[k].  The contract of vmv_validate_batch_multi, word for word (offsets, limits, checks before the first launch
+ * and device-free checks first, environments of another device refused, no host synchronisation, tables and scratch per
+ * (device, stream) freed by vmv_release_staging), with the bits of one vmv_validate_motion_batch per environment,
+ * concatenated.  The launches per 2^20-edge slice (segments clipped at its ends): the validity words zeroed, rake 0 of
+ * the environment half once per variant class present, the self-collision half and the scan once over the slice, the
+ * later pass's tiles built on the device from the scan, the remaining rakes of the environment half once per class,
+ * those of the self-collision half once, the attachment walk over the segments with an attachment. */
+int vmv_validate_motion_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                    const float *d_start, const float *d_goal, uint64_t *d_bits, void *stream);
+int vmv_validate_motion_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                         const float *start, const float *goal, uint64_t *bits);
 
 /* <robot>.debug(q, env) — robot_helper.hh:249-253 -> Robot::fkcc_debug: per fine sphere the environment objects it
  * collides with (sphere_environment_get_collisions, collision/validity.hh:161-256: the five sorted primitive lists with
@@ -214,7 +226,7 @@ int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *s
                                    uint64_t *bits);
 /* The host-buffer variants stage through a per-thread device arena that is reused between calls (requests above 64 MiB
  * are not kept), and vmv_validate_motion_batch keeps 8 bytes of device scratch per edge per (device, stream) for its task
- * lists, vmv_validate_batch_multi its tables.  Frees the calling thread's arena and every stream's scratch and tables
+ * lists, the multi-environment calls their tables.  Frees the calling thread's arena and every stream's scratch and tables
  * (waits for the batches in flight); optional — none of this memory is touched at thread or process exit. */
 int vmv_release_staging(void);
 

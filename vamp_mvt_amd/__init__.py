@@ -653,6 +653,57 @@ class _Robot(types.ModuleType):
                                                 bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_multi_host")
         return unpack_bits(bits, n)
 
+    def validate_motion_batch_multi(self, starts, goals, environments, counts):
+        """bool[n]: edges starts[i] -> goals[i], [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None =
+        the empty environment), in one call.  The same answers as one validate_motion_batch per environment,
+        concatenated.  numpy in -> numpy out; torch CUDA tensors in -> torch.bool CUDA tensor out, launched on torch's
+        current stream."""
+        environments = list(environments)
+        counts = np.asarray(counts)
+        if counts.ndim != 1 or len(counts) != len(environments):
+            raise ValueError(f"expected one count per environment, got {counts.shape} counts for {len(environments)}")
+        if counts.size and (not np.issubdtype(counts.dtype, np.integer) or (counts < 0).any()):
+            raise ValueError("counts must be non-negative integers")
+        for e in environments:
+            if e is not None and not isinstance(e, Environment):
+                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
+        torch_in = _is_torch_cuda(starts)
+        if torch_in:
+            if not _is_torch_cuda(goals):
+                raise TypeError("starts is a torch CUDA tensor, goals is not")
+            sa, sb = tuple(starts.shape), tuple(goals.shape)
+        else:
+            a, b = _f32(starts), _f32(goals)
+            sa, sb = a.shape, b.shape
+        if len(sa) != 2 or sa[1] != self._dim or sa != sb:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = sa[0]
+        if int(offsets[-1]) != n:
+            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} edges")
+        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
+        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        offs = offsets.ctypes.data_as(_lib.c_size_p)
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(starts.device):
+                at = starts.contiguous().float()
+                bt = goals.to(at.device).contiguous().float()
+                bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=at.device)
+                stream = ctypes.c_void_p(torch.cuda.current_stream(at.device).cuda_stream)
+                check(lib.vmv_validate_motion_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(at.data_ptr()),
+                                                          ctypes.c_void_p(bt.data_ptr()), ctypes.c_void_p(bits.data_ptr()),
+                                                          stream), "vmv_validate_motion_batch_multi")
+                shifts = torch.arange(64, device=at.device, dtype=torch.int64)
+                return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+        bits = np.zeros((n + 63) // 64, np.uint64)
+        check(lib.vmv_validate_motion_batch_multi_host(self._id, handles, offs, len(envs), _fp(a), _fp(b),
+                                                       bits.ctypes.data_as(_lib.c_u64_p)),
+              "vmv_validate_motion_batch_multi_host")
+        return unpack_bits(bits, n)
+
     def validate_motion_batch(self, starts, goals, environment: Environment | None = None):
         if _is_torch_cuda(starts):
             return self._torch_bits(starts, goals, environment)

@@ -1028,13 +1028,15 @@ namespace
         return env->robot_status[r];
     }
 
-    // the checks of vmv_validate_batch_multi(_host) that need no device, in the header's order; *n = offsets[n_envs]
+    // the checks of vmv_validate_batch_multi(_host) and vmv_validate_motion_batch_multi(_host) that need no device, in the
+    // header's order; q and q2 are the input arrays (the configurations twice, or the starts and the goals);
+    // *n = offsets[n_envs]
     int multi_args(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const void *q,
-                   const void *bits, size_t *n)
+                   const void *q2, const void *bits, size_t *n)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         std::string err;
-        if (!envs || !offsets || !q || !bits)
+        if (!envs || !offsets || !q || !q2 || !bits)
             err = "null pointer";
         else if (n_envs >= vmv::kMultiMaxConfigs)
             err = "n_envs must be below 2^31";
@@ -1114,7 +1116,7 @@ extern "C"
                                  const float *d_q, uint64_t *d_bits, void *stream)
     {
         size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_bits, &n); rc != VMV_OK) return rc;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_q, d_bits, &n); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         for (size_t k = 0; k < n_envs; ++k)
             if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
@@ -1125,6 +1127,24 @@ extern "C"
             launch[k] = &envs[k]->launch[robot];
         }
         return kLaunchers[robot]->validate_multi(launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
+    }
+
+    int vmv_validate_motion_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                        const float *d_start, const float *d_goal, uint64_t *d_bits, void *stream)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, d_start, d_goal, d_bits, &n); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        std::vector<const vmv::EnvLaunch *> launch(n_envs);
+        for (size_t k = 0; k < n_envs; ++k)
+        {
+            if (int rc = ensure_robot(envs[k], robot); rc != VMV_OK) return rc;  // (once per environment and robot)
+            launch[k] = &envs[k]->launch[robot];
+        }
+        return kLaunchers[robot]->validate_motion_multi(launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
+                                                        static_cast<hipStream_t>(stream));
     }
 
     int vmv_fk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
@@ -1322,7 +1342,7 @@ extern "C"
                                       const float *q, uint64_t *bits)
     {
         size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, q, bits, &n); rc != VMV_OK) return rc;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, q, q, bits, &n); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         if (int rc = require_device(); rc != VMV_OK) return rc;
         const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
@@ -1332,6 +1352,25 @@ extern "C"
         uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + qb);
         if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
         int rc = vmv_validate_batch_multi(robot, envs, offsets, n_envs, dq, dbits, nullptr);
+        if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        g_staging.trim();
+        return rc;
+    }
+    int vmv_validate_motion_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                             const float *start, const float *goal, uint64_t *bits)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, start, goal, bits, &n); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
+        char *arena = static_cast<char *>(g_staging.get(2 * qb + wb));
+        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
+        float *da = reinterpret_cast<float *>(arena), *db = reinterpret_cast<float *>(arena + qb);
+        uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + 2 * qb);
+        if (hipMemcpy(da, start, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
+        if (hipMemcpy(db, goal, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
+        int rc = vmv_validate_motion_batch_multi(robot, envs, offsets, n_envs, da, db, dbits, nullptr);
         if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
         g_staging.trim();
         return rc;

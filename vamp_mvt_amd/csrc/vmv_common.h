@@ -67,6 +67,9 @@ namespace vmv
                               uint64_t *d_bits, hipStream_t);
         int (*validate_motion)(const EnvLaunch &, const float *d_a, const float *d_b, size_t n, uint64_t *d_bits,
                                hipStream_t);
+        // vmv_validate_motion_batch_multi: edges [offsets[k], offsets[k + 1]) against *envs[k], as validate_multi
+        int (*validate_motion_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_a,
+                                     const float *d_b, uint64_t *d_bits, hipStream_t);
         int (*fk)(const float *d_q, size_t n, float *d_out, hipStream_t);
         // once per (environment, robot), after the robot's EnvDev is on the device: evaluates the robot's static links
         // against the environment and stores the answer in d_env->static_hit (synchronous)
@@ -106,4 +109,18 @@ namespace vmv
     // task counts of the pass that covers rakes [lo, hi) of the edges still valid in d_bits -> s.excl, s.total[slot]
     int launch_edge_pass_scan(const EdgeScratch &s, const uint64_t *d_bits, uint32_t n, uint32_t lo, uint32_t hi, uint32_t slot,
                               hipStream_t stream);
+
+    // ---- vmv_validate_motion_batch_multi: the later pass's tiles, built on the device from the scan ----
+    // Segment k's later-pass tasks are [excl[lo_k], excl[hi_k]) (total for the last edge).  Per variant class c, the
+    // non-empty segments of the class are entries[at[c] .. at[c] + m[c]) (indices into the MultiSeg table);
+    // launch_edge_multi_tiles writes chunk[c] = tasks per tile (a multiple of 32, at least sum / grid[c]) and
+    // starts[at[c] + c + j] = tiles of the class's entries before j (m[c] + 1 values), so that the class has at most
+    // grid[c] + m[c] tiles and a tile never spans two segments.
+    constexpr int kEdgeMultiClasses = 4;
+    struct EdgeMultiPlan
+    {
+        uint32_t at[kEdgeMultiClasses], m[kEdgeMultiClasses], grid[kEdgeMultiClasses];
+    };
+    int launch_edge_multi_tiles(const EdgeScratch &s, const MultiSeg *d_segs, const uint32_t *d_entries, const EdgeMultiPlan &plan,
+                                uint32_t n, uint32_t *d_starts, uint32_t *d_chunk, hipStream_t stream);
 }  // namespace vmv

@@ -145,6 +145,68 @@ namespace vmv
             }
         }
 
+        // vmv_validate_motion_batch_multi: one workgroup per variant class (vmv_common.h: EdgeMultiPlan).  Sums the class's
+        // later-pass tasks, sets the tile size, then scans the tiles per segment in rounds of kScanThreads segments.
+        __device__ __forceinline__ uint32_t segment_tasks(const MultiSeg &S, const uint32_t *__restrict__ excl,
+                                                          const uint32_t *__restrict__ total, const uint32_t n)
+        {
+            return (S.hi < n ? excl[S.hi] : *total) - excl[S.lo];
+        }
+
+        __global__ __launch_bounds__(kScanThreads) void edge_multi_tiles_kernel(const MultiSeg *__restrict__ segs,
+                                                                                const uint32_t *__restrict__ entries,
+                                                                                const EdgeMultiPlan plan,
+                                                                                const uint32_t *__restrict__ excl,
+                                                                                const uint32_t *__restrict__ total, const uint32_t n,
+                                                                                uint32_t *__restrict__ starts,
+                                                                                uint32_t *__restrict__ chunk)
+        {
+            __shared__ uint32_t part[kScanThreads / kWave];
+            const uint32_t c = blockIdx.x, m = plan.m[c];
+            if (m == 0u) return;
+            const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+            const uint32_t *ent = entries + plan.at[c];
+            uint32_t *st = starts + plan.at[c] + c;
+            uint32_t mine = 0u;
+            for (uint32_t j = threadIdx.x; j < m; j += kScanThreads) mine += segment_tasks(segs[ent[j]], excl, total, n);
+            mine = wave_sum(mine);
+            if (lane == 0) part[wave] = mine;
+            __syncthreads();
+            uint32_t sum = 0u;
+            for (uint32_t i = 0; i < kScanThreads / kWave; ++i) sum += part[i];
+            const uint32_t per = (uint32_t) (((uint64_t) sum + plan.grid[c] - 1u) / plan.grid[c]);
+            const uint32_t size = per <= 32u ? 32u : (per + 31u) & ~31u;
+            uint32_t carry = 0u;
+            for (uint32_t base = 0; base < m; base += kScanThreads)
+            {
+                __syncthreads();  // (part[] is rewritten)
+                const uint32_t j = base + threadIdx.x;
+                const uint32_t tiles = j < m ? (segment_tasks(segs[ent[j]], excl, total, n) + size - 1u) / size : 0u;
+                uint32_t incl = tiles;
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1)
+                {
+                    const uint32_t up = (uint32_t) __shfl_up((int) incl, d);
+                    incl += (lane >= (uint32_t) d) ? up : 0u;
+                }
+                if (lane == kWave - 1) part[wave] = incl;
+                __syncthreads();
+                uint32_t before = carry, round = 0u;
+                for (uint32_t i = 0; i < kScanThreads / kWave; ++i)
+                {
+                    before += (i < wave) ? part[i] : 0u;
+                    round += part[i];
+                }
+                if (j < m) st[j] = before + incl - tiles;
+                carry += round;
+            }
+            if (threadIdx.x == 0)
+            {
+                st[m] = carry;
+                chunk[c] = size;
+            }
+        }
+
         struct ScratchBuffer
         {
             void *base = nullptr;
@@ -208,6 +270,15 @@ namespace vmv
         hipLaunchKernelGGL(edge_scan_write_kernel, dim3(blocks), dim3(kScanThreads), 0, stream, s.steps, bits8, n, lo, hi,
                            s.block_sums, s.excl, s.total + slot);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_status(e, "edge pass scan");
+        return VMV_OK;
+    }
+
+    int launch_edge_multi_tiles(const EdgeScratch &s, const MultiSeg *d_segs, const uint32_t *d_entries, const EdgeMultiPlan &plan,
+                                uint32_t n, uint32_t *d_starts, uint32_t *d_chunk, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(edge_multi_tiles_kernel, dim3(kEdgeMultiClasses), dim3(kScanThreads), 0, stream, d_segs, d_entries,
+                           plan, (const uint32_t *) s.excl, (const uint32_t *) s.total, n, d_starts, d_chunk);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_status(e, "edge multi tiles");
         return VMV_OK;
     }
 }  // namespace vmv

@@ -476,9 +476,21 @@ namespace VMV_ROBOT_NS
     constexpr uint32_t kChunkEdges = VMV_CHUNK_EDGES;     // multiple of 64: chunks own whole validity words
     constexpr uint32_t kCtrlWords = 4 + kChunkEdges / 32; // [0] next edge, [4..] validity bits of the chunk
 
+    // SEG (vmv_validate_motion_batch_multi): one chunk, the one from edge seg_begin, and only the edges of the segment
+    // [seg_lo, seg_hi) in it; the others are dead on arrival, and a word shared with another segment is ANDed in.
+    __device__ __forceinline__ uint32_t segment_mask32(const size_t first, const uint32_t lo, const uint32_t hi)
+    {
+        const size_t a = lo > first ? lo - first : 0u, b = hi > first ? (hi - first < 32u ? hi - first : 32u) : 0u;
+        if (b <= a) return 0u;
+        return (b == 32u ? ~0u : (1u << b) - 1u) & ~((1u << a) - 1u);
+    }
+
+    template <bool SEG = false>
     __device__ __forceinline__ void motion_body(const EnvView &E, lds_ptr slab, lds_u32 *ctrl,
                                                 const float *__restrict__ start, const float *__restrict__ goal,
-                                                const size_t n, uint32_t *__restrict__ bits32, const uint32_t chunk)
+                                                const size_t n, uint32_t *__restrict__ bits32, const uint32_t chunk,
+                                                const uint32_t seg_lo = 0u, const uint32_t seg_hi = 0u,
+                                                const uint32_t seg_begin = 0u)
     {
         // chunk: edges per workgroup pass, a multiple of 64 and at most kChunkEdges (the launcher shrinks it for small
         // batches so that the grid still fills the chip: a 2,000-edge planner batch is 32 workgroups at 64, 4 at 512)
@@ -492,7 +504,8 @@ namespace VMV_ROBOT_NS
         lds_u32 *chunk_bits = ctrl + 4;
         const float percent = (float) (k + 1) / 8.0f;  // validate.hh:12-21
 
-        for (size_t begin = (size_t) blockIdx.x * chunk; begin < n; begin += (size_t) gridDim.x * chunk)
+        for (size_t begin = SEG ? (size_t) seg_begin : (size_t) blockIdx.x * chunk; begin < n;
+             begin += SEG ? n : (size_t) gridDim.x * chunk)  // (SEG: one chunk)
         {
             const size_t end = (begin + chunk < n) ? begin + chunk : n;
             if (tid < chunk / 32)
@@ -501,6 +514,7 @@ namespace VMV_ROBOT_NS
                 uint32_t in = (w < n_words) ? bits32[w] : 0u;
                 const size_t first_edge = w * 32;  // bits at or beyond n are never continued (and come back as 0)
                 if (first_edge + 32 > n) in &= (first_edge < n) ? ((1u << (uint32_t) (n - first_edge)) - 1u) : 0u;
+                if constexpr (SEG) in &= segment_mask32(first_edge, seg_lo, seg_hi);
                 chunk_bits[tid] = in;
             }
             if (tid == 0) ctrl[0] = (uint32_t) (begin + kGroups);
@@ -594,7 +608,18 @@ namespace VMV_ROBOT_NS
             if (tid < chunk / 32)
             {
                 const size_t w = begin / 32 + tid;
-                if (w < n_words) bits32[w] = chunk_bits[tid];
+                if constexpr (SEG)
+                {
+                    const uint32_t mask = segment_mask32(w * 32, seg_lo, seg_hi);
+                    if (mask == ~0u)
+                        bits32[w] = chunk_bits[tid];
+                    else if (mask != 0u)  // (shared with another segment)
+                        atomicAnd(bits32 + w, chunk_bits[tid] | ~mask);
+                }
+                else
+                {
+                    if (w < n_words) bits32[w] = chunk_bits[tid];
+                }
             }
             __syncthreads();
         }
@@ -633,25 +658,33 @@ namespace VMV_ROBOT_NS
         return lo;
     }
 
-    template <int PART, int V = kEnvFull>  // 0 environment half, 1 self-collision half, 3 both halves along one FK (fkcc_fused)
+    // SEG (vmv_validate_motion_batch_multi, environment half): the workgroup's tasks are [t_begin, tasks) of the segment
+    // [seg_lo, seg_hi), strided by its waves.  First pass: t_begin is a multiple of 32, the edges outside the segment are
+    // out of range, the launcher zeroed the validity words, and a byte whose 32-bit word holds edges of another segment
+    // is ORed in.  Later pass: the task's edge is searched among the segment's edges only.
+    template <int PART, int V = kEnvFull, bool SEG = false>  // 0 environment half, 1 self-collision half, 3 both halves along one FK (fkcc_fused)
     __device__ __forceinline__ void rake_task_body(const EnvView &E, lds_ptr slab, const float *__restrict__ start,
                                                    const float *__restrict__ goal, const uint32_t n, uint8_t *__restrict__ bits8,
                                                    uint32_t *__restrict__ steps_out, const uint32_t *__restrict__ excl,
-                                                   const uint32_t tasks, const uint32_t lo_i, const bool first)
+                                                   const uint32_t tasks, const uint32_t lo_i, const bool first,
+                                                   const uint32_t seg_lo = 0u, const uint32_t seg_hi = 0u,
+                                                   const uint32_t t_begin = 0u)
     {
         constexpr bool SELF = PART == 1;  // continues the edges the environment half left valid (PART 3 writes, like PART 0)
         const uint32_t lane = __lane_id();
         const uint32_t k = lane & 7u, g = lane >> 3;
         const float percent = (float) (k + 1u) / 8.0f;  // validate.hh:12-21
-        const uint32_t stride = gridDim.x * (uint32_t) (kWavesPerBlock * 8);
-        for (uint32_t t0 = (blockIdx.x * (uint32_t) kWavesPerBlock + threadIdx.x / kWave) * 8u; t0 < tasks; t0 += stride)
+        const uint32_t stride = SEG ? (uint32_t) (kWavesPerBlock * 8) : gridDim.x * (uint32_t) (kWavesPerBlock * 8);
+        const uint32_t t_first = SEG ? t_begin + (threadIdx.x / kWave) * 8u
+                                     : (blockIdx.x * (uint32_t) kWavesPerBlock + threadIdx.x / kWave) * 8u;
+        for (uint32_t t0 = t_first; t0 < tasks; t0 += stride)
         {
             const uint32_t t = t0 + g;
             uint32_t e = t, i = 0u, byte = 0u;
             bool work;
             if (first)
             {
-                work = e < n;
+                work = SEG ? (e >= seg_lo && e < seg_hi) : e < n;
                 if constexpr (SELF)
                 {
                     byte = bits8[t0 >> 3];
@@ -661,13 +694,16 @@ namespace VMV_ROBOT_NS
             else
             {
                 work = t < tasks;
-                e = find_task_edge(excl, n, work ? t : 0u);
+                if constexpr (SEG)
+                    e = seg_lo + find_task_edge(excl + seg_lo, seg_hi - seg_lo, work ? t : 0u);
+                else
+                    e = find_task_edge(excl, n, work ? t : 0u);
                 i = lo_i + (t - excl[e]);
                 work = work && ((bits8[e >> 3] >> (e & 7u)) & 1u) != 0u;  // already invalid: nothing to add
             }
             if (!wave_any(work))
             {
-                if (first && !SELF && lane == 0u) bits8[t0 >> 3] = 0u;
+                if (first && !SELF && !SEG && lane == 0u) bits8[t0 >> 3] = 0u;
                 continue;
             }
             // the edge (validate.hh:31-41, :50)
@@ -691,6 +727,8 @@ namespace VMV_ROBOT_NS
             const float distance = l2_norm<R::kDim>(v);
             const uint32_t st = (uint32_t) fmaxf(ceilf(distance / 8.0f * (float) R::kResolution), 1.F);
             const float denom = (float) (8u * st);
+            if constexpr (SEG && !SELF)  // (stored before the collision test: st is not kept alive across it)
+                if (first && k == 0u && work) steps_out[e] = st;
 #pragma unroll
             for (int j = 0; j < R::kDim; ++j)
             {
@@ -728,6 +766,19 @@ namespace VMV_ROBOT_NS
                 if constexpr (SELF)
                 {
                     if (lane == 0u && out != byte) bits8[t0 >> 3] = (uint8_t) out;
+                }
+                else if constexpr (SEG)
+                {
+                    const uint32_t d0 = t0 & ~31u;
+                    if (lane == 0u)
+                    {
+                        if (d0 < seg_lo || (d0 + 32u > seg_hi && seg_hi < n))
+                        {
+                            if (out != 0u) atomicOr(reinterpret_cast<uint32_t *>(bits8) + (t0 >> 5), out << (t0 & 24u));
+                        }
+                        else
+                            bits8[t0 >> 3] = (uint8_t) out;
+                    }
                 }
                 else
                 {
@@ -805,6 +856,77 @@ namespace VMV_ROBOT_NS
         lds_ptr wave_slab = (lds_ptr) smem + head + wave * slab_floats();
         lds_u32 *ctrl = (lds_u32 *) ((lds_ptr) smem + head + kWavesPerBlock * slab_floats());
         motion_body(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk);
+    }
+
+    // vmv_validate_motion_batch_multi: the segmented twins of rake_tasks_env_kernel and validate_motion_attach_kernel
+    // (the bodies' SEG forms); every workgroup stages exactly one environment.
+    //   first pass: workgroup b takes tiles[b] = {segment, 32-bit validity word}: rake 0 of the segment's edges in that
+    //               word, one validity byte per wave;
+    //   later pass: workgroup b takes tile b of its class (launch_edge_multi_tiles): tile b - starts[j] of the segment
+    //               entries[j], starts[j] <= b < starts[j + 1], i.e. `*chunk` consecutive tasks of that one segment.  The
+    //               grid is sized for the most tiles there can be; the workgroups beyond the last one leave before they
+    //               stage anything.  (One tile per workgroup, no loop over tiles: see validate_env_multi_kernel.)
+    // The pass is a template argument, so that the later pass's tile search and segment bounds do not share one register
+    // budget with pass 0's body (with a runtime `first`, up to 4 more VGPRs spilled than in rake_tasks_env_kernel).
+    template <int V, bool FIRST>
+    __global__ __launch_bounds__(kBlock, (V == kEnvFull || V == kEnvClouds) ? VMV_MOTION_ENV_BLOCKS : VMV_MOTION_PRIMS_BLOCKS) void rake_tasks_env_multi_kernel(
+        const MultiSeg *__restrict__ segs, const MultiTile *__restrict__ tiles, const uint32_t *__restrict__ entries,
+        const uint32_t m, const uint32_t *__restrict__ starts, const uint32_t *__restrict__ chunk,
+        const float *__restrict__ start, const float *__restrict__ goal, const uint32_t n, uint8_t *__restrict__ bits8,
+        uint32_t *__restrict__ steps_out, const uint32_t *__restrict__ excl, const uint32_t *__restrict__ total)
+    {
+        uint32_t seg, t_begin, t_end;
+        if constexpr (FIRST)
+        {
+            const MultiTile tile = tiles[blockIdx.x];
+            seg = tile.seg, t_begin = tile.word * 32u;
+            const uint32_t top = (segs[seg].hi + 7u) & ~7u;  // (the waves whose byte lies past the segment have nothing to do)
+            t_end = top - t_begin < 32u ? top : t_begin + 32u;
+        }
+        else
+        {
+            const uint32_t b = blockIdx.x;
+            if (b >= starts[m]) return;  // (before the environment is staged)
+            uint32_t lo = 0u, hi = m;    // starts[lo] <= b < starts[hi]: 64 probes per round, one per lane
+            while (hi - lo > 1u)
+            {
+                const uint32_t p = lo + (uint32_t) (((uint64_t) (__lane_id() + 1u) * (hi - lo)) / (uint64_t) (kWave + 1));
+                const uint32_t below = (uint32_t) __popcll(__ballot(starts[p] <= b));  // a prefix of the lanes
+                const uint32_t p_lo = (uint32_t) __shfl((int) p, (int) (below > 0u ? below - 1u : 0u));
+                const uint32_t p_hi = (uint32_t) __shfl((int) p, (int) (below < (uint32_t) kWave ? below : kWave - 1));
+                lo = (uint32_t) __builtin_amdgcn_readfirstlane((int) (below > 0u ? p_lo : lo));
+                hi = (uint32_t) __builtin_amdgcn_readfirstlane((int) (below < (uint32_t) kWave ? p_hi : hi));
+            }
+            seg = entries[lo];
+            const uint32_t s_lo = segs[seg].lo, s_hi = segs[seg].hi, size = *chunk;
+            const uint32_t end = s_hi < n ? excl[s_hi] : *total;
+            t_begin = excl[s_lo] + (b - starts[lo]) * size;
+            t_end = end - t_begin < size ? end : t_begin + size;
+        }
+        const MultiSeg S = segs[seg];
+        extern __shared__ __align__(16) float smem[];
+        const EnvView E = stage_environment(S.env, S.tests_in_lds, smem);
+        lds_ptr wave_slab = (lds_ptr) smem + S.slab + (threadIdx.x / kWave) * slab_floats();
+        rake_task_body<0, V, true>(E, wave_slab + __lane_id(), start, goal, n, bits8, steps_out, excl, t_end, FIRST ? 0u : 1u,
+                                   FIRST, S.lo, S.hi, t_begin);
+    }
+
+    // workgroup b walks the edges of segment tiles[b].seg in the chunk that starts at edge 32 * tiles[b].word
+    __global__ __launch_bounds__(kBlock, 2) void validate_motion_attach_multi_kernel(const MultiSeg *__restrict__ segs,
+                                                                                    const MultiTile *__restrict__ tiles,
+                                                                                    const float *__restrict__ start,
+                                                                                    const float *__restrict__ goal,
+                                                                                    const uint32_t n, uint32_t *__restrict__ bits,
+                                                                                    const uint32_t chunk)
+    {
+        extern __shared__ __align__(16) float smem[];
+        const MultiTile tile = tiles[blockIdx.x];
+        const MultiSeg S = segs[tile.seg];
+        const EnvView E = stage_environment(S.env, S.tests_in_lds, smem);
+        const uint32_t wave = threadIdx.x / kWave;
+        lds_ptr wave_slab = (lds_ptr) smem + S.slab + wave * slab_floats();
+        lds_u32 *ctrl = (lds_u32 *) ((lds_ptr) smem + S.slab + kWavesPerBlock * slab_floats());
+        motion_body<true>(E, wave_slab + __lane_id(), ctrl, start, goal, n, bits, chunk, S.lo, S.hi, tile.word * 32u);
     }
 
     __global__ __launch_bounds__(kBlock) void fk_batch_kernel(const float *__restrict__ q, const size_t n,
@@ -1158,6 +1280,162 @@ namespace VMV_ROBOT_NS
             return VMV_OK;
         }
 
+        // vmv_validate_motion_batch_multi: launch_rake_tasks (two-kernel form) made segmented, slice by slice (segments
+        // clipped at the slice's ends).  Per slice: the validity words zeroed; pass 0 of the environment half, one launch
+        // per variant class present (each segment runs the class launch_rake_tasks picks for its environment alone), one
+        // workgroup per 32-edge validity word of a segment; the self-collision half and the scan once over the slice (they
+        // do not depend on the environment); the later pass's tiles from the scan, on the device; the later pass of the
+        // environment half per class; the self-collision half's later pass; the attachment walk over the segments whose
+        // environment has one.  Table: [segments | pass-0 tiles per class | later-pass entries per class | attachment
+        // tiles] written by the host, then [starts | chunk] written by launch_edge_multi_tiles.
+        int launch_validate_motion_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_a,
+                                         const float *d_b, uint64_t *d_bits, hipStream_t stream)
+        {
+            constexpr int kClasses = kEdgeMultiClasses;                    // kEnvZOnly, kEnvPrims, kEnvFull, kEnvClouds
+            constexpr uint32_t per_block = (uint32_t) (kWavesPerBlock * 8);  // tasks per workgroup pass
+            const size_t n_all = offsets[n_envs];
+            if (n_all == 0) return VMV_OK;
+            auto class_of = [](const EnvLaunch &e)
+            {
+                if (prims_only(e)) return (e.host.n_capsule + e.host.n_cuboid == 0) ? 0 : 1;
+                return clouds_only(e) ? 3 : 2;
+            };
+            std::vector<uint32_t> tests_in_lds(n_envs), bytes(n_envs);  // every plan before anything is launched
+            size_t attach_edges = 0;
+            for (size_t k = 0; k < n_envs; ++k)
+                if (offsets[k] < offsets[k + 1])
+                {
+                    if (int rc = plan_lds(*envs[k], tests_in_lds[k], bytes[k]); rc != VMV_OK) return rc;
+                    if (envs[k]->host.n_attach > 0) attach_edges += offsets[k + 1] - offsets[k];
+                }
+            uint32_t chunk = kChunkEdges;  // the attachment walk's, sized as launch_validate_motion sizes it
+            while (chunk > 64u && (attach_edges + chunk - 1) / chunk < 2048u) chunk /= 2u;
+            using EnvKernel = decltype(&rake_tasks_env_multi_kernel<kEnvFull, true>);
+            const EnvKernel first_kernels[kClasses] = {
+                rake_tasks_env_multi_kernel<kEnvZOnly, true>, rake_tasks_env_multi_kernel<kEnvPrims, true>,
+                rake_tasks_env_multi_kernel<kEnvFull, true>, rake_tasks_env_multi_kernel<kEnvClouds, true>};
+            const EnvKernel later_kernels[kClasses] = {
+                rake_tasks_env_multi_kernel<kEnvZOnly, false>, rake_tasks_env_multi_kernel<kEnvPrims, false>,
+                rake_tasks_env_multi_kernel<kEnvFull, false>, rake_tasks_env_multi_kernel<kEnvClouds, false>};
+            size_t k0 = 0;
+            for (size_t base = 0; base < n_all; base += kEdgeSliceEdges)  // (slices are multiples of 64 edges)
+            {
+                const size_t top = std::min(base + (size_t) kEdgeSliceEdges, n_all);
+                const uint32_t n = (uint32_t) (top - base);
+                while (offsets[k0 + 1] <= base) ++k0;
+                std::vector<MultiSeg> segs;
+                std::vector<uint8_t> cls, att;
+                size_t n_tiles[kClasses] = {}, n_edges[kClasses] = {}, n_att = 0;
+                uint32_t shmem[kClasses] = {}, shmem_att = 0;
+                EdgeMultiPlan plan{};
+                for (size_t k = k0; k < n_envs && offsets[k] < top; ++k)
+                {
+                    const uint32_t lo = (uint32_t) (std::max(offsets[k], base) - base);
+                    const uint32_t hi = (uint32_t) (std::min(offsets[k + 1], top) - base);
+                    if (lo >= hi) continue;
+                    const EnvLaunch &e = *envs[k];
+                    const int c = class_of(e);
+                    segs.push_back(MultiSeg{e.d_env, lo, hi, tests_in_lds[k],
+                                            ((e.host.n_floats + tests_in_lds[k] + 3u) & ~3u) + kEnvRadiiFloats});
+                    cls.push_back((uint8_t) c);
+                    att.push_back(e.host.n_attach > 0);
+                    n_tiles[c] += (hi - 1u) / 32u - lo / 32u + 1u;
+                    n_edges[c] += hi - lo;
+                    plan.m[c] += 1u;
+                    shmem[c] = std::max(shmem[c], bytes[k]);
+                    if (e.host.n_attach > 0)
+                    {
+                        n_att += (hi - 1u) / chunk - lo / chunk + 1u;
+                        shmem_att = std::max(shmem_att, bytes[k]);
+                    }
+                }
+                size_t at0[kClasses], total0 = 0;
+                uint32_t m_all = 0;
+                for (int c = 0; c < kClasses; ++c)
+                {
+                    at0[c] = total0, total0 += n_tiles[c];
+                    plan.at[c] = m_all, m_all += plan.m[c];
+                    // the later pass's grid launch_rake_tasks would take for the class's edges; the tiles fill it
+                    const size_t guess = n_edges[c] * 8u < 8192u ? 8192u : n_edges[c] * 8u;
+                    plan.grid[c] = (uint32_t) std::min(grid_for(guess, per_block), 8192);
+                }
+                const size_t o_tiles = (segs.size() * sizeof(MultiSeg) + 15u) & ~size_t{15};
+                const size_t o_entries = o_tiles + total0 * sizeof(MultiTile);
+                const size_t o_att = o_entries + (((size_t) m_all * sizeof(uint32_t) + 7u) & ~size_t{7});
+                const size_t host_bytes = o_att + n_att * sizeof(MultiTile);
+                const size_t o_starts = (host_bytes + 15u) & ~size_t{15};
+                const size_t o_chunk = o_starts + ((((size_t) m_all + kClasses) * sizeof(uint32_t) + 15u) & ~size_t{15});
+                MultiTableLease lease;
+                if (int rc = lease.acquire(stream, o_chunk + kClasses * sizeof(uint32_t)); rc != VMV_OK) return rc;
+                char *h = static_cast<char *>(lease.host);
+                std::memcpy(h, segs.data(), segs.size() * sizeof(MultiSeg));
+                MultiTile *tiles = reinterpret_cast<MultiTile *>(h + o_tiles), *att_tiles = reinterpret_cast<MultiTile *>(h + o_att);
+                uint32_t *entries = reinterpret_cast<uint32_t *>(h + o_entries);
+                size_t fill[kClasses], fill_m[kClasses], fill_att = 0;
+                for (int c = 0; c < kClasses; ++c) fill[c] = at0[c], fill_m[c] = plan.at[c];
+                for (uint32_t s = 0; s < (uint32_t) segs.size(); ++s)
+                {
+                    const uint32_t lo = segs[s].lo, hi = segs[s].hi;
+                    for (uint32_t w = lo / 32u; w <= (hi - 1u) / 32u; ++w) tiles[fill[cls[s]]++] = MultiTile{s, w};
+                    entries[fill_m[cls[s]]++] = s;
+                    if (att[s])
+                        for (uint32_t c0 = lo / chunk; c0 <= (hi - 1u) / chunk; ++c0) att_tiles[fill_att++] = MultiTile{s, c0 * (chunk / 32u)};
+                }
+                char *dv = static_cast<char *>(lease.dev);
+                const MultiSeg *d_segs = reinterpret_cast<const MultiSeg *>(dv);
+                const MultiTile *d_tiles = reinterpret_cast<const MultiTile *>(dv + o_tiles);
+                const MultiTile *d_att = reinterpret_cast<const MultiTile *>(dv + o_att);
+                const uint32_t *d_entries = reinterpret_cast<const uint32_t *>(dv + o_entries);
+                uint32_t *d_starts = reinterpret_cast<uint32_t *>(dv + o_starts), *d_chunk = reinterpret_cast<uint32_t *>(dv + o_chunk);
+                EdgeScratchLease scratch;  // (after the tables: the two pools are always taken in this order)
+                if (int rc = scratch.acquire(stream, n); rc != VMV_OK) return rc;
+                const EdgeScratch &S = scratch.s;
+                const float *a = d_a + base * R::kDim, *b = d_b + base * R::kDim;
+                uint64_t *words = d_bits + base / 64;
+                uint8_t *bits8 = reinterpret_cast<uint8_t *>(words);
+                VMV_HIP_TU(hipMemsetAsync(words, 0, (n + 63u) / 64u * sizeof(uint64_t), stream));
+                if (int rc = lease.upload(stream, host_bytes); rc != VMV_OK) return rc;
+                for (int c = 0; c < kClasses; ++c)
+                    if (n_tiles[c] > 0 && shmem[c] > 64u * 1024u)
+                        for (const EnvKernel kernel : {first_kernels[c], later_kernels[c]})
+                            VMV_HIP_TU(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                           (int) shmem[c]));
+                for (int c = 0; c < kClasses; ++c)  // pass 0: rake 0 of every edge
+                    if (n_tiles[c] > 0)
+                        hipLaunchKernelGGL(first_kernels[c], dim3((uint32_t) n_tiles[c]), dim3(kBlock), shmem[c], stream, d_segs,
+                                           d_tiles + at0[c], (const uint32_t *) nullptr, 0u, (const uint32_t *) nullptr,
+                                           (const uint32_t *) nullptr, a, b, n, bits8, S.steps, (const uint32_t *) nullptr,
+                                           (const uint32_t *) nullptr);
+                hipLaunchKernelGGL(rake_tasks_self_kernel, dim3(grid_for(n, per_block)), dim3(kBlock), 0, stream, a, b, n, bits8,
+                                   (const uint32_t *) nullptr, (const uint32_t *) nullptr, 0u, 1u);
+                VMV_HIP_TU(hipGetLastError());
+                if (int rc = launch_edge_pass_scan(S, words, n, 1u, 0xffffffffu, 0u, stream); rc != VMV_OK) return rc;
+                if (int rc = launch_edge_multi_tiles(S, d_segs, d_entries, plan, n, d_starts, d_chunk, stream); rc != VMV_OK)
+                    return rc;
+                for (int c = 0; c < kClasses; ++c)  // the later pass: rakes 1 and up of the edges still valid
+                    if (plan.m[c] > 0)
+                        hipLaunchKernelGGL(later_kernels[c], dim3(plan.grid[c] + plan.m[c]), dim3(kBlock), shmem[c], stream, d_segs,
+                                           (const MultiTile *) nullptr, d_entries + plan.at[c], plan.m[c],
+                                           (const uint32_t *) (d_starts + plan.at[c] + c), (const uint32_t *) (d_chunk + c), a, b,
+                                           n, bits8, (uint32_t *) nullptr, (const uint32_t *) S.excl, (const uint32_t *) S.total);
+                const size_t guess = (size_t) n * 8u < 8192u ? 8192u : (size_t) n * 8u;
+                const int later_grid = grid_for(guess, per_block) < 8192 ? grid_for(guess, per_block) : 8192;
+                hipLaunchKernelGGL(rake_tasks_self_kernel, dim3(later_grid), dim3(kBlock), 0, stream, a, b, n, bits8,
+                                   (const uint32_t *) S.excl, (const uint32_t *) S.total, 1u, 0u);
+                VMV_HIP_TU(hipGetLastError());
+                if (n_att > 0)  // the attachment part continues the edges still valid
+                {
+                    if (shmem_att > 64u * 1024u)
+                        VMV_HIP_TU(hipFuncSetAttribute((const void *) validate_motion_attach_multi_kernel,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int) shmem_att));
+                    hipLaunchKernelGGL(validate_motion_attach_multi_kernel, dim3((uint32_t) n_att), dim3(kBlock), shmem_att, stream,
+                                       d_segs, d_att, a, b, n, reinterpret_cast<uint32_t *>(words), chunk);
+                    VMV_HIP_TU(hipGetLastError());
+                }
+            }
+            return VMV_OK;
+        }
+
         int launch_prepare(const EnvLaunch &env, EnvDev *d_env)
         {
             if (R::kNStaticLinks == 0) return VMV_OK;  // static_hit stays 0
@@ -1224,6 +1502,7 @@ namespace VMV_ROBOT_NS
 #if !defined(__HIP_DEVICE_COMPILE__)
     extern const RobotLaunchers VMV_ROBOT_LAUNCH = {VMV_ROBOT_NS::launch_validate, VMV_ROBOT_NS::launch_validate_multi,
                                                     VMV_ROBOT_NS::launch_validate_motion,
+                                                    VMV_ROBOT_NS::launch_validate_motion_multi,
                                                     VMV_ROBOT_NS::launch_fk, VMV_ROBOT_NS::launch_prepare,
                                                     VMV_ROBOT_NS::launch_eefk, VMV_ROBOT_NS::launch_contacts,
                                                     VMV_ROBOT_NS::R::kNSelfPairs};

@@ -197,6 +197,21 @@ def validate_path(robot, path, environment) -> bool:
     return bool(robot.validate_motion_batch(p[:-1], p[1:], environment).all())
 
 
+def validate_paths(robot, paths, environments) -> np.ndarray:
+    """validate_path for many paths, path p in environments[p] (None = the empty environment) -> bool[len(paths)]: every
+    path's consecutive pairs in ONE validate_motion_batch_multi call.  A path of fewer than 2 waypoints is valid."""
+    dim = robot.dimension()
+    pts = [np.asarray(p, np.float32).reshape(-1, dim) for p in paths]
+    counts = [max(len(p) - 1, 0) for p in pts]
+    empty = np.zeros((0, dim), np.float32)
+    ok = robot.validate_motion_batch_multi(np.concatenate([p[:-1] for p in pts] + [empty]),
+                                           np.concatenate([p[1:] for p in pts] + [empty]), environments, counts)
+    # path p is valid iff its segment holds no invalid edge (prefix counts: empty segments need no special case)
+    bad = np.concatenate([[0], np.cumsum(~ok)])
+    ends = np.concatenate([[0], np.cumsum(counts)])
+    return bad[ends[1:]] == bad[ends[:-1]]
+
+
 @dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
