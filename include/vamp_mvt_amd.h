@@ -190,6 +190,27 @@ int vmv_validate_motion_batch_multi(int robot, const vmv_env *const *envs, const
 int vmv_validate_motion_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                          const float *start, const float *goal, uint64_t *bits);
 
+/* Builds the part of each environment that depends on the robot (broad-phase grids, reach certificates, static links)
+ * for all of them together, on the device.  After VMV_OK every later call with (envs[k], robot) finds it built; without
+ * this call the part is built on the first use of (environment, robot), one environment at a time on the host (the
+ * multi-environment validate calls build their not-yet-built environments this way, in one batch).  Both ways give the
+ * same part, bit for bit.  Checks before any work, device-free ones first: unknown robot; envs NULL with n_envs > 0 or
+ * a NULL handle (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment (VMV_ERR_NOT_FINALIZED); an environment
+ * finalized on another device than the current one (VMV_ERR_INVALID_ARGUMENT) — a call that fails a check prepares
+ * nothing.  n_envs == 0 is VMV_OK.  Repeated handles are allowed, parts already built are skipped.  Synchronous, like
+ * vmv_env_finalize, and thread safe against itself and against first uses on other threads (whoever comes second
+ * waits).  A failure is recorded per (environment, robot) and returned by every later use; the call returns the first
+ * non-OK status in envs order after preparing the others.  VMV_NO_GRID, VMV_NO_LINK_SKIP, VMV_GRID_CELLS and
+ * VMV_GRID_MIN_CELL mean what they mean on first use.  Device memory: one allocation per call, shared by the
+ * environments it prepared and freed by vmv_env_destroy of the last of them. */
+int vmv_env_prepare_multi(int robot, const vmv_env *const *envs, size_t n_envs);
+/* Inspection of the robot part (builds it as a first use would if it is not built yet).  Grid of one class:
+ * dims 0,0,0 = this environment runs without a grid; cells = uint32 [dims0][dims1][dims2][words]. */
+int vmv_env_grid_info(const vmv_env *env, int robot, int grid_class, uint32_t *dims3, float *origin3, float *inv_cell,
+                      uint32_t *words);
+int vmv_env_grid_cells(const vmv_env *env, int robot, int grid_class, uint32_t *out, size_t capacity, size_t *n);
+int vmv_env_robot_flags(const vmv_env *env, int robot, uint64_t *link_skip, uint32_t *static_hit);
+
 /* <robot>.debug(q, env) — robot_helper.hh:249-253 -> Robot::fkcc_debug: per fine sphere the environment objects it
  * collides with (sphere_environment_get_collisions, collision/validity.hh:161-256: the five sorted primitive lists with
  * their early break, then the heightfields; no point clouds), and the fine sphere pairs of the self-collision groups

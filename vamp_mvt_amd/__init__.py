@@ -421,6 +421,32 @@ class Environment:
               "vmv_spheres_in_collision_batch_host")
         return hits.astype(bool)
 
+    def robot_part(self, robot):
+        """What this environment holds for `robot` (a robot module or its name), built by `<robot>.prepare` or by the
+        first use: {"grids": four of {"dims", "origin", "inv_cell", "cells" uint32[dx][dy][dz][words]} or None (no
+        broad-phase grid), "link_skip", "static_hit"}.  Builds the part the first-use way if it is not built yet."""
+        rid = robot._id if isinstance(robot, _Robot) else lib.vmv_robot_id(str(robot).encode())
+        h = self.handle()
+        grids = []
+        for c in range(4):
+            dims, origin = np.zeros(3, np.uint32), np.zeros(3, np.float32)
+            inv_cell, words = ctypes.c_float(0), ctypes.c_uint32(0)
+            check(lib.vmv_env_grid_info(h, rid, c, dims.ctypes.data_as(_lib.c_u32_p), _fp(origin), ctypes.byref(inv_cell),
+                                        ctypes.byref(words)), "vmv_env_grid_info")
+            if not dims.any():
+                grids.append(None)
+                continue
+            cells = np.zeros((int(dims[0]), int(dims[1]), int(dims[2]), int(words.value)), np.uint32)
+            n = ctypes.c_size_t(0)
+            check(lib.vmv_env_grid_cells(h, rid, c, cells.ctypes.data_as(_lib.c_u32_p), cells.size, ctypes.byref(n)),
+                  "vmv_env_grid_cells")
+            if n.value != cells.size:
+                raise RuntimeError(f"grid {c}: {n.value} cell words, expected {cells.size}")
+            grids.append(dict(dims=dims, origin=origin, inv_cell=float(inv_cell.value), cells=cells))
+        skip, hit = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        check(lib.vmv_env_robot_flags(h, rid, ctypes.byref(skip), ctypes.byref(hit)), "vmv_env_robot_flags")
+        return dict(grids=grids, link_skip=int(skip.value), static_hit=int(hit.value))
+
     # -- inspection (host tables; no GPU needed) ----------------------------------------------------------------
     def host_tables(self):
         """Sorted primitive tables as the kernels see them (built without uploading)."""
@@ -607,6 +633,18 @@ class _Robot(types.ModuleType):
         check(lib.vmv_validate_batch_host(self._id, self._env(environment), _fp(q), n,
                                           bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_host")
         return unpack_bits(bits, n)
+
+    def prepare(self, environments):
+        """Builds what each environment holds for this robot (broad-phase grids, reach certificates, static links) for
+        all of them in one call, on the device, instead of one by one on their first use.  None = the empty
+        environment.  Changes no answer: the parts are the ones the first use would build, bit for bit."""
+        environments = list(environments)
+        for e in environments:
+            if e is not None and not isinstance(e, Environment):
+                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        check(lib.vmv_env_prepare_multi(self._id, handles, len(envs)), "vmv_env_prepare_multi")
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

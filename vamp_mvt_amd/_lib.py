@@ -116,6 +116,10 @@ def _load():
         "vmv_validate_motion_batch_host": (I, [I, V, c_float_p, c_float_p, S, c_u64_p]),
         "vmv_validate_motion_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V, V]),
         "vmv_validate_motion_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_float_p, c_u64_p]),
+        "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
+        "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
+        "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
+        "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),
         "vmv_release_staging": (I, []),
         "vmv_halton_configs": (I, [I, ctypes.c_uint64, V, S, V]),
         "vmv_time_validate_batch": (I, [I, V, V, S, V, I, V, c_float_p]),

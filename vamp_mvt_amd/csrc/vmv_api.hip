@@ -8,11 +8,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -280,11 +283,21 @@ struct vmv_env
     vmv::EnvDev base{};
     std::vector<vmv::GridPrim> grid_prims;
     uint32_t grid_words = 0;
-    std::once_flag robot_once[8];
-    std::mutex robot_mutex;  // serialises the lazy builds (they append to `allocations`)
+    // per robot: kRobotNone -> kRobotBuilding (claimed by one lazy build or one vmv_env_prepare_multi call, under
+    // robot_mutex) -> kRobotBuilt (launch[r], robot_status[r], robot_error[r] final; released with robot_cv)
+    std::atomic<int> robot_state[8] = {};
+    std::mutex robot_mutex;  // guards the state changes and `allocations` / `shared_allocations`
+    std::condition_variable robot_cv;
     int robot_status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::string robot_error[8];
     std::vector<void *> allocations;
+    std::vector<std::shared_ptr<void>> shared_allocations;  // device memory of a batch preparation, freed by its last holder
+};
+enum
+{
+    kRobotNone = 0,
+    kRobotBuilding = 1,
+    kRobotBuilt = 2
 };
 
 namespace
@@ -1014,18 +1027,245 @@ namespace
         return VMV_OK;
     }
 
+    int robot_result(const vmv_env *env, int r)  // of a built part
+    {
+        if (env->robot_status[r] != VMV_OK) g_last_error = env->robot_error[r];
+        return env->robot_status[r];
+    }
+
+    // the lazy path: the first caller builds on the host (holding robot_mutex, as builds of other robots for this
+    // environment append to the same lists), everybody else waits for whoever has claimed the part
     int ensure_robot(const vmv_env *cenv, int r)
     {
         vmv_env *env = const_cast<vmv_env *>(cenv);
-        std::call_once(env->robot_once[r],
-                       [&]()
-                       {
-                           std::lock_guard<std::mutex> lock(env->robot_mutex);
-                           env->robot_status[r] = build_robot_part(env, r);
-                           if (env->robot_status[r] != VMV_OK) env->robot_error[r] = g_last_error;
-                       });
-        if (env->robot_status[r] != VMV_OK) g_last_error = env->robot_error[r];
-        return env->robot_status[r];
+        if (env->robot_state[r].load(std::memory_order_acquire) != kRobotBuilt)
+        {
+            std::unique_lock<std::mutex> lock(env->robot_mutex);
+            env->robot_cv.wait(lock, [&]() { return env->robot_state[r].load(std::memory_order_relaxed) != kRobotBuilding; });
+            if (env->robot_state[r].load(std::memory_order_relaxed) == kRobotNone)
+            {
+                env->robot_state[r].store(kRobotBuilding, std::memory_order_relaxed);
+                env->robot_status[r] = build_robot_part(env, r);
+                if (env->robot_status[r] != VMV_OK) env->robot_error[r] = g_last_error;
+                env->robot_state[r].store(kRobotBuilt, std::memory_order_release);
+                env->robot_cv.notify_all();
+            }
+        }
+        return robot_result(env, r);
+    }
+
+    struct DeviceFree
+    {
+        void operator()(void *p) const { (void) hipFree(p); }
+    };
+
+    // The batch path (vmv_env_prepare_multi and the multi-environment validate calls): claims every environment of
+    // `envs` whose part for robot r nobody has built or claimed, builds those parts together on the device, and waits
+    // for the ones somebody else is building.  All environments are finalized on the current device.  Bit for bit what
+    // build_robot_part makes.  The EnvDev images go up once, complete but for link_skip and static_hit, which the
+    // reach and static-link kernels store into them in place.
+    int build_robot_parts(const vmv_env *const *cenvs, size_t n_envs, int r)
+    {
+        std::vector<vmv_env *> mine, theirs;
+        for (size_t k = 0; k < n_envs; ++k)
+        {
+            vmv_env *env = const_cast<vmv_env *>(cenvs[k]);
+            if (env->robot_state[r].load(std::memory_order_acquire) == kRobotBuilt) continue;
+            std::lock_guard<std::mutex> lock(env->robot_mutex);
+            const int st = env->robot_state[r].load(std::memory_order_relaxed);
+            if (st == kRobotNone)
+            {
+                env->robot_state[r].store(kRobotBuilding, std::memory_order_relaxed);
+                mine.push_back(env);
+            }
+            else if (st == kRobotBuilding && std::find(mine.begin(), mine.end(), env) == mine.end())
+                theirs.push_back(env);
+        }
+        const size_t n = mine.size();
+        std::vector<int> status(n, VMV_OK);
+        std::vector<vmv::EnvDev> images(n);
+        std::shared_ptr<void> keep;  // [EnvDev images | cell words]
+        vmv::EnvDev *d_images = nullptr;
+        void *d_tables = nullptr;
+        std::string error;
+        const int rc = [&]() -> int
+        {
+            if (n == 0) return VMV_OK;
+            const bool use_grid = std::getenv("VMV_NO_GRID") == nullptr, use_skip = std::getenv("VMV_NO_LINK_SKIP") == nullptr;
+            std::vector<vmv::PrepPrim> prims;
+            std::vector<vmv::PrepGridJob> grid_jobs;
+            std::vector<vmv::PrepReachJob> reach_jobs;
+            std::vector<size_t> reach_env;                           // the reach job's environment (index in `mine`)
+            std::vector<int> grid_class(n * vmv::kGridClasses, -1);  // (environment, class) -> grid job
+            size_t cell_words = 0;
+            for (size_t k = 0; k < n; ++k)
+            {
+                const vmv_env *env = mine[k];
+                images[k] = env->base;
+                images[k].link_skip = 0ull;
+                const bool grid = use_grid && !env->grid_prims.empty();
+                // (an environment without primitives is certified too: no link can touch it)
+                const bool reach = use_skip && env->base.masked_fine && kRobots[r].n_reach > 0 &&
+                                   env->base.n_capt + env->base.n_mvt + env->base.n_heightfield == 0;
+                if (!grid && !reach) continue;
+                if (env->grid_prims.size() > vmv::kPrepMaxPrims)
+                {
+                    g_last_error = "more primitives with candidate bits than four words hold";
+                    return VMV_ERR_CAPACITY;  // (finalize never makes such a list)
+                }
+                const uint32_t prim_lo = (uint32_t) prims.size();
+                for (const vmv::GridPrim &g : env->grid_prims)
+                {
+                    vmv::PrepPrim q{g.type, g.word, g.bit, {}};
+                    std::memcpy(q.p, g.p, sizeof(float) * (g.type == 0 ? 4 : g.type <= 2 ? 8 : 15));
+                    prims.push_back(q);
+                }
+                if (reach)
+                {
+                    reach_jobs.push_back(vmv::PrepReachJob{prim_lo, (uint32_t) env->grid_prims.size(), nullptr, (uint32_t) reach_env.size()});
+                    reach_env.push_back(k);
+                }
+                if (!grid) continue;
+                vmv::GridGeometry geo[vmv::kGridClasses];
+                bool ok = true;
+                for (int c = 0; c < vmv::kGridClasses && ok; ++c)
+                {
+                    if (c > 0 && kRobots[r].grid_radius[c] == kRobots[r].grid_radius[c - 1])
+                        geo[c] = geo[c - 1];
+                    else
+                        ok = vmv::grid_geometry(env->grid_prims, env->grid_words, (double) kRobots[r].grid_radius[c], geo[c]);
+                }
+                if (!ok) continue;
+                for (int c = 0; c < vmv::kGridClasses; ++c)
+                {
+                    if (c > 0 && kRobots[r].grid_radius[c] == kRobots[r].grid_radius[c - 1])
+                    {
+                        grid_class[k * vmv::kGridClasses + c] = grid_class[k * vmv::kGridClasses + c - 1];
+                        continue;
+                    }
+                    vmv::PrepGridJob j{};
+                    j.prim_lo = prim_lo, j.n_prims = (uint32_t) env->grid_prims.size();
+                    for (int a = 0; a < 3; ++a) j.dims[a] = geo[c].dims[a], j.origin[a] = geo[c].origin[a];
+                    j.words = env->grid_words;
+                    j.hf = geo[c].hf, j.half_diag = geo[c].half_diag, j.R = (double) kRobots[r].grid_radius[c];
+                    j.cell_lo = cell_words;
+                    cell_words += (size_t) j.dims[0] * j.dims[1] * j.dims[2] * j.words;
+                    grid_class[k * vmv::kGridClasses + c] = (int) grid_jobs.size();
+                    grid_jobs.push_back(j);
+                }
+                for (int c = 0; c < vmv::kGridClasses; ++c)
+                {
+                    vmv::GridDev &g = images[k].grid[c];
+                    for (int a = 0; a < 3; ++a) g.dims[a] = geo[c].dims[a], g.origin[a] = geo[c].origin[a];
+                    g.inv_cell = geo[c].inv_cell;
+                }
+                images[k].grid_words = env->grid_words;
+            }
+            // the allocation the environments keep: their images, then the cell words
+            const size_t image_bytes = (n * sizeof(vmv::EnvDev) + 255) & ~size_t{255};
+            void *d_keep = nullptr;
+            VMV_HIP(hipMalloc(&d_keep, image_bytes + std::max<size_t>(cell_words, 4) * sizeof(uint32_t)));
+            keep = std::shared_ptr<void>(d_keep, DeviceFree{});
+            d_images = static_cast<vmv::EnvDev *>(d_keep);
+            uint32_t *d_cells = reinterpret_cast<uint32_t *>(static_cast<char *>(d_keep) + image_bytes);
+            for (size_t k = 0; k < n; ++k)
+                for (int c = 0; c < vmv::kGridClasses; ++c)
+                    if (const int j = grid_class[k * vmv::kGridClasses + c]; j >= 0)
+                        images[k].grid[c].cells = d_cells + grid_jobs[(size_t) j].cell_lo;
+            for (size_t i = 0; i < reach_jobs.size(); ++i) reach_jobs[i].image = d_images + reach_env[i];
+            VMV_HIP(hipMemcpy(d_images, images.data(), n * sizeof(vmv::EnvDev), hipMemcpyHostToDevice));
+            // the tables of this call: primitives, jobs, the robot's reach links and samples, the certificates' answers
+            std::vector<vmv::PrepReachLink> links;
+            std::vector<float> samples;
+            for (int k = 0; k < kRobots[r].n_reach && !reach_jobs.empty(); ++k)
+            {
+                const vmv_link_reach &lr = kRobots[r].reach[k];
+                if (lr.n <= 0 || lr.group < 0 || lr.group >= 64) continue;
+                links.push_back(vmv::PrepReachLink{lr.group, (uint32_t) (samples.size() / 3), (uint32_t) lr.n,
+                                                   (double) lr.radius + (double) lr.slack + 1e-3});
+                samples.insert(samples.end(), &lr.samples[0][0], &lr.samples[0][0] + 3 * (size_t) lr.n);
+            }
+            std::vector<unsigned long long> skip(reach_jobs.size(), 0ull);
+            if (!grid_jobs.empty() || !reach_jobs.empty())
+            {
+                size_t at = 0;
+                auto place = [&](size_t bytes)
+                {
+                    const size_t o = at;
+                    at += (bytes + 255) & ~size_t{255};
+                    return o;
+                };
+                const size_t o_prims = place(prims.size() * sizeof(vmv::PrepPrim)), o_grid = place(grid_jobs.size() * sizeof(vmv::PrepGridJob)),
+                             o_reach = place(reach_jobs.size() * sizeof(vmv::PrepReachJob)), o_links = place(links.size() * sizeof(vmv::PrepReachLink)),
+                             o_samples = place(samples.size() * sizeof(float)), o_skip = place(skip.size() * sizeof(unsigned long long));
+                std::vector<char> host(o_skip);
+                std::memcpy(host.data() + o_prims, prims.data(), prims.size() * sizeof(vmv::PrepPrim));
+                std::memcpy(host.data() + o_grid, grid_jobs.data(), grid_jobs.size() * sizeof(vmv::PrepGridJob));
+                std::memcpy(host.data() + o_reach, reach_jobs.data(), reach_jobs.size() * sizeof(vmv::PrepReachJob));
+                std::memcpy(host.data() + o_links, links.data(), links.size() * sizeof(vmv::PrepReachLink));
+                std::memcpy(host.data() + o_samples, samples.data(), samples.size() * sizeof(float));
+                VMV_HIP(hipMalloc(&d_tables, std::max<size_t>(at, 256)));
+                char *t = static_cast<char *>(d_tables);
+                if (!host.empty()) VMV_HIP(hipMemcpy(t, host.data(), host.size(), hipMemcpyHostToDevice));
+                const vmv::PrepPrim *d_prims = reinterpret_cast<const vmv::PrepPrim *>(t + o_prims);
+                if (!grid_jobs.empty())
+                    if (int rc = vmv::launch_grid_fill(d_prims, reinterpret_cast<const vmv::PrepGridJob *>(t + o_grid), grid_jobs.data(),
+                                                       grid_jobs.size(), d_cells, nullptr);
+                        rc != VMV_OK)
+                        return rc;
+                if (!reach_jobs.empty() && !links.empty())
+                {
+                    unsigned long long *d_skip = reinterpret_cast<unsigned long long *>(t + o_skip);
+                    if (int rc = vmv::launch_reach(d_prims, reinterpret_cast<const vmv::PrepReachJob *>(t + o_reach), reach_jobs.size(),
+                                                   reinterpret_cast<const vmv::PrepReachLink *>(t + o_links), (uint32_t) links.size(),
+                                                   reinterpret_cast<const float *>(t + o_samples), d_skip, nullptr);
+                        rc != VMV_OK)
+                        return rc;
+                    VMV_HIP(hipMemcpy(skip.data(), d_skip, skip.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+                    for (size_t i = 0; i < skip.size(); ++i) images[reach_env[i]].link_skip = skip[i];
+                }
+            }
+            // static links (after the grids and certificates on the same stream: the kernel reads both)
+            std::vector<vmv::EnvLaunch> launch(n);
+            std::vector<const vmv::EnvLaunch *> launch_p(n);
+            std::vector<vmv::EnvDev *> image_p(n);
+            for (size_t k = 0; k < n; ++k)
+            {
+                launch[k].d_env = d_images + k, launch[k].host = images[k];
+                launch_p[k] = &launch[k], image_p[k] = d_images + k;
+            }
+            if (int rc = kLaunchers[r]->prepare_multi(launch_p.data(), image_p.data(), n, status.data()); rc != VMV_OK) return rc;
+            VMV_HIP(hipDeviceSynchronize());
+            return VMV_OK;
+        }();
+        if (rc != VMV_OK) error = g_last_error;
+        if (d_tables)
+        {
+            (void) hipDeviceSynchronize();  // (a failed call may have kernels in flight that read the tables)
+            (void) hipFree(d_tables);
+        }
+        for (size_t k = 0; k < n; ++k)
+        {
+            vmv_env *env = mine[k];
+            std::lock_guard<std::mutex> lock(env->robot_mutex);
+            const int st = rc != VMV_OK ? rc : status[k];
+            env->launch[r].host = images[k];
+            env->launch[r].d_env = d_images ? d_images + k : nullptr;
+            if (keep) env->shared_allocations.push_back(keep);
+            env->robot_status[r] = st;
+            if (st != VMV_OK)
+                env->robot_error[r] = rc != VMV_OK ? error : std::string("the environment exceeds the on-chip staging capacity");
+            env->robot_state[r].store(kRobotBuilt, std::memory_order_release);
+            env->robot_cv.notify_all();
+        }
+        for (vmv_env *env : theirs)
+        {
+            std::unique_lock<std::mutex> lock(env->robot_mutex);
+            env->robot_cv.wait(lock, [&]() { return env->robot_state[r].load(std::memory_order_relaxed) == kRobotBuilt; });
+        }
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int st = robot_result(cenvs[k], r); st != VMV_OK) return st;
+        return VMV_OK;
     }
 
     // the checks of vmv_validate_batch_multi(_host) and vmv_validate_motion_batch_multi(_host) that need no device, in the
@@ -1120,12 +1360,9 @@ extern "C"
         if (n == 0) return VMV_OK;
         for (size_t k = 0; k < n_envs; ++k)
             if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
         std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k)
-        {
-            if (int rc = ensure_robot(envs[k], robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-            launch[k] = &envs[k]->launch[robot];
-        }
+        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
         return kLaunchers[robot]->validate_multi(launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
     }
 
@@ -1137,14 +1374,81 @@ extern "C"
         if (n == 0) return VMV_OK;
         for (size_t k = 0; k < n_envs; ++k)
             if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
         std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k)
-        {
-            if (int rc = ensure_robot(envs[k], robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-            launch[k] = &envs[k]->launch[robot];
-        }
+        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
         return kLaunchers[robot]->validate_motion_multi(launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
                                                         static_cast<hipStream_t>(stream));
+    }
+
+    int vmv_env_prepare_multi(int robot, const vmv_env *const *envs, size_t n_envs)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (n_envs == 0) return VMV_OK;
+        if (!envs)
+        {
+            g_last_error = "null pointer";
+            return VMV_ERR_INVALID_ARGUMENT;
+        }
+        for (size_t k = 0; k < n_envs; ++k)
+            if (!envs[k])
+            {
+                g_last_error = "envs[" + std::to_string(k) + "] is NULL";
+                return VMV_ERR_INVALID_ARGUMENT;
+            }
+        for (size_t k = 0; k < n_envs; ++k)
+            if (!envs[k]->finalized)
+            {
+                g_last_error = "envs[" + std::to_string(k) + "] is not finalized";
+                return VMV_ERR_NOT_FINALIZED;
+            }
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        return build_robot_parts(envs, n_envs, robot);
+    }
+
+    int vmv_env_grid_info(const vmv_env *env, int robot, int grid_class, uint32_t *dims3, float *origin3, float *inv_cell,
+                          uint32_t *words)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!env || grid_class < 0 || grid_class >= vmv::kGridClasses) return VMV_ERR_INVALID_ARGUMENT;
+        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
+        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
+        const vmv::EnvDev &D = env->launch[robot].host;
+        const vmv::GridDev &g = D.grid[grid_class];
+        const bool has = g.cells != nullptr;
+        for (int k = 0; k < 3; ++k)
+        {
+            if (dims3) dims3[k] = has ? g.dims[k] : 0u;
+            if (origin3) origin3[k] = has ? g.origin[k] : 0.f;
+        }
+        if (inv_cell) *inv_cell = has ? g.inv_cell : 0.f;
+        if (words) *words = has ? D.grid_words : 0u;
+        return VMV_OK;
+    }
+    int vmv_env_grid_cells(const vmv_env *env, int robot, int grid_class, uint32_t *out, size_t capacity, size_t *n)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!env || !n || grid_class < 0 || grid_class >= vmv::kGridClasses) return VMV_ERR_INVALID_ARGUMENT;
+        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
+        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
+        const vmv::EnvDev &D = env->launch[robot].host;
+        const vmv::GridDev &g = D.grid[grid_class];
+        *n = g.cells ? (size_t) g.dims[0] * g.dims[1] * g.dims[2] * D.grid_words : 0;
+        const size_t m = std::min(capacity, *n);
+        if (out && m) VMV_HIP(hipMemcpy(out, g.cells, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return VMV_OK;
+    }
+    int vmv_env_robot_flags(const vmv_env *env, int robot, uint64_t *link_skip, uint32_t *static_hit)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!env) return VMV_ERR_INVALID_ARGUMENT;
+        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
+        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
+        if (link_skip) *link_skip = env->launch[robot].host.link_skip;
+        if (static_hit)  // (the kernel's answer lives in the device image only)
+            VMV_HIP(hipMemcpy(static_hit, &env->launch[robot].d_env->static_hit, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return VMV_OK;
     }
 
     int vmv_fk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)

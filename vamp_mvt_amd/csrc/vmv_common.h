@@ -74,6 +74,10 @@ namespace vmv
         // once per (environment, robot), after the robot's EnvDev is on the device: evaluates the robot's static links
         // against the environment and stores the answer in d_env->static_hit (synchronous)
         int (*prepare)(const EnvLaunch &, EnvDev *d_env);
+        // the same for many environments in one launch: d_envs[k] is the device image of *envs[k] (already complete but
+        // for static_hit), status[k] = VMV_OK or why environment k could not be launched (it is then left out);
+        // synchronous, returns non-OK only for a failure of the launch as a whole
+        int (*prepare_multi)(const EnvLaunch *const *envs, EnvDev *const *d_envs, size_t n_envs, int *status);
         int (*eefk)(const float *d_q, size_t n, float *d_out16, hipStream_t);  // 4 x 4 row-major frames
         // contact report (Robot::fkcc_debug) from the fine spheres of launch fk
         int (*contacts)(const EnvLaunch &, const float *d_spheres, size_t n, uint32_t *d_env_words, uint32_t *d_pair_words,
@@ -84,6 +88,40 @@ namespace vmv
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;
 
     int hip_status(hipError_t e, const char *what);  // records vmv_last_error(), maps to VMV_ERR_*
+
+    // ---- vmv_env_prepare_multi: grids and reach certificates of many environments (vmv_env_prepare.hip) ----
+    constexpr uint32_t kPrepMaxPrims = 128;  // primitives of an environment that has grid_prims (4 candidate words)
+    struct PrepPrim  // vmv::GridPrim with its parameters in place
+    {
+        int type;
+        uint32_t word, bit;
+        float p[15];
+    };
+    struct PrepGridJob  // one grid (environment, class) to fill
+    {
+        uint32_t prim_lo, n_prims;  // its environment's records in the PrepPrim table
+        uint32_t dims[3], words;
+        float origin[3];
+        double hf, half_diag, R;    // vmv::GridGeometry, the class's radius
+        unsigned long long cell_lo;  // first word of the grid in the cell buffer
+    };
+    struct PrepReachLink  // vmv_link_reach of one robot, samples in one table
+    {
+        int group;
+        uint32_t sample_lo, n;
+        double need;  // radius + slack + 1 mm
+    };
+    struct PrepReachJob  // one environment whose certificates are to be evaluated
+    {
+        uint32_t prim_lo, n_prims;
+        EnvDev *image;  // link_skip is stored here ...
+        uint32_t out;   // ... and in skip_out[out]
+    };
+    // all on `stream`, no synchronisation; jobs with dims whose product is 0 are not allowed
+    int launch_grid_fill(const PrepPrim *d_prims, const PrepGridJob *d_jobs, const PrepGridJob *jobs, size_t n_jobs,
+                         uint32_t *d_cells, hipStream_t stream);
+    int launch_reach(const PrepPrim *d_prims, const PrepReachJob *d_jobs, size_t n_jobs, const PrepReachLink *d_links,
+                     uint32_t n_links, const float *d_samples, unsigned long long *d_skip_out, hipStream_t stream);
 
     // ---- (edge, rake) task scheduling of vmv_validate_motion_batch: the robot-independent half (vmv_edge_tasks.hip) ----
     constexpr uint32_t kEdgeScanBlock = 2048;        // edges per workgroup of the scan kernels

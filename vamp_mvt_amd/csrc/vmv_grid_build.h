@@ -20,6 +20,13 @@
 #include <cstdlib>
 #include <vector>
 
+// the distance expressions also run in the batch preparation kernels (vmv_env_prepare.hip): same text, same operations
+#if defined(__HIPCC__)
+#define VMV_GRID_HD __host__ __device__
+#else
+#define VMV_GRID_HD
+#endif
+
 namespace vmv
 {
     struct GridArrays
@@ -38,9 +45,19 @@ namespace vmv
         uint32_t word, bit;
     };
 
+    // the part of a grid that costs O(primitives): everything but the cell words
+    struct GridGeometry
+    {
+        uint32_t dims[3] = {0, 0, 0};
+        float origin[3] = {0, 0, 0};
+        float inv_cell = 0.f;
+        double hf = 0, half_diag = 0;  // edge of a cell as the device sees it (1 / inv_cell), the radius a cell claims
+    };
+    constexpr double kGridMargin = 1e-3;
+
     namespace grid_detail
     {
-        inline double capsule_g(const float *c, const double x[3], bool z_aligned, double &lip)
+        VMV_GRID_HD inline double capsule_g(const float *c, const double x[3], bool z_aligned, double &lip)
         {
             const double p1[3] = {c[0], c[1], c[2]};
             const double v[3] = {z_aligned ? 0.0 : c[3], z_aligned ? 0.0 : c[4], c[5]};
@@ -62,7 +79,7 @@ namespace vmv
             return std::sqrt(d2) - c[6];
         }
 
-        inline double cuboid_g(const float *c, const double x[3], bool z_aligned, double &lip)
+        VMV_GRID_HD inline double cuboid_g(const float *c, const double x[3], bool z_aligned, double &lip)
         {
             double a[3][3];
             for (int i = 0; i < 3; ++i)
@@ -97,6 +114,29 @@ namespace vmv
             lip = std::sqrt(std::max(worst, 1.0));
             return std::sqrt(s);
         }
+
+        // g_p(x) of a primitive of any type (and its Lipschitz bound)
+        VMV_GRID_HD inline double prim_g(int type, const float *p, const double x[3], double &lip)
+        {
+            if (type == 0)
+            {
+                const double dx = x[0] - p[0], dy = x[1] - p[1], dz = x[2] - p[2];
+                return std::sqrt(dx * dx + dy * dy + dz * dz) - p[3];
+            }
+            if (type <= 2) return capsule_g(p, x, type == 2, lip);
+            return cuboid_g(p, x, type == 4, lip);
+        }
+
+        // is the primitive listed for the cell with centre c?
+        VMV_GRID_HD inline bool cell_lists(int type, const float *p, const double c[3], double R, double half_diag)
+        {
+            double lip = 1.0;
+            const double d = prim_g(type, p, c, lip);
+            return d < R + kGridMargin + lip * half_diag;
+        }
+
+        // centre of cell i along one axis
+        VMV_GRID_HD inline double cell_centre(float origin, uint32_t i, double hf) { return (double) origin + (i + 0.5) * hf; }
     }  // namespace grid_detail
 
     // bbox of the primitive (for the grid extent), conservative
@@ -120,12 +160,12 @@ namespace vmv
         }
     }
 
-    inline bool build_grid(const std::vector<GridPrim> &prims, uint32_t words, double R, GridArrays &out)
+    // extent, cell edge and dimensions of the grid for query spheres of radius <= R; false = no grid (full loops)
+    inline bool grid_geometry(const std::vector<GridPrim> &prims, uint32_t words, double R, GridGeometry &out)
     {
-        out = GridArrays{};
-        out.words = words;
+        out = GridGeometry{};
         if (prims.empty() || words == 0) return false;
-        constexpr double kMargin = 1e-3;
+        constexpr double kMargin = kGridMargin;
         double lo[3] = {1e30, 1e30, 1e30}, hi[3] = {-1e30, -1e30, -1e30};
         for (const auto &g : prims)
         {
@@ -154,30 +194,30 @@ namespace vmv
         // the device computes the cell as floor((x - origin) * inv_cell) in fp32: use the fp32 values here too and
         // let every cell claim a slightly larger cube so that rounding at cell borders stays covered
         out.inv_cell = (float) (1.0 / h);
-        const double hf = 1.0 / (double) out.inv_cell;
-        const double half_diag = 0.5 * hf * std::sqrt(3.0) * 1.001 + 1e-5;
+        out.hf = 1.0 / (double) out.inv_cell;
+        out.half_diag = 0.5 * out.hf * std::sqrt(3.0) * 1.001 + 1e-5;
+        return true;
+    }
+
+    inline bool build_grid(const std::vector<GridPrim> &prims, uint32_t words, double R, GridArrays &out)
+    {
+        out = GridArrays{};
+        out.words = words;
+        GridGeometry geo;
+        if (!grid_geometry(prims, words, R, geo)) return false;
+        for (int k = 0; k < 3; ++k) out.dims[k] = geo.dims[k], out.origin[k] = geo.origin[k];
+        out.inv_cell = geo.inv_cell;
         out.cells.assign((size_t) out.dims[0] * out.dims[1] * out.dims[2] * words, 0u);
         for (uint32_t ix = 0; ix < out.dims[0]; ++ix)
             for (uint32_t iy = 0; iy < out.dims[1]; ++iy)
                 for (uint32_t iz = 0; iz < out.dims[2]; ++iz)
                 {
-                    const double c[3] = {(double) out.origin[0] + (ix + 0.5) * hf, (double) out.origin[1] + (iy + 0.5) * hf,
-                                         (double) out.origin[2] + (iz + 0.5) * hf};
+                    const double c[3] = {grid_detail::cell_centre(out.origin[0], ix, geo.hf),
+                                         grid_detail::cell_centre(out.origin[1], iy, geo.hf),
+                                         grid_detail::cell_centre(out.origin[2], iz, geo.hf)};
                     uint32_t *cell = &out.cells[(((size_t) ix * out.dims[1] + iy) * out.dims[2] + iz) * words];
                     for (const auto &g : prims)
-                    {
-                        double lip = 1.0, d;
-                        if (g.type == 0)
-                        {
-                            const double dx = c[0] - g.p[0], dy = c[1] - g.p[1], dz = c[2] - g.p[2];
-                            d = std::sqrt(dx * dx + dy * dy + dz * dz) - g.p[3];
-                        }
-                        else if (g.type <= 2)
-                            d = grid_detail::capsule_g(g.p, c, g.type == 2, lip);
-                        else
-                            d = grid_detail::cuboid_g(g.p, c, g.type == 4, lip);
-                        if (d < R + kMargin + lip * half_diag) cell[g.word] |= 1u << g.bit;
-                    }
+                        if (grid_detail::cell_lists(g.type, g.p, c, R, geo.half_diag)) cell[g.word] |= 1u << g.bit;
                 }
         return true;
     }

@@ -198,6 +198,21 @@ namespace VMV_ROBOT_NS
         if (threadIdx.x == 0) env->static_hit = hit ? 1u : 0u;
     }
 
+    // The same for many environments (vmv_env_prepare_multi): workgroup b stages environment b with its own LDS plan.
+    struct StaticJob
+    {
+        EnvDev *env;
+        uint32_t tests_in_lds;
+    };
+    __global__ __launch_bounds__(kBlock) void static_links_multi_kernel(const StaticJob *__restrict__ jobs)
+    {
+        extern __shared__ __align__(16) float smem[];
+        const StaticJob J = jobs[blockIdx.x];
+        const EnvView E = stage_environment(J.env, J.tests_in_lds, smem);
+        const bool hit = R::static_env_hit(E);
+        if (threadIdx.x == 0) J.env->static_hit = hit ? 1u : 0u;
+    }
+
     // Attachment part of Robot::fkcc_attach (only launched for environments with an attachment): ANDs into the words.
     __global__ __launch_bounds__(kBlock, 2) void validate_attach_kernel(const EnvDev *__restrict__ env,
                                                                        const uint32_t tests_in_lds,
@@ -1451,6 +1466,40 @@ namespace VMV_ROBOT_NS
             return VMV_OK;
         }
 
+        int launch_prepare_multi(const EnvLaunch *const *envs, EnvDev *const *d_envs, size_t n_envs, int *status)
+        {
+            for (size_t k = 0; k < n_envs; ++k) status[k] = VMV_OK;
+            if (R::kNStaticLinks == 0 || n_envs == 0) return VMV_OK;  // static_hit stays 0
+            std::vector<StaticJob> jobs;
+            jobs.reserve(n_envs);
+            uint32_t shmem_max = 0;
+            for (size_t k = 0; k < n_envs; ++k)
+            {
+                uint32_t tests_in_lds, shmem;
+                if ((status[k] = plan_lds(*envs[k], tests_in_lds, shmem)) != VMV_OK) continue;
+                jobs.push_back(StaticJob{d_envs[k], tests_in_lds});
+                shmem_max = shmem > shmem_max ? shmem : shmem_max;
+            }
+            if (jobs.empty()) return VMV_OK;
+            StaticJob *d_jobs = nullptr;
+            VMV_HIP_TU(hipMalloc((void **) &d_jobs, jobs.size() * sizeof(StaticJob)));
+            hipError_t e = hipMemcpy(d_jobs, jobs.data(), jobs.size() * sizeof(StaticJob), hipMemcpyHostToDevice);
+            if (e == hipSuccess && shmem_max > 64u * 1024u)
+                e = hipFuncSetAttribute((const void *) static_links_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int) shmem_max);
+            constexpr size_t kMaxGrid = size_t{1} << 30;
+            for (size_t j0 = 0; e == hipSuccess && j0 < jobs.size(); j0 += kMaxGrid)
+            {
+                const size_t m = jobs.size() - j0 < kMaxGrid ? jobs.size() - j0 : kMaxGrid;
+                hipLaunchKernelGGL(static_links_multi_kernel, dim3((uint32_t) m), dim3(kBlock), shmem_max, nullptr, d_jobs + j0);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            (void) hipFree(d_jobs);
+            if (e != hipSuccess) return hip_status(e, "static_links_multi_kernel");
+            return VMV_OK;
+        }
+
         // d_spheres: [n][kNSpheres][4] from launch_fk; d_env_words: [n][kNSpheres][kReportWords + 1]; d_pair_words:
         // [n][pair_words] zeroed by the caller
         int launch_contacts(const EnvLaunch &env, const float *d_spheres, size_t n, uint32_t *d_env_words,
@@ -1504,6 +1553,7 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_validate_motion,
                                                     VMV_ROBOT_NS::launch_validate_motion_multi,
                                                     VMV_ROBOT_NS::launch_fk, VMV_ROBOT_NS::launch_prepare,
+                                                    VMV_ROBOT_NS::launch_prepare_multi,
                                                     VMV_ROBOT_NS::launch_eefk, VMV_ROBOT_NS::launch_contacts,
                                                     VMV_ROBOT_NS::R::kNSelfPairs};
 #endif
