@@ -19,6 +19,7 @@ Kernel-side shape of one robot:
 from __future__ import annotations
 
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -222,9 +223,18 @@ def link_samples(m, N=LINK_SAMPLES_N):
     return out
 
 
-def gate_rates(m, n=4096, seed=0, tables=()):
+def multi_table_bits(t, q):
+    """bit of the multi-joint clearance table t (self_tables_multi) for configurations q[N][dim] inside the joint bounds"""
+    N = t["n"]
+    idx = np.zeros(q.shape[0], np.int64)
+    for j, lo_j, inv_j in zip(t["joints"], t["lo"], t["inv"]):
+        idx = idx * N + np.clip(((q[:, j] - lo_j) * inv_j).astype(np.int64), 0, N - 1)
+    return ((t["words"][idx >> 5] >> (idx & 31).astype(np.uint32)) & 1) != 0
+
+
+def gate_rates(m, n=4096, seed=0, tables=(), multi=()):
     """Share of uniformly random configurations whose bounding-pair gate fires (and whose clearance-table bit, if the
-    group has one, is set), per self-collision group."""
+    group has one - two-joint `tables`, multi-joint `multi` -, is set), per self-collision group."""
     rng = np.random.default_rng(seed)
     q = np.array(m["lower"]) + np.array(m["span"]) * rng.random((n, m["dimension"]))
     c = eval_tape(m, q)
@@ -237,6 +247,8 @@ def gate_rates(m, n=4096, seed=0, tables=()):
         cell = t["table"][np.clip(((q[:, i] - loi) * ii).astype(int), 0, N - 1), np.clip(((q[:, j] - loj) * ij).astype(int), 0, N - 1)]
         for bit, gi in enumerate(t["groups"]):
             fire[gi] = fire[gi] & (((cell >> bit) & 1) != 0)
+    for t in multi:
+        fire[t["group"]] = fire[t["group"]] & multi_table_bits(t, q)
     return [float(f.mean()) for f in fire]
 
 
@@ -314,7 +326,150 @@ def self_tables(m, N=SELF_TABLE_N):
     return out
 
 
-SELF_DEAL_MAX_A = 40  # A-side spheres kept in registers for the re-dealt self-collision form
+SELF_MULTI_N = {3: 64, 4: 32}   # cells per joint of the three- and four-joint clearance tables
+SELF_MULTI_MIN_RATE = 0.02      # a group joins only if its bounding gate fires for this share of uniform configurations ...
+SELF_MULTI_MIN_CUT = 0.5        # ... and the table removes at least this share of those firings
+SELF_MULTI_MAX_BYTES = 256 * 1024  # new tables per robot
+_MULTI_CACHE = {}
+
+
+def eval_spheres(m, q, spheres, batch=4096):
+    """eval_tape restricted to the given spheres (only the ops they depend on) -> centres [N][len(spheres)][3]"""
+    want = set()
+    stack = [v for s in spheres for (kind, v) in m["outputs"][s] if kind == "op"]
+    while stack:
+        i = stack.pop()
+        if i not in want:
+            want.add(i)
+            stack += deps(*m["ops"][i])
+    order = sorted(want)
+    binary = {"mul": np.multiply, "add": np.add, "sub": np.subtract}
+
+    def run(qb):
+        vals = {}
+        for i in order:
+            op, a, b = m["ops"][i]
+            if op == "in":
+                vals[i] = qb[:, a]
+            elif op in ("sin", "cos"):
+                vals[i] = (np.sin if op == "sin" else np.cos)(vals[a])
+            elif op == "neg":
+                vals[i] = -vals[a]
+            elif op in binary:
+                vals[i] = binary[op](vals[a], vals[b])
+            elif op == "cmul":
+                vals[i] = a * vals[b]
+            elif op == "cadd":
+                vals[i] = a + vals[b]
+            else:
+                raise ValueError(op)
+        out = np.zeros((qb.shape[0], len(spheres), 3))
+        for s, sphere in enumerate(spheres):
+            for k, (kind, v) in enumerate(m["outputs"][sphere]):
+                out[:, s, k] = vals[v] if kind == "op" else v
+        return out
+    return np.concatenate([run(q[i:i + batch]) for i in range(0, q.shape[0], batch)])
+
+
+def self_tables_multi(m, cells=None):
+    """Three- and four-joint clearance tables for the self-collision half: self_tables' certificate for the groups whose
+    pair distances depend on three or four joints (found numerically, as there).  A cell of the (q_i, q_j, q_k[, q_l])
+    grid is CERTAINLY free for a group when every fine pair's clearance at the cell centre (float64) exceeds what the
+    pair can lose inside the cell plus SELF_TABLE_MARGIN.  The loss bound generalises the two-joint one: the lever arm
+    rho_k of every dependent joint (exact chord of a +-h rotation) may grow by sum_m rho_m * (half a cell of joint m)
+    across the cell (rho_k only depends on the joints between k and B, and changes by at most rho_m per radian of such
+    a joint; the sum is taken over all other joints, so the order does not matter); + 10 %, cells taken 1 % larger than
+    they are.  Outside the joint bounds (and for NaN) the device reads every bit as 1.
+    A group gets a table only if its bounding gate fires for at least SELF_MULTI_MIN_RATE of uniform configurations and
+    the table removes at least SELF_MULTI_MIN_CUT of those firings; the groups that remove most come first while the
+    tables stay within SELF_MULTI_MAX_BYTES per robot.  One bit per cell, cell index ((c_i * N + c_j) * N + c_k)[* N + c_l],
+    bit (index & 31) of word (index >> 5).
+    -> [dict(group=index into self_groups, joints=(..), n=N, words=uint32[N^d / 32] (bit 1 = must test), lo=(..),
+    inv=(..), free_share=share of the cells free, fires=gate rate, fires_with_table=gate-and-bit rate)]"""
+    cells = dict(SELF_MULTI_N if cells is None else cells)
+    key = (m["name"], tuple(sorted(cells.items())))
+    if key in _MULTI_CACHE:
+        return _MULTI_CACHE[key]
+    dim = m["dimension"]
+    lo, span = np.array(m["lower"], float), np.array(m["span"], float)
+    r = np.array(m["radii"], float)
+    rng = np.random.default_rng(7)
+    q0 = lo + span * rng.random((6, dim))
+    c0 = eval_tape(m, q0)
+    shifted0 = []
+    for j in range(dim):
+        q1 = q0.copy()
+        q1[:, j] += 0.37 * span[j] * np.where(q1[:, j] - lo[j] < 0.5 * span[j], 1.0, -1.0)
+        shifted0.append(eval_tape(m, q1))
+    base_rates = gate_rates(m, n=16384, seed=1)
+    cs = eval_tape(m, lo + span * np.random.default_rng(1).random((16384, dim)))  # (gate_rates' own sample)
+    cands = []
+    for gi, g in enumerate(m["self_groups"]):
+        pr = np.array(g["pairs"])
+        d0 = np.linalg.norm(c0[:, pr[:, 0]] - c0[:, pr[:, 1]], axis=2)
+        dep = [j for j in range(dim)
+               if np.abs(np.linalg.norm(shifted0[j][:, pr[:, 0]] - shifted0[j][:, pr[:, 1]], axis=2) - d0).max() > 1e-9]
+        if len(dep) in cells and base_rates[gi] >= SELF_MULTI_MIN_RATE:
+            # no table can remove a firing whose nearest pair is closer than the margin: skip the hopeless groups early
+            near = ((np.linalg.norm(cs[:, pr[:, 0]] - cs[:, pr[:, 1]], axis=2) - r[pr[:, 0]] - r[pr[:, 1]]).min(axis=1)
+                    <= SELF_TABLE_MARGIN)
+            fire = np.linalg.norm(cs[:, g["bound_a"]] - cs[:, g["bound_b"]], axis=1) < r[g["bound_a"]] + r[g["bound_b"]]
+            if (fire & near).mean() <= (1.0 - SELF_MULTI_MIN_CUT) * fire.mean():
+                cands.append((gi, tuple(dep)))
+    out = []
+    h = 1e-3
+    for gi, dep in cands:
+        N, d = cells[len(dep)], len(dep)
+        pr = np.array(m["self_groups"][gi]["pairs"])
+        spheres = sorted(set(pr.reshape(-1).tolist()))
+        a, b = np.searchsorted(spheres, pr[:, 0]), np.searchsorted(spheres, pr[:, 1])
+        rs = r[pr[:, 0]] + r[pr[:, 1]]
+        half = [0.5 * span[j] / N * 1.01 for j in dep]
+        total = N ** d
+        assert total % 32 == 0
+        def chunk(c_lo):
+            idx = np.arange(c_lo, min(c_lo + (1 << 14), total))
+            Q = np.tile(lo + 0.5 * span, (len(idx), 1))
+            rest = idx.copy()
+            for j in reversed(dep):
+                Q[:, j] = lo[j] + span[j] * ((rest % N) + 0.5) / N
+                rest //= N
+
+            def diff(axis=None, dq=0.0):
+                Q2 = Q
+                if axis is not None:
+                    Q2 = Q.copy()
+                    Q2[:, axis] += dq
+                C = eval_spheres(m, Q2, spheres, batch=len(idx))
+                return C[:, b] - C[:, a]
+
+            def norm(v):
+                return np.sqrt(np.einsum("ijk,ijk->ij", v, v))
+            clear = norm(diff()) - rs
+            rho = [norm(diff(j, h) - diff(j, -h)) / (2 * np.sin(h)) for j in dep]
+            slack = sum((rho[k] + sum(rho[o] * half[o] for o in range(d) if o != k)) * half[k] for k in range(d))
+            return (clear <= 1.1 * slack + SELF_TABLE_MARGIN).any(axis=1)
+        with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:  # (numpy releases the GIL inside its loops)
+            must = np.concatenate(list(ex.map(chunk, range(0, total, 1 << 14))))
+        words = (must.reshape(-1, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(axis=1, dtype=np.uint32)
+        t = dict(group=gi, joints=dep, n=N, words=words, lo=tuple(float(lo[j]) for j in dep),
+                 inv=tuple(N / float(span[j]) for j in dep), free_share=1.0 - float(must.mean()), fires=base_rates[gi])
+        t["fires_with_table"] = gate_rates(m, n=16384, seed=1, multi=[t])[gi]
+        if t["fires"] - t["fires_with_table"] >= SELF_MULTI_MIN_CUT * t["fires"]:
+            out.append(t)
+    # most removed firings first, within the size limit; then in group order
+    out.sort(key=lambda t: t["fires_with_table"] - t["fires"])
+    kept, size = [], 0
+    for t in out:
+        if size + 4 * len(t["words"]) <= SELF_MULTI_MAX_BYTES:
+            kept.append(t)
+            size += 4 * len(t["words"])
+    kept.sort(key=lambda t: t["group"])
+    _MULTI_CACHE[key] = kept
+    return kept
+
+
+SELF_DEAL_MAX_A = 40 # A-side spheres kept in registers for the re-dealt self-collision form
 ENV_CHUNK = {"panda": 4, "ur5": 6, "baxter": 5}   # fine spheres per slab chunk in the environment kernels (default CHUNK); a smaller slab
 ENV_BLOCKS = {"panda": 6, "ur5": 5, "baxter": 5}  # (baxter: 0.331 -> 0.307 ms per 1M configs at 5)  # ... lets five or six workgroups (20 - 24 waves) share a CU's LDS where the registers allow it
 # Panda, round 3: with the merged gates and the FK of a group emitted chunk by chunk the three-list kernel needs 81 VGPRs;
@@ -724,7 +879,22 @@ def emit_robot(m):
         for bit, gi in enumerate(t["groups"]):
             table_bit[gi] = (ti, bit)
     group_index = {id(sg): gi for gi, sg in enumerate(m["self_groups"])}
-    rates = gate_rates(m, tables=tables)
+    multi = self_tables_multi(m)
+    multi_of = {t["group"]: ti for ti, t in enumerate(multi)}  # index into self_groups -> multi-joint table number
+    rates = gate_rates(m, tables=tables, multi=multi)
+    # the table loads of a configuration, issued ahead of FK (one load each, hidden behind it).  The multi-joint bits ride
+    # in the word of the first two-joint table (bits 8 and up; its own are bits 0 - 7), so they cost no register of their own
+    assert len(multi) <= 24
+    multi_word, multi_shift = ("tb0", 8) if tables else ("tm", 0)
+    table_loads = []
+    for ti in range(len(tables)):
+        bits = f"self_table{ti}(q)"
+        if ti == 0:
+            bits += "".join(f" | (self_multi{k}(q) << {multi_shift + k})" for k in range(len(multi)))
+        table_loads.append(f"        {'const ' if ti or not multi else ''}unsigned tb{ti} = (VMV_ABLATE_SELF == 16) ? ~0u : {bits};")
+    if multi and not tables:
+        table_loads.append("        unsigned tm = (VMV_ABLATE_SELF == 16) ? ~0u : "
+                           + " | ".join(f"(self_multi{k}(q) << {k})" for k in range(len(multi))) + ";")
     dense_ids = {id(sg) for sg, r in zip(m["self_groups"], rates)
                  if r >= SELF_DENSE_RATE and len({p[0] for p in sg["pairs"]}) >= SELF_DENSE_MIN_A}
     if tables:
@@ -748,6 +918,26 @@ def emit_robot(m):
             L.append(f"        const bool in = fi >= 0.0f && fj >= 0.0f && fi < {N}.0f && fj < {N}.0f;  // (false for NaN)")
             L.append(f"        typedef const unsigned char __attribute__((address_space(1))) *gb_cptr;")
             L.append(f"        return in ? (unsigned) ((gb_cptr) kSelfTable{ti})[(unsigned) fi * {N}u + (unsigned) fj] : 0xffu;")
+            L.append("    }")
+    if multi:
+        L.append("    // Three- and four-joint clearance tables (tools/gen_hip.py: self_tables_multi): one bit per cell, 1 = the group may")
+        L.append("    // have a colliding fine pair somewhere in the cell, 0 = certainly free (same certificate as the two-joint tables,")
+        L.append("    // lever arms of every dependent joint).  Outside the joint bounds every bit reads 1 (vmv::self_table_bit).")
+        for ti, t in enumerate(multi):
+            sg = m["self_groups"][t["group"]]
+            N = t["n"]
+            L.append(f"    // multi-joint table {ti}: joints {', '.join(str(j) for j in t['joints'])}; {N} cells per joint; "
+                     f"{sg['a']} vs. {sg['b']} ({t['free_share'] * 100:.1f} % of the cells free; gate fires for "
+                     f"{t['fires'] * 100:.1f} % of uniform configurations, with the bit {t['fires_with_table'] * 100:.1f} %)")
+            L.append(f"    __device__ const unsigned kSelfMulti{ti}[{len(t['words'])}] = {{")
+            for k in range(0, len(t["words"]), 16):
+                L.append("        " + ",".join(f"0x{int(v):08x}u" for v in t["words"][k:k + 16]) + ",")
+            L.append("    };")
+            L.append(f"    __device__ __forceinline__ unsigned self_multi{ti}(const float (&q)[kDim])")
+            L.append("    {")
+            for k, (j, lo_j, inv_j) in enumerate(zip(t["joints"], t["lo"], t["inv"])):
+                L.append(f"        const float f{k} = (q[{j}] - {flit(lo_j)}) * {flit(inv_j)};")
+            L.append(f"        return vmv::self_table_bit<{N}>(kSelfMulti{ti}, " + ", ".join(f"f{k}" for k in range(len(t["joints"]))) + ");")
             L.append("    }")
     L.append("    // Self-collision half of Robot::fkcc<rake> (\"robot self-collisions\").")
     L.append("    // Groups (A, B) run when B is the current link; gates (bounding pair) are per lane, exact.")
@@ -776,8 +966,7 @@ def emit_robot(m):
     L.append("        vmv::lds_u32 *const cand = list + 2 * vmv::kWave + 4;  // A-side candidate word per owner lane")
     L.append(f"        vmv::lds_u32 *const list2 = cand + vmv::kWave;        // item lists: (owner lane | tag << 6), <= {max(CHUNK, SPARSE_BATCH)} * 64 entries")
     L.append(f"        static_assert(vmv::kSelfScratchWords >= 3 * vmv::kWave + 4 + {CHUNK} * vmv::kWave, \"self-collision scratch\");")
-    for ti in range(len(tables)):
-        L.append(f"        const unsigned tb{ti} = (VMV_ABLATE_SELF == 16) ? 0xffu : self_table{ti}(q);  // issued first: one load, hidden behind FK")
+    L.extend(table_loads)
     def emit_self_link(em, ln, bi, batch_set, I):
         """one B link of the self-collision half (appends to em.lines); groups whose A link is in batch_set"""
         groups = [sg for sg in self_by_b.get(ln, []) if sg["a"] in batch_set]
@@ -791,6 +980,11 @@ def emit_robot(m):
         for sg in groups:
             em.need(sorted({p[0] for p in sg["pairs"]}) + [sg["bound_a"]])
         em.need([bb] + fine)
+        if multi and not getattr(em, "tables_folded", False):
+            # the multi-joint loads are folded into their word here, behind the FK of the chain up to the first B link: left
+            # to the first use, their destination and shift registers would stay live into the widest part of the walk
+            em.lines.append(f'{I}asm volatile("" : "+v"({multi_word}));')
+            em.tables_folded = True
         gate_names = []
         for gi, sg in enumerate(groups):
             ba = sg["bound_a"]
@@ -799,6 +993,8 @@ def emit_robot(m):
             gate_names.append(gn)
             tb = table_bit.get(group_index[id(sg)])
             tbit = f" && ((tb{tb[0]} >> {tb[1]}) & 1u) != 0u" if tb else ""
+            if group_index[id(sg)] in multi_of:
+                tbit = f" && (({multi_word} >> {multi_shift + multi_of[group_index[id(sg)]]}) & 1u) != 0u"
             em.lines.append(
                 f"{I}const bool {gn} = vmv::group_any<G>(vmv::neg(vmv::sql2_3({em.coord(ba, 0)}, {em.coord(ba, 1)}, "
                 f"{em.coord(ba, 2)}, {em.coord(bb, 0)}, {em.coord(bb, 1)}, {em.coord(bb, 2)}) - {flit(float(f32(rs * rs)))}){tbit})"
@@ -845,6 +1041,24 @@ def emit_robot(m):
                     f"{J}    cand_{gate_names[gi]} |= vmv::neg(vmv::sql2_3({em.coord(s, 0)}, {em.coord(s, 1)}, {em.coord(s, 2)}, "
                     f"{em.coord(bb, 0)}, {em.coord(bb, 1)}, {em.coord(bb, 2)}) - {flit(float(f32(rs * rs)))}) ? {1 << ai}u : 0u;")
             em.lines.append(f"{J}}}")
+        def entry_list(K, batch_groups):
+            # entries are appended group by group, so entry counts are also item boundaries: the items are
+            # dealt GROUP-MAJOR (all items of group 0, then group 1, ...) and a round of 64 items touches one or
+            # two groups instead of all of them - only those run their A loops
+            em.lines.append(f"{K}int k = 0;")
+            for li, gi in enumerate(batch_groups):
+                em.lines.append(f"{K}const int kk{li} = k;")
+                em.lines.append(f"{K}k = vmv::deal_append(list2, k, {gate_names[gi]}, {li}u << 6);  // {groups[gi]['a']}")
+            em.lines.append(f"{K}const int kk{len(batch_groups)} = k;")
+            for li in range(len(batch_groups)):
+                em.lines.append(f"{K}const int n{li} = kk{li + 1} - kk{li};")
+
+        # the (lane, group) entry list of the sparse groups does not depend on the chunk, and the rounds only read it: where
+        # nothing else writes list2 between the chunks (one batch of sparse groups, no dense group) it is built once per
+        # B link, ahead of the chunks (each chunk's wave_lds_sync after staging orders it before the reads)
+        shared_list = len(chunks) > 1 and not dense and 0 < len(sparse) <= SPARSE_BATCH
+        if shared_list:
+            entry_list(J, sparse)
         done = 0
         for ci, ch in enumerate(chunks):
             off = radii_off[ln] + 1 + done
@@ -855,21 +1069,17 @@ def emit_robot(m):
             # the merged entry list holds at most SPARSE_BATCH * 64 (lane, group) entries
             for sb in range(0, len(sparse), SPARSE_BATCH):
                 batch_groups = sparse[sb:sb + SPARSE_BATCH]
-                em.lines.append(f"{J}if (VMV_ABLATE_SELF != 4 && vmv::wave_any(" + " || ".join(gate_names[gi] for gi in batch_groups) + f"))  // sparse groups, chunk {ci}")
-                em.lines.append(f"{J}{{")
                 K = J + "    "
-                # entries are appended group by group, so entry counts are also item boundaries: the items are
-                # dealt GROUP-MAJOR (all items of group 0, then group 1, ...) and a round of 64 items touches one or
-                # two groups instead of all of them - only those run their A loops
-                em.lines.append(f"{K}int k = 0;")
-                for li, gi in enumerate(batch_groups):
-                    em.lines.append(f"{K}const int kk{li} = k;")
-                    em.lines.append(f"{K}k = vmv::deal_append(list2, k, {gate_names[gi]}, {li}u << 6);  // {groups[gi]['a']}")
-                em.lines.append(f"{K}const int kk{len(batch_groups)} = k;")
-                em.lines.append(f"{K}vmv::wave_lds_sync();")
+                if shared_list:
+                    em.lines.append(f"{J}if (VMV_ABLATE_SELF != 4 && k != 0)  // sparse groups, chunk {ci}")
+                    em.lines.append(f"{J}{{")
+                else:
+                    em.lines.append(f"{J}if (VMV_ABLATE_SELF != 4 && vmv::wave_any(" + " || ".join(gate_names[gi] for gi in batch_groups) + f"))  // sparse groups, chunk {ci}")
+                    em.lines.append(f"{J}{{")
+                    entry_list(K, batch_groups)
+                    em.lines.append(f"{K}vmv::wave_lds_sync();")
                 em.lines.append(f"{K}const int items = k * {len(ch)};")
-                for li in range(len(batch_groups)):
-                    em.lines.append(f"{K}const int n{li} = kk{li + 1} - kk{li};")
+                for li in range(len(batch_groups)):  # (per chunk: a reciprocal lives in a vector register, the counts do not)
                     em.lines.append(f"{K}const float inv{li} = 1.0f / (float) (n{li} > 0 ? n{li} : 1);")
                 em.lines.append(f"{K}for (int base = 0; base < items; base += vmv::kWave)")
                 em.lines.append(f"{K}{{")
@@ -988,8 +1198,7 @@ def emit_robot(m):
         L.append("        vmv::lds_u32 *const flags = list + vmv::kWave;")
         L.append("        vmv::lds_u32 *const cand = list + 2 * vmv::kWave + 4;")
         L.append("        vmv::lds_u32 *const list2 = cand + vmv::kWave;")
-        for ti in range(len(tables)):
-            L.append(f"        const unsigned tb{ti} = (VMV_ABLATE_SELF == 16) ? 0xffu : self_table{ti}(q);")
+        L.extend(table_loads)
         em = Emitter(m, prefix="t", indent="        ")
         bset = set(batches[0])
         for ln in links:

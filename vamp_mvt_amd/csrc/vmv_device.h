@@ -1515,6 +1515,31 @@ namespace vmv
         done += run;
     }
 
+    // Bit of a three- or four-joint clearance table (tools/gen_hip.py: self_tables_multi): one bit per cell of an N^D grid,
+    // cell index ((c0 * N + c1) * N + c2)[* N + c3], bit (index & 31) of word (index >> 5).  f0.. are the joints' cell
+    // coordinates in fp32, (q - lower) * N / span, the index arithmetic of the two-joint self_table0.  1 = the group must
+    // be tested; outside the grid and for NaN the answer is 1 (the load then reads word 0 and is ignored).  One dword load.
+    template <int N>
+    __device__ __forceinline__ uint32_t self_cell_bit(const uint32_t *table, const bool in, const uint32_t idx)
+    {
+        typedef const uint32_t __attribute__((address_space(1))) *gw_cptr;
+        const uint32_t word = ((gw_cptr) table)[idx >> 5];
+        return in ? (word >> (idx & 31u)) & 1u : 1u;
+    }
+    template <int N>
+    __device__ __forceinline__ uint32_t self_table_bit(const uint32_t *table, const float f0, const float f1, const float f2)
+    {
+        const bool in = f0 >= 0.0f && f1 >= 0.0f && f2 >= 0.0f && f0 < (float) N && f1 < (float) N && f2 < (float) N;  // (false for NaN)
+        return self_cell_bit<N>(table, in, in ? ((uint32_t) f0 * N + (uint32_t) f1) * N + (uint32_t) f2 : 0u);
+    }
+    template <int N>
+    __device__ __forceinline__ uint32_t self_table_bit(const uint32_t *table, const float f0, const float f1, const float f2, const float f3)
+    {
+        const bool in = f0 >= 0.0f && f1 >= 0.0f && f2 >= 0.0f && f3 >= 0.0f && f0 < (float) N && f1 < (float) N &&
+                        f2 < (float) N && f3 < (float) N;  // (false for NaN)
+        return self_cell_bit<N>(table, in, in ? (((uint32_t) f0 * N + (uint32_t) f1) * N + (uint32_t) f2) * N + (uint32_t) f3 : 0u);
+    }
+
     // Re-dealing support for the self-collision groups: list the lanes whose predicate holds; returns how many.
     __device__ __forceinline__ int deal_list(lds_u32 *list, const bool pred)
     {
