@@ -232,9 +232,10 @@ def multi_table_bits(t, q):
     return ((t["words"][idx >> 5] >> (idx & 31).astype(np.uint32)) & 1) != 0
 
 
-def gate_rates(m, n=4096, seed=0, tables=(), multi=()):
+def gate_rates(m, n=4096, seed=0, tables=(), multi=(), any_rate=False):
     """Share of uniformly random configurations whose bounding-pair gate fires (and whose clearance-table bit, if the
-    group has one - two-joint `tables`, multi-joint `multi` -, is set), per self-collision group."""
+    group has one - two-joint `tables`, multi-joint `multi` -, is set), per self-collision group.  With any_rate:
+    -> (that list, share of the configurations for which the gate of at least one group fires)."""
     rng = np.random.default_rng(seed)
     q = np.array(m["lower"]) + np.array(m["span"]) * rng.random((n, m["dimension"]))
     c = eval_tape(m, q)
@@ -249,7 +250,8 @@ def gate_rates(m, n=4096, seed=0, tables=(), multi=()):
             fire[gi] = fire[gi] & (((cell >> bit) & 1) != 0)
     for t in multi:
         fire[t["group"]] = fire[t["group"]] & multi_table_bits(t, q)
-    return [float(f.mean()) for f in fire]
+    rates = [float(f.mean()) for f in fire]
+    return (rates, float(np.any(fire, axis=0).mean())) if any_rate else rates
 
 
 SELF_TABLE_N = 256  # cells per joint of the two-joint clearance tables
@@ -490,6 +492,10 @@ MOTION_SELF_BLOCKS = {"ur5": 5}
 # body spills 28 VGPRs instead of 77 at 4, and such batches never fill more than 2 - 3 waves per SIMD: 256 edges 0.104 ->
 # 0.096 ms, 2,048 0.133 -> 0.126, 8,192 0.148 -> 0.135 (at 2: 0.094 / 0.123 / 0.148); UR5 (no spill at 3) unchanged
 FUSED_BLOCKS = {"panda": 3, "ur5": 3}
+# robots for which the gate of some group fires (tables applied) for less than this share of uniform configurations screen
+# every pass with fkcc_self_screen and run fkcc_self on the flagged configurations only (validate_self_kernel).  Sampled
+# rates: Panda 0.16, Fetch 0.28, Baxter 0.65, UR5 0.94.  A/B per robot: DESIGN section 6.
+SELF_SCREEN_MAX_RATE = 0.5
 SELF_DENSE_RATE = 0.5   # groups whose bounding-pair gate fires for at least this share of uniform configurations ...
 SELF_DENSE_MIN_A = 3    # ... and whose A side is at least this large use the pre-test + compaction form
 SPARSE_BATCH = 8        # sparse groups merged per item list (the list holds SPARSE_BATCH * 64 entries = CHUNK * 64)
@@ -605,6 +611,12 @@ def grid_classes(m):
     while len(radii) < GRID_CLASSES:
         radii.append(radii[-1])
     return radii, cls
+
+
+def self_screen_rate(m):
+    """share of uniform configurations for which the gate of some self-collision group fires, clearance tables applied
+    (gate_rates' default sample): what kSelfScreen is decided from"""
+    return gate_rates(m, tables=self_tables(m), multi=self_tables_multi(m), any_rate=True)[1]
 
 
 def static_links(m):
@@ -881,7 +893,7 @@ def emit_robot(m):
     group_index = {id(sg): gi for gi, sg in enumerate(m["self_groups"])}
     multi = self_tables_multi(m)
     multi_of = {t["group"]: ti for ti, t in enumerate(multi)}  # index into self_groups -> multi-joint table number
-    rates = gate_rates(m, tables=tables, multi=multi)
+    rates, any_gate_rate = gate_rates(m, tables=tables, multi=multi, any_rate=True)
     # the table loads of a configuration, issued ahead of FK (one load each, hidden behind it).  The multi-joint bits ride
     # in the word of the first two-joint table (bits 8 and up; its own are bits 0 - 7), so they cost no register of their own
     assert len(multi) <= 24
@@ -967,6 +979,19 @@ def emit_robot(m):
     L.append(f"        vmv::lds_u32 *const list2 = cand + vmv::kWave;        // item lists: (owner lane | tag << 6), <= {max(CHUNK, SPARSE_BATCH)} * 64 entries")
     L.append(f"        static_assert(vmv::kSelfScratchWords >= 3 * vmv::kWave + 4 + {CHUNK} * vmv::kWave, \"self-collision scratch\");")
     L.extend(table_loads)
+    def gate_term(em, sg):
+        """the gate of one group on this lane's configuration: bounding pair closer than the radii, and the group's
+        clearance-table bit where it has one.  The one text of it: fkcc_self and fkcc_self_screen both call this, and with
+        -ffp-contract=off the same text gives the same bits."""
+        ba, bb = sg["bound_a"], env_by_link[sg["b"]]["bound"]
+        rs = f32(f32(radii[ba]) + f32(radii[bb]))
+        tb = table_bit.get(group_index[id(sg)])
+        tbit = f" && ((tb{tb[0]} >> {tb[1]}) & 1u) != 0u" if tb else ""
+        if group_index[id(sg)] in multi_of:
+            tbit = f" && (({multi_word} >> {multi_shift + multi_of[group_index[id(sg)]]}) & 1u) != 0u"
+        return (f"vmv::neg(vmv::sql2_3({em.coord(ba, 0)}, {em.coord(ba, 1)}, {em.coord(ba, 2)}, "
+                f"{em.coord(bb, 0)}, {em.coord(bb, 1)}, {em.coord(bb, 2)}) - {flit(float(f32(rs * rs)))}){tbit}")
+
     def emit_self_link(em, ln, bi, batch_set, I):
         """one B link of the self-collision half (appends to em.lines); groups whose A link is in batch_set"""
         groups = [sg for sg in self_by_b.get(ln, []) if sg["a"] in batch_set]
@@ -987,17 +1012,10 @@ def emit_robot(m):
             em.tables_folded = True
         gate_names = []
         for gi, sg in enumerate(groups):
-            ba = sg["bound_a"]
-            rs = f32(f32(radii[ba]) + f32(radii[bb]))
             gn = f"gate_{bi}_{links.index(ln)}_{gi}"
             gate_names.append(gn)
-            tb = table_bit.get(group_index[id(sg)])
-            tbit = f" && ((tb{tb[0]} >> {tb[1]}) & 1u) != 0u" if tb else ""
-            if group_index[id(sg)] in multi_of:
-                tbit = f" && (({multi_word} >> {multi_shift + multi_of[group_index[id(sg)]]}) & 1u) != 0u"
             em.lines.append(
-                f"{I}const bool {gn} = vmv::group_any<G>(vmv::neg(vmv::sql2_3({em.coord(ba, 0)}, {em.coord(ba, 1)}, "
-                f"{em.coord(ba, 2)}, {em.coord(bb, 0)}, {em.coord(bb, 1)}, {em.coord(bb, 2)}) - {flit(float(f32(rs * rs)))}){tbit})"
+                f"{I}const bool {gn} = vmv::group_any<G>({gate_term(em, sg)})"
                 f" && !bad{' && VMV_ABLATE_SELF != 8' if id(sg) in dense_ids else ''};  // {sg['a']} vs. {ln}")
         sparse = [gi for gi, sg in enumerate(groups) if id(sg) not in dense_ids]
         dense = [gi for gi, sg in enumerate(groups) if id(sg) in dense_ids]
@@ -1174,6 +1192,27 @@ def emit_robot(m):
     L.append("        return bad;")
     L.append("    }")
     L.append(f"    constexpr int kSelfPasses = {len(batches)};")
+    L.append("")
+
+    # ---- the screen of the self-collision half --------------------------------------------------------------------
+    screen = any_gate_rate < SELF_SCREEN_MAX_RATE
+    L.append("    // \"Could fkcc_self<1> find anything for q?\": the OR of every group's gate (the same terms as in fkcc_self, without")
+    L.append("    // its `&& !bad`, over all A batches in one walk) on the FK of the bounding centres alone.  False = every gate of")
+    L.append("    // fkcc_self is false and it returns `skip`; true = run fkcc_self.  No LDS.")
+    L.append(f"    // Some gate fires for {any_gate_rate * 100:.1f} % of uniform configurations (SELF_SCREEN_MAX_RATE {SELF_SCREEN_MAX_RATE}).")
+    L.append(f"    constexpr bool kSelfScreen = {'true' if screen else 'false'};")
+    L.append("    __device__ __forceinline__ bool fkcc_self_screen(const float (&q)[kDim])")
+    L.append("    {")
+    L.extend(table_loads)
+    em = Emitter(m, prefix="s", indent="        ")
+    em.lines.append("        bool any = false;")
+    for ln in links:
+        for sg in self_by_b.get(ln, []):
+            em.need([sg["bound_a"], env_by_link[ln]["bound"]])
+            em.lines.append(f"        any |= {gate_term(em, sg)};  // {sg['a']} vs. {ln}")
+    L += em.lines
+    L.append("        return any;")
+    L.append("    }")
     L.append("")
 
     # ---- both halves in one walk of the chain (one FK per configuration) -------------------------------------------
@@ -1377,6 +1416,11 @@ def emit_robot(m):
     L.append("    fkcc_self(const float (&q)[kDim], vmv::lds_ptr slab, const vmv::lds_cptr radii, const bool skip)")
     L.append("    {")
     L.append(f"        return {n}::fkcc_self<G>(q, slab, radii, skip);")
+    L.append("    }")
+    L.append(f"    static constexpr bool kSelfScreen = {n}::kSelfScreen;")
+    L.append("    static __device__ __forceinline__ bool fkcc_self_screen(const float (&q)[kDim])")
+    L.append("    {")
+    L.append(f"        return {n}::fkcc_self_screen(q);")
     L.append("    }")
     L.append("    static __device__ __forceinline__ void sphere_fk(const float (&q)[kDim], float4 *out)")
     L.append("    {")

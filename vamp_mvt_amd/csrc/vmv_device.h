@@ -1605,17 +1605,10 @@ namespace vmv
         uint32_t next_pass;                          // passes claimed so far
     };
 
-    // One wave (lane = its lane number): reads words [w0, w0 + nw) of `bits`, clears the bits at or beyond n in the batch's
-    // last word `last` (tail = n % 64), stores the words as read and as to be edited, builds their prefix and resets the
-    // pass counter.  The caller makes the workgroup wait for it.
-    __device__ __forceinline__ void self_share_load(SelfShare &S, const uint64_t *__restrict__ bits, const uint32_t w0,
-                                                    const uint32_t nw, const uint32_t last, const uint32_t tail,
-                                                    const uint32_t lane)
+    // One wave (lane = its lane number; lane k holds word k of the share, 0 beyond it): stores the words the passes are to
+    // enumerate, builds their popcount prefix and resets the pass counter.  The caller makes the workgroup wait for it.
+    __device__ __forceinline__ void self_share_enumerate(SelfShare &S, const uint64_t mine, const uint32_t lane)
     {
-        uint64_t mine = (lane < nw) ? bits[w0 + lane] : 0ull;
-        // vmv_validate_batch_self is an entry point of its own: a caller's words may have bits set at or beyond n (all-ones
-        // words); they are cleared here, so no configuration past the end of the batch is ever read
-        if (w0 + lane == last && tail != 0u) mine = (mine << (64u - tail)) >> (64u - tail);
         uint32_t incl = (uint32_t) __popcll(mine);
 #pragma unroll
         for (uint32_t d = 1; d < kSelfShareWords; d <<= 1)
@@ -1626,19 +1619,34 @@ namespace vmv
         if (lane < kSelfShareWords)
         {
             S.read[lane] = mine;
-            S.result[lane] = mine;
             S.before[lane + 1u] = incl;
         }
         if (lane == 0u) S.before[0] = 0u, S.next_pass = 0u;
     }
 
+    // One wave (lane = its lane number): reads words [w0, w0 + nw) of `bits`, clears the bits at or beyond n in the batch's
+    // last word `last` (tail = n % 64) and stores the words as to be edited and as what the passes enumerate
+    // (self_share_enumerate).  The caller makes the workgroup wait for it.
+    __device__ __forceinline__ void self_share_load(SelfShare &S, const uint64_t *__restrict__ bits, const uint32_t w0,
+                                                    const uint32_t nw, const uint32_t last, const uint32_t tail,
+                                                    const uint32_t lane)
+    {
+        uint64_t mine = (lane < nw) ? bits[w0 + lane] : 0ull;
+        // vmv_validate_batch_self is an entry point of its own: a caller's words may have bits set at or beyond n (all-ones
+        // words); they are cleared here, so no configuration past the end of the batch is ever read
+        if (w0 + lane == last && tail != 0u) mine = (mine << (64u - tail)) >> (64u - tail);
+        if (lane < kSelfShareWords) S.result[lane] = mine;
+        self_share_enumerate(S, mine, lane);
+    }
+
     // The calling wave's next pass: the index, among the share's valid configurations, of its first lane (all lanes alike;
     // at or beyond the share's total when the share is used up).  One LDS atomic per wave and pass, nothing waits.
-    __device__ __forceinline__ uint32_t self_share_claim(SelfShare &S, const uint32_t lane)
+    // (`width`: configurations per pass, <= 64)
+    __device__ __forceinline__ uint32_t self_share_claim(SelfShare &S, const uint32_t lane, const uint32_t width = (uint32_t) kWave)
     {
         uint32_t claim = 0u;
         if (lane == 0u) claim = atomicAdd(&S.next_pass, 1u);
-        return (uint32_t) __builtin_amdgcn_readfirstlane((int) claim) * (uint32_t) kWave;
+        return (uint32_t) __builtin_amdgcn_readfirstlane((int) claim) * width;
     }
 
     // word x 64 + bit of the share's j-th valid configuration; ~0 for j >= total (an idle lane).  The word is the last

@@ -415,7 +415,16 @@ namespace VMV_ROBOT_NS
     // and the kernel lasted 1.6 mean wave lives: profiles/r04_self_stamp_summary.txt).  Nothing is exchanged but the
     // words themselves (no list in memory, no device-scope atomics: the words are edited in LDS and stored once).  The
     // launcher picks `group` so that the grid is one round of resident workgroups.
+    //
+    // SCREEN (robots with R::kSelfScreen; VMV_SELF_SCREEN=0 selects the other instance: measurement and test aid): a share
+    // runs two rounds of passes.  The first runs R::fkcc_self_screen - table bits, the FK of the bounding centres, every
+    // group's gate - on the valid configurations and collects the flagged ones in flag words (LDS atomicOr); one wave then
+    // makes the flag words the enumeration, and the second round runs fkcc_self on the flagged configurations alone, packed
+    // 64 to a pass.  An unflagged configuration has every gate of fkcc_self false, so fkcc_self would have returned `skip`
+    // for it: the words are the same.  The flag words lie in wave 0's slab, which no wave touches before the second round.
+    // The second round deals the flagged configurations evenly over the workgroup's waves (at most 64 per pass).
     static_assert(kSelfShareWords == (uint32_t) kWavesPerBlock * 8u, "a share holds group <= 8 words per wave");
+    template <bool SCREEN>
     __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_kernel(const float *__restrict__ q, const uint32_t n,
                                                                     uint64_t *__restrict__ bits, const uint32_t group)
     {
@@ -425,6 +434,8 @@ namespace VMV_ROBOT_NS
         stage_radii(stage);
         const uint32_t wave = uniform(threadIdx.x / kWave);
         lds_ptr wave_slab = (lds_ptr) stage + kSelfRadiiFloats + wave * self_slab_floats();
+        static_assert(kSelfRadiiFloats % 2u == 0u && self_slab_floats() >= 2u * kSelfShareWords, "the flag words fit a slab");
+        unsigned long long *const flag = (unsigned long long *) (stage + kSelfRadiiFloats);  // [kSelfShareWords], SCREEN only
         const uint32_t words = (n + (uint32_t) kWave - 1u) / (uint32_t) kWave;
         const uint32_t share = group * (uint32_t) kWavesPerBlock;  // <= kSelfShareWords (the launcher clamps group)
         const uint32_t tail = n % (uint32_t) kWave;
@@ -433,16 +444,44 @@ namespace VMV_ROBOT_NS
             const uint32_t nw = (words - w0 < share) ? words - w0 : share;
             // (lane numbers re-derived opaquely: the table addresses built from threadIdx were hoisted out of the loop and
             // spilled)
-            if (wave == 0u) self_share_load(S, bits, w0, nw, words - 1u, tail, opaque_lane_id());
+            if (wave == 0u)
+            {
+                self_share_load(S, bits, w0, nw, words - 1u, tail, opaque_lane_id());
+                if (SCREEN && opaque_lane_id() < kSelfShareWords) flag[opaque_lane_id()] = 0ull;
+            }
             __syncthreads();
-            const uint32_t total = uniform(S.before[nw]);
+            uint32_t total = uniform(S.before[nw]);
+            uint32_t width = (uint32_t) kWave;  // configurations per pass of the (second) round
+            if constexpr (SCREEN)
+            {
+                for (;;)
+                {
+                    const uint32_t pass = self_share_claim(S, opaque_lane_id());
+                    if (pass >= total) break;  // wave-uniform
+                    const uint32_t at = self_share_locate(S, nw, pass + opaque_lane_id(), total);
+                    const uint32_t idx = w0 * (uint32_t) kWave + (at != ~0u ? at : 0u);
+                    float cfg[R::kDim];
+#pragma unroll
+                    for (int d = 0; d < R::kDim; ++d) cfg[d] = q[(size_t) idx * R::kDim + d];
+                    if (R::fkcc_self_screen(cfg) && at != ~0u)
+                        atomicOr(&flag[at / (uint32_t) kWave], 1ull << (at % (uint32_t) kWave));  // LDS atomic
+                }
+                __syncthreads();
+                if (wave == 0u) self_share_enumerate(S, opaque_lane_id() < nw ? flag[opaque_lane_id()] : 0ull, opaque_lane_id());
+                __syncthreads();  // (also: wave 0 has read the flag words before its slab is written)
+                total = uniform(S.before[nw]);
+                // the flagged configurations of a share rarely fill one pass per wave: dealt evenly, no wave waits at the
+                // barrier for another's pass (a pass is a long dependent chain whatever its lanes; self kernel 0.0634 -> 0.0608 ms)
+                width = (total + (uint32_t) kWavesPerBlock - 1u) / (uint32_t) kWavesPerBlock;
+                width = width < 1u ? 1u : (width > (uint32_t) kWave ? (uint32_t) kWave : width);
+            }
             for (;;)
             {
-                const uint32_t pass = self_share_claim(S, opaque_lane_id());
+                const uint32_t pass = self_share_claim(S, opaque_lane_id(), width);
                 if (pass >= total) break;  // wave-uniform: the share is used up
                 VMV_STAMP_PASS;
                 const uint32_t lane = opaque_lane_id();
-                const uint32_t at = self_share_locate(S, nw, pass + lane, total);
+                const uint32_t at = (!SCREEN || lane < width) ? self_share_locate(S, nw, pass + lane, total) : ~0u;
                 const uint32_t idx = w0 * (uint32_t) kWave + (at != ~0u ? at : 0u);  // (a valid bit always lies below n <= 2^31)
                 float cfg[R::kDim];
 #pragma unroll
@@ -1041,7 +1080,7 @@ namespace VMV_ROBOT_NS
                 static const size_t resident = []
                 {
                     int per_cu = 0, dev = 0, cus = 256;
-                    const void *k = (const void *) validate_self_kernel;
+                    const void *k = (const void *) validate_self_kernel<R::kSelfScreen>;
                     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0) != hipSuccess || per_cu < 1)
                         per_cu = R::kSelfBlocks;
                     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1052,6 +1091,9 @@ namespace VMV_ROBOT_NS
                 uint32_t group = (uint32_t) ((words + resident - 1) / resident);
                 if (const char *e = getenv("VMV_SELF_GROUP")) group = (uint32_t) strtoul(e, nullptr, 10);
                 group = group < 1u ? 1u : (group > 8u ? 8u : group);
+                auto self_kernel = validate_self_kernel<R::kSelfScreen>;
+                if (const char *e = getenv("VMV_SELF_SCREEN"))  // "0": the unscreened instance (measurement and test aid)
+                    if (strtoul(e, nullptr, 10) == 0ul) self_kernel = validate_self_kernel<false>;
                 constexpr size_t kSlice = size_t{1} << 31;  // 32-bit counts inside the kernel; slices own whole words
                 for (size_t lo = 0; lo < n; lo += kSlice)
                 {
@@ -1070,7 +1112,7 @@ namespace VMV_ROBOT_NS
                     }
                     VMV_HIP_TU(hipMemsetAsync(d_stamp, 0, blocks * kWavesPerBlock * 4 * sizeof(uint64_t), stream));
 #endif
-                    hipLaunchKernelGGL(validate_self_kernel, dim3(blocks), dim3(kBlock), 0, stream, d_q + lo * R::kDim, m,
+                    hipLaunchKernelGGL(self_kernel, dim3(blocks), dim3(kBlock), 0, stream, d_q + lo * R::kDim, m,
                                        d_bits + lo / kWave, group);
 #ifdef VMV_SELF_STAMP
                     // header: n, group, workgroups, 1 (the shared-pass kernel; files of older builds may hold 0, the per-wave
