@@ -269,6 +269,51 @@ size_t vmv_shard_words(size_t n, int world);
  * scaled by Robot::scale_configuration).  Valid while skip + n <= 1,000,000 (the reference re-seeds after that). */
 int vmv_halton_configs(int robot, uint64_t skip, float *d_q, size_t n, void *stream);
 
+/* ---- lockstep planner: many independent RRT-Connect problems in one call ------------------------------- */
+/* RRT-Connect (planning/rrtc.hh:33-245 without dynamic domain, one goal) for n_problems problems at once, problem p from
+ * starts[p] to goals[p] ([n_problems][dimension] host arrays) in envs[p], its samples the Halton samples
+ * halton_skips[p] + 1, + 2, ... (halton_skips NULL = all 0).  The problems advance in lockstep rounds: per round a step
+ * kernel (nearest neighbour, extension, connect march, tree bookkeeping, termination; one workgroup per unfinished
+ * problem) writes ONE edge question per unfinished problem, and one vmv_validate_motion_batch_multi launch sequence
+ * answers all of them.  Every check_every rounds (0 = the default, 16) the host reads which problems are finished and
+ * drops them from the next rounds.  A problem's result depends on its own inputs alone, bit for bit (DESIGN §5c gives the
+ * arithmetic: fp32, one rounding per operation, the first nearest node on ties).  Each problem owns a pool of max_samples
+ * nodes on the device (max_samples * (dimension + 1) * 4 bytes) and never holds more.
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / starts / goals / settings / out
+ * or a NULL handle, range not finite or <= 0, max_samples < 2, halton skip + max_iterations > 1,000,000 (the sequence's
+ * validity limit, as vmv_halton_configs), n_problems >= 2^31 (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment
+ * (VMV_ERR_NOT_FINALIZED); an environment of another device (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out
+ * untouched.  n_problems == 0 is VMV_OK with an empty result.  A start or goal with a non-finite joint: that problem ends
+ * unsolved (every edge from or to it is invalid).  Environments not yet prepared for the robot are prepared in one batch.
+ * Synchronous, host buffers, on the default stream; repeated handles are allowed. */
+typedef struct
+{
+    float range;                 /* rrtc_settings.hh: range */
+    int balance;                 /* 0 / 1 */
+    float tree_ratio;
+    uint32_t max_iterations, max_samples;
+    uint32_t check_every;        /* rounds between two looks of the host at the finished flags; 0 = default */
+} vmv_rrtc_settings;
+typedef struct vmv_plans vmv_plans;
+enum
+{
+    VMV_PLAN_SOLVED = 0,
+    VMV_PLAN_MAX_ITERATIONS = 1, /* the loop ended because iterations reached max_iterations (checked first) */
+    VMV_PLAN_MAX_SAMPLES = 2     /* ... because the two trees together hold max_samples nodes */
+};
+int vmv_rrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                   const uint64_t *halton_skips, const vmv_rrtc_settings *settings, vmv_plans **out);
+/* Per problem (arrays of n_problems, any may be NULL): status (VMV_PLAN_*), iterations, sizes2 = |A|, |B| as the
+ * planner's last iteration named the trees (PlanningResult::size), path_lengths in waypoints (0 = unsolved).  Totals (may
+ * be NULL): rounds = validation launches made, questions = edge questions the problems asked (the null questions of
+ * finished problems not counted). */
+int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterations, uint32_t *sizes2,
+                      uint32_t *path_lengths, uint64_t *rounds, uint64_t *questions);
+/* every path's waypoints ([path_length][dimension] each, the stored node bits, start first), packed in problem order;
+ * VMV_ERR_CAPACITY if capacity_floats is too small (nothing is written) */
+int vmv_plans_paths(const vmv_plans *plans, float *out, size_t capacity_floats);
+int vmv_plans_destroy(vmv_plans *plans);
+
 /* ---- measurement support (bench.py) ---------------------------------------------------------------------- */
 /* Runs vmv_validate_batch `iters` times on `stream` between two HIP events recorded on that same stream and
  * returns the average kernel time in milliseconds. */

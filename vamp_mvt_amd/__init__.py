@@ -646,6 +646,60 @@ class _Robot(types.ModuleType):
         handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
         check(lib.vmv_env_prepare_multi(self._id, handles, len(envs)), "vmv_env_prepare_multi")
 
+    def rrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
+        """vmv_rrtc_multi: lockstep RRT-Connect, problem p from starts[p] to goals[p] in environments[p] (None = the
+        empty environment) with the Halton samples skips[p] + 1, ... (None = all 0).  settings: range, balance,
+        tree_ratio, max_iterations, max_samples and optionally check_every.  -> dict of per-problem numpy arrays
+        (status, iterations, sizes [n][2], path_lengths), the packed waypoints (paths [sum(path_lengths)][dim]) and
+        the totals rounds and questions.  planning.rrtc_multi is the caller-facing form.  Every argument is checked
+        before any library call."""
+        environments = list(environments)
+        for e in environments:
+            if e is not None and not isinstance(e, Environment):
+                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = a.shape[0]
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        if skips is None:
+            sk = None
+        else:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        rng, ratio = float(settings.range), float(settings.tree_ratio)
+        max_it, max_s, every = int(settings.max_iterations), int(settings.max_samples), int(getattr(settings, "check_every", 0))
+        if not (math.isfinite(rng) and rng > 0):
+            raise ValueError("range must be finite and positive")
+        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32):
+            raise ValueError("max_iterations, max_samples (>= 2) and check_every must fit 32 bits")
+        cs = _lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every)
+        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
+        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+        handles = (ctypes.c_void_p * max(n, 1))(*[e.handle() for e in envs])
+        plans = ctypes.c_void_p()
+        check(lib.vmv_rrtc_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
+                                 ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
+                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
+                  "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
+                    rounds=int(rounds.value), questions=int(questions.value))
+
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty
         environment), in one call.  The same answers as one validate_batch per environment, concatenated.  numpy in ->

@@ -24,6 +24,12 @@ STATUS_NAMES = {0: "VMV_OK", 1: "VMV_ERR_INVALID_ARGUMENT", 2: "VMV_ERR_NO_DEVIC
                 4: "VMV_ERR_CAPACITY", 5: "VMV_ERR_NOT_FINALIZED", 6: "VMV_ERR_UNKNOWN_ROBOT", 7: "VMV_ERR_FINALIZED"}
 
 
+class RrtcSettings(ctypes.Structure):
+    """vmv_rrtc_settings"""
+    _fields_ = [("range", ctypes.c_float), ("balance", ctypes.c_int), ("tree_ratio", ctypes.c_float),
+                ("max_iterations", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -117,6 +123,11 @@ def _load():
         "vmv_validate_motion_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V, V]),
         "vmv_validate_motion_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_float_p, c_u64_p]),
         "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
+        "vmv_rrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(RrtcSettings),
+                               ctypes.POINTER(V)]),
+        "vmv_plans_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_plans_paths": (I, [V, c_float_p, S]),
+        "vmv_plans_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

@@ -287,6 +287,22 @@ def install(robot):
                                   max_samples=int(settings.max_samples))
         return as_result(planning.rrtc(robot, _cfg(robot, start), _goals(robot, goal), environment, s, rng), t0)
 
+    def rrtc_multi(starts, goals, environments, settings, skips=None):
+        """planning.rrtc_multi with this robot: many RRT-Connect problems in lockstep on the device ->
+        list[PlanningResult] (each with `status`; nanoseconds is the whole call's time divided by the problems)"""
+        t0 = time.perf_counter_ns()
+        s = planning.RRTCMultiSettings(range=float(settings.range), balance=bool(settings.balance),
+                                       tree_ratio=float(settings.tree_ratio), max_iterations=int(settings.max_iterations),
+                                       max_samples=int(settings.max_samples), check_every=int(getattr(settings, "check_every", 0)))
+        results = planning.rrtc_multi(robot, starts, goals, environments, s, skips)
+        each = (time.perf_counter_ns() - t0) // max(len(results), 1)
+        out = []
+        for r in results:
+            res = as_result(r, t0)
+            res.nanoseconds, res.status = each, r.status
+            out.append(res)
+        return out
+
     def fcit(start, goal, environment, settings, rng):
         t0 = time.perf_counter_ns()
         s = planning.FCITSettings(batch_size=int(settings.batch_size), max_samples=int(settings.max_samples),
@@ -364,6 +380,7 @@ def install(robot):
         return PlanningResult(res, time.perf_counter_ns() - t0, 0, [], res.cost() if len(res) >= 2 else 0.0)
 
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
+    robot.rrtc_multi = rrtc_multi
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 

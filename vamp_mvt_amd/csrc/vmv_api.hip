@@ -187,26 +187,13 @@ namespace vmv
         q[i] = lower[j] + span[j] * u;
     }
 
-    // Halton sample (skip + 1 + row) of the reference's sequence, element j (random/halton.hh:75-108): the
-    // incremental float arithmetic there keeps exact integers n, d = b^k, so the value is n / d with n the
-    // digit-reversed index; then Robot::scale_configuration (q * s_m + s_a, two roundings).
+    // Halton sample (skip + 1 + row) of the reference's sequence, element j (halton_element, vmv_common.h)
     __global__ void halton_kernel(float *q, size_t total, int dim, uint64_t skip, const float *lower, const float *span)
     {
         const size_t idx = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
         if (idx >= total) return;
-        const uint32_t primes[16] = {3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59};
         const int j = (int) (idx % (size_t) dim);
-        uint64_t k = skip + idx / (size_t) dim + 1;
-        const uint32_t b = primes[j];
-        uint32_t n = 0, d = 1;
-        while (k > 0)
-        {
-            n = n * b + (uint32_t) (k % b);
-            d *= b;
-            k /= b;
-        }
-        const float u = (float) n / (float) d;
-        q[idx] = u * span[j] + lower[j];
+        q[idx] = halton_element(skip + idx / (size_t) dim + 1, j, lower[j], span[j]);
     }
 
     // sphere_environment_in_collision (collision/validity.hh:47-158) for a batch of free spheres, one lane per sphere

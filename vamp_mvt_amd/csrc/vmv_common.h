@@ -89,6 +89,25 @@ namespace vmv
 
     int hip_status(hipError_t e, const char *what);  // records vmv_last_error(), maps to VMV_ERR_*
 
+    // Element j of Halton sample number k (1-based) of the reference's sequence (random/halton.hh:75-108): the
+    // incremental float arithmetic there keeps exact integers n, d = b^digits, so the value is n / d with n the
+    // digit-reversed index; then Robot::scale_configuration (q * s_m + s_a, two roundings).  The
+    // reference's sequence up to k = 1,000,000 (it re-seeds after that).  Shared by halton_kernel and the lockstep planner.
+    __device__ __forceinline__ float halton_element(uint64_t k, int j, float lower, float span)
+    {
+        static constexpr uint32_t primes[16] = {3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59};
+        const uint32_t b = primes[j];
+        uint32_t n = 0, d = 1;
+        while (k > 0)
+        {
+            n = n * b + (uint32_t) (k % b);
+            d *= b;
+            k /= b;
+        }
+        const float u = (float) n / (float) d;
+        return u * span + lower;
+    }
+
     // ---- vmv_env_prepare_multi: grids and reach certificates of many environments (vmv_env_prepare.hip) ----
     constexpr uint32_t kPrepMaxPrims = 128;  // primitives of an environment that has grid_prims (4 candidate words)
     struct PrepPrim  // vmv::GridPrim with its parameters in place

@@ -86,6 +86,22 @@ class RRTCSettings:
 
 
 @dataclass
+class RRTCMultiSettings:
+    """settings of `rrtc_multi`: those of RRTCSettings, except that max_samples defaults to 8,192 — every problem of a
+    call owns a node pool of max_samples nodes on the device — and check_every (rounds between two looks of the host at
+    which problems are finished; 0 = the library's default)"""
+    range: float = 2.0
+    balance: bool = True
+    tree_ratio: float = 1.0
+    max_iterations: int = 100000
+    max_samples: int = 8192
+    check_every: int = 0
+
+
+PLAN_STATUS = ("solved", "max_iterations", "max_samples")  # VMV_PLAN_*
+
+
+@dataclass
 class PlanningResult:
     """planning/plan.hh:172-179"""
     path: list = field(default_factory=list)
@@ -95,6 +111,7 @@ class PlanningResult:
     cost: float = float("inf")
     edges_checked: int = 0
     samples_drawn: int = 0
+    status: str = ""  # rrtc_multi: one of PLAN_STATUS
 
     @property
     def solved(self):
@@ -187,6 +204,38 @@ def rrtc(robot, start, goal, environment, settings: RRTCSettings | None = None, 
             return res
     res.size = [len(tree_a.parent), len(tree_b.parent)]
     return res
+
+
+def rrtc_multi(robot, starts, goals, environments, settings: RRTCMultiSettings | None = None, skips=None):
+    """RRT-Connect for many independent problems in lockstep on the device: problem p from starts[p] to goals[p]
+    ([n][dim] arrays, one goal each) in environments[p] (None = the empty environment), sampling the Halton samples
+    skips[p] + 1, skips[p] + 2, ... (None = 0 for all).  -> list[PlanningResult], one per problem: `path` (waypoints,
+    empty if unsolved), `iterations`, `size` = [|A|, |B|] and `status` (one of PLAN_STATUS).
+
+    Per round every unfinished problem asks one edge question and ONE validate_motion_batch_multi launch sequence
+    answers all of them; nearest-neighbour search, extension, connect march and bookkeeping run in a device kernel, so
+    a round costs a handful of launches however many problems are in flight.
+
+    The decisions are those of `rrtc` (rrtc.hh without dynamic domain), in fp32 with one rounding per operation and
+    the first nearest node on ties, so a problem's result is defined bit for bit and does not depend on the other
+    problems of the call.  Agreement with `rrtc` itself is NOT pinned: where `range` is not an fp32 number, or numpy's
+    float64 intermediates round differently, `rrtc` may take another decision.
+
+    The default max_samples of this call is 8,192 (RRTCMultiSettings), not rrtc's 100,000: the node pool is
+    allocated per problem, max_samples * (dim + 1) * 4 bytes each.  skips[p] + max_iterations may not exceed 1,000,000
+    (the Halton sequence's validity limit)."""
+    s = settings or RRTCMultiSettings()
+    raw = robot.rrtc_multi_raw(starts, goals, environments, s, skips)
+    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+    out = []
+    for p in range(len(ends)):
+        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
+        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
+                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])],
+                                  status=PLAN_STATUS[int(raw["status"][p])]))
+    if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
+        out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
+    return out
 
 
 def validate_path(robot, path, environment) -> bool:
