@@ -3,8 +3,10 @@
 // under /root/reference (never copied).  Only headers that need no third-party
 // library are used: vamp/vector.hh (+vector/{interface,avx,utils}.hh,
 // constants.hh, utils.hh) and vamp/random/halton.hh.  Everything that pulls
-// Eigen / pdqsort / nigh (collision/*, robots/*, planning/*) is unbuildable in
-// this image and is NOT stubbed.
+// Eigen / nigh (collision/shapes.hh and what includes it, robots/*,
+// planning/*) is unbuildable in this image and is NOT stubbed.  The four
+// point-cloud headers of collision/ (mvt.hh, capt.hh, filter.hh,
+// filter_centervox.hh) do build: see oracle/ref_cloud.cc.
 //
 // Used by tests/ and tools/ to pin the arithmetic contract of SURVEY.md §2
 // (sin, cos, approximate sqrt, hsum / l2_norm, test_zero, Halton sequence).

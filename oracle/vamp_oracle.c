@@ -581,7 +581,9 @@ static void subdivide(capt_builder *b, uint32_t points_begin, uint32_t how_many,
 /* capt.hh:296-369 */
 int vo_env_add_capt(vo_env *e, const float *pts, size_t n, float r_min, float r_max, float r_point)
 {
-    if (n < 2) return -1;
+    /* one point: the reference builds a one-leaf tree (nlog2 = 0, no tests) that CAPT::collides answers; its
+     * collides_simd reads tests[0] of that empty vector (capt.hh:445), so the product refuses n < 2 */
+    if (n < 1) return -1;
     vo_capt c;
     memset(&c, 0, sizeof(c));
     c.r_min = r_min;
@@ -929,8 +931,9 @@ int vo_env_mvt_view(const vo_env *e, size_t index, vo_mvt_view *out)
 }
 
 /* MVT::collides (mvt.hh:204-279) == one lane of collides_simd (mvt.hh:282-403; the 8-point SIMD chunks read the
- * voxel's +inf padding, which never collides).  Float -> uint16 casts are applied to in-range values exactly as
- * written; where the reference's cast would be undefined (negative upper bound) the range is empty here. */
+ * voxel's +inf padding, which never collides).  Float -> uint16 casts are applied exactly as written: an upper bound in
+ * (-1, 0) truncates to cell 0 (defined, and what the compiled reference does: tests/golden/ref_mvt.npz); where the
+ * reference's cast would be undefined (upper bound <= -1) the range is empty here. */
 static int mvt_collides_lane(const vo_mvt *m, float cx, float cy, float cz, float radius)
 {
     const float c[3] = {cx, cy, cz};
@@ -945,9 +948,9 @@ static int mvt_collides_lane(const vo_mvt *m, float cx, float cy, float cz, floa
         const float g = (c[k] - m->ws_min[k]) * m->inv_scale;
         const float a = fmaxf(0.0f, g - gqr);
         const float b = fminf((float) (m->grid_width - 1), g + gqr);
-        if (b < 0.0f) return 0;
+        if (b <= -1.0f) return 0;
         lo[k] = (int) (uint16_t) a;
-        hi[k] = (int) (uint16_t) b;
+        hi[k] = (int) (uint16_t) fmaxf(b, 0.0f);
     }
     const uint32_t gw = m->grid_width;
     for (int vx = lo[0]; vx <= hi[0]; ++vx)

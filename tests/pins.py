@@ -114,3 +114,23 @@ def brute_force_collides(cloud, c, r, r_point):
     d2 = (d2 + (d[..., 2] * d[..., 2]).astype(np.float32)).astype(np.float32)
     rr = (r + F(r_point)).astype(np.float32)
     return (d2 <= (rr * rr).astype(np.float32)[:, None]).any(1)
+
+
+def scene_cloud(n, seed, spread=1.6):
+    """points on a few boxes / a cylinder around the robot plus outliers beyond the cull range (and a culled point 0)"""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for _ in range(5):
+        c = rng.uniform(-0.9, 0.9, 3) + [0, 0, 0.4]
+        half = rng.uniform(0.05, 0.3, 3)
+        p = rng.uniform(-1, 1, (n // 6, 3)) * half
+        face = rng.integers(0, 3, len(p))
+        p[np.arange(len(p)), face] = np.sign(p[np.arange(len(p)), face]) * half[face]
+        parts.append(c + p)
+    a = rng.uniform(0, 2 * np.pi, n - 5 * (n // 6))
+    parts.append(np.stack([0.5 + 0.1 * np.cos(a), -0.4 + 0.1 * np.sin(a), rng.uniform(0, 0.8, len(a))], 1))
+    pc = np.concatenate(parts).astype(np.float32)
+    rng.shuffle(pc)
+    pc[::97] *= np.float32(spread)  # some points outside the range / workspace
+    pc[0] = [3.0, -2.5, 0.1]        # point 0 is culled: exercises the reference's tail entries (filter.hh:195-216)
+    return pc

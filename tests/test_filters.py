@@ -1,37 +1,20 @@
 """Point-cloud filters: vamp.filter_pointcloud with filter_type "scdf" (collision/filter.hh:175-275)
 and "centervox" (collision/filter_centervox.hh).
 
-Oracle = oracle/vamp_oracle.c (vo_filter_scdf / vo_filter_centervox).  Parity unpinned against the reference itself:
-it cannot be built here (pdqsort, nanobind) and ships no filter fixtures; the restatement follows the source text, with
-equal Morton codes kept in their current order (the reference's pdqsort leaves that order open).  CPU tests pin the
-oracle against an independent slow Python restatement and against the filters' defining properties; the GPU tests
-compare the HIP implementation with the oracle point for point, in order."""
+Oracle = oracle/vamp_oracle.c (vo_filter_scdf / vo_filter_centervox).  Both filters are pinned against the reference's
+own headers compiled in place (tests/test_ref_cloud_pins.py and its GPU twin, tests/golden/ref_{scdf,centervox}.npz)
+wherever the answer is independent of tie order; the restatement keeps equal Morton codes in their current order (the
+reference's pdqsort leaves that order open).  The tests here pin the oracle against an independent slow Python
+restatement and against the filters' defining properties, and compare the HIP implementation with the oracle point for
+point, in order, at the larger sizes."""
 import numpy as np
 import pytest
+
+from pins import scene_cloud
 
 ORIGIN = np.array([0.0, 0.0, 0.333], np.float32)  # Panda first joint (reference src/vamp/constants.py)
 RANGE = np.float32(1.19)
 LO, HI = ORIGIN - RANGE, ORIGIN + RANGE
-
-
-def scene_cloud(n, seed, spread=1.6):
-    """points on a few boxes / a cylinder around the robot plus outliers beyond the cull range (and a culled point 0)"""
-    rng = np.random.default_rng(seed)
-    parts = []
-    for _ in range(5):
-        c = rng.uniform(-0.9, 0.9, 3) + [0, 0, 0.4]
-        half = rng.uniform(0.05, 0.3, 3)
-        p = rng.uniform(-1, 1, (n // 6, 3)) * half
-        face = rng.integers(0, 3, len(p))
-        p[np.arange(len(p)), face] = np.sign(p[np.arange(len(p)), face]) * half[face]
-        parts.append(c + p)
-    a = rng.uniform(0, 2 * np.pi, n - 5 * (n // 6))
-    parts.append(np.stack([0.5 + 0.1 * np.cos(a), -0.4 + 0.1 * np.sin(a), rng.uniform(0, 0.8, len(a))], 1))
-    pc = np.concatenate(parts).astype(np.float32)
-    rng.shuffle(pc)
-    pc[::97] *= np.float32(spread)  # some points outside the range / workspace
-    pc[0] = [3.0, -2.5, 0.1]        # point 0 is culled: exercises the reference's tail entries (filter.hh:195-216)
-    return pc
 
 
 def slow_scdf(pc, min_dist, max_range, origin, lo, hi, cull):

@@ -1,10 +1,12 @@
 """Multi-level Voxel Table (collision/mvt.hh): oracle consistency, product host build vs oracle,
-and the HIP query vs the oracle on the GPU."""
+and the HIP query vs the oracle on the GPU.  The oracle's build and query, the host builder and the HIP query are pinned
+against mvt.hh itself, compiled in place, by tests/test_ref_cloud_pins.py and its GPU twin (tests/golden/ref_mvt.npz)."""
 import ctypes
 
 import numpy as np
 import pytest
 
+from cloud_pins import mvt_pool_cases
 from envs import WORKSPACE, make_env
 from vamp_mvt_amd.workloads import shell_cloud
 
@@ -60,14 +62,7 @@ def test_mvt_pool_limits_match_between_product_and_oracle(vamp, oracle):
         lib.vmv_env_destroy(h)
         return rc, reason.value, info
 
-    cases = [
-        (shell_cloud(1500, 3, 0.5, 1.0, 0.0, 1.2), PANDA),                     # fits
-        (shell_cloud(10000, 3), PANDA),                                         # pools run out
-        (np.random.default_rng(0).uniform(-1, 1, (5000, 3)).astype(np.float32), PANDA),   # > 10 % of voxels
-        (np.tile(np.array([[0.5, 0.5, 0.5]], np.float32), (70, 1)) + np.float32(1e-4) * np.arange(70)[:, None], PANDA),
-        (shell_cloud(300, 4), (0.012, 0.24, *WORKSPACE["fetch"], 0.0025)),
-        (shell_cloud(50, 4), (0.012, 0.5, *WORKSPACE["baxter"], 0.0025)),
-    ]
+    cases = mvt_pool_cases()  # shared with the reference-compiled pins, which record what the reference itself does
     outcomes = []
     for pts, args in cases:
         e = oracle.env()

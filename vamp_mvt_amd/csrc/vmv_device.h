@@ -690,8 +690,10 @@ namespace vmv
     // independent there, the 8-point chunks only add +inf padding that never collides).  Per lane: global box
     // test, the <= 3 x 3 x 3 cells around the centre (grid_query_radius is clamped to one cell, which is what makes
     // the answer structure-dependent for radii above r_max), voxel box cull, then the voxel's points with `<=`.
-    // Float -> uint16 casts apply to in-range values as written; where the reference's cast is undefined
-    // (negative upper bound, outside the global-box pre-test only for radii > 1 cell) the range is empty.
+    // Float -> uint16 casts apply as written: an upper bound in (-1, 0) truncates to cell 0, as the reference's cast
+    // does (a centre just below the workspace whose reach ends on a point of its first cell; pinned by
+    // tests/golden/ref_mvt.npz); where the reference's cast is undefined (upper bound <= -1, past the global-box
+    // pre-test only for radii > 1 cell) the range is empty.
     __device__ __forceinline__ bool
     mvt_collides(env_cptr D, const uint32_t mi, float x, float y, float z, float r, bool active)
     {
@@ -710,7 +712,7 @@ namespace vmv
         const float gx = (x - D->mvt[mi].ws_min[0]) * isf, gy = (y - D->mvt[mi].ws_min[1]) * isf,
                     gz = (z - D->mvt[mi].ws_min[2]) * isf;
         const float bx = fminf(top, gx + gqr), by = fminf(top, gy + gqr), bz = fminf(top, gz + gqr);
-        in = in && !(bx < 0.0f || by < 0.0f || bz < 0.0f);
+        in = in && !(bx <= -1.0f || by <= -1.0f || bz <= -1.0f);
         const uint32_t x0 = (uint32_t) (uint16_t) fmaxf(0.0f, gx - gqr), y0 = (uint32_t) (uint16_t) fmaxf(0.0f, gy - gqr),
                        z0 = (uint32_t) (uint16_t) fmaxf(0.0f, gz - gqr);
         const uint32_t x1 = (uint32_t) (uint16_t) fmaxf(bx, 0.0f), y1 = (uint32_t) (uint16_t) fmaxf(by, 0.0f),
