@@ -90,11 +90,20 @@ int vmv_env_add_sphere(vmv_env *env, float x, float y, float z, float r);
  * axis_3 xyz | half extents 1..3 (collision/shapes.hh:32-49).  Filed as z-aligned iff axis_3_z == 1. */
 int vmv_env_add_cuboid(vmv_env *env, const float *params15);
 /* Environment.add_capsule — environment.cc:134-147.  8 floats: x1 y1 z1 | xv yv zv | r | rdv
- * (collision/shapes.hh:128-143).  Filed as z-aligned iff xv == 0 and yv == 0. */
+ * (collision/shapes.hh:128-143).  Filed as z-aligned iff xv == 0 and yv == 0.
+ * min_distance is collision/shapes.hh:165-189, with one rule where that is not a number: if the origin lies on the
+ * capsule's axis the reference divides 0 by 0; the true distance, 0, is stored instead, and so is any min_distance that
+ * is still not finite (a zero-length capsule with rdv = inf).  Such an entry sorts first and never triggers the sorted
+ * early break (for any sphere with max_extent > 0).  This reproduces the reference wherever its own sorted order is
+ * defined (the capsule inserted first); where it is not, the environment answers the OR of the reference's predicates
+ * over every capsule. */
 int vmv_env_add_capsule(vmv_env *env, const float *params8);
 /* make_heightfield(center, scaling, dimensions, data) + Environment.add_heightfield — collision/factory.hh:363-423,
  * bindings/environment.cc:100,149-151, collision/shapes.hh:250-312.  data: host pointer, row-major [yd][xd] fp32;
- * scale3 as given to make_heightfield (the shape stores the reciprocals).  At most 4 per environment. */
+ * scale3 as given to make_heightfield (the shape stores the reciprocals).  At most 4 per environment.
+ * Cell index (collision/sphere_heightfield.hh:20-26): clamped to [0, xd] x [0, yd], one past the image on both axes.
+ * xs == xd in any row but the last reads the first cell of the next row, as in the reference; xs == xd in the last
+ * row and ys == yd are past the reference's buffer (undefined there) and read the last pixel here. */
 int vmv_env_add_heightfield(vmv_env *env, const float *center3, const float *scale3, size_t xd, size_t yd,
                             const float *data);
 int vmv_env_heightfield_count(const vmv_env *env, size_t *count);

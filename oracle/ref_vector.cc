@@ -2,11 +2,13 @@
 // reference's own dependency-free SIMD layer, compiled from where it lies
 // under /root/reference (never copied).  Only headers that need no third-party
 // library are used: vamp/vector.hh (+vector/{interface,avx,utils}.hh,
-// constants.hh, utils.hh) and vamp/random/halton.hh.  Everything that pulls
-// Eigen / nigh (collision/shapes.hh and what includes it, robots/*,
-// planning/*) is unbuildable in this image and is NOT stubbed.  The four
-// point-cloud headers of collision/ (mvt.hh, capt.hh, filter.hh,
-// filter_centervox.hh) do build: see oracle/ref_cloud.cc.
+// constants.hh, utils.hh) and vamp/random/halton.hh.  Everything that USES
+// Eigen / nigh (collision/factory.hh, Attachment::pose, robots/*, planning/*)
+// is unbuildable in this image and is NOT stubbed.  The four point-cloud
+// headers of collision/ (mvt.hh, capt.hh, filter.hh, filter_centervox.hh) do
+// build: see oracle/ref_cloud.cc.  So do collision/shapes.hh, environment.hh,
+// validity.hh and the sphere_*.hh predicates, which include Eigen headers
+// without calling anything from them: see oracle/ref_prims.cc.
 //
 // Used by tests/ and tools/ to pin the arithmetic contract of SURVEY.md §2
 // (sin, cos, approximate sqrt, hsum / l2_norm, test_zero, Halton sequence).

@@ -247,8 +247,13 @@ static float dot3(float ax, float ay, float az, float bx, float by, float bz)
 {
     return (ax * bx) + (ay * by) + (az * bz); /* collision/math.hh:16-26 */
 }
-/* scalar clamp<float> (collision/math.hh:47-51): max(min(v, upper), lower) */
-static float sclamp(float v, float lo, float hi) { return fmaxf(fminf(v, hi), lo); }
+/* scalar clamp<float> (collision/math.hh:47-51): std::max(std::min(v, upper), lower), whose comparisons hand a NaN back
+ * (fminf / fmaxf would drop it: the reference's min_distance of a zero-length capsule is a NaN) */
+static float sclamp(float v, float lo, float hi)
+{
+    const float m = (hi < v) ? hi : v;
+    return (m < lo) ? lo : m;
+}
 
 #define SORT_BY_MIN_DISTANCE(T, name)                                     \
     static int name(const void *a, const void *b)                         \
@@ -306,19 +311,23 @@ void vo_env_add_cuboid(vo_env *e, const float *p)
     }
 }
 
-/* collision/shapes.hh:165-189 */
+/* collision/shapes.hh:165-189.  Where the reference divides 0 by 0 (ol == 0: the origin lies on the capsule's axis) the
+ * true distance, 0, is stored, and so is any value that is still not finite (a zero-length capsule with rdv = inf): the
+ * product's rule (include/vamp_mvt_amd.h).  It reproduces the reference wherever the reference's own order is defined. */
 static float capsule_min_distance(const vo_capsule *c)
 {
     const float dot = sclamp(dot3(-c->x1, -c->y1, -c->z1, c->xv, c->yv, c->zv) * c->rdv, 0.F, 1.F);
     const float xp = c->x1 + c->xv * dot, yp = c->y1 + c->yv * dot, zp = c->z1 + c->zv * dot;
     float xo = -xp, yo = -yp, zo = -zp;
     const float ol = sqrtf(dot3(xo, yo, zo, xo, yo, zo));
+    if (ol == 0.F) return 0.F;
     xo = xo / ol;
     yo = yo / ol;
     zo = zo / ol;
     const float ro = sclamp(ol, 0.F, c->r);
     const float xn = xp + ro * xo, yn = yp + ro * yo, zn = zp + ro * zo;
-    return sqrtf(xn * xn + yn * yn + zn * zn);
+    const float d = sqrtf(xn * xn + yn * yn + zn * zn);
+    return isfinite(d) ? d : 0.F;
 }
 
 /* environment.cc:134-147: z-aligned iff xv == 0 and yv == 0 */
@@ -1130,6 +1139,11 @@ static int sphere_environment_in_collision(const vo_env *e, const float *sx, con
 int vo_sphere_environment_in_collision(const vo_env *e, const float c[3], float r)
 {
     return sphere_environment_in_collision(e, &c[0], &c[1], &c[2], r, 1);
+}
+void vo_spheres_in_collision(const vo_env *e, const float *spheres_xyzr, size_t n, uint8_t *out)
+{
+    for (size_t i = 0; i < n; ++i)
+        out[i] = (uint8_t) vo_sphere_environment_in_collision(e, spheres_xyzr + 4 * i, spheres_xyzr[4 * i + 3]);
 }
 
 /* ------------------------------------------------------------------------- */

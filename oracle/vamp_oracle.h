@@ -13,14 +13,18 @@
  * tools/ref_fk_eval.py; sin/cos/l2_norm/Halton are checked against the
  * reference's own vector.hh / halton.hh compiled in place (oracle/_ref); whole
  * pipeline known answers come from SURVEY.md §8c (sphere cage, Halton counts).
- * Not pinned by any reference artefact: cuboid/capsule tests and the CAPT
- * build/query beyond the survey's recorded statistics ("parity unpinned").
+ * The primitive tests, min_distance, the per-list sort and the sorted early
+ * break are checked against collision/validity.hh compiled in place
+ * (oracle/ref_prims.cc, tests/golden/ref_prims.npz).  Not pinned by any
+ * reference artefact: attachments ("parity unpinned").
  *
  * Arithmetic contract: IEEE fp32, one rounding per written operation
  * (compile with -ffp-contract=off, no fast-math).  The only deliberate
  * deviation from the reference: `max_extent` in the sorted early-break uses a
  * correctly rounded sqrt instead of AVX `v * rsqrt_ps(v)` (vector/avx.hh:411-415),
- * whose low bits are vendor-defined and therefore not reproducible.
+ * whose low bits are vendor-defined and therefore not reproducible.  One
+ * rule where the reference has none: a capsule min_distance that is not
+ * finite is stored as 0 (include/vamp_mvt_amd.h, vmv_env_add_capsule).
  */
 #ifndef VAMP_ORACLE_H
 #define VAMP_ORACLE_H
@@ -108,6 +112,8 @@ int vo_capt_collides_simd(const vo_env *e, size_t index, const float *cx, const 
 
 /* sphere_environment_in_collision (collision/validity.hh:47-158) for one sphere (a rake of one lane); 1 = collides */
 int vo_sphere_environment_in_collision(const vo_env *e, const float c[3], float r);
+/* the same for spheres[n][4] = x y z r, each on its own: out[i] = 1 collides / 0 free */
+void vo_spheres_in_collision(const vo_env *e, const float *spheres_xyzr, size_t n, uint8_t *out);
 
 /* filter_pointcloud(pc, min_dist, max_range, origin, workspace_min, workspace_max, cull) — collision/filter.hh:175-275
  * ("scdf", the space-filling-curve filter); out_xyz has room for n points; returns how many were kept. */

@@ -85,6 +85,7 @@ class Oracle:
         L.vo_capt_collides.argtypes = [ctypes.c_void_p, ctypes.c_size_t, _fp, ctypes.c_float]
         L.vo_capt_collides_simd.argtypes = [ctypes.c_void_p, ctypes.c_size_t, _fp, _fp, _fp, _fp, ctypes.c_int]
         L.vo_sphere_environment_in_collision.argtypes = [ctypes.c_void_p, _fp, ctypes.c_float]
+        L.vo_spheres_in_collision.argtypes = [ctypes.c_void_p, _fp, ctypes.c_size_t, _u8p]
         for fn in ("vo_filter_scdf", "vo_filter_centervox"):
             getattr(L, fn).restype = ctypes.c_size_t
         L.vo_filter_scdf.argtypes = [_fp, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp, ctypes.c_int, _fp]
@@ -325,6 +326,13 @@ class OracleEnv:
         out = np.zeros((max(n, 1), 9), np.float32)
         self.o.L.vo_env_get_capsules(self.h, int(z_aligned), _f(out))
         return out[:n]
+
+    def spheres_in_collision(self, spheres):
+        """sphere_environment_in_collision for spheres[n][4] = x y z r, each on its own -> bool[n]"""
+        s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        out = np.zeros(len(s), np.uint8)
+        self.o.L.vo_spheres_in_collision(self.h, _f(s), len(s), out.ctypes.data_as(_u8p))
+        return out.astype(bool)
 
     def capt(self, index=0):
         v = CaptView()

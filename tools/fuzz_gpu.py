@@ -51,6 +51,10 @@ def random_spec(rng, robot):
         p2 = p1.copy()
         p2[2] += np.float32(rng.uniform(0.05, 0.6))
         spec.append(("capsule", capsule(p1, p2, rng.uniform(0.01, 0.08))))
+    if rng.random() < 0.1:   # a capsule whose axis passes through the origin (min_distance 0 / 0: stored as 0), anywhere in
+        p1 = pos()           # the insertion order; now and then a pole that starts at the origin
+        p2 = -p1 * np.float32(rng.choice([1.0, rng.uniform(0.2, 1.0)])) if rng.random() < 0.6 else np.zeros(3, np.float32)
+        spec.insert(int(rng.integers(0, len(spec) + 1)), ("capsule", capsule(p2, p1, rng.uniform(0.01, 0.05))))
     if rng.random() < 0.15:  # ill-formed primitives: the pruning layers must switch themselves off
         for k, (kind, p) in enumerate(spec):
             if kind == "cuboid" and k % 3 == 0:

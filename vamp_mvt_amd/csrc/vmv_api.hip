@@ -290,7 +290,13 @@ enum
 namespace
 {
     float dot3h(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx) + (ay * by) + (az * bz); }
-    float clamp_scalar(float v, float lo, float hi) { return std::max(std::min(v, hi), lo); }  // collision/math.hh:47-51
+    // collision/math.hh:47-51: std::max(std::min(v, upper), lower) of the C++ library, written out: a NaN comes back as
+    // NaN (in a HIP translation unit std::min / std::max on floats may resolve to fminf / fmaxf, which drop it)
+    float clamp_scalar(float v, float lo, float hi)
+    {
+        const float m = (hi < v) ? hi : v;
+        return (m < lo) ? lo : m;
+    }
 
     // collision/shapes.hh:52-67
     float cuboid_min_distance(const float *p)
@@ -308,7 +314,9 @@ namespace
         return std::sqrt(xn * xn + yn * yn + zn * zn);
     }
 
-    // collision/shapes.hh:165-189
+    // collision/shapes.hh:165-189.  Where the reference divides 0 by 0 (ol == 0: the origin lies on the capsule's axis) the
+    // true distance is 0, and that is what is stored; so is any value that is still not finite (a zero-length capsule
+    // with rdv = inf).  Such an entry sorts first and never triggers the sorted early break (include/vamp_mvt_amd.h).
     float capsule_min_distance(const float *p)
     {
         const float x1 = p[0], y1 = p[1], z1 = p[2], xv = p[3], yv = p[4], zv = p[5], r = p[6], rdv = p[7];
@@ -316,12 +324,14 @@ namespace
         const float xp = x1 + xv * t, yp = y1 + yv * t, zp = z1 + zv * t;
         float xo = -xp, yo = -yp, zo = -zp;
         const float ol = std::sqrt(dot3h(xo, yo, zo, xo, yo, zo));
+        if (ol == 0.F) return 0.F;
         xo = xo / ol;
         yo = yo / ol;
         zo = zo / ol;
         const float ro = clamp_scalar(ol, 0.F, r);
         const float xn = xp + ro * xo, yn = yp + ro * yo, zn = zp + ro * zo;
-        return std::sqrt(xn * xn + yn * yn + zn * zn);
+        const float d = std::sqrt(xn * xn + yn * yn + zn * zn);
+        return std::isfinite(d) ? d : 0.F;
     }
 
     template <typename T>
