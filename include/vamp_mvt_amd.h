@@ -323,6 +323,67 @@ int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterati
 int vmv_plans_paths(const vmv_plans *plans, float *out, size_t capacity_floats);
 int vmv_plans_destroy(vmv_plans *plans);
 
+/* ---- lockstep simplifier: many independent paths in one call -------------------------------------------- */
+/* simplify() (planning/simplify.hh:192-260) with the SHORTCUT and BSPLINE routines for n_paths paths at once: path p is
+ * points[offsets[p] .. offsets[p + 1]) ([offsets[n_paths]][dimension] host floats, offsets in waypoints, offsets[0] = 0)
+ * in envs[p].  The paths advance in lockstep rounds like the problems of vmv_rrtc_multi: per round a step kernel (one
+ * wave per unfinished path: consumes the answers of the previous round, erases or replaces waypoints, advances the
+ * routine) writes questions_per_round edge questions per unfinished path, and one vmv_validate_motion_batch_multi launch
+ * sequence answers all of them.  Shortcut asks the next candidates j of its waypoint i from the far end and takes the
+ * largest valid one; a B-spline step asks both motions of the next candidates that passed the min_change test.  Both
+ * end with the path the reference's one-question-at-a-time loops end with, so a path's result depends on its own
+ * inputs and the settings other than questions_per_round and check_every alone, bit for bit (DESIGN §5d gives the
+ * arithmetic: fp32, one rounding per operation).  Paths of fewer than 3 waypoints come back as they are without a
+ * question.  Each path owns max_waypoints waypoints (twice, 2 * max_waypoints * dimension * 4 bytes on the device): a
+ * B-spline subdivision that would need more is not made, the path stays as it stood (still a valid path between its
+ * ends) and ends with VMV_SIMPLIFY_CAPACITY.
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / points / offsets / settings /
+ * out or a NULL handle, offsets not starting at 0 or decreasing, an operation other than SHORTCUT / BSPLINE (REDUCE and
+ * PERTURB draw random numbers: not part of this call), n_operations > 8, interpolate != 0, questions_per_round not one
+ * of 0 2 4 8 16 32 64, max_waypoints below the longest path, n_paths * questions_per_round >= 2^31
+ * (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment (VMV_ERR_NOT_FINALIZED); an environment of another device
+ * (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out untouched.  n_paths == 0 is VMV_OK with an empty result.
+ * A question that touches a non-finite waypoint is invalid, and no non-finite distance exceeds min_change.
+ * Environments not yet prepared for the robot are prepared in one batch.  Synchronous, host buffers, on the default
+ * stream; repeated handles are allowed. */
+enum
+{
+    VMV_SIMPLIFY_BSPLINE = 0, /* the values of planning/simplify_settings.hh: SimplifyRoutine */
+    VMV_SIMPLIFY_REDUCE = 1,  /* refused */
+    VMV_SIMPLIFY_SHORTCUT = 2,
+    VMV_SIMPLIFY_PERTURB = 3  /* refused */
+};
+enum
+{
+    VMV_SIMPLIFY_OK = 0,
+    VMV_SIMPLIFY_CAPACITY = 1 /* a subdivision would have exceeded max_waypoints */
+};
+typedef struct
+{
+    uint32_t max_iterations;
+    uint32_t interpolate;             /* must be 0 */
+    uint32_t n_operations;            /* <= 8; repeated operations and either order are allowed */
+    uint32_t operations[8];           /* VMV_SIMPLIFY_SHORTCUT / VMV_SIMPLIFY_BSPLINE, run in this order per iteration */
+    uint32_t bspline_max_steps;
+    float bspline_min_change;
+    float bspline_midpoint_interpolation;
+    uint32_t max_waypoints;           /* waypoints a path may grow to; 0 = default (2,048) */
+    uint32_t questions_per_round;     /* edge questions per path per round: 2 4 8 16 32 64; 0 = default */
+    uint32_t check_every;             /* rounds between two looks of the host at the finished flags; 0 = default */
+} vmv_simplify_settings;
+typedef struct vmv_paths vmv_paths;
+int vmv_simplify_multi(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                       const vmv_simplify_settings *settings, vmv_paths **out);
+/* Per path (arrays of n_paths, any may be NULL): status (VMV_SIMPLIFY_*), iterations as the reference counts them,
+ * lengths in waypoints, questions asked.  Totals (may be NULL): rounds = validation launches made, total_questions =
+ * edge questions the paths asked (the null questions of unused slots and finished paths not counted). */
+int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterations, uint32_t *lengths,
+                      uint32_t *questions, uint64_t *rounds, uint64_t *total_questions);
+/* every path's waypoints ([length][dimension] each), packed in path order; VMV_ERR_CAPACITY if capacity_floats is too
+ * small (nothing is written) */
+int vmv_paths_points(const vmv_paths *paths, float *out, size_t capacity_floats);
+int vmv_paths_destroy(vmv_paths *paths);
+
 /* ---- measurement support (bench.py) ---------------------------------------------------------------------- */
 /* Runs vmv_validate_batch `iters` times on `stream` between two HIP events recorded on that same stream and
  * returns the average kernel time in milliseconds. */

@@ -63,6 +63,9 @@ def _fp(a):
     return a.ctypes.data_as(_lib.c_float_p)
 
 
+_SIMPLIFY_OPS = {"BSPLINE": 0, "SHORTCUT": 2}  # VMV_SIMPLIFY_*: the routines vmv_simplify_multi runs
+
+
 def unpack_bits(words: np.ndarray, n: int) -> np.ndarray:
     """uint64 validity words (bit i%64 of word i//64) -> bool[n]."""
     b = np.unpackbits(np.ascontiguousarray(words, dtype="<u8").view(np.uint8), bitorder="little")
@@ -699,6 +702,80 @@ class _Robot(types.ModuleType):
             lib.vmv_plans_destroy(plans)
         return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
                     rounds=int(rounds.value), questions=int(questions.value))
+
+    def simplify_multi_raw(self, paths, environments, settings):
+        """vmv_simplify_multi: the reference's simplify() with the SHORTCUT and BSPLINE routines for many paths in
+        lockstep, path p ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).
+        settings: max_iterations, operations (a list of "SHORTCUT" / "BSPLINE"), max_steps, min_change,
+        midpoint_interpolation and optionally interpolate (must be 0), max_waypoints, questions_per_round, check_every
+        (0 = the library's default).  -> dict of per-path numpy arrays (status, iterations, lengths, questions), the
+        packed waypoints (points [sum(lengths)][dim]) and the totals rounds and total_questions.
+        planning.simplify_multi is the caller-facing form.  Every argument is checked before any library call."""
+        environments = list(environments)
+        for e in environments:
+            if e is not None and not isinstance(e, Environment):
+                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        pts = []
+        for p in paths:
+            a = np.asarray(p, dtype=np.float32)
+            if a.size == 0:
+                a = np.zeros((0, self._dim), np.float32)
+            if a.ndim != 2 or a.shape[1] != self._dim:
+                raise TypeError(f"expected every path as [len][{self._dim}] waypoints")
+            pts.append(a)
+        n = len(pts)
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per path, got {len(environments)} for {n} paths")
+        ops = []
+        for op in settings.operations:
+            name = str(getattr(op, "name", op)).upper()
+            if name in ("REDUCE", "PERTURB"):
+                raise NotImplementedError(f"{name} draws random numbers: simplify_multi runs SHORTCUT and BSPLINE only")
+            if name not in _SIMPLIFY_OPS:
+                raise ValueError(f"unknown simplification routine {op!r}")
+            ops.append(_SIMPLIFY_OPS[name])
+        if len(ops) > 8:
+            raise ValueError("at most 8 operations per iteration")
+        if int(getattr(settings, "interpolate", 0)) != 0:
+            raise NotImplementedError("interpolate is not part of simplify_multi: interpolate the returned paths")
+        max_it, max_steps = int(settings.max_iterations), int(settings.max_steps)
+        max_wp, w = int(getattr(settings, "max_waypoints", 0)), int(getattr(settings, "questions_per_round", 0))
+        every = int(getattr(settings, "check_every", 0))
+        if not (0 <= max_it < 2 ** 32 and 0 <= max_steps < 2 ** 32 and 0 <= every < 2 ** 32 and 0 <= max_wp <= 2 ** 24):
+            raise ValueError("max_iterations, max_steps and check_every must fit 32 bits, max_waypoints 24")
+        if w not in (0, 2, 4, 8, 16, 32, 64):
+            raise ValueError("questions_per_round must be one of 2, 4, 8, 16, 32, 64 (0 = default)")
+        longest = max((len(a) for a in pts), default=0)
+        if longest > (max_wp or 2048):
+            raise ValueError(f"max_waypoints is below the longest path ({longest} waypoints)")
+        cs = _lib.SimplifySettings(max_it, 0, len(ops), (ctypes.c_uint32 * 8)(*ops), max_steps, float(settings.min_change),
+                                   float(settings.midpoint_interpolation), max_wp, w, every)
+        offsets = np.zeros(n + 1, np.uintp)
+        offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
+        packed = np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, self._dim), np.float32)]))
+        if n == 0:
+            return dict(status=np.zeros(0, np.uint8), iterations=np.zeros(0, np.uint32), lengths=np.zeros(0, np.uint32),
+                        questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0)
+        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
+        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+        handles = (ctypes.c_void_p * max(n, 1))(*[e.handle() for e in envs])
+        out = ctypes.c_void_p()
+        check(lib.vmv_simplify_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                     ctypes.byref(cs), ctypes.byref(out)), "vmv_simplify_multi")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            lengths, questions = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            rounds, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_paths_summary(out, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                        iterations.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
+                                        questions.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(total)),
+                  "vmv_paths_summary")
+            points = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_paths_points(out, _fp(points), points.size), "vmv_paths_points")
+        finally:
+            lib.vmv_paths_destroy(out)
+        return dict(status=status, iterations=iterations, lengths=lengths, questions=questions, points=points,
+                    rounds=int(rounds.value), total_questions=int(total.value))
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

@@ -30,6 +30,14 @@ class RrtcSettings(ctypes.Structure):
                 ("max_iterations", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
 
 
+class SimplifySettings(ctypes.Structure):
+    """vmv_simplify_settings"""
+    _fields_ = [("max_iterations", ctypes.c_uint32), ("interpolate", ctypes.c_uint32), ("n_operations", ctypes.c_uint32),
+                ("operations", ctypes.c_uint32 * 8), ("bspline_max_steps", ctypes.c_uint32),
+                ("bspline_min_change", ctypes.c_float), ("bspline_midpoint_interpolation", ctypes.c_float),
+                ("max_waypoints", ctypes.c_uint32), ("questions_per_round", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -128,6 +136,11 @@ def _load():
         "vmv_plans_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_plans_paths": (I, [V, c_float_p, S]),
         "vmv_plans_destroy": (I, [V]),
+        "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
+                                   ctypes.POINTER(V)]),
+        "vmv_paths_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_paths_points": (I, [V, c_float_p, S]),
+        "vmv_paths_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

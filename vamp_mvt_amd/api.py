@@ -15,9 +15,9 @@ and signatures (bindings/robot_helper.hh:326-597, bindings/settings.cc:13-117, s
 What is NOT the reference's: the planners themselves.  The reference's are serial C++ templates (rrtc.hh, prm.hh,
 fcit.hh, simplify.hh) that ask one validity question at a time; these are host-side loops (vamp_mvt_amd/planning.py)
 that ask the same kinds of questions in batches of the GPU path, so iteration counts, tree sizes and path costs differ
-from the reference's (no reference test pins those).  `simplify` is a shortcutting pass only (the reference's
-simplifiers are out of this build's scope): every shortcut is a `validate_motion` question answered on
-the GPU.  `xorshift()` raises, as the reference's does where SIMDxorshift is unavailable (robot_helper.hh:406-409)."""
+from the reference's (no reference test pins those).  `simplify` is a greedy shortcutting pass (every shortcut is a
+`validate_motion` question answered on the GPU); `<robot>.simplify_multi` runs the reference's SHORTCUT and BSPLINE
+routines themselves, for many paths at once on the device (planning.simplify_multi).  `xorshift()` raises, as the reference's does where SIMDxorshift is unavailable (robot_helper.hh:406-409)."""
 from __future__ import annotations
 
 import logging
@@ -141,7 +141,8 @@ class PerturbSettings:
 
 @dataclass
 class SimplifySettings:
-    """vp::SimplifySettings (settings.cc:109-117); this build runs the SHORTCUT routine only"""
+    """vp::SimplifySettings (settings.cc:109-117); `simplify` runs a greedy shortcut pass only, `simplify_multi` the
+    SHORTCUT and BSPLINE routines as listed in `operations`"""
     max_iterations: int = 4
     interpolate: int = 0
     operations: list = field(default_factory=lambda: [SimplifyRoutine.SHORTCUT, SimplifyRoutine.BSPLINE])
@@ -379,8 +380,25 @@ def install(robot):
             res.interpolate_to_n_states(int(settings.interpolate))
         return PlanningResult(res, time.perf_counter_ns() - t0, 0, [], res.cost() if len(res) >= 2 else 0.0)
 
+    def simplify_multi(paths, environments, settings=None):
+        """planning.simplify_multi with this robot: the reference's SHORTCUT and BSPLINE routines for many paths in
+        lockstep on the device -> list[PlanningResult] (each with `status`; nanoseconds is the whole call's time
+        divided by the paths).  `settings`: a SimplifySettings or a planning.SimplifyMultiSettings."""
+        t0 = time.perf_counter_ns()
+        results = planning.simplify_multi(robot, paths, environments, settings)
+        each = (time.perf_counter_ns() - t0) // max(len(results), 1)
+        out = []
+        for r in results:
+            path = Path()
+            for q in r.path:
+                path.append(q)
+            res = PlanningResult(path, each, r.iterations, [], r.cost)
+            res.status = r.status
+            out.append(res)
+        return out
+
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
-    robot.rrtc_multi = rrtc_multi
+    robot.rrtc_multi, robot.simplify_multi = rrtc_multi, simplify_multi
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 

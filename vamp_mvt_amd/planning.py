@@ -99,6 +99,25 @@ class RRTCMultiSettings:
 
 
 PLAN_STATUS = ("solved", "max_iterations", "max_samples")  # VMV_PLAN_*
+SIMPLIFY_STATUS = ("ok", "capacity")  # VMV_SIMPLIFY_*
+
+
+@dataclass
+class SimplifyMultiSettings:
+    """settings of `simplify_multi`: the reference's simplification defaults (max_iterations, operations, and the
+    B-spline routine's max_steps, min_change, midpoint_interpolation), then what the lockstep form adds: max_waypoints
+    (every path of a call owns that many waypoints on the device, twice), questions_per_round (edge questions per path
+    per round: 2, 4, 8, 16, 32 or 64) and check_every (rounds between two looks of the host at which paths are
+    finished); 0 = the library's default for each of the three"""
+    max_iterations: int = 4
+    operations: list = field(default_factory=lambda: ["SHORTCUT", "BSPLINE"])
+    max_steps: int = 5
+    min_change: float = 0.05
+    midpoint_interpolation: float = 0.5
+    max_waypoints: int = 2048
+    questions_per_round: int = 0
+    check_every: int = 0
+    interpolate: int = 0  # must stay 0
 
 
 @dataclass
@@ -111,7 +130,7 @@ class PlanningResult:
     cost: float = float("inf")
     edges_checked: int = 0
     samples_drawn: int = 0
-    status: str = ""  # rrtc_multi: one of PLAN_STATUS
+    status: str = ""  # rrtc_multi: one of PLAN_STATUS; simplify_multi: one of SIMPLIFY_STATUS
 
     @property
     def solved(self):
@@ -235,6 +254,61 @@ def rrtc_multi(robot, starts, goals, environments, settings: RRTCMultiSettings |
                                   status=PLAN_STATUS[int(raw["status"][p])]))
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
+    return out
+
+
+def _as_simplify_multi_settings(settings) -> SimplifyMultiSettings:
+    """SimplifyMultiSettings from the reference-shaped SimplifySettings (api.py: its B-spline numbers sit in .bspline)"""
+    if settings is None:
+        return SimplifyMultiSettings()
+    if isinstance(settings, SimplifyMultiSettings):
+        return settings
+    b = settings.bspline
+    return SimplifyMultiSettings(max_iterations=settings.max_iterations, operations=list(settings.operations),
+                                 max_steps=b.max_steps, min_change=b.min_change,
+                                 midpoint_interpolation=b.midpoint_interpolation,
+                                 max_waypoints=getattr(settings, "max_waypoints", 2048),
+                                 questions_per_round=getattr(settings, "questions_per_round", 0),
+                                 check_every=getattr(settings, "check_every", 0),
+                                 interpolate=getattr(settings, "interpolate", 0))
+
+
+def path_cost(path) -> float:
+    """Path::cost (planning/plan.hh:13-32): the fp32 sum of the segment lengths; inf below 2 waypoints"""
+    if len(path) < 2:
+        return float("inf")
+    p = np.stack(path).astype(np.float32)
+    seg = np.sqrt(((p[1:] - p[:-1]) ** 2).sum(1, dtype=np.float32))
+    return float(seg.sum(dtype=np.float32))
+
+
+def simplify_multi(robot, paths, environments, settings=None):
+    """The reference's simplify() (planning/simplify.hh) with its SHORTCUT and BSPLINE routines for many independent
+    paths in lockstep on the device: paths[p] ([len][dim] array or list of waypoints) in environments[p] (None = the
+    empty environment).  -> list[PlanningResult], one per path: `path`, `iterations` (as the reference counts them),
+    `cost` (Path::cost) and `status` (one of SIMPLIFY_STATUS).  settings: SimplifyMultiSettings, or the
+    reference-shaped SimplifySettings (converted).
+
+    Per round every unfinished path asks questions_per_round edge questions and ONE validate_motion_batch_multi launch
+    sequence answers all of them; erasing, subdividing, the min_change test and the bookkeeping run in a device kernel
+    (DESIGN §5d).  Shortcut asks the candidates of a waypoint from the far end a window at a time, a B-spline step
+    both motions of each candidate; either way the path is the one the reference's one-question-at-a-time loops end
+    with, in fp32 with one rounding per operation, so a path's result is defined bit for bit and does not depend on
+    questions_per_round, check_every or the other paths of the call.
+
+    REDUCE and PERTURB (they draw random numbers) and `interpolate` raise NotImplementedError.  A path owns
+    max_waypoints waypoints; where a B-spline subdivision would need more, the path comes back as it stood, a valid
+    path still, with status "capacity"."""
+    s = _as_simplify_multi_settings(settings)
+    raw = robot.simplify_multi_raw(paths, environments, s)
+    ends = np.cumsum(raw["lengths"], dtype=np.int64)
+    out = []
+    for p in range(len(ends)):
+        pts = [q.copy() for q in raw["points"][ends[p] - int(raw["lengths"][p]):ends[p]]]
+        out.append(PlanningResult(path=pts, iterations=int(raw["iterations"][p]), cost=path_cost(pts),
+                                  edges_checked=int(raw["questions"][p]), status=SIMPLIFY_STATUS[int(raw["status"][p])]))
+    if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
+        out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["total_questions"]
     return out
 
 
