@@ -178,3 +178,34 @@ def test_non_finite_endpoints_end_unsolved_and_leave_the_others_alone(vamp, scen
     rest = [0, 2, 4, 5]
     assert any(want[i].solved and want[i].iterations > 0 for i in rest)
     check([problems[i] for i in rest], [got[i] for i in rest], [want[i] for i in rest])
+
+
+@pytest.fixture(scope="module")
+def staggered(vamp, mixed_batch):
+    """five problems of the mixed batch that finish in different rounds: two the direct question solves (finished in round
+    2), the two shortest of the cage and one among the cuboids that needs iterations; run with the default check_every"""
+    problems, want, _ = mixed_batch
+    by_questions = sorted(range(len(problems)), key=lambda i: want[i].questions)
+    pick = [i for i in by_questions if want[i].questions == 1][:2]
+    pick += [i for i in by_questions if problems[i].scene.kind == "cage"][:2]
+    pick.append(next(i for i in by_questions if problems[i].scene.kind == "mixed" and want[i].iterations > 0))
+    assert len(pick) == 5 and len({want[i].questions for i in pick}) >= 4
+    pick.sort()  # the batch's interleaved order
+    some = [problems[i] for i in pick]
+    return some, [want[i] for i in pick], run(vamp, some, settings_of())
+
+
+@pytest.mark.parametrize("every", [1, 3])
+def test_the_host_looks_every_check_every_rounds_and_changes_no_bit(vamp, staggered, every):
+    """a problem asks one question per round and ends in the round after its last, so the call ends at the first look at
+    or after round max(questions) + 1"""
+    problems, want, base = staggered
+    check(problems, base, want)
+    got = run(vamp, problems, settings_of(check_every=every))
+    assert [key(g) for g in got] == [key(g) for g in base]
+    rounds, questions = got[0].validity_calls, got[0].edges_checked
+    assert questions == base[0].edges_checked == sum(w.questions for w in want)
+    assert rounds > 0 and rounds % every == 0
+    assert rounds * len(problems) >= questions
+    assert rounds == every * -(-(max(w.questions for w in want) + 1) // every)
+    assert base[0].validity_calls == 16 * -(-(max(w.questions for w in want) + 1) // 16)

@@ -299,3 +299,50 @@ def test_installed_name_and_reference_settings_take_the_same_road(vamp, batch):
     got2 = vamp.panda.simplify_multi([it.path for it in some], [it.scene.env for it in some], s)
     assert [(STATUS[g.status], int(g.iterations), [np.asarray(q, np.float32).tobytes() for q in g.path]) for g in got2] == \
         [key(w) for w in want2]
+
+
+@pytest.fixture(scope="module")
+def staggered(vamp, batch):
+    """six paths of the batch that finish in different rounds: two whose straight line is valid (finished in round 2), one
+    too short to ask anything, and the three of the others that need the fewest rounds alone; run with the default
+    check_every at 4 questions per round"""
+    items, want, _ = batch
+    rounds = [windowed_rounds(w.trace, 4) for w in want]
+    by_rounds = sorted(range(len(items)), key=lambda i: rounds[i])
+    pick = [i for i in by_rounds if len(items[i].path) > 2 and want[i].questions == 1][:2]
+    pick.append(next(i for i, it in enumerate(items) if it.tag == "two"))
+    pick += [i for i in by_rounds if want[i].iterations > 0 and (want[i].erased or want[i].replaced)][:3]
+    assert len(pick) == 6 and len({rounds[i] for i in pick}) >= 3
+    pick.sort()
+    some = [items[i] for i in pick]
+    return some, [want[i] for i in pick], run(vamp, some, settings_of(questions_per_round=4))
+
+
+@pytest.mark.parametrize("every", [1, 3])
+def test_the_host_looks_every_check_every_rounds_and_changes_no_bit(vamp, staggered, every):
+    """the call ends at the first look after the last path has ended, within the bounds the tests above use: the rounds
+    the slowest path needs alone, the one that consumes its last answers, and at most check_every more"""
+    items, want, base = staggered
+    check(items, base, want)
+    got = run(vamp, items, settings_of(check_every=every, questions_per_round=4))
+    assert [key(g) for g in got] == [key(g) for g in base]
+    counts = [windowed_questions(w.trace, 4) for w in want]
+    assert [g.edges_checked for g in got[1:]] == counts[1:] and got[0].edges_checked == sum(counts)
+    rounds, need = got[0].validity_calls, max(windowed_rounds(w.trace, 4) for w in want)
+    assert rounds > 0 and rounds % every == 0
+    assert rounds * 4 >= max(counts)
+    assert need <= rounds <= need + every + 1
+
+
+def test_a_call_of_short_paths_runs_no_round(vamp, scenes, cage_plans):
+    """0, 1 and 2 waypoints only, in real environments and the empty one (None): nothing is asked, every path comes back
+    with its input bytes"""
+    cage, empty, p = scenes["cage"], scenes["empty"], cage_plans[0]
+    assert cage.env is not None and empty.env is None and not cage.question(p[0], p[-1])
+    items = [Item(cage, [p[0], p[-1]], "two, blocked"), Item(empty, [], "none"), Item(empty, p[:2], "two"),
+             Item(cage, p[:1], "one"), Item(empty, p[3:4], "one"), Item(scenes["mixed"], p[1:3], "two")]
+    for s in (settings_of(), settings_of(check_every=1, questions_per_round=2)):
+        got = run(vamp, items, s)
+        assert [[q.tobytes() for q in g.path] for g in got] == [[q.tobytes() for q in it.path] for it in items]
+        assert all(g.status == "ok" and g.iterations == 0 for g in got)
+        assert [g.validity_calls for g in got] == [0] * len(items) and [g.edges_checked for g in got] == [0] * len(items)

@@ -496,6 +496,38 @@ def _is_torch_cuda(x):
     return t is not None and isinstance(x, t.Tensor) and x.is_cuda
 
 
+def _check_environments(environments):
+    for e in environments:
+        if e is not None and not isinstance(e, Environment):
+            raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+
+
+def _env_handles(environments):
+    """-> (the Environment objects, the empty environment for None; the c_void_p array of their finalized handles).
+    The caller holds the list until the library call has returned: the handles live as long as the objects."""
+    envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
+    return envs, (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+
+
+def _segments(environments, counts):
+    """one count per environment -> (the environments as a checked list, uint64[n + 1]: the exclusive offsets and the total)"""
+    environments, counts = list(environments), np.asarray(counts)
+    if counts.ndim != 1 or len(counts) != len(environments):
+        raise ValueError(f"expected one count per environment, got {counts.shape} counts for {len(environments)}")
+    if counts.size and (not np.issubdtype(counts.dtype, np.integer) or (counts < 0).any()):
+        raise ValueError("counts must be non-negative integers")
+    _check_environments(environments)
+    return environments, np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
+
+
+def _torch_unpack_bits(bits, n):
+    """unpack_bits for a torch int64 tensor of validity words -> torch.bool[n] on the same device"""
+    import torch
+
+    shifts = torch.arange(64, device=bits.device, dtype=torch.int64)
+    return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+
+
 class _Robot(types.ModuleType):
     def __init__(self, name: str):
         super().__init__(f"{__name__}.{name}")
@@ -642,11 +674,8 @@ class _Robot(types.ModuleType):
         all of them in one call, on the device, instead of one by one on their first use.  None = the empty
         environment.  Changes no answer: the parts are the ones the first use would build, bit for bit."""
         environments = list(environments)
-        for e in environments:
-            if e is not None and not isinstance(e, Environment):
-                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
-        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
-        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        _check_environments(environments)
+        envs, handles = _env_handles(environments)
         check(lib.vmv_env_prepare_multi(self._id, handles, len(envs)), "vmv_env_prepare_multi")
 
     def rrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
@@ -657,9 +686,7 @@ class _Robot(types.ModuleType):
         the totals rounds and questions.  planning.rrtc_multi is the caller-facing form.  Every argument is checked
         before any library call."""
         environments = list(environments)
-        for e in environments:
-            if e is not None and not isinstance(e, Environment):
-                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        _check_environments(environments)
         a, b = _f32(starts), _f32(goals)
         if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
             raise TypeError(f"expected two [n][{self._dim}] arrays")
@@ -682,9 +709,7 @@ class _Robot(types.ModuleType):
         if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32):
             raise ValueError("max_iterations, max_samples (>= 2) and check_every must fit 32 bits")
         cs = _lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every)
-        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
-        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
-        handles = (ctypes.c_void_p * max(n, 1))(*[e.handle() for e in envs])
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
         check(lib.vmv_rrtc_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
                                  ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi")
@@ -712,9 +737,7 @@ class _Robot(types.ModuleType):
         packed waypoints (points [sum(lengths)][dim]) and the totals rounds and total_questions.
         planning.simplify_multi is the caller-facing form.  Every argument is checked before any library call."""
         environments = list(environments)
-        for e in environments:
-            if e is not None and not isinstance(e, Environment):
-                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
+        _check_environments(environments)
         pts = []
         for p in paths:
             a = np.asarray(p, dtype=np.float32)
@@ -756,9 +779,7 @@ class _Robot(types.ModuleType):
         if n == 0:
             return dict(status=np.zeros(0, np.uint8), iterations=np.zeros(0, np.uint32), lengths=np.zeros(0, np.uint32),
                         questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0)
-        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
-        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
-        handles = (ctypes.c_void_p * max(n, 1))(*[e.handle() for e in envs])
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         out = ctypes.c_void_p()
         check(lib.vmv_simplify_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
                                      ctypes.byref(cs), ctypes.byref(out)), "vmv_simplify_multi")
@@ -781,16 +802,7 @@ class _Robot(types.ModuleType):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty
         environment), in one call.  The same answers as one validate_batch per environment, concatenated.  numpy in ->
         numpy out; torch CUDA tensor in -> torch.bool CUDA tensor out, launched on torch's current stream."""
-        environments = list(environments)
-        counts = np.asarray(counts)
-        if counts.ndim != 1 or len(counts) != len(environments):
-            raise ValueError(f"expected one count per environment, got {counts.shape} counts for {len(environments)}")
-        if counts.size and (not np.issubdtype(counts.dtype, np.integer) or (counts < 0).any()):
-            raise ValueError("counts must be non-negative integers")
-        for e in environments:
-            if e is not None and not isinstance(e, Environment):
-                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
-        offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
+        environments, offsets = _segments(environments, counts)
         torch_in = _is_torch_cuda(configurations)
         if torch_in:
             shape = tuple(configurations.shape)
@@ -802,9 +814,7 @@ class _Robot(types.ModuleType):
         n = shape[0]
         if int(offsets[-1]) != n:
             raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
-        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
-        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
-        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         offs = offsets.ctypes.data_as(_lib.c_size_p)
         if torch_in:
             import torch
@@ -815,8 +825,7 @@ class _Robot(types.ModuleType):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
                 check(lib.vmv_validate_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(qt.data_ptr()),
                                                    ctypes.c_void_p(bits.data_ptr()), stream), "vmv_validate_batch_multi")
-                shifts = torch.arange(64, device=qt.device, dtype=torch.int64)
-                return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+                return _torch_unpack_bits(bits, n)
         bits = np.zeros((n + 63) // 64, np.uint64)
         check(lib.vmv_validate_batch_multi_host(self._id, handles, offs, len(envs), _fp(q),
                                                 bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_multi_host")
@@ -827,16 +836,7 @@ class _Robot(types.ModuleType):
         the empty environment), in one call.  The same answers as one validate_motion_batch per environment,
         concatenated.  numpy in -> numpy out; torch CUDA tensors in -> torch.bool CUDA tensor out, launched on torch's
         current stream."""
-        environments = list(environments)
-        counts = np.asarray(counts)
-        if counts.ndim != 1 or len(counts) != len(environments):
-            raise ValueError(f"expected one count per environment, got {counts.shape} counts for {len(environments)}")
-        if counts.size and (not np.issubdtype(counts.dtype, np.integer) or (counts < 0).any()):
-            raise ValueError("counts must be non-negative integers")
-        for e in environments:
-            if e is not None and not isinstance(e, Environment):
-                raise TypeError(f"expected Environment or None, got {type(e).__name__}")
-        offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
+        environments, offsets = _segments(environments, counts)
         torch_in = _is_torch_cuda(starts)
         if torch_in:
             if not _is_torch_cuda(goals):
@@ -850,9 +850,7 @@ class _Robot(types.ModuleType):
         n = sa[0]
         if int(offsets[-1]) != n:
             raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} edges")
-        # the Environment objects stay referenced (`environments`) until the call returns: their handles stay alive
-        envs = [_EMPTY_ENVIRONMENT if e is None else e for e in environments]
-        handles = (ctypes.c_void_p * max(len(envs), 1))(*[e.handle() for e in envs])
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         offs = offsets.ctypes.data_as(_lib.c_size_p)
         if torch_in:
             import torch
@@ -865,8 +863,7 @@ class _Robot(types.ModuleType):
                 check(lib.vmv_validate_motion_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(at.data_ptr()),
                                                           ctypes.c_void_p(bt.data_ptr()), ctypes.c_void_p(bits.data_ptr()),
                                                           stream), "vmv_validate_motion_batch_multi")
-                shifts = torch.arange(64, device=at.device, dtype=torch.int64)
-                return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+                return _torch_unpack_bits(bits, n)
         bits = np.zeros((n + 63) // 64, np.uint64)
         check(lib.vmv_validate_motion_batch_multi_host(self._id, handles, offs, len(envs), _fp(a), _fp(b),
                                                        bits.ctypes.data_as(_lib.c_u64_p)),
@@ -933,8 +930,7 @@ class _Robot(types.ModuleType):
             n = a.shape[0]
             bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=a.device)
             self.validate_bits_device(a, environment, bits, None if b is None else b.contiguous().float())
-            shifts = torch.arange(64, device=a.device, dtype=torch.int64)
-            return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
+            return _torch_unpack_bits(bits, n)
 
 
 _EMPTY_ENVIRONMENT = Environment()

@@ -1,10 +1,8 @@
 // vmv_rrtc_multi.hip — lockstep RRT-Connect over many independent problems (vmv_rrtc_multi).
 //
-// Every problem is a state machine in device memory.  One round = rrtc_step_kernel (one workgroup per unfinished
-// problem: consumes the answer to the problem's previous edge question, updates the trees, advances to the next question
-// and writes that edge into the round's start / goal arrays) + one vmv_validate_motion_batch_multi call over those edges.
-// The host does nothing per problem inside a round and does not synchronise; every check_every rounds it reads the
-// finished flags and rebuilds the active list.
+// Every problem is a state machine in device memory, advanced by the rounds of vmv_lockstep.h with one question per
+// problem: rrtc_step_kernel (one workgroup per unfinished problem) consumes the answer to the problem's previous edge
+// question, updates the trees, advances to the next question and writes that edge into the round's start / goal arrays.
 //
 // Arithmetic contract: fp32, one rounding per written operation (-ffp-contract=off; sqrtf and / are correctly rounded
 // on gfx950), the nearest node is the FIRST of the least sqrtf(sum of squares in joint order).  The workgroup's lanes
@@ -14,14 +12,10 @@
 // Every store is a plain vector store by the owning workgroup; no atomics.
 #include "../../include/vamp_mvt_amd.h"
 
-#include "vmv_common.h"
+#include "vmv_lockstep.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
 struct vmv_plans
 {
@@ -362,32 +356,6 @@ namespace vmv
                               D.starts + (size_t) p * P.dim, D.goals + (size_t) p * P.dim, paths + offsets[p] * P.dim);
         }
 
-        struct DeviceBuffers  // freed on every way out
-        {
-            std::vector<void *> ptrs;
-            void *pinned = nullptr;
-            ~DeviceBuffers()
-            {
-                for (void *p : ptrs) (void) hipFree(p);
-                if (pinned) (void) hipHostFree(pinned);
-            }
-            template <typename T>
-            hipError_t alloc(T **out, size_t count)
-            {
-                void *p = nullptr;
-                const hipError_t e = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-                if (e == hipSuccess) ptrs.push_back(p);
-                *out = static_cast<T *>(p);
-                return e;
-            }
-        };
-#define VMV_RRTC_HIP(call)                                    \
-    do                                                        \
-    {                                                         \
-        const hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_status(e_, #call);   \
-    } while (0)
-
     // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
     // robot's part built.  lower / span: the robot's joint bounds (Robot::s_a, s_m).
     int rrtc_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
@@ -407,83 +375,52 @@ namespace vmv
         float *d_starts = nullptr, *d_goals = nullptr;
         uint64_t *d_skips = nullptr, *d_bits = nullptr, *d_offsets = nullptr;
         uint32_t *d_active = nullptr;
-        VMV_RRTC_HIP(mem.alloc(&D.state, n));
-        VMV_RRTC_HIP(mem.alloc(&D.pool, n * (size_t) S.max_samples * (size_t) dim));
-        VMV_RRTC_HIP(mem.alloc(&D.parent, n * (size_t) S.max_samples));
-        VMV_RRTC_HIP(mem.alloc(&d_starts, qn));
-        VMV_RRTC_HIP(mem.alloc(&d_goals, qn));
-        VMV_RRTC_HIP(mem.alloc(&d_skips, n));
-        VMV_RRTC_HIP(mem.alloc(&d_active, n));
-        VMV_RRTC_HIP(mem.alloc(&D.q_start, qn));
-        VMV_RRTC_HIP(mem.alloc(&D.q_goal, qn));
-        VMV_RRTC_HIP(mem.alloc(&d_bits, (n + 63) / 64));
-        VMV_RRTC_HIP(mem.alloc(&D.done, n));
-        VMV_RRTC_HIP(mem.alloc(&d_offsets, n));
-        VMV_RRTC_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.pool, n * (size_t) S.max_samples * (size_t) dim));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) S.max_samples));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_starts, qn));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_goals, qn));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_active, n));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (n + 63) / 64));
+        VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n));
+        VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
         uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
         D.starts = d_starts, D.goals = d_goals, D.skips = d_skips, D.active = d_active, D.bits = d_bits;
 
-        VMV_RRTC_HIP(hipMemcpyAsync(d_starts, starts, qn * 4, hipMemcpyHostToDevice, stream));
-        VMV_RRTC_HIP(hipMemcpyAsync(d_goals, goals, qn * 4, hipMemcpyHostToDevice, stream));
+        VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_starts, starts, qn * 4, hipMemcpyHostToDevice, stream));
+        VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_goals, goals, qn * 4, hipMemcpyHostToDevice, stream));
         if (skips)
-            VMV_RRTC_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
         else
-            VMV_RRTC_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
-        VMV_RRTC_HIP(hipMemsetAsync(d_bits, 0, ((n + 63) / 64) * 8, stream));
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
+        VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((n + 63) / 64) * 8, stream));
         const uint32_t n32 = (uint32_t) n;
         hipLaunchKernelGGL(rrtc_init_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream, P, D, n32);
-        VMV_RRTC_HIP(hipGetLastError());
+        VMV_LOCKSTEP_HIP(hipGetLastError());
 
         std::vector<uint32_t> active(n);
         std::vector<const vmv_env *> active_envs(envs, envs + n);
-        std::vector<size_t> offsets(n + 1);
         for (size_t k = 0; k < n; ++k) active[k] = (uint32_t) k;
-        for (size_t k = 0; k <= n; ++k) offsets[k] = k;
-        VMV_RRTC_HIP(hipMemcpy(d_active, active.data(), n * 4, hipMemcpyHostToDevice));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), n * 4, hipMemcpyHostToDevice));
 
         // every problem ends within 1 + max_iterations + max_samples questions (each question after the direct one belongs
         // to a new iteration or adds a node): a bound on the rounds that does not depend on the device's answers
         const uint64_t max_rounds = 2ull + (uint64_t) S.max_iterations + (uint64_t) S.max_samples + check_every;
         uint64_t rounds = 0;
-        while (!active.empty())
-        {
-            if (rounds > max_rounds)
-            {
-                (void) hipDeviceSynchronize();
-                return hip_status(hipErrorUnknown, "vmv_rrtc_multi: the round bound was exceeded");
-            }
-            const size_t na = active.size();
-            for (uint32_t r = 0; r < check_every; ++r, ++rounds)
-            {
-                hipLaunchKernelGGL(rrtc_step_kernel, dim3((uint32_t) na), dim3(kRrtcBlock), 0, stream, P, D);
-                if (const hipError_t e = hipGetLastError(); e != hipSuccess)
-                {
-                    (void) hipDeviceSynchronize();
-                    return hip_status(e, "rrtc_step_kernel");
-                }
-                if (int rc = vmv_validate_motion_batch_multi(robot, active_envs.data(), offsets.data(), na, D.q_start, D.q_goal,
-                                                             d_bits, stream);
-                    rc != VMV_OK)
-                {
-                    (void) hipDeviceSynchronize();
-                    return rc;
-                }
-            }
-            VMV_RRTC_HIP(hipMemcpyAsync(h_done, D.done, n, hipMemcpyDeviceToHost, stream));
-            VMV_RRTC_HIP(hipStreamSynchronize(stream));
-            size_t kept = 0;
-            for (size_t k = 0; k < na; ++k)
-                if (!h_done[active[k]]) active[kept] = active[k], active_envs[kept] = active_envs[k], ++kept;
-            if (kept != na)
-            {
-                active.resize(kept), active_envs.resize(kept);
-                if (kept) VMV_RRTC_HIP(hipMemcpy(d_active, active.data(), kept * 4, hipMemcpyHostToDevice));
-            }
-        }
+        const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
+        const auto step = [&](uint32_t na) { hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D); };
+        if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, L, "vmv_rrtc_multi",
+                                     "rrtc_step_kernel", step, rounds);
+            rc != VMV_OK)
+            return rc;
 
         // results: the states, then the paths traced on the device into one packed buffer
         std::vector<RrtcState> states(n);
-        VMV_RRTC_HIP(hipMemcpy(states.data(), D.state, n * sizeof(RrtcState), hipMemcpyDeviceToHost));
+        VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(RrtcState), hipMemcpyDeviceToHost));
         plans->n = n, plans->dim = dim, plans->rounds = rounds, plans->questions = 0;
         plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
         std::vector<uint64_t> path_offsets(n);
@@ -503,12 +440,12 @@ namespace vmv
         if (total)
         {
             float *d_paths = nullptr;
-            VMV_RRTC_HIP(mem.alloc(&d_paths, total * (size_t) dim));
-            VMV_RRTC_HIP(hipMemcpy(d_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
             hipLaunchKernelGGL(rrtc_trace_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream, P, D, n32,
                                d_offsets, d_paths);
-            VMV_RRTC_HIP(hipGetLastError());
-            VMV_RRTC_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
+            VMV_LOCKSTEP_HIP(hipGetLastError());
+            VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
         }
         return VMV_OK;
     }
@@ -535,24 +472,12 @@ extern "C"
             if (skip > 1000000ull || skip + settings->max_iterations > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
         }
         if (!halton_skips && settings->max_iterations > 1000000u) return VMV_ERR_INVALID_ARGUMENT;
-        vmv_plans *plans = new (std::nothrow) vmv_plans;
-        if (!plans) return VMV_ERR_HIP;
-        plans->dim = dim;
-        int rc = VMV_OK;
-        if (n_problems > 0)
-        {
+        return vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
             float lower[16], span[16], descale[16];
-            rc = vmv_env_prepare_multi(robot, envs, n_problems);
-            if (rc == VMV_OK) rc = vmv_robot_bounds(robot, lower, span, descale);
-            if (rc == VMV_OK) rc = vmv::rrtc_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, *settings, plans);
-        }
-        if (rc != VMV_OK)
-        {
-            delete plans;
-            return rc;
-        }
-        *out = plans;
-        return VMV_OK;
+            const int rc = vmv_robot_bounds(robot, lower, span, descale);
+            if (rc != VMV_OK) return rc;
+            return vmv::rrtc_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, *settings, plans);
+        });
     }
 
     int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterations, uint32_t *sizes2, uint32_t *path_lengths,

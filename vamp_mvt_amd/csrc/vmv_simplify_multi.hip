@@ -1,10 +1,9 @@
 // vmv_simplify_multi.hip — lockstep path simplification over many independent paths (vmv_simplify_multi).
 //
 // simplify() of planning/simplify.hh with the SHORTCUT and BSPLINE routines.  Every path is a state machine in device
-// memory.  One round = simplify_step_kernel (one wave per unfinished path: consumes the W answers of the path's previous
-// questions, erases or replaces waypoints, advances the routine and writes the next W edges into the round's start /
-// goal arrays) + one vmv_validate_motion_batch_multi call over those edges.  The host does nothing per path inside a
-// round and does not synchronise; every check_every rounds it reads the finished flags and rebuilds the active list.
+// memory, advanced by the rounds of vmv_lockstep.h with W questions per path: simplify_step_kernel (one wave per
+// unfinished path) consumes the W answers of the path's previous questions, erases or replaces waypoints, advances the
+// routine and writes the next W edges into the round's start / goal arrays.
 //
 // Why a window of W questions gives the serial loop's path: shortcut_path takes, for waypoint i, the first valid j of the
 // scan j = size-1 .. i+2, i.e. the largest valid j; a window asks the next W candidates in that order and the lowest set
@@ -19,13 +18,10 @@
 // atomics.
 #include "../../include/vamp_mvt_amd.h"
 
-#include "vmv_common.h"
+#include "vmv_lockstep.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
-#include <vector>
 
 struct vmv_paths
 {
@@ -386,32 +382,6 @@ namespace vmv
             for (size_t e = threadIdx.x; e < (size_t) st.size * P.dim; e += kSimpBlock) o[e] = path[e];
         }
 
-        struct DeviceBuffers  // freed on every way out
-        {
-            std::vector<void *> ptrs;
-            void *pinned = nullptr;
-            ~DeviceBuffers()
-            {
-                for (void *p : ptrs) (void) hipFree(p);
-                if (pinned) (void) hipHostFree(pinned);
-            }
-            template <typename T>
-            hipError_t alloc(T **out, size_t count)
-            {
-                void *p = nullptr;
-                const hipError_t e = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-                if (e == hipSuccess) ptrs.push_back(p);
-                *out = static_cast<T *>(p);
-                return e;
-            }
-        };
-#define VMV_SIMP_HIP(call)                                    \
-    do                                                        \
-    {                                                         \
-        const hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_status(e_, #call);   \
-    } while (0)
-
         uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
         uint64_t sat_mul(uint64_t a, uint64_t b) { return (a && b > ~0ull / a) ? ~0ull : a * b; }
 
@@ -459,72 +429,40 @@ namespace vmv
             float *d_points = nullptr;
             uint64_t *d_offsets = nullptr, *d_bits = nullptr, *d_out_offsets = nullptr;
             uint32_t *d_active = nullptr;
-            VMV_SIMP_HIP(mem.alloc(&D.state, n));
-            VMV_SIMP_HIP(mem.alloc(&D.buf, n * 2u * (size_t) P.max_waypoints * dim));
-            VMV_SIMP_HIP(mem.alloc(&D.cand, n * kSimpMaxCandidates));
-            VMV_SIMP_HIP(mem.alloc(&d_points, total_in * dim));
-            VMV_SIMP_HIP(mem.alloc(&d_offsets, n + 1));
-            VMV_SIMP_HIP(mem.alloc(&d_active, std::max<size_t>(na0, 1)));
-            VMV_SIMP_HIP(mem.alloc(&D.q_start, qn));
-            VMV_SIMP_HIP(mem.alloc(&D.q_goal, qn));
-            VMV_SIMP_HIP(mem.alloc(&d_bits, (na0 * W + 63) / 64 + 1));
-            VMV_SIMP_HIP(mem.alloc(&D.done, n));
-            VMV_SIMP_HIP(mem.alloc(&d_out_offsets, n));
-            VMV_SIMP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.buf, n * 2u * (size_t) P.max_waypoints * dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.cand, n * kSimpMaxCandidates));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_points, total_in * dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_active, std::max<size_t>(na0, 1)));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (na0 * W + 63) / 64 + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_out_offsets, n));
+            VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
             uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
             D.points = d_points, D.offsets = d_offsets, D.active = d_active, D.bits = d_bits;
 
-            if (total_in) VMV_SIMP_HIP(hipMemcpyAsync(d_points, points, total_in * dim * 4, hipMemcpyHostToDevice, stream));
-            VMV_SIMP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
-            VMV_SIMP_HIP(hipMemsetAsync(d_bits, 0, ((na0 * W + 63) / 64 + 1) * 8, stream));
+            if (total_in) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, total_in * dim * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((na0 * W + 63) / 64 + 1) * 8, stream));
             const uint32_t n32 = (uint32_t) n;
             hipLaunchKernelGGL(simplify_init_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D);
-            VMV_SIMP_HIP(hipGetLastError());
-            if (na0) VMV_SIMP_HIP(hipMemcpy(d_active, active.data(), na0 * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipGetLastError());
+            if (na0) VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), na0 * 4, hipMemcpyHostToDevice));
 
-            std::vector<size_t> seg(na0 + 1);
-            for (size_t k = 0; k <= na0; ++k) seg[k] = k * W;
-            const uint64_t max_rounds = round_bound(P, longest, check_every);
             uint64_t rounds = 0;
-            while (!active.empty())
-            {
-                if (rounds > max_rounds)
-                {
-                    (void) hipDeviceSynchronize();
-                    return hip_status(hipErrorUnknown, "vmv_simplify_multi: the round bound was exceeded");
-                }
-                const size_t na = active.size();
-                for (uint32_t r = 0; r < check_every; ++r, ++rounds)
-                {
-                    hipLaunchKernelGGL(simplify_step_kernel, dim3((uint32_t) na), dim3(kSimpBlock), 0, stream, P, D);
-                    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
-                    {
-                        (void) hipDeviceSynchronize();
-                        return hip_status(e, "simplify_step_kernel");
-                    }
-                    if (int rc = vmv_validate_motion_batch_multi(robot, active_envs.data(), seg.data(), na, D.q_start, D.q_goal,
-                                                                 d_bits, stream);
-                        rc != VMV_OK)
-                    {
-                        (void) hipDeviceSynchronize();
-                        return rc;
-                    }
-                }
-                VMV_SIMP_HIP(hipMemcpyAsync(h_done, D.done, n, hipMemcpyDeviceToHost, stream));
-                VMV_SIMP_HIP(hipStreamSynchronize(stream));
-                size_t kept = 0;
-                for (size_t k = 0; k < na; ++k)
-                    if (!h_done[active[k]]) active[kept] = active[k], active_envs[kept] = active_envs[k], ++kept;
-                if (kept != na)
-                {
-                    active.resize(kept), active_envs.resize(kept);
-                    if (kept) VMV_SIMP_HIP(hipMemcpy(d_active, active.data(), kept * 4, hipMemcpyHostToDevice));
-                }
-            }
+            const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
+            const auto step = [&](uint32_t na) { hipLaunchKernelGGL(simplify_step_kernel, dim3(na), dim3(kSimpBlock), 0, stream, P, D); };
+            if (int rc = lockstep_rounds(robot, stream, check_every, round_bound(P, longest, check_every), W, active, active_envs, L,
+                                         "vmv_simplify_multi", "simplify_step_kernel", step, rounds);
+                rc != VMV_OK)
+                return rc;
 
             // results: the states, then the paths gathered on the device into one packed buffer
             std::vector<SimplifyState> states(n);
-            VMV_SIMP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(SimplifyState), hipMemcpyDeviceToHost));
+            VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(SimplifyState), hipMemcpyDeviceToHost));
             paths->n = n, paths->dim = (int) dim, paths->rounds = rounds, paths->total_questions = 0;
             paths->status.resize(n), paths->iterations.resize(n), paths->lengths.resize(n), paths->questions.resize(n);
             std::vector<uint64_t> out_offsets(n);
@@ -544,11 +482,11 @@ namespace vmv
             if (total)
             {
                 float *d_out = nullptr;
-                VMV_SIMP_HIP(mem.alloc(&d_out, total * dim));
-                VMV_SIMP_HIP(hipMemcpy(d_out_offsets, out_offsets.data(), n * 8, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_out, total * dim));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_out_offsets, out_offsets.data(), n * 8, hipMemcpyHostToDevice));
                 hipLaunchKernelGGL(simplify_gather_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D, d_out_offsets, d_out);
-                VMV_SIMP_HIP(hipGetLastError());
-                VMV_SIMP_HIP(hipMemcpy(paths->points.data(), d_out, total * dim * 4, hipMemcpyDeviceToHost));
+                VMV_LOCKSTEP_HIP(hipGetLastError());
+                VMV_LOCKSTEP_HIP(hipMemcpy(paths->points.data(), d_out, total * dim * 4, hipMemcpyDeviceToHost));
             }
             return VMV_OK;
         }
@@ -592,24 +530,10 @@ extern "C"
         P.dim = (uint32_t) dim, P.max_waypoints = max_waypoints, P.max_iterations = S.max_iterations, P.n_ops = S.n_operations;
         P.max_steps = S.bspline_max_steps, P.w = W;
         P.min_change = S.bspline_min_change, P.midpoint = S.bspline_midpoint_interpolation;
-        vmv_paths *paths = new (std::nothrow) vmv_paths;
-        if (!paths) return VMV_ERR_HIP;
-        paths->dim = dim;
-        int rc = VMV_OK;
-        if (n_paths > 0)
-        {
-            rc = vmv_env_prepare_multi(robot, envs, n_paths);
-            if (rc == VMV_OK)
-                rc = vmv::simplify_multi_run(robot, envs, n_paths, points, offsets, P,
-                                             S.check_every ? S.check_every : vmv::kSimpDefaultCheckEvery, paths);
-        }
-        if (rc != VMV_OK)
-        {
-            delete paths;
-            return rc;
-        }
-        *out = paths;
-        return VMV_OK;
+        const uint32_t check_every = S.check_every ? S.check_every : vmv::kSimpDefaultCheckEvery;
+        return vmv::lockstep_call(robot, envs, n_paths, dim, out, [&](vmv_paths *paths) {
+            return vmv::simplify_multi_run(robot, envs, n_paths, points, offsets, P, check_every, paths);
+        });
     }
 
     int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterations, uint32_t *lengths, uint32_t *questions,
