@@ -502,6 +502,12 @@ SPARSE_BATCH = 8        # sparse groups merged per item list (the list holds SPA
 SELF_MARGIN = 1e-4      # metres; enclosure of fine spheres by bounding spheres is asserted to 2e-6 by tools/robot_trace.py
 DEFAULT_CHUNK = 8  # fine spheres staged in the LDS slab at a time
 assert SPARSE_BATCH <= 8 and DEFAULT_CHUNK <= 8  # vmv::kSelfScratchWords holds 8 * 64 list entries
+# robots whose primitive-only configuration kernels deal the fine phase as (item, candidate) pairs (vmv::env_fine_pairs;
+# VMV_FINE_PAIRS=0 selects the packed instance at run time).  Measured with all four on it, 1M configurations against
+# shell64 (profiles/r13_pair_fine_ab.txt, session 2): environment kernel Panda 0.1207 -> 0.1159 ms, UR5 0.1288 -> 0.1231,
+# Fetch 0.1950 -> 0.1948 (stays packed: nothing to gain), Baxter 0.2355 -> 0.2521 (73 VGPRs against 71, six waves
+# per SIMD instead of seven: stays packed).  Panda keeps its six workgroups per CU at 80 VGPRs (profiles/r13_resource_usage.txt).
+FINE_PAIRS = {"panda", "ur5"}
 
 
 GRID_CLASSES = 4  # vmv::kGridClasses
@@ -732,9 +738,13 @@ def emit_robot(m):
             I = "                "
             em.lines.append(f"{I}const int rank = vmv::lane_rank(gate);  // this lane's position in the gate's lane list")
             em.lines.append(f"{I}int pk_fill = 0, pk_done = 0;  // items staged in the slab / already run, wave-uniform")
+            # (PAIRS: the configuration walks deal a list's (item, candidate) pairs instead: vmv_device.h, "pair-dealt fine phase")
+            em.lines.append(f"{I}const int pk_rank = gate ? rank : -1;")
             for ci, ch in enumerate(chunks):
                 if ci > 0:
-                    em.lines.append(f"{I}vmv::env_fine_flush<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_done, "
+                    em.lines.append(f"{I}if constexpr (PAIRS && G == 1) vmv::env_pairs_flush<Tab, V, kPackSlots>(E, pk_items, scratch, "
+                                    f"pk_fill, pk_done, n_gate, {len(ch)} * n_gate, {radii_off[ln] + 1}, pk_rank);")
+                    em.lines.append(f"{I}else vmv::env_fine_flush<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_done, "
                                     f"n_gate, {len(ch)} * n_gate, {radii_off[ln] + 1});")
                 em.emit_ops(private & em.closure(ch), indent=I)
                 em.lines.append(f"{I}if (gate)")
@@ -745,7 +755,9 @@ def emit_robot(m):
                                     + ", ".join(em.coord(s, k) for k in range(3)) + ");")
                 em.lines.append(f"{I}}}")
                 em.lines.append(f"{I}pk_fill += {len(ch)} * n_gate;")
-            em.lines.append(f"{I}vmv::env_fine_packed<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_fill, pk_done, "
+            em.lines.append(f"{I}if constexpr (PAIRS && G == 1) vmv::env_pairs_run<Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, "
+                            f"pk_done, n_gate, {radii_off[ln] + 1}, pk_rank);")
+            em.lines.append(f"{I}else vmv::env_fine_packed<G, Tab, V, kPackSlots>(E, pk_items, scratch, pk_fill, pk_fill, pk_done, "
                             f"n_gate, {radii_off[ln] + 1});")
 
         # (the bounding sphere goes to the gate in registers: no slab row, no LDS round trip between caller and gate)
@@ -772,7 +784,7 @@ def emit_robot(m):
         else:
             em.lines.append(f"            const bool gate = vmv::env_gate<G, Tab, V>(E, {bc}, scratch, {radii_off[ln]}, {link_class[ln]}, !bad);")
         em.lines.append("            const int n_gate = __popcll(__ballot(gate));  // passing lanes (whole rakes), wave-uniform")
-        em.lines.append("            if (VMV_ABLATE_ENV >= 1) bad |= gate;  // measurement aid: no fine phase (wrong answers)")
+        em.lines.append("            if (VMV_ABLATE_ENV >= 1 && VMV_ABLATE_ENV != 10) bad |= gate;  // measurement aid: no fine phase (wrong answers)")
         em.lines.append("            else if (n_gate != 0)")
         em.lines.append("            {")
         if packed:  # (the packed form stages after the gate: lanes write at their rank among passing lanes)
@@ -845,7 +857,9 @@ def emit_robot(m):
     L.append("    // (vmv::capt_gate_pair, two dependent-fetch chains in flight per wave) ahead of the first link's gate; each gate")
     L.append("    // then takes its answer instead of querying.  Same predicates on the same spheres: the OR is unchanged.")
     env_function("fkcc_env_paired", "int G, int V", True)
-    env_function("fkcc_env", "int G, int V", False)
+    L.append("    // PAIRS (configuration walks, G = 1, of the primitive-only variants): the fine phase deals (item, candidate) pairs")
+    L.append("    // (vmv::env_fine_pairs) instead of items (vmv::env_fine_packed); the rakes and fkcc_env_paired never do.")
+    env_function("fkcc_env", "int G, int V, bool PAIRS = false", False)
 
     # ---- static links ------------------------------------------------------------------------------------------
     L.append("    // The environment groups of the links that never move, for every lane alike: run once per (environment, robot)")
@@ -1394,12 +1408,14 @@ def emit_robot(m):
     L.append("    }")
     L.append(f"    static constexpr int kSelfBlocks = {SELF_BLOCKS.get(n, 2)};  // workgroups per CU the self-collision kernel is compiled for")
     L.append(f"    static constexpr int kMotionSelfBlocks = {MOTION_SELF_BLOCKS.get(n, SELF_BLOCKS.get(n, 2))};  // ... and its (edge, rake) task kernel")
-    L.append("    template <int G, int V>")
+    L.append("    template <int G, int V, bool PAIRS = false>")
     L.append("    static __device__ __forceinline__ bool")
     L.append("    fkcc_env(const vmv::EnvView &E, const float (&q)[kDim], vmv::lds_ptr slab, const bool skip)")
     L.append("    {")
-    L.append(f"        return {n}::fkcc_env<G, V>(E, q, slab, skip);")
+    L.append(f"        return {n}::fkcc_env<G, V, PAIRS>(E, q, slab, skip);")
     L.append("    }")
+    L.append(f"    static constexpr bool kFinePairs = {'true' if n in FINE_PAIRS else 'false'};  // configuration kernels of the "
+             "primitive-only variants: pair-dealt fine phase")
     L.append(f"    static constexpr bool kHasFused = {n}::kHasFused;")
     L.append(f"    static constexpr int kFusedBlocks = {FUSED_BLOCKS.get(n, 4)};  // workgroups per CU the fused kernel is compiled for")
     L.append("    template <int G, int V>")

@@ -27,6 +27,9 @@ def report(robot):
             continue
         if m.group(1) == "Function Name":
             cur = {"name": re.sub(r"^_ZN3vmv\d+[a-z0-9]+?\d+|E[PKjmS_\d\w]*$", "", m.group(2))}
+            second = re.search(r"ILi\d+ELb([01])E", m.group(2))  # <V, PAIRS> instances of the configuration kernels
+            if second:
+                cur["name"] += "_Lb" + second.group(1)
             rows.append(cur)
         else:
             cur[m.group(1)] = m.group(2)

@@ -379,7 +379,9 @@ namespace vmv
 
 #ifndef VMV_ABLATE_ENV
 #define VMV_ABLATE_ENV 0  // measurement aid (tools only): 1 = environment kernel without fine phase, 2 = FK only,
-                          // 6 / 7 / 8 / 9 = CAPT query stops after the top box / the descent / the leaf test / the first vector
+                          // 6 / 7 / 8 / 9 = CAPT query stops after the top box / the descent / the leaf test / the first vector,
+                          // 10 = the fine rounds run, but an item evaluates its first candidate only (wrong answers: what
+                          // the surplus steps of the max-over-lanes candidate walks cost, profiles/r13_pair_fine_before.txt)
 #endif
 
     // CAPT::collides_simd (collision/capt.hh:428-512) for the wave's 64 sphere queries (one per lane; the reference's
@@ -1000,7 +1002,7 @@ namespace vmv
     template <int T, bool SHARED>  // SHARED: lists may share candidate words (every variant but the three-list one)
     __device__ __forceinline__ void list_masked(const EnvView &E, const uint32_t n, const uint32_t off, const uint32_t wbase,
                                                 const uint32_t shift, float x, float y, float z, float r, float rsq, float ext,
-                                                bool active, bool &hit, const lds_u32 *mask_src)
+                                                bool active, bool &hit, const lds_u32 *mask_src, bool &took)
     {
         if (n == 0) return;
         constexpr int REC = PrimTraits<T>::rec;
@@ -1009,6 +1011,11 @@ namespace vmv
         {
             uint32_t m = active ? mask_src[(wbase + w) * kWave] : 0u;
             if constexpr (SHARED) m = (m >> shift) & list_word_mask(n);  // (this list's bits; shift 0, all bits for longer lists)
+            if (VMV_ABLATE_ENV == 10)  // measurement aid: the item's first candidate only
+            {
+                m = took ? 0u : m & (0u - m);
+                took = took || m != 0u;
+            }
             // branch-free body: a lane that has run out evaluates record 0 and discards the result (straight-line code
             // instead of an exec-masked region with its copies of every loop-carried value)
             while (wave_any(m != 0u))
@@ -1103,11 +1110,12 @@ namespace vmv
         if constexpr (MODE == 2)
         {
             lds_u32 *const mask = mask_src;
-            if constexpr ((V >> kSphere) & 1) list_masked<kSphere, V != kEnvZOnly>(E, VMV_HN(kSphere, sphere), VMV_HOFF(kSphere, sphere), VMV_HWB(kSphere, sphere), VMV_HSH(kSphere, sphere), x, y, z, r, rsq, ext, active, hit, mask);
-            if constexpr ((V >> kCapsule) & 1) list_masked<kCapsule, V != kEnvZOnly>(E, VMV_HN(kCapsule, capsule), VMV_HOFF(kCapsule, capsule), VMV_HWB(kCapsule, capsule), VMV_HSH(kCapsule, capsule), x, y, z, r, rsq, ext, active, hit, mask);
-            if constexpr ((V >> kZCapsule) & 1) list_masked<kZCapsule, V != kEnvZOnly>(E, VMV_HN(kZCapsule, zcapsule), VMV_HOFF(kZCapsule, zcapsule), VMV_HWB(kZCapsule, zcapsule), VMV_HSH(kZCapsule, zcapsule), x, y, z, r, rsq, ext, active, hit, mask);
-            if constexpr ((V >> kCuboid) & 1) list_masked<kCuboid, V != kEnvZOnly>(E, VMV_HN(kCuboid, cuboid), VMV_HOFF(kCuboid, cuboid), VMV_HWB(kCuboid, cuboid), VMV_HSH(kCuboid, cuboid), x, y, z, r, rsq, ext, active, hit, mask);
-            if constexpr ((V >> kZCuboid) & 1) list_masked<kZCuboid, V != kEnvZOnly>(E, VMV_HN(kZCuboid, zcuboid), VMV_HOFF(kZCuboid, zcuboid), VMV_HWB(kZCuboid, zcuboid), VMV_HSH(kZCuboid, zcuboid), x, y, z, r, rsq, ext, active, hit, mask);
+            bool took = false;  // (VMV_ABLATE_ENV == 10 only)
+            if constexpr ((V >> kSphere) & 1) list_masked<kSphere, V != kEnvZOnly>(E, VMV_HN(kSphere, sphere), VMV_HOFF(kSphere, sphere), VMV_HWB(kSphere, sphere), VMV_HSH(kSphere, sphere), x, y, z, r, rsq, ext, active, hit, mask, took);
+            if constexpr ((V >> kCapsule) & 1) list_masked<kCapsule, V != kEnvZOnly>(E, VMV_HN(kCapsule, capsule), VMV_HOFF(kCapsule, capsule), VMV_HWB(kCapsule, capsule), VMV_HSH(kCapsule, capsule), x, y, z, r, rsq, ext, active, hit, mask, took);
+            if constexpr ((V >> kZCapsule) & 1) list_masked<kZCapsule, V != kEnvZOnly>(E, VMV_HN(kZCapsule, zcapsule), VMV_HOFF(kZCapsule, zcapsule), VMV_HWB(kZCapsule, zcapsule), VMV_HSH(kZCapsule, zcapsule), x, y, z, r, rsq, ext, active, hit, mask, took);
+            if constexpr ((V >> kCuboid) & 1) list_masked<kCuboid, V != kEnvZOnly>(E, VMV_HN(kCuboid, cuboid), VMV_HOFF(kCuboid, cuboid), VMV_HWB(kCuboid, cuboid), VMV_HSH(kCuboid, cuboid), x, y, z, r, rsq, ext, active, hit, mask, took);
+            if constexpr ((V >> kZCuboid) & 1) list_masked<kZCuboid, V != kEnvZOnly>(E, VMV_HN(kZCuboid, zcuboid), VMV_HOFF(kZCuboid, zcuboid), VMV_HWB(kZCuboid, zcuboid), VMV_HSH(kZCuboid, zcuboid), x, y, z, r, rsq, ext, active, hit, mask, took);
         }
         else
         {
@@ -1515,6 +1523,141 @@ namespace vmv
         env_fine_packed<G, Tab, V, C>(E, items, scratch, fill, run, done, k, radii_offset);
         fill -= run;
         done += run;
+    }
+
+    // ---- pair-dealt fine phase (configuration walks of the primitive-only variants; profiles/r13_pair_fine_ab.txt) ----
+    // env_fine_packed gives every lane one item and lets it walk that item's candidate bits, list by list: a round runs
+    // as many steps per list as its busiest lane has candidates, the whole wave along.  Here the (item, candidate)
+    // pairs of one list are dealt instead, one pair per lane and round, so a round is one prim_eval and no lane waits
+    // for another lane's candidates.  Per list of the environment:
+    //   1. the passing lanes turn their candidate bits of the list into entries (rank in the gate's lane list << 8 |
+    //      position in the list).  Each step of the walk takes one bit per lane; the lanes that still had one find
+    //      their entry's number in the step's ballot, so no scan is needed.  The entry list holds kPairEntries entries
+    //      and lives in word 0 of the lanes' candidate words, which every lane holds in registers meanwhile and puts
+    //      back at the end (a link with several runs reads them again); a list with more entries is run in several
+    //      fills, each walking the bits again and keeping the entries whose number falls into it.
+    //   2. with P entries in the fill and S spheres staged (whole spheres: the runs cover multiples of k items), pair t
+    //      is (entry t / S, sphere t % S): its item sits in slot sphere * k + rank.  The lane evaluates the expressions
+    //      of list_masked on it — ext from its own item (G = 1), the same prim_eval, the same predicate — and sets the
+    //      owner's flag on a hit.  The answer per item is the OR of the same pure per-pair predicates: same bits.
+    // tools/experiments/pair_fine_study.py: pair_rounds is this dealing, counted per wave of the bench workload.
+    constexpr int kPairEntries = kWave;
+    template <int T, bool SHARED, int C>
+    __device__ __forceinline__ void pairs_list(const EnvView &E, const uint32_t n, const uint32_t off, const uint32_t wbase,
+                                               const uint32_t shift, const uint32_t (&cw)[kMaskWords], const uint32_t tag,
+                                               lds_u32 *list, lds_cptr items, const int S, const int s0, const int k,
+                                               const float inv_S, const int radii_offset)
+    {
+        if (n == 0) return;
+        constexpr int REC = PrimTraits<T>::rec;
+        const uint32_t lane = __lane_id();
+        lds_u32 *const flags = list + kWave, *const ent = list + 2 * kWave + 4;
+        const uint32_t words = (n + 31) / 32;
+        uint32_t first = 0u, total;  // the fill holds entries [first, first + kPairEntries) of the list's `total`
+        do
+        {
+            total = 0u;
+            for (uint32_t w = 0; w < words; ++w)
+            {
+                const uint32_t kw = wbase + w;
+                uint32_t m = (kw == 0u) ? cw[0] : (kw == 1u) ? cw[1] : (kw == 2u) ? cw[2] : cw[3];
+                if constexpr (SHARED) m = (m >> shift) & list_word_mask(n);
+                for (;;)
+                {
+                    const uint64_t live = __ballot(m != 0u);
+                    if (live == 0ull) break;
+                    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t) (live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) live, 0u));
+                    const uint32_t pos = total + below - first;  // (entries before the fill wrap to large numbers)
+                    if (m != 0u && pos < (uint32_t) kPairEntries) ent[pos] = tag | (w * 32u + (uint32_t) __ffs((int) m) - 1u);
+                    m &= m - 1u;
+                    total += (uint32_t) __popcll(live);
+                }
+            }
+            if (total == 0u) return;
+            wave_lds_sync();
+            const int P = (int) (total - first < (uint32_t) kPairEntries ? total - first : (uint32_t) kPairEntries);
+            const int pairs = P * S;
+            for (int base = 0; base < pairs; base += kWave)
+            {
+                const int t = base + (int) lane;
+                const bool act = t < pairs;
+                // e = t / S (exact: t < 64 * 64 converts exactly, and (t + 0.5) / S lies at least 0.5 / S from an integer,
+                // S <= C / k, far more than the two roundings move it)
+                const int e = act ? (int) (((float) t + 0.5f) * inv_S) : 0;
+                const int s = act ? t - e * S : 0;
+                const uint32_t en = ent[e];
+                const uint32_t j = en >> 8;
+                const uint32_t src = list[j];
+                const int slot = s * k + (int) j;
+                const float x = items[slot], y = items[C + slot], z = items[2 * C + slot];
+                const float r = E.radii[radii_offset + s0 + s];
+                const float ext = sqrtf(dot3(x, y, z, x, y, z)) + r, rsq = r * r;
+                float v, md, reach;
+                prim_eval<T>(E.lds + off + (en & 0xffu) * REC, x, y, z, r, rsq, v, md, reach);
+                if (act && neg(md - ext) && neg(v)) flags[src] = 1u;
+            }
+            first += (uint32_t) kPairEntries;
+            if (first < total) wave_lds_sync();  // (the next fill overwrites the entries)
+        } while (first < total);
+    }
+
+    // Runs all `fill_` staged items of a link (k_ items per sphere, sphere-major; done_ = items of the link run before).
+    // rank_: this lane's position in the gate's lane list, -1 if it did not pass.
+    template <typename Tab, int V, int C>
+    __device__ __noinline__ void
+    env_fine_pairs(const EnvView E_, lds_ptr items_, lds_ptr scratch_, const int fill_, const int done_, const int k_,
+                   const int radii_offset_, const int rank_)
+    {
+        static_assert(kMaskWords * 32 <= 256 && kWave <= 256, "an entry is rank << 8 | position");
+        const uint32_t lane = __lane_id();
+        const EnvView E{uniform(E_.dev), uniform(E_.lds), uniform(E_.capt0_planes_in_lds), uniform(E_.radii)};
+        lds_u32 *list = (lds_u32 *) uniform((lds_cptr) scratch_);
+        lds_u32 *mask_lane = list + 2 * kWave + 4 + lane;
+        const lds_cptr items = uniform((lds_cptr) items_);
+        const int fill = uniform(fill_), done = uniform(done_), k = uniform(k_), radii_offset = uniform(radii_offset_);
+        // spheres staged and spheres of the link run before (exact: see env_fine_packed)
+        const float inv_k = 1.0f / (float) k;
+        const int S = uniform((int) (((float) fill + 0.5f) * inv_k)), s0 = uniform((int) (((float) done + 0.5f) * inv_k));
+        const float inv_S = 1.0f / (float) S;
+        const bool passed = rank_ >= 0;
+        uint32_t cw[kMaskWords];
+#pragma unroll
+        for (int w = 0; w < kMaskWords; ++w) cw[w] = passed ? mask_lane[w * kWave] : 0u;
+        wave_lds_sync();  // (every lane holds its words: word 0 becomes the entry list)
+        const uint32_t tag = (uint32_t) rank_ << 8;
+        const env_cptr Dp = E.dev;
+#define D (*Dp)
+        const ListHdr H = load_list_hdr<V, false>(Dp);
+        if constexpr ((V >> kSphere) & 1) pairs_list<kSphere, V != kEnvZOnly, C>(E, VMV_HN(kSphere, sphere), VMV_HOFF(kSphere, sphere), VMV_HWB(kSphere, sphere), VMV_HSH(kSphere, sphere), cw, tag, list, items, S, s0, k, inv_S, radii_offset);
+        if constexpr ((V >> kCapsule) & 1) pairs_list<kCapsule, V != kEnvZOnly, C>(E, VMV_HN(kCapsule, capsule), VMV_HOFF(kCapsule, capsule), VMV_HWB(kCapsule, capsule), VMV_HSH(kCapsule, capsule), cw, tag, list, items, S, s0, k, inv_S, radii_offset);
+        if constexpr ((V >> kZCapsule) & 1) pairs_list<kZCapsule, V != kEnvZOnly, C>(E, VMV_HN(kZCapsule, zcapsule), VMV_HOFF(kZCapsule, zcapsule), VMV_HWB(kZCapsule, zcapsule), VMV_HSH(kZCapsule, zcapsule), cw, tag, list, items, S, s0, k, inv_S, radii_offset);
+        if constexpr ((V >> kCuboid) & 1) pairs_list<kCuboid, V != kEnvZOnly, C>(E, VMV_HN(kCuboid, cuboid), VMV_HOFF(kCuboid, cuboid), VMV_HWB(kCuboid, cuboid), VMV_HSH(kCuboid, cuboid), cw, tag, list, items, S, s0, k, inv_S, radii_offset);
+        if constexpr ((V >> kZCuboid) & 1) pairs_list<kZCuboid, V != kEnvZOnly, C>(E, VMV_HN(kZCuboid, zcuboid), VMV_HOFF(kZCuboid, zcuboid), VMV_HWB(kZCuboid, zcuboid), VMV_HSH(kZCuboid, zcuboid), cw, tag, list, items, S, s0, k, inv_S, radii_offset);
+#undef D
+        wave_lds_sync();
+        if (passed) mask_lane[0] = cw[0];
+        wave_lds_sync();
+    }
+
+    // The two calls the generated walk makes where the packed phase calls env_fine_flush / env_fine_packed.  Runs are
+    // whole spheres here (everything staged), so fill and done stay multiples of k.  Environments without candidate
+    // words (masked_fine == 0) keep the packed rounds and their flush rule.
+    template <typename Tab, int V, int C>
+    __device__ __forceinline__ void env_pairs_run(const EnvView &E, lds_ptr items, lds_ptr scratch, const int fill, const int done,
+                                                  const int k, const int radii_offset, const int rank)
+    {
+        if (E.dev->masked_fine != 0u) env_fine_pairs<Tab, V, C>(E, items, scratch, fill, done, k, radii_offset, rank);
+        else env_fine_packed<1, Tab, V, C>(E, items, scratch, fill, fill, done, k, radii_offset);
+    }
+    template <typename Tab, int V, int C>
+    __device__ __forceinline__ void env_pairs_flush(const EnvView &E, lds_ptr items, lds_ptr scratch, int &fill, int &done,
+                                                    const int k, const int need, const int radii_offset, const int rank)
+    {
+        if (fill + need <= C) return;
+        if (E.dev->masked_fine == 0u) return env_fine_flush<1, Tab, V, C>(E, items, scratch, fill, done, k, need, radii_offset);
+        env_fine_pairs<Tab, V, C>(E, items, scratch, fill, done, k, radii_offset, rank);
+        done += fill;
+        fill = 0;
     }
 
     // Bit of a three- or four-joint clearance table (tools/gen_hip.py: self_tables_multi): one bit per cell of an N^D grid,

@@ -150,7 +150,8 @@ namespace VMV_ROBOT_NS
     // 4+ waves per SIMD (<= 128 VGPRs, small slab); the self-collision kernel is pure register arithmetic.
     // kernel 1 writes the validity words, kernel 2 ANDs into them (same stream, in order).
     // V: what the variant compiles in (vmv_device.h kEnvFull / kEnvPrims / kEnvZOnly; the launcher picks).
-    template <int V>
+    // PAIRS (primitive-only variants): the fine phase deals (item, candidate) pairs (vmv_device.h env_fine_pairs).
+    template <int V, bool PAIRS = false>
     __global__ __launch_bounds__(kBlock, (V == kEnvFull) ? 4 : (V == kEnvClouds) ? VMV_CLOUDS_BLOCKS : (V == kEnvPrims) ? VMV_PRIMS_BLOCKS : R::kEnvBlocks) void validate_env_kernel(const EnvDev *__restrict__ env,
                                                                       const uint32_t tests_in_lds,
                                                                       const float *__restrict__ q, const uint32_t n,
@@ -176,7 +177,7 @@ namespace VMV_ROBOT_NS
             load_configs<R::kDim>(q, first, n, wave_slab, cfg, lane);
             const bool finite = sanitize_config<R::kDim>(cfg);
             const bool in_range = first + lane < n && finite;
-            const bool bad = R::template fkcc_env<1, V>(E, cfg, slab, !in_range);
+            const bool bad = R::template fkcc_env<1, V, PAIRS>(E, cfg, slab, !in_range);
             const uint64_t word = __ballot(in_range && !bad);
             if (opaque_lane_id() == 0u) bits[first / kWave] = word;  // (not `lane`: it would stay live across the whole body)
         }
@@ -254,7 +255,7 @@ namespace VMV_ROBOT_NS
         return first < lo || (hi < n && first + (uint32_t) kWave > hi);
     }
 
-    template <int V>
+    template <int V, bool PAIRS = false>
     __global__ __launch_bounds__(kBlock, (V == kEnvFull) ? 4 : (V == kEnvClouds) ? VMV_CLOUDS_BLOCKS : (V == kEnvPrims) ? VMV_PRIMS_BLOCKS : R::kEnvBlocks) void validate_env_multi_kernel(
         const MultiSeg *__restrict__ segs, const MultiTile *__restrict__ tiles, const float *__restrict__ q, const uint32_t n,
         uint64_t *__restrict__ bits)
@@ -275,7 +276,7 @@ namespace VMV_ROBOT_NS
         for (int j = 0; j < R::kDim; ++j) cfg[j] = in_seg ? cfg[j] : 0.0f;
         const bool finite = sanitize_config<R::kDim>(cfg);
         const bool in_range = in_seg && finite;
-        const bool bad = R::template fkcc_env<1, V>(E, cfg, wave_slab + lane, !in_range);
+        const bool bad = R::template fkcc_env<1, V, PAIRS>(E, cfg, wave_slab + lane, !in_range);
         const uint64_t w = __ballot(in_range && !bad);
         if (opaque_lane_id() == 0u)
         {
@@ -1035,6 +1036,14 @@ namespace VMV_ROBOT_NS
             return env.host.n_capt != 0 && env.host.n_floats + env.host.n_mvt + env.host.n_heightfield == 0;
         }
 
+        // the pair-dealt instances of the primitive-only configuration kernels (robots with R::kFinePairs;
+        // VMV_FINE_PAIRS=0 selects the other instances: measurement and test aid)
+        bool fine_pairs()
+        {
+            if (const char *e = getenv("VMV_FINE_PAIRS")) return strtoul(e, nullptr, 10) != 0ul && R::kFinePairs;
+            return R::kFinePairs;
+        }
+
         int grid_for(size_t items, size_t per_block)
         {
             const size_t blocks = (items + per_block - 1) / per_block;
@@ -1058,8 +1067,12 @@ namespace VMV_ROBOT_NS
                 if (rc != VMV_OK) return rc;
                 auto kernel = clouds_only(env) ? validate_env_kernel<kEnvClouds> : validate_env_kernel<kEnvFull>;
                 if (prims_only(env))
-                    kernel = (env.host.n_capsule + env.host.n_cuboid == 0) ? validate_env_kernel<kEnvZOnly> :
-                                                                               validate_env_kernel<kEnvPrims>;
+                {
+                    const bool z_only = env.host.n_capsule + env.host.n_cuboid == 0;
+                    kernel = z_only ? validate_env_kernel<kEnvZOnly> : validate_env_kernel<kEnvPrims>;
+                    if constexpr (R::kFinePairs)  // (the pair-dealt instances exist for these robots only)
+                        if (fine_pairs()) kernel = z_only ? validate_env_kernel<kEnvZOnly, true> : validate_env_kernel<kEnvPrims, true>;
+                }
                 if (shmem > 64u * 1024u)
                     VMV_HIP_TU(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                    (int) shmem));
@@ -1212,6 +1225,7 @@ namespace VMV_ROBOT_NS
             const MultiTile *d_tiles = reinterpret_cast<const MultiTile *>(static_cast<const char *>(lease.dev) + seg_bytes);
             if (any_shared) VMV_HIP_TU(hipMemsetAsync(d_bits, 0, (n + kWave - 1) / kWave * sizeof(uint64_t), stream));
             if (int rc = lease.upload(stream, seg_bytes + total * sizeof(MultiTile)); rc != VMV_OK) return rc;
+            const bool pairs = fine_pairs();
             auto launch = [&](const void *kernel, int c) -> int
             {
                 if (n_tiles[c] == 0) return VMV_OK;
@@ -1225,6 +1239,12 @@ namespace VMV_ROBOT_NS
                     if (c == kAttach)
                         hipLaunchKernelGGL(validate_attach_multi_kernel, grid, dim3(kBlock), shmem[c], stream, d_segs, t, d_q, m,
                                            d_bits);
+                    else if (c == 0 && pairs)
+                        hipLaunchKernelGGL((validate_env_multi_kernel<kEnvZOnly, R::kFinePairs>), grid, dim3(kBlock), shmem[c],
+                                           stream, d_segs, t, d_q, m, d_bits);
+                    else if (c == 1 && pairs)
+                        hipLaunchKernelGGL((validate_env_multi_kernel<kEnvPrims, R::kFinePairs>), grid, dim3(kBlock), shmem[c],
+                                           stream, d_segs, t, d_q, m, d_bits);
                     else if (c == 0)
                         hipLaunchKernelGGL(validate_env_multi_kernel<kEnvZOnly>, grid, dim3(kBlock), shmem[c], stream, d_segs, t,
                                            d_q, m, d_bits);
@@ -1241,8 +1261,11 @@ namespace VMV_ROBOT_NS
                 VMV_HIP_TU(hipGetLastError());
                 return VMV_OK;
             };
-            const void *kernels[kClasses + 1] = {(const void *) validate_env_multi_kernel<kEnvZOnly>,
-                                                 (const void *) validate_env_multi_kernel<kEnvPrims>,
+            // (robots without the pair-dealt instances: R::kFinePairs is false, `pairs` too, both names are one kernel)
+            const void *kernels[kClasses + 1] = {pairs ? (const void *) validate_env_multi_kernel<kEnvZOnly, R::kFinePairs> :
+                                                         (const void *) validate_env_multi_kernel<kEnvZOnly>,
+                                                 pairs ? (const void *) validate_env_multi_kernel<kEnvPrims, R::kFinePairs> :
+                                                         (const void *) validate_env_multi_kernel<kEnvPrims>,
                                                  (const void *) validate_env_multi_kernel<kEnvFull>,
                                                  (const void *) validate_env_multi_kernel<kEnvClouds>,
                                                  (const void *) validate_attach_multi_kernel};
