@@ -323,6 +323,65 @@ int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterati
 int vmv_plans_paths(const vmv_plans *plans, float *out, size_t capacity_floats);
 int vmv_plans_destroy(vmv_plans *plans);
 
+/* ---- batched PRM: many independent roadmap problems in one call ------------------------------------------ */
+/* A probabilistic roadmap per problem, for n_problems problems at once: problem p runs from starts[p] to goals[p] in
+ * envs[p]; its roadmap is built over n_samples samples, the Halton samples halton_skips[p] + 1, ... (NULL = all 0) or,
+ * where `samples` is not NULL, the caller's ([n_problems][n_samples][dimension] host floats; halton_skips is then not
+ * read).  The launches are a fixed sequence whatever the problems are: the vertices and ONE vmv_validate_batch_multi
+ * call; the k nearest valid vertices of every valid vertex; the candidate edges and ONE vmv_validate_motion_batch_multi
+ * call; the shortest path; the paths gathered.  The host synchronises once in between (the per-problem edge counts).
+ * Per problem, bit-defined (fp32, one rounding per written operation):
+ *   V = n_samples + 2 vertices: 0 = start, 1 = goal, 2 + i = sample i; valid[v] = validate(vertex v) (a non-finite
+ *   joint: invalid).  !valid[0] or !valid[1]: VMV_PLAN_INVALID_ENDPOINT, no path, no edge is asked.
+ *   d2(v, u) = sum over the joints in order of (v[j] - u[j])^2, w = sqrtf(d2), R2 = radius * radius (+inf: no cut).
+ *   nbr(v), for every valid v: the k valid vertices u != v with 0 < d2(v, u) <= R2 that come first in the order (d2, then
+ *   vertex id), fewer if fewer exist; vertices 0 and 1 are never each other's neighbour.
+ *   Candidate edges, in this order: (0, 1); then for v ascending, for slot s ascending, u = nbr(v)[s]: the edge {v, u} if
+ *   v < u or v is not in nbr(u) (every undirected pair once).  The question of {a, b}, a < b, is validate_motion(a -> b).
+ *   Edge (0, 1) valid: VMV_PLAN_SOLVED, path = [start, goal], cost = w(0, 1), iterations 0.  Else g[0] = 0, g[v] = min over
+ *   the valid edges {u, v} of fl(g[u] + w(u, v)) (the least fixpoint; w = +inf relaxes nothing); g[1] = +inf:
+ *   VMV_PLAN_NO_PATH; else VMV_PLAN_SOLVED, cost = g[1], the path walked back from 1 with parent(v) = the lowest id u with
+ *   a valid edge {u, v}, fl(g[u] + w(u, v)) == g[v] and g[u] < g[v] (a walk that finds no parent ends as
+ *   VMV_PLAN_NO_PATH); iterations = n_samples (also for VMV_PLAN_NO_PATH).
+ * A problem's result depends on its own inputs alone, bit for bit.  Agreement with the reference's incremental PRM
+ * (planning/prm.hh) is not claimed.  The result is a vmv_plans: vmv_plans_summary reports sizes2 = [valid vertices,
+ * valid edges], rounds = validation calls made, questions = candidate edges asked; vmv_plans_paths and
+ * vmv_plans_destroy work as for vmv_rrtc_multi.
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / starts / goals / settings / out
+ * or a NULL handle, n_samples not a multiple of 64 or outside 64 .. 8,128, k outside 1 .. 16, radius NaN or <= 0, halton
+ * skip + n_samples > 1,000,000 where samples is NULL, n_problems * (n_samples + 2) * k >= 2^31
+ * (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment (VMV_ERR_NOT_FINALIZED); an environment of another device
+ * (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out untouched.  n_problems == 0 is VMV_OK with an empty result.
+ * Environments not yet prepared for the robot are prepared in one batch.  Synchronous, host buffers, on the default
+ * stream; repeated handles are allowed.  The vertices are validated as 2 * n_problems segments of one
+ * vmv_validate_batch_multi call: each problem's samples own whole validity words (hence the multiple of 64), its two
+ * endpoints share a word with other problems' and rest on that call's flat layout (shared words are zeroed first and
+ * each segment's bits combined in atomically). */
+typedef struct
+{
+    uint32_t n_samples, k;
+    float radius;                /* neighbours lie within this distance; +inf = no cut */
+    int keep_roadmaps;           /* 0 / 1: keep host copies of every problem's vertex flags and candidate edges */
+} vmv_prm_settings;
+enum
+{
+    VMV_PLAN_NO_PATH = 3,         /* start and goal are valid and the roadmap does not connect them */
+    VMV_PLAN_INVALID_ENDPOINT = 4 /* the start or the goal is invalid */
+};
+int vmv_prm_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                  const uint64_t *halton_skips, const float *samples, const vmv_prm_settings *settings, vmv_plans **out);
+/* Per problem of a vmv_prm_multi result (arrays of n_problems, any may be NULL): valid vertices, candidate edges, valid
+ * edges, cost (+inf = unsolved).  VMV_ERR_INVALID_ARGUMENT on the plans of vmv_rrtc_multi; the next two also unless
+ * keep_roadmaps was set, or for p out of range. */
+int vmv_plans_roadmap_summary(const vmv_plans *plans, uint32_t *valid_vertices, uint32_t *candidate_edges,
+                              uint32_t *valid_edges, float *costs);
+/* valid[v] of problem p's n_samples + 2 vertices */
+int vmv_plans_roadmap_vertices(const vmv_plans *plans, size_t p, uint8_t *valid);
+/* problem p's candidate edges in candidate order: *n = their number (n may be NULL); pairs2 [n][2] vertex ids a < b and
+ * valid [n] (either may be NULL; with both NULL the call only counts); VMV_ERR_CAPACITY if capacity (in edges) is too
+ * small (nothing is written but *n) */
+int vmv_plans_roadmap_edges(const vmv_plans *plans, size_t p, uint32_t *pairs2, uint8_t *valid, size_t capacity, size_t *n);
+
 /* ---- lockstep simplifier: many independent paths in one call -------------------------------------------- */
 /* simplify() (planning/simplify.hh:192-260) with the SHORTCUT and BSPLINE routines for n_paths paths at once: path p is
  * points[offsets[p] .. offsets[p + 1]) ([offsets[n_paths]][dimension] host floats, offsets in waypoints, offsets[0] = 0)

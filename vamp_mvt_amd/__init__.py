@@ -728,6 +728,85 @@ class _Robot(types.ModuleType):
         return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
                     rounds=int(rounds.value), questions=int(questions.value))
 
+    def prm_multi_raw(self, starts, goals, environments, settings, skips=None, samples=None):
+        """vmv_prm_multi: one roadmap per problem, problem p from starts[p] to goals[p] in environments[p] (None = the
+        empty environment) over the Halton samples skips[p] + 1, ... (None = all 0) or over `samples`
+        ([n][n_samples][dim], or [n_samples][dim] for every problem).  settings: n_samples, k, radius, keep_roadmaps.
+        -> dict of per-problem numpy arrays (status, iterations, sizes [n][2] = valid vertices and valid edges,
+        path_lengths, candidate_edges, costs), the packed waypoints (paths [sum(path_lengths)][dim]), the totals rounds
+        and questions, and with keep_roadmaps `roadmaps`: per problem (vertex flags bool[n_samples + 2], candidate
+        pairs uint32[m][2], their flags bool[m]).  planning.prm_multi is the caller-facing form.  Every argument is
+        checked before any library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = a.shape[0]
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        ns, k, radius = int(settings.n_samples), int(settings.k), float(settings.radius)
+        keep = bool(getattr(settings, "keep_roadmaps", False))
+        if ns % 64 != 0 or not 64 <= ns <= 8128:
+            raise ValueError("n_samples must be a multiple of 64 from 64 to 8,128")
+        if not 1 <= k <= 16:
+            raise ValueError("k must be from 1 to 16")
+        if not radius > 0:
+            raise ValueError("radius must be positive (inf = no cut)")
+        if n * (ns + 2) * k >= 2 ** 31:
+            raise ValueError("n_problems * (n_samples + 2) * k must stay below 2^31")
+        sk = sm = None
+        if samples is not None:
+            sm = _f32(samples)
+            if sm.shape == (ns, self._dim):
+                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
+            if sm.shape != (n, ns, self._dim):
+                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
+        if skips is not None:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
+                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        cs = _lib.PrmSettings(ns, k, radius, int(keep))
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        plans = ctypes.c_void_p()
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        check(lib.vmv_prm_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
+                                None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(plans)), "vmv_prm_multi")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(u8), iterations.ctypes.data_as(_lib.c_u32_p),
+                                        sizes.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
+                                        ctypes.byref(rounds), ctypes.byref(questions)), "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+            candidates, costs = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+            check(lib.vmv_plans_roadmap_summary(plans, None, candidates.ctypes.data_as(_lib.c_u32_p), None, _fp(costs)),
+                  "vmv_plans_roadmap_summary")
+            out = dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
+                       candidate_edges=candidates, costs=costs, rounds=int(rounds.value), questions=int(questions.value))
+            if keep:
+                roadmaps = []
+                for p in range(n):
+                    vertex = np.zeros(ns + 2, np.uint8)
+                    check(lib.vmv_plans_roadmap_vertices(plans, p, vertex.ctypes.data_as(u8)), "vmv_plans_roadmap_vertices")
+                    m = int(candidates[p])
+                    pairs, flags = np.zeros((m, 2), np.uint32), np.zeros(m, np.uint8)
+                    got = ctypes.c_size_t(0)
+                    check(lib.vmv_plans_roadmap_edges(plans, p, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(u8), m,
+                                                      ctypes.byref(got)), "vmv_plans_roadmap_edges")
+                    roadmaps.append((vertex.astype(bool), pairs[:got.value], flags[:got.value].astype(bool)))
+                out["roadmaps"] = roadmaps
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return out
+
     def simplify_multi_raw(self, paths, environments, settings):
         """vmv_simplify_multi: the reference's simplify() with the SHORTCUT and BSPLINE routines for many paths in
         lockstep, path p ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).

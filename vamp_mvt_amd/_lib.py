@@ -30,6 +30,12 @@ class RrtcSettings(ctypes.Structure):
                 ("max_iterations", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
 
 
+class PrmSettings(ctypes.Structure):
+    """vmv_prm_settings"""
+    _fields_ = [("n_samples", ctypes.c_uint32), ("k", ctypes.c_uint32), ("radius", ctypes.c_float),
+                ("keep_roadmaps", ctypes.c_int)]
+
+
 class SimplifySettings(ctypes.Structure):
     """vmv_simplify_settings"""
     _fields_ = [("max_iterations", ctypes.c_uint32), ("interpolate", ctypes.c_uint32), ("n_operations", ctypes.c_uint32),
@@ -136,6 +142,11 @@ def _load():
         "vmv_plans_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_plans_paths": (I, [V, c_float_p, S]),
         "vmv_plans_destroy": (I, [V]),
+        "vmv_prm_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, c_float_p, ctypes.POINTER(PrmSettings),
+                              ctypes.POINTER(V)]),
+        "vmv_plans_roadmap_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p, c_float_p]),
+        "vmv_plans_roadmap_vertices": (I, [V, S, ctypes.POINTER(ctypes.c_uint8)]),
+        "vmv_plans_roadmap_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
         "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
                                    ctypes.POINTER(V)]),
         "vmv_paths_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),

@@ -349,6 +349,25 @@ def install(robot):
                 n *= 2
         return as_result(res, t0)
 
+    def prm_multi(starts, goals, environments, settings, skips=None, samples=None):
+        """planning.prm_multi with this robot and the reference-shaped RoadmapSettings: n_samples = min(max_samples,
+        2048) rounded down to a multiple of 64 and at least 64, k = min(max_neighbors(n_samples), 16) and at least 1, as
+        roadmap() maps it -> list[PlanningResult] (each with `status`; nanoseconds is the whole call's time divided by the problems)"""
+        t0 = time.perf_counter_ns()
+        n = max(64, min(int(settings.max_samples), 2048) // 64 * 64)
+        s = planning.PRMMultiSettings(n_samples=n, k=max(1, min(settings.max_neighbors(n), 16)))
+        results = planning.prm_multi(robot, starts, goals, environments, s, skips, samples)
+        each = (time.perf_counter_ns() - t0) // max(len(results), 1)
+        out = []
+        for r in results:
+            path = Path()
+            for q in r.path:
+                path.append(q)
+            res = PlanningResult(path, each, r.iterations, r.size, r.cost)
+            res.status = r.status
+            out.append(res)
+        return out
+
     def simplify(path, environment, settings, rng):
         """greedy shortcutting: for every waypoint the farthest later waypoint it can reach by a valid motion; the
         candidate motions of one pass are validated together (`validate_motion_batch`)"""
@@ -398,7 +417,7 @@ def install(robot):
         return out
 
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
-    robot.rrtc_multi, robot.simplify_multi = rrtc_multi, simplify_multi
+    robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 

@@ -1,0 +1,28 @@
+// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi): vmv_plans_summary,
+// vmv_plans_paths and vmv_plans_destroy (vmv_rrtc_multi.hip) read the first block whichever call made it.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+struct vmv_plans
+{
+    size_t n = 0;
+    int dim = 0;
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> iterations, sizes2, path_lengths;
+    std::vector<float> paths;  // packed in problem order
+    uint64_t rounds = 0, questions = 0;
+
+    // vmv_prm_multi only (vmv_plans_roadmap_*)
+    bool prm = false, kept = false;  // made by vmv_prm_multi; with keep_roadmaps
+    uint32_t n_samples = 0;
+    std::vector<uint32_t> candidate_edges;  // [n]
+    std::vector<float> costs;               // [n]
+    std::vector<uint8_t> vertex_valid;      // kept: [n][n_samples + 2]
+    std::vector<uint32_t> edge_offsets;     // kept: [n + 1] first candidate edge of each problem
+    std::vector<uint32_t> edge_pairs;       // kept: [edges][2] vertex ids a < b, in candidate order
+    std::vector<uint8_t> edge_valid;        // kept: [edges]
+};

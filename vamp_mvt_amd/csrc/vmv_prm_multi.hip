@@ -1,0 +1,625 @@
+// vmv_prm_multi.hip — a batched PRM over many independent problems (vmv_prm_multi).
+//
+// A fixed sequence of launches, whatever the problems are: the vertices (Halton samples or the caller's) and ONE
+// vmv_validate_batch_multi call; prm_knn_kernel (the k nearest valid vertices of every valid vertex); the candidate
+// edges counted, scanned and written in the contract's order and ONE vmv_validate_motion_batch_multi call;
+// prm_sssp_kernel (one workgroup per problem: the fp32 shortest-path fixpoint and the parent walk); the paths gathered
+// into the packed vmv_plans buffers.  The host synchronises once in between, for the per-problem edge counts the edge
+// call's offsets need.
+//
+// Arithmetic contract: fp32, one rounding per written operation (-ffp-contract=off; sqrtf is correctly rounded on
+// gfx950).  d2(v, u) = the sum over the joints in order of (v[j] - u[j])^2, so d2(v, u) == d2(u, v) bit for bit;
+// neighbours are ordered by (d2, vertex id), a total order, so any parallel selection gives the same lists.  Joints
+// beyond the robot's are staged as zeros: adding +0 to a non-negative or non-finite sum changes no bit.
+// Vertex memory: the samples of all problems [P][n_samples][dim], then (start, goal) of all problems [P][2][dim]; a
+// problem's samples own whole validity words (n_samples is a multiple of 64).  The P endpoint segments of two
+// configurations each SHARE validity words: correctness there rests on vmv_validate_batch_multi's flat layout, which zeroes
+// the words of a call with such segments and ORs / ANDs each segment's bits in atomically.
+// Plain vector stores; atomics on LDS words only.  Every loop has a bound that holds whatever the data says.
+#include "../../include/vamp_mvt_amd.h"
+
+#include "vmv_lockstep.h"
+#include "vmv_plans.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cmath>
+#include <cstring>
+
+namespace vmv
+{
+    namespace
+    {
+        constexpr uint32_t kPrmBlock = 256;
+        constexpr uint32_t kPrmKMax = 16;
+        constexpr uint32_t kPrmMaxDim = 16;
+        constexpr uint32_t kPrmMinSamples = 64, kPrmMaxSamples = 8128;
+        constexpr uint32_t kPrmMaxVertices = kPrmMaxSamples + 2;
+        constexpr uint32_t kPrmSsspBlock = 512;
+        constexpr uint32_t kPrmLaunchBlocks = 32768;  // workgroups per launch of the per-problem kernels: a larger call
+                                                      // is launched chunk by chunk of problems (grids stay far below 2^32 threads)
+        constexpr uint32_t kNone = 0xffffffffu;
+        constexpr uint32_t kInfBits = 0x7f800000u;
+
+        struct PrmParams
+        {
+            uint32_t dim, n_samples, V, k, n_problems;
+            float r2;
+            float lower[kPrmMaxDim], span[kPrmMaxDim];
+        };
+
+        struct PrmResult  // 32 bytes per problem
+        {
+            uint32_t status, path_len, iterations, valid_vertices, candidate_edges, valid_edges;
+            float cost;
+            uint32_t pad;
+        };
+
+        struct PrmArrays
+        {
+            float *verts;             // [P * n_samples + 2 * P][dim]
+            const uint64_t *vbits;    // validity of the vertices, in that order
+            const uint64_t *skips;    // [P]
+            uint32_t *nbr;            // [P][V][k] neighbour lists, kNone after the last
+            uint32_t *counts;         // [P * V + 1] candidate edges owned by (problem, vertex), the last 0
+            uint32_t *first;          // [P * V + 1] their exclusive scan: first edge of (problem, vertex), the last the total
+            uint32_t *edge_offsets;   // [P + 1] first edge of each problem
+            uint32_t *pairs;          // [E][2] vertex ids a < b of edge e
+            float *weights;           // [E]
+            float *q_a, *q_b;         // [E][dim] the edge questions
+            const uint64_t *ebits;    // their answers
+            uint32_t *walk;           // [P][V] the path's vertex ids from the goal backwards
+            PrmResult *result;        // [P]
+        };
+
+        __device__ __forceinline__ size_t vertex_at(const PrmParams &P, uint32_t p, uint32_t v)  // index into verts / vbits
+        {
+            return v < 2u ? (size_t) P.n_problems * P.n_samples + 2u * (size_t) p + v : (size_t) p * P.n_samples + (v - 2u);
+        }
+        __device__ __forceinline__ bool bit_at(const uint64_t *__restrict__ bits, size_t i)
+        {
+            return (bits[i >> 6] >> (i & 63u)) & 1ull;
+        }
+        __device__ __forceinline__ bool ends_valid(const PrmParams &P, const uint64_t *__restrict__ vbits, uint32_t p)
+        {
+            return bit_at(vbits, vertex_at(P, p, 0)) && bit_at(vbits, vertex_at(P, p, 1));
+        }
+        __device__ __forceinline__ float dist2(const float *__restrict__ a, const float *__restrict__ b, uint32_t dim)
+        {
+            float sum = 0.f;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                const float df = a[j] - b[j];
+                sum = sum + df * df;
+            }
+            return sum;
+        }
+
+        __global__ __launch_bounds__(kPrmBlock) void prm_halton_kernel(const PrmParams P, const PrmArrays D)
+        {
+            const size_t total = (size_t) P.n_problems * P.n_samples * P.dim;
+            const size_t i = (size_t) blockIdx.x * kPrmBlock + threadIdx.x;
+            if (i >= total) return;
+            const uint32_t j = (uint32_t) (i % P.dim);
+            const size_t s = i / P.dim;
+            const uint32_t p = (uint32_t) (s / P.n_samples), k = (uint32_t) (s % P.n_samples);
+            D.verts[i] = halton_element(D.skips[p] + 1ull + k, (int) j, P.lower[j], P.span[j]);
+        }
+
+        // One lane per query vertex, a workgroup within one problem (problem p0 + blockIdx.x / tiles, tile blockIdx.x % tiles).  The candidates go through LDS a tile
+        // of kPrmBlock at a time: every lane reads the same candidate (a broadcast read) and its validity flag is the
+        // same in the whole wave.  The k best sit in registers as a sorted list of KMAX entries, fully unrolled; the
+        // list's first KMAX - k entries hold the key 0, below every real key (d2 > 0), so they never move and the k-th
+        // best is always the last entry: one strict `<` against it rejects most candidates.  Keys are the bits of d2
+        // (positive floats order as unsigned integers; +inf included); an empty entry holds 0xffffffff.  Candidates come
+        // in ascending id order, so among equal keys the strict `<` keeps the lower id.
+        template <int DIM>
+        __global__ __launch_bounds__(kPrmBlock) void prm_knn_kernel(const PrmParams P, const PrmArrays D, const uint32_t p0, const uint32_t tiles)
+        {
+            __shared__ __align__(16) float s_tile[kPrmBlock * DIM];
+            __shared__ uint32_t s_valid[kPrmBlock];
+            const uint32_t p = p0 + blockIdx.x / tiles, tid = threadIdx.x, v = (blockIdx.x % tiles) * kPrmBlock + tid, V = P.V, dim = P.dim;
+            if (!ends_valid(P, D.vbits, p)) return;  // workgroup-uniform: INVALID_ENDPOINT asks nothing (the lists are not read)
+            const bool query = v < V && bit_at(D.vbits, vertex_at(P, p, v));
+            float q[DIM];
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) q[j] = (query && (uint32_t) j < dim) ? D.verts[vertex_at(P, p, v) * dim + j] : 0.f;
+            uint32_t bk[kPrmKMax], bi[kPrmKMax];
+#pragma unroll
+            for (uint32_t s = 0; s < kPrmKMax; ++s) bk[s] = s < kPrmKMax - P.k ? 0u : kNone, bi[s] = kNone;
+            const uint32_t r2_bits = __float_as_uint(P.r2);
+
+            for (uint32_t base = 0; base < V; base += kPrmBlock)  // <= ceil(V / kPrmBlock) tiles
+            {
+                const uint32_t u_mine = base + tid;
+                const bool ok = u_mine < V && bit_at(D.vbits, vertex_at(P, p, u_mine));
+                s_valid[tid] = ok ? 1u : 0u;
+#pragma unroll
+                for (int j = 0; j < DIM; ++j)
+                    s_tile[tid * DIM + j] = (ok && (uint32_t) j < dim) ? D.verts[vertex_at(P, p, u_mine) * dim + j] : 0.f;
+                __syncthreads();
+                const uint32_t count = V - base < kPrmBlock ? V - base : kPrmBlock;
+                if (query)
+                    for (uint32_t c = 0; c < count; ++c)
+                    {
+                        if (!s_valid[c]) continue;  // the same in every lane
+                        const uint32_t u = base + c;
+                        float sum = 0.f;
+#pragma unroll
+                        for (int j = 0; j < DIM; ++j)
+                        {
+                            const float df = q[j] - s_tile[c * DIM + j];
+                            sum = sum + df * df;
+                        }
+                        const uint32_t key = __float_as_uint(sum);  // valid vertices are finite: sum is in [+0, +inf]
+                        if (!(key < bk[kPrmKMax - 1])) continue;
+                        if (key == 0u || key > r2_bits || u == v || (u < 2u && v < 2u)) continue;
+#pragma unroll
+                        for (int s = kPrmKMax - 1; s >= 1; --s)
+                        {
+                            const bool shift = key < bk[s - 1];
+                            const bool here = !shift && key < bk[s];
+                            bi[s] = shift ? bi[s - 1] : (here ? u : bi[s]);
+                            bk[s] = shift ? bk[s - 1] : (here ? key : bk[s]);
+                        }
+                        if (key < bk[0]) bk[0] = key, bi[0] = u;
+                    }
+                __syncthreads();  // the tile is rewritten
+            }
+            if (v < V)
+            {
+                uint32_t *out = D.nbr + ((size_t) p * V + v) * P.k;
+#pragma unroll
+                for (uint32_t s = 0; s < kPrmKMax; ++s)
+                    if (s >= kPrmKMax - P.k) out[s - (kPrmKMax - P.k)] = bi[s];
+            }
+        }
+
+        // slot s of vertex v is an edge of the list iff v < u, or v is not among u's neighbours
+        __device__ __forceinline__ bool owns(const uint32_t *__restrict__ nbr_p, uint32_t k, uint32_t v, uint32_t u)
+        {
+            if (v < u) return true;
+            bool found = false;
+            for (uint32_t t = 0; t < k; ++t) found |= nbr_p[(size_t) u * k + t] == v;
+            return !found;
+        }
+
+        // counts[p * V + v] = the candidate edges vertex v of problem p contributes (vertex 0: the edge (0, 1) as well);
+        // counts[P * V] = 0, so that the exclusive scan ends with the total
+        __global__ __launch_bounds__(kPrmBlock) void prm_count_kernel(const PrmParams P, const PrmArrays D)
+        {
+            const size_t total = (size_t) P.n_problems * P.V;
+            const size_t i = (size_t) blockIdx.x * kPrmBlock + threadIdx.x;
+            if (i > total) return;
+            uint32_t n = 0;
+            if (i < total)
+            {
+                const uint32_t p = (uint32_t) (i / P.V), v = (uint32_t) (i % P.V);
+                if (ends_valid(P, D.vbits, p) && bit_at(D.vbits, vertex_at(P, p, v)))
+                {
+                    const uint32_t *nbr_p = D.nbr + (size_t) p * P.V * P.k;
+                    n = v == 0u ? 1u : 0u;
+                    for (uint32_t s = 0; s < P.k; ++s)
+                    {
+                        const uint32_t u = nbr_p[(size_t) v * P.k + s];
+                        if (u >= P.V) break;  // kNone: the list ended
+                        n += owns(nbr_p, P.k, v, u) ? 1u : 0u;
+                    }
+                }
+            }
+            D.counts[i] = n;
+        }
+
+        __global__ __launch_bounds__(kPrmBlock) void prm_offsets_kernel(const PrmParams P, const PrmArrays D)
+        {
+            const uint32_t p = blockIdx.x * kPrmBlock + threadIdx.x;
+            if (p <= P.n_problems) D.edge_offsets[p] = D.first[(size_t) p * P.V];
+        }
+
+        // the edges of (p, v) start at first[p * V + v], in slot order
+        __global__ __launch_bounds__(kPrmBlock) void prm_write_kernel(const PrmParams P, const PrmArrays D)
+        {
+            const size_t total = (size_t) P.n_problems * P.V;
+            const size_t i = (size_t) blockIdx.x * kPrmBlock + threadIdx.x;
+            if (i >= total) return;
+            uint32_t e = D.first[i];
+            const uint32_t end = D.first[i + 1];
+            if (e == end) return;
+            const uint32_t p = (uint32_t) (i / P.V), v = (uint32_t) (i % P.V), dim = P.dim;
+            const uint32_t *nbr_p = D.nbr + (size_t) p * P.V * P.k;
+            const auto emit = [&](uint32_t a, uint32_t b) {
+                const float *qa = D.verts + vertex_at(P, p, a) * dim, *qb = D.verts + vertex_at(P, p, b) * dim;
+                D.pairs[2 * (size_t) e] = a, D.pairs[2 * (size_t) e + 1] = b;
+                D.weights[e] = sqrtf(dist2(qa, qb, dim));
+                for (uint32_t j = 0; j < dim; ++j) D.q_a[(size_t) e * dim + j] = qa[j], D.q_b[(size_t) e * dim + j] = qb[j];
+                ++e;
+            };
+            if (v == 0u) emit(0u, 1u);
+            for (uint32_t s = 0; s < P.k && e < end; ++s)
+            {
+                const uint32_t u = nbr_p[(size_t) v * P.k + s];
+                if (u >= P.V) break;
+                if (owns(nbr_p, P.k, v, u)) emit(v < u ? v : u, v < u ? u : v);
+            }
+        }
+
+        // One workgroup per problem.  g lives in LDS as the bits of non-negative floats, which order as unsigned integers:
+        // g[v] = min over valid edges {u, v} of fl(g[u] + w) is reached by edge-parallel sweeps with atomicMin in both
+        // directions; fl(a + w) is monotone in a and >= a, so the least fixpoint is the same whatever the order of the
+        // relaxations, and V sweeps bound it.  Then the parent walk from the goal: per step the lowest id u with a valid
+        // edge {u, cur}, fl(g[u] + w) == g[cur] and g[u] < g[cur] (a workgroup min-reduction), at most V steps.
+        __global__ __launch_bounds__(kPrmSsspBlock) void prm_sssp_kernel(const PrmParams P, const PrmArrays D, const uint32_t p0)
+        {
+            __shared__ uint32_t g[kPrmMaxVertices];
+            __shared__ uint32_t s_count[2], s_best;
+            const uint32_t p = p0 + blockIdx.x, tid = threadIdx.x, V = P.V;
+            PrmResult r{};
+            r.status = VMV_PLAN_NO_PATH, r.cost = INFINITY;
+            if (tid < 2u) s_count[tid] = 0u;
+            if (tid == 0u) s_best = kNone;
+            for (uint32_t v = tid; v < V; v += kPrmSsspBlock) g[v] = kInfBits;
+            __syncthreads();
+            uint32_t mine = 0;
+            for (uint32_t v = tid; v < V; v += kPrmSsspBlock) mine += bit_at(D.vbits, vertex_at(P, p, v)) ? 1u : 0u;
+            if (mine) atomicAdd(&s_count[0], mine);
+            const uint32_t e0 = D.edge_offsets[p], e1 = D.edge_offsets[p + 1];
+            mine = 0;
+            for (uint32_t e = e0 + tid; e < e1; e += kPrmSsspBlock) mine += bit_at(D.ebits, e) ? 1u : 0u;
+            if (mine) atomicAdd(&s_count[1], mine);
+            if (tid == 0u) g[0] = 0u;
+            __syncthreads();
+            r.valid_vertices = s_count[0], r.valid_edges = s_count[1], r.candidate_edges = e1 - e0;
+
+            uint32_t *walk = D.walk + (size_t) p * V;
+            if (!ends_valid(P, D.vbits, p))
+                r.status = VMV_PLAN_INVALID_ENDPOINT;
+            else if (e1 > e0 && bit_at(D.ebits, e0))  // the edge (0, 1) comes first
+            {
+                r.status = VMV_PLAN_SOLVED, r.path_len = 2, r.cost = D.weights[e0];
+                if (tid == 0u) walk[0] = 1u, walk[1] = 0u;
+            }
+            else
+            {
+                r.iterations = P.n_samples;
+                for (uint32_t sweep = 0; sweep < V; ++sweep)
+                {
+                    int changed = 0;
+                    for (uint32_t e = e0 + tid; e < e1; e += kPrmSsspBlock)
+                    {
+                        if (!bit_at(D.ebits, e)) continue;
+                        const float w = D.weights[e];
+                        if (!(w < INFINITY)) continue;  // an overflowed d2 relaxes nothing
+                        const uint32_t a = D.pairs[2 * (size_t) e], b = D.pairs[2 * (size_t) e + 1];
+                        const uint32_t ga = g[a], gb = g[b];
+                        if (ga < kInfBits)
+                        {
+                            const uint32_t c = __float_as_uint(__uint_as_float(ga) + w);
+                            if (c < gb) changed |= atomicMin(&g[b], c) > c;
+                        }
+                        if (gb < kInfBits)
+                        {
+                            const uint32_t c = __float_as_uint(__uint_as_float(gb) + w);
+                            if (c < ga) changed |= atomicMin(&g[a], c) > c;
+                        }
+                    }
+                    if (!__syncthreads_or(changed)) break;
+                }
+                if (g[1] < kInfBits)
+                {
+                    uint32_t cur = 1u, len = 1u;
+                    bool lost = false;
+                    if (tid == 0u) walk[0] = 1u;
+                    for (uint32_t step = 0; step + 1u < V && cur != 0u; ++step)
+                    {
+                        const uint32_t gc = g[cur];
+                        uint32_t best = kNone;
+                        for (uint32_t e = e0 + tid; e < e1; e += kPrmSsspBlock)
+                        {
+                            if (!bit_at(D.ebits, e)) continue;
+                            const uint32_t a = D.pairs[2 * (size_t) e], b = D.pairs[2 * (size_t) e + 1];
+                            if (a != cur && b != cur) continue;
+                            const uint32_t u = a == cur ? b : a, gu = g[u];
+                            const float w = D.weights[e];
+                            if (!(w < INFINITY) || !(gu < gc)) continue;
+                            if (__float_as_uint(__uint_as_float(gu) + w) == gc && u < best) best = u;
+                        }
+                        if (best != kNone) atomicMin(&s_best, best);
+                        __syncthreads();
+                        best = s_best;
+                        __syncthreads();
+                        if (tid == 0u) s_best = kNone;
+                        if (best == kNone)  // only where an edge is below half an ulp of g: ends as NO_PATH
+                        {
+                            lost = true;
+                            break;
+                        }
+                        cur = best;
+                        if (tid == 0u) walk[len] = cur;
+                        ++len;
+                        __syncthreads();
+                    }
+                    if (!lost && cur == 0u) r.status = VMV_PLAN_SOLVED, r.path_len = len, r.cost = __uint_as_float(g[1]);
+                }
+            }
+            if (tid == 0u) D.result[p] = r;
+        }
+
+        __global__ __launch_bounds__(kPrmBlock) void prm_gather_kernel(const PrmParams P, const PrmArrays D,
+                                                                        const uint64_t *__restrict__ offsets, float *__restrict__ paths)
+        {
+            const uint32_t p = blockIdx.x * kPrmBlock + threadIdx.x;
+            if (p >= P.n_problems) return;
+            const uint32_t len = D.result[p].path_len <= P.V ? D.result[p].path_len : 0u;
+            const uint32_t *walk = D.walk + (size_t) p * P.V;
+            float *out = paths + offsets[p] * P.dim;
+            for (uint32_t s = 0; s < len; ++s)
+            {
+                const uint32_t v = walk[len - 1u - s];
+                if (v >= P.V) return;
+                const float *q = D.verts + vertex_at(P, p, v) * P.dim;
+                for (uint32_t j = 0; j < P.dim; ++j) out[(size_t) s * P.dim + j] = q[j];
+            }
+        }
+
+#define VMV_PRM_LAUNCHED(name)                                \
+    do                                                        \
+    {                                                         \
+        const hipError_t e_ = hipGetLastError();              \
+        if (e_ != hipSuccess)                                 \
+        {                                                     \
+            (void) hipDeviceSynchronize();                    \
+            return hip_status(e_, name);                      \
+        }                                                     \
+    } while (0)
+
+        // The caller has checked every argument, n > 0, and every environment is finalized on the current device with
+        // the robot's part built.
+        int prm_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
+                          const float *starts, const float *goals, const uint64_t *skips, const float *samples,
+                          const vmv_prm_settings &S, vmv_plans *plans)
+        {
+            PrmParams P{};
+            P.dim = (uint32_t) dim, P.n_samples = S.n_samples, P.V = S.n_samples + 2u, P.k = S.k, P.n_problems = (uint32_t) n;
+            P.r2 = S.radius * S.radius;
+            for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
+            const size_t ns = S.n_samples, V = P.V, n_sample_cfgs = n * ns, n_cfgs = n_sample_cfgs + 2 * n, nv = n * V;
+            const uint32_t n32 = (uint32_t) n;
+            hipStream_t stream = nullptr;
+
+            DeviceBuffers mem;
+            PrmArrays D{};
+            uint64_t *d_vbits = nullptr, *d_skips = nullptr, *d_ebits = nullptr, *d_path_offsets = nullptr;
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.verts, n_cfgs * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_vbits, (n_cfgs + 63) / 64));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.nbr, nv * S.k));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.counts, nv + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.first, nv + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.edge_offsets, n + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.walk, nv));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.result, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_path_offsets, n));
+            D.vbits = d_vbits, D.skips = d_skips;
+
+            // 1. vertices: the samples of all problems, then (start, goal) of all problems; one validation call
+            if (samples)
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.verts, samples, n_sample_cfgs * (size_t) dim * 4, hipMemcpyHostToDevice, stream));
+            else
+            {
+                if (skips)
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
+                else
+                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
+                const size_t total = n_sample_cfgs * (size_t) dim;
+                hipLaunchKernelGGL(prm_halton_kernel, dim3((uint32_t) ((total + kPrmBlock - 1) / kPrmBlock)), dim3(kPrmBlock), 0, stream, P, D);
+                VMV_PRM_LAUNCHED("prm_halton_kernel");
+            }
+            std::vector<float> ends(2 * n * (size_t) dim);
+            for (size_t p = 0; p < n; ++p)
+            {
+                std::memcpy(&ends[(2 * p) * (size_t) dim], starts + p * (size_t) dim, (size_t) dim * 4);
+                std::memcpy(&ends[(2 * p + 1) * (size_t) dim], goals + p * (size_t) dim, (size_t) dim * 4);
+            }
+            VMV_LOCKSTEP_HIP(hipMemcpy(D.verts + n_sample_cfgs * (size_t) dim, ends.data(), ends.size() * 4, hipMemcpyHostToDevice));
+            {
+                std::vector<const vmv_env *> envs2(2 * n);
+                std::vector<size_t> seg(2 * n + 1);
+                for (size_t p = 0; p < n; ++p)
+                {
+                    envs2[p] = envs2[n + p] = envs[p];
+                    seg[p] = p * ns, seg[n + p] = n_sample_cfgs + 2 * p;
+                }
+                seg[2 * n] = n_cfgs;
+                if (int rc = vmv_validate_batch_multi(robot, envs2.data(), seg.data(), 2 * n, D.verts, d_vbits, stream); rc != VMV_OK)
+                {
+                    (void) hipDeviceSynchronize();
+                    return rc;
+                }
+            }
+            uint64_t validation_calls = 1;
+
+            // 2. neighbours
+            {
+                const uint32_t tiles = (uint32_t) ((V + kPrmBlock - 1) / kPrmBlock), chunk = kPrmLaunchBlocks / tiles;  // tiles <= 32
+                for (uint32_t p0 = 0; p0 < n32; p0 += chunk)
+                {
+                    const dim3 grid(std::min(chunk, n32 - p0) * tiles);
+                    if (dim <= 8)
+                        hipLaunchKernelGGL(prm_knn_kernel<8>, grid, dim3(kPrmBlock), 0, stream, P, D, p0, tiles);
+                    else
+                        hipLaunchKernelGGL(prm_knn_kernel<16>, grid, dim3(kPrmBlock), 0, stream, P, D, p0, tiles);
+                    VMV_PRM_LAUNCHED("prm_knn_kernel");
+                }
+            }
+
+            // 3. candidate edges: counted, scanned, written in the contract's order; one validation call
+            const uint32_t vertex_blocks = (uint32_t) ((nv + 1 + kPrmBlock - 1) / kPrmBlock);
+            hipLaunchKernelGGL(prm_count_kernel, dim3(vertex_blocks), dim3(kPrmBlock), 0, stream, P, D);
+            VMV_PRM_LAUNCHED("prm_count_kernel");
+            {
+                size_t scan_bytes = 0;
+                VMV_LOCKSTEP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, D.counts, D.first, (int) (nv + 1), stream));
+                uint8_t *scan_tmp = nullptr;
+                VMV_LOCKSTEP_HIP(mem.alloc(&scan_tmp, scan_bytes));
+                VMV_LOCKSTEP_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, D.counts, D.first, (int) (nv + 1), stream));
+            }
+            hipLaunchKernelGGL(prm_offsets_kernel, dim3((n32 + 1 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D);
+            VMV_PRM_LAUNCHED("prm_offsets_kernel");
+            std::vector<uint32_t> edge_offsets(n + 1);
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(edge_offsets.data(), D.edge_offsets, (n + 1) * 4, hipMemcpyDeviceToHost, stream));
+            VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));  // the call's one synchronisation before its results
+            const size_t E = edge_offsets[n];
+            if (E >= kMultiMaxConfigs) return hip_status(hipErrorInvalidValue, "vmv_prm_multi: 2^31 candidate edges or more");
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.pairs, 2 * E));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.weights, E));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_a, E * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_b, E * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_ebits, (E + 63) / 64));
+            D.ebits = d_ebits;
+            if (E > 0)
+            {
+                hipLaunchKernelGGL(prm_write_kernel, dim3(vertex_blocks), dim3(kPrmBlock), 0, stream, P, D);
+                VMV_PRM_LAUNCHED("prm_write_kernel");
+                std::vector<size_t> seg(edge_offsets.begin(), edge_offsets.end());
+                if (int rc = vmv_validate_motion_batch_multi(robot, envs, seg.data(), n, D.q_a, D.q_b, d_ebits, stream); rc != VMV_OK)
+                {
+                    (void) hipDeviceSynchronize();
+                    return rc;
+                }
+                ++validation_calls;
+            }
+
+            // 4. shortest paths
+            for (uint32_t p0 = 0; p0 < n32; p0 += kPrmLaunchBlocks)
+            {
+                hipLaunchKernelGGL(prm_sssp_kernel, dim3(std::min(kPrmLaunchBlocks, n32 - p0)), dim3(kPrmSsspBlock), 0, stream, P, D, p0);
+                VMV_PRM_LAUNCHED("prm_sssp_kernel");
+            }
+
+            // 5. results: the per-problem records, then the paths gathered on the device into one packed buffer
+            std::vector<PrmResult> results(n);
+            VMV_LOCKSTEP_HIP(hipMemcpy(results.data(), D.result, n * sizeof(PrmResult), hipMemcpyDeviceToHost));
+            plans->n = n, plans->dim = dim, plans->rounds = validation_calls, plans->questions = E;
+            plans->prm = true, plans->n_samples = S.n_samples;
+            plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
+            plans->candidate_edges.resize(n), plans->costs.resize(n);
+            std::vector<uint64_t> path_offsets(n);
+            uint64_t total = 0;
+            for (size_t p = 0; p < n; ++p)
+            {
+                const PrmResult &r = results[p];
+                plans->status[p] = (uint8_t) r.status;
+                plans->iterations[p] = r.iterations;
+                plans->sizes2[2 * p] = r.valid_vertices, plans->sizes2[2 * p + 1] = r.valid_edges;
+                plans->path_lengths[p] = r.path_len;
+                plans->candidate_edges[p] = r.candidate_edges, plans->costs[p] = r.cost;
+                path_offsets[p] = total;
+                total += r.path_len;
+            }
+            plans->paths.resize(total * (size_t) dim);
+            if (total)
+            {
+                float *d_paths = nullptr;
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_path_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL(prm_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D,
+                                   d_path_offsets, d_paths);
+                VMV_PRM_LAUNCHED("prm_gather_kernel");
+                VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
+            }
+            if (S.keep_roadmaps)
+            {
+                std::vector<uint64_t> vbits((n_cfgs + 63) / 64), ebits((E + 63) / 64);
+                VMV_LOCKSTEP_HIP(hipMemcpy(vbits.data(), d_vbits, vbits.size() * 8, hipMemcpyDeviceToHost));
+                const auto bit = [](const std::vector<uint64_t> &w, size_t i) { return (uint8_t) ((w[i >> 6] >> (i & 63)) & 1u); };
+                plans->vertex_valid.resize(nv);
+                for (size_t p = 0; p < n; ++p)
+                    for (size_t v = 0; v < V; ++v)
+                        plans->vertex_valid[p * V + v] = bit(vbits, v < 2 ? n_sample_cfgs + 2 * p + v : p * ns + (v - 2));
+                plans->edge_offsets.assign(edge_offsets.begin(), edge_offsets.end());
+                plans->edge_pairs.resize(2 * E), plans->edge_valid.resize(E);
+                if (E)
+                {
+                    VMV_LOCKSTEP_HIP(hipMemcpy(ebits.data(), d_ebits, ebits.size() * 8, hipMemcpyDeviceToHost));
+                    VMV_LOCKSTEP_HIP(hipMemcpy(plans->edge_pairs.data(), D.pairs, 2 * E * 4, hipMemcpyDeviceToHost));
+                    for (size_t e = 0; e < E; ++e) plans->edge_valid[e] = bit(ebits, e);
+                }
+                plans->kept = true;
+            }
+            return VMV_OK;
+        }
+    }  // namespace
+}  // namespace vmv
+
+extern "C"
+{
+    int vmv_prm_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                      const uint64_t *halton_skips, const float *samples, const vmv_prm_settings *settings, vmv_plans **out)
+    {
+        // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
+        // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
+        const int dim = vmv_robot_dimension(robot);
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPrmMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_problems >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+        for (size_t k = 0; k < n_problems; ++k)
+            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+        const uint32_t ns = settings->n_samples;
+        if (ns % 64u != 0u || ns < vmv::kPrmMinSamples || ns > vmv::kPrmMaxSamples) return VMV_ERR_INVALID_ARGUMENT;
+        if (settings->k < 1u || settings->k > vmv::kPrmKMax) return VMV_ERR_INVALID_ARGUMENT;
+        if (!(settings->radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;  // NaN as well
+        if (!samples && halton_skips)
+            for (size_t k = 0; k < n_problems; ++k)
+                if (halton_skips[k] > 1000000ull || halton_skips[k] + ns > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_problems * (size_t) (ns + 2u) * (size_t) settings->k >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_problems == 0)  // an empty result is a PRM result too
+        {
+            vmv_plans *plans = new (std::nothrow) vmv_plans;
+            if (!plans) return VMV_ERR_HIP;
+            plans->dim = dim, plans->prm = true, plans->n_samples = ns, plans->kept = settings->keep_roadmaps != 0;
+            plans->edge_offsets.assign(1, 0u);
+            *out = plans;
+            return VMV_OK;
+        }
+        return vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
+            float lower[16], span[16], descale[16];
+            const int rc = vmv_robot_bounds(robot, lower, span, descale);
+            if (rc != VMV_OK) return rc;
+            return vmv::prm_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, samples, *settings,
+                                      plans);
+        });
+    }
+
+    int vmv_plans_roadmap_summary(const vmv_plans *plans, uint32_t *valid_vertices, uint32_t *candidate_edges, uint32_t *valid_edges,
+                                  float *costs)
+    {
+        if (!plans || !plans->prm) return VMV_ERR_INVALID_ARGUMENT;
+        for (size_t p = 0; p < plans->n; ++p)
+        {
+            if (valid_vertices) valid_vertices[p] = plans->sizes2[2 * p];
+            if (candidate_edges) candidate_edges[p] = plans->candidate_edges[p];
+            if (valid_edges) valid_edges[p] = plans->sizes2[2 * p + 1];
+            if (costs) costs[p] = plans->costs[p];
+        }
+        return VMV_OK;
+    }
+
+    int vmv_plans_roadmap_vertices(const vmv_plans *plans, size_t p, uint8_t *valid)
+    {
+        if (!plans || !plans->prm || !plans->kept || p >= plans->n || !valid) return VMV_ERR_INVALID_ARGUMENT;
+        const size_t V = (size_t) plans->n_samples + 2;
+        std::memcpy(valid, plans->vertex_valid.data() + p * V, V);
+        return VMV_OK;
+    }
+
+    int vmv_plans_roadmap_edges(const vmv_plans *plans, size_t p, uint32_t *pairs2, uint8_t *valid, size_t capacity, size_t *n)
+    {
+        if (!plans || !plans->prm || !plans->kept || p >= plans->n) return VMV_ERR_INVALID_ARGUMENT;
+        const size_t lo = plans->edge_offsets[p], count = plans->edge_offsets[p + 1] - lo;
+        if (n) *n = count;
+        if ((pairs2 || valid) && capacity < count) return VMV_ERR_CAPACITY;
+        if (pairs2 && count) std::memcpy(pairs2, plans->edge_pairs.data() + 2 * lo, 2 * count * 4);
+        if (valid && count) std::memcpy(valid, plans->edge_valid.data() + lo, count);
+        return VMV_OK;
+    }
+}

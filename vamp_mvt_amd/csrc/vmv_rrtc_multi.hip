@@ -13,19 +13,10 @@
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
+#include "vmv_plans.h"
 
 #include <cmath>
 #include <cstring>
-
-struct vmv_plans
-{
-    size_t n = 0;
-    int dim = 0;
-    std::vector<uint8_t> status;
-    std::vector<uint32_t> iterations, sizes2, path_lengths;
-    std::vector<float> paths;  // packed in problem order
-    uint64_t rounds = 0, questions = 0;
-};
 
 namespace vmv
 {

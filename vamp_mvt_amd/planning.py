@@ -98,7 +98,18 @@ class RRTCMultiSettings:
     check_every: int = 0
 
 
-PLAN_STATUS = ("solved", "max_iterations", "max_samples")  # VMV_PLAN_*
+@dataclass
+class PRMMultiSettings:
+    """settings of `prm_multi`: n_samples samples per problem (a multiple of 64 from 64 to 8,128), the k nearest
+    neighbours per vertex (1 .. 16) within `radius` (inf = no cut), keep_roadmaps = also return every problem's vertex
+    flags and candidate edges"""
+    n_samples: int = 2048
+    k: int = 8
+    radius: float = float("inf")
+    keep_roadmaps: bool = False
+
+
+PLAN_STATUS = ("solved", "max_iterations", "max_samples", "no_path", "invalid_endpoint")  # VMV_PLAN_*
 SIMPLIFY_STATUS = ("ok", "capacity")  # VMV_SIMPLIFY_*
 
 
@@ -130,7 +141,8 @@ class PlanningResult:
     cost: float = float("inf")
     edges_checked: int = 0
     samples_drawn: int = 0
-    status: str = ""  # rrtc_multi: one of PLAN_STATUS; simplify_multi: one of SIMPLIFY_STATUS
+    status: str = ""  # rrtc_multi, prm_multi: one of PLAN_STATUS; simplify_multi: one of SIMPLIFY_STATUS
+    roadmap: object = None  # prm_multi with keep_roadmaps: (vertex flags, candidate pairs [m][2], their flags)
 
     @property
     def solved(self):
@@ -254,6 +266,36 @@ def rrtc_multi(robot, starts, goals, environments, settings: RRTCMultiSettings |
                                   status=PLAN_STATUS[int(raw["status"][p])]))
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
+    return out
+
+
+def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | None = None, skips=None, samples=None):
+    """A roadmap per problem for many independent problems in one call on the device: problem p from starts[p] to
+    goals[p] ([n][dim] arrays) in environments[p] (None = the empty environment), over the Halton samples skips[p] + 1,
+    ... (None = 0 for all) or over `samples` ([n][n_samples][dim]; [n_samples][dim] serves every problem).
+    -> list[PlanningResult], one per problem: `path` (waypoints, empty if unsolved), `cost` (inf if unsolved),
+    `iterations` (n_samples where the roadmap was searched, 0 for a direct solution or an invalid endpoint), `size` =
+    [valid vertices, valid edges], `edges_checked` = candidate edges, `status` (one of PLAN_STATUS: "solved", "no_path",
+    "invalid_endpoint") and, with keep_roadmaps, `roadmap`.
+
+    The launches are a fixed sequence whatever the problems are: all vertices of all problems in ONE
+    validate_batch_multi call, the k nearest valid neighbours of every valid vertex, all candidate edges in ONE
+    validate_motion_batch_multi call, the shortest path per problem.  The result is defined bit for bit —
+    fp32 with one rounding per operation, neighbours in the order (squared distance, vertex id), the shortest-path
+    cost as the least fixpoint of g[v] = min fl(g[u] + w), the parent with the lowest id — and depends on the problem's
+    own inputs alone.  Agreement with the reference's incremental PRM is not claimed."""
+    s = settings or PRMMultiSettings()
+    raw = robot.prm_multi_raw(starts, goals, environments, s, skips, samples)
+    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+    out = []
+    for p in range(len(ends)):
+        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
+        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
+                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
+                                  edges_checked=int(raw["candidate_edges"][p]), status=PLAN_STATUS[int(raw["status"][p])],
+                                  roadmap=raw["roadmaps"][p] if "roadmaps" in raw else None))
+    if out:  # the call's validation calls ride on the first result
+        out[0].validity_calls = raw["rounds"]
     return out
 
 
