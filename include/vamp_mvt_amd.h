@@ -443,6 +443,60 @@ int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterati
 int vmv_paths_points(const vmv_paths *paths, float *out, size_t capacity_floats);
 int vmv_paths_destroy(vmv_paths *paths);
 
+/* ---- lockstep AORRTC: cost-bounded RRT-Connect searches for many independent problems --------------------- */
+/* AORRTC (planning/aorrtc.hh, one goal, PHS sampling, no dynamic domain) for n_problems problems at once; the arguments
+ * are those of vmv_rrtc_multi.  Per problem:
+ *   1. a first solution by vmv_rrtc_multi's contract with max_iterations and max_samples of these settings (rrtc's own two
+ *      maxima are overwritten, aorrtc.hh:384-386), on the Halton samples halton_skips[p] + 1, ...; unsolved: the problem
+ *      ends with that status and no path;
+ *   2. with simplify_intermediate, the path simplified by vmv_simplify_multi's contract under `simplify` (a path of more
+ *      than simplify.max_waypoints waypoints stays as it is);
+ *   3. first_cost = cost = Path::cost (the fp32 sum of the segment lengths in order); without `optimize`, or with a path
+ *      of 2 waypoints, the problem ends here;
+ *   4. while iterations < max_iterations, cost - distance(start, goal) > 1e-8f and (max_searches == 0 or searches <
+ *      max_searches): one cost-bounded search below `cost` with a budget of min(max_iterations - iterations,
+ *      max_internal_iterations) iterations on fresh trees; ++searches, iterations += the search's; a solution is
+ *      simplified as in 2. and, if its cost < cost, becomes the path (++improvements);
+ *   5. VMV_PLAN_SOLVED with the best path; iterations of all stages; sizes2 = the trees of the last search run.
+ * A search (DESIGN 5f gives every operation; fp32, one rounding per written operation, + - * / sqrtf and integer
+ * operations only): samples drawn directly from the prolate hyperspheroid of the bound with foci start and goal - a
+ * counter-based 32-bit hash seeded with (uint32) halton_skips[p] for the uniforms, a polynomial ln, Marsaglia's polar
+ * method, a Householder reflection - and rejected outside the joint bounds; the nearest node by the asymmetric
+ * cost-space key of aorrtc.hh:61-85 as an associative argmin (the first of the least key among the admissible nodes);
+ * with cost_bound_resample up to max_cost_bound_resamples attempts to re-parent the new node under a resampled cost
+ * bound (aorrtc.hh:197-237); the connect march of vmv_rrtc_multi towards the other tree's nearest node where that can
+ * beat the bound.  A problem's result depends on its own inputs and the settings other than check_every alone, bit for
+ * bit.  Search g of every still-optimising problem is one lockstep call (one 256-thread workgroup per unfinished problem
+ * and one edge question per problem per round, as vmv_rrtc_multi); the first solutions and the simplifications of a
+ * generation are one vmv_rrtc_multi / vmv_simplify_multi call each over the problems concerned; the host compares costs.
+ * Each problem owns a pool of max_samples nodes on the device (max_samples * (dimension + 2) * 4 bytes).
+ * Checks before anything is launched, device-free ones first: those of vmv_rrtc_multi (n_problems >= 2^25 is refused
+ * here), max_internal_iterations == 0, max_cost_bound_resamples > 64, the simplifier's settings as vmv_simplify_multi
+ * checks them (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment (VMV_ERR_NOT_FINALIZED); an environment of another
+ * device (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out untouched.  n_problems == 0 is VMV_OK with an empty
+ * result.  A start or goal with a non-finite joint: that problem ends unsolved.  Synchronous, host buffers, on the
+ * default stream; repeated handles are allowed.  The result is a vmv_plans: vmv_plans_summary (rounds and questions
+ * count every stage), vmv_plans_paths, vmv_plans_destroy, and vmv_plans_costs below. */
+typedef struct
+{
+    vmv_rrtc_settings rrtc;          /* range, balance, tree_ratio, check_every; its two maxima are overwritten */
+    vmv_simplify_settings simplify;
+    int optimize;                    /* 0: first solution (+ simplification) only */
+    int cost_bound_resample;         /* 0 / 1 */
+    int simplify_intermediate;       /* 0 / 1 */
+    uint32_t max_iterations;         /* of all stages together */
+    uint32_t max_internal_iterations; /* of one cost-bounded search; > 0 */
+    uint32_t max_samples;            /* nodes of a problem's two trees together, in every stage */
+    uint32_t max_cost_bound_resamples; /* <= 64 */
+    uint32_t max_searches;           /* cost-bounded searches per problem; 0 = no limit but max_iterations */
+} vmv_aorrtc_settings;
+int vmv_aorrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                     const uint64_t *halton_skips, const vmv_aorrtc_settings *settings, vmv_plans **out);
+/* Per problem of a vmv_aorrtc_multi result (arrays of n_problems, any may be NULL): the cost after the first stage, the
+ * cost of the returned path (+inf = unsolved), the cost-bounded searches run, those that gave a cheaper path.
+ * VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
+int vmv_plans_costs(const vmv_plans *plans, float *first_costs, float *costs, uint32_t *searches, uint32_t *improvements);
+
 /* ---- measurement support (bench.py) ---------------------------------------------------------------------- */
 /* Runs vmv_validate_batch `iters` times on `stream` between two HIP events recorded on that same stream and
  * returns the average kernel time in milliseconds. */
@@ -452,6 +506,11 @@ int vmv_time_validate_batch(int robot, const vmv_env *env, const float *d_q, siz
 int vmv_fill_uniform_configs(int robot, float *d_q, size_t n, uint64_t seed, void *stream);
 /* name of the dominant kernel symbol for a robot (to match rocprofv3 --kernel-trace rows) */
 const char *vmv_kernel_name(int robot, const char *entry_point);
+/* test support: n successive PHS samples of vmv_aorrtc_multi's sampler for the foci start and goal and the bound
+ * max_cost, drawn in a kernel from the uniform stream (seed, counter): out_q [n][dimension], out_in_bounds [n] (1 = inside
+ * the joint bounds), *out_counter = the counter after the last draw.  Host buffers, synchronous. */
+int vmv_phs_samples(int robot, const float *start, const float *goal, float max_cost, uint32_t seed, uint32_t counter, size_t n,
+                    float *out_q, uint8_t *out_in_bounds, uint32_t *out_counter);
 
 #ifdef __cplusplus
 }

@@ -528,6 +528,34 @@ def _torch_unpack_bits(bits, n):
     return (((bits[:, None] >> shifts[None, :]) & 1) != 0).reshape(-1)[:n]
 
 
+def _simplify_settings_struct(settings, longest=0):
+    """vmv_simplify_settings from a SimplifyMultiSettings-shaped object, checked as simplify_multi_raw documents;
+    longest: the longest input path in waypoints"""
+    ops = []
+    for op in settings.operations:
+        name = str(getattr(op, "name", op)).upper()
+        if name in ("REDUCE", "PERTURB"):
+            raise NotImplementedError(f"{name} draws random numbers: simplify_multi runs SHORTCUT and BSPLINE only")
+        if name not in _SIMPLIFY_OPS:
+            raise ValueError(f"unknown simplification routine {op!r}")
+        ops.append(_SIMPLIFY_OPS[name])
+    if len(ops) > 8:
+        raise ValueError("at most 8 operations per iteration")
+    if int(getattr(settings, "interpolate", 0)) != 0:
+        raise NotImplementedError("interpolate is not part of simplify_multi: interpolate the returned paths")
+    max_it, max_steps = int(settings.max_iterations), int(settings.max_steps)
+    max_wp, w = int(getattr(settings, "max_waypoints", 0)), int(getattr(settings, "questions_per_round", 0))
+    every = int(getattr(settings, "check_every", 0))
+    if not (0 <= max_it < 2 ** 32 and 0 <= max_steps < 2 ** 32 and 0 <= every < 2 ** 32 and 0 <= max_wp <= 2 ** 24):
+        raise ValueError("max_iterations, max_steps and check_every must fit 32 bits, max_waypoints 24")
+    if w not in (0, 2, 4, 8, 16, 32, 64):
+        raise ValueError("questions_per_round must be one of 2, 4, 8, 16, 32, 64 (0 = default)")
+    if longest > (max_wp or 2048):
+        raise ValueError(f"max_waypoints is below the longest path ({longest} waypoints)")
+    return _lib.SimplifySettings(max_it, 0, len(ops), (ctypes.c_uint32 * 8)(*ops), max_steps, float(settings.min_change),
+                               float(settings.midpoint_interpolation), max_wp, w, every)
+
+
 class _Robot(types.ModuleType):
     def __init__(self, name: str):
         super().__init__(f"{__name__}.{name}")
@@ -728,6 +756,81 @@ class _Robot(types.ModuleType):
         return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
                     rounds=int(rounds.value), questions=int(questions.value))
 
+    def aorrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
+        """vmv_aorrtc_multi: AORRTC for many problems (a first solution by rrtc_multi's contract, simplified by
+        simplify_multi's, then cost-bounded RRT-Connect searches in lockstep), the arguments those of rrtc_multi_raw.
+        settings: range, balance, tree_ratio, check_every, optimize, cost_bound_resample, simplify_intermediate,
+        max_iterations, max_internal_iterations, max_samples, max_cost_bound_resamples, max_searches and `simplify` (as
+        simplify_multi_raw takes it).  -> rrtc_multi_raw's dict plus first_costs, costs, searches, improvements per
+        problem.  planning.aorrtc_multi is the caller-facing form.  Every argument is checked before any library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = a.shape[0]
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        if skips is None:
+            sk = None
+        else:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        rng, ratio = float(settings.range), float(settings.tree_ratio)
+        max_it, max_in, max_s = int(settings.max_iterations), int(settings.max_internal_iterations), int(settings.max_samples)
+        resamples, searches = int(settings.max_cost_bound_resamples), int(settings.max_searches)
+        every = int(getattr(settings, "check_every", 0))
+        if not (math.isfinite(rng) and rng > 0):
+            raise ValueError("range must be finite and positive")
+        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32 and 0 <= searches < 2 ** 32):
+            raise ValueError("max_iterations, max_samples (>= 2), max_searches and check_every must fit 32 bits")
+        if not 1 <= max_in < 2 ** 32:
+            raise ValueError("max_internal_iterations must be positive and fit 32 bits")
+        if not 0 <= resamples <= 64:
+            raise ValueError("max_cost_bound_resamples must be from 0 to 64")
+        cs = _lib.AorrtcSettings(_lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every),
+                                 _simplify_settings_struct(settings.simplify), int(bool(settings.optimize)),
+                                 int(bool(settings.cost_bound_resample)), int(bool(settings.simplify_intermediate)), max_it,
+                                 max_in, max_s, resamples, searches)
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        plans = ctypes.c_void_p()
+        check(lib.vmv_aorrtc_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
+                                   ctypes.byref(cs), ctypes.byref(plans)), "vmv_aorrtc_multi")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
+                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
+                  "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+            first, costs = np.zeros(n, np.float32), np.zeros(n, np.float32)
+            n_searches, improvements = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            check(lib.vmv_plans_costs(plans, _fp(first), _fp(costs), n_searches.ctypes.data_as(_lib.c_u32_p),
+                                      improvements.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_costs")
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, first_costs=first,
+                    costs=costs, searches=n_searches, improvements=improvements, rounds=int(rounds.value),
+                    questions=int(questions.value))
+
+    def phs_samples(self, start, goal, max_cost, seed, counter, n):
+        """vmv_phs_samples (test support): n successive samples of aorrtc_multi's device sampler for the foci start and
+        goal under the bound max_cost, from the uniform stream (seed, counter) -> (q [n][dim], in_bounds bool[n], the
+        counter after the last draw)"""
+        a, b = _f32(start, (self._dim,)), _f32(goal, (self._dim,))
+        q, ok, c = np.zeros((int(n), self._dim), np.float32), np.zeros(int(n), np.uint8), ctypes.c_uint32(0)
+        check(lib.vmv_phs_samples(self._id, _fp(a), _fp(b), float(max_cost), int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF,
+                                  int(n), _fp(q), ok.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(c)),
+              "vmv_phs_samples")
+        return q, ok.astype(bool), int(c.value)
+
     def prm_multi_raw(self, starts, goals, environments, settings, skips=None, samples=None):
         """vmv_prm_multi: one roadmap per problem, problem p from starts[p] to goals[p] in environments[p] (None = the
         empty environment) over the Halton samples skips[p] + 1, ... (None = all 0) or over `samples`
@@ -828,30 +931,7 @@ class _Robot(types.ModuleType):
         n = len(pts)
         if len(environments) != n:
             raise ValueError(f"expected one environment per path, got {len(environments)} for {n} paths")
-        ops = []
-        for op in settings.operations:
-            name = str(getattr(op, "name", op)).upper()
-            if name in ("REDUCE", "PERTURB"):
-                raise NotImplementedError(f"{name} draws random numbers: simplify_multi runs SHORTCUT and BSPLINE only")
-            if name not in _SIMPLIFY_OPS:
-                raise ValueError(f"unknown simplification routine {op!r}")
-            ops.append(_SIMPLIFY_OPS[name])
-        if len(ops) > 8:
-            raise ValueError("at most 8 operations per iteration")
-        if int(getattr(settings, "interpolate", 0)) != 0:
-            raise NotImplementedError("interpolate is not part of simplify_multi: interpolate the returned paths")
-        max_it, max_steps = int(settings.max_iterations), int(settings.max_steps)
-        max_wp, w = int(getattr(settings, "max_waypoints", 0)), int(getattr(settings, "questions_per_round", 0))
-        every = int(getattr(settings, "check_every", 0))
-        if not (0 <= max_it < 2 ** 32 and 0 <= max_steps < 2 ** 32 and 0 <= every < 2 ** 32 and 0 <= max_wp <= 2 ** 24):
-            raise ValueError("max_iterations, max_steps and check_every must fit 32 bits, max_waypoints 24")
-        if w not in (0, 2, 4, 8, 16, 32, 64):
-            raise ValueError("questions_per_round must be one of 2, 4, 8, 16, 32, 64 (0 = default)")
-        longest = max((len(a) for a in pts), default=0)
-        if longest > (max_wp or 2048):
-            raise ValueError(f"max_waypoints is below the longest path ({longest} waypoints)")
-        cs = _lib.SimplifySettings(max_it, 0, len(ops), (ctypes.c_uint32 * 8)(*ops), max_steps, float(settings.min_change),
-                                   float(settings.midpoint_interpolation), max_wp, w, every)
+        cs = _simplify_settings_struct(settings, max((len(a) for a in pts), default=0))
         offsets = np.zeros(n + 1, np.uintp)
         offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
         packed = np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, self._dim), np.float32)]))

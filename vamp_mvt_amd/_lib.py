@@ -44,6 +44,14 @@ class SimplifySettings(ctypes.Structure):
                 ("max_waypoints", ctypes.c_uint32), ("questions_per_round", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
 
 
+class AorrtcSettings(ctypes.Structure):
+    """vmv_aorrtc_settings"""
+    _fields_ = [("rrtc", RrtcSettings), ("simplify", SimplifySettings), ("optimize", ctypes.c_int),
+                ("cost_bound_resample", ctypes.c_int), ("simplify_intermediate", ctypes.c_int),
+                ("max_iterations", ctypes.c_uint32), ("max_internal_iterations", ctypes.c_uint32),
+                ("max_samples", ctypes.c_uint32), ("max_cost_bound_resamples", ctypes.c_uint32), ("max_searches", ctypes.c_uint32)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -147,6 +155,11 @@ def _load():
         "vmv_plans_roadmap_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p, c_float_p]),
         "vmv_plans_roadmap_vertices": (I, [V, S, ctypes.POINTER(ctypes.c_uint8)]),
         "vmv_plans_roadmap_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
+        "vmv_aorrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
+                                 ctypes.POINTER(V)]),
+        "vmv_plans_costs": (I, [V, c_float_p, c_float_p, c_u32_p, c_u32_p]),
+        "vmv_phs_samples": (I, [I, c_float_p, c_float_p, F, ctypes.c_uint32, ctypes.c_uint32, S, c_float_p,
+                                ctypes.POINTER(ctypes.c_uint8), c_u32_p]),
         "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
                                    ctypes.POINTER(V)]),
         "vmv_paths_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),

@@ -152,9 +152,22 @@ class SimplifySettings:
     bspline: BSplineSettings = field(default_factory=BSplineSettings)
 
 
+@dataclass
 class AORRTCSettings:
-    def __init__(self):
-        raise NotImplementedError("aorrtc is not part of this build (SURVEY.md §2: out of scope)")
+    """planning/aorrtc_settings.hh (settings.cc); `<robot>.aorrtc` and `<robot>.aorrtc_multi` run planning.aorrtc_multi:
+    max_samples is the node pool every problem owns on the device, max_cost_bound_resamples above 64 is clamped to 64,
+    and anytime=True, use_phs=False and rrtc.dynamic_domain=True raise at the call"""
+    rrtc: RRTCSettings = field(default_factory=lambda: RRTCSettings(dynamic_domain=False))
+    simplify: SimplifySettings = field(default_factory=SimplifySettings)
+    optimize: bool = True
+    cost_bound_resample: bool = True
+    simplify_intermediate: bool = True
+    use_phs: bool = True
+    anytime: bool = False
+    max_iterations: int = 100000
+    max_internal_iterations: int = 100000
+    max_samples: int = 100000
+    max_cost_bound_resamples: int = 1000
 
 
 # --------------------------------------------------------------------------------------------- per-robot objects
@@ -304,6 +317,45 @@ def install(robot):
             out.append(res)
         return out
 
+    def aorrtc_multi(starts, goals, environments, settings, skips=None):
+        """planning.aorrtc_multi with this robot and the reference-shaped AORRTCSettings -> list[PlanningResult] (each
+        with `status`, `first_cost`, `searches`, `improvements`; nanoseconds is the whole call's time divided by the
+        problems).  A planning.AORRTCMultiSettings is taken as it is."""
+        t0 = time.perf_counter_ns()
+        if isinstance(settings, planning.AORRTCMultiSettings):
+            s = settings
+        else:
+            if bool(getattr(settings, "anytime", False)):
+                raise NotImplementedError("anytime=True (Anytime RRT-Connect) is not part of aorrtc_multi")
+            if not bool(getattr(settings, "use_phs", True)):
+                raise NotImplementedError("use_phs=False is not part of aorrtc_multi: rejection from the Halton box finds nothing")
+            if bool(getattr(settings.rrtc, "dynamic_domain", False)):
+                raise NotImplementedError("rrtc.dynamic_domain=True is not part of aorrtc_multi")
+            s = planning.AORRTCMultiSettings(
+                range=float(settings.rrtc.range), balance=bool(settings.rrtc.balance), tree_ratio=float(settings.rrtc.tree_ratio),
+                optimize=bool(settings.optimize), cost_bound_resample=bool(settings.cost_bound_resample),
+                simplify_intermediate=bool(settings.simplify_intermediate), max_iterations=int(settings.max_iterations),
+                max_internal_iterations=int(settings.max_internal_iterations), max_samples=int(settings.max_samples),
+                max_cost_bound_resamples=min(int(settings.max_cost_bound_resamples), 64),
+                max_searches=int(getattr(settings, "max_searches", 0)), simplify=settings.simplify,
+                check_every=int(getattr(settings, "check_every", 0)))
+        results = planning.aorrtc_multi(robot, starts, goals, environments, s, skips)
+        each = (time.perf_counter_ns() - t0) // max(len(results), 1)
+        out = []
+        for r in results:
+            path = Path()
+            for q in r.path:
+                path.append(q)
+            res = PlanningResult(path, each, r.iterations, r.size, r.cost)
+            res.status, res.first_cost, res.searches, res.improvements = r.status, r.first_cost, r.searches, r.improvements
+            out.append(res)
+        return out
+
+    def aorrtc(start, goal, environment, settings, rng=None):
+        """one problem of aorrtc_multi (one goal; `rng` is not used: the first stage samples the Halton sequence from its
+        start, the searches their own stream)"""
+        return aorrtc_multi(_cfg(robot, start)[None], _cfg(robot, goal)[None], [environment], settings)[0]
+
     def fcit(start, goal, environment, settings, rng):
         t0 = time.perf_counter_ns()
         s = planning.FCITSettings(batch_size=int(settings.batch_size), max_samples=int(settings.max_samples),
@@ -418,6 +470,7 @@ def install(robot):
 
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
+    robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 
@@ -431,6 +484,8 @@ def _planner_settings(robot_module, robot_name, planner_name):
         "rrtc": lambda: RRTCSettings(range=ROBOT_RRT_RANGES.get(robot_name, RRTCSettings.range)),
         "prm": lambda: PRMSettings(PRMNeighborParams(robot_module.dimension(), robot_module.space_measure())),
         "fcit": lambda: FCITSettings(FCITNeighborParams(robot_module.dimension(), robot_module.space_measure())),
+        "aorrtc": lambda: AORRTCSettings(rrtc=RRTCSettings(range=ROBOT_RRT_RANGES.get(robot_name, RRTCSettings.range),
+                                                           dynamic_domain=False)),
     }
     if planner_name not in makers:
         raise NotImplementedError(f"no automatic settings for planner '{planner_name}' in this build")

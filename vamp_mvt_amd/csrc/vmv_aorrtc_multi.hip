@@ -1,0 +1,997 @@
+// vmv_aorrtc_multi.hip — cost-bounded RRT-Connect rounds for many independent problems (vmv_aorrtc_multi).
+//
+// AORRTC (planning/aorrtc.hh) per problem: a first solution (vmv_rrtc_multi's contract), simplified (vmv_simplify_multi's
+// contract), then searches under the cost bound of the best path so far, each on fresh trees inside the informed set of
+// that bound, each new solution simplified and kept if it is cheaper.  The first solution and every simplification are
+// calls of vmv_rrtc_multi / vmv_simplify_multi over the sub-batch concerned; search g of every still-optimising problem
+// runs as ONE lockstep call of aox_step_kernel below (rounds of vmv_lockstep.h, one question per problem); the host
+// compares costs between generations.
+//
+// The contract of one search, per problem (fp32, one rounding per written operation, -ffp-contract=off; sqrtf and / are
+// correctly rounded on gfx950; sums over joints sequential in joint order):
+//   uniform stream   seed = (uint32) halton_skip, a 32-bit counter c (0 at the first search, runs on through all searches
+//                    of the problem), pre-incremented per draw: x = c * 0x9E3779B9 + seed; x ^= x >> 16;
+//                    x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16; U = float(x >> 8) * 2^-24.
+//   ln32(s), 0<s<1   e = unbiased exponent, m = mantissa in [1, 2); mantissa bits > 0x3504f3 (fl(sqrt 2)): m = m / 2, e = e + 1;
+//                    t = (m - 1) / (m + 1), t2 = t * t, p = 1/11, p = p * t2 + 1/k for k = 9 7 5 3 1,
+//                    ln32 = float(e) * HI + (float(e) * LO + (2 * t) * p), HI = 0x3f317180, LO = 0x3717f7d1 (ln 2 split).
+//   Gaussian pair    repeat u1 = 2U - 1, u2 = 2U - 1, s = u1 u1 + u2 u2 until 0 < s < 1; m = sqrtf((-2 ln32(s)) / s);
+//                    (u1 m, u2 m).
+//   PHS frame        dmin = distance(start, goal), centre = (start + goal) * 0.5, a1 = (goal - start) / dmin, v = a1 with
+//                    v[0] += (a1[0] >= 0 ? 1 : -1), vv = sum v[j] v[j]  (the Householder reflection e1 -> -+a1).
+//   PHS sample       g[0 .. n+1] from ceil((n + 2) / 2) pairs (a surplus value dropped), norm = sqrtf(sum g[i] g[i]),
+//                    r1 = max_cost * 0.5, rc = sqrtf(max(max_cost max_cost - dmin dmin, 0)) * 0.5,
+//                    y[j] = (g[j] / norm) * (j == 0 ? r1 : rc), k = (2 * sum v[j] y[j]) / vv, t = centre + (y - v * k);
+//                    out of bounds unless lower[j] <= t[j] <= fl(lower[j] + span[j]) for every joint (NaN: out).
+//   aox_nearest(T, t, c)  over the counted nodes i of T: d_i = sqrtf(sum (node_i[j] - t[j])^2), admissible iff
+//                    !(cost_i > 0) || !(c < cost_i + d_i), key_i = sqrtf(d_i d_i + (cost_i - c)(cost_i - c)); the FIRST
+//                    index with the least key among the admissible nodes, and its d_i.  An associative argmin: the
+//                    workgroup's lanes stride over the tree.
+//   one search       fresh trees (roots cost 0, A = the start tree); while iterations < budget && |A| + |B| < max_samples:
+//                    ++iterations, the balance swap of vmv_rrtc_multi; t = PHS sample, out of bounds: continue;
+//                    g = dist(t, rootA), f = g + dist(t, rootB), c_rand = U * max(max_cost - f, 0) + g;
+//                    (ni, d) = aox_nearest(A, t, c_rand), !(d > 0): continue; new = near + (t - near) * (min(d, R) / d);
+//                    ask near -> new, invalid: continue; new_cost = cost[ni] + dist(new, near);
+//                    cost_bound_resample: g2 = dist(new, rootA), up to max_cost_bound_resamples times:
+//                    cr = max(new_cost - g2, 0), draw U, (mi, md) = aox_nearest(A, new, U * cr + g2) with `new` not yet
+//                    counted; stop if mi == ni or !(cost[mi] + md < new_cost) or cr == 0; ask A[mi] -> new: valid:
+//                    ni = mi, new_cost = cost[mi] + md; invalid: stop;
+//                    add new (parent ni, cost new_cost); (bi, bd) = aox_nearest(B, new, max_cost - new_cost);
+//                    !((new_cost + bd) + cost[bi] < max_cost): continue; the connect march of vmv_rrtc_multi from B[bi]
+//                    towards new, every added node with cost[prev] + dist(w, from); connected: solved, the path traced as
+//                    vmv_rrtc_multi traces it.  Unsolved: MAX_ITERATIONS if the budget was reached, else MAX_SAMPLES.
+//
+// aox_step_kernel: one 256-thread workgroup per unfinished problem; the phases are extend, re-parent (A[mi] -> new is in
+// flight while `new` sits uncounted in A's next slot) and march.  One lane draws the sample and shares it through LDS;
+// every branch is taken by the whole workgroup.  Iterations that ask nothing loop inside the kernel, at most kAoxSpinCap
+// per launch (then a null question; the state carries on, so the cap changes no result).  A problem's two trees share one
+// pool of max_samples nodes, the start tree from the front, the goal tree from the back, with parent and cost arrays.
+// Every store is a plain vector store by the owning workgroup; no atomics.
+#include "../../include/vamp_mvt_amd.h"
+
+#include "vmv_lockstep.h"
+#include "vmv_plans.h"
+
+#include <cmath>
+#include <cstring>
+#include <limits>
+
+namespace vmv
+{
+    namespace
+    {
+        constexpr uint32_t kAoxBlock = 256;
+        constexpr uint32_t kAoxWaves = kAoxBlock / kWave;
+        constexpr uint32_t kAoxMaxDim = 16;
+        constexpr uint32_t kAoxDefaultCheckEvery = 16;
+        constexpr uint32_t kAoxSpinCap = 64;        // iterations without a question per launch
+        constexpr uint32_t kAoxMaxResamples = 64;   // max_cost_bound_resamples the call accepts
+        constexpr uint32_t kAoxNone = 0xffffffffu;
+
+        enum : uint32_t
+        {
+            kAoxFresh = 0,     // nothing asked yet
+            kAoxIdle = 1,      // a null question is in flight (the spin cap): the loop goes on
+            kAoxExtend = 2,    // near -> new is in flight (new sits in A's next slot, not yet counted)
+            kAoxReparent = 3,  // A[mi] -> new is in flight (new still uncounted)
+            kAoxMarch = 4,     // step k of the connect march is in flight (w sits in B's next slot, not yet counted)
+            kAoxDone = 5
+        };
+
+        struct AoxState  // 96 bytes per problem
+        {
+            uint32_t phase, status, iterations, counter;  // counter: the uniform stream's, kept across searches
+            uint32_t n[2];           // nodes of the start tree (side 0) and the goal tree (side 1)
+            uint32_t a_side, slot;   // which side is A; position of the question in flight in its round's arrays
+            uint32_t new_i, ni, mi;  // `new` in A once counted; its parent so far; the parent being asked
+            uint32_t resamples;      // cost-bound resamples made for `new`
+            uint32_t bi, prev, k, n_steps;
+            float bd, new_cost, cand_cost, g2;  // cand_cost: new_cost if A[mi] -> new is valid
+            float max_cost;
+            uint32_t budget, path_len, questions;
+        };
+        static_assert(sizeof(AoxState) == 96, "24 words per problem");
+
+        struct AoxParams
+        {
+            uint32_t dim, max_samples, balance, resample, max_resamples;
+            float range, tree_ratio;
+            float lower[kAoxMaxDim], span[kAoxMaxDim];
+        };
+
+        struct AoxArrays
+        {
+            AoxState *state;              // [n_problems]
+            float *pool;                  // [n_problems][max_samples][dim]
+            uint32_t *parent;             // [n_problems][max_samples], indices within the node's own tree
+            float *cost;                  // [n_problems][max_samples]
+            const float *starts, *goals;  // [n_problems][dim]
+            const uint64_t *skips;        // [n_problems]
+            const float *max_cost;        // [n_problems] the bound of the search to come
+            const uint32_t *budget;       // [n_problems] its iterations
+            const uint32_t *active;       // [n_active] problem of each workgroup
+            float *q_start, *q_goal;      // [n_active][dim] the round's questions
+            const uint64_t *bits;         // answers of the previous round
+            uint8_t *done;                // [n_problems]
+        };
+
+        struct PhsFrame
+        {
+            float centre[kAoxMaxDim], v[kAoxMaxDim];
+            float dmin, vv;
+        };
+
+        __device__ __forceinline__ size_t aox_at(uint32_t side, uint32_t i, uint32_t max_samples)
+        {
+            return side ? (size_t) (max_samples - 1u - i) : (size_t) i;
+        }
+        __device__ __forceinline__ uint32_t aox_count(const AoxState &st, uint32_t side) { return side ? st.n[1] : st.n[0]; }
+        __device__ __forceinline__ uint32_t aox_grow(AoxState &st, uint32_t side)  // -> index of the node now counted
+        {
+            const uint32_t i = aox_count(st, side);
+            if (side)
+                st.n[1] = i + 1u;
+            else
+                st.n[0] = i + 1u;
+            return i;
+        }
+
+        __device__ __forceinline__ float aox_dist(const float *a, const float *b, uint32_t dim)
+        {
+            float sum = 0.f;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                const float df = a[j] - b[j];
+                sum = sum + df * df;
+            }
+            return sqrtf(sum);
+        }
+
+        __device__ __forceinline__ float aox_uniform(uint32_t seed, uint32_t &c)
+        {
+            ++c;
+            uint32_t x = c * 0x9E3779B9u + seed;
+            x ^= x >> 16;
+            x *= 0x7feb352du;
+            x ^= x >> 15;
+            x *= 0x846ca68bu;
+            x ^= x >> 16;
+            return (float) (x >> 8) * 5.9604644775390625e-08f;  // 2^-24: exact
+        }
+
+        __device__ __forceinline__ float aox_ln32(float s)
+        {
+            const uint32_t bits = __float_as_uint(s);
+            int e = (int) (bits >> 23) - 127;
+            uint32_t mant = bits & 0x7fffffu;
+            if (mant > 0x3504f3u)  // above fl(sqrt(2)): m / 2 and the next exponent
+                e += 1, mant |= 0x3f000000u;
+            else
+                mant |= 0x3f800000u;
+            const float m = __uint_as_float(mant);
+            const float t = (m - 1.f) / (m + 1.f), t2 = t * t;
+            float p = 1.f / 11.f;
+            p = p * t2 + 1.f / 9.f;
+            p = p * t2 + 1.f / 7.f;
+            p = p * t2 + 1.f / 5.f;
+            p = p * t2 + 1.f / 3.f;
+            p = p * t2 + 1.f;
+            const float ln2_hi = __uint_as_float(0x3f317180u), ln2_lo = __uint_as_float(0x3717f7d1u);
+            return (float) e * ln2_hi + ((float) e * ln2_lo + (2.f * t) * p);
+        }
+
+        __device__ void aox_gaussian_pair(uint32_t seed, uint32_t &c, float &g0, float &g1)
+        {
+            float u1, u2, s;
+            do
+            {
+                u1 = 2.f * aox_uniform(seed, c) - 1.f;
+                u2 = 2.f * aox_uniform(seed, c) - 1.f;
+                s = u1 * u1 + u2 * u2;
+            } while (!(0.f < s && s < 1.f));
+            const float m = sqrtf((-2.f * aox_ln32(s)) / s);
+            g0 = u1 * m, g1 = u2 * m;
+        }
+
+        // one thread
+        __device__ void phs_frame(const float *start, const float *goal, uint32_t dim, PhsFrame &F)
+        {
+            float sum = 0.f;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                const float df = goal[j] - start[j];
+                sum = sum + df * df;
+            }
+            F.dmin = sqrtf(sum);
+            float vv = 0.f;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                F.centre[j] = (start[j] + goal[j]) * 0.5f;
+                float v = (goal[j] - start[j]) / F.dmin;
+                if (j == 0) v = v + (v >= 0.f ? 1.f : -1.f);
+                F.v[j] = v;
+                vv = vv + v * v;
+            }
+            F.vv = vv;
+        }
+
+        // one thread; g: dim + 2 floats of scratch, t: the sample -> in bounds
+        __device__ bool phs_sample(const PhsFrame &F, uint32_t dim, const float *lower, const float *span, float max_cost,
+                                   uint32_t seed, uint32_t &c, float *g, float *t)
+        {
+            const uint32_t ng = dim + 2u;
+            for (uint32_t i = 0; i < ng; i += 2)
+            {
+                float g0, g1;
+                aox_gaussian_pair(seed, c, g0, g1);
+                g[i] = g0;
+                if (i + 1u < ng) g[i + 1u] = g1;
+            }
+            float sum = 0.f;
+            for (uint32_t i = 0; i < ng; ++i) sum = sum + g[i] * g[i];
+            const float norm = sqrtf(sum);
+            const float r1 = max_cost * 0.5f;
+            const float rc = sqrtf(fmaxf(max_cost * max_cost - F.dmin * F.dmin, 0.f)) * 0.5f;
+            float dot = 0.f;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                g[j] = (g[j] / norm) * (j == 0 ? r1 : rc);  // y
+                dot = dot + F.v[j] * g[j];
+            }
+            const float k = (2.f * dot) / F.vv;
+            bool ok = true;
+            for (uint32_t j = 0; j < dim; ++j)
+            {
+                const float x = F.centre[j] + (g[j] - F.v[j] * k);
+                t[j] = x;
+                ok = ok && lower[j] <= x && x <= lower[j] + span[j];
+            }
+            return ok;
+        }
+
+        __device__ __forceinline__ bool aox_closer(float k, uint32_t i, float best_k, uint32_t best_i)
+        {
+            return k < best_k || (k == best_k && i < best_i);
+        }
+
+        // (first index with the least key among the admissible nodes, its distance to s_t) over nodes [0, count) of one
+        // tree; the same values in every thread.  Called by all threads of the workgroup (barriers, cross-lane reads with
+        // every lane enabled).  kAoxNone where no key compares below +inf.
+        __device__ void aox_nearest(const float *__restrict__ pool, const float *__restrict__ cost, const uint32_t side,
+                                    const uint32_t count, const AoxParams &P, const float *s_t, const float c, float *s_rk,
+                                    float *s_rd, uint32_t *s_ri, float &out_d, uint32_t &out_i)
+        {
+            float best_k = INFINITY, best_d = NAN;
+            uint32_t best_i = kAoxNone;
+            for (uint32_t i = threadIdx.x; i < count; i += kAoxBlock)  // increasing i per lane: `<` keeps the first
+            {
+                const size_t at = aox_at(side, i, P.max_samples);
+                const float *q = pool + at * P.dim;
+                float sum = 0.f;
+                for (uint32_t j = 0; j < P.dim; ++j)
+                {
+                    const float df = q[j] - s_t[j];
+                    sum = sum + df * df;
+                }
+                const float d = sqrtf(sum), ci = cost[at];
+                const bool admissible = !(ci > 0.f) || !(c < ci + d);
+                const float dc = ci - c;
+                const float key = sqrtf(d * d + dc * dc);
+                if (admissible && key < best_k) best_k = key, best_d = d, best_i = i;
+            }
+#pragma unroll
+            for (int off = kWave / 2; off > 0; off >>= 1)  // (all 64 lanes are enabled here: the loop above has ended)
+            {
+                const float ok = __shfl_xor(best_k, off), od = __shfl_xor(best_d, off);
+                const uint32_t oi = (uint32_t) __shfl_xor((int) best_i, off);
+                if (aox_closer(ok, oi, best_k, best_i)) best_k = ok, best_d = od, best_i = oi;
+            }
+            if ((threadIdx.x & (kWave - 1)) == 0)
+                s_rk[threadIdx.x / kWave] = best_k, s_rd[threadIdx.x / kWave] = best_d, s_ri[threadIdx.x / kWave] = best_i;
+            __syncthreads();
+            best_k = s_rk[0], best_d = s_rd[0], best_i = s_ri[0];
+#pragma unroll
+            for (uint32_t w = 1; w < kAoxWaves; ++w)
+                if (aox_closer(s_rk[w], s_ri[w], best_k, best_i)) best_k = s_rk[w], best_d = s_rd[w], best_i = s_ri[w];
+            __syncthreads();  // s_rk / s_rd / s_ri / s_t may be rewritten after this
+            out_d = best_d, out_i = best_i;
+        }
+
+        // waypoints of a solved search: root(A) .. new, then B_prev .. root(B) without its first node if that equals
+        // `new` bit for bit (as vmv_rrtc_multi traces); one thread.  out == nullptr: count only.
+        __device__ uint32_t aox_trace(const AoxState &st, const float *pool, const uint32_t *parent, const uint32_t dim,
+                                      const uint32_t M, float *out)
+        {
+            const uint32_t sa = st.a_side, sb = sa ^ 1u;
+            uint32_t la = 1, lb = 1;
+            for (uint32_t i = st.new_i; parent[aox_at(sa, i, M)] != i; i = parent[aox_at(sa, i, M)]) ++la;
+            for (uint32_t i = st.prev; parent[aox_at(sb, i, M)] != i; i = parent[aox_at(sb, i, M)]) ++lb;
+            const uint32_t *pn = reinterpret_cast<const uint32_t *>(pool + aox_at(sa, st.new_i, M) * dim);
+            const uint32_t *pp = reinterpret_cast<const uint32_t *>(pool + aox_at(sb, st.prev, M) * dim);
+            bool same = true;
+            for (uint32_t j = 0; j < dim; ++j) same = same && pn[j] == pp[j];
+            const uint32_t skip = same ? 1u : 0u, len = la + lb - skip;
+            if (!out) return len;
+            const bool reversed = sa != 0;  // A is the goal tree: the path was collected goal -> start
+            uint32_t pos = la;              // A's branch is written backwards from position la - 1
+            for (uint32_t i = st.new_i;; i = parent[aox_at(sa, i, M)])
+            {
+                --pos;
+                const float *q = pool + aox_at(sa, i, M) * dim;
+                float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
+                for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
+                if (parent[aox_at(sa, i, M)] == i) break;
+            }
+            pos = la;
+            uint32_t seen = 0;
+            for (uint32_t i = st.prev;; i = parent[aox_at(sb, i, M)], ++seen)
+            {
+                if (seen >= skip)
+                {
+                    const float *q = pool + aox_at(sb, i, M) * dim;
+                    float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
+                    for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
+                    ++pos;
+                }
+                if (parent[aox_at(sb, i, M)] == i) break;
+            }
+            return len;
+        }
+
+        // fresh trees, bound and budget for the search to come of every active problem; the uniform counter stays
+        __global__ __launch_bounds__(kAoxBlock) void aox_init_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active)
+        {
+            const uint32_t a = blockIdx.x * kAoxBlock + threadIdx.x;
+            if (a >= n_active) return;
+            const uint32_t p = D.active[a], M = P.max_samples;
+            float *pool = D.pool + (size_t) p * M * P.dim;
+            for (uint32_t j = 0; j < P.dim; ++j)
+            {
+                pool[aox_at(0, 0, M) * P.dim + j] = D.starts[(size_t) p * P.dim + j];
+                pool[aox_at(1, 0, M) * P.dim + j] = D.goals[(size_t) p * P.dim + j];
+            }
+            uint32_t *parent = D.parent + (size_t) p * M;
+            float *cost = D.cost + (size_t) p * M;
+            parent[aox_at(0, 0, M)] = 0, parent[aox_at(1, 0, M)] = 0;  // roots are their own parent
+            cost[aox_at(0, 0, M)] = 0.f, cost[aox_at(1, 0, M)] = 0.f;
+            AoxState st{};
+            st.phase = kAoxFresh, st.status = VMV_PLAN_MAX_ITERATIONS;
+            st.counter = D.state[p].counter;
+            st.n[0] = st.n[1] = 1;
+            st.new_i = kAoxNone;
+            st.max_cost = D.max_cost[p], st.budget = D.budget[p];
+            D.state[p] = st;
+            D.done[p] = 0;
+        }
+
+        // One workgroup per active problem; every branch below is taken by the whole workgroup (its conditions are
+        // values every thread holds alike), so the barriers and cross-lane reads inside aox_nearest() are safe.
+        __global__ __launch_bounds__(kAoxBlock) void aox_step_kernel(const AoxParams P, const AoxArrays D)
+        {
+            __shared__ float s_t[kAoxMaxDim];
+            __shared__ float s_g[kAoxMaxDim + 2];
+            __shared__ float s_rk[kAoxWaves], s_rd[kAoxWaves];
+            __shared__ uint32_t s_ri[kAoxWaves];
+            __shared__ PhsFrame s_frame;
+            __shared__ float s_c;           // the sampled cost bound of the next aox_nearest
+            __shared__ uint32_t s_ok, s_counter;
+            const uint32_t a = blockIdx.x, p = D.active[a], tid = threadIdx.x, dim = P.dim, M = P.max_samples;
+            AoxState st = D.state[p];
+            float *pool = D.pool + (size_t) p * M * dim;
+            uint32_t *parent = D.parent + (size_t) p * M;
+            float *cost = D.cost + (size_t) p * M;
+            float *qs = D.q_start + (size_t) a * dim, *qg = D.q_goal + (size_t) a * dim;
+            const float *start = D.starts + (size_t) p * dim, *goal = D.goals + (size_t) p * dim;
+            const float R = P.range;
+            const uint32_t seed = (uint32_t) D.skips[p];
+            if (tid == 0) s_counter = st.counter;  // lane 0 alone draws
+            __syncthreads();
+            const auto save = [&]() {
+                if (tid == 0)
+                {
+                    st.counter = s_counter;
+                    D.state[p] = st;
+                }
+            };
+
+            enum { kLoop, kResample, kCommit, kMarchStep, kFinish } act = kLoop;
+            if (st.phase == kAoxDone)
+                act = kFinish;
+            else if (st.phase != kAoxFresh && st.phase != kAoxIdle)
+            {
+                const bool ans = (D.bits[st.slot >> 6] >> (st.slot & 63u)) & 1ull;
+                const uint32_t sa = st.a_side, sb = sa ^ 1u;
+                if (st.phase == kAoxExtend)
+                {
+                    if (ans)
+                    {
+                        const float *nw = pool + aox_at(sa, aox_count(st, sa), M) * dim;
+                        st.new_cost = cost[aox_at(sa, st.ni, M)] + aox_dist(nw, pool + aox_at(sa, st.ni, M) * dim, dim);
+                        st.g2 = aox_dist(nw, pool + aox_at(sa, 0, M) * dim, dim);
+                        st.resamples = 0;
+                        act = kResample;
+                    }
+                }
+                else if (st.phase == kAoxReparent)
+                {
+                    if (ans)
+                        st.ni = st.mi, st.new_cost = st.cand_cost, act = kResample;
+                    else
+                        act = kCommit;
+                }
+                else  // kAoxMarch
+                {
+                    if (ans)
+                    {
+                        st.prev = aox_grow(st, sb);
+                        if (++st.k == st.n_steps)
+                            st.status = VMV_PLAN_SOLVED, act = kFinish;
+                        else
+                            act = kMarchStep;
+                    }
+                }
+            }
+
+            if (act == kResample)  // `new` sits uncounted in A's next slot with parent ni and cost new_cost so far
+            {
+                const uint32_t sa = st.a_side;
+                const size_t new_at = aox_at(sa, aox_count(st, sa), M);
+                if (tid < dim) s_t[tid] = pool[new_at * dim + tid];
+                __syncthreads();
+                act = kCommit;
+                if (P.resample && st.resamples < P.max_resamples)  // one attempt per launch: its question ends the launch
+                {
+                    ++st.resamples;
+                    const float cr = fmaxf(st.new_cost - st.g2, 0.f);
+                    if (tid == 0) s_c = aox_uniform(seed, s_counter) * cr + st.g2;
+                    __syncthreads();
+                    const float c = s_c;
+                    float md;
+                    uint32_t mi;
+                    aox_nearest(pool, cost, sa, aox_count(st, sa), P, s_t, c, s_rk, s_rd, s_ri, md, mi);
+                    const float cand = mi == kAoxNone ? INFINITY : cost[aox_at(sa, mi, M)] + md;
+                    if (mi != kAoxNone && mi != st.ni && cand < st.new_cost && cr != 0.f)
+                    {
+                        if (tid < dim) qs[tid] = pool[aox_at(sa, mi, M) * dim + tid], qg[tid] = s_t[tid];
+                        st.mi = mi, st.cand_cost = cand;
+                        st.phase = kAoxReparent, st.slot = a, ++st.questions;
+                        save();
+                        return;
+                    }
+                }
+            }
+
+            if (act == kCommit)  // count `new`, then look for a connection that beats the bound
+            {
+                const uint32_t sa = st.a_side, sb = sa ^ 1u;
+                st.new_i = aox_grow(st, sa);
+                const size_t new_at = aox_at(sa, st.new_i, M);
+                if (tid == 0) parent[new_at] = st.ni, cost[new_at] = st.new_cost;
+                if (tid < dim) s_t[tid] = pool[new_at * dim + tid];
+                __syncthreads();  // the cost is read by later searches of this launch
+                aox_nearest(pool, cost, sb, aox_count(st, sb), P, s_t, st.max_cost - st.new_cost, s_rk, s_rd, s_ri, st.bd, st.bi);
+                act = kLoop;
+                if (st.bi != kAoxNone && (st.new_cost + st.bd) + cost[aox_at(sb, st.bi, M)] < st.max_cost)
+                {
+                    const float c = ceilf(st.bd / R);
+                    st.n_steps = (c >= 1.f && c < 2147483648.f) ? (uint32_t) c : 1u;
+                    st.k = 0, st.prev = st.bi;
+                    act = kMarchStep;
+                }
+            }
+
+            if (act == kMarchStep)
+            {
+                const uint32_t sa = st.a_side, sb = sa ^ 1u;
+                if (st.n[0] + st.n[1] >= M)
+                    act = kLoop;  // the pool is full: the march ends unconnected
+                else
+                {
+                    const float *o = pool + aox_at(sb, st.bi, M) * dim, *nw = pool + aox_at(sa, st.new_i, M) * dim;
+                    const float *from = pool + aox_at(sb, st.prev, M) * dim;
+                    const size_t w_at = aox_at(sb, aox_count(st, sb), M);
+                    const float s = st.bd > 0.f ? fminf((float) (st.k + 1u) * R, st.bd) / st.bd : 0.f;
+                    float sum = 0.f;  // every thread computes the whole of w: dist(w, from) needs no exchange
+                    for (uint32_t j = 0; j < dim; ++j)
+                    {
+                        float w = nw[j];
+                        if (st.bd > 0.f) w = o[j] + (nw[j] - o[j]) * s;
+                        const float df = w - from[j];
+                        sum = sum + df * df;
+                        if (tid == j) pool[w_at * dim + j] = w, qs[j] = from[j], qg[j] = w;
+                    }
+                    st.phase = kAoxMarch, st.slot = a, ++st.questions;
+                    if (tid == 0) parent[w_at] = st.prev, cost[w_at] = cost[aox_at(sb, st.prev, M)] + sqrtf(sum);
+                    save();
+                    return;
+                }
+            }
+
+            if (act == kLoop)
+            {
+                if (tid == 0) phs_frame(start, goal, dim, s_frame);
+                uint32_t spins = 0;
+                for (;;)
+                {
+                    if (st.iterations >= st.budget)
+                    {
+                        st.status = VMV_PLAN_MAX_ITERATIONS, act = kFinish;
+                        break;
+                    }
+                    if (st.n[0] + st.n[1] >= M)
+                    {
+                        st.status = VMV_PLAN_MAX_SAMPLES, act = kFinish;
+                        break;
+                    }
+                    if (spins >= kAoxSpinCap)  // a null question; the loop goes on in the next round
+                    {
+                        if (tid < dim) qs[tid] = start[tid], qg[tid] = start[tid];
+                        st.phase = kAoxIdle, st.slot = a;
+                        save();
+                        return;
+                    }
+                    ++spins;
+                    ++st.iterations;
+                    {
+                        const float na = (float) aox_count(st, st.a_side), nb = (float) aox_count(st, st.a_side ^ 1u);
+                        if (!P.balance || fabsf(na - nb) / na < P.tree_ratio) st.a_side ^= 1u;
+                    }
+                    const uint32_t sa = st.a_side, sb = sa ^ 1u;
+                    if (tid == 0)
+                    {
+                        const bool ok = phs_sample(s_frame, dim, P.lower, P.span, st.max_cost, seed, s_counter, s_g, s_t);
+                        s_ok = ok ? 1u : 0u;
+                        if (ok)
+                        {
+                            const float g = aox_dist(s_t, pool + aox_at(sa, 0, M) * dim, dim);
+                            const float f = g + aox_dist(s_t, pool + aox_at(sb, 0, M) * dim, dim);
+                            const float c_range = fmaxf(st.max_cost - f, 0.f);
+                            s_c = aox_uniform(seed, s_counter) * c_range + g;
+                        }
+                    }
+                    __syncthreads();
+                    const bool ok = s_ok != 0u;
+                    const float c = s_c;
+                    __syncthreads();  // lane 0 may draw again
+                    if (!ok) continue;
+                    float d;
+                    uint32_t ni;
+                    aox_nearest(pool, cost, sa, aox_count(st, sa), P, s_t, c, s_rk, s_rd, s_ri, d, ni);
+                    if (ni == kAoxNone || !(d > 0.f)) continue;
+                    const float s = fminf(d, R) / d;
+                    if (tid < dim)
+                    {
+                        const float near = pool[aox_at(sa, ni, M) * dim + tid];
+                        const float nw = near + (s_t[tid] - near) * s;
+                        pool[aox_at(sa, aox_count(st, sa), M) * dim + tid] = nw;
+                        qs[tid] = near;
+                        qg[tid] = nw;
+                    }
+                    st.ni = ni;
+                    st.phase = kAoxExtend, st.slot = a, ++st.questions;
+                    save();
+                    return;
+                }
+            }
+
+            // finished (now or in an earlier round): the null question start -> start, its answer is ignored
+            if (tid < dim) qs[tid] = start[tid], qg[tid] = start[tid];
+            if (st.phase != kAoxDone && tid == 0)
+            {
+                st.phase = kAoxDone, st.slot = a;
+                st.path_len = st.status == VMV_PLAN_SOLVED ? aox_trace(st, pool, parent, dim, M, nullptr) : 0u;
+                st.counter = s_counter;
+                D.state[p] = st;
+                D.done[p] = 1;
+            }
+        }
+
+        __global__ __launch_bounds__(kAoxBlock) void aox_trace_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active,
+                                                                       const uint64_t *__restrict__ offsets, float *__restrict__ paths)
+        {
+            const uint32_t a = blockIdx.x * kAoxBlock + threadIdx.x;
+            if (a >= n_active) return;
+            const uint32_t p = D.active[a];
+            const AoxState st = D.state[p];
+            if (st.phase != kAoxDone || st.status != VMV_PLAN_SOLVED) return;
+            (void) aox_trace(st, D.pool + (size_t) p * P.max_samples * P.dim, D.parent + (size_t) p * P.max_samples, P.dim,
+                             P.max_samples, paths + offsets[a] * P.dim);
+        }
+
+        // vmv_phs_samples: n successive samples of one problem's stream, drawn by one lane as aox_step_kernel draws them
+        __global__ __launch_bounds__(kWave) void phs_samples_kernel(const AoxParams P, const float *__restrict__ start,
+                                                                     const float *__restrict__ goal, const float max_cost,
+                                                                     const uint32_t seed, const uint32_t counter, const uint32_t n,
+                                                                     float *__restrict__ out_q, uint8_t *__restrict__ out_ok,
+                                                                     uint32_t *__restrict__ out_counter)
+        {
+            __shared__ PhsFrame s_frame;
+            __shared__ float s_g[kAoxMaxDim + 2], s_t[kAoxMaxDim];
+            if (threadIdx.x != 0 || blockIdx.x != 0) return;
+            phs_frame(start, goal, P.dim, s_frame);
+            uint32_t c = counter;
+            for (uint32_t i = 0; i < n; ++i)
+            {
+                const bool ok = phs_sample(s_frame, P.dim, P.lower, P.span, max_cost, seed, c, s_g, s_t);
+                for (uint32_t j = 0; j < P.dim; ++j) out_q[(size_t) i * P.dim + j] = s_t[j];
+                out_ok[i] = ok ? 1 : 0;
+            }
+            *out_counter = c;
+        }
+
+        float host_dist(const float *a, const float *b, int dim)
+        {
+            float sum = 0.f;
+            for (int j = 0; j < dim; ++j)
+            {
+                const float df = b[j] - a[j];
+                sum = sum + df * df;
+            }
+            return std::sqrt(sum);
+        }
+
+        // Path::cost (planning/plan.hh:13-32): the fp32 sum of the segment lengths in order
+        float host_path_cost(const std::vector<float> &pts, int dim)
+        {
+            const size_t len = pts.size() / (size_t) dim;
+            if (len < 2) return std::numeric_limits<float>::infinity();
+            float acc = 0.f;
+            for (size_t k = 0; k + 1 < len; ++k) acc = acc + host_dist(&pts[k * dim], &pts[(k + 1) * dim], dim);
+            return acc;
+        }
+
+        // vmv_simplify_multi over paths[idx[...]] in their environments, in place; a path longer than the simplifier's
+        // max_waypoints stays as it is.  The call's rounds and questions are added to the totals.
+        int simplify_some(int robot, const vmv_env *const *envs, int dim, const std::vector<uint32_t> &idx,
+                          std::vector<std::vector<float>> &paths, const vmv_simplify_settings &S, uint64_t &rounds,
+                          uint64_t &questions)
+        {
+            const size_t max_waypoints = S.max_waypoints ? S.max_waypoints : 2048;  // the simplifier's default
+            std::vector<uint32_t> which;
+            std::vector<const vmv_env *> sub_envs;
+            std::vector<float> points;
+            std::vector<size_t> offsets{0};
+            for (const uint32_t p : idx)
+            {
+                const size_t len = paths[p].size() / (size_t) dim;
+                if (len > max_waypoints) continue;
+                which.push_back(p), sub_envs.push_back(envs[p]);
+                points.insert(points.end(), paths[p].begin(), paths[p].end());
+                offsets.push_back(offsets.back() + len);
+            }
+            if (which.empty()) return VMV_OK;
+            vmv_paths *out = nullptr;
+            if (int rc = vmv_simplify_multi(robot, sub_envs.data(), which.size(), points.data(), offsets.data(), &S, &out); rc != VMV_OK)
+                return rc;
+            std::vector<uint32_t> lengths(which.size());
+            uint64_t r = 0, q = 0;
+            int rc = vmv_paths_summary(out, nullptr, nullptr, lengths.data(), nullptr, &r, &q);
+            size_t total = 0;
+            for (const uint32_t len : lengths) total += len;
+            std::vector<float> simplified(total * (size_t) dim);
+            if (rc == VMV_OK) rc = vmv_paths_points(out, simplified.data(), simplified.size());
+            (void) vmv_paths_destroy(out);
+            if (rc != VMV_OK) return rc;
+            size_t at = 0;
+            for (size_t k = 0; k < which.size(); ++k)
+            {
+                const size_t count = (size_t) lengths[k] * (size_t) dim;
+                paths[which[k]].assign(simplified.begin() + at, simplified.begin() + at + count);
+                at += count;
+            }
+            rounds += r, questions += q;
+            return VMV_OK;
+        }
+
+        // The searches of an aorrtc call: device buffers for all n problems, allocated once; one generation = one search of
+        // every problem in `active`, each with its own bound and budget.
+        struct AoxSearches
+        {
+            int robot, dim;
+            size_t n;
+            uint32_t check_every, max_resamples, max_samples;
+            AoxParams P{};
+            AoxArrays D{};
+            DeviceBuffers mem;
+            float *d_starts = nullptr, *d_goals = nullptr, *d_max_cost = nullptr;
+            uint64_t *d_skips = nullptr, *d_bits = nullptr, *d_offsets = nullptr;
+            uint32_t *d_active = nullptr, *d_budget = nullptr;
+            uint8_t *h_done = nullptr;
+            float *d_paths = nullptr;  // the traced paths of one generation, packed
+            uint64_t paths_capacity = 0;  // in waypoints
+            hipStream_t stream = nullptr;
+            ~AoxSearches()
+            {
+                if (d_paths) (void) hipFree(d_paths);
+            }
+
+            int setup(const float *starts, const float *goals, const uint64_t *skips)
+            {
+                const size_t qn = n * (size_t) dim;
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.pool, n * (size_t) max_samples * (size_t) dim));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) max_samples));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.cost, n * (size_t) max_samples));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_starts, qn));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_goals, qn));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_max_cost, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_budget, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_active, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (n + 63) / 64));
+                VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n));
+                VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
+                h_done = static_cast<uint8_t *>(mem.pinned);
+                D.starts = d_starts, D.goals = d_goals, D.skips = d_skips, D.active = d_active, D.bits = d_bits;
+                D.max_cost = d_max_cost, D.budget = d_budget;
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_starts, starts, qn * 4, hipMemcpyHostToDevice, stream));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_goals, goals, qn * 4, hipMemcpyHostToDevice, stream));
+                if (skips)
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
+                else
+                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
+                VMV_LOCKSTEP_HIP(hipMemsetAsync(D.state, 0, n * sizeof(AoxState), stream));  // every counter starts at 0
+                VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((n + 63) / 64) * 8, stream));
+                VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+                return VMV_OK;
+            }
+
+            // One search of every problem of `active` (bound max_cost[p], budget[p] iterations; both indexed by problem).
+            // -> states[p] of the active problems, and found[p] = the waypoints of those that solved it.
+            int generation(const vmv_env *const *envs, const std::vector<uint32_t> &active_in, const std::vector<float> &max_cost,
+                           const std::vector<uint32_t> &budget, std::vector<AoxState> &states, std::vector<std::vector<float>> &found,
+                           uint64_t &rounds_total)
+            {
+                std::vector<uint32_t> active(active_in);
+                std::vector<const vmv_env *> active_envs(active.size());
+                uint32_t max_budget = 0;
+                for (size_t k = 0; k < active.size(); ++k)
+                    active_envs[k] = envs[active[k]], max_budget = std::max(max_budget, budget[active[k]]);
+                const uint32_t na = (uint32_t) active.size();
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), na * 4ull, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_max_cost, max_cost.data(), n * 4, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_budget, budget.data(), n * 4, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL(aox_init_kernel, dim3((na + kAoxBlock - 1) / kAoxBlock), dim3(kAoxBlock), 0, stream, P, D, na);
+                VMV_LOCKSTEP_HIP(hipGetLastError());
+
+                // an iteration asks at most 1 + max_resamples questions that add no node (an invalid extension; or the re-parent
+                // questions and the march's invalid step), every other question adds a node; a null round of the spin cap stands
+                // for kAoxSpinCap iterations that asked nothing: a bound on the rounds that does not depend on the device's answers
+                const uint64_t max_rounds = (uint64_t) max_budget * (1ull + max_resamples) + max_samples + check_every + 2ull;
+                uint64_t rounds = 0;
+                const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
+                const auto step = [&](uint32_t count) { hipLaunchKernelGGL(aox_step_kernel, dim3(count), dim3(kAoxBlock), 0, stream, P, D); };
+                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, L, "vmv_aorrtc_multi",
+                                             "aox_step_kernel", step, rounds);
+                    rc != VMV_OK)
+                    return rc;
+                rounds_total += rounds;
+
+                states.resize(n);
+                VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(AoxState), hipMemcpyDeviceToHost));
+                std::vector<uint64_t> offsets(na);
+                uint64_t total = 0;
+                for (uint32_t k = 0; k < na; ++k)
+                {
+                    offsets[k] = total;
+                    total += states[active_in[k]].path_len;
+                }
+                if (!total) return VMV_OK;
+                // (lockstep_rounds compacted d_active: the trace runs over the generation's whole list again)
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active_in.data(), na * 4ull, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, offsets.data(), na * 8ull, hipMemcpyHostToDevice));
+                if (total > paths_capacity)  // the trace buffer only grows: most generations reuse it
+                {
+                    const uint64_t want = std::max<uint64_t>(total, 2 * paths_capacity);
+                    if (d_paths) (void) hipFree(d_paths);
+                    d_paths = nullptr, paths_capacity = 0;
+                    VMV_LOCKSTEP_HIP(hipMalloc(&d_paths, want * (size_t) dim * 4));
+                    paths_capacity = want;
+                }
+                hipLaunchKernelGGL(aox_trace_kernel, dim3((na + kAoxBlock - 1) / kAoxBlock), dim3(kAoxBlock), 0, stream, P, D, na,
+                                   d_offsets, d_paths);
+                hipError_t e = hipGetLastError();
+                std::vector<float> packed(total * (size_t) dim);
+                if (e == hipSuccess) e = hipMemcpy(packed.data(), d_paths, packed.size() * 4, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return hip_status(e, "aox_trace_kernel");
+                for (uint32_t k = 0; k < na; ++k)
+                {
+                    const uint32_t p = active_in[k];
+                    const size_t count = (size_t) states[p].path_len * (size_t) dim;
+                    found[p].assign(packed.begin() + offsets[k] * dim, packed.begin() + offsets[k] * dim + count);
+                }
+                return VMV_OK;
+            }
+        };
+
+        // After the first stage: `plans` is vmv_rrtc_multi's result for the n > 0 problems and becomes the call's result.
+        int aorrtc_after_first(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
+                               const float *starts, const float *goals, const uint64_t *skips, const vmv_aorrtc_settings &S,
+                               vmv_plans *plans)
+        {
+            const float inf = std::numeric_limits<float>::infinity();
+            plans->first_costs.assign(n, inf), plans->final_costs.assign(n, inf);
+            plans->searches.assign(n, 0), plans->improvements.assign(n, 0);
+            std::vector<std::vector<float>> best(n);
+            std::vector<uint32_t> solved;
+            size_t at = 0;
+            for (size_t p = 0; p < n; ++p)
+            {
+                const size_t count = (size_t) plans->path_lengths[p] * (size_t) dim;
+                best[p].assign(plans->paths.begin() + at, plans->paths.begin() + at + count);
+                at += count;
+                if (plans->status[p] == VMV_PLAN_SOLVED) solved.push_back((uint32_t) p);
+            }
+            if (S.simplify_intermediate)
+                if (int rc = simplify_some(robot, envs, dim, solved, best, S.simplify, plans->rounds, plans->questions); rc != VMV_OK)
+                    return rc;
+            std::vector<uint32_t> optimising;
+            std::vector<float> dmin(n, 0.f);
+            for (const uint32_t p : solved)
+            {
+                plans->first_costs[p] = plans->final_costs[p] = host_path_cost(best[p], dim);
+                dmin[p] = host_dist(starts + (size_t) p * dim, goals + (size_t) p * dim, dim);
+                if (S.optimize && best[p].size() != 2u * (size_t) dim) optimising.push_back(p);
+            }
+
+            if (!optimising.empty())
+            {
+                AoxSearches X;
+                X.robot = robot, X.dim = dim, X.n = n;
+                X.check_every = S.rrtc.check_every ? S.rrtc.check_every : kAoxDefaultCheckEvery;
+                X.max_resamples = S.cost_bound_resample ? S.max_cost_bound_resamples : 0u, X.max_samples = S.max_samples;
+                X.P.dim = (uint32_t) dim, X.P.max_samples = S.max_samples, X.P.balance = S.rrtc.balance ? 1u : 0u;
+                X.P.resample = S.cost_bound_resample ? 1u : 0u, X.P.max_resamples = S.max_cost_bound_resamples;
+                X.P.range = S.rrtc.range, X.P.tree_ratio = S.rrtc.tree_ratio;
+                for (int j = 0; j < dim; ++j) X.P.lower[j] = lower[j], X.P.span[j] = span[j];
+                if (int rc = X.setup(starts, goals, skips); rc != VMV_OK) return rc;
+                std::vector<float> max_cost(n, 0.f);
+                std::vector<uint32_t> budget(n, 0);
+                std::vector<AoxState> states;
+                std::vector<std::vector<float>> found(n);
+                for (;;)
+                {
+                    std::vector<uint32_t> active;
+                    for (const uint32_t p : optimising)
+                        if (plans->iterations[p] < S.max_iterations && plans->final_costs[p] - dmin[p] > 1e-8f &&
+                            (S.max_searches == 0 || plans->searches[p] < S.max_searches))
+                        {
+                            active.push_back(p);
+                            max_cost[p] = plans->final_costs[p];
+                            budget[p] = std::min(S.max_iterations - plans->iterations[p], S.max_internal_iterations);
+                        }
+                    if (active.empty()) break;
+                    if (int rc = X.generation(envs, active, max_cost, budget, states, found, plans->rounds); rc != VMV_OK) return rc;
+                    std::vector<uint32_t> improved;
+                    for (const uint32_t p : active)
+                    {
+                        const AoxState &st = states[p];
+                        ++plans->searches[p];
+                        plans->iterations[p] += st.iterations;
+                        plans->sizes2[2 * p] = st.n[st.a_side], plans->sizes2[2 * p + 1] = st.n[st.a_side ^ 1u];
+                        plans->questions += st.questions;
+                        if (st.status == VMV_PLAN_SOLVED) improved.push_back(p);
+                    }
+                    if (S.simplify_intermediate)
+                        if (int rc = simplify_some(robot, envs, dim, improved, found, S.simplify, plans->rounds, plans->questions);
+                            rc != VMV_OK)
+                            return rc;
+                    for (const uint32_t p : improved)
+                    {
+                        const float c = host_path_cost(found[p], dim);
+                        if (c < plans->final_costs[p])
+                        {
+                            best[p].swap(found[p]);
+                            plans->final_costs[p] = c;
+                            ++plans->improvements[p];
+                        }
+                    }
+                }
+            }
+
+            plans->aorrtc = true;
+            plans->paths.clear();
+            for (size_t p = 0; p < n; ++p)
+            {
+                plans->path_lengths[p] = (uint32_t) (best[p].size() / (size_t) dim);
+                plans->paths.insert(plans->paths.end(), best[p].begin(), best[p].end());
+            }
+            return VMV_OK;
+        }
+
+        int phs_samples_run(int robot, int dim, const float *start, const float *goal, float max_cost, uint32_t seed, uint32_t counter,
+                            size_t n, float *out_q, uint8_t *out_in_bounds, uint32_t *out_counter)
+        {
+            AoxParams P{};
+            P.dim = (uint32_t) dim;
+            float descale[16];
+            if (int rc = vmv_robot_bounds(robot, P.lower, P.span, descale); rc != VMV_OK) return rc;
+            DeviceBuffers mem;
+            float *d_start = nullptr, *d_goal = nullptr, *d_q = nullptr;
+            uint8_t *d_ok = nullptr;
+            uint32_t *d_counter = nullptr;
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_start, (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_goal, (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_q, n * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_ok, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_counter, (size_t) 1));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_start, start, (size_t) dim * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_goal, goal, (size_t) dim * 4, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(phs_samples_kernel, dim3(1), dim3(kWave), 0, nullptr, P, d_start, d_goal, max_cost, seed, counter,
+                               (uint32_t) n, d_q, d_ok, d_counter);
+            VMV_LOCKSTEP_HIP(hipGetLastError());
+            if (n)
+            {
+                VMV_LOCKSTEP_HIP(hipMemcpy(out_q, d_q, n * (size_t) dim * 4, hipMemcpyDeviceToHost));
+                VMV_LOCKSTEP_HIP(hipMemcpy(out_in_bounds, d_ok, n, hipMemcpyDeviceToHost));
+            }
+            VMV_LOCKSTEP_HIP(hipMemcpy(out_counter, d_counter, 4, hipMemcpyDeviceToHost));
+            return VMV_OK;
+        }
+    }  // namespace
+}  // namespace vmv
+
+extern "C"
+{
+    int vmv_aorrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                         const uint64_t *halton_skips, const vmv_aorrtc_settings *settings, vmv_plans **out)
+    {
+        // device-free checks first, in vmv_rrtc_multi's order; the simplifier's settings by an empty call of the simplifier
+        const int dim = vmv_robot_dimension(robot);
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kAoxMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_problems >= vmv::kMultiMaxConfigs / 64) return VMV_ERR_INVALID_ARGUMENT;  // (64 questions per path per round)
+        const vmv_aorrtc_settings &S = *settings;
+        if (S.max_internal_iterations == 0 || S.max_cost_bound_resamples > vmv::kAoxMaxResamples) return VMV_ERR_INVALID_ARGUMENT;
+        {
+            vmv_paths *none = nullptr;
+            if (int rc = vmv_simplify_multi(robot, nullptr, 0, nullptr, nullptr, &S.simplify, &none); rc != VMV_OK) return rc;
+            (void) vmv_paths_destroy(none);
+        }
+        vmv_rrtc_settings first = S.rrtc;
+        first.max_iterations = S.max_iterations, first.max_samples = S.max_samples;  // aorrtc.hh:384-386
+        vmv_plans *plans = nullptr;
+        if (int rc = vmv_rrtc_multi(robot, envs, n_problems, starts, goals, halton_skips, &first, &plans); rc != VMV_OK) return rc;
+        int rc = VMV_OK;
+        if (n_problems > 0)
+        {
+            float lower[16], span[16], descale[16];
+            rc = vmv_robot_bounds(robot, lower, span, descale);
+            if (rc == VMV_OK)
+                rc = vmv::aorrtc_after_first(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, S, plans);
+        }
+        else
+            plans->aorrtc = true;
+        if (rc != VMV_OK)
+        {
+            delete plans;
+            return rc;
+        }
+        *out = plans;
+        return VMV_OK;
+    }
+
+    int vmv_plans_costs(const vmv_plans *plans, float *first_costs, float *costs, uint32_t *searches, uint32_t *improvements)
+    {
+        if (!plans || !plans->aorrtc) return VMV_ERR_INVALID_ARGUMENT;
+        const size_t n = plans->n;
+        if (first_costs && n) std::memcpy(first_costs, plans->first_costs.data(), n * 4);
+        if (costs && n) std::memcpy(costs, plans->final_costs.data(), n * 4);
+        if (searches && n) std::memcpy(searches, plans->searches.data(), n * 4);
+        if (improvements && n) std::memcpy(improvements, plans->improvements.data(), n * 4);
+        return VMV_OK;
+    }
+
+    int vmv_phs_samples(int robot, const float *start, const float *goal, float max_cost, uint32_t seed, uint32_t counter,
+                        size_t n, float *out_q, uint8_t *out_in_bounds, uint32_t *out_counter)
+    {
+        const int dim = vmv_robot_dimension(robot);
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kAoxMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!start || !goal || !out_counter || (n > 0 && (!out_q || !out_in_bounds)) || n >= (size_t{1} << 24))
+            return VMV_ERR_INVALID_ARGUMENT;
+        return vmv::phs_samples_run(robot, dim, start, goal, max_cost, seed, counter, n, out_q, out_in_bounds, out_counter);
+    }
+}

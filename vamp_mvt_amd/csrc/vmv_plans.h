@@ -1,4 +1,4 @@
-// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi): vmv_plans_summary,
+// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi, vmv_aorrtc_multi): vmv_plans_summary,
 // vmv_plans_paths and vmv_plans_destroy (vmv_rrtc_multi.hip) read the first block whichever call made it.
 #pragma once
 
@@ -25,4 +25,9 @@ struct vmv_plans
     std::vector<uint32_t> edge_offsets;     // kept: [n + 1] first candidate edge of each problem
     std::vector<uint32_t> edge_pairs;       // kept: [edges][2] vertex ids a < b, in candidate order
     std::vector<uint8_t> edge_valid;        // kept: [edges]
+
+    // vmv_aorrtc_multi only (vmv_plans_costs)
+    bool aorrtc = false;
+    std::vector<float> first_costs, final_costs;  // [n] after the first stage; of the returned path (+inf = unsolved)
+    std::vector<uint32_t> searches, improvements; // [n] cost-bounded searches run; those that gave a cheaper path
 };

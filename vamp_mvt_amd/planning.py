@@ -21,7 +21,7 @@ Nothing here is on the measured hot path; all collision work goes through vamp_m
 from __future__ import annotations
 
 import heapq
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -109,6 +109,29 @@ class PRMMultiSettings:
     keep_roadmaps: bool = False
 
 
+@dataclass
+class AORRTCMultiSettings:
+    """settings of `aorrtc_multi` (planning/aorrtc_settings.hh): range, balance, tree_ratio of the RRT-Connect searches;
+    max_iterations of all stages together, max_internal_iterations of one cost-bounded search, max_samples (every problem
+    owns a node pool of that many nodes on the device, hence 8,192 and not the reference's 100,000),
+    max_cost_bound_resamples (at most 64; the reference's default is 1,000), max_searches (cost-bounded searches per
+    problem, 0 = no limit but max_iterations; not in the reference), `simplify` (SimplifyMultiSettings or the
+    reference-shaped SimplifySettings) and check_every (0 = the library's default)"""
+    range: float = 2.0
+    balance: bool = True
+    tree_ratio: float = 1.0
+    optimize: bool = True
+    cost_bound_resample: bool = True
+    simplify_intermediate: bool = True
+    max_iterations: int = 100000
+    max_internal_iterations: int = 100000
+    max_samples: int = 8192
+    max_cost_bound_resamples: int = 64
+    max_searches: int = 0
+    simplify: object = None
+    check_every: int = 0
+
+
 PLAN_STATUS = ("solved", "max_iterations", "max_samples", "no_path", "invalid_endpoint")  # VMV_PLAN_*
 SIMPLIFY_STATUS = ("ok", "capacity")  # VMV_SIMPLIFY_*
 
@@ -143,6 +166,9 @@ class PlanningResult:
     samples_drawn: int = 0
     status: str = ""  # rrtc_multi, prm_multi: one of PLAN_STATUS; simplify_multi: one of SIMPLIFY_STATUS
     roadmap: object = None  # prm_multi with keep_roadmaps: (vertex flags, candidate pairs [m][2], their flags)
+    first_cost: float = float("inf")  # aorrtc_multi: the cost after the first stage
+    searches: int = 0                 # aorrtc_multi: cost-bounded searches run
+    improvements: int = 0             # aorrtc_multi: those that gave a cheaper path
 
     @property
     def solved(self):
@@ -296,6 +322,40 @@ def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | N
                                   roadmap=raw["roadmaps"][p] if "roadmaps" in raw else None))
     if out:  # the call's validation calls ride on the first result
         out[0].validity_calls = raw["rounds"]
+    return out
+
+
+def aorrtc_multi(robot, starts, goals, environments, settings: AORRTCMultiSettings | None = None, skips=None):
+    """AORRTC (planning/aorrtc.hh) for many independent problems on the device, the arguments those of `rrtc_multi`.
+    -> list[PlanningResult], one per problem: `path` (the cheapest found, empty if the first stage found none), `cost`
+    and `first_cost` (Path::cost of the returned path and of the first stage's; inf if unsolved), `searches`,
+    `improvements`, `iterations` (all stages), `size` = [|A|, |B|] of the last search run and `status`.
+
+    Per problem: a first solution by `rrtc_multi`'s contract, simplified by `simplify_multi`'s; then, while the budget
+    lasts, RRT-Connect searches under the cost of the best path so far on fresh trees — samples drawn directly from the
+    prolate hyperspheroid of that cost, the nearest node by the reference's asymmetric cost-space rule, new nodes
+    re-parented under resampled cost bounds — each new solution simplified and kept if it is cheaper.  Search g of
+    every still-optimising problem is one lockstep call (one edge question per problem per round); the
+    solutions of a generation are simplified in one `simplify_multi` call; the host compares costs.
+
+    Every operation is fp32 with one rounding, the sampler included (a counter-based hash seeded with skips[p], its own
+    ln, Marsaglia's polar method, a Householder reflection: + - * / sqrt and integer operations only), so a problem's
+    result is defined bit for bit and does not depend on the other problems of the call or on check_every.  Agreement
+    with the reference's own random stream is not claimed."""
+    s = settings or AORRTCMultiSettings()
+    if not isinstance(s.simplify, SimplifyMultiSettings):
+        s = replace(s, simplify=_as_simplify_multi_settings(s.simplify))
+    raw = robot.aorrtc_multi_raw(starts, goals, environments, s, skips)
+    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+    out = []
+    for p in range(len(ends)):
+        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
+        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
+                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
+                                  first_cost=float(raw["first_costs"][p]), searches=int(raw["searches"][p]),
+                                  improvements=int(raw["improvements"][p]), status=PLAN_STATUS[int(raw["status"][p])]))
+    if out:  # the call's totals over all stages ride on the first result
+        out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
 
 
