@@ -497,6 +497,63 @@ int vmv_aorrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, c
  * VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
 int vmv_plans_costs(const vmv_plans *plans, float *first_costs, float *costs, uint32_t *searches, uint32_t *improvements);
 
+/* ---- lazy complete-graph search: many independent problems in one call ----------------------------------- */
+/* A* over the complete graph of a problem's valid samples with every unchecked edge taken as free, for n_problems problems
+ * at once; the arguments are those of vmv_prm_multi (starts, goals, envs, halton_skips or the caller's `samples`).  The
+ * vertices of all problems go through ONE vmv_validate_batch_multi call (vmv_prm_multi's layout); then the problems
+ * advance in lockstep rounds like those of vmv_rrtc_multi: per round a step kernel (one 256-thread workgroup per unfinished
+ * problem; g, h, parents and the open / closed flags of the valid vertices in LDS, the pair state in global memory)
+ * writes questions_per_round edge questions per unfinished problem, and one vmv_validate_motion_batch_multi launch
+ * sequence answers all of them.
+ * Per problem, bit-defined (fp32, one rounding per written operation):
+ *   V = n_samples + 2 vertices: 0 = start, 1 = goal, 2 + i = sample i; valid[v] = validate(vertex v) (a non-finite
+ *   joint: invalid).  !valid[0] or !valid[1]: VMV_PLAN_INVALID_ENDPOINT, no path, no edge is asked.
+ *   d2(u, v) = sum over the joints in order of (u[j] - v[j])^2, w(u, v) = sqrtf(d2(u, v)), h(v) = w(v, 1).
+ *   State: a set B of blocked unordered pairs, empty at first, and iterations = 0.
+ *   Search (at most V pops): iterations == max_iterations: VMV_PLAN_MAX_ITERATIONS, no path; else ++iterations, g[0] = 0,
+ *   every other g = +inf, open = {0}, nothing closed.  Pop the open, not closed vertex u least by (fl(g[u] + h[u]), then
+ *   vertex id); none: VMV_PLAN_NO_PATH; u == 1: the path is the parent chain.  Else close u, and for every valid, not
+ *   closed v != u with {u, v} not in B: c = fl(g[u] + w(u, v)); c < g[v]: g[v] = c, parent[v] = u, v is open.  A closed
+ *   vertex is never reopened.  g[1] is the left-to-right fp32 sum along the path.
+ *   Check: the path's edges from the start; the question of {a, b}, a < b, is validate_motion(a -> b).  An edge known
+ *   valid is skipped; one answered valid is remembered and the walk goes on; the first one answered invalid enters B and
+ *   the search runs again; every edge valid: VMV_PLAN_SOLVED, the path the vertices' stored bits, cost = g[1].
+ *   The first proposed path is always [0, 1].
+ * A problem's result (status, iterations, path, cost, valid vertices, |B|, edges known valid) depends on its own inputs
+ * and max_iterations alone, bit for bit: not on the batch, questions_per_round or check_every.  Slot 0 of a round is the
+ * next question the rules above reach, so every round makes progress; the other slots are predictions — the proposed
+ * path's later unknown edges, then the first unknown edge of the paths found with the round's questions taken as invalid;
+ * none with a problem's first question, the straight edge — whose answers only fill a cache that the walk consults before it asks (a cached invalid answer enters B when the walk
+ * reaches that edge).  Unused slots and finished problems ask the null question start -> start.  A problem runs at most
+ * 64 searches per round, predictions included; beyond that it asks null questions and carries on in the next round.
+ * Agreement with the reference's FCIT* (planning/fcit.hh, an edge-queue search) is not claimed.
+ * Device memory per problem: 2 * V * ceil(V / 32) * 4 bytes of pair state (two answer-cache bits and one blocked bit per
+ * ordered pair), V * (dimension + 1) * 4 bytes of vertices and path, questions_per_round * (2 * dimension + 2) * 4 bytes
+ * of questions; the pair state is 1.07 MB at n_samples = 2,048 and 18.6 KB at 256.
+ * The result is a vmv_plans: vmv_plans_summary reports iterations = searches run, sizes2 = [valid vertices, blocked
+ * edges], rounds = validation calls made (the vertices' included), questions = edge questions asked (null questions not
+ * counted); vmv_plans_paths and vmv_plans_destroy work as for vmv_rrtc_multi.
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / starts / goals / settings / out
+ * or a NULL handle, n_samples not a multiple of 64 or outside 64 .. 2,048, questions_per_round outside 1 .. 32,
+ * max_iterations == 0, halton skip + n_samples > 1,000,000 where samples is NULL, n_problems * V * ceil(V / 32) >= 2^31
+ * (the words of one pair-state matrix) or n_problems * questions_per_round >= 2^31 (the questions of a round)
+ * (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment (VMV_ERR_NOT_FINALIZED); an environment of another device
+ * (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out untouched.  n_problems == 0 is VMV_OK with an empty result.
+ * Environments not yet prepared for the robot are prepared in one batch.  Synchronous, host buffers, on the default
+ * stream; repeated handles are allowed. */
+typedef struct
+{
+    uint32_t n_samples;
+    uint32_t max_iterations;      /* searches per problem; >= 1 */
+    uint32_t questions_per_round; /* edge questions per problem per round: 1 .. 32 */
+    uint32_t check_every;         /* rounds between two looks of the host at the finished flags; 0 = default */
+} vmv_fcit_settings;
+int vmv_fcit_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                   const uint64_t *halton_skips, const float *samples, const vmv_fcit_settings *settings, vmv_plans **out);
+/* Per problem of a vmv_fcit_multi result (arrays of n_problems, either may be NULL): cost (+inf = unsolved) and the edges
+ * the walk found valid.  VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
+int vmv_plans_fcit_summary(const vmv_plans *plans, float *costs, uint32_t *known_valid_edges);
+
 /* ---- measurement support (bench.py) ---------------------------------------------------------------------- */
 /* Runs vmv_validate_batch `iters` times on `stream` between two HIP events recorded on that same stream and
  * returns the average kernel time in milliseconds. */

@@ -910,6 +910,70 @@ class _Robot(types.ModuleType):
             lib.vmv_plans_destroy(plans)
         return out
 
+    def fcit_multi_raw(self, starts, goals, environments, settings, skips=None, samples=None):
+        """vmv_fcit_multi: a lazy A* search of the complete graph over each problem's valid samples, the arguments those
+        of prm_multi_raw.  settings: n_samples, max_iterations, questions_per_round, check_every.  -> dict of
+        per-problem numpy arrays (status, iterations = searches run, sizes [n][2] = valid vertices and blocked edges,
+        path_lengths, costs, known_valid_edges), the packed waypoints (paths [sum(path_lengths)][dim]) and the totals
+        rounds and questions.  planning.fcit_multi is the caller-facing form.  Every argument is checked before any
+        library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = a.shape[0]
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        ns, max_it = int(settings.n_samples), int(settings.max_iterations)
+        per_round, every = int(settings.questions_per_round), int(getattr(settings, "check_every", 0))
+        if ns % 64 != 0 or not 64 <= ns <= 2048:
+            raise ValueError("n_samples must be a multiple of 64 from 64 to 2,048")
+        if not 1 <= per_round <= 32:
+            raise ValueError("questions_per_round must be from 1 to 32")
+        if not (1 <= max_it < 2 ** 32 and 0 <= every < 2 ** 32):
+            raise ValueError("max_iterations must be positive, and fit 32 bits as check_every must")
+        if n * (ns + 2) * ((ns + 2 + 31) // 32) >= 2 ** 31 or n * per_round >= 2 ** 31:
+            raise ValueError("n_problems * (n_samples + 2) * ceil((n_samples + 2) / 32) and n_problems * questions_per_round "
+                             "must stay below 2^31")
+        sk = sm = None
+        if samples is not None:
+            sm = _f32(samples)
+            if sm.shape == (ns, self._dim):
+                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
+            if sm.shape != (n, ns, self._dim):
+                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
+        if skips is not None:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
+                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        cs = _lib.FcitSettings(ns, max_it, per_round, every)
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        plans = ctypes.c_void_p()
+        check(lib.vmv_fcit_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
+                                 None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(plans)), "vmv_fcit_multi")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
+                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
+                  "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+            costs, known = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+            check(lib.vmv_plans_fcit_summary(plans, _fp(costs), known.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_fcit_summary")
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, costs=costs,
+                    known_valid_edges=known, rounds=int(rounds.value), questions=int(questions.value))
+
     def simplify_multi_raw(self, paths, environments, settings):
         """vmv_simplify_multi: the reference's simplify() with the SHORTCUT and BSPLINE routines for many paths in
         lockstep, path p ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).

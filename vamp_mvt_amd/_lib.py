@@ -36,6 +36,12 @@ class PrmSettings(ctypes.Structure):
                 ("keep_roadmaps", ctypes.c_int)]
 
 
+class FcitSettings(ctypes.Structure):
+    """vmv_fcit_settings"""
+    _fields_ = [("n_samples", ctypes.c_uint32), ("max_iterations", ctypes.c_uint32), ("questions_per_round", ctypes.c_uint32),
+                ("check_every", ctypes.c_uint32)]
+
+
 class SimplifySettings(ctypes.Structure):
     """vmv_simplify_settings"""
     _fields_ = [("max_iterations", ctypes.c_uint32), ("interpolate", ctypes.c_uint32), ("n_operations", ctypes.c_uint32),
@@ -158,6 +164,9 @@ def _load():
         "vmv_aorrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
                                  ctypes.POINTER(V)]),
         "vmv_plans_costs": (I, [V, c_float_p, c_float_p, c_u32_p, c_u32_p]),
+        "vmv_fcit_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, c_float_p, ctypes.POINTER(FcitSettings),
+                               ctypes.POINTER(V)]),
+        "vmv_plans_fcit_summary": (I, [V, c_float_p, c_u32_p]),
         "vmv_phs_samples": (I, [I, c_float_p, c_float_p, F, ctypes.c_uint32, ctypes.c_uint32, S, c_float_p,
                                 ctypes.POINTER(ctypes.c_uint8), c_u32_p]),
         "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),

@@ -420,6 +420,25 @@ def install(robot):
             out.append(res)
         return out
 
+    def fcit_multi(starts, goals, environments, settings, skips=None, samples=None):
+        """planning.fcit_multi with this robot and the reference-shaped FCITSettings: n_samples = min(max_samples, 2048)
+        rounded down to a multiple of 64 and at least 64, max_iterations as given (at least 1) -> list[PlanningResult]
+        (each with `status`; nanoseconds is the whole call's time divided by the problems)"""
+        t0 = time.perf_counter_ns()
+        n = max(64, min(int(settings.max_samples), 2048) // 64 * 64)
+        s = planning.FCITMultiSettings(n_samples=n, max_iterations=max(1, min(int(settings.max_iterations), 2 ** 32 - 1)))
+        results = planning.fcit_multi(robot, starts, goals, environments, s, skips, samples)
+        each = (time.perf_counter_ns() - t0) // max(len(results), 1)
+        out = []
+        for r in results:
+            path = Path()
+            for q in r.path:
+                path.append(q)
+            res = PlanningResult(path, each, r.iterations, r.size, r.cost)
+            res.status = r.status
+            out.append(res)
+        return out
+
     def simplify(path, environment, settings, rng):
         """greedy shortcutting: for every waypoint the farthest later waypoint it can reach by a valid motion; the
         candidate motions of one pass are validated together (`validate_motion_batch`)"""
@@ -471,6 +490,7 @@ def install(robot):
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
+    robot.fcit_multi = fcit_multi
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 

@@ -1,4 +1,4 @@
-// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi, vmv_aorrtc_multi): vmv_plans_summary,
+// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi, vmv_aorrtc_multi, vmv_fcit_multi): vmv_plans_summary,
 // vmv_plans_paths and vmv_plans_destroy (vmv_rrtc_multi.hip) read the first block whichever call made it.
 #pragma once
 
@@ -30,4 +30,8 @@ struct vmv_plans
     bool aorrtc = false;
     std::vector<float> first_costs, final_costs;  // [n] after the first stage; of the returned path (+inf = unsolved)
     std::vector<uint32_t> searches, improvements; // [n] cost-bounded searches run; those that gave a cheaper path
+
+    // vmv_fcit_multi only (vmv_plans_fcit_summary; n_samples and costs as above)
+    bool fcit = false;
+    std::vector<uint32_t> known_valid;  // [n] edges the walk found valid
 };

@@ -110,6 +110,19 @@ class PRMMultiSettings:
 
 
 @dataclass
+class FCITMultiSettings:
+    """settings of `fcit_multi`: n_samples samples per problem (a multiple of 64 from 64 to 2,048), max_iterations
+    searches per problem, questions_per_round (edge questions per problem per round, 1 .. 32: the first is the one the
+    search needs next, the others are predictions; 1 is what the measured sweep favours, since a prediction costs a
+    search) and check_every (rounds between two looks of the host at which problems are finished; 0 = the library's
+    default)"""
+    n_samples: int = 1024
+    max_iterations: int = 100000
+    questions_per_round: int = 1
+    check_every: int = 0
+
+
+@dataclass
 class AORRTCMultiSettings:
     """settings of `aorrtc_multi` (planning/aorrtc_settings.hh): range, balance, tree_ratio of the RRT-Connect searches;
     max_iterations of all stages together, max_internal_iterations of one cost-bounded search, max_samples (every problem
@@ -169,6 +182,7 @@ class PlanningResult:
     first_cost: float = float("inf")  # aorrtc_multi: the cost after the first stage
     searches: int = 0                 # aorrtc_multi: cost-bounded searches run
     improvements: int = 0             # aorrtc_multi: those that gave a cheaper path
+    known_valid_edges: int = 0        # fcit_multi: edges the walk found valid
 
     @property
     def solved(self):
@@ -322,6 +336,35 @@ def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | N
                                   roadmap=raw["roadmaps"][p] if "roadmaps" in raw else None))
     if out:  # the call's validation calls ride on the first result
         out[0].validity_calls = raw["rounds"]
+    return out
+
+
+def fcit_multi(robot, starts, goals, environments, settings: FCITMultiSettings | None = None, skips=None, samples=None):
+    """A lazy search of the complete graph over each problem's valid samples, for many independent problems in one call
+    on the device; the arguments are those of `prm_multi`.  -> list[PlanningResult], one per problem: `path` (waypoints,
+    empty if unsolved), `cost` (inf if unsolved), `iterations` (searches run), `size` = [valid vertices, blocked edges],
+    `known_valid_edges` and `status` (one of PLAN_STATUS: "solved", "max_iterations", "no_path", "invalid_endpoint").
+
+    Per problem: A* from the start to the goal over the valid vertices with every unchecked edge taken as free; the
+    proposed path's edges are asked from the start, the first invalid one is blocked and the search runs again, until a
+    proposed path is valid throughout or none is left.  The complete graph contains every k-nearest graph
+    over the same samples, so what `prm_multi` solves this solves, at no higher cost, and it asks only the edges of the
+    paths it proposes.  All vertices go through ONE validate_batch_multi call; the searches advance in lockstep rounds
+    of questions_per_round questions per problem, the first the one the search needs, the others predictions that only
+    fill an answer cache.  The result is defined bit for bit (fp32, one rounding per operation, pops ordered by (g + h,
+    vertex id), closed vertices never reopened) and depends on the problem's own inputs and max_iterations alone.
+    Agreement with the reference's FCIT* (an edge-queue search) is not claimed."""
+    s = settings or FCITMultiSettings()
+    raw = robot.fcit_multi_raw(starts, goals, environments, s, skips, samples)
+    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+    out = []
+    for p in range(len(ends)):
+        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
+        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
+                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
+                                  known_valid_edges=int(raw["known_valid_edges"][p]), status=PLAN_STATUS[int(raw["status"][p])]))
+    if out:  # the call's totals ride on the first result (validity_calls: the vertices' call and one per round)
+        out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
 
 
