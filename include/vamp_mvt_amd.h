@@ -382,6 +382,81 @@ int vmv_plans_roadmap_vertices(const vmv_plans *plans, size_t p, uint8_t *valid)
  * small (nothing is written but *n) */
 int vmv_plans_roadmap_edges(const vmv_plans *plans, size_t p, uint32_t *pairs2, uint8_t *valid, size_t capacity, size_t *n);
 
+/* ---- device-resident roadmaps: built once per scene, asked many times ------------------------------------ */
+/* vmv_roadmaps_build builds n_roadmaps roadmaps in one call, roadmap r in envs[r], over n_samples samples each: the Halton
+ * samples halton_skips[r] + 1, ... (NULL = all 0) or, where `samples` is not NULL, the caller's
+ * ([n_roadmaps][n_samples][dimension] host floats).  It is vmv_prm_multi without endpoints: all samples through ONE
+ * vmv_validate_batch_multi call, the k nearest valid samples of every valid sample, all candidate edges through ONE
+ * vmv_validate_motion_batch_multi call, one host synchronisation in between (the edge counts).  The samples, their validity
+ * words, the candidate pairs, their weights and their answers stay on the device inside the handle.
+ * Roadmap r, bit-defined (the arithmetic of vmv_prm_multi): vertices are the samples i = 0 .. n_samples - 1,
+ *   valid[i] = finite and validate; nbr(v) for a valid v = the k valid u != v with 0 < d2(v, u) <= radius^2 first in the
+ *   order (d2, id); candidate edges for v ascending, slot ascending, u = nbr(v)[slot]: {v, u} if v < u or v is not in nbr(u);
+ *   each is asked lower id -> higher id.  Samples 0 and 1 are ordinary vertices.
+ * A roadmap does not depend on which other roadmaps share the call.
+ * The handle records the robot, the device and the environment handles.  AN ENVIRONMENT MUST OUTLIVE ITS ROADMAPS, and a
+ * roadmap answers for the environment as it was finalized at build time (an environment is immutable after
+ * vmv_env_finalize, so a handle cannot go stale while its environments live).  The handle is used on the device it was
+ * built on (another current device: VMV_ERR_INVALID_ARGUMENT).
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / settings / out or a NULL handle,
+ * n_samples not a multiple of 64 or outside 64 .. 8,128, k outside 1 .. 16, radius NaN or <= 0, halton skip + n_samples >
+ * 1,000,000 where samples is NULL, n_roadmaps * n_samples * k >= 2^31 (VMV_ERR_INVALID_ARGUMENT); an unfinalized environment
+ * (VMV_ERR_NOT_FINALIZED); an environment of another device (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out
+ * untouched.  n_roadmaps == 0 is VMV_OK with an empty handle.  Synchronous, host buffers, on the default stream; repeated
+ * environment handles are allowed. */
+typedef struct vmv_roadmaps vmv_roadmaps;
+typedef struct
+{
+    uint32_t n_samples, k;
+    float radius;                /* neighbours lie within this distance; +inf = no cut */
+} vmv_roadmap_settings;
+typedef struct
+{
+    uint32_t k_connect;          /* connections tried per endpoint, 1 .. 32 */
+    float radius;                /* they lie within this distance; +inf = no cut */
+} vmv_roadmap_query_settings;
+int vmv_roadmaps_build(int robot, const vmv_env *const *envs, size_t n_roadmaps, const uint64_t *halton_skips,
+                       const float *samples, const vmv_roadmap_settings *settings, vmv_roadmaps **out);
+/* n_queries queries in one call, query q from starts[q] to goals[q] ([n_queries][dimension] host floats) against roadmap
+ * roadmap_of_query[q] (NULL = all 0).  A fixed launch sequence with no host synchronisation before the results: all
+ * endpoints through ONE vmv_validate_batch_multi call (the host groups the queries by roadmap with a stable counting sort,
+ * one segment per roadmap that has queries, and un-permutes the results); a connect kernel; 1 + 2 * k_connect edge
+ * questions per query through ONE vmv_validate_motion_batch_multi call; a shortest-path kernel (one workgroup per query,
+ * over the roadmap's shared edge list plus the query's own connection edges); the paths gathered.
+ * Per query, bit-defined: graph ids 0 = start, 1 = goal, 2 + i = sample i.  An endpoint that is not finite or
+ *   not valid: VMV_PLAN_INVALID_ENDPOINT, nothing is asked.  conn(e), e = start, goal: the k_connect valid samples u with
+ *   0 < d2(e, u) <= radius^2 first in the order (d2, id).  Questions, in this order: start -> goal; start -> u over
+ *   conn(start); goal -> u over conn(goal).  The direct edge valid: VMV_PLAN_SOLVED, path = [start, goal], cost =
+ *   sqrtf(d2(start, goal)), iterations 0.  Else iterations = n_samples; over the roadmap's valid edges plus the valid
+ *   connection edges g[0] = 0, g = the least fixpoint of g[v] = min fl(g[u] + w), parent(v) = the lowest id u with an edge
+ *   {u, v}, fl(g[u] + w) == g[v] and g[u] < g[v]; g[1] finite and the walk from 1 reaching 0: VMV_PLAN_SOLVED, cost =
+ *   g[1]; else VMV_PLAN_NO_PATH.
+ * A query's result depends on its endpoints, its roadmap and the settings alone.  The result is a vmv_plans:
+ * vmv_plans_summary reports sizes2 = [valid connection edges of the start, of the goal], rounds = validation calls that
+ * carried a question (2; 1 if no query has both endpoints valid: the edge call then carries null questions only),
+ * questions = the sum of the queries' questions; vmv_plans_paths and vmv_plans_destroy work as for vmv_rrtc_multi,
+ * vmv_plans_query_summary gives the costs, vmv_plans_roadmap_* refuse it.  Each query owns a block of 1 + 2 * k_connect
+ * question slots; unused slots, and every slot of a query with an invalid endpoint, carry a null question (an endpoint to
+ * itself) that is neither counted nor read.
+ * Device-free checks first: NULL roadmaps / starts / goals / settings / out, k_connect outside 1 .. 32, radius NaN or <= 0,
+ * n_queries * (1 + 2 * k_connect) >= 2^31, a roadmap_of_query entry >= the handle's roadmap count
+ * (VMV_ERR_INVALID_ARGUMENT).  A call that fails leaves *out untouched.  n_queries == 0 is VMV_OK with an empty result. */
+int vmv_roadmaps_query(const vmv_roadmaps *roadmaps, size_t n_queries, const uint32_t *roadmap_of_query, const float *starts,
+                       const float *goals, const vmv_roadmap_query_settings *settings, vmv_plans **out);
+/* Per query of a vmv_roadmaps_query result (arrays of n_queries, either may be NULL): cost (+inf = unsolved) and
+ * edges_checked = 1 + |conn(start)| + |conn(goal)| (0 for VMV_PLAN_INVALID_ENDPOINT).  VMV_ERR_INVALID_ARGUMENT on plans
+ * of another origin. */
+int vmv_plans_query_summary(const vmv_plans *plans, float *costs, uint32_t *edges_checked);
+/* Per roadmap (arrays of the handle's roadmap count, any may be NULL): valid samples, candidate edges, valid edges. */
+int vmv_roadmaps_summary(const vmv_roadmaps *roadmaps, uint32_t *valid_vertices, uint32_t *candidate_edges,
+                         uint32_t *valid_edges);
+/* roadmap r's samples ([n_samples][dimension]) and valid[i] of each (either may be NULL), copied from the device */
+int vmv_roadmaps_vertices(const vmv_roadmaps *roadmaps, size_t r, float *samples, uint8_t *valid);
+/* roadmap r's candidate edges in candidate order, as vmv_plans_roadmap_edges gives a problem's: pairs2 [n][2] sample ids
+ * a < b, valid [n]; VMV_ERR_CAPACITY if capacity (in edges) is too small (nothing is written but *n) */
+int vmv_roadmaps_edges(const vmv_roadmaps *roadmaps, size_t r, uint32_t *pairs2, uint8_t *valid, size_t capacity, size_t *n);
+int vmv_roadmaps_destroy(vmv_roadmaps *roadmaps);
+
 /* ---- lockstep simplifier: many independent paths in one call -------------------------------------------- */
 /* simplify() (planning/simplify.hh:192-260) with the SHORTCUT and BSPLINE routines for n_paths paths at once: path p is
  * points[offsets[p] .. offsets[p + 1]) ([offsets[n_paths]][dimension] host floats, offsets in waypoints, offsets[0] = 0)

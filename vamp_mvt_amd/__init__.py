@@ -281,12 +281,14 @@ class Environment:
         self._ops = []
         self._handle = None
         self._device = None
+        self._generation = 0  # handles destroyed so far: what holds a handle beyond one call (DeviceRoadmaps) compares it
 
     # -- mutation ------------------------------------------------------------------------------------------
     def _dirty(self):
         if self._handle is not None:
             lib.vmv_env_destroy(self._handle)
             self._handle = None
+            self._generation += 1
 
     def add_sphere(self, sphere: Sphere):
         self._ops.append(("sphere", (sphere.x, sphere.y, sphere.z, sphere.r)))
@@ -909,6 +911,118 @@ class _Robot(types.ModuleType):
         finally:
             lib.vmv_plans_destroy(plans)
         return out
+
+    def roadmaps_build_raw(self, environments, settings, skips=None, samples=None):
+        """vmv_roadmaps_build: one device-resident roadmap per environment (None = the empty environment) over the Halton
+        samples skips[r] + 1, ... (None = all 0) or over `samples` ([n][n_samples][dim], or [n_samples][dim] for every
+        roadmap).  settings: n_samples, k, radius.  -> (the handle, the Environment objects it refers to): the caller
+        keeps both and ends with roadmaps_destroy_raw.  planning.build_roadmaps is the caller-facing form.  Every argument
+        is checked before any library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        n = len(environments)
+        ns, k, radius = int(settings.n_samples), int(settings.k), float(settings.radius)
+        if ns % 64 != 0 or not 64 <= ns <= 8128:
+            raise ValueError("n_samples must be a multiple of 64 from 64 to 8,128")
+        if not 1 <= k <= 16:
+            raise ValueError("k must be from 1 to 16")
+        if not radius > 0:
+            raise ValueError("radius must be positive (inf = no cut)")
+        if n * ns * k >= 2 ** 31:
+            raise ValueError("n_roadmaps * n_samples * k must stay below 2^31")
+        sk = sm = None
+        if samples is not None:
+            sm = _f32(samples)
+            if sm.shape == (ns, self._dim):
+                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
+            if sm.shape != (n, ns, self._dim):
+                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
+        if skips is not None:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per roadmap, got shape {sk.shape} for {n} roadmaps")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
+                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        cs = _lib.RoadmapSettings(ns, k, radius)
+        envs, handles = _env_handles(environments)
+        handle = ctypes.c_void_p()
+        check(lib.vmv_roadmaps_build(self._id, handles, n, None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
+                                     None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(handle)), "vmv_roadmaps_build")
+        return handle, envs
+
+    def roadmaps_query_raw(self, handle, n_roadmaps, starts, goals, index=None, settings=None):
+        """vmv_roadmaps_query: query q from starts[q] to goals[q] against roadmap index[q] (None = all 0) of a handle of
+        n_roadmaps roadmaps.  settings: k_connect, radius.  -> dict of per-query numpy arrays (status, iterations, sizes
+        [n][2] = valid connection edges of the start and of the goal, path_lengths, costs, edges_checked), the packed
+        waypoints (paths [sum(path_lengths)][dim]) and the totals rounds and questions.  DeviceRoadmaps.query is the
+        caller-facing form.  Every argument is checked before any library call."""
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
+            raise TypeError(f"expected two [n][{self._dim}] arrays")
+        n = a.shape[0]
+        kc, radius = int(settings.k_connect), float(settings.radius)
+        if not 1 <= kc <= 32:
+            raise ValueError("k_connect must be from 1 to 32")
+        if not radius > 0:
+            raise ValueError("radius must be positive (inf = no cut)")
+        if n * (1 + 2 * kc) >= 2 ** 31:
+            raise ValueError("n_queries * (1 + 2 * k_connect) must stay below 2^31")
+        ix = None
+        if index is not None:
+            ix = np.asarray(index)
+            if ix.shape != (n,):
+                raise ValueError(f"expected one roadmap index per query, got shape {ix.shape} for {n} queries")
+            if ix.size and (not np.issubdtype(ix.dtype, np.integer) or (ix < 0).any() or int(ix.max()) >= n_roadmaps):
+                raise ValueError(f"roadmap indices must be integers from 0 to {n_roadmaps - 1}")
+            ix = np.ascontiguousarray(ix, np.uint32)
+        elif n and n_roadmaps < 1:
+            raise ValueError("the handle holds no roadmap")
+        cs = _lib.RoadmapQuerySettings(kc, radius)
+        plans = ctypes.c_void_p()
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        check(lib.vmv_roadmaps_query(handle, n, None if ix is None else ix.ctypes.data_as(_lib.c_u32_p), _fp(a), _fp(b),
+                                     ctypes.byref(cs), ctypes.byref(plans)), "vmv_roadmaps_query")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(u8), iterations.ctypes.data_as(_lib.c_u32_p),
+                                        sizes.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
+                                        ctypes.byref(rounds), ctypes.byref(questions)), "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+            costs, asked = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+            check(lib.vmv_plans_query_summary(plans, _fp(costs), asked.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_query_summary")
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, costs=costs,
+                    edges_checked=asked, rounds=int(rounds.value), questions=int(questions.value))
+
+    def roadmaps_summary_raw(self, handle, n_roadmaps):
+        """vmv_roadmaps_summary -> (valid samples, candidate edges, valid edges), uint32[n_roadmaps] each"""
+        out = [np.zeros(n_roadmaps, np.uint32) for _ in range(3)]
+        check(lib.vmv_roadmaps_summary(handle, *[x.ctypes.data_as(_lib.c_u32_p) for x in out]), "vmv_roadmaps_summary")
+        return tuple(out)
+
+    def roadmaps_roadmap_raw(self, handle, r, n_samples):
+        """vmv_roadmaps_vertices and vmv_roadmaps_edges of roadmap r -> (samples [n_samples][dim], their flags bool[n_samples],
+        candidate pairs uint32[m][2] of sample ids, their flags bool[m])"""
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        samples, vertex = np.zeros((n_samples, self._dim), np.float32), np.zeros(n_samples, np.uint8)
+        check(lib.vmv_roadmaps_vertices(handle, r, _fp(samples), vertex.ctypes.data_as(u8)), "vmv_roadmaps_vertices")
+        m = ctypes.c_size_t(0)
+        check(lib.vmv_roadmaps_edges(handle, r, None, None, 0, ctypes.byref(m)), "vmv_roadmaps_edges")
+        pairs, flags = np.zeros((m.value, 2), np.uint32), np.zeros(m.value, np.uint8)
+        check(lib.vmv_roadmaps_edges(handle, r, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(u8), m.value, None),
+              "vmv_roadmaps_edges")
+        return samples, vertex.astype(bool), pairs, flags.astype(bool)
+
+    def roadmaps_destroy_raw(self, handle):
+        """vmv_roadmaps_destroy"""
+        check(lib.vmv_roadmaps_destroy(handle), "vmv_roadmaps_destroy")
 
     def fcit_multi_raw(self, starts, goals, environments, settings, skips=None, samples=None):
         """vmv_fcit_multi: a lazy A* search of the complete graph over each problem's valid samples, the arguments those

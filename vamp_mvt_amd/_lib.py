@@ -36,6 +36,16 @@ class PrmSettings(ctypes.Structure):
                 ("keep_roadmaps", ctypes.c_int)]
 
 
+class RoadmapSettings(ctypes.Structure):
+    """vmv_roadmap_settings"""
+    _fields_ = [("n_samples", ctypes.c_uint32), ("k", ctypes.c_uint32), ("radius", ctypes.c_float)]
+
+
+class RoadmapQuerySettings(ctypes.Structure):
+    """vmv_roadmap_query_settings"""
+    _fields_ = [("k_connect", ctypes.c_uint32), ("radius", ctypes.c_float)]
+
+
 class FcitSettings(ctypes.Structure):
     """vmv_fcit_settings"""
     _fields_ = [("n_samples", ctypes.c_uint32), ("max_iterations", ctypes.c_uint32), ("questions_per_round", ctypes.c_uint32),
@@ -161,6 +171,13 @@ def _load():
         "vmv_plans_roadmap_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p, c_float_p]),
         "vmv_plans_roadmap_vertices": (I, [V, S, ctypes.POINTER(ctypes.c_uint8)]),
         "vmv_plans_roadmap_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
+        "vmv_roadmaps_build": (I, [I, ctypes.POINTER(V), S, c_u64_p, c_float_p, ctypes.POINTER(RoadmapSettings), ctypes.POINTER(V)]),
+        "vmv_roadmaps_query": (I, [V, S, c_u32_p, c_float_p, c_float_p, ctypes.POINTER(RoadmapQuerySettings), ctypes.POINTER(V)]),
+        "vmv_plans_query_summary": (I, [V, c_float_p, c_u32_p]),
+        "vmv_roadmaps_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p]),
+        "vmv_roadmaps_vertices": (I, [V, S, c_float_p, ctypes.POINTER(ctypes.c_uint8)]),
+        "vmv_roadmaps_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
+        "vmv_roadmaps_destroy": (I, [V]),
         "vmv_aorrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
                                  ctypes.POINTER(V)]),
         "vmv_plans_costs": (I, [V, c_float_p, c_float_p, c_u32_p, c_u32_p]),

@@ -420,6 +420,10 @@ def install(robot):
             out.append(res)
         return out
 
+    def build_roadmaps(environments, settings=None, skips=None, samples=None):
+        """planning.build_roadmaps with this robot -> planning.DeviceRoadmaps (`settings`: a planning.RoadmapsSettings)"""
+        return planning.build_roadmaps(robot, environments, settings, skips, samples)
+
     def fcit_multi(starts, goals, environments, settings, skips=None, samples=None):
         """planning.fcit_multi with this robot and the reference-shaped FCITSettings: n_samples = min(max_samples, 2048)
         rounded down to a multiple of 64 and at least 64, max_iterations as given (at least 1) -> list[PlanningResult]
@@ -490,7 +494,7 @@ def install(robot):
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
-    robot.fcit_multi = fcit_multi
+    robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 
 

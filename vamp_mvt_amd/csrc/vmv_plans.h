@@ -1,4 +1,4 @@
-// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi, vmv_aorrtc_multi, vmv_fcit_multi): vmv_plans_summary,
+// vmv_plans.h — the result object of the planning calls (vmv_rrtc_multi, vmv_prm_multi, vmv_aorrtc_multi, vmv_fcit_multi, vmv_roadmaps_query): vmv_plans_summary,
 // vmv_plans_paths and vmv_plans_destroy (vmv_rrtc_multi.hip) read the first block whichever call made it.
 #pragma once
 
@@ -34,4 +34,7 @@ struct vmv_plans
     // vmv_fcit_multi only (vmv_plans_fcit_summary; n_samples and costs as above)
     bool fcit = false;
     std::vector<uint32_t> known_valid;  // [n] edges the walk found valid
+
+    // vmv_roadmaps_query only (vmv_plans_query_summary; costs as above, candidate_edges = the questions a query asked)
+    bool query = false;
 };

@@ -20,6 +20,7 @@
 
 #include "vmv_lockstep.h"
 #include "vmv_plans.h"
+#include "vmv_prm_common.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -30,17 +31,6 @@ namespace vmv
 {
     namespace
     {
-        constexpr uint32_t kPrmBlock = 256;
-        constexpr uint32_t kPrmKMax = 16;
-        constexpr uint32_t kPrmMaxDim = 16;
-        constexpr uint32_t kPrmMinSamples = 64, kPrmMaxSamples = 8128;
-        constexpr uint32_t kPrmMaxVertices = kPrmMaxSamples + 2;
-        constexpr uint32_t kPrmSsspBlock = 512;
-        constexpr uint32_t kPrmLaunchBlocks = 32768;  // workgroups per launch of the per-problem kernels: a larger call
-                                                      // is launched chunk by chunk of problems (grids stay far below 2^32 threads)
-        constexpr uint32_t kNone = 0xffffffffu;
-        constexpr uint32_t kInfBits = 0x7f800000u;
-
         struct PrmParams
         {
             uint32_t dim, n_samples, V, k, n_problems;
@@ -76,23 +66,9 @@ namespace vmv
         {
             return v < 2u ? (size_t) P.n_problems * P.n_samples + 2u * (size_t) p + v : (size_t) p * P.n_samples + (v - 2u);
         }
-        __device__ __forceinline__ bool bit_at(const uint64_t *__restrict__ bits, size_t i)
-        {
-            return (bits[i >> 6] >> (i & 63u)) & 1ull;
-        }
         __device__ __forceinline__ bool ends_valid(const PrmParams &P, const uint64_t *__restrict__ vbits, uint32_t p)
         {
             return bit_at(vbits, vertex_at(P, p, 0)) && bit_at(vbits, vertex_at(P, p, 1));
-        }
-        __device__ __forceinline__ float dist2(const float *__restrict__ a, const float *__restrict__ b, uint32_t dim)
-        {
-            float sum = 0.f;
-            for (uint32_t j = 0; j < dim; ++j)
-            {
-                const float df = a[j] - b[j];
-                sum = sum + df * df;
-            }
-            return sum;
         }
 
         __global__ __launch_bounds__(kPrmBlock) void prm_halton_kernel(const PrmParams P, const PrmArrays D)
@@ -108,11 +84,7 @@ namespace vmv
 
         // One lane per query vertex, a workgroup within one problem (problem p0 + blockIdx.x / tiles, tile blockIdx.x % tiles).  The candidates go through LDS a tile
         // of kPrmBlock at a time: every lane reads the same candidate (a broadcast read) and its validity flag is the
-        // same in the whole wave.  The k best sit in registers as a sorted list of KMAX entries, fully unrolled; the
-        // list's first KMAX - k entries hold the key 0, below every real key (d2 > 0), so they never move and the k-th
-        // best is always the last entry: one strict `<` against it rejects most candidates.  Keys are the bits of d2
-        // (positive floats order as unsigned integers; +inf included); an empty entry holds 0xffffffff.  Candidates come
-        // in ascending id order, so among equal keys the strict `<` keeps the lower id.
+        // same in the whole wave.  The k best sit in the register list of vmv_prm_common.h.
         template <int DIM>
         __global__ __launch_bounds__(kPrmBlock) void prm_knn_kernel(const PrmParams P, const PrmArrays D, const uint32_t p0, const uint32_t tiles)
         {
@@ -125,8 +97,7 @@ namespace vmv
 #pragma unroll
             for (int j = 0; j < DIM; ++j) q[j] = (query && (uint32_t) j < dim) ? D.verts[vertex_at(P, p, v) * dim + j] : 0.f;
             uint32_t bk[kPrmKMax], bi[kPrmKMax];
-#pragma unroll
-            for (uint32_t s = 0; s < kPrmKMax; ++s) bk[s] = s < kPrmKMax - P.k ? 0u : kNone, bi[s] = kNone;
+            knn_list_init(bk, bi, P.k);
             const uint32_t r2_bits = __float_as_uint(P.r2);
 
             for (uint32_t base = 0; base < V; base += kPrmBlock)  // <= ceil(V / kPrmBlock) tiles
@@ -154,15 +125,7 @@ namespace vmv
                         const uint32_t key = __float_as_uint(sum);  // valid vertices are finite: sum is in [+0, +inf]
                         if (!(key < bk[kPrmKMax - 1])) continue;
                         if (key == 0u || key > r2_bits || u == v || (u < 2u && v < 2u)) continue;
-#pragma unroll
-                        for (int s = kPrmKMax - 1; s >= 1; --s)
-                        {
-                            const bool shift = key < bk[s - 1];
-                            const bool here = !shift && key < bk[s];
-                            bi[s] = shift ? bi[s - 1] : (here ? u : bi[s]);
-                            bk[s] = shift ? bk[s - 1] : (here ? key : bk[s]);
-                        }
-                        if (key < bk[0]) bk[0] = key, bi[0] = u;
+                        knn_list_insert(bk, bi, key, u);
                     }
                 __syncthreads();  // the tile is rewritten
             }
@@ -173,15 +136,6 @@ namespace vmv
                 for (uint32_t s = 0; s < kPrmKMax; ++s)
                     if (s >= kPrmKMax - P.k) out[s - (kPrmKMax - P.k)] = bi[s];
             }
-        }
-
-        // slot s of vertex v is an edge of the list iff v < u, or v is not among u's neighbours
-        __device__ __forceinline__ bool owns(const uint32_t *__restrict__ nbr_p, uint32_t k, uint32_t v, uint32_t u)
-        {
-            if (v < u) return true;
-            bool found = false;
-            for (uint32_t t = 0; t < k; ++t) found |= nbr_p[(size_t) u * k + t] == v;
-            return !found;
         }
 
         // counts[p * V + v] = the candidate edges vertex v of problem p contributes (vertex 0: the edge (0, 1) as well);
@@ -243,10 +197,9 @@ namespace vmv
             }
         }
 
-        // One workgroup per problem.  g lives in LDS as the bits of non-negative floats, which order as unsigned integers:
-        // g[v] = min over valid edges {u, v} of fl(g[u] + w) is reached by edge-parallel sweeps with atomicMin in both
-        // directions; fl(a + w) is monotone in a and >= a, so the least fixpoint is the same whatever the order of the
-        // relaxations, and V sweeps bound it.  Then the parent walk from the goal: per step the lowest id u with a valid
+        // One workgroup per problem.  g lives in LDS; sweeps of sssp_relax over the valid edges reach the least fixpoint
+        // whatever the order of the relaxations, and V sweeps bound it.
+        // Then the parent walk from the goal: per step the lowest id u with a valid
         // edge {u, cur}, fl(g[u] + w) == g[cur] and g[u] < g[cur] (a workgroup min-reduction), at most V steps.
         __global__ __launch_bounds__(kPrmSsspBlock) void prm_sssp_kernel(const PrmParams P, const PrmArrays D, const uint32_t p0)
         {
@@ -287,20 +240,7 @@ namespace vmv
                     for (uint32_t e = e0 + tid; e < e1; e += kPrmSsspBlock)
                     {
                         if (!bit_at(D.ebits, e)) continue;
-                        const float w = D.weights[e];
-                        if (!(w < INFINITY)) continue;  // an overflowed d2 relaxes nothing
-                        const uint32_t a = D.pairs[2 * (size_t) e], b = D.pairs[2 * (size_t) e + 1];
-                        const uint32_t ga = g[a], gb = g[b];
-                        if (ga < kInfBits)
-                        {
-                            const uint32_t c = __float_as_uint(__uint_as_float(ga) + w);
-                            if (c < gb) changed |= atomicMin(&g[b], c) > c;
-                        }
-                        if (gb < kInfBits)
-                        {
-                            const uint32_t c = __float_as_uint(__uint_as_float(gb) + w);
-                            if (c < ga) changed |= atomicMin(&g[a], c) > c;
-                        }
+                        changed |= sssp_relax(g, D.pairs[2 * (size_t) e], D.pairs[2 * (size_t) e + 1], D.weights[e]);  // an overflowed d2 relaxes nothing
                     }
                     if (!__syncthreads_or(changed)) break;
                 }
@@ -318,10 +258,8 @@ namespace vmv
                             if (!bit_at(D.ebits, e)) continue;
                             const uint32_t a = D.pairs[2 * (size_t) e], b = D.pairs[2 * (size_t) e + 1];
                             if (a != cur && b != cur) continue;
-                            const uint32_t u = a == cur ? b : a, gu = g[u];
-                            const float w = D.weights[e];
-                            if (!(w < INFINITY) || !(gu < gc)) continue;
-                            if (__float_as_uint(__uint_as_float(gu) + w) == gc && u < best) best = u;
+                            const uint32_t u = a == cur ? b : a;
+                            if (u < best && sssp_is_parent(g, gc, u, D.weights[e])) best = u;
                         }
                         if (best != kNone) atomicMin(&s_best, best);
                         __syncthreads();
@@ -360,17 +298,6 @@ namespace vmv
                 for (uint32_t j = 0; j < P.dim; ++j) out[(size_t) s * P.dim + j] = q[j];
             }
         }
-
-#define VMV_PRM_LAUNCHED(name)                                \
-    do                                                        \
-    {                                                         \
-        const hipError_t e_ = hipGetLastError();              \
-        if (e_ != hipSuccess)                                 \
-        {                                                     \
-            (void) hipDeviceSynchronize();                    \
-            return hip_status(e_, name);                      \
-        }                                                     \
-    } while (0)
 
         // The caller has checked every argument, n > 0, and every environment is finalized on the current device with
         // the robot's part built.

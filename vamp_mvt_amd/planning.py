@@ -110,6 +110,23 @@ class PRMMultiSettings:
 
 
 @dataclass
+class RoadmapsSettings:
+    """settings of `build_roadmaps`: n_samples samples per roadmap (a multiple of 64 from 64 to 8,128) and the k nearest
+    neighbours per sample (1 .. 16) within `radius` (inf = no cut)"""
+    n_samples: int = 2048
+    k: int = 8
+    radius: float = float("inf")
+
+
+@dataclass
+class RoadmapQuerySettings:
+    """settings of `DeviceRoadmaps.query`: the k_connect nearest valid samples tried per endpoint (1 .. 32, independent of
+    the roadmap's k) within `radius` (inf = no cut)"""
+    k_connect: int = 8
+    radius: float = float("inf")
+
+
+@dataclass
 class FCITMultiSettings:
     """settings of `fcit_multi`: n_samples samples per problem (a multiple of 64 from 64 to 2,048), max_iterations
     searches per problem, questions_per_round (edge questions per problem per round, 1 .. 32: the first is the one the
@@ -337,6 +354,95 @@ def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | N
     if out:  # the call's validation calls ride on the first result
         out[0].validity_calls = raw["rounds"]
     return out
+
+
+class DeviceRoadmaps:
+    """Roadmaps kept on the device (`build_roadmaps`): `len()` roadmaps, roadmap r built in environments[r].  Holds the
+    library's handle and the Environment objects it refers to, so that no environment is collected before its roadmaps;
+    the handle is destroyed by `close()` (or `with`), at the latest when the object is collected.  A roadmap answers for
+    its environment as it was when the roadmap was built: an Environment changed since (or moved to another device) has
+    given up the handle the roadmap refers to, and `query` then raises ValueError."""
+
+    def __init__(self, robot, handle, environments, settings):
+        self._robot, self._handle, self._environments, self.settings = robot, handle, environments, settings
+        self._generations = [e._generation for e in environments]
+
+    def __len__(self):
+        return len(self._environments)
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the roadmaps are closed")
+        return self._handle
+
+    def close(self):
+        handle, self._handle = self._handle, None
+        if handle is not None:
+            self._robot.roadmaps_destroy_raw(handle)
+        self._environments = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # at interpreter exit the library may be gone first
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def summary(self):
+        """-> (valid samples, candidate edges, valid edges) per roadmap, uint32 arrays"""
+        return self._robot.roadmaps_summary_raw(self._open(), len(self))
+
+    def roadmap(self, r):
+        """roadmap r as kept on the device -> (samples [n_samples][dim], their flags, candidate pairs [m][2] of sample
+        ids a < b in candidate order, their flags)"""
+        if not 0 <= int(r) < len(self):
+            raise IndexError(f"roadmap {r} of {len(self)}")
+        return self._robot.roadmaps_roadmap_raw(self._open(), int(r), int(self.settings.n_samples))
+
+    def query(self, starts, goals, index=None, settings: RoadmapQuerySettings | None = None):
+        """Query q from starts[q] to goals[q] ([n][dim] arrays) against roadmap index[q] (None = roadmap 0 for all).
+        -> list[PlanningResult], one per query: `path` (waypoints, empty if unsolved), `cost` (inf if unsolved),
+        `iterations` (n_samples where the roadmap was searched, 0 for a direct solution or an invalid endpoint), `size` =
+        [valid connection edges of the start, of the goal], `edges_checked` = 1 + the connections tried for both endpoints
+        and `status` ("solved", "no_path", "invalid_endpoint").
+
+        A fixed sequence of launches whatever the queries are: all endpoints in ONE validate_batch_multi call, the
+        k_connect nearest valid samples of every endpoint, 1 + 2 k_connect edge questions per query in ONE
+        validate_motion_batch_multi call, the shortest path per query over the roadmap's edges and its own connection
+        edges.  Defined bit for bit, as `prm_multi` is; a query's result depends on its endpoints, its
+        roadmap and the settings alone."""
+        s = settings or RoadmapQuerySettings()
+        handle = self._open()
+        stale = [r for r, (e, g) in enumerate(zip(self._environments, self._generations)) if e._generation != g]
+        if stale:
+            raise ValueError(f"the environments of roadmaps {stale} changed after the roadmaps were built")
+        raw = self._robot.roadmaps_query_raw(handle, len(self), starts, goals, index, s)
+        ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+        out = []
+        for q in range(len(ends)):
+            pts = raw["paths"][ends[q] - int(raw["path_lengths"][q]):ends[q]]
+            out.append(PlanningResult(path=[p.copy() for p in pts], iterations=int(raw["iterations"][q]),
+                                      size=[int(raw["sizes"][q, 0]), int(raw["sizes"][q, 1])], cost=float(raw["costs"][q]),
+                                      edges_checked=int(raw["edges_checked"][q]), status=PLAN_STATUS[int(raw["status"][q])]))
+        if out:  # the call's validation calls ride on the first result
+            out[0].validity_calls = raw["rounds"]
+        return out
+
+
+def build_roadmaps(robot, environments, settings: RoadmapsSettings | None = None, skips=None, samples=None) -> DeviceRoadmaps:
+    """One roadmap per environment (None = the empty environment), built in one call and kept on the device: over the
+    Halton samples skips[r] + 1, ... (None = 0 for all) or over `samples` ([n][n_samples][dim]; [n_samples][dim] serves
+    every roadmap).  All samples go through ONE validate_batch_multi call and all candidate edges through ONE
+    validate_motion_batch_multi call, as in `prm_multi`, but no endpoint takes part: the cost is paid once per scene and
+    `DeviceRoadmaps.query` answers any number of (start, goal) pairs against it."""
+    s = settings or RoadmapsSettings()
+    handle, envs = robot.roadmaps_build_raw(environments, s, skips, samples)
+    return DeviceRoadmaps(robot, handle, envs, s)
 
 
 def fcit_multi(robot, starts, goals, environments, settings: FCITMultiSettings | None = None, skips=None, samples=None):
