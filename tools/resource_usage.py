@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Developer tool: per-kernel register / spill / occupancy report of the robot translation units
-(hipcc -Rpass-analysis=kernel-resource-usage).  usage: tools/resource_usage.py [robot ...] [-Dflag ...]"""
+"""Developer tool: per-kernel register / spill / occupancy report of the robot translation units, or of any other
+translation unit of csrc/ (hipcc -Rpass-analysis=kernel-resource-usage).
+usage: tools/resource_usage.py [robot | file.hip ...] [-Dflag ...]"""
 import os
 import re
 import subprocess
@@ -15,8 +16,14 @@ from __graft_entry__ import CSRC, HIPFLAGS  # noqa: E402
 EXTRA = [a for a in sys.argv[1:] if a.startswith("-")]
 
 
+def demangled(name):
+    r = subprocess.run(["c++filt", "-p", name], capture_output=True, text=True)  # -p: without the parameter types
+    return re.sub(r"^void |vmv::|\(anonymous namespace\)::", "", r.stdout.strip()) if r.returncode == 0 and r.stdout.strip() else name
+
+
 def report(robot):
-    src = os.path.join(CSRC, "gen", f"tu_{robot}.hip")
+    plain = robot.endswith(".hip")  # a translation unit of csrc/ by its file name
+    src = os.path.join(CSRC, os.path.basename(robot)) if plain else os.path.join(CSRC, "gen", f"tu_{robot}.hip")
     r = subprocess.run(["hipcc", *HIPFLAGS, *EXTRA, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"],
                        capture_output=True, text=True)
     rows, cur = [], None
@@ -26,7 +33,7 @@ def report(robot):
         if not m:
             continue
         if m.group(1) == "Function Name":
-            cur = {"name": re.sub(r"^_ZN3vmv\d+[a-z0-9]+?\d+|E[PKjmS_\d\w]*$", "", m.group(2))}
+            cur = {"name": demangled(m.group(2)) if plain else re.sub(r"^_ZN3vmv\d+[a-z0-9]+?\d+|E[PKjmS_\d\w]*$", "", m.group(2))}
             second = re.search(r"ILi\d+ELb([01])E", m.group(2))  # <V, PAIRS> instances of the configuration kernels
             if second:
                 cur["name"] += "_Lb" + second.group(1)

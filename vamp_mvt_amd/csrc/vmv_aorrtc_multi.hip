@@ -23,34 +23,36 @@
 //                    r1 = max_cost * 0.5, rc = sqrtf(max(max_cost max_cost - dmin dmin, 0)) * 0.5,
 //                    y[j] = (g[j] / norm) * (j == 0 ? r1 : rc), k = (2 * sum v[j] y[j]) / vv, t = centre + (y - v * k);
 //                    out of bounds unless lower[j] <= t[j] <= fl(lower[j] + span[j]) for every joint (NaN: out).
-//   aox_nearest(T, t, c)  over the counted nodes i of T: d_i = sqrtf(sum (node_i[j] - t[j])^2), admissible iff
+//   nearest(T, t, c)      over the counted nodes i of T: d_i = sqrtf(sum (node_i[j] - t[j])^2), admissible iff
 //                    !(cost_i > 0) || !(c < cost_i + d_i), key_i = sqrtf(d_i d_i + (cost_i - c)(cost_i - c)); the FIRST
 //                    index with the least key among the admissible nodes, and its d_i.  An associative argmin: the
-//                    workgroup's lanes stride over the tree.
+//                    workgroup's lanes stride over the tree (nearest<true> of vmv_two_trees.h with this key).
 //   one search       fresh trees (roots cost 0, A = the start tree); while iterations < budget && |A| + |B| < max_samples:
 //                    ++iterations, the balance swap of vmv_rrtc_multi; t = PHS sample, out of bounds: continue;
 //                    g = dist(t, rootA), f = g + dist(t, rootB), c_rand = U * max(max_cost - f, 0) + g;
-//                    (ni, d) = aox_nearest(A, t, c_rand), !(d > 0): continue; new = near + (t - near) * (min(d, R) / d);
+//                    (ni, d) = nearest(A, t, c_rand), !(d > 0): continue; new = near + (t - near) * (min(d, R) / d);
 //                    ask near -> new, invalid: continue; new_cost = cost[ni] + dist(new, near);
 //                    cost_bound_resample: g2 = dist(new, rootA), up to max_cost_bound_resamples times:
-//                    cr = max(new_cost - g2, 0), draw U, (mi, md) = aox_nearest(A, new, U * cr + g2) with `new` not yet
+//                    cr = max(new_cost - g2, 0), draw U, (mi, md) = nearest(A, new, U * cr + g2) with `new` not yet
 //                    counted; stop if mi == ni or !(cost[mi] + md < new_cost) or cr == 0; ask A[mi] -> new: valid:
 //                    ni = mi, new_cost = cost[mi] + md; invalid: stop;
-//                    add new (parent ni, cost new_cost); (bi, bd) = aox_nearest(B, new, max_cost - new_cost);
+//                    add new (parent ni, cost new_cost); (bi, bd) = nearest(B, new, max_cost - new_cost);
 //                    !((new_cost + bd) + cost[bi] < max_cost): continue; the connect march of vmv_rrtc_multi from B[bi]
-//                    towards new, every added node with cost[prev] + dist(w, from); connected: solved, the path traced as
-//                    vmv_rrtc_multi traces it.  Unsolved: MAX_ITERATIONS if the budget was reached, else MAX_SAMPLES.
+//                    towards new, every added node with cost[prev] + dist(w, from); connected: solved, the path traced by
+//                    vmv_rrtc_multi's trace_path (vmv_two_trees.h).  Unsolved: MAX_ITERATIONS if the budget was reached, else MAX_SAMPLES.
 //
 // aox_step_kernel: one 256-thread workgroup per unfinished problem; the phases are extend, re-parent (A[mi] -> new is in
 // flight while `new` sits uncounted in A's next slot) and march.  One lane draws the sample and shares it through LDS;
 // every branch is taken by the whole workgroup.  Iterations that ask nothing loop inside the kernel, at most kAoxSpinCap
 // per launch (then a null question; the state carries on, so the cap changes no result).  A problem's two trees share one
-// pool of max_samples nodes, the start tree from the front, the goal tree from the back, with parent and cost arrays.
+// pool of max_samples nodes, the start tree from the front, the goal tree from the back (vmv_two_trees.h), with parent and
+// cost arrays.
 // Every store is a plain vector store by the owning workgroup; no atomics.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
 #include "vmv_plans.h"
+#include "vmv_two_trees.h"
 
 #include <cmath>
 #include <cstring>
@@ -60,13 +62,10 @@ namespace vmv
 {
     namespace
     {
-        constexpr uint32_t kAoxBlock = 256;
-        constexpr uint32_t kAoxWaves = kAoxBlock / kWave;
-        constexpr uint32_t kAoxMaxDim = 16;
+        constexpr uint32_t kAoxBlock = kTreeBlock;
         constexpr uint32_t kAoxDefaultCheckEvery = 16;
         constexpr uint32_t kAoxSpinCap = 64;        // iterations without a question per launch
         constexpr uint32_t kAoxMaxResamples = 64;   // max_cost_bound_resamples the call accepts
-        constexpr uint32_t kAoxNone = 0xffffffffu;
 
         enum : uint32_t
         {
@@ -96,7 +95,7 @@ namespace vmv
         {
             uint32_t dim, max_samples, balance, resample, max_resamples;
             float range, tree_ratio;
-            float lower[kAoxMaxDim], span[kAoxMaxDim];
+            float lower[kPlanMaxDim], span[kPlanMaxDim];
         };
 
         struct AoxArrays
@@ -117,35 +116,9 @@ namespace vmv
 
         struct PhsFrame
         {
-            float centre[kAoxMaxDim], v[kAoxMaxDim];
+            float centre[kPlanMaxDim], v[kPlanMaxDim];
             float dmin, vv;
         };
-
-        __device__ __forceinline__ size_t aox_at(uint32_t side, uint32_t i, uint32_t max_samples)
-        {
-            return side ? (size_t) (max_samples - 1u - i) : (size_t) i;
-        }
-        __device__ __forceinline__ uint32_t aox_count(const AoxState &st, uint32_t side) { return side ? st.n[1] : st.n[0]; }
-        __device__ __forceinline__ uint32_t aox_grow(AoxState &st, uint32_t side)  // -> index of the node now counted
-        {
-            const uint32_t i = aox_count(st, side);
-            if (side)
-                st.n[1] = i + 1u;
-            else
-                st.n[0] = i + 1u;
-            return i;
-        }
-
-        __device__ __forceinline__ float aox_dist(const float *a, const float *b, uint32_t dim)
-        {
-            float sum = 0.f;
-            for (uint32_t j = 0; j < dim; ++j)
-            {
-                const float df = a[j] - b[j];
-                sum = sum + df * df;
-            }
-            return sqrtf(sum);
-        }
 
         __device__ __forceinline__ float aox_uniform(uint32_t seed, uint32_t &c)
         {
@@ -249,131 +222,36 @@ namespace vmv
             return ok;
         }
 
-        __device__ __forceinline__ bool aox_closer(float k, uint32_t i, float best_k, uint32_t best_i)
-        {
-            return k < best_k || (k == best_k && i < best_i);
-        }
-
-        // (first index with the least key among the admissible nodes, its distance to s_t) over nodes [0, count) of one
-        // tree; the same values in every thread.  Called by all threads of the workgroup (barriers, cross-lane reads with
-        // every lane enabled).  kAoxNone where no key compares below +inf.
-        __device__ void aox_nearest(const float *__restrict__ pool, const float *__restrict__ cost, const uint32_t side,
-                                    const uint32_t count, const AoxParams &P, const float *s_t, const float c, float *s_rk,
-                                    float *s_rd, uint32_t *s_ri, float &out_d, uint32_t &out_i)
-        {
-            float best_k = INFINITY, best_d = NAN;
-            uint32_t best_i = kAoxNone;
-            for (uint32_t i = threadIdx.x; i < count; i += kAoxBlock)  // increasing i per lane: `<` keeps the first
-            {
-                const size_t at = aox_at(side, i, P.max_samples);
-                const float *q = pool + at * P.dim;
-                float sum = 0.f;
-                for (uint32_t j = 0; j < P.dim; ++j)
-                {
-                    const float df = q[j] - s_t[j];
-                    sum = sum + df * df;
-                }
-                const float d = sqrtf(sum), ci = cost[at];
-                const bool admissible = !(ci > 0.f) || !(c < ci + d);
-                const float dc = ci - c;
-                const float key = sqrtf(d * d + dc * dc);
-                if (admissible && key < best_k) best_k = key, best_d = d, best_i = i;
-            }
-#pragma unroll
-            for (int off = kWave / 2; off > 0; off >>= 1)  // (all 64 lanes are enabled here: the loop above has ended)
-            {
-                const float ok = __shfl_xor(best_k, off), od = __shfl_xor(best_d, off);
-                const uint32_t oi = (uint32_t) __shfl_xor((int) best_i, off);
-                if (aox_closer(ok, oi, best_k, best_i)) best_k = ok, best_d = od, best_i = oi;
-            }
-            if ((threadIdx.x & (kWave - 1)) == 0)
-                s_rk[threadIdx.x / kWave] = best_k, s_rd[threadIdx.x / kWave] = best_d, s_ri[threadIdx.x / kWave] = best_i;
-            __syncthreads();
-            best_k = s_rk[0], best_d = s_rd[0], best_i = s_ri[0];
-#pragma unroll
-            for (uint32_t w = 1; w < kAoxWaves; ++w)
-                if (aox_closer(s_rk[w], s_ri[w], best_k, best_i)) best_k = s_rk[w], best_d = s_rd[w], best_i = s_ri[w];
-            __syncthreads();  // s_rk / s_rd / s_ri / s_t may be rewritten after this
-            out_d = best_d, out_i = best_i;
-        }
-
-        // waypoints of a solved search: root(A) .. new, then B_prev .. root(B) without its first node if that equals
-        // `new` bit for bit (as vmv_rrtc_multi traces); one thread.  out == nullptr: count only.
-        __device__ uint32_t aox_trace(const AoxState &st, const float *pool, const uint32_t *parent, const uint32_t dim,
-                                      const uint32_t M, float *out)
-        {
-            const uint32_t sa = st.a_side, sb = sa ^ 1u;
-            uint32_t la = 1, lb = 1;
-            for (uint32_t i = st.new_i; parent[aox_at(sa, i, M)] != i; i = parent[aox_at(sa, i, M)]) ++la;
-            for (uint32_t i = st.prev; parent[aox_at(sb, i, M)] != i; i = parent[aox_at(sb, i, M)]) ++lb;
-            const uint32_t *pn = reinterpret_cast<const uint32_t *>(pool + aox_at(sa, st.new_i, M) * dim);
-            const uint32_t *pp = reinterpret_cast<const uint32_t *>(pool + aox_at(sb, st.prev, M) * dim);
-            bool same = true;
-            for (uint32_t j = 0; j < dim; ++j) same = same && pn[j] == pp[j];
-            const uint32_t skip = same ? 1u : 0u, len = la + lb - skip;
-            if (!out) return len;
-            const bool reversed = sa != 0;  // A is the goal tree: the path was collected goal -> start
-            uint32_t pos = la;              // A's branch is written backwards from position la - 1
-            for (uint32_t i = st.new_i;; i = parent[aox_at(sa, i, M)])
-            {
-                --pos;
-                const float *q = pool + aox_at(sa, i, M) * dim;
-                float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
-                for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
-                if (parent[aox_at(sa, i, M)] == i) break;
-            }
-            pos = la;
-            uint32_t seen = 0;
-            for (uint32_t i = st.prev;; i = parent[aox_at(sb, i, M)], ++seen)
-            {
-                if (seen >= skip)
-                {
-                    const float *q = pool + aox_at(sb, i, M) * dim;
-                    float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
-                    for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
-                    ++pos;
-                }
-                if (parent[aox_at(sb, i, M)] == i) break;
-            }
-            return len;
-        }
-
         // fresh trees, bound and budget for the search to come of every active problem; the uniform counter stays
         __global__ __launch_bounds__(kAoxBlock) void aox_init_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active)
         {
             const uint32_t a = blockIdx.x * kAoxBlock + threadIdx.x;
             if (a >= n_active) return;
             const uint32_t p = D.active[a], M = P.max_samples;
-            float *pool = D.pool + (size_t) p * M * P.dim;
-            for (uint32_t j = 0; j < P.dim; ++j)
-            {
-                pool[aox_at(0, 0, M) * P.dim + j] = D.starts[(size_t) p * P.dim + j];
-                pool[aox_at(1, 0, M) * P.dim + j] = D.goals[(size_t) p * P.dim + j];
-            }
-            uint32_t *parent = D.parent + (size_t) p * M;
+            init_roots(D.pool + (size_t) p * M * P.dim, D.parent + (size_t) p * M, D.starts + (size_t) p * P.dim,
+                       D.goals + (size_t) p * P.dim, P.dim, M);
             float *cost = D.cost + (size_t) p * M;
-            parent[aox_at(0, 0, M)] = 0, parent[aox_at(1, 0, M)] = 0;  // roots are their own parent
-            cost[aox_at(0, 0, M)] = 0.f, cost[aox_at(1, 0, M)] = 0.f;
+            cost[node_at(0, 0, M)] = 0.f, cost[node_at(1, 0, M)] = 0.f;
             AoxState st{};
             st.phase = kAoxFresh, st.status = VMV_PLAN_MAX_ITERATIONS;
             st.counter = D.state[p].counter;
             st.n[0] = st.n[1] = 1;
-            st.new_i = kAoxNone;
+            st.new_i = kNone;
             st.max_cost = D.max_cost[p], st.budget = D.budget[p];
             D.state[p] = st;
             D.done[p] = 0;
         }
 
         // One workgroup per active problem; every branch below is taken by the whole workgroup (its conditions are
-        // values every thread holds alike), so the barriers and cross-lane reads inside aox_nearest() are safe.
+        // values every thread holds alike), so the barriers and cross-lane reads inside nearest() are safe.
         __global__ __launch_bounds__(kAoxBlock) void aox_step_kernel(const AoxParams P, const AoxArrays D)
         {
-            __shared__ float s_t[kAoxMaxDim];
-            __shared__ float s_g[kAoxMaxDim + 2];
-            __shared__ float s_rk[kAoxWaves], s_rd[kAoxWaves];
-            __shared__ uint32_t s_ri[kAoxWaves];
+            __shared__ float s_t[kPlanMaxDim];
+            __shared__ float s_g[kPlanMaxDim + 2];
+            __shared__ float s_rk[kTreeWaves], s_rd[kTreeWaves];
+            __shared__ uint32_t s_ri[kTreeWaves];
             __shared__ PhsFrame s_frame;
-            __shared__ float s_c;           // the sampled cost bound of the next aox_nearest
+            __shared__ float s_c;           // the sampled cost bound of the next search
             __shared__ uint32_t s_ok, s_counter;
             const uint32_t a = blockIdx.x, p = D.active[a], tid = threadIdx.x, dim = P.dim, M = P.max_samples;
             AoxState st = D.state[p];
@@ -394,6 +272,18 @@ namespace vmv
                 }
             };
 
+            // the contract's nearest(T, s_t, c): T's first admissible node of the least key, and its distance to s_t
+            const auto search = [&](uint32_t side, float c, float &out_d, uint32_t &out_i) {
+                nearest<true>(
+                    pool, side, count_of(st.n, side), dim, M,
+                    [&](const float *q, size_t at) {
+                        const float d = tree_dist(q, s_t, dim), ci = cost[at];
+                        const float dc = ci - c;
+                        return Scored{!(ci > 0.f) || !(c < ci + d), sqrtf(d * d + dc * dc), d};
+                    },
+                    s_rk, s_rd, s_ri, out_d, out_i);
+            };
+
             enum { kLoop, kResample, kCommit, kMarchStep, kFinish } act = kLoop;
             if (st.phase == kAoxDone)
                 act = kFinish;
@@ -405,9 +295,9 @@ namespace vmv
                 {
                     if (ans)
                     {
-                        const float *nw = pool + aox_at(sa, aox_count(st, sa), M) * dim;
-                        st.new_cost = cost[aox_at(sa, st.ni, M)] + aox_dist(nw, pool + aox_at(sa, st.ni, M) * dim, dim);
-                        st.g2 = aox_dist(nw, pool + aox_at(sa, 0, M) * dim, dim);
+                        const float *nw = pool + node_at(sa, count_of(st.n, sa), M) * dim;
+                        st.new_cost = cost[node_at(sa, st.ni, M)] + tree_dist(nw, pool + node_at(sa, st.ni, M) * dim, dim);
+                        st.g2 = tree_dist(nw, pool + node_at(sa, 0, M) * dim, dim);
                         st.resamples = 0;
                         act = kResample;
                     }
@@ -423,7 +313,7 @@ namespace vmv
                 {
                     if (ans)
                     {
-                        st.prev = aox_grow(st, sb);
+                        st.prev = grow(st.n, sb);
                         if (++st.k == st.n_steps)
                             st.status = VMV_PLAN_SOLVED, act = kFinish;
                         else
@@ -435,7 +325,7 @@ namespace vmv
             if (act == kResample)  // `new` sits uncounted in A's next slot with parent ni and cost new_cost so far
             {
                 const uint32_t sa = st.a_side;
-                const size_t new_at = aox_at(sa, aox_count(st, sa), M);
+                const size_t new_at = node_at(sa, count_of(st.n, sa), M);
                 if (tid < dim) s_t[tid] = pool[new_at * dim + tid];
                 __syncthreads();
                 act = kCommit;
@@ -448,11 +338,11 @@ namespace vmv
                     const float c = s_c;
                     float md;
                     uint32_t mi;
-                    aox_nearest(pool, cost, sa, aox_count(st, sa), P, s_t, c, s_rk, s_rd, s_ri, md, mi);
-                    const float cand = mi == kAoxNone ? INFINITY : cost[aox_at(sa, mi, M)] + md;
-                    if (mi != kAoxNone && mi != st.ni && cand < st.new_cost && cr != 0.f)
+                    search(sa, c, md, mi);
+                    const float cand = mi == kNone ? INFINITY : cost[node_at(sa, mi, M)] + md;
+                    if (mi != kNone && mi != st.ni && cand < st.new_cost && cr != 0.f)
                     {
-                        if (tid < dim) qs[tid] = pool[aox_at(sa, mi, M) * dim + tid], qg[tid] = s_t[tid];
+                        if (tid < dim) qs[tid] = pool[node_at(sa, mi, M) * dim + tid], qg[tid] = s_t[tid];
                         st.mi = mi, st.cand_cost = cand;
                         st.phase = kAoxReparent, st.slot = a, ++st.questions;
                         save();
@@ -464,17 +354,16 @@ namespace vmv
             if (act == kCommit)  // count `new`, then look for a connection that beats the bound
             {
                 const uint32_t sa = st.a_side, sb = sa ^ 1u;
-                st.new_i = aox_grow(st, sa);
-                const size_t new_at = aox_at(sa, st.new_i, M);
+                st.new_i = grow(st.n, sa);
+                const size_t new_at = node_at(sa, st.new_i, M);
                 if (tid == 0) parent[new_at] = st.ni, cost[new_at] = st.new_cost;
                 if (tid < dim) s_t[tid] = pool[new_at * dim + tid];
                 __syncthreads();  // the cost is read by later searches of this launch
-                aox_nearest(pool, cost, sb, aox_count(st, sb), P, s_t, st.max_cost - st.new_cost, s_rk, s_rd, s_ri, st.bd, st.bi);
+                search(sb, st.max_cost - st.new_cost, st.bd, st.bi);
                 act = kLoop;
-                if (st.bi != kAoxNone && (st.new_cost + st.bd) + cost[aox_at(sb, st.bi, M)] < st.max_cost)
+                if (st.bi != kNone && (st.new_cost + st.bd) + cost[node_at(sb, st.bi, M)] < st.max_cost)
                 {
-                    const float c = ceilf(st.bd / R);
-                    st.n_steps = (c >= 1.f && c < 2147483648.f) ? (uint32_t) c : 1u;
+                    st.n_steps = march_steps(st.bd, R);
                     st.k = 0, st.prev = st.bi;
                     act = kMarchStep;
                 }
@@ -487,9 +376,9 @@ namespace vmv
                     act = kLoop;  // the pool is full: the march ends unconnected
                 else
                 {
-                    const float *o = pool + aox_at(sb, st.bi, M) * dim, *nw = pool + aox_at(sa, st.new_i, M) * dim;
-                    const float *from = pool + aox_at(sb, st.prev, M) * dim;
-                    const size_t w_at = aox_at(sb, aox_count(st, sb), M);
+                    const float *o = pool + node_at(sb, st.bi, M) * dim, *nw = pool + node_at(sa, st.new_i, M) * dim;
+                    const float *from = pool + node_at(sb, st.prev, M) * dim;
+                    const size_t w_at = node_at(sb, count_of(st.n, sb), M);
                     const float s = st.bd > 0.f ? fminf((float) (st.k + 1u) * R, st.bd) / st.bd : 0.f;
                     float sum = 0.f;  // every thread computes the whole of w: dist(w, from) needs no exchange
                     for (uint32_t j = 0; j < dim; ++j)
@@ -501,7 +390,7 @@ namespace vmv
                         if (tid == j) pool[w_at * dim + j] = w, qs[j] = from[j], qg[j] = w;
                     }
                     st.phase = kAoxMarch, st.slot = a, ++st.questions;
-                    if (tid == 0) parent[w_at] = st.prev, cost[w_at] = cost[aox_at(sb, st.prev, M)] + sqrtf(sum);
+                    if (tid == 0) parent[w_at] = st.prev, cost[w_at] = cost[node_at(sb, st.prev, M)] + sqrtf(sum);
                     save();
                     return;
                 }
@@ -525,17 +414,14 @@ namespace vmv
                     }
                     if (spins >= kAoxSpinCap)  // a null question; the loop goes on in the next round
                     {
-                        if (tid < dim) qs[tid] = start[tid], qg[tid] = start[tid];
+                        ask_nothing(qs, qg, start, dim);
                         st.phase = kAoxIdle, st.slot = a;
                         save();
                         return;
                     }
                     ++spins;
                     ++st.iterations;
-                    {
-                        const float na = (float) aox_count(st, st.a_side), nb = (float) aox_count(st, st.a_side ^ 1u);
-                        if (!P.balance || fabsf(na - nb) / na < P.tree_ratio) st.a_side ^= 1u;
-                    }
+                    st.a_side = next_a_side(st.n, st.a_side, P.balance, P.tree_ratio);
                     const uint32_t sa = st.a_side, sb = sa ^ 1u;
                     if (tid == 0)
                     {
@@ -543,8 +429,8 @@ namespace vmv
                         s_ok = ok ? 1u : 0u;
                         if (ok)
                         {
-                            const float g = aox_dist(s_t, pool + aox_at(sa, 0, M) * dim, dim);
-                            const float f = g + aox_dist(s_t, pool + aox_at(sb, 0, M) * dim, dim);
+                            const float g = tree_dist(s_t, pool + node_at(sa, 0, M) * dim, dim);
+                            const float f = g + tree_dist(s_t, pool + node_at(sb, 0, M) * dim, dim);
                             const float c_range = fmaxf(st.max_cost - f, 0.f);
                             s_c = aox_uniform(seed, s_counter) * c_range + g;
                         }
@@ -556,17 +442,9 @@ namespace vmv
                     if (!ok) continue;
                     float d;
                     uint32_t ni;
-                    aox_nearest(pool, cost, sa, aox_count(st, sa), P, s_t, c, s_rk, s_rd, s_ri, d, ni);
-                    if (ni == kAoxNone || !(d > 0.f)) continue;
-                    const float s = fminf(d, R) / d;
-                    if (tid < dim)
-                    {
-                        const float near = pool[aox_at(sa, ni, M) * dim + tid];
-                        const float nw = near + (s_t[tid] - near) * s;
-                        pool[aox_at(sa, aox_count(st, sa), M) * dim + tid] = nw;
-                        qs[tid] = near;
-                        qg[tid] = nw;
-                    }
+                    search(sa, c, d, ni);
+                    if (ni == kNone || !(d > 0.f)) continue;
+                    ask_extension(pool, node_at(sa, ni, M), node_at(sa, count_of(st.n, sa), M), dim, s_t, d, R, qs, qg);
                     st.ni = ni;
                     st.phase = kAoxExtend, st.slot = a, ++st.questions;
                     save();
@@ -574,19 +452,19 @@ namespace vmv
                 }
             }
 
-            // finished (now or in an earlier round): the null question start -> start, its answer is ignored
-            if (tid < dim) qs[tid] = start[tid], qg[tid] = start[tid];
+            // finished (now or in an earlier round)
+            ask_nothing(qs, qg, start, dim);
             if (st.phase != kAoxDone && tid == 0)
             {
                 st.phase = kAoxDone, st.slot = a;
-                st.path_len = st.status == VMV_PLAN_SOLVED ? aox_trace(st, pool, parent, dim, M, nullptr) : 0u;
+                st.path_len = st.status == VMV_PLAN_SOLVED ? trace_path(st.a_side, st.new_i, st.prev, pool, parent, dim, M, nullptr) : 0u;
                 st.counter = s_counter;
                 D.state[p] = st;
                 D.done[p] = 1;
             }
         }
 
-        __global__ __launch_bounds__(kAoxBlock) void aox_trace_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active,
+        __global__ __launch_bounds__(kAoxBlock) void aox_paths_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active,
                                                                        const uint64_t *__restrict__ offsets, float *__restrict__ paths)
         {
             const uint32_t a = blockIdx.x * kAoxBlock + threadIdx.x;
@@ -594,8 +472,8 @@ namespace vmv
             const uint32_t p = D.active[a];
             const AoxState st = D.state[p];
             if (st.phase != kAoxDone || st.status != VMV_PLAN_SOLVED) return;
-            (void) aox_trace(st, D.pool + (size_t) p * P.max_samples * P.dim, D.parent + (size_t) p * P.max_samples, P.dim,
-                             P.max_samples, paths + offsets[a] * P.dim);
+            (void) trace_path(st.a_side, st.new_i, st.prev, D.pool + (size_t) p * P.max_samples * P.dim,
+                              D.parent + (size_t) p * P.max_samples, P.dim, P.max_samples, paths + offsets[a] * P.dim);
         }
 
         // vmv_phs_samples: n successive samples of one problem's stream, drawn by one lane as aox_step_kernel draws them
@@ -606,7 +484,7 @@ namespace vmv
                                                                      uint32_t *__restrict__ out_counter)
         {
             __shared__ PhsFrame s_frame;
-            __shared__ float s_g[kAoxMaxDim + 2], s_t[kAoxMaxDim];
+            __shared__ float s_g[kPlanMaxDim + 2], s_t[kPlanMaxDim];
             if (threadIdx.x != 0 || blockIdx.x != 0) return;
             phs_frame(start, goal, P.dim, s_frame);
             uint32_t c = counter;
@@ -693,10 +571,9 @@ namespace vmv
             AoxParams P{};
             AoxArrays D{};
             DeviceBuffers mem;
-            float *d_starts = nullptr, *d_goals = nullptr, *d_max_cost = nullptr;
-            uint64_t *d_skips = nullptr, *d_bits = nullptr, *d_offsets = nullptr;
-            uint32_t *d_active = nullptr, *d_budget = nullptr;
-            uint8_t *h_done = nullptr;
+            LockstepBuffers B;
+            float *d_max_cost = nullptr;
+            uint32_t *d_budget = nullptr;
             float *d_paths = nullptr;  // the traced paths of one generation, packed
             uint64_t paths_capacity = 0;  // in waypoints
             hipStream_t stream = nullptr;
@@ -707,34 +584,18 @@ namespace vmv
 
             int setup(const float *starts, const float *goals, const uint64_t *skips)
             {
-                const size_t qn = n * (size_t) dim;
                 VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
                 VMV_LOCKSTEP_HIP(mem.alloc(&D.pool, n * (size_t) max_samples * (size_t) dim));
                 VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) max_samples));
                 VMV_LOCKSTEP_HIP(mem.alloc(&D.cost, n * (size_t) max_samples));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_starts, qn));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_goals, qn));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
                 VMV_LOCKSTEP_HIP(mem.alloc(&d_max_cost, n));
                 VMV_LOCKSTEP_HIP(mem.alloc(&d_budget, n));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_active, n));
-                VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
-                VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (n + 63) / 64));
-                VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n));
-                VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
-                h_done = static_cast<uint8_t *>(mem.pinned);
-                D.starts = d_starts, D.goals = d_goals, D.skips = d_skips, D.active = d_active, D.bits = d_bits;
+                if (int rc = B.alloc(mem, n, n, 1, (size_t) dim, stream); rc != VMV_OK) return rc;
+                if (int rc = upload_problems(mem, n, (size_t) dim, starts, goals, skips, stream, &D.starts, &D.goals, &D.skips); rc != VMV_OK)
+                    return rc;
+                D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits, D.done = B.done;
                 D.max_cost = d_max_cost, D.budget = d_budget;
-                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_starts, starts, qn * 4, hipMemcpyHostToDevice, stream));
-                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_goals, goals, qn * 4, hipMemcpyHostToDevice, stream));
-                if (skips)
-                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
-                else
-                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
                 VMV_LOCKSTEP_HIP(hipMemsetAsync(D.state, 0, n * sizeof(AoxState), stream));  // every counter starts at 0
-                VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((n + 63) / 64) * 8, stream));
                 VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
                 return VMV_OK;
             }
@@ -751,7 +612,7 @@ namespace vmv
                 for (size_t k = 0; k < active.size(); ++k)
                     active_envs[k] = envs[active[k]], max_budget = std::max(max_budget, budget[active[k]]);
                 const uint32_t na = (uint32_t) active.size();
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), na * 4ull, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), na * 4ull, hipMemcpyHostToDevice));
                 VMV_LOCKSTEP_HIP(hipMemcpy(d_max_cost, max_cost.data(), n * 4, hipMemcpyHostToDevice));
                 VMV_LOCKSTEP_HIP(hipMemcpy(d_budget, budget.data(), n * 4, hipMemcpyHostToDevice));
                 hipLaunchKernelGGL(aox_init_kernel, dim3((na + kAoxBlock - 1) / kAoxBlock), dim3(kAoxBlock), 0, stream, P, D, na);
@@ -762,9 +623,8 @@ namespace vmv
                 // for kAoxSpinCap iterations that asked nothing: a bound on the rounds that does not depend on the device's answers
                 const uint64_t max_rounds = (uint64_t) max_budget * (1ull + max_resamples) + max_samples + check_every + 2ull;
                 uint64_t rounds = 0;
-                const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
                 const auto step = [&](uint32_t count) { hipLaunchKernelGGL(aox_step_kernel, dim3(count), dim3(kAoxBlock), 0, stream, P, D); };
-                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, L, "vmv_aorrtc_multi",
+                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), "vmv_aorrtc_multi",
                                              "aox_step_kernel", step, rounds);
                     rc != VMV_OK)
                     return rc;
@@ -772,17 +632,14 @@ namespace vmv
 
                 states.resize(n);
                 VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(AoxState), hipMemcpyDeviceToHost));
-                std::vector<uint64_t> offsets(na);
+                std::vector<uint32_t> lengths(na);
+                for (uint32_t k = 0; k < na; ++k) lengths[k] = states[active_in[k]].path_len;
                 uint64_t total = 0;
-                for (uint32_t k = 0; k < na; ++k)
-                {
-                    offsets[k] = total;
-                    total += states[active_in[k]].path_len;
-                }
+                const std::vector<uint64_t> offsets = path_offsets_of(lengths.data(), na, total);
                 if (!total) return VMV_OK;
                 // (lockstep_rounds compacted d_active: the trace runs over the generation's whole list again)
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active_in.data(), na * 4ull, hipMemcpyHostToDevice));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, offsets.data(), na * 8ull, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active_in.data(), na * 4ull, hipMemcpyHostToDevice));
+                VMV_LOCKSTEP_HIP(hipMemcpy(B.path_offsets, offsets.data(), na * 8ull, hipMemcpyHostToDevice));
                 if (total > paths_capacity)  // the trace buffer only grows: most generations reuse it
                 {
                     const uint64_t want = std::max<uint64_t>(total, 2 * paths_capacity);
@@ -791,16 +648,16 @@ namespace vmv
                     VMV_LOCKSTEP_HIP(hipMalloc(&d_paths, want * (size_t) dim * 4));
                     paths_capacity = want;
                 }
-                hipLaunchKernelGGL(aox_trace_kernel, dim3((na + kAoxBlock - 1) / kAoxBlock), dim3(kAoxBlock), 0, stream, P, D, na,
-                                   d_offsets, d_paths);
+                hipLaunchKernelGGL(aox_paths_kernel, dim3((na + kAoxBlock - 1) / kAoxBlock), dim3(kAoxBlock), 0, stream, P, D, na,
+                                   B.path_offsets, d_paths);
                 hipError_t e = hipGetLastError();
                 std::vector<float> packed(total * (size_t) dim);
                 if (e == hipSuccess) e = hipMemcpy(packed.data(), d_paths, packed.size() * 4, hipMemcpyDeviceToHost);
-                if (e != hipSuccess) return hip_status(e, "aox_trace_kernel");
+                if (e != hipSuccess) return hip_status(e, "aox_paths_kernel");
                 for (uint32_t k = 0; k < na; ++k)
                 {
                     const uint32_t p = active_in[k];
-                    const size_t count = (size_t) states[p].path_len * (size_t) dim;
+                    const size_t count = (size_t) lengths[k] * (size_t) dim;
                     found[p].assign(packed.begin() + offsets[k] * dim, packed.begin() + offsets[k] * dim + count);
                 }
                 return VMV_OK;
@@ -941,7 +798,7 @@ extern "C"
     {
         // device-free checks first, in vmv_rrtc_multi's order; the simplifier's settings by an empty call of the simplifier
         const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kAoxMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
         if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
         if (n_problems >= vmv::kMultiMaxConfigs / 64) return VMV_ERR_INVALID_ARGUMENT;  // (64 questions per path per round)
         const vmv_aorrtc_settings &S = *settings;
@@ -989,7 +846,7 @@ extern "C"
                         size_t n, float *out_q, uint8_t *out_in_bounds, uint32_t *out_counter)
     {
         const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kAoxMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
         if (!start || !goal || !out_counter || (n > 0 && (!out_q || !out_in_bounds)) || n >= (size_t{1} << 24))
             return VMV_ERR_INVALID_ARGUMENT;
         return vmv::phs_samples_run(robot, dim, start, goal, max_cost, seed, counter, n, out_q, out_in_bounds, out_counter);

@@ -1,6 +1,7 @@
 // vmv_fcit_multi.hip — a lazy search of the complete graph over many independent problems (vmv_fcit_multi).
 //
-// The vertices are vmv_prm_multi's (the same memory layout, ONE vmv_validate_batch_multi call).  Then lockstep rounds
+// The vertices are vmv_prm_multi's (vmv_prm_common.h: the same memory layout, the same stage 1 with its ONE
+// vmv_validate_batch_multi call).  Then lockstep rounds
 // (vmv_lockstep.h): per round fcit_step_kernel, one workgroup per unfinished problem, consumes the answers to the
 // problem's previous questions, advances the serial algorithm — A* over the valid vertices with every unchecked edge taken
 // as free, the proposed path's edges asked from the start, the first invalid one blocked, search again — until it needs an
@@ -21,6 +22,7 @@
 
 #include "vmv_lockstep.h"
 #include "vmv_plans.h"
+#include "vmv_prm_common.h"
 
 #include <cmath>
 #include <cstring>
@@ -29,15 +31,13 @@ namespace vmv
 {
     namespace
     {
-        constexpr uint32_t kFcitBlock = 256, kFcitWaves = kFcitBlock / 64;
-        constexpr uint32_t kFcitMaxDim = 16;
+        constexpr uint32_t kFcitBlock = 256, kFcitWaves = kFcitBlock / kWave;
         constexpr uint32_t kFcitMinSamples = 64, kFcitMaxSamples = 2048;
         constexpr uint32_t kFcitMaxVertices = kFcitMaxSamples + 2;
         constexpr uint32_t kFcitMaxQuestions = 32;
         constexpr uint32_t kFcitDefaultCheckEvery = 4;
         constexpr uint32_t kFcitSearchCap = 64;   // searches per problem per round, committed and speculative together
         constexpr uint32_t kFcitMaxOverlay = 64;  // pairs a round's predictions may assume invalid
-        constexpr uint32_t kInfBits = 0x7f800000u;
         constexpr unsigned long long kNoKey = ~0ull;
 
         enum : uint32_t { kPhaseInit = 0, kPhaseRun = 1, kPhaseDone = 2 };
@@ -47,7 +47,6 @@ namespace vmv
         struct FcitParams
         {
             uint32_t dim, n_samples, V, row_words, W, max_iterations, n_problems;
-            float lower[kFcitMaxDim], span[kFcitMaxDim];
         };
 
         struct FcitState  // 56 bytes per problem; all zeros = a problem not yet started
@@ -63,7 +62,7 @@ namespace vmv
         {
             float *verts;           // [P * n_samples + 2 * P][dim], vmv_prm_multi's layout
             const uint64_t *vbits;  // validity of the vertices, in that order
-            const uint64_t *skips;  // [P]
+            uint64_t *skips;        // [P] the Halton skips stage 1 samples after
             uint32_t *answers;      // [P][V][row_words]
             uint32_t *blocked;      // [P][V][row_words]
             uint32_t *walk;         // [P][V] the proposed path's vertex ids, start first
@@ -74,23 +73,6 @@ namespace vmv
             float *q_start, *q_goal;  // [active][W][dim]
             const uint64_t *bits;
         };
-
-        __device__ __forceinline__ size_t vertex_at(const FcitParams &P, uint32_t p, uint32_t v)  // index into verts / vbits
-        {
-            return v < 2u ? (size_t) P.n_problems * P.n_samples + 2u * (size_t) p + v : (size_t) p * P.n_samples + (v - 2u);
-        }
-        __device__ __forceinline__ bool bit_at(const uint64_t *bits, size_t i) { return (bits[i >> 6] >> (i & 63u)) & 1ull; }
-
-        __global__ __launch_bounds__(kFcitBlock) void fcit_halton_kernel(const FcitParams P, const FcitArrays D)
-        {
-            const size_t total = (size_t) P.n_problems * P.n_samples * P.dim;
-            const size_t i = (size_t) blockIdx.x * kFcitBlock + threadIdx.x;
-            if (i >= total) return;
-            const uint32_t j = (uint32_t) (i % P.dim);
-            const size_t s = i / P.dim;
-            const uint32_t p = (uint32_t) (s / P.n_samples), k = (uint32_t) (s % P.n_samples);
-            D.verts[i] = halton_element(D.skips[p] + 1ull + k, (int) j, P.lower[j], P.span[j]);
-        }
 
         // the pair state of one problem; a < b wherever a pair is named
         struct PairBits
@@ -153,12 +135,12 @@ namespace vmv
                         best = key < best ? key : best;
                     }
 #pragma unroll
-                for (int off = 32; off >= 1; off >>= 1)
+                for (int off = kWave / 2; off >= 1; off >>= 1)
                 {
-                    const unsigned long long o = __shfl_xor(best, off, 64);
+                    const unsigned long long o = __shfl_xor(best, off, kWave);
                     best = o < best ? o : best;
                 }
-                if ((tid & 63u) == 0u) L.red[tid >> 6] = best;
+                if (tid % kWave == 0u) L.red[tid / kWave] = best;
                 if (tid == 0u) L.n_other = 0u;
                 __syncthreads();
 #pragma unroll
@@ -235,7 +217,7 @@ namespace vmv
                     L.prefix[n_words] = sum;
                 }
                 __syncthreads();
-                const bool ends_ok = bit_at(D.vbits, vertex_at(P, p, 0)) && bit_at(D.vbits, vertex_at(P, p, 1));
+                const bool ends_ok = ends_valid(P, D.vbits, p);
                 n_valid = L.prefix[n_words];
                 if (st.phase == kPhaseInit)
                 {
@@ -414,34 +396,6 @@ namespace vmv
             }
         }
 
-        __global__ __launch_bounds__(kFcitBlock) void fcit_gather_kernel(const FcitParams P, const FcitArrays D,
-                                                                          const uint64_t *__restrict__ offsets, float *__restrict__ paths)
-        {
-            const uint32_t p = blockIdx.x * kFcitBlock + threadIdx.x;
-            if (p >= P.n_problems) return;
-            const uint32_t len = D.state[p].path_len <= P.V ? D.state[p].path_len : 0u;
-            const uint32_t *walk = D.walk + (size_t) p * P.V;
-            float *out = paths + offsets[p] * P.dim;
-            for (uint32_t s = 0; s < len; ++s)
-            {
-                const uint32_t v = walk[s];
-                if (v >= P.V) return;
-                const float *q = D.verts + vertex_at(P, p, v) * P.dim;
-                for (uint32_t j = 0; j < P.dim; ++j) out[(size_t) s * P.dim + j] = q[j];
-            }
-        }
-
-#define VMV_FCIT_LAUNCHED(name)                               \
-    do                                                        \
-    {                                                         \
-        const hipError_t e_ = hipGetLastError();              \
-        if (e_ != hipSuccess)                                 \
-        {                                                     \
-            (void) hipDeviceSynchronize();                    \
-            return hip_status(e_, name);                      \
-        }                                                     \
-    } while (0)
-
         // The caller has checked every argument, n > 0, and every environment is finalized on the current device with
         // the robot's part built.
         int fcit_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
@@ -451,7 +405,6 @@ namespace vmv
             FcitParams P{};
             P.dim = (uint32_t) dim, P.n_samples = S.n_samples, P.V = S.n_samples + 2u, P.row_words = (P.V + 31u) / 32u;
             P.W = S.questions_per_round, P.max_iterations = S.max_iterations, P.n_problems = (uint32_t) n;
-            for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
             const uint32_t check_every = S.check_every ? S.check_every : kFcitDefaultCheckEvery;
             const size_t ns = S.n_samples, V = P.V, W = P.W, n_sample_cfgs = n * ns, n_cfgs = n_sample_cfgs + 2 * n, nv = n * V;
             const size_t matrix_words = nv * P.row_words, n_slots = n * W;
@@ -459,67 +412,28 @@ namespace vmv
             hipStream_t stream = nullptr;
 
             DeviceBuffers mem;
+            LockstepBuffers B;
             FcitArrays D{};
-            uint64_t *d_vbits = nullptr, *d_skips = nullptr, *d_bits = nullptr, *d_path_offsets = nullptr;
-            uint32_t *d_active = nullptr;
+            uint64_t *d_vbits = nullptr;
             VMV_LOCKSTEP_HIP(mem.alloc(&D.verts, n_cfgs * (size_t) dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_vbits, (n_cfgs + 63) / 64));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.skips, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.answers, matrix_words));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.blocked, matrix_words));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.walk, nv));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.asked, 2 * n_slots));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_active, n));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, n_slots * (size_t) dim));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, n_slots * (size_t) dim));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (n_slots + 63) / 64));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_path_offsets, n));
-            VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
-            uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
-            D.vbits = d_vbits, D.skips = d_skips, D.active = d_active, D.bits = d_bits;
+            if (int rc = B.alloc(mem, n, n, W, (size_t) dim, stream); rc != VMV_OK) return rc;
+            D.vbits = d_vbits, D.done = B.done, D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits;
             VMV_LOCKSTEP_HIP(hipMemsetAsync(D.answers, 0, matrix_words * 4, stream));
             VMV_LOCKSTEP_HIP(hipMemsetAsync(D.blocked, 0, matrix_words * 4, stream));
             VMV_LOCKSTEP_HIP(hipMemsetAsync(D.state, 0, n * sizeof(FcitState), stream));
-            VMV_LOCKSTEP_HIP(hipMemsetAsync(D.done, 0, n, stream));
-            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((n_slots + 63) / 64) * 8, stream));
 
-            // 1. vertices, as vmv_prm_multi: the samples of all problems, then (start, goal) of all problems; one validation call
-            if (samples)
-                VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.verts, samples, n_sample_cfgs * (size_t) dim * 4, hipMemcpyHostToDevice, stream));
-            else
-            {
-                if (skips)
-                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
-                else
-                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
-                const size_t total = n_sample_cfgs * (size_t) dim;
-                hipLaunchKernelGGL(fcit_halton_kernel, dim3((uint32_t) ((total + kFcitBlock - 1) / kFcitBlock)), dim3(kFcitBlock), 0, stream, P, D);
-                VMV_FCIT_LAUNCHED("fcit_halton_kernel");
-            }
-            std::vector<float> ends(2 * n * (size_t) dim);
-            for (size_t p = 0; p < n; ++p)
-            {
-                std::memcpy(&ends[(2 * p) * (size_t) dim], starts + p * (size_t) dim, (size_t) dim * 4);
-                std::memcpy(&ends[(2 * p + 1) * (size_t) dim], goals + p * (size_t) dim, (size_t) dim * 4);
-            }
-            VMV_LOCKSTEP_HIP(hipMemcpy(D.verts + n_sample_cfgs * (size_t) dim, ends.data(), ends.size() * 4, hipMemcpyHostToDevice));
-            {
-                std::vector<const vmv_env *> envs2(2 * n);
-                std::vector<size_t> seg(2 * n + 1);
-                for (size_t p = 0; p < n; ++p)
-                {
-                    envs2[p] = envs2[n + p] = envs[p];
-                    seg[p] = p * ns, seg[n + p] = n_sample_cfgs + 2 * p;
-                }
-                seg[2 * n] = n_cfgs;
-                if (int rc = vmv_validate_batch_multi(robot, envs2.data(), seg.data(), 2 * n, D.verts, d_vbits, stream); rc != VMV_OK)
-                {
-                    (void) hipDeviceSynchronize();
-                    return rc;
-                }
-            }
+            // 1. vertices: vmv_prm_multi's stage 1
+            if (int rc = prm_stage_vertices(robot, envs, n, S.n_samples, P.dim, starts, goals, skips, samples, lower, span, D.verts, D.skips,
+                                            d_vbits, stream, "fcit_halton_kernel");
+                rc != VMV_OK)
+                return rc;
 
             // 2. the rounds.  The first leaves out the problems with an invalid endpoint: a call of nothing else asks nothing.
             std::vector<uint64_t> vbits((2 * n + 63) / 64 + 1);
@@ -536,7 +450,7 @@ namespace vmv
                 active.push_back((uint32_t) p), active_envs.push_back(envs[p]);
             }
             const bool any_ok = std::find(ends_ok.begin(), ends_ok.end(), (uint8_t) 1) != ends_ok.end();
-            VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), n * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), n * 4, hipMemcpyHostToDevice));
             const auto step = [&](uint32_t na) {
                 if (dim <= 8)
                     hipLaunchKernelGGL(fcit_step_kernel<8>, dim3(na), dim3(kFcitBlock), 0, stream, P, D);
@@ -549,8 +463,7 @@ namespace vmv
                 // slot 0 of a round is a pair never asked before, or the round ran kFcitSearchCap committed searches: a bound
                 // on the rounds that does not depend on the device's answers
                 const uint64_t max_rounds = (uint64_t) V * (V - 1) / 2 + (uint64_t) S.max_iterations / kFcitSearchCap + check_every + 2ull;
-                const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
-                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, W, active, active_envs, L, "vmv_fcit_multi",
+                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, W, active, active_envs, B.arrays(), "vmv_fcit_multi",
                                              "fcit_step_kernel", step, rounds);
                     rc != VMV_OK)
                     return rc;
@@ -558,7 +471,7 @@ namespace vmv
             else  // every problem ends in its first step, with no question: the step alone, no validation call
             {
                 step(n32);
-                VMV_FCIT_LAUNCHED("fcit_step_kernel");
+                VMV_PRM_LAUNCHED("fcit_step_kernel");
             }
 
             // 3. results: the states, then the paths gathered on the device into one packed buffer
@@ -568,8 +481,6 @@ namespace vmv
             plans->fcit = true, plans->n_samples = S.n_samples;
             plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
             plans->costs.resize(n), plans->known_valid.resize(n);
-            std::vector<uint64_t> path_offsets(n);
-            uint64_t total = 0;
             for (size_t p = 0; p < n; ++p)
             {
                 const FcitState &st = states[p];
@@ -580,21 +491,14 @@ namespace vmv
                 plans->path_lengths[p] = st.path_len;
                 plans->costs[p] = st.cost, plans->known_valid[p] = st.known_valid;
                 plans->questions += st.questions;
-                path_offsets[p] = total;
-                total += st.path_len;
             }
-            plans->paths.resize(total * (size_t) dim);
-            if (total)
-            {
-                float *d_paths = nullptr;
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_path_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(fcit_gather_kernel, dim3((n32 + kFcitBlock - 1) / kFcitBlock), dim3(kFcitBlock), 0, stream, P, D,
-                                   d_path_offsets, d_paths);
-                VMV_FCIT_LAUNCHED("fcit_gather_kernel");
-                VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
-            }
-            return VMV_OK;
+            return pack_paths(mem, B.path_offsets, plans->path_lengths, (size_t) dim, nullptr, "fcit_gather_kernel",
+                              [&](const uint64_t *d_offsets, float *d_paths) {
+                                  hipLaunchKernelGGL(walk_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream,
+                                                     PrmLayout{P.dim, P.n_samples, P.n_problems}, D.verts, D.walk, &D.state->path_len,
+                                                     (uint32_t) (sizeof(FcitState) / 4), false, d_offsets, d_paths);
+                              },
+                              plans->paths);
         }
     }  // namespace
 }  // namespace vmv
@@ -606,19 +510,13 @@ extern "C"
     {
         // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
         // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
-        const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kFcitMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_problems >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_problems; ++k)
-            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+        int dim = 0;
+        if (int rc = vmv::check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
         const uint32_t ns = settings->n_samples, W = settings->questions_per_round;
         if (ns % 64u != 0u || ns < vmv::kFcitMinSamples || ns > vmv::kFcitMaxSamples) return VMV_ERR_INVALID_ARGUMENT;
         if (W < 1u || W > vmv::kFcitMaxQuestions) return VMV_ERR_INVALID_ARGUMENT;
         if (settings->max_iterations < 1u) return VMV_ERR_INVALID_ARGUMENT;
-        if (!samples && halton_skips)
-            for (size_t k = 0; k < n_problems; ++k)
-                if (halton_skips[k] > 1000000ull || halton_skips[k] + ns > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
+        if (!samples && !vmv::halton_skips_ok(halton_skips, n_problems, ns)) return VMV_ERR_INVALID_ARGUMENT;
         // the words of one pair-state matrix and the questions of one round, both counted in 32 bits somewhere
         if (n_problems * (size_t) (ns + 2u) * (size_t) ((ns + 2u + 31u) / 32u) >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
         if (n_problems * (size_t) W >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;

@@ -1,11 +1,14 @@
-// vmv_lockstep.h — the host side the lockstep calls share (vmv_rrtc_multi, vmv_simplify_multi; DESIGN §5c "A round").
+// vmv_lockstep.h — the host side the lockstep calls share (vmv_rrtc_multi, vmv_simplify_multi, vmv_aorrtc_multi,
+// vmv_fcit_multi; DESIGN §5c "A round"), and the host steps every planner call has around its kernels: the device-free
+// argument checks, the problem uploads and the packed paths of a result (vmv_prm_multi and vmv_roadmaps_* as well).
 //
 // Every item of a call (a planning problem, a path) is a state machine in device memory.  One round = the call's step
 // kernel (one workgroup per unfinished item: consumes the answers to the item's previous questions, advances its state and
 // writes its next questions into the round's start / goal arrays) + one vmv_validate_motion_batch_multi call over those
 // edges.  The host does nothing per item inside a round and does not synchronise; every check_every rounds it reads the
 // finished flags and compacts the active list.  lockstep_rounds() below is that loop, with every synchronisation point
-// and every error exit of a call's rounds; the kernels, the state and the allocation sizes stay with each caller.
+// and every error exit of a call's rounds, LockstepBuffers the arrays it runs on; the kernels and the state stay with
+// each caller.
 #pragma once
 
 #include "../../include/vamp_mvt_amd.h"
@@ -13,12 +16,17 @@
 #include "vmv_common.h"
 
 #include <algorithm>
+#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 namespace vmv
 {
+    constexpr uint32_t kPlanMaxDim = 16;  // joints of a robot the planner calls accept
+    constexpr uint32_t kNone = 0xffffffffu;
+    constexpr uint64_t kMaxHaltonIndex = 1000000ull;
+
     struct DeviceBuffers  // freed on every way out
     {
         std::vector<void *> ptrs;
@@ -45,7 +53,7 @@ namespace vmv
         if (e_ != hipSuccess) return hip_status(e_, #call);   \
     } while (0)
 
-    struct LockstepArrays  // what the rounds of one call read and write; allocated and sized by the caller
+    struct LockstepArrays  // what the rounds of one call read and write (LockstepBuffers::arrays())
     {
         uint32_t *active;               // [initial active count] item of each workgroup, uploaded by the caller
         const float *q_start, *q_goal;  // [active][per_item][dim] the round's questions
@@ -54,6 +62,125 @@ namespace vmv
         uint8_t *h_done;                // [n_items] pinned
         size_t n_items;
     };
+
+    namespace  // internal linkage: the library exports nothing of what follows
+    {
+    // The arrays every lockstep call needs, for n_items items of which at most n_active are active at once, each with
+    // per_item questions of dim floats per round.  `done` and the answers start as zeros (in stream order).
+    struct LockstepBuffers
+    {
+        uint32_t *active = nullptr;
+        float *q_start = nullptr, *q_goal = nullptr;
+        uint64_t *bits = nullptr, *path_offsets = nullptr;  // path_offsets: [n_items], for pack_paths
+        uint8_t *done = nullptr, *h_done = nullptr;
+        size_t n_items = 0;
+
+        int alloc(DeviceBuffers &mem, size_t n, size_t n_active, size_t per_item, size_t dim, hipStream_t stream)
+        {
+            const size_t slots = std::max<size_t>(n_active, 1) * per_item, words = (slots + 63) / 64 + 1;
+            n_items = n;
+            VMV_LOCKSTEP_HIP(mem.alloc(&active, std::max<size_t>(n_active, 1)));
+            VMV_LOCKSTEP_HIP(mem.alloc(&q_start, slots * dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&q_goal, slots * dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&bits, words));
+            VMV_LOCKSTEP_HIP(mem.alloc(&done, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&path_offsets, n));
+            VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
+            h_done = static_cast<uint8_t *>(mem.pinned);
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(bits, 0, words * 8, stream));
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(done, 0, std::max<size_t>(n, 16), stream));
+            return VMV_OK;
+        }
+        LockstepArrays arrays() const { return {active, q_start, q_goal, bits, done, h_done, n_items}; }
+    };
+
+    // skips [n] on the device; NULL = zeros
+    inline int upload_skips(uint64_t *d_skips, const uint64_t *skips, size_t n, hipStream_t stream)
+    {
+        if (skips)
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
+        else
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
+        return VMV_OK;
+    }
+
+    // the inputs of n planning problems on the device: starts, goals [n][dim] and the Halton skips [n]
+    inline int upload_problems(DeviceBuffers &mem, size_t n, size_t dim, const float *starts, const float *goals, const uint64_t *skips,
+                               hipStream_t stream, const float **d_starts, const float **d_goals, const uint64_t **d_skips)
+    {
+        float *s = nullptr, *g = nullptr;
+        uint64_t *k = nullptr;
+        VMV_LOCKSTEP_HIP(mem.alloc(&s, n * dim));
+        VMV_LOCKSTEP_HIP(mem.alloc(&g, n * dim));
+        VMV_LOCKSTEP_HIP(mem.alloc(&k, n));
+        VMV_LOCKSTEP_HIP(hipMemcpyAsync(s, starts, n * dim * 4, hipMemcpyHostToDevice, stream));
+        VMV_LOCKSTEP_HIP(hipMemcpyAsync(g, goals, n * dim * 4, hipMemcpyHostToDevice, stream));
+        *d_starts = s, *d_goals = g, *d_skips = k;
+        return upload_skips(k, skips, n, stream);
+    }
+
+    // exclusive prefix sum of the path lengths; total: their sum
+    inline std::vector<uint64_t> path_offsets_of(const uint32_t *lengths, size_t n, uint64_t &total)
+    {
+        std::vector<uint64_t> offsets(n);
+        total = 0;
+        for (size_t k = 0; k < n; ++k) offsets[k] = total, total += lengths[k];
+        return offsets;
+    }
+
+    // The paths of a result, packed in item order into `paths`: item k has lengths[k] waypoints of dim floats.
+    // launch(d_offsets, d_paths) launches the caller's gather / trace kernel `kernel`, which writes device item s at
+    // waypoint d_offsets[s] — the offset of item order[s], or of item s where order is NULL.
+    template <typename Launch>
+    int pack_paths(DeviceBuffers &mem, uint64_t *d_offsets, const std::vector<uint32_t> &lengths, size_t dim, const uint32_t *order,
+                   const char *kernel, Launch &&launch, std::vector<float> &paths)
+    {
+        const size_t n = lengths.size();
+        uint64_t total = 0;
+        std::vector<uint64_t> offsets = path_offsets_of(lengths.data(), n, total);
+        paths.resize(total * dim);
+        if (!total) return VMV_OK;
+        if (order)
+        {
+            const std::vector<uint64_t> by_item(offsets);
+            for (size_t s = 0; s < n; ++s) offsets[s] = by_item[order[s]];
+        }
+        float *d_paths = nullptr;
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * dim));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, offsets.data(), n * 8, hipMemcpyHostToDevice));
+        launch(d_offsets, d_paths);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+        {
+            (void) hipDeviceSynchronize();
+            return hip_status(e, kernel);
+        }
+        VMV_LOCKSTEP_HIP(hipMemcpy(paths.data(), d_paths, total * dim * 4, hipMemcpyDeviceToHost));
+        return VMV_OK;
+    }
+
+    // The device-free checks the planner entry points begin with, in their order: the robot, the NULL pointers, the
+    // problem count, the NULL handles.  -> VMV_OK and the robot's dimension, or the first failing check's code.
+    inline int check_planner_call(int robot, const void *settings, const void *out, const vmv_env *const *envs, size_t n_problems,
+                                  const float *starts, const float *goals, int *dim)
+    {
+        *dim = vmv_robot_dimension(robot);
+        if (robot < 0 || robot >= vmv_num_robots() || *dim <= 0 || *dim > (int) kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_problems >= kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+        for (size_t k = 0; k < n_problems; ++k)
+            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+        return VMV_OK;
+    }
+    // whether `draws` Halton elements after every skip stay within the sequence's limit (NULL skips = zeros)
+    inline bool halton_skips_ok(const uint64_t *skips, size_t n, uint64_t draws)
+    {
+        if (!skips) return draws <= kMaxHaltonIndex;
+        for (size_t k = 0; k < n; ++k)
+            if (skips[k] > kMaxHaltonIndex || skips[k] + draws > kMaxHaltonIndex) return false;
+        return true;
+    }
+
+    }  // namespace
 
     // Runs rounds until no item is active.  active / active_envs: the unfinished items and their environments, compacted
     // in place; item k of the list owns questions [k * per_item, (k + 1) * per_item) of a round.  launch_step(na) launches

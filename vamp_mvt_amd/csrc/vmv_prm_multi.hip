@@ -11,7 +11,9 @@
 // gfx950).  d2(v, u) = the sum over the joints in order of (v[j] - u[j])^2, so d2(v, u) == d2(u, v) bit for bit;
 // neighbours are ordered by (d2, vertex id), a total order, so any parallel selection gives the same lists.  Joints
 // beyond the robot's are staged as zeros: adding +0 to a non-negative or non-finite sum changes no bit.
-// Vertex memory: the samples of all problems [P][n_samples][dim], then (start, goal) of all problems [P][2][dim]; a
+// Vertex memory (vertex_at of vmv_prm_common.h, where stage 1, the Halton fill, the offsets kernel and the walk gather
+// live too, shared with vmv_fcit_multi and vmv_roadmaps_*): the samples of all problems [P][n_samples][dim], then
+// (start, goal) of all problems [P][2][dim]; a
 // problem's samples own whole validity words (n_samples is a multiple of 64).  The P endpoint segments of two
 // configurations each SHARE validity words: correctness there rests on vmv_validate_batch_multi's flat layout, which zeroes
 // the words of a call with such segments and ORs / ANDs each segment's bits in atomically.
@@ -35,7 +37,6 @@ namespace vmv
         {
             uint32_t dim, n_samples, V, k, n_problems;
             float r2;
-            float lower[kPrmMaxDim], span[kPrmMaxDim];
         };
 
         struct PrmResult  // 32 bytes per problem
@@ -49,7 +50,7 @@ namespace vmv
         {
             float *verts;             // [P * n_samples + 2 * P][dim]
             const uint64_t *vbits;    // validity of the vertices, in that order
-            const uint64_t *skips;    // [P]
+            uint64_t *skips;          // [P] the Halton skips stage 1 samples after
             uint32_t *nbr;            // [P][V][k] neighbour lists, kNone after the last
             uint32_t *counts;         // [P * V + 1] candidate edges owned by (problem, vertex), the last 0
             uint32_t *first;          // [P * V + 1] their exclusive scan: first edge of (problem, vertex), the last the total
@@ -61,26 +62,6 @@ namespace vmv
             uint32_t *walk;           // [P][V] the path's vertex ids from the goal backwards
             PrmResult *result;        // [P]
         };
-
-        __device__ __forceinline__ size_t vertex_at(const PrmParams &P, uint32_t p, uint32_t v)  // index into verts / vbits
-        {
-            return v < 2u ? (size_t) P.n_problems * P.n_samples + 2u * (size_t) p + v : (size_t) p * P.n_samples + (v - 2u);
-        }
-        __device__ __forceinline__ bool ends_valid(const PrmParams &P, const uint64_t *__restrict__ vbits, uint32_t p)
-        {
-            return bit_at(vbits, vertex_at(P, p, 0)) && bit_at(vbits, vertex_at(P, p, 1));
-        }
-
-        __global__ __launch_bounds__(kPrmBlock) void prm_halton_kernel(const PrmParams P, const PrmArrays D)
-        {
-            const size_t total = (size_t) P.n_problems * P.n_samples * P.dim;
-            const size_t i = (size_t) blockIdx.x * kPrmBlock + threadIdx.x;
-            if (i >= total) return;
-            const uint32_t j = (uint32_t) (i % P.dim);
-            const size_t s = i / P.dim;
-            const uint32_t p = (uint32_t) (s / P.n_samples), k = (uint32_t) (s % P.n_samples);
-            D.verts[i] = halton_element(D.skips[p] + 1ull + k, (int) j, P.lower[j], P.span[j]);
-        }
 
         // One lane per query vertex, a workgroup within one problem (problem p0 + blockIdx.x / tiles, tile blockIdx.x % tiles).  The candidates go through LDS a tile
         // of kPrmBlock at a time: every lane reads the same candidate (a broadcast read) and its validity flag is the
@@ -162,12 +143,6 @@ namespace vmv
                 }
             }
             D.counts[i] = n;
-        }
-
-        __global__ __launch_bounds__(kPrmBlock) void prm_offsets_kernel(const PrmParams P, const PrmArrays D)
-        {
-            const uint32_t p = blockIdx.x * kPrmBlock + threadIdx.x;
-            if (p <= P.n_problems) D.edge_offsets[p] = D.first[(size_t) p * P.V];
         }
 
         // the edges of (p, v) start at first[p * V + v], in slot order
@@ -282,23 +257,6 @@ namespace vmv
             if (tid == 0u) D.result[p] = r;
         }
 
-        __global__ __launch_bounds__(kPrmBlock) void prm_gather_kernel(const PrmParams P, const PrmArrays D,
-                                                                        const uint64_t *__restrict__ offsets, float *__restrict__ paths)
-        {
-            const uint32_t p = blockIdx.x * kPrmBlock + threadIdx.x;
-            if (p >= P.n_problems) return;
-            const uint32_t len = D.result[p].path_len <= P.V ? D.result[p].path_len : 0u;
-            const uint32_t *walk = D.walk + (size_t) p * P.V;
-            float *out = paths + offsets[p] * P.dim;
-            for (uint32_t s = 0; s < len; ++s)
-            {
-                const uint32_t v = walk[len - 1u - s];
-                if (v >= P.V) return;
-                const float *q = D.verts + vertex_at(P, p, v) * P.dim;
-                for (uint32_t j = 0; j < P.dim; ++j) out[(size_t) s * P.dim + j] = q[j];
-            }
-        }
-
         // The caller has checked every argument, n > 0, and every environment is finalized on the current device with
         // the robot's part built.
         int prm_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
@@ -308,17 +266,16 @@ namespace vmv
             PrmParams P{};
             P.dim = (uint32_t) dim, P.n_samples = S.n_samples, P.V = S.n_samples + 2u, P.k = S.k, P.n_problems = (uint32_t) n;
             P.r2 = S.radius * S.radius;
-            for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
             const size_t ns = S.n_samples, V = P.V, n_sample_cfgs = n * ns, n_cfgs = n_sample_cfgs + 2 * n, nv = n * V;
             const uint32_t n32 = (uint32_t) n;
             hipStream_t stream = nullptr;
 
             DeviceBuffers mem;
             PrmArrays D{};
-            uint64_t *d_vbits = nullptr, *d_skips = nullptr, *d_ebits = nullptr, *d_path_offsets = nullptr;
+            uint64_t *d_vbits = nullptr, *d_ebits = nullptr, *d_path_offsets = nullptr;
             VMV_LOCKSTEP_HIP(mem.alloc(&D.verts, n_cfgs * (size_t) dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_vbits, (n_cfgs + 63) / 64));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.skips, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.nbr, nv * S.k));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.counts, nv + 1));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.first, nv + 1));
@@ -326,43 +283,13 @@ namespace vmv
             VMV_LOCKSTEP_HIP(mem.alloc(&D.walk, nv));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.result, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_path_offsets, n));
-            D.vbits = d_vbits, D.skips = d_skips;
+            D.vbits = d_vbits;
 
             // 1. vertices: the samples of all problems, then (start, goal) of all problems; one validation call
-            if (samples)
-                VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.verts, samples, n_sample_cfgs * (size_t) dim * 4, hipMemcpyHostToDevice, stream));
-            else
-            {
-                if (skips)
-                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
-                else
-                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
-                const size_t total = n_sample_cfgs * (size_t) dim;
-                hipLaunchKernelGGL(prm_halton_kernel, dim3((uint32_t) ((total + kPrmBlock - 1) / kPrmBlock)), dim3(kPrmBlock), 0, stream, P, D);
-                VMV_PRM_LAUNCHED("prm_halton_kernel");
-            }
-            std::vector<float> ends(2 * n * (size_t) dim);
-            for (size_t p = 0; p < n; ++p)
-            {
-                std::memcpy(&ends[(2 * p) * (size_t) dim], starts + p * (size_t) dim, (size_t) dim * 4);
-                std::memcpy(&ends[(2 * p + 1) * (size_t) dim], goals + p * (size_t) dim, (size_t) dim * 4);
-            }
-            VMV_LOCKSTEP_HIP(hipMemcpy(D.verts + n_sample_cfgs * (size_t) dim, ends.data(), ends.size() * 4, hipMemcpyHostToDevice));
-            {
-                std::vector<const vmv_env *> envs2(2 * n);
-                std::vector<size_t> seg(2 * n + 1);
-                for (size_t p = 0; p < n; ++p)
-                {
-                    envs2[p] = envs2[n + p] = envs[p];
-                    seg[p] = p * ns, seg[n + p] = n_sample_cfgs + 2 * p;
-                }
-                seg[2 * n] = n_cfgs;
-                if (int rc = vmv_validate_batch_multi(robot, envs2.data(), seg.data(), 2 * n, D.verts, d_vbits, stream); rc != VMV_OK)
-                {
-                    (void) hipDeviceSynchronize();
-                    return rc;
-                }
-            }
+            if (int rc = prm_stage_vertices(robot, envs, n, S.n_samples, P.dim, starts, goals, skips, samples, lower, span, D.verts, D.skips,
+                                            d_vbits, stream, "prm_halton_kernel");
+                rc != VMV_OK)
+                return rc;
             uint64_t validation_calls = 1;
 
             // 2. neighbours
@@ -390,7 +317,8 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(mem.alloc(&scan_tmp, scan_bytes));
                 VMV_LOCKSTEP_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, D.counts, D.first, (int) (nv + 1), stream));
             }
-            hipLaunchKernelGGL(prm_offsets_kernel, dim3((n32 + 1 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D);
+            hipLaunchKernelGGL(edge_offsets_kernel, dim3((n32 + 1 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, D.edge_offsets,
+                               D.first, n32, P.V);
             VMV_PRM_LAUNCHED("prm_offsets_kernel");
             std::vector<uint32_t> edge_offsets(n + 1);
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(edge_offsets.data(), D.edge_offsets, (n + 1) * 4, hipMemcpyDeviceToHost, stream));
@@ -430,8 +358,6 @@ namespace vmv
             plans->prm = true, plans->n_samples = S.n_samples;
             plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
             plans->candidate_edges.resize(n), plans->costs.resize(n);
-            std::vector<uint64_t> path_offsets(n);
-            uint64_t total = 0;
             for (size_t p = 0; p < n; ++p)
             {
                 const PrmResult &r = results[p];
@@ -440,20 +366,16 @@ namespace vmv
                 plans->sizes2[2 * p] = r.valid_vertices, plans->sizes2[2 * p + 1] = r.valid_edges;
                 plans->path_lengths[p] = r.path_len;
                 plans->candidate_edges[p] = r.candidate_edges, plans->costs[p] = r.cost;
-                path_offsets[p] = total;
-                total += r.path_len;
             }
-            plans->paths.resize(total * (size_t) dim);
-            if (total)
-            {
-                float *d_paths = nullptr;
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_path_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(prm_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D,
-                                   d_path_offsets, d_paths);
-                VMV_PRM_LAUNCHED("prm_gather_kernel");
-                VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
-            }
+            if (int rc = pack_paths(mem, d_path_offsets, plans->path_lengths, (size_t) dim, nullptr, "prm_gather_kernel",
+                                    [&](const uint64_t *d_offsets, float *d_paths) {
+                                        hipLaunchKernelGGL(walk_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream,
+                                                           PrmLayout{P.dim, P.n_samples, P.n_problems}, D.verts, D.walk, &D.result->path_len,
+                                                           (uint32_t) (sizeof(PrmResult) / 4), true, d_offsets, d_paths);
+                                    },
+                                    plans->paths);
+                rc != VMV_OK)
+                return rc;
             if (S.keep_roadmaps)
             {
                 std::vector<uint64_t> vbits((n_cfgs + 63) / 64), ebits((E + 63) / 64);
@@ -485,19 +407,13 @@ extern "C"
     {
         // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
         // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
-        const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPrmMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_problems >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_problems; ++k)
-            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+        int dim = 0;
+        if (int rc = vmv::check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
         const uint32_t ns = settings->n_samples;
         if (ns % 64u != 0u || ns < vmv::kPrmMinSamples || ns > vmv::kPrmMaxSamples) return VMV_ERR_INVALID_ARGUMENT;
         if (settings->k < 1u || settings->k > vmv::kPrmKMax) return VMV_ERR_INVALID_ARGUMENT;
         if (!(settings->radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;  // NaN as well
-        if (!samples && halton_skips)
-            for (size_t k = 0; k < n_problems; ++k)
-                if (halton_skips[k] > 1000000ull || halton_skips[k] + ns > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
+        if (!samples && !vmv::halton_skips_ok(halton_skips, n_problems, ns)) return VMV_ERR_INVALID_ARGUMENT;
         if (n_problems * (size_t) (ns + 2u) * (size_t) settings->k >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
         if (n_problems == 0)  // an empty result is a PRM result too
         {

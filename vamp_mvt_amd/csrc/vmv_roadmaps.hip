@@ -12,6 +12,8 @@
 // rm_query_sssp_kernel (one workgroup per query: the fp32 shortest-path fixpoint over the roadmap's shared edge list plus
 // the query's own connection edges, and the parent walk); the paths gathered into the packed vmv_plans buffers.
 //
+// The Halton fill and the edge-offsets kernel are vmv_prm_common.h's, shared with vmv_prm_multi; the result tail is
+// pack_paths of vmv_lockstep.h.
 // Arithmetic contract: that of vmv_prm_multi.hip (fp32, one rounding per written operation, keys (d2, id)).  On the device
 // the queries are in the order of the host's stable counting sort by roadmap ("position" s below); the host un-permutes.
 // Plain vector stores; atomics on LDS words only.  Every loop has a bound that holds whatever the data says.
@@ -48,19 +50,17 @@ namespace vmv
     namespace
     {
         constexpr uint32_t kConnectMax = 32;
-        constexpr uint32_t kWaveLanes = 64;
 
         struct BuildParams
         {
             uint32_t dim, n_samples, k, n_roadmaps;
             float r2;
-            float lower[kPrmMaxDim], span[kPrmMaxDim];
         };
         struct BuildArrays
         {
             float *verts;            // [R][n_samples][dim]
             const uint64_t *vbits;
-            const uint64_t *skips;   // [R]
+            uint64_t *skips;         // [R] the Halton skips the samples come after
             uint32_t *nbr;           // [R][n_samples][k] neighbour lists, kNone after the last
             uint32_t *counts;        // [R * n_samples + 1] candidate edges owned by (roadmap, sample), the last 0
             uint32_t *first;         // [R * n_samples + 1] their exclusive scan, the last the total
@@ -71,16 +71,6 @@ namespace vmv
             const uint64_t *ebits;
             uint32_t *stats;         // [R][2] valid vertices, valid edges
         };
-
-        __global__ __launch_bounds__(kPrmBlock) void rm_halton_kernel(const BuildParams P, const BuildArrays D)
-        {
-            const size_t total = (size_t) P.n_roadmaps * P.n_samples * P.dim;
-            const size_t i = (size_t) blockIdx.x * kPrmBlock + threadIdx.x;
-            if (i >= total) return;
-            const uint32_t j = (uint32_t) (i % P.dim);
-            const size_t s = i / P.dim;
-            D.verts[i] = halton_element(D.skips[s / P.n_samples] + 1ull + s % P.n_samples, (int) j, P.lower[j], P.span[j]);
-        }
 
         // prm_knn_kernel over a roadmap's samples alone: one lane per sample, a workgroup within one roadmap (roadmap
         // r0 + blockIdx.x / tiles, tile blockIdx.x % tiles), the candidates through LDS a tile of kPrmBlock at a time.
@@ -159,12 +149,6 @@ namespace vmv
                 }
             }
             D.counts[i] = n;
-        }
-
-        __global__ __launch_bounds__(kPrmBlock) void rm_offsets_kernel(const BuildParams P, const BuildArrays D)
-        {
-            const uint32_t r = blockIdx.x * kPrmBlock + threadIdx.x;
-            if (r <= P.n_roadmaps) D.edge_offsets[r] = D.first[(size_t) r * P.n_samples];
         }
 
         // the edges of (r, v) start at first[r * n_samples + v], in slot order; each is asked lower id -> higher id
@@ -249,7 +233,7 @@ namespace vmv
         // out.  The order is total, so the list is the contract's.  A query with an invalid endpoint asks nothing: all its
         // slots carry the null question (the endpoint to itself), as every slot beyond a list's end does.
         template <int DIM>
-        __global__ __launch_bounds__(kWaveLanes) void rm_connect_kernel(const QueryParams P, const QueryArrays D, const uint32_t e0)
+        __global__ __launch_bounds__(kWave) void rm_connect_kernel(const QueryParams P, const QueryArrays D, const uint32_t e0)
         {
             extern __shared__ uint32_t s_key[];  // [n_samples]
             const uint32_t ep = e0 + blockIdx.x, s = ep >> 1, side = ep & 1u, lane = threadIdx.x;
@@ -268,7 +252,7 @@ namespace vmv
 #pragma unroll
                 for (int j = 0; j < DIM; ++j) q[j] = (uint32_t) j < dim ? me[j] : 0.f;
                 const uint32_t r2_bits = __float_as_uint(P.r2);
-                for (uint32_t u = lane; u < ns; u += kWaveLanes)  // n_samples / 64 rounds
+                for (uint32_t u = lane; u < ns; u += kWave)  // n_samples / 64 rounds
                 {
                     uint32_t key = kNone;
                     if ((words[u >> 6] >> lane) & 1ull)
@@ -288,25 +272,25 @@ namespace vmv
                 for (uint32_t pass = 0; pass < kc; ++pass)
                 {
                     uint32_t bk = kNone, bu = kNone;
-                    for (uint32_t u = lane; u < ns; u += kWaveLanes)  // ascending ids: the strict `<` keeps the lower one
+                    for (uint32_t u = lane; u < ns; u += kWave)  // ascending ids: the strict `<` keeps the lower one
                     {
                         const uint32_t key = s_key[u];
                         if (key < bk) bk = key, bu = u;
                     }
 #pragma unroll
-                    for (int off = 32; off >= 1; off >>= 1)
+                    for (int off = kWave / 2; off >= 1; off >>= 1)
                     {
                         const uint32_t ok = __shfl_xor(bk, off), ou = __shfl_xor(bu, off);
                         if (ok < bk || (ok == bk && ou < bu)) bk = ok, bu = ou;
                     }
                     if (bk == kNone) break;  // the same in every lane: no sample is left
-                    if ((bu & (kWaveLanes - 1u)) == lane) s_key[bu] = kNone;
+                    if ((bu & (kWave - 1u)) == lane) s_key[bu] = kNone;
                     if (lane == 0u) D.conn_id[(size_t) ep * kc + found] = bu, D.conn_w[(size_t) ep * kc + found] = sqrtf(__uint_as_float(bk));
                     if (lane < dim) qa[(size_t) found * dim + lane] = me[lane], qb[(size_t) found * dim + lane] = verts_r[(size_t) bu * dim + lane];
                     ++found;
                 }
             }
-            for (uint32_t i = found * dim + lane; i < kc * dim; i += kWaveLanes) qa[i] = qb[i] = me[i % dim];
+            for (uint32_t i = found * dim + lane; i < kc * dim; i += kWave) qa[i] = qb[i] = me[i % dim];
             if (lane == 0u) D.conn_n[ep] = found;
             if (side == 0u && lane < dim)
             {
@@ -449,37 +433,27 @@ namespace vmv
             BuildParams P{};
             P.dim = (uint32_t) dim, P.n_samples = S.n_samples, P.k = S.k, P.n_roadmaps = (uint32_t) n;
             P.r2 = S.radius * S.radius;
-            for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
             const uint32_t n32 = (uint32_t) n;
             hipStream_t stream = nullptr;
             VMV_LOCKSTEP_HIP(hipGetDevice(&rm->device));
 
             DeviceBuffers tmp;  // what the build alone needs
             BuildArrays D{};
-            uint64_t *d_skips = nullptr;
             VMV_LOCKSTEP_HIP(rm->mem.alloc(&rm->verts, n_cfgs * (size_t) dim));
             VMV_LOCKSTEP_HIP(rm->mem.alloc(&rm->vbits, n_cfgs / 64));
             VMV_LOCKSTEP_HIP(rm->mem.alloc(&rm->d_edge_offsets, n + 1));
-            VMV_LOCKSTEP_HIP(tmp.alloc(&d_skips, n));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&D.skips, n));
             VMV_LOCKSTEP_HIP(tmp.alloc(&D.nbr, n_cfgs * S.k));
             VMV_LOCKSTEP_HIP(tmp.alloc(&D.counts, n_cfgs + 1));
             VMV_LOCKSTEP_HIP(tmp.alloc(&D.first, n_cfgs + 1));
             VMV_LOCKSTEP_HIP(tmp.alloc(&D.stats, 2 * n));
-            D.verts = rm->verts, D.vbits = rm->vbits, D.skips = d_skips, D.edge_offsets = rm->d_edge_offsets;
+            D.verts = rm->verts, D.vbits = rm->vbits, D.edge_offsets = rm->d_edge_offsets;
 
             // 1. the samples of all roadmaps; one validation call
             if (samples)
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.verts, samples, n_cfgs * (size_t) dim * 4, hipMemcpyHostToDevice, stream));
-            else
-            {
-                if (skips)
-                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
-                else
-                    VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
-                const size_t total = n_cfgs * (size_t) dim;
-                hipLaunchKernelGGL(rm_halton_kernel, dim3((uint32_t) ((total + kPrmBlock - 1) / kPrmBlock)), dim3(kPrmBlock), 0, stream, P, D);
-                VMV_PRM_LAUNCHED("rm_halton_kernel");
-            }
+            else if (int rc = halton_fill(D.verts, D.skips, skips, n, S.n_samples, P.dim, lower, span, stream, "rm_halton_kernel"); rc != VMV_OK)
+                return rc;
             {
                 std::vector<size_t> seg(n + 1);
                 for (size_t r = 0; r <= n; ++r) seg[r] = r * ns;
@@ -515,7 +489,8 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(tmp.alloc(&scan_tmp, scan_bytes));
                 VMV_LOCKSTEP_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, D.counts, D.first, (int) (n_cfgs + 1), stream));
             }
-            hipLaunchKernelGGL(rm_offsets_kernel, dim3((n32 + 1 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D);
+            hipLaunchKernelGGL(edge_offsets_kernel, dim3((n32 + 1 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, D.edge_offsets,
+                               D.first, n32, P.n_samples);
             VMV_PRM_LAUNCHED("rm_offsets_kernel");
             rm->edge_offsets.resize(n + 1);
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(rm->edge_offsets.data(), D.edge_offsets, (n + 1) * 4, hipMemcpyDeviceToHost, stream));
@@ -608,9 +583,9 @@ namespace vmv
                 const dim3 grid(std::min(kPrmLaunchBlocks, 2u * n32 - e0));
                 const size_t lds = (size_t) rm->n_samples * 4;
                 if (dim <= 8)
-                    hipLaunchKernelGGL(rm_connect_kernel<8>, grid, dim3(kWaveLanes), lds, stream, P, D, e0);
+                    hipLaunchKernelGGL(rm_connect_kernel<8>, grid, dim3(kWave), lds, stream, P, D, e0);
                 else
-                    hipLaunchKernelGGL(rm_connect_kernel<16>, grid, dim3(kWaveLanes), lds, stream, P, D, e0);
+                    hipLaunchKernelGGL(rm_connect_kernel<16>, grid, dim3(kWave), lds, stream, P, D, e0);
                 VMV_PRM_LAUNCHED("rm_connect_kernel");
             }
 
@@ -650,22 +625,12 @@ namespace vmv
             }
             // the edge call is made whatever the endpoints are; one that carried null questions only is not counted
             plans->rounds = questions ? 2 : 1, plans->questions = questions;
-            std::vector<uint64_t> by_query(n), path_offsets(n);
-            uint64_t total = 0;
-            for (size_t q = 0; q < n; ++q) by_query[q] = total, total += plans->path_lengths[q];
-            for (size_t s = 0; s < n; ++s) path_offsets[s] = by_query[order[s]];
-            plans->paths.resize(total * (size_t) dim);
-            if (total)
-            {
-                float *d_paths = nullptr;
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_path_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(rm_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D, d_path_offsets,
-                                   d_paths);
-                VMV_PRM_LAUNCHED("rm_gather_kernel");
-                VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
-            }
-            return VMV_OK;
+            return pack_paths(mem, d_path_offsets, plans->path_lengths, (size_t) dim, order.data(), "rm_gather_kernel",
+                              [&](const uint64_t *d_offsets, float *d_paths) {
+                                  hipLaunchKernelGGL(rm_gather_kernel, dim3((n32 + kPrmBlock - 1) / kPrmBlock), dim3(kPrmBlock), 0, stream, P, D,
+                                                     d_offsets, d_paths);
+                              },
+                              plans->paths);
         }
 
         bool on_its_device(const vmv_roadmaps *rm)
@@ -689,7 +654,7 @@ extern "C"
     {
         // device-free checks first; the environments' own (unfinalized, another device) are those of vmv_env_prepare_multi
         const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPrmMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
         if (!settings || !out || (n_roadmaps > 0 && !envs)) return VMV_ERR_INVALID_ARGUMENT;
         if (n_roadmaps >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
         for (size_t r = 0; r < n_roadmaps; ++r)

@@ -8,12 +8,14 @@
 // on gfx950), the nearest node is the FIRST of the least sqrtf(sum of squares in joint order).  The workgroup's lanes
 // stride over the tree; that changes the order nodes are LOOKED at, not the result: the (distance, index) argmin is
 // associative.  A problem's two trees share one pool of max_samples nodes, the start tree from the front and the goal
-// tree from the back; the planner's two size rules keep |A| + |B| <= max_samples.
+// tree from the back; the planner's two size rules keep |A| + |B| <= max_samples.  The pool's addressing, the nearest
+// search and the path trace are vmv_two_trees.h's, shared with vmv_aorrtc_multi.
 // Every store is a plain vector store by the owning workgroup; no atomics.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
 #include "vmv_plans.h"
+#include "vmv_two_trees.h"
 
 #include <cmath>
 #include <cstring>
@@ -22,11 +24,8 @@ namespace vmv
 {
     namespace
     {
-        constexpr uint32_t kRrtcBlock = 256;
-        constexpr uint32_t kRrtcWaves = kRrtcBlock / kWave;
-        constexpr uint32_t kRrtcMaxDim = 16;
+        constexpr uint32_t kRrtcBlock = kTreeBlock;
         constexpr uint32_t kRrtcDefaultCheckEvery = 16;
-        constexpr uint32_t kNone = 0xffffffffu;
 
         enum : uint32_t
         {
@@ -55,7 +54,7 @@ namespace vmv
         {
             uint32_t dim, max_samples, max_iterations, balance;
             float range, tree_ratio;
-            float lower[kRrtcMaxDim], span[kRrtcMaxDim];
+            float lower[kPlanMaxDim], span[kPlanMaxDim];
         };
 
         struct RrtcArrays
@@ -71,126 +70,12 @@ namespace vmv
             uint8_t *done;             // [n_problems]
         };
 
-        __device__ __forceinline__ size_t node_at(uint32_t side, uint32_t i, uint32_t max_samples)
-        {
-            return side ? (size_t) (max_samples - 1u - i) : (size_t) i;
-        }
-
-        // nodes of one side's tree; constant subscripts only, so that the state stays in registers
-        __device__ __forceinline__ uint32_t count_of(const RrtcState &st, uint32_t side) { return side ? st.n[1] : st.n[0]; }
-        __device__ __forceinline__ uint32_t grow(RrtcState &st, uint32_t side)  // -> index of the node now counted
-        {
-            const uint32_t i = count_of(st, side);
-            if (side)
-                st.n[1] = i + 1u;
-            else
-                st.n[0] = i + 1u;
-            return i;
-        }
-
-        __device__ __forceinline__ bool closer(float d, uint32_t i, float best_d, uint32_t best_i)
-        {
-            return d < best_d || (d == best_d && i < best_i);
-        }
-
-        // (first index with the least distance to s_t, that distance) over nodes [0, count) of one tree; the same
-        // values in every thread.  Called by all threads of the workgroup (barriers, cross-lane reads with every lane
-        // enabled).  kNone where no distance compares below +inf (a non-finite root).
-        __device__ void nearest(const float *__restrict__ pool, const uint32_t side, const uint32_t count, const RrtcParams &P,
-                                const float *s_t, float *s_rd, uint32_t *s_ri, float &out_d, uint32_t &out_i)
-        {
-            float best_d = INFINITY;
-            uint32_t best_i = kNone;
-            for (uint32_t i = threadIdx.x; i < count; i += kRrtcBlock)  // increasing i per lane: `<` keeps the first
-            {
-                const float *q = pool + node_at(side, i, P.max_samples) * P.dim;
-                float sum = 0.f;
-                for (uint32_t j = 0; j < P.dim; ++j)
-                {
-                    const float df = q[j] - s_t[j];
-                    sum = sum + df * df;
-                }
-                const float d = sqrtf(sum);
-                if (d < best_d) best_d = d, best_i = i;
-            }
-#pragma unroll
-            for (int off = kWave / 2; off > 0; off >>= 1)  // (all 64 lanes are enabled here: the loop above has ended)
-            {
-                const float od = __shfl_xor(best_d, off);
-                const uint32_t oi = (uint32_t) __shfl_xor((int) best_i, off);
-                if (closer(od, oi, best_d, best_i)) best_d = od, best_i = oi;
-            }
-            if ((threadIdx.x & (kWave - 1)) == 0) s_rd[threadIdx.x / kWave] = best_d, s_ri[threadIdx.x / kWave] = best_i;
-            __syncthreads();
-            best_d = s_rd[0], best_i = s_ri[0];
-#pragma unroll
-            for (uint32_t w = 1; w < kRrtcWaves; ++w)
-                if (closer(s_rd[w], s_ri[w], best_d, best_i)) best_d = s_rd[w], best_i = s_ri[w];
-            __syncthreads();  // s_rd / s_ri / s_t may be rewritten after this
-            out_d = best_d, out_i = best_i;
-        }
-
-        // waypoints of a solved problem: root(A) .. new, then B_prev .. root(B) without its first node if that equals
-        // `new` bit for bit; one thread.  out == nullptr: count only.
-        __device__ uint32_t trace_path(const RrtcState &st, const float *pool, const uint32_t *parent, const RrtcParams &P,
-                                       const float *start, const float *goal, float *out)
-        {
-            const uint32_t dim = P.dim;
-            if (st.new_i == kNone)  // direct
-            {
-                if (out)
-                    for (uint32_t j = 0; j < dim; ++j) out[j] = start[j], out[dim + j] = goal[j];
-                return 2;
-            }
-            const uint32_t sa = st.a_side, sb = sa ^ 1u;
-            uint32_t la = 1, lb = 1;
-            for (uint32_t i = st.new_i; parent[node_at(sa, i, P.max_samples)] != i; i = parent[node_at(sa, i, P.max_samples)]) ++la;
-            for (uint32_t i = st.prev; parent[node_at(sb, i, P.max_samples)] != i; i = parent[node_at(sb, i, P.max_samples)]) ++lb;
-            const uint32_t *pn = reinterpret_cast<const uint32_t *>(pool + node_at(sa, st.new_i, P.max_samples) * dim);
-            const uint32_t *pp = reinterpret_cast<const uint32_t *>(pool + node_at(sb, st.prev, P.max_samples) * dim);
-            bool same = true;
-            for (uint32_t j = 0; j < dim; ++j) same = same && pn[j] == pp[j];
-            const uint32_t skip = same ? 1u : 0u, len = la + lb - skip;
-            if (!out) return len;
-            const bool reversed = sa != 0;  // A is the goal tree: the path was collected goal -> start
-            uint32_t pos = la;              // pa is written backwards from position la - 1
-            for (uint32_t i = st.new_i;; i = parent[node_at(sa, i, P.max_samples)])
-            {
-                --pos;
-                const float *q = pool + node_at(sa, i, P.max_samples) * dim;
-                float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
-                for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
-                if (parent[node_at(sa, i, P.max_samples)] == i) break;
-            }
-            pos = la;
-            uint32_t seen = 0;
-            for (uint32_t i = st.prev;; i = parent[node_at(sb, i, P.max_samples)], ++seen)
-            {
-                if (seen >= skip)
-                {
-                    const float *q = pool + node_at(sb, i, P.max_samples) * dim;
-                    float *o = out + (size_t) (reversed ? len - 1u - pos : pos) * dim;
-                    for (uint32_t j = 0; j < dim; ++j) o[j] = q[j];
-                    ++pos;
-                }
-                if (parent[node_at(sb, i, P.max_samples)] == i) break;
-            }
-            return len;
-        }
-
         __global__ __launch_bounds__(kRrtcBlock) void rrtc_init_kernel(const RrtcParams P, const RrtcArrays D, const uint32_t n)
         {
             const uint32_t p = blockIdx.x * kRrtcBlock + threadIdx.x;
             if (p >= n) return;
-            float *pool = D.pool + (size_t) p * P.max_samples * P.dim;
-            uint32_t *parent = D.parent + (size_t) p * P.max_samples;
-            for (uint32_t j = 0; j < P.dim; ++j)
-            {
-                pool[node_at(0, 0, P.max_samples) * P.dim + j] = D.starts[(size_t) p * P.dim + j];
-                pool[node_at(1, 0, P.max_samples) * P.dim + j] = D.goals[(size_t) p * P.dim + j];
-            }
-            parent[node_at(0, 0, P.max_samples)] = 0;  // roots are their own parent
-            parent[node_at(1, 0, P.max_samples)] = 0;
+            init_roots(D.pool + (size_t) p * P.max_samples * P.dim, D.parent + (size_t) p * P.max_samples,
+                       D.starts + (size_t) p * P.dim, D.goals + (size_t) p * P.dim, P.dim, P.max_samples);
             RrtcState st{};
             st.phase = kPhaseInit, st.status = VMV_PLAN_MAX_ITERATIONS;
             st.n[0] = st.n[1] = 1;
@@ -203,9 +88,9 @@ namespace vmv
         // values every thread holds alike), so the barriers and cross-lane reads inside nearest() are safe.
         __global__ __launch_bounds__(kRrtcBlock) void rrtc_step_kernel(const RrtcParams P, const RrtcArrays D)
         {
-            __shared__ float s_t[kRrtcMaxDim];
-            __shared__ float s_rd[kRrtcWaves];
-            __shared__ uint32_t s_ri[kRrtcWaves];
+            __shared__ float s_t[kPlanMaxDim];
+            __shared__ float s_rd[kTreeWaves];
+            __shared__ uint32_t s_ri[kTreeWaves];
             const uint32_t a = blockIdx.x, p = D.active[a], tid = threadIdx.x, dim = P.dim, M = P.max_samples;
             RrtcState st = D.state[p];
             float *pool = D.pool + (size_t) p * M * dim;
@@ -213,6 +98,11 @@ namespace vmv
             float *qs = D.q_start + (size_t) a * dim, *qg = D.q_goal + (size_t) a * dim;
             const float *start = D.starts + (size_t) p * dim, *goal = D.goals + (size_t) p * dim;
             const float R = P.range;
+            // the nearest node is the first of the least distance to s_t: the key is the distance itself
+            const auto to_target = [&](const float *q, size_t) {
+                const float d = tree_dist(q, s_t, dim);
+                return Scored{true, d, d};
+            };
 
             enum { kLoop, kMarchStep, kFinish } act = kLoop;
             if (st.phase == kPhaseDone)
@@ -236,13 +126,12 @@ namespace vmv
                 {
                     if (ans)
                     {
-                        st.new_i = grow(st, sa);
+                        st.new_i = grow(st.n, sa);
                         if (tid < dim) s_t[tid] = pool[node_at(sa, st.new_i, M) * dim + tid];
                         __syncthreads();
-                        nearest(pool, sb, count_of(st, sb), P, s_t, s_rd, s_ri, st.bd, st.bi);
+                        nearest<false>(pool, sb, count_of(st.n, sb), dim, M, to_target, s_rd, nullptr, s_ri, st.bd, st.bi);
                         if (st.bi == kNone) st.bi = 0, st.bd = NAN;  // a non-finite root: the march's first step is invalid
-                        const float c = ceilf(st.bd / R);
-                        st.n_steps = (c >= 1.f && c < 2147483648.f) ? (uint32_t) c : 1u;
+                        st.n_steps = march_steps(st.bd, R);
                         st.k = 0, st.prev = st.bi;
                         act = kMarchStep;
                     }
@@ -251,7 +140,7 @@ namespace vmv
                 {
                     if (ans)
                     {
-                        st.prev = grow(st, sb);
+                        st.prev = grow(st.n, sb);
                         if (++st.k == st.n_steps)
                             st.status = VMV_PLAN_SOLVED, act = kFinish;
                         else
@@ -272,12 +161,12 @@ namespace vmv
                         const float o = pool[node_at(sb, st.bi, M) * dim + tid], nw = pool[node_at(sa, st.new_i, M) * dim + tid];
                         float w = nw;
                         if (st.bd > 0.f) w = o + (nw - o) * (fminf((float) (st.k + 1u) * R, st.bd) / st.bd);
-                        pool[node_at(sb, count_of(st, sb), M) * dim + tid] = w;
+                        pool[node_at(sb, count_of(st.n, sb), M) * dim + tid] = w;
                         qs[tid] = pool[node_at(sb, st.prev, M) * dim + tid];
                         qg[tid] = w;
                     }
                     st.phase = kPhaseMarch, st.slot = a, ++st.questions;
-                    if (tid == 0) parent[node_at(sb, count_of(st, sb), M)] = st.prev, D.state[p] = st;
+                    if (tid == 0) parent[node_at(sb, count_of(st.n, sb), M)] = st.prev, D.state[p] = st;
                     return;
                 }
             }
@@ -298,39 +187,30 @@ namespace vmv
                         break;
                     }
                     ++st.iterations;
-                    {
-                        const float na = (float) count_of(st, st.a_side), nb = (float) count_of(st, st.a_side ^ 1u);
-                        if (!P.balance || fabsf(na - nb) / na < P.tree_ratio) st.a_side ^= 1u;
-                    }
+                    st.a_side = next_a_side(st.n, st.a_side, P.balance, P.tree_ratio);
                     ++st.draws;
                     if (tid < dim) s_t[tid] = halton_element(skip + st.draws, (int) tid, P.lower[tid], P.span[tid]);
                     __syncthreads();
                     const uint32_t sa = st.a_side;
                     float d;
                     uint32_t ni;
-                    nearest(pool, sa, count_of(st, sa), P, s_t, s_rd, s_ri, d, ni);
+                    nearest<false>(pool, sa, count_of(st.n, sa), dim, M, to_target, s_rd, nullptr, s_ri, d, ni);
                     if (ni == kNone || !(d > 0.f)) continue;
-                    const float s = fminf(d, R) / d;
-                    if (tid < dim)
-                    {
-                        const float near = pool[node_at(sa, ni, M) * dim + tid];
-                        const float nw = near + (s_t[tid] - near) * s;
-                        pool[node_at(sa, count_of(st, sa), M) * dim + tid] = nw;
-                        qs[tid] = near;
-                        qg[tid] = nw;
-                    }
+                    ask_extension(pool, node_at(sa, ni, M), node_at(sa, count_of(st.n, sa), M), dim, s_t, d, R, qs, qg);
                     st.phase = kPhaseExtend, st.slot = a, ++st.questions;
-                    if (tid == 0) parent[node_at(sa, count_of(st, sa), M)] = ni, D.state[p] = st;
+                    if (tid == 0) parent[node_at(sa, count_of(st.n, sa), M)] = ni, D.state[p] = st;
                     return;
                 }
             }
 
-            // finished (now or in an earlier round): the null question start -> start, its answer is ignored
-            if (tid < dim) qs[tid] = start[tid], qg[tid] = start[tid];
+            // finished (now or in an earlier round)
+            ask_nothing(qs, qg, start, dim);
             if (st.phase != kPhaseDone && tid == 0)
             {
                 st.phase = kPhaseDone, st.slot = a;
-                st.path_len = st.status == VMV_PLAN_SOLVED ? trace_path(st, pool, parent, P, start, goal, nullptr) : 0u;
+                st.path_len = 0u;
+                if (st.status == VMV_PLAN_SOLVED)  // a direct solution is (start, goal)
+                    st.path_len = st.new_i == kNone ? 2u : trace_path(st.a_side, st.new_i, st.prev, pool, parent, dim, M, nullptr);
                 D.state[p] = st;
                 D.done[p] = 1;
             }
@@ -343,8 +223,12 @@ namespace vmv
             if (p >= n) return;
             const RrtcState st = D.state[p];
             if (st.phase != kPhaseDone || st.status != VMV_PLAN_SOLVED) return;
-            (void) trace_path(st, D.pool + (size_t) p * P.max_samples * P.dim, D.parent + (size_t) p * P.max_samples, P,
-                              D.starts + (size_t) p * P.dim, D.goals + (size_t) p * P.dim, paths + offsets[p] * P.dim);
+            float *out = paths + offsets[p] * P.dim;
+            if (st.new_i == kNone)  // direct
+                for (uint32_t j = 0; j < P.dim; ++j) out[j] = D.starts[(size_t) p * P.dim + j], out[P.dim + j] = D.goals[(size_t) p * P.dim + j];
+            else
+                (void) trace_path(st.a_side, st.new_i, st.prev, D.pool + (size_t) p * P.max_samples * P.dim,
+                                  D.parent + (size_t) p * P.max_samples, P.dim, P.max_samples, out);
         }
 
     // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
@@ -358,37 +242,18 @@ namespace vmv
         P.balance = S.balance ? 1u : 0u, P.range = S.range, P.tree_ratio = S.tree_ratio;
         for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
         const uint32_t check_every = S.check_every ? S.check_every : kRrtcDefaultCheckEvery;
-        const size_t qn = n * (size_t) dim;
         hipStream_t stream = nullptr;
 
         DeviceBuffers mem;
+        LockstepBuffers B;
         RrtcArrays D{};
-        float *d_starts = nullptr, *d_goals = nullptr;
-        uint64_t *d_skips = nullptr, *d_bits = nullptr, *d_offsets = nullptr;
-        uint32_t *d_active = nullptr;
         VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
         VMV_LOCKSTEP_HIP(mem.alloc(&D.pool, n * (size_t) S.max_samples * (size_t) dim));
         VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) S.max_samples));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_starts, qn));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_goals, qn));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_active, n));
-        VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
-        VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (n + 63) / 64));
-        VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n));
-        VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
-        uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
-        D.starts = d_starts, D.goals = d_goals, D.skips = d_skips, D.active = d_active, D.bits = d_bits;
-
-        VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_starts, starts, qn * 4, hipMemcpyHostToDevice, stream));
-        VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_goals, goals, qn * 4, hipMemcpyHostToDevice, stream));
-        if (skips)
-            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_skips, skips, n * 8, hipMemcpyHostToDevice, stream));
-        else
-            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_skips, 0, n * 8, stream));
-        VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((n + 63) / 64) * 8, stream));
+        if (int rc = B.alloc(mem, n, n, 1, (size_t) dim, stream); rc != VMV_OK) return rc;
+        if (int rc = upload_problems(mem, n, (size_t) dim, starts, goals, skips, stream, &D.starts, &D.goals, &D.skips); rc != VMV_OK)
+            return rc;
+        D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits, D.done = B.done;
         const uint32_t n32 = (uint32_t) n;
         hipLaunchKernelGGL(rrtc_init_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream, P, D, n32);
         VMV_LOCKSTEP_HIP(hipGetLastError());
@@ -396,15 +261,14 @@ namespace vmv
         std::vector<uint32_t> active(n);
         std::vector<const vmv_env *> active_envs(envs, envs + n);
         for (size_t k = 0; k < n; ++k) active[k] = (uint32_t) k;
-        VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), n * 4, hipMemcpyHostToDevice));
+        VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), n * 4, hipMemcpyHostToDevice));
 
         // every problem ends within 1 + max_iterations + max_samples questions (each question after the direct one belongs
         // to a new iteration or adds a node): a bound on the rounds that does not depend on the device's answers
         const uint64_t max_rounds = 2ull + (uint64_t) S.max_iterations + (uint64_t) S.max_samples + check_every;
         uint64_t rounds = 0;
-        const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
         const auto step = [&](uint32_t na) { hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D); };
-        if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, L, "vmv_rrtc_multi",
+        if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), "vmv_rrtc_multi",
                                      "rrtc_step_kernel", step, rounds);
             rc != VMV_OK)
             return rc;
@@ -414,8 +278,6 @@ namespace vmv
         VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(RrtcState), hipMemcpyDeviceToHost));
         plans->n = n, plans->dim = dim, plans->rounds = rounds, plans->questions = 0;
         plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
-        std::vector<uint64_t> path_offsets(n);
-        uint64_t total = 0;
         for (size_t k = 0; k < n; ++k)
         {
             const RrtcState &st = states[k];
@@ -424,21 +286,13 @@ namespace vmv
             plans->sizes2[2 * k] = st.n[st.a_side], plans->sizes2[2 * k + 1] = st.n[st.a_side ^ 1u];
             plans->path_lengths[k] = st.path_len;
             plans->questions += st.questions;
-            path_offsets[k] = total;
-            total += st.path_len;
         }
-        plans->paths.resize(total * (size_t) dim);
-        if (total)
-        {
-            float *d_paths = nullptr;
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, total * (size_t) dim));
-            VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, path_offsets.data(), n * 8, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(rrtc_trace_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream, P, D, n32,
-                               d_offsets, d_paths);
-            VMV_LOCKSTEP_HIP(hipGetLastError());
-            VMV_LOCKSTEP_HIP(hipMemcpy(plans->paths.data(), d_paths, total * (size_t) dim * 4, hipMemcpyDeviceToHost));
-        }
-        return VMV_OK;
+        return pack_paths(mem, B.path_offsets, plans->path_lengths, (size_t) dim, nullptr, "rrtc_trace_kernel",
+                          [&](const uint64_t *d_offsets, float *d_paths) {
+                              hipLaunchKernelGGL(rrtc_trace_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream,
+                                                 P, D, n32, d_offsets, d_paths);
+                          },
+                          plans->paths);
     }
     }  // namespace
 }  // namespace vmv
@@ -450,19 +304,10 @@ extern "C"
     {
         // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
         // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
-        const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kRrtcMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_problems >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_problems; ++k)
-            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+        int dim = 0;
+        if (int rc = vmv::check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
         if (!std::isfinite(settings->range) || !(settings->range > 0.f) || settings->max_samples < 2) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_problems; ++k)
-        {
-            const uint64_t skip = halton_skips ? halton_skips[k] : 0;
-            if (skip > 1000000ull || skip + settings->max_iterations > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
-        }
-        if (!halton_skips && settings->max_iterations > 1000000u) return VMV_ERR_INVALID_ARGUMENT;
+        if (!vmv::halton_skips_ok(halton_skips, n_problems, settings->max_iterations)) return VMV_ERR_INVALID_ARGUMENT;
         return vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
             float lower[16], span[16], descale[16];
             const int rc = vmv_robot_bounds(robot, lower, span, descale);

@@ -38,7 +38,6 @@ namespace vmv
     namespace
     {
         constexpr uint32_t kSimpBlock = kWave;  // one wave per path: its answers are one ballot-sized word
-        constexpr uint32_t kSimpMaxDim = 16;
         constexpr uint32_t kSimpDefaultCheckEvery = 16;
         constexpr uint32_t kSimpDefaultQuestions = 16;
         constexpr uint32_t kSimpDefaultWaypoints = 2048;
@@ -422,40 +421,32 @@ namespace vmv
                 if (len > 2) active.push_back((uint32_t) k), active_envs.push_back(envs[k]);  // shorter ones ask nothing
             }
             offsets64[n] = total_in;
-            const size_t na0 = active.size(), qn = std::max<size_t>(na0, 1) * W * dim;
+            const size_t na0 = active.size();
 
             DeviceBuffers mem;
+            LockstepBuffers B;
             SimplifyArrays D{};
             float *d_points = nullptr;
-            uint64_t *d_offsets = nullptr, *d_bits = nullptr, *d_out_offsets = nullptr;
-            uint32_t *d_active = nullptr;
+            uint64_t *d_offsets = nullptr;
             VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.buf, n * 2u * (size_t) P.max_waypoints * dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.cand, n * kSimpMaxCandidates));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_points, total_in * dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n + 1));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_active, std::max<size_t>(na0, 1)));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_start, qn));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.q_goal, qn));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (na0 * W + 63) / 64 + 1));
-            VMV_LOCKSTEP_HIP(mem.alloc(&D.done, n));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_out_offsets, n));
-            VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
-            uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
-            D.points = d_points, D.offsets = d_offsets, D.active = d_active, D.bits = d_bits;
+            if (int rc = B.alloc(mem, n, na0, W, dim, stream); rc != VMV_OK) return rc;
+            D.points = d_points, D.offsets = d_offsets, D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits;
+            D.done = B.done;
 
             if (total_in) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, total_in * dim * 4, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
-            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, ((na0 * W + 63) / 64 + 1) * 8, stream));
             const uint32_t n32 = (uint32_t) n;
             hipLaunchKernelGGL(simplify_init_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D);
             VMV_LOCKSTEP_HIP(hipGetLastError());
-            if (na0) VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), na0 * 4, hipMemcpyHostToDevice));
+            if (na0) VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), na0 * 4, hipMemcpyHostToDevice));
 
             uint64_t rounds = 0;
-            const LockstepArrays L{d_active, D.q_start, D.q_goal, d_bits, D.done, h_done, n};
             const auto step = [&](uint32_t na) { hipLaunchKernelGGL(simplify_step_kernel, dim3(na), dim3(kSimpBlock), 0, stream, P, D); };
-            if (int rc = lockstep_rounds(robot, stream, check_every, round_bound(P, longest, check_every), W, active, active_envs, L,
+            if (int rc = lockstep_rounds(robot, stream, check_every, round_bound(P, longest, check_every), W, active, active_envs, B.arrays(),
                                          "vmv_simplify_multi", "simplify_step_kernel", step, rounds);
                 rc != VMV_OK)
                 return rc;
@@ -465,8 +456,6 @@ namespace vmv
             VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(SimplifyState), hipMemcpyDeviceToHost));
             paths->n = n, paths->dim = (int) dim, paths->rounds = rounds, paths->total_questions = 0;
             paths->status.resize(n), paths->iterations.resize(n), paths->lengths.resize(n), paths->questions.resize(n);
-            std::vector<uint64_t> out_offsets(n);
-            uint64_t total = 0;
             for (size_t k = 0; k < n; ++k)
             {
                 const SimplifyState &st = states[k];
@@ -475,20 +464,12 @@ namespace vmv
                 paths->lengths[k] = st.size;
                 paths->questions[k] = st.questions;
                 paths->total_questions += st.questions;
-                out_offsets[k] = total;
-                total += st.size;
             }
-            paths->points.resize(total * dim);
-            if (total)
-            {
-                float *d_out = nullptr;
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_out, total * dim));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_out_offsets, out_offsets.data(), n * 8, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(simplify_gather_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D, d_out_offsets, d_out);
-                VMV_LOCKSTEP_HIP(hipGetLastError());
-                VMV_LOCKSTEP_HIP(hipMemcpy(paths->points.data(), d_out, total * dim * 4, hipMemcpyDeviceToHost));
-            }
-            return VMV_OK;
+            return pack_paths(mem, B.path_offsets, paths->lengths, dim, nullptr, "simplify_gather_kernel",
+                              [&](const uint64_t *d_out_offsets, float *d_out) {
+                                  hipLaunchKernelGGL(simplify_gather_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D, d_out_offsets, d_out);
+                              },
+                              paths->points);
         }
     }  // namespace
 }  // namespace vmv
@@ -501,7 +482,7 @@ extern "C"
         // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
         // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
         const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kSimpMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
         if (!settings || !out || (n_paths > 0 && (!envs || !offsets))) return VMV_ERR_INVALID_ARGUMENT;
         const vmv_simplify_settings &S = *settings;
         const uint32_t W = S.questions_per_round ? S.questions_per_round : vmv::kSimpDefaultQuestions;
