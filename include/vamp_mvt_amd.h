@@ -279,7 +279,8 @@ size_t vmv_shard_words(size_t n, int world);
 int vmv_halton_configs(int robot, uint64_t skip, float *d_q, size_t n, void *stream);
 
 /* ---- lockstep planner: many independent RRT-Connect problems in one call ------------------------------- */
-/* RRT-Connect (planning/rrtc.hh:33-245 without dynamic domain, one goal) for n_problems problems at once, problem p from
+/* RRT-Connect (planning/rrtc.hh:33-245 without dynamic domain, one goal, start_tree_first = false; vmv_rrtc_multi_goals
+ * below has the three) for n_problems problems at once, problem p from
  * starts[p] to goals[p] ([n_problems][dimension] host arrays) in envs[p], its samples the Halton samples
  * halton_skips[p] + 1, + 2, ... (halton_skips NULL = all 0).  The problems advance in lockstep rounds: per round a step
  * kernel (nearest neighbour, extension, connect march, tree bookkeeping, termination; one workgroup per unfinished
@@ -322,6 +323,38 @@ int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterati
  * VMV_ERR_CAPACITY if capacity_floats is too small (nothing is written) */
 int vmv_plans_paths(const vmv_plans *plans, float *out, size_t capacity_floats);
 int vmv_plans_destroy(vmv_plans *plans);
+/* vmv_rrtc_multi with the three things of planning/rrtc.hh:33-245 it leaves out ("Goal sets, dynamic domain,
+ * start_tree_first"); with all three off and one goal per problem the result is vmv_rrtc_multi's, byte for byte.
+ *   Goal sets: goals is [goal_offsets[n_problems]][dimension] and problem p owns goals [goal_offsets[p],
+ *     goal_offsets[p + 1]) (goal_offsets NULL = one goal per problem, goals [n_problems][dimension]).  The questions
+ *     start -> goal g are asked in order of g, one per round; the first valid one ends the problem with (start, goal g).
+ *     Otherwise every goal is a root of the goal tree (goal g at index g).  A non-finite goal is never the nearest node.
+ *   Dynamic domain (rrtc.hh:121-126, 148-155, 226-237): every node has a radius, unset (FLT_MAX) at first.  An iteration
+ *     whose sample lies farther from its nearest node than that node's radius ends there: it has spent its iteration and
+ *     its draw and asks nothing, so the step kernel draws again within the same round.  A valid extension multiplies a set
+ *     radius of the nearest node by (1 + alpha); an invalid one sets an unset radius to `radius` and makes a set one
+ *     max(r * (1 - alpha), min_radius).  The connect march neither reads nor writes a radius.  Costs max_samples * 4 more
+ *     bytes per problem.
+ *   start_tree_first: the first iteration starts with A = goal tree, so that with equal sizes the balance rule hands the
+ *     first extension to the start tree (the reference's default; 0 is vmv_rrtc_multi's behaviour).
+ * Checks: those of vmv_rrtc_multi in its order, then goal_offsets not starting at 0 or decreasing, an empty goal set,
+ * 1 + a set's goals > max_samples, 2^31 goals or more in all; with dynamic_domain set, radius or min_radius not finite or
+ * <= 0, alpha not finite, < 0 or >= 1 (all VMV_ERR_INVALID_ARGUMENT; with dynamic_domain 0 the three values are not read).
+ * A call that fails leaves *out untouched.  n_problems == 0 is VMV_OK with an empty result.  vmv_plans_summary,
+ * vmv_plans_paths and vmv_plans_destroy work on the result as on vmv_rrtc_multi's. */
+typedef struct
+{
+    vmv_rrtc_settings base;
+    int dynamic_domain;          /* 0 / 1 */
+    float radius, alpha, min_radius; /* rrtc_settings.hh: 4, 0.0001, 1 */
+    int start_tree_first;        /* 0 / 1 */
+} vmv_rrtc_goals_settings;
+int vmv_rrtc_multi_goals(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                         const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings,
+                         vmv_plans **out);
+/* Per problem of a vmv_rrtc_multi_goals result (n_problems, may be NULL): the index, within its own set, of the goal its
+ * path ends in; UINT32_MAX = unsolved.  VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
+int vmv_plans_goal_indices(const vmv_plans *plans, uint32_t *goal_index);
 
 /* ---- batched PRM: many independent roadmap problems in one call ------------------------------------------ */
 /* A probabilistic roadmap per problem, for n_problems problems at once: problem p runs from starts[p] to goals[p] in

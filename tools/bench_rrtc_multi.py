@@ -12,9 +12,12 @@ is a host clock around a window; windows alternate between the two methods and a
 (tens of milliseconds per plan), so by default it runs an evenly spaced subset of the problems (--loop-problems, 0 = all)
 and is compared per problem; the lockstep call always runs all of them, and is also timed on that same subset.
 Agreement of the solved sets is reported, not asserted: planning.rrtc computes in float64 intermediates and may take
-another decision than the fp32 contract of rrtc_multi.
+another decision than the fp32 contract of rrtc_multi.  --dynamic-domain and --goals G measure the lockstep
+call with the reference's dynamic domain, and with G goals per problem (planning.rrtc_multi_goals); the loop takes the
+same goal arrays but has no dynamic domain.
 
-    python tools/bench_rrtc_multi.py [--reps 3] [--workloads mbm,cage] [--loop-problems 64] [--out DIR]
+    python tools/bench_rrtc_multi.py [--reps 3] [--workloads mbm,cage] [--loop-problems 64] [--dynamic-domain] [--goals G]
+                                     [--out DIR]
 """
 from __future__ import annotations
 
@@ -56,15 +59,41 @@ def workload_cage(n=1024):
             [env] * n, np.arange(n, dtype=np.int64))
 
 
+def goal_sets(robot, goals, envs, count, seed=29):
+    """per problem its own goal and count - 1 configurations valid in its environment, drawn uniformly with a fixed seed"""
+    n, dim, tries = len(envs), goals.shape[1], 256 * (count - 1)  # (about 1 in 25 uniform draws is valid in the sphere cage)
+    rng = np.random.default_rng(seed)
+    q = (robot._lower + robot._span * rng.random((n * tries, dim), dtype=np.float32)).astype(np.float32)
+    ok = robot.validate_batch_multi(q, envs, [tries] * n).reshape(n, tries)
+    q = q.reshape(n, tries, dim)
+    sets = []
+    for p in range(n):
+        extra = q[p][ok[p]][:count - 1]
+        if len(extra) != count - 1:
+            raise RuntimeError(f"problem {p}: {len(extra)} of {tries} drawn configurations are valid, {count - 1} are needed")
+        sets.append(np.concatenate([goals[p:p + 1], extra]))
+    return sets
+
+
 def run(name, starts, goals, envs, skips, args, log):
     robot = vamp.panda
     n = len(envs)
     s = planning.RRTCMultiSettings(range=args.range, max_iterations=args.max_iterations, max_samples=args.max_samples,
-                                   check_every=args.check_every)
+                                   check_every=args.check_every, dynamic_domain=args.dynamic_domain)
     s1 = planning.RRTCSettings(range=args.range, max_iterations=args.max_iterations, max_samples=args.max_samples)
     t0 = time.perf_counter()
     robot.prepare(envs)  # finalize + the robot part of every environment, outside the timed region
     prepare_s = time.perf_counter() - t0
+    if args.goals > 1:  # goal sets: rrtc_multi_goals against the loop of planning.rrtc with the same goal arrays
+        sets = goal_sets(robot, goals, envs, args.goals)
+        goals = np.empty(n, object)
+        goals[:] = sets
+
+        def rrtc_multi(starts, goals, envs, s, skips):
+            return planning.rrtc_multi_goals(robot, starts, list(goals), envs, s, skips)
+    else:
+        def rrtc_multi(starts, goals, envs, s, skips):
+            return planning.rrtc_multi(robot, starts, goals, envs, s, skips)
     sub = np.arange(n) if args.loop_problems <= 0 or args.loop_problems >= n else \
         np.unique(np.linspace(0, n - 1, args.loop_problems).astype(np.int64))
     samplers = []
@@ -74,10 +103,10 @@ def run(name, starts, goals, envs, skips, args, log):
         samplers.append(h)
 
     def multi_all():
-        return planning.rrtc_multi(robot, starts, goals, envs, s, skips)
+        return rrtc_multi(starts, goals, envs, s, skips)
 
     def multi_sub():
-        return planning.rrtc_multi(robot, starts[sub], goals[sub], [envs[i] for i in sub], s, skips[sub])
+        return rrtc_multi(starts[sub], goals[sub], [envs[i] for i in sub], s, skips[sub])
 
     def loop_sub():
         fresh = copy.deepcopy(samplers)  # (a run consumes its sampler; the copy is cheap next to the plans)
@@ -101,7 +130,8 @@ def run(name, starts, goals, envs, skips, args, log):
                 "ms_per_solved_plan": round(med / max(solved, 1), 5)}
 
     rec = {"workload": name, "settings": {"range": s.range, "max_iterations": s.max_iterations, "max_samples": s.max_samples,
-                                          "check_every": s.check_every}, "prepare_s": round(prepare_s, 3),
+                                          "check_every": s.check_every, "dynamic_domain": s.dynamic_domain, "goals": args.goals},
+           "prepare_s": round(prepare_s, 3),
            "multi_all": summary("multi_all", n), "multi_subset": summary("multi_subset", len(sub)),
            "loop_subset": summary("loop_subset", len(sub))}
     for k, count in (("multi_all", n), ("multi_subset", len(sub))):
@@ -130,6 +160,10 @@ def main():
     ap.add_argument("--max-iterations", type=int, default=10000)
     ap.add_argument("--max-samples", type=int, default=8192)
     ap.add_argument("--check-every", type=int, default=0)
+    ap.add_argument("--dynamic-domain", action="store_true",
+                    help="the reference's dynamic domain (radius 4, alpha 0.0001, min_radius 1); the loop of planning.rrtc has none")
+    ap.add_argument("--goals", type=int, default=1,
+                    help="goals per problem: its own and G - 1 valid configurations drawn with a fixed seed (rrtc_multi_goals)")
     ap.add_argument("--out", default=None, help="directory for rrtc_multi_bench.json")
     args = ap.parse_args()
     vamp.set_device(0)

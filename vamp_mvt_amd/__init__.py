@@ -758,6 +758,84 @@ class _Robot(types.ModuleType):
         return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
                     rounds=int(rounds.value), questions=int(questions.value))
 
+    def rrtc_multi_goals_raw(self, starts, goals, goal_counts, environments, settings, skips=None):
+        """vmv_rrtc_multi_goals: rrtc_multi_raw with goal sets, dynamic domain and start_tree_first.  goals: the goals of
+        all problems packed, [sum(goal_counts)][dim]; goal_counts: goals per problem (each at least 1), None = one each.
+        settings: those of rrtc_multi_raw and dynamic_domain, radius, alpha, min_radius, start_tree_first.
+        -> rrtc_multi_raw's dict plus goal_indices per problem (-1 = unsolved).  planning.rrtc_multi_goals is the
+        caller-facing form.  Every argument is checked before any library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        a, b = _f32(starts), _f32(goals)
+        if a.ndim != 2 or a.shape[1] != self._dim or b.ndim != 2 or b.shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] starts and packed [goals][{self._dim}] goals")
+        n = a.shape[0]
+        if goal_counts is None:
+            offsets = None
+            if b.shape[0] != n:
+                raise TypeError(f"expected one goal per problem, got {b.shape[0]} for {n} problems")
+        else:
+            counts = np.asarray(goal_counts)
+            if counts.shape != (n,) or (n and not np.issubdtype(counts.dtype, np.integer)):
+                raise TypeError(f"expected one goal set per problem, got shape {counts.shape} for {n} problems")
+            if n and (counts < 1).any():
+                raise TypeError("every problem needs at least one goal")
+            offsets = np.zeros(n + 1, np.uint64)
+            np.cumsum(counts, out=offsets[1:])
+            if int(offsets[n]) != b.shape[0]:
+                raise TypeError(f"expected {int(offsets[n])} packed goals, got {b.shape[0]}")
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        if skips is None:
+            sk = None
+        else:
+            sk = np.asarray(skips)
+            if sk.shape != (n,):
+                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
+            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+                raise ValueError("skips must be non-negative integers")
+            sk = np.ascontiguousarray(sk, np.uint64)
+        rng, ratio = float(settings.range), float(settings.tree_ratio)
+        max_it, max_s, every = int(settings.max_iterations), int(settings.max_samples), int(getattr(settings, "check_every", 0))
+        if not (math.isfinite(rng) and rng > 0):
+            raise ValueError("range must be finite and positive")
+        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32):
+            raise ValueError("max_iterations, max_samples (>= 2) and check_every must fit 32 bits")
+        if offsets is not None and n and int(np.diff(offsets).max()) + 1 > max_s:
+            raise ValueError("the start and the goals of a problem must fit max_samples")
+        dynamic = bool(getattr(settings, "dynamic_domain", False))
+        radius, alpha = float(getattr(settings, "radius", 4.0)), float(getattr(settings, "alpha", 0.0001))
+        min_radius = float(getattr(settings, "min_radius", 1.0))
+        if dynamic:
+            if not (math.isfinite(radius) and radius > 0 and math.isfinite(min_radius) and min_radius > 0):
+                raise ValueError("radius and min_radius must be finite and positive")
+            if not (math.isfinite(alpha) and 0 <= alpha < 1):
+                raise ValueError("alpha must be in [0, 1)")
+        cs = _lib.RrtcGoalsSettings(_lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every), int(dynamic),
+                                    radius, alpha, min_radius, int(bool(getattr(settings, "start_tree_first", False))))
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        plans = ctypes.c_void_p()
+        check(lib.vmv_rrtc_multi_goals(self._id, handles, n, _fp(a), _fp(b),
+                                       None if offsets is None else offsets.ctypes.data_as(_lib.c_size_p),
+                                       None if sk is None else sk.ctypes.data_as(_lib.c_u64_p), ctypes.byref(cs),
+                                       ctypes.byref(plans)), "vmv_rrtc_multi_goals")
+        try:
+            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
+                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
+                  "vmv_plans_summary")
+            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
+            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+            goal_indices = np.zeros(n, np.uint32)
+            check(lib.vmv_plans_goal_indices(plans, goal_indices.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_goal_indices")
+        finally:
+            lib.vmv_plans_destroy(plans)
+        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
+                    rounds=int(rounds.value), questions=int(questions.value), goal_indices=goal_indices.view(np.int32).copy())
+
     def aorrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
         """vmv_aorrtc_multi: AORRTC for many problems (a first solution by rrtc_multi's contract, simplified by
         simplify_multi's, then cost-bounded RRT-Connect searches in lockstep), the arguments those of rrtc_multi_raw.

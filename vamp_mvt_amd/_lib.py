@@ -30,6 +30,12 @@ class RrtcSettings(ctypes.Structure):
                 ("max_iterations", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
 
 
+class RrtcGoalsSettings(ctypes.Structure):
+    """vmv_rrtc_goals_settings"""
+    _fields_ = [("base", RrtcSettings), ("dynamic_domain", ctypes.c_int), ("radius", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("min_radius", ctypes.c_float), ("start_tree_first", ctypes.c_int)]
+
+
 class PrmSettings(ctypes.Structure):
     """vmv_prm_settings"""
     _fields_ = [("n_samples", ctypes.c_uint32), ("k", ctypes.c_uint32), ("radius", ctypes.c_float),
@@ -163,6 +169,9 @@ def _load():
         "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
         "vmv_rrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(RrtcSettings),
                                ctypes.POINTER(V)]),
+        "vmv_rrtc_multi_goals": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_size_p, c_u64_p,
+                                     ctypes.POINTER(RrtcGoalsSettings), ctypes.POINTER(V)]),
+        "vmv_plans_goal_indices": (I, [V, c_u32_p]),
         "vmv_plans_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_plans_paths": (I, [V, c_float_p, S]),
         "vmv_plans_destroy": (I, [V]),

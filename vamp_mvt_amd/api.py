@@ -303,19 +303,34 @@ def install(robot):
 
     def rrtc_multi(starts, goals, environments, settings, skips=None):
         """planning.rrtc_multi with this robot: many RRT-Connect problems in lockstep on the device ->
-        list[PlanningResult] (each with `status`; nanoseconds is the whole call's time divided by the problems)"""
+        list[PlanningResult] (each with `status`; nanoseconds is the whole call's time divided by the problems).  A
+        planning.RRTCMultiSettings is taken as it is, its dynamic_domain and start_tree_first included.  A
+        reference-shaped RRTCSettings is reduced to range, balance, tree_ratio, max_iterations and max_samples: its
+        dynamic_domain, radius, alpha, min_radius and start_tree_first are NOT used."""
         t0 = time.perf_counter_ns()
-        s = planning.RRTCMultiSettings(range=float(settings.range), balance=bool(settings.balance),
-                                       tree_ratio=float(settings.tree_ratio), max_iterations=int(settings.max_iterations),
-                                       max_samples=int(settings.max_samples), check_every=int(getattr(settings, "check_every", 0)))
-        results = planning.rrtc_multi(robot, starts, goals, environments, s, skips)
+        return timed_results(planning.rrtc_multi(robot, starts, goals, environments, multi_settings(settings), skips), t0)
+
+    def multi_settings(settings):
+        if isinstance(settings, planning.RRTCMultiSettings):
+            return settings
+        return planning.RRTCMultiSettings(range=float(settings.range), balance=bool(settings.balance),
+                                          tree_ratio=float(settings.tree_ratio), max_iterations=int(settings.max_iterations),
+                                          max_samples=int(settings.max_samples), check_every=int(getattr(settings, "check_every", 0)))
+
+    def timed_results(results, t0):
         each = (time.perf_counter_ns() - t0) // max(len(results), 1)
         out = []
         for r in results:
             res = as_result(r, t0)
-            res.nanoseconds, res.status = each, r.status
+            res.nanoseconds, res.status, res.goal_index = each, r.status, r.goal_index
             out.append(res)
         return out
+
+    def rrtc_multi_goals(starts, goal_sets, environments, settings, skips=None):
+        """planning.rrtc_multi_goals with this robot: rrtc_multi with a [G_p][dim] set of goals per problem ->
+        list[PlanningResult] (each with `status` and `goal_index`).  The settings are taken as rrtc_multi takes them."""
+        t0 = time.perf_counter_ns()
+        return timed_results(planning.rrtc_multi_goals(robot, starts, goal_sets, environments, multi_settings(settings), skips), t0)
 
     def aorrtc_multi(starts, goals, environments, settings, skips=None):
         """planning.aorrtc_multi with this robot and the reference-shaped AORRTCSettings -> list[PlanningResult] (each
@@ -493,6 +508,7 @@ def install(robot):
 
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
+    robot.rrtc_multi_goals = rrtc_multi_goals
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
     robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]

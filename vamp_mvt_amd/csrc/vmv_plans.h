@@ -16,6 +16,10 @@ struct vmv_plans
     std::vector<float> paths;  // packed in problem order
     uint64_t rounds = 0, questions = 0;
 
+    // vmv_rrtc_multi_goals only (vmv_plans_goal_indices)
+    bool rrtc_goals = false;
+    std::vector<uint32_t> goal_indices;  // [n] the goal, within its own set, a solved path ends in; UINT32_MAX = unsolved
+
     // vmv_prm_multi only (vmv_plans_roadmap_*)
     bool prm = false, kept = false;  // made by vmv_prm_multi; with keep_roadmaps
     uint32_t n_samples = 0;

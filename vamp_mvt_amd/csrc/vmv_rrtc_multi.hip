@@ -1,4 +1,5 @@
-// vmv_rrtc_multi.hip — lockstep RRT-Connect over many independent problems (vmv_rrtc_multi).
+// vmv_rrtc_multi.hip — lockstep RRT-Connect over many independent problems (vmv_rrtc_multi), and the same
+// with goal sets, dynamic domain and start_tree_first (vmv_rrtc_multi_goals): one set of kernels serves both.
 //
 // Every problem is a state machine in device memory, advanced by the rounds of vmv_lockstep.h with one question per
 // problem: rrtc_step_kernel (one workgroup per unfinished problem) consumes the answer to the problem's previous edge
@@ -11,6 +12,12 @@
 // tree from the back; the planner's two size rules keep |A| + |B| <= max_samples.  The pool's addressing, the nearest
 // search and the path trace are vmv_two_trees.h's, shared with vmv_aorrtc_multi.
 // Every store is a plain vector store by the owning workgroup; no atomics.
+//
+// Goal sets: the direct phase asks start -> goal g in order of g, one question per round; the goal tree then starts with
+// all goals as roots (goal g at index g, its own parent), which the nearest search, the march and the trace take as they
+// are.  Dynamic domain: a radius per node (radii, FLT_MAX = unset), tested after the nearest search of an iteration - a
+// rejected sample asks nothing, so the step kernel draws again in the same launch - and updated when the extension's
+// answer arrives; the march neither reads nor writes a radius.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
@@ -26,11 +33,12 @@ namespace vmv
     {
         constexpr uint32_t kRrtcBlock = kTreeBlock;
         constexpr uint32_t kRrtcDefaultCheckEvery = 16;
+        constexpr float kRadiusUnset = 3.402823466e+38f;  // FLT_MAX: a node no extension has failed from yet
 
         enum : uint32_t
         {
             kPhaseInit = 0,    // nothing asked yet
-            kPhaseDirect = 1,  // start -> goal is in flight
+            kPhaseDirect = 1,  // start -> goal k is in flight
             kPhaseExtend = 2,  // near -> new is in flight (new sits in A's next slot, not yet counted)
             kPhaseMarch = 3,   // step k of the connect march is in flight (w sits in B's next slot, not yet counted)
             kPhaseDone = 4
@@ -44,7 +52,7 @@ namespace vmv
             uint32_t slot;     // position of the question in flight in its round's arrays
             uint32_t new_i;    // `new` in A (kNone on a direct solution)
             uint32_t bi, prev; // B's node nearest to `new`; last node of the march
-            uint32_t k, n_steps;
+            uint32_t k, n_steps;  // k: the march's step; in the direct phase the goal asked; once done, the goal a solved path ends in
             float bd;
             uint32_t path_len, questions;
         };
@@ -54,6 +62,8 @@ namespace vmv
         {
             uint32_t dim, max_samples, max_iterations, balance;
             float range, tree_ratio;
+            uint32_t dynamic_domain, start_tree_first;  // rrtc_settings.hh; both 0 for vmv_rrtc_multi
+            float radius, alpha, min_radius;
             float lower[kPlanMaxDim], span[kPlanMaxDim];
         };
 
@@ -62,7 +72,10 @@ namespace vmv
             RrtcState *state;          // [n_problems]
             float *pool;               // [n_problems][max_samples][dim]
             uint32_t *parent;          // [n_problems][max_samples], indices within the node's own tree
-            const float *starts, *goals;  // [n_problems][dim]
+            float *radii;              // [n_problems][max_samples] with dynamic domain, else NULL
+            const float *starts;       // [n_problems][dim]
+            const float *goals;        // [n_goals][dim], problem p owns goals [goal_offsets[p], goal_offsets[p + 1])
+            const uint32_t *goal_offsets;  // [n_problems + 1]; NULL = one goal per problem
             const uint64_t *skips;     // [n_problems]
             const uint32_t *active;    // [n_active] problem of each workgroup
             float *q_start, *q_goal;   // [n_active][dim] the round's questions
@@ -70,15 +83,34 @@ namespace vmv
             uint8_t *done;             // [n_problems]
         };
 
+        __device__ __forceinline__ uint32_t first_goal(const RrtcArrays &D, uint32_t p) { return D.goal_offsets ? D.goal_offsets[p] : p; }
+        __device__ __forceinline__ uint32_t goal_count(const RrtcArrays &D, uint32_t p)
+        {
+            return D.goal_offsets ? D.goal_offsets[p + 1] - D.goal_offsets[p] : 1u;
+        }
+
         __global__ __launch_bounds__(kRrtcBlock) void rrtc_init_kernel(const RrtcParams P, const RrtcArrays D, const uint32_t n)
         {
             const uint32_t p = blockIdx.x * kRrtcBlock + threadIdx.x;
             if (p >= n) return;
-            init_roots(D.pool + (size_t) p * P.max_samples * P.dim, D.parent + (size_t) p * P.max_samples,
-                       D.starts + (size_t) p * P.dim, D.goals + (size_t) p * P.dim, P.dim, P.max_samples);
+            const uint32_t M = P.max_samples, g0 = first_goal(D, p), G = goal_count(D, p);
+            float *pool = D.pool + (size_t) p * M * P.dim;
+            uint32_t *parent = D.parent + (size_t) p * M;
+            init_roots(pool, parent, D.starts + (size_t) p * P.dim, D.goals + (size_t) g0 * P.dim, P.dim, M);
+            for (uint32_t g = 1; g < G; ++g)  // the further goals of a set: roots 1 .. G - 1 of the goal tree
+            {
+                for (uint32_t j = 0; j < P.dim; ++j) pool[node_at(1, g, M) * P.dim + j] = D.goals[(size_t) (g0 + g) * P.dim + j];
+                parent[node_at(1, g, M)] = g;
+            }
+            if (D.radii)
+            {
+                D.radii[(size_t) p * M + node_at(0, 0, M)] = kRadiusUnset;
+                for (uint32_t g = 0; g < G; ++g) D.radii[(size_t) p * M + node_at(1, g, M)] = kRadiusUnset;
+            }
             RrtcState st{};
             st.phase = kPhaseInit, st.status = VMV_PLAN_MAX_ITERATIONS;
-            st.n[0] = st.n[1] = 1;
+            st.n[0] = st.n[1] = 1;  // (a direct solution reports [1, 1]; the goal tree counts its G roots once it is used)
+            st.a_side = P.start_tree_first ? 1u : 0u;
             st.new_i = kNone;
             D.state[p] = st;
             D.done[p] = 0;
@@ -96,7 +128,8 @@ namespace vmv
             float *pool = D.pool + (size_t) p * M * dim;
             uint32_t *parent = D.parent + (size_t) p * M;
             float *qs = D.q_start + (size_t) a * dim, *qg = D.q_goal + (size_t) a * dim;
-            const float *start = D.starts + (size_t) p * dim, *goal = D.goals + (size_t) p * dim;
+            float *radii = D.radii ? D.radii + (size_t) p * M : nullptr;
+            const float *start = D.starts + (size_t) p * dim, *goals = D.goals + (size_t) first_goal(D, p) * dim;
             const float R = P.range;
             // the nearest node is the first of the least distance to s_t: the key is the distance itself
             const auto to_target = [&](const float *q, size_t) {
@@ -109,8 +142,8 @@ namespace vmv
                 act = kFinish;
             else if (st.phase == kPhaseInit)
             {
-                if (tid < dim) qs[tid] = start[tid], qg[tid] = goal[tid];
-                st.phase = kPhaseDirect, st.slot = a, st.questions = 1;
+                if (tid < dim) qs[tid] = start[tid], qg[tid] = goals[tid];
+                st.phase = kPhaseDirect, st.slot = a, st.questions = 1, st.k = 0;
                 if (tid == 0) D.state[p] = st;
                 return;
             }
@@ -120,10 +153,35 @@ namespace vmv
                 const uint32_t sa = st.a_side, sb = sa ^ 1u;
                 if (st.phase == kPhaseDirect)
                 {
-                    if (ans) st.status = VMV_PLAN_SOLVED, st.new_i = kNone, act = kFinish;
+                    const uint32_t G = goal_count(D, p);
+                    if (ans)
+                        st.status = VMV_PLAN_SOLVED, st.new_i = kNone, act = kFinish;  // st.k is the goal
+                    else if (++st.k < G)  // the next goal of the set, in the next round
+                    {
+                        if (tid < dim) qs[tid] = start[tid], qg[tid] = goals[(size_t) st.k * dim + tid];
+                        st.slot = a, ++st.questions;
+                        if (tid == 0) D.state[p] = st;
+                        return;
+                    }
+                    else
+                        st.n[1] = G;  // no goal is direct: every goal is a root of the goal tree
                 }
                 else if (st.phase == kPhaseExtend)
                 {
+                    if (radii && tid == 0)  // the node the extension left from is the parent of A's next slot
+                    {
+                        // The one radius store of this launch.  A failed extension falls through to the loop below, whose
+                        // first sample is often nearest to this same node: the loop's barriers (after its target is
+                        // written, and inside nearest()) lie between this store and every thread's read of radii there.
+                        const size_t near_at = node_at(sa, parent[node_at(sa, count_of(st.n, sa), M)], M);
+                        const float r = radii[near_at];
+                        if (ans)
+                        {
+                            if (r != kRadiusUnset) radii[near_at] = r * (1.f + P.alpha);
+                        }
+                        else
+                            radii[near_at] = r == kRadiusUnset ? P.radius : fmaxf(r * (1.f - P.alpha), P.min_radius);
+                    }
                     if (ans)
                     {
                         st.new_i = grow(st.n, sa);
@@ -166,7 +224,11 @@ namespace vmv
                         qg[tid] = w;
                     }
                     st.phase = kPhaseMarch, st.slot = a, ++st.questions;
-                    if (tid == 0) parent[node_at(sb, count_of(st.n, sb), M)] = st.prev, D.state[p] = st;
+                    if (tid == 0)
+                    {
+                        parent[node_at(sb, count_of(st.n, sb), M)] = st.prev, D.state[p] = st;
+                        if (radii) radii[node_at(sb, count_of(st.n, sb), M)] = kRadiusUnset;
+                    }
                     return;
                 }
             }
@@ -196,9 +258,16 @@ namespace vmv
                     uint32_t ni;
                     nearest<false>(pool, sa, count_of(st.n, sa), dim, M, to_target, s_rd, nullptr, s_ri, d, ni);
                     if (ni == kNone || !(d > 0.f)) continue;
+                    // dynamic domain: the sample lies outside the nearest node's radius - the iteration and its draw are
+                    // spent, nothing is asked (every thread reads the same word, so the branch is the workgroup's)
+                    if (radii && radii[node_at(sa, ni, M)] < d) continue;
                     ask_extension(pool, node_at(sa, ni, M), node_at(sa, count_of(st.n, sa), M), dim, s_t, d, R, qs, qg);
                     st.phase = kPhaseExtend, st.slot = a, ++st.questions;
-                    if (tid == 0) parent[node_at(sa, count_of(st.n, sa), M)] = ni, D.state[p] = st;
+                    if (tid == 0)
+                    {
+                        parent[node_at(sa, count_of(st.n, sa), M)] = ni, D.state[p] = st;
+                        if (radii) radii[node_at(sa, count_of(st.n, sa), M)] = kRadiusUnset;
+                    }
                     return;
                 }
             }
@@ -209,8 +278,16 @@ namespace vmv
             {
                 st.phase = kPhaseDone, st.slot = a;
                 st.path_len = 0u;
-                if (st.status == VMV_PLAN_SOLVED)  // a direct solution is (start, goal)
+                if (st.status == VMV_PLAN_SOLVED)  // a direct solution is (start, goal k)
+                {
                     st.path_len = st.new_i == kNone ? 2u : trace_path(st.a_side, st.new_i, st.prev, pool, parent, dim, M, nullptr);
+                    if (st.new_i != kNone)  // the goal is the root the goal tree's branch ends in
+                    {
+                        uint32_t i = st.a_side ? st.new_i : st.prev;
+                        while (parent[node_at(1, i, M)] != i) i = parent[node_at(1, i, M)];
+                        st.k = i;
+                    }
+                }
                 D.state[p] = st;
                 D.done[p] = 1;
             }
@@ -225,21 +302,26 @@ namespace vmv
             if (st.phase != kPhaseDone || st.status != VMV_PLAN_SOLVED) return;
             float *out = paths + offsets[p] * P.dim;
             if (st.new_i == kNone)  // direct
-                for (uint32_t j = 0; j < P.dim; ++j) out[j] = D.starts[(size_t) p * P.dim + j], out[P.dim + j] = D.goals[(size_t) p * P.dim + j];
+                for (uint32_t j = 0; j < P.dim; ++j)
+                    out[j] = D.starts[(size_t) p * P.dim + j], out[P.dim + j] = D.goals[(size_t) (first_goal(D, p) + st.k) * P.dim + j];
             else
                 (void) trace_path(st.a_side, st.new_i, st.prev, D.pool + (size_t) p * P.max_samples * P.dim,
                                   D.parent + (size_t) p * P.max_samples, P.dim, P.max_samples, out);
         }
 
     // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
-    // robot's part built.  lower / span: the robot's joint bounds (Robot::s_a, s_m).
+    // robot's part built.  lower / span: the robot's joint bounds (Robot::s_a, s_m).  goal_offsets: NULL = goals is
+    // [n][dim], one goal per problem.  `call` names the entry point in vmv_last_error().
     int rrtc_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
-                       const float *starts, const float *goals, const uint64_t *skips, const vmv_rrtc_settings &S,
-                       vmv_plans *plans)
+                       const float *starts, const float *goals, const size_t *goal_offsets, const uint64_t *skips,
+                       const vmv_rrtc_goals_settings &GS, const char *call, vmv_plans *plans)
     {
+        const vmv_rrtc_settings &S = GS.base;
         RrtcParams P{};
         P.dim = (uint32_t) dim, P.max_samples = S.max_samples, P.max_iterations = S.max_iterations;
         P.balance = S.balance ? 1u : 0u, P.range = S.range, P.tree_ratio = S.tree_ratio;
+        P.dynamic_domain = GS.dynamic_domain ? 1u : 0u, P.start_tree_first = GS.start_tree_first ? 1u : 0u;
+        P.radius = GS.radius, P.alpha = GS.alpha, P.min_radius = GS.min_radius;
         for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.span[j] = span[j];
         const uint32_t check_every = S.check_every ? S.check_every : kRrtcDefaultCheckEvery;
         hipStream_t stream = nullptr;
@@ -251,8 +333,31 @@ namespace vmv
         VMV_LOCKSTEP_HIP(mem.alloc(&D.pool, n * (size_t) S.max_samples * (size_t) dim));
         VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) S.max_samples));
         if (int rc = B.alloc(mem, n, n, 1, (size_t) dim, stream); rc != VMV_OK) return rc;
-        if (int rc = upload_problems(mem, n, (size_t) dim, starts, goals, skips, stream, &D.starts, &D.goals, &D.skips); rc != VMV_OK)
-            return rc;
+        if (P.dynamic_domain) VMV_LOCKSTEP_HIP(mem.alloc(&D.radii, n * (size_t) S.max_samples));
+        size_t max_goals = 1;  // of one problem: its direct questions
+        if (!goal_offsets)
+        {
+            if (int rc = upload_problems(mem, n, (size_t) dim, starts, goals, skips, stream, &D.starts, &D.goals, &D.skips); rc != VMV_OK)
+                return rc;
+        }
+        else
+        {
+            std::vector<uint32_t> offsets32(n + 1);
+            for (size_t k = 0; k <= n; ++k) offsets32[k] = (uint32_t) goal_offsets[k];
+            for (size_t k = 0; k < n; ++k) max_goals = std::max(max_goals, goal_offsets[k + 1] - goal_offsets[k]);
+            float *d_starts = nullptr, *d_goals = nullptr;
+            uint32_t *d_offsets = nullptr;
+            uint64_t *d_skips = nullptr;
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_starts, n * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_goals, goal_offsets[n] * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n + 1));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_skips, n));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_starts, starts, n * (size_t) dim * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_goals, goals, goal_offsets[n] * (size_t) dim * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_offsets, offsets32.data(), (n + 1) * 4, hipMemcpyHostToDevice));
+            if (int rc = upload_skips(d_skips, skips, n, stream); rc != VMV_OK) return rc;
+            D.starts = d_starts, D.goals = d_goals, D.goal_offsets = d_offsets, D.skips = d_skips;
+        }
         D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits, D.done = B.done;
         const uint32_t n32 = (uint32_t) n;
         hipLaunchKernelGGL(rrtc_init_kernel, dim3((n32 + kRrtcBlock - 1) / kRrtcBlock), dim3(kRrtcBlock), 0, stream, P, D, n32);
@@ -263,12 +368,12 @@ namespace vmv
         for (size_t k = 0; k < n; ++k) active[k] = (uint32_t) k;
         VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), n * 4, hipMemcpyHostToDevice));
 
-        // every problem ends within 1 + max_iterations + max_samples questions (each question after the direct one belongs
+        // every problem ends within G + max_iterations + max_samples questions (each question after the G direct ones belongs
         // to a new iteration or adds a node): a bound on the rounds that does not depend on the device's answers
-        const uint64_t max_rounds = 2ull + (uint64_t) S.max_iterations + (uint64_t) S.max_samples + check_every;
+        const uint64_t max_rounds = 1ull + max_goals + (uint64_t) S.max_iterations + (uint64_t) S.max_samples + check_every;
         uint64_t rounds = 0;
         const auto step = [&](uint32_t na) { hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D); };
-        if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), "vmv_rrtc_multi",
+        if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), call,
                                      "rrtc_step_kernel", step, rounds);
             rc != VMV_OK)
             return rc;
@@ -278,9 +383,11 @@ namespace vmv
         VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(RrtcState), hipMemcpyDeviceToHost));
         plans->n = n, plans->dim = dim, plans->rounds = rounds, plans->questions = 0;
         plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
+        plans->goal_indices.resize(n);
         for (size_t k = 0; k < n; ++k)
         {
             const RrtcState &st = states[k];
+            plans->goal_indices[k] = st.status == VMV_PLAN_SOLVED ? st.k : UINT32_MAX;
             plans->status[k] = (uint8_t) st.status;
             plans->iterations[k] = st.iterations;
             plans->sizes2[2 * k] = st.n[st.a_side], plans->sizes2[2 * k + 1] = st.n[st.a_side ^ 1u];
@@ -312,8 +419,55 @@ extern "C"
             float lower[16], span[16], descale[16];
             const int rc = vmv_robot_bounds(robot, lower, span, descale);
             if (rc != VMV_OK) return rc;
-            return vmv::rrtc_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, *settings, plans);
+            vmv_rrtc_goals_settings all{};  // the additions off
+            all.base = *settings;
+            return vmv::rrtc_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, nullptr, halton_skips, all,
+                                       "vmv_rrtc_multi", plans);
         });
+    }
+
+    int vmv_rrtc_multi_goals(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                             const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings,
+                             vmv_plans **out)
+    {
+        // vmv_rrtc_multi's checks in its order, then those of the goal table and of the dynamic domain's values
+        int dim = 0;
+        if (int rc = vmv::check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
+        const vmv_rrtc_settings &base = settings->base;
+        if (!std::isfinite(base.range) || !(base.range > 0.f) || base.max_samples < 2) return VMV_ERR_INVALID_ARGUMENT;
+        if (!vmv::halton_skips_ok(halton_skips, n_problems, base.max_iterations)) return VMV_ERR_INVALID_ARGUMENT;
+        if (goal_offsets && n_problems > 0)
+        {
+            if (goal_offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
+            for (size_t k = 0; k < n_problems; ++k)
+            {
+                if (goal_offsets[k + 1] <= goal_offsets[k]) return VMV_ERR_INVALID_ARGUMENT;  // decreasing, or an empty set
+                if (goal_offsets[k + 1] - goal_offsets[k] > (size_t) base.max_samples - 1) return VMV_ERR_INVALID_ARGUMENT;
+            }
+            if (goal_offsets[n_problems] >= (1ull << 31)) return VMV_ERR_INVALID_ARGUMENT;
+        }
+        if (settings->dynamic_domain)
+        {
+            if (!std::isfinite(settings->radius) || !(settings->radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
+            if (!std::isfinite(settings->min_radius) || !(settings->min_radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
+            if (!std::isfinite(settings->alpha) || !(settings->alpha >= 0.f) || !(settings->alpha < 1.f)) return VMV_ERR_INVALID_ARGUMENT;
+        }
+        const int rc = vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
+            float lower[16], span[16], descale[16];
+            const int rc = vmv_robot_bounds(robot, lower, span, descale);
+            if (rc != VMV_OK) return rc;
+            return vmv::rrtc_multi_run(robot, dim, lower, span, envs, n_problems, starts, goals, goal_offsets, halton_skips, *settings,
+                                       "vmv_rrtc_multi_goals", plans);
+        });
+        if (rc == VMV_OK) (*out)->rrtc_goals = true;
+        return rc;
+    }
+
+    int vmv_plans_goal_indices(const vmv_plans *plans, uint32_t *goal_index)
+    {
+        if (!plans || !plans->rrtc_goals) return VMV_ERR_INVALID_ARGUMENT;
+        if (goal_index && plans->n) std::memcpy(goal_index, plans->goal_indices.data(), plans->n * 4);
+        return VMV_OK;
     }
 
     int vmv_plans_summary(const vmv_plans *plans, uint8_t *status, uint32_t *iterations, uint32_t *sizes2, uint32_t *path_lengths,

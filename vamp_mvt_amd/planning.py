@@ -89,13 +89,20 @@ class RRTCSettings:
 class RRTCMultiSettings:
     """settings of `rrtc_multi`: those of RRTCSettings, except that max_samples defaults to 8,192 — every problem of a
     call owns a node pool of max_samples nodes on the device — and check_every (rounds between two looks of the host at
-    which problems are finished; 0 = the library's default)"""
+    which problems are finished; 0 = the library's default).  dynamic_domain with radius, alpha, min_radius, and
+    start_tree_first are rrtc_settings.hh's; their defaults here are OFF (the reference's are dynamic_domain=True and
+    start_tree_first=True), which is `rrtc_multi` as it always was"""
     range: float = 2.0
     balance: bool = True
     tree_ratio: float = 1.0
     max_iterations: int = 100000
     max_samples: int = 8192
     check_every: int = 0
+    dynamic_domain: bool = False
+    radius: float = 4.0
+    alpha: float = 0.0001
+    min_radius: float = 1.0
+    start_tree_first: bool = False
 
 
 @dataclass
@@ -200,6 +207,7 @@ class PlanningResult:
     searches: int = 0                 # aorrtc_multi: cost-bounded searches run
     improvements: int = 0             # aorrtc_multi: those that gave a cheaper path
     known_valid_edges: int = 0        # fcit_multi: edges the walk found valid
+    goal_index: int = -1              # rrtc_multi_goals: the goal of the problem's set the path ends in (-1 = unsolved)
 
     @property
     def solved(self):
@@ -311,9 +319,24 @@ def rrtc_multi(robot, starts, goals, environments, settings: RRTCMultiSettings |
 
     The default max_samples of this call is 8,192 (RRTCMultiSettings), not rrtc's 100,000: the node pool is
     allocated per problem, max_samples * (dim + 1) * 4 bytes each.  skips[p] + max_iterations may not exceed 1,000,000
-    (the Halton sequence's validity limit)."""
+    (the Halton sequence's validity limit).
+
+    With dynamic_domain or start_tree_first set in the settings (RRTCMultiSettings; both off by default) the call goes
+    through `rrtc_multi_goals`' entry point with one goal per problem, and the results carry `goal_index` 0."""
     s = settings or RRTCMultiSettings()
-    raw = robot.rrtc_multi_raw(starts, goals, environments, s, skips)
+    if _rrtc_additions_off(s):
+        return _rrtc_results(robot.rrtc_multi_raw(starts, goals, environments, s, skips))
+    return _rrtc_results(robot.rrtc_multi_goals_raw(starts, goals, None, environments, s, skips))
+
+
+def _rrtc_additions_off(s):
+    """whether the five fields RRTCMultiSettings has beyond vmv_rrtc_settings all have their defaults"""
+    d = RRTCMultiSettings()
+    return all(getattr(s, k, getattr(d, k)) == getattr(d, k)
+               for k in ("dynamic_domain", "radius", "alpha", "min_radius", "start_tree_first"))
+
+
+def _rrtc_results(raw):
     ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
     out = []
     for p in range(len(ends)):
@@ -321,9 +344,34 @@ def rrtc_multi(robot, starts, goals, environments, settings: RRTCMultiSettings |
         out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
                                   size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])],
                                   status=PLAN_STATUS[int(raw["status"][p])]))
+        if "goal_indices" in raw:
+            out[-1].goal_index = int(raw["goal_indices"][p])
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
+
+
+def rrtc_multi_goals(robot, starts, goal_sets, environments, settings: RRTCMultiSettings | None = None, skips=None):
+    """`rrtc_multi` with a set of goals per problem (rrtc.hh:33-38): problem p from starts[p] to any goal of goal_sets[p], a
+    [G_p][dim] array with G_p >= 1 (the IK solutions of one grasp pose, say; a [dim] vector or an empty set is refused).
+    -> list[PlanningResult] as `rrtc_multi`'s, each with `goal_index`: the goal of its own set a solved problem's path
+    ends in (-1 = unsolved).
+
+    Per problem the edges start -> goal g are tried first, in order of g and one per round; the first valid one is the
+    path.  Otherwise every goal is a root of the goal tree and the search is `rrtc_multi`'s.  The settings'
+    dynamic_domain (radius, alpha, min_radius) and start_tree_first work as in rrtc.hh; a sample the dynamic domain
+    rejects asks no edge question and so costs no round.  With those off and one goal per problem the results
+    are `rrtc_multi`'s bit for bit.  1 + G_p may not exceed max_samples."""
+    s = settings or RRTCMultiSettings()
+    sets = []
+    for g in goal_sets:
+        g = np.asarray(g, np.float32)
+        if g.ndim != 2 or g.shape[0] < 1 or g.shape[1] != robot.dimension():
+            raise TypeError(f"expected every goal set as a [G][{robot.dimension()}] array with G >= 1, got shape {g.shape}")
+        sets.append(g)
+    packed = np.concatenate(sets) if sets else np.zeros((0, robot.dimension()), np.float32)
+    counts = np.array([len(g) for g in sets], np.int64)
+    return _rrtc_results(robot.rrtc_multi_goals_raw(starts, packed, counts, environments, s, skips))
 
 
 def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | None = None, skips=None, samples=None):
