@@ -234,6 +234,48 @@ int vmv_env_report_layout(const vmv_env *env, uint32_t *first_word5);
 /* the fine pairs the report covers: n_pairs, and (a, b) sphere indices into pairs2 (may be NULL) */
 int vmv_robot_self_pairs(int robot, size_t *n_pairs, uint16_t *pairs2);
 
+/* Clearances: how far each configuration is from contact (no counterpart in the reference, whose answers are booleans).
+ * Per configuration two fp32 values, d_clearance [n][2]:
+ *   [0] env  = min over the robot's fine spheres s (those of vmv_fk_batch) and over every contact c of the environment
+ *              of the signed distance between the two surfaces, negative = penetration:
+ *                sphere                |c_s - c_p| - (r_s + r_p)
+ *                capsule, z-capsule    distance to the segment, minus both radii
+ *                cuboid, z-cuboid      distance to the box (0 inside), minus r_s; the z-aligned kind with its first two
+ *                                      axes in x, y and +z as the third, as the reference's test reads it
+ *                heightfield           the reference's vertical value z - r_s - height, the cell chosen by the fp32
+ *                                      arithmetic of its sphere_heightfield test
+ *              +inf for an environment without contacts (and for env == NULL);
+ *   [1] self = min over the fine self pairs (a, b) of vmv_robot_self_pairs of |c_a - c_b| - (r_a + r_b).
+ * The minimum is FLAT: the bounding-sphere gates, reach certificates, candidate words and the sorted early break of the
+ * validation kernels prune a boolean and play no part in it.
+ * d_witness [n][4] uint32 (may be NULL): env_sphere; env_kind (0 sphere, 1 capsule, 2 z-capsule, 3 cuboid, 4 z-cuboid,
+ * 5 heightfield); env_index = the position in that kind's list as vmv_env_get_spheres / _cuboids / _capsules return it
+ * after finalize, for heightfields the insertion index; self_pair = index into vmv_robot_self_pairs.  A field with
+ * nothing to point at is UINT32_MAX.  Among equal fp32 values the first wins, ordered by sphere index, then kind, then
+ * list index; for self pairs the lowest pair index.  So a configuration's values and witness do not depend on the batch
+ * size, on its position in the batch, or on which of these calls computed it.
+ * Arithmetic: fp32 + - * / sqrt, one rounding per operation (no contraction), on the sphere centres of Robot::sphere_fk,
+ * which stay on chip.  A configuration with a non-finite joint gives NaN in both values and UINT32_MAX in all four
+ * witness fields.
+ * Out of scope: an environment holding a point cloud (CAPT or MVT) - a distance to a cloud needs a nearest-neighbour
+ * structure, which neither index is - or an attachment is refused with VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names
+ * the kind.  Checks before anything is launched, those that need no device first: unknown robot; NULL d_q / d_clearance
+ * (VMV_ERR_INVALID_ARGUMENT); a refused kind; an unfinalized environment (VMV_ERR_NOT_FINALIZED); then the device.
+ * env == NULL: the self clearance alone.  The sign agrees with vmv_validate_batch except within rounding of contact, and
+ * where the reference's bounding-sphere gate reads another heightfield cell than the fine spheres do. */
+int vmv_clearance_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, uint32_t *d_witness,
+                        void *stream);
+int vmv_clearance_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, uint32_t *witness);
+/* Many environments in one call: configurations [offsets[k], offsets[k+1]) against envs[k].  Offsets, limits, the order
+ * of the checks (NULL handles named by index, a refused kind named by index, unfinalized environments, environments of
+ * another device; n >= 2^31 refused before any array is read), the absence of host synchronisation and the tables per
+ * (device, stream) are those of vmv_validate_batch_multi.  Every envs[k] is a handle (no NULL).  The values and the
+ * witness are bit for bit those of one vmv_clearance_batch per environment, concatenated.  One launch. */
+int vmv_clearance_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                              float *d_clearance, uint32_t *d_witness, void *stream);
+int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
+                                   float *clearance, uint32_t *witness);
+
 /* sphere_environment_in_collision(environment, x, y, z, r) — collision/validity.hh:47-158, the predicate every fkcc
  * check is made of (and CAPT::collides / MVT::collides behind it, collision/capt.hh:374-415), for a batch of free
  * spheres: spheres [n][4] = x y z r, hits[i] = 1 iff sphere i collides with the environment.  Each sphere is its own

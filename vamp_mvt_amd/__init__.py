@@ -699,6 +699,88 @@ class _Robot(types.ModuleType):
                                           bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_host")
         return unpack_bits(bits, n)
 
+    def clearance(self, configuration, environment: Environment | None = None):
+        """(env, self): the signed distance from contact of one configuration, as clearance_batch defines it."""
+        out = self.clearance_batch(_f32(configuration, (self._dim,))[None, :], environment)
+        return float(out[0, 0]), float(out[0, 1])
+
+    def clearance_batch(self, configurations, environment: Environment | None = None, witness: bool = False):
+        """float32[n][2] = (env, self) per configuration: the smallest signed distance (metres, negative = penetration)
+        between a fine sphere of the robot and a contact of the environment - spheres, capsules, cuboids, heightfields
+        (their vertical value) - and between the two spheres of a fine self pair (include/vamp_mvt_amd.h:
+        vmv_clearance_batch).  environment=None: env = +inf.  witness=True: also uint32[n][4] = (env_sphere, env_kind,
+        env_index, self_pair), UINT32_MAX where there is nothing to point at; env_kind 0 sphere, 1 capsule, 2 z-capsule,
+        3 cuboid, 4 z-cuboid, 5 heightfield, env_index the position in Environment.host_tables()'s sorted list of that
+        kind.  Environments with a point cloud or an attachment are refused.  numpy in -> numpy out; a torch CUDA tensor
+        in -> torch CUDA tensors out (the witness as int32: UINT32_MAX reads -1), launched on torch's current stream."""
+        if environment is not None and not isinstance(environment, Environment):
+            raise TypeError(f"expected Environment or None, got {type(environment).__name__}")
+        torch_in = _is_torch_cuda(configurations)
+        shape = tuple(configurations.shape) if torch_in else None
+        if not torch_in:
+            q = _f32(configurations)
+            shape = q.shape
+        if len(shape) != 2 or shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] configurations")
+        n = shape[0]
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(configurations.device):
+                h = None if environment is None else environment.handle()
+                qt = configurations.contiguous().float()
+                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
+                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
+                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
+                check(lib.vmv_clearance_batch(self._id, h, ctypes.c_void_p(qt.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                              ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
+                      "vmv_clearance_batch")
+                return (out, wit) if witness else out
+        h = None if environment is None else environment.handle()
+        out = np.zeros((n, 2), np.float32)
+        wit = np.zeros((n, 4), np.uint32) if witness else None
+        check(lib.vmv_clearance_batch_host(self._id, h, _fp(q), n, _fp(out),
+                                           wit.ctypes.data_as(_lib.c_u32_p) if witness else None), "vmv_clearance_batch_host")
+        return (out, wit) if witness else out
+
+    def clearance_batch_multi(self, configurations, environments, counts, witness: bool = False):
+        """clearance_batch for configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the
+        empty environment: env = +inf), in one call and one launch.  Bit for bit one clearance_batch per environment,
+        concatenated.  numpy in -> numpy out; a torch CUDA tensor in -> torch CUDA tensors out, as clearance_batch."""
+        environments, offsets = _segments(environments, counts)
+        torch_in = _is_torch_cuda(configurations)
+        if torch_in:
+            shape = tuple(configurations.shape)
+        else:
+            q = _f32(configurations)
+            shape = q.shape
+        if len(shape) != 2 or shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] configurations")
+        n = shape[0]
+        if int(offsets[-1]) != n:
+            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(configurations.device):
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+                qt = configurations.contiguous().float()
+                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
+                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
+                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
+                check(lib.vmv_clearance_batch_multi(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
+                                                    ctypes.c_void_p(qt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                    ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
+                      "vmv_clearance_batch_multi")
+                return (out, wit) if witness else out
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        out = np.zeros((n, 2), np.float32)
+        wit = np.zeros((n, 4), np.uint32) if witness else None
+        check(lib.vmv_clearance_batch_multi_host(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs), _fp(q),
+                                                 _fp(out), wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
+              "vmv_clearance_batch_multi_host")
+        return (out, wit) if witness else out
+
     def prepare(self, environments):
         """Builds what each environment holds for this robot (broad-phase grids, reach certificates, static links) for
         all of them in one call, on the device, instead of one by one on their first use.  None = the empty

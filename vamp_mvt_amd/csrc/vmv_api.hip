@@ -1268,8 +1268,21 @@ namespace
     // the checks of vmv_validate_batch_multi(_host) and vmv_validate_motion_batch_multi(_host) that need no device, in the
     // header's order; q and q2 are the input arrays (the configurations twice, or the starts and the goals);
     // *n = offsets[n_envs]
+    // vmv_clearance_batch*: the kinds a clearance is not defined for (include/vamp_mvt_amd.h), read from the host
+    // builder, so the refusal needs neither a device nor a finalized environment; `who` names the argument
+    int clearance_kinds(const vmv_env *env, const std::string &who)
+    {
+        const char *kind = !env->capts.empty() ? "a CAPT point cloud" :
+                           !env->mvts.empty() ? "an MVT point cloud" :
+                           (env->attached && !env->attach_spheres.empty()) ? "an attachment" : nullptr;
+        if (!kind) return VMV_OK;
+        g_last_error = who + " holds " + kind + ": a clearance is defined against primitives and heightfields only";
+        return VMV_ERR_INVALID_ARGUMENT;
+    }
+
+    // (clearance: the vmv_clearance_batch_multi(_host) form - also refuses the kinds of clearance_kinds, by index)
     int multi_args(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const void *q,
-                   const void *q2, const void *bits, size_t *n)
+                   const void *q2, const void *bits, size_t *n, bool clearance = false)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         std::string err;
@@ -1291,6 +1304,8 @@ namespace
             g_last_error = err;
             return VMV_ERR_INVALID_ARGUMENT;
         }
+        for (size_t k = 0; clearance && k < n_envs; ++k)
+            if (int rc = clearance_kinds(envs[k], "envs[" + std::to_string(k) + "]"); rc != VMV_OK) return rc;
         for (size_t k = 0; k < n_envs; ++k)
             if (!envs[k]->finalized)
             {
@@ -1685,6 +1700,86 @@ extern "C"
     {
         if (!b) return VMV_ERR_INVALID_ARGUMENT;
         return validate_host_common(robot, env, a, b, n, bits);
+    }
+
+    // ---- clearances (include/vamp_mvt_amd.h: vmv_clearance_batch) ----
+    // the checks of vmv_clearance_batch(_host) that need no device, in the header's order
+    static int clearance_args(int robot, const vmv_env *env, const void *q, const void *clearance)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!q || !clearance)
+        {
+            g_last_error = "null pointer";
+            return VMV_ERR_INVALID_ARGUMENT;
+        }
+        if (!env) return VMV_OK;  // the self clearance alone
+        if (int rc = clearance_kinds(env, "the environment"); rc != VMV_OK) return rc;
+        if (!env->finalized)
+        {
+            g_last_error = "the environment is not finalized";
+            return VMV_ERR_NOT_FINALIZED;
+        }
+        return VMV_OK;
+    }
+    int vmv_clearance_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, uint32_t *d_witness,
+                            void *stream)
+    {
+        if (int rc = clearance_args(robot, env, d_q, d_clearance); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (env)
+        {
+            if (int rc = check_device(env); rc != VMV_OK) return rc;
+            if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
+        }
+        return kLaunchers[robot]->clearance(env ? &env->launch[robot] : nullptr, d_q, n, d_clearance, d_witness,
+                                            static_cast<hipStream_t>(stream));
+    }
+    int vmv_clearance_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                  float *d_clearance, uint32_t *d_witness, void *stream)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_q, d_clearance, &n, true); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
+        std::vector<const vmv::EnvLaunch *> launch(n_envs);
+        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
+        return kLaunchers[robot]->clearance_multi(launch.data(), offsets, n_envs, d_q, d_clearance, d_witness,
+                                                  static_cast<hipStream_t>(stream));
+    }
+    // staging of the two host forms: [configurations | clearances | witness] in the arena; `multi`: envs / offsets / n_envs
+    static int clearance_host_common(int robot, const vmv_env *env, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                     bool multi, const float *q, size_t n, float *clearance, uint32_t *witness)
+    {
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255};
+        const size_t cb = (n * 8 + 255) & ~size_t{255}, wb = witness ? n * 16 : 0;
+        char *arena = static_cast<char *>(g_staging.get(qb + cb + wb));
+        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
+        float *dq = reinterpret_cast<float *>(arena), *dc = reinterpret_cast<float *>(arena + qb);
+        uint32_t *dw = witness ? reinterpret_cast<uint32_t *>(arena + qb + cb) : nullptr;
+        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
+        int rc = multi ? vmv_clearance_batch_multi(robot, envs, offsets, n_envs, dq, dc, dw, nullptr) :
+                         vmv_clearance_batch(robot, env, dq, n, dc, dw, nullptr);
+        if (rc == VMV_OK && hipMemcpy(clearance, dc, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        if (rc == VMV_OK && witness && hipMemcpy(witness, dw, n * 16, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        g_staging.trim();
+        return rc;
+    }
+    int vmv_clearance_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, uint32_t *witness)
+    {
+        if (int rc = clearance_args(robot, env, q, clearance); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return clearance_host_common(robot, env, nullptr, nullptr, 0, false, q, n, clearance, witness);
+    }
+    int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
+                                       float *clearance, uint32_t *witness)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, q, q, clearance, &n, true); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return clearance_host_common(robot, nullptr, envs, offsets, n_envs, true, q, n, clearance, witness);
     }
 
     // ---- multi-GPU sharding arithmetic (vamp_mvt_amd/sharding.py: shard_range) ----

@@ -83,6 +83,12 @@ namespace vmv
         int (*contacts)(const EnvLaunch &, const float *d_spheres, size_t n, uint32_t *d_env_words, uint32_t *d_pair_words,
                         hipStream_t);
         int n_self_pairs;
+        // vmv_clearance_batch: d_out [n][2] = (environment, self) clearance, d_witness [n][4] or nullptr; env == nullptr:
+        // the self clearance alone.  The environment holds no point cloud and no attachment (the API refuses those).
+        int (*clearance)(const EnvLaunch *env, const float *d_q, size_t n, float *d_out, uint32_t *d_witness, hipStream_t);
+        // vmv_clearance_batch_multi: configurations [offsets[k], offsets[k + 1]) against *envs[k], as validate_multi
+        int (*clearance_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                               float *d_out, uint32_t *d_witness, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

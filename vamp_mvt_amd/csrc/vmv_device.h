@@ -938,6 +938,65 @@ namespace vmv
         }
     }
 
+    // ------------------------------------------------------------------------
+    // one primitive against one sphere: the signed distance between the two surfaces (negative = penetration), the
+    // quantity of vmv_clearance_batch (include/vamp_mvt_amd.h).  prim_eval's values are squared test
+    // values whose sign alone matters; these are metres: distance to the centre / segment / box, minus the radii.  fp32
+    // + - * / sqrt, one rounding each.  The closest-point arithmetic is prim_eval's (the capsule's parameter through the
+    // stored rdv, the cuboid's axes as stored), so the sign of a clearance is the sign of the test wherever neither is
+    // within rounding of zero.
+    // ------------------------------------------------------------------------
+    template <int T, typename PTR>
+    __device__ __forceinline__ float prim_clearance(PTR rec, float x, float y, float z, float r)
+    {
+        if constexpr (T == kSphere)
+        {
+            const v4f a = load4(rec);  // x y z r | min_d
+            return sqrtf(sql2_3(a.x, a.y, a.z, x, y, z)) - (r + a.w);
+        }
+        else if constexpr (T == kCapsule)
+        {
+            const v4f a = load4(rec);      // x1 y1 z1 xv
+            const v4f b = load4(rec + 4);  // yv zv r rdv
+            const float dot = dot3(x - a.x, y - a.y, z - a.z, a.w, b.x, b.y);
+            const float cdf = vclamp(dot * b.w, 0.F, 1.F);
+            const float sum = sql2_3(x, y, z, a.x + a.w * cdf, a.y + b.x * cdf, a.z + b.y * cdf);
+            return sqrtf(sum) - (r + b.z);
+        }
+        else if constexpr (T == kZCapsule)
+        {
+            const v4f a = load4(rec);      // x1 y1 z1 zv
+            const v4f b = load4(rec + 4);  // r rdv min_d 0
+            const float dot = (z - a.z) * a.w;
+            const float cdf = vclamp(dot * b.y, 0.F, 1.F);
+            const float sum = sql2_3(x, y, z, a.x, a.y, a.z + a.w * cdf);
+            return sqrtf(sum) - (r + b.x);
+        }
+        else if constexpr (T == kCuboid)
+        {
+            const v4f a = load4(rec);       // x y z a1x
+            const v4f b = load4(rec + 4);   // a1y a1z a2x a2y
+            const v4f c = load4(rec + 8);   // a2z a3x a3y a3z
+            const v4f d = load4(rec + 12);  // r1 r2 r3 min_d
+            const float xs = x - a.x, ys = y - a.y, zs = z - a.z;
+            const float a1 = x86_max(vabs(dot3(a.w, b.x, b.y, xs, ys, zs)) - d.x, 0.f);
+            const float a2 = x86_max(vabs(dot3(b.z, b.w, c.x, xs, ys, zs)) - d.y, 0.f);
+            const float a3 = x86_max(vabs(dot3(c.y, c.z, c.w, xs, ys, zs)) - d.z, 0.f);
+            return sqrtf(dot3(a1, a2, a3, a1, a2, a3)) - r;  // (0 inside the box)
+        }
+        else
+        {
+            const v4f a = load4(rec);      // x y z a1x
+            const v4f b = load4(rec + 4);  // a1y a2x a2y r1
+            const v4f c = load4(rec + 8);  // r2 r3 min_d 0
+            const float xs = x - a.x, ys = y - a.y, zs = z - a.z;
+            const float a1 = x86_max(vabs((a.w * xs) + (b.x * ys)) - b.w, 0.f);
+            const float a2 = x86_max(vabs((b.y * xs) + (b.z * ys)) - c.x, 0.f);
+            const float a3 = x86_max(vabs(zs) - c.y, 0.f);
+            return sqrtf(dot3(a1, a2, a3, a1, a2, a3)) - r;
+        }
+    }
+
     // Candidate margin.  A fine sphere lies inside its link's bounding sphere (the bounding sphere is the smallest
     // ball enclosing the link's spheres; tools/robot_trace.py asserts the enclosure in the link frame, and rigid fp32
     // FK preserves it to ~1e-6 m).  Every primitive test is `distance(centre, primitive)^2 - reach^2` with a
@@ -1047,6 +1106,65 @@ namespace vmv
         const float zh = a->data[u];
         const float zhs = a->zs * zh + a->z;
         return neg(z - r - zhs);
+    }
+
+    // ... and the value whose sign that is: the reference's vertical clearance z - r - height, the cell chosen by the
+    // same fp32 arithmetic (vmv_clearance_batch)
+    __device__ __forceinline__ float heightfield_clearance(const env_cptr Dp, const uint32_t hi, float x, float y, float z, float r)
+    {
+        const HeightFieldDev __attribute__((address_space(4))) *a = &Dp->heightfield[hi];
+        const float xo = a->x - x, yo = a->y - y;
+        const float xs = floorf(vclamp(a->xs * xo + a->xd2, 0.F, a->xd));
+        const float ys = floorf(vclamp(a->ys * yo + a->yd2, 0.F, a->yd));
+        const float index = ys * a->xd + xs;
+        int idx = (int) rintf(index);
+        idx = idx < 0 ? 0 : idx;
+        const uint32_t u = (uint32_t) idx > a->last ? a->last : (uint32_t) idx;
+        const float zh = a->data[u];
+        const float zhs = a->zs * zh + a->z;
+        return z - r - zhs;
+    }
+
+    // vmv_clearance_batch: the smallest clearance of one sphere over every contact of the environment, FLAT - every
+    // record of every list, in list order; no min_distance prefix, no candidate words, no gate (those prune a boolean).
+    // key = kind << kClearanceKindShift | position in the kind's list (kind: PrimType, 5 = heightfield); among equal
+    // values the first in (kind, position) order is kept, so callers that walk spheres in ascending order and take a
+    // later sphere only when it is strictly smaller implement the tie rule of the header.  Records through the scalar
+    // cache, wave-uniform addresses, as list_full reads them.  A NaN value (an ill-formed record) is never taken.
+    constexpr uint32_t kClearanceKindShift = 28u;
+    constexpr uint32_t kClearanceHeightfield = 5u;
+    template <int T>
+    __device__ __forceinline__ void list_clearance(const EnvView &E, const uint32_t n, const uint32_t off, float x, float y,
+                                                   float z, float r, float &best, uint32_t &key)
+    {
+        constexpr int REC = PrimTraits<T>::rec;
+        const env_cptr Dp = E.dev;
+        rec_cptr rec = VMV_REC_BASE(E, (*Dp)) + off;
+#pragma unroll 4  // (the records of four iterations are fetched together: the loop waits for the scalar cache once, not four times)
+        for (uint32_t i = 0; i < n; ++i, rec += REC)
+        {
+            const float v = prim_clearance<T>(rec, x, y, z, r);
+            const bool take = v < best;
+            best = take ? v : best;
+            key = take ? (((uint32_t) T << kClearanceKindShift) | i) : key;
+        }
+    }
+    __device__ __forceinline__ void sphere_clearance(const EnvView &E, float x, float y, float z, float r, float &best, uint32_t &key)
+    {
+        const env_cptr D = E.dev;
+        list_clearance<kSphere>(E, D->n_sphere, D->off_sphere, x, y, z, r, best, key);
+        list_clearance<kCapsule>(E, D->n_capsule, D->off_capsule, x, y, z, r, best, key);
+        list_clearance<kZCapsule>(E, D->n_zcapsule, D->off_zcapsule, x, y, z, r, best, key);
+        list_clearance<kCuboid>(E, D->n_cuboid, D->off_cuboid, x, y, z, r, best, key);
+        list_clearance<kZCuboid>(E, D->n_zcuboid, D->off_zcuboid, x, y, z, r, best, key);
+        const uint32_t n_hf = D->n_heightfield;
+        for (uint32_t h = 0; h < n_hf; ++h)
+        {
+            const float v = heightfield_clearance(D, h, x, y, z, r);
+            const bool take = v < best;
+            best = take ? v : best;
+            key = take ? ((kClearanceHeightfield << kClearanceKindShift) | h) : key;
+        }
     }
 
     // The list part of the environment header (counts, block offsets, candidate-word bases), fetched ONCE per gate /

@@ -996,6 +996,150 @@ namespace VMV_ROBOT_NS
     }
 
     // ---------------------------------------------------------------------------------------------------------
+    // vmv_clearance_batch: per configuration the smallest signed distance of a fine sphere to a contact of the
+    // environment and of a fine self pair, with the witness (include/vamp_mvt_amd.h, DESIGN.md 5i).  Fused: a workgroup
+    // takes a tile of kClrTile configurations; the first kClrTile lanes run Robot::sphere_fk, one configuration each, into
+    // an LDS slab ([configuration][sphere] float4, rows of an odd number of float4 so that the lanes of a 128-bit read
+    // fall into different bank groups) and the spheres never reach HBM.  Then lane = configuration, and the workgroup's
+    // kClrStreams = kBlock / kClrTile streams share the configuration's spheres (stream t takes spheres t, t + streams,
+    // ..) and then its self pairs the same way; with 64-configuration tiles a stream is a wave, and the sphere / pair
+    // number and every record address are wave-uniform.  Each stream keeps (value, key) minima with a strict compare in
+    // ascending key order; the streams' partial results meet in LDS and the configuration's first lane joins them, on
+    // equal values the lower sphere (pair) index wins - the minimum of a total order, so it does not depend on the tile
+    // size, on where the configuration sits in the batch, or on which kernel computed it.
+    // LDS after the staged environment: [slab | 5 partial rows of kBlock words].
+    // ---------------------------------------------------------------------------------------------------------
+    constexpr uint32_t kClrRow = (uint32_t) R::kNSpheres | 1u;
+    constexpr uint32_t kClrTile = (kClrRow * 64u * 16u <= 64u * 1024u) ? 64u : 32u;  // (Panda, UR5: 64; Fetch, Baxter: 32)
+    constexpr uint32_t kClrStreams = (uint32_t) kBlock / kClrTile;
+    constexpr uint32_t kClrSlabFloats = kClrTile * kClrRow * 4u;
+    constexpr uint32_t kClrTailFloats = kClrSlabFloats + 5u * (uint32_t) kBlock;
+
+    // configurations [first, min(first + kClrTile, hi)) of the batch; `tail` = the LDS behind the staged environment
+    __device__ __forceinline__ void clearance_tile(const bool has_env, const EnvView &E, float *tail, const float *__restrict__ q,
+                                                   const uint32_t first, const uint32_t hi, float *__restrict__ out,
+                                                   uint32_t *__restrict__ witness)
+    {
+        constexpr uint32_t kNone = 0xffffffffu;
+        float4 *slab = reinterpret_cast<float4 *>(tail);
+        float *part_env = tail + kClrSlabFloats, *part_self = part_env + 3 * kBlock;
+        uint32_t *part_key = reinterpret_cast<uint32_t *>(part_env) + kBlock, *part_sphere = part_key + kBlock;
+        uint32_t *part_pair = reinterpret_cast<uint32_t *>(part_self) + kBlock;
+        const uint32_t tid = threadIdx.x;
+        const uint32_t c = tid % kClrTile;
+        const uint32_t stream = kClrTile == (uint32_t) kWave ? uniform(tid / kClrTile) : tid / kClrTile;
+        const uint32_t count = hi - first < kClrTile ? hi - first : kClrTile;
+        const float4 *row = slab + c * kClrRow;
+        bool finite = true;
+        if (tid < kClrTile)
+        {
+            float cfg[R::kDim];
+            const size_t at = (size_t) (c < count ? first + c : first) * R::kDim;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) cfg[j] = q[at + j];
+            finite = sanitize_config<R::kDim>(cfg);  // (a non-finite configuration poses the zero configuration; its results are replaced below)
+            R::sphere_fk(cfg, slab + c * kClrRow);
+        }
+        __syncthreads();
+
+        float env_best = __builtin_inff();
+        uint32_t env_key = kNone, env_sphere = kNone;
+        if (has_env)
+        {
+            constexpr uint32_t kRounds = ((uint32_t) R::kNSpheres + kClrStreams - 1u) / kClrStreams;
+            for (uint32_t k = 0; k < kRounds; ++k)
+            {
+                const uint32_t s = stream + k * kClrStreams;
+                const bool live = s < (uint32_t) R::kNSpheres;
+                const float4 sp = row[live ? s : 0u];
+                float v = __builtin_inff();
+                uint32_t key = kNone;
+                sphere_clearance(E, sp.x, sp.y, sp.z, sp.w, v, key);
+                const bool take = live && v < env_best;
+                env_best = take ? v : env_best;
+                env_key = take ? key : env_key;
+                env_sphere = take ? s : env_sphere;
+            }
+        }
+        float self_best = __builtin_inff();
+        uint32_t self_pair = kNone;
+        if constexpr (R::kNSelfPairs > 0)
+        {
+            constexpr uint32_t kRounds = ((uint32_t) R::kNSelfPairs + kClrStreams - 1u) / kClrStreams;
+            for (uint32_t k = 0; k < kRounds; ++k)
+            {
+                const uint32_t p = stream + k * kClrStreams;
+                const bool live = p < (uint32_t) R::kNSelfPairs;
+                const float4 a = row[VMV_ROBOT_NS::kSelfPairs[live ? p : 0u][0]];
+                const float4 b = row[VMV_ROBOT_NS::kSelfPairs[live ? p : 0u][1]];
+                const float v = sqrtf(sql2_3(a.x, a.y, a.z, b.x, b.y, b.z)) - (a.w + b.w);
+                const bool take = live && v < self_best;
+                self_best = take ? v : self_best;
+                self_pair = take ? p : self_pair;
+            }
+        }
+        part_env[tid] = env_best, part_key[tid] = env_key, part_sphere[tid] = env_sphere;
+        part_self[tid] = self_best, part_pair[tid] = self_pair;
+        __syncthreads();
+        if (tid < count)  // (stream 0 of configuration c: its own partial results are the start)
+        {
+            for (uint32_t t = 1; t < kClrStreams; ++t)
+            {
+                const uint32_t o = t * kClrTile + c;
+                const float v = part_env[o];
+                const uint32_t s = part_sphere[o];
+                if (v < env_best || (v == env_best && s < env_sphere)) env_best = v, env_key = part_key[o], env_sphere = s;
+                const float w = part_self[o];
+                const uint32_t p = part_pair[o];
+                if (w < self_best || (w == self_best && p < self_pair)) self_best = w, self_pair = p;
+            }
+            const size_t i = (size_t) first + c;
+            const float nan = __builtin_nanf("");
+            out[2 * i] = finite ? env_best : nan;
+            out[2 * i + 1] = finite ? self_best : nan;
+            if (witness)
+            {
+                const bool some = finite && env_key != kNone;
+                witness[4 * i] = some ? env_sphere : kNone;
+                witness[4 * i + 1] = some ? env_key >> kClearanceKindShift : kNone;
+                witness[4 * i + 2] = some ? env_key & ((1u << kClearanceKindShift) - 1u) : kNone;
+                witness[4 * i + 3] = finite ? self_pair : kNone;
+            }
+        }
+    }
+
+    // Workgroup b takes tile b.  n is 32-bit: the launcher cuts larger batches into slices.  env == nullptr: the self
+    // clearance alone.  (Both kernels are templates for their place in the code object alone: instantiations are emitted
+    // at the end of the translation unit, so every kernel that was there before keeps its address.)
+    template <int = 0>
+    __global__ __launch_bounds__(kBlock) void clearance_kernel(const EnvDev *__restrict__ env, const uint32_t head,
+                                                                const float *__restrict__ q, const uint32_t n,
+                                                                float *__restrict__ out, uint32_t *__restrict__ witness)
+    {
+        extern __shared__ __align__(16) float smem[];
+        EnvView E{};
+        if (env) E = stage_environment(env, 0u, smem);  // (workgroup-uniform)
+        // one tile per workgroup, no loop: around a loop over tiles the FK's constants and the tile's addresses stayed live
+        // (Fetch: 254 VGPRs against 169)
+        clearance_tile(env != nullptr, E, smem + head, q, blockIdx.x * kClrTile, n, out, witness);
+    }
+
+    // vmv_clearance_batch_multi: workgroup b takes tile b of the table, MultiTile::word = the tile's first configuration,
+    // and stages that tile's environment; the body is the single-environment one.
+    template <int = 0>
+    __global__ __launch_bounds__(kBlock) void clearance_multi_kernel(const MultiSeg *__restrict__ segs,
+                                                                      const MultiTile *__restrict__ tiles,
+                                                                      const float *__restrict__ q, float *__restrict__ out,
+                                                                      uint32_t *__restrict__ witness)
+    {
+        extern __shared__ __align__(16) float smem[];
+        const MultiTile tile = tiles[blockIdx.x];
+        const MultiSeg S = segs[tile.seg];
+        const EnvView E = stage_environment(S.env, 0u, smem);
+        clearance_tile(true, E, smem + S.slab, q, tile.word, S.hi, out, witness);
+    }
+
+    // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
     namespace
@@ -1609,6 +1753,73 @@ namespace VMV_ROBOT_NS
             VMV_HIP_TU(hipGetLastError());
             return VMV_OK;
         }
+
+        // LDS of the clearance kernels: the staged environment (no point-cloud planes: such environments are refused), then
+        // the tile's slab and partial rows.  head = float offset of the slab.
+        uint32_t clearance_head(const EnvDev &D) { return ((D.n_floats + 3u) & ~3u) + kEnvRadiiFloats; }
+
+        // env == nullptr: the self clearance alone (d_out[i][0] = +inf); d_witness may be nullptr
+        int launch_clearance(const EnvLaunch *env, const float *d_q, size_t n, float *d_out, uint32_t *d_witness,
+                             hipStream_t stream)
+        {
+            const uint32_t head = env ? clearance_head(env->host) : 0u;
+            const uint32_t shmem = (head + kClrTailFloats) * (uint32_t) sizeof(float);
+            if (shmem > kMaxLdsBytes) return VMV_ERR_CAPACITY;
+            if (shmem > 64u * 1024u)
+                VMV_HIP_TU(hipFuncSetAttribute((const void *) clearance_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int) shmem));
+            constexpr size_t kSlice = (size_t{1} << 20) * kClrTile;  // one workgroup per tile, 2^20 workgroups per launch
+            for (size_t lo = 0; lo < n; lo += kSlice)
+            {
+                const uint32_t m = (uint32_t) (n - lo < kSlice ? n - lo : kSlice);
+                hipLaunchKernelGGL(clearance_kernel<>, dim3((m + kClrTile - 1u) / kClrTile), dim3(kBlock), shmem, stream,
+                                   env ? env->d_env : (const EnvDev *) nullptr, head, d_q + lo * R::kDim, m, d_out + 2 * lo,
+                                   d_witness ? d_witness + 4 * lo : (uint32_t *) nullptr);
+            }
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+
+        // vmv_clearance_batch_multi: one launch, one workgroup per tile of kClrTile configurations of one segment.
+        // Table: [segments | tiles].
+        int launch_clearance_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                   float *d_out, uint32_t *d_witness, hipStream_t stream)
+        {
+            constexpr size_t kMaxGrid = size_t{1} << 20;  // workgroups per launch
+            if (offsets[n_envs] == 0) return VMV_OK;
+            std::vector<MultiSeg> segs(n_envs);
+            size_t n_tiles = 0;
+            uint32_t shmem = 0;
+            for (size_t k = 0; k < n_envs; ++k)
+            {
+                const uint32_t head = clearance_head(envs[k]->host);
+                segs[k] = MultiSeg{envs[k]->d_env, (uint32_t) offsets[k], (uint32_t) offsets[k + 1], 0u, head};
+                if (offsets[k] == offsets[k + 1]) continue;
+                n_tiles += (offsets[k + 1] - offsets[k] + kClrTile - 1) / kClrTile;
+                shmem = std::max(shmem, (head + kClrTailFloats) * (uint32_t) sizeof(float));
+            }
+            if (shmem > kMaxLdsBytes) return VMV_ERR_CAPACITY;
+            const size_t seg_bytes = (n_envs * sizeof(MultiSeg) + 15u) & ~size_t{15};
+            MultiTableLease lease;
+            if (int rc = lease.acquire(stream, seg_bytes + n_tiles * sizeof(MultiTile)); rc != VMV_OK) return rc;
+            std::memcpy(lease.host, segs.data(), n_envs * sizeof(MultiSeg));
+            MultiTile *tiles = reinterpret_cast<MultiTile *>(static_cast<char *>(lease.host) + seg_bytes);
+            size_t fill = 0;
+            for (size_t k = 0; k < n_envs; ++k)
+                for (size_t first = offsets[k]; first < offsets[k + 1]; first += kClrTile)
+                    tiles[fill++] = MultiTile{(uint32_t) k, (uint32_t) first};
+            if (int rc = lease.upload(stream, seg_bytes + n_tiles * sizeof(MultiTile)); rc != VMV_OK) return rc;
+            const MultiSeg *d_segs = static_cast<const MultiSeg *>(lease.dev);
+            const MultiTile *d_tiles = reinterpret_cast<const MultiTile *>(static_cast<const char *>(lease.dev) + seg_bytes);
+            if (shmem > 64u * 1024u)
+                VMV_HIP_TU(hipFuncSetAttribute((const void *) clearance_multi_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int) shmem));
+            for (size_t t0 = 0; t0 < n_tiles; t0 += kMaxGrid)
+                hipLaunchKernelGGL(clearance_multi_kernel<>, dim3((uint32_t) std::min(n_tiles - t0, kMaxGrid)), dim3(kBlock), shmem,
+                                   stream, d_segs, d_tiles + t0, d_q, d_out, d_witness);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
     }  // namespace
 
 }  // namespace VMV_ROBOT_NS
@@ -1620,6 +1831,7 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_fk, VMV_ROBOT_NS::launch_prepare,
                                                     VMV_ROBOT_NS::launch_prepare_multi,
                                                     VMV_ROBOT_NS::launch_eefk, VMV_ROBOT_NS::launch_contacts,
-                                                    VMV_ROBOT_NS::R::kNSelfPairs};
+                                                    VMV_ROBOT_NS::R::kNSelfPairs,
+                                                    VMV_ROBOT_NS::launch_clearance, VMV_ROBOT_NS::launch_clearance_multi};
 #endif
 }  // namespace vmv

@@ -635,6 +635,64 @@ def validate_paths(robot, paths, environments) -> np.ndarray:
 
 
 @dataclass
+class PathClearance:
+    """path_clearance's answer for one path: the smallest `env` and `self` clearance over its samples (self_: `self` is
+    no field name), and the (segment, k) of the sample each was found at (the first such sample; None for a path without
+    waypoints)"""
+    env: float
+    self_: float
+    env_at: tuple | None
+    self_at: tuple | None
+
+
+def path_samples(path, resolution):
+    """The samples path_clearance takes of one path ([len][dim]) -> (float32 [n][dim], int64 [n][2] = (segment, k)).
+    Segment (a, b) is sampled at a + (b - a) * k / m for k = 0..m with m = max(1, ceil(|b - a| * resolution)), computed in
+    float64 and cast to fp32; both end points of every segment are samples, so an inner waypoint appears twice.  A path
+    of one waypoint is that one sample, at (0, 0)."""
+    p = np.asarray(path, np.float64)
+    if p.ndim != 2:
+        raise TypeError("expected a [len][dim] path")
+    if len(p) == 1:
+        return p.astype(np.float32), np.zeros((1, 2), np.int64)
+    pts, at = [np.zeros((0, p.shape[1]))], [np.zeros((0, 2), np.int64)]
+    for i in range(len(p) - 1):
+        a, b = p[i], p[i + 1]
+        m = max(1, int(np.ceil(np.sqrt(((b - a) ** 2).sum()) * resolution)))
+        k = np.arange(m + 1)
+        pts.append(a[None, :] + (b - a)[None, :] * (k / m)[:, None])
+        at.append(np.stack([np.full(m + 1, i), k], axis=1).astype(np.int64))
+    return np.concatenate(pts).astype(np.float32), np.concatenate(at)
+
+
+def path_clearance(robot, paths, environments, resolution=None):
+    """The clearance of finished plans: paths[p] ([len][dim]) in environments[p] (None = the empty environment) ->
+    list[PathClearance].  Every segment is sampled as path_samples describes, `resolution` samples per unit of
+    configuration-space length (default: robot.resolution()), and the samples of all paths go through ONE
+    clearance_batch_multi call.  These samples are NOT the rakes validate_motion walks (those step back from the far end
+    in fp32, 8 to a rake): a path's clearance is a measurement at its own, evenly spaced samples, not a replay of the
+    validation, and a positive value does not by itself prove validate_motion true."""
+    res = float(robot.resolution() if resolution is None else resolution)
+    dim = robot.dimension()
+    samples = [path_samples(np.asarray(p, np.float64).reshape(-1, dim), res) if len(p) else
+               (np.zeros((0, dim), np.float32), np.zeros((0, 2), np.int64)) for p in paths]
+    counts = [len(s[0]) for s in samples]
+    values = robot.clearance_batch_multi(np.concatenate([s[0] for s in samples] + [np.zeros((0, dim), np.float32)]),
+                                         environments, counts)
+    out, lo = [], 0
+    for (_, at), n in zip(samples, counts):
+        v = np.asarray(values[lo:lo + n])
+        lo += n
+        if n == 0:
+            out.append(PathClearance(float("inf"), float("inf"), None, None))
+            continue
+        ie, js = int(np.argmin(v[:, 0])), int(np.argmin(v[:, 1]))
+        out.append(PathClearance(float(v[ie, 0]), float(v[js, 1]), (int(at[ie, 0]), int(at[ie, 1])),
+                                 (int(at[js, 0]), int(at[js, 1]))))
+    return out
+
+
+@dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
     edges: np.ndarray     # [m][2] index pairs (valid motions)
