@@ -276,6 +276,36 @@ int vmv_clearance_batch_multi(int robot, const vmv_env *const *envs, const size_
 int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
                                    float *clearance, uint32_t *witness);
 
+/* Clearance gradients: the two values and the witness of vmv_clearance_batch, BIT FOR BIT (the call launches that call's
+ * kernel unchanged, then a second kernel on the same stream that reads q and the witness), plus d_grad [n][2][dim] fp32:
+ * d_grad[i][0] = d env / d q, d_grad[i][1] = d self / d q, both with the WITNESS HELD FIXED - the derivative of the
+ * minimum wherever the minimiser is unique, one of its one-sided derivatives elsewhere.
+ *   env, witness sphere s against the witness primitive: g_j = n . dc_s/dq_j, n = (c_s - p) / |c_s - p|, p the closest
+ *     point of the primitive to c_s by the closest-point arithmetic that produced the value: a sphere's centre; the
+ *     clamped point on a capsule's / z-capsule's segment; the clamped point in a cuboid's / z-cuboid's box - a centre
+ *     inside the box has the flat value -r_s and the gradient 0; heightfield: the value is z - r - height(cell), the
+ *     cell held fixed, so n = (0, 0, 1).  |c_s - p| = 0: gradient 0.
+ *   self, witness pair (a, b): g_j = n . (dc_a/dq_j - dc_b/dq_j), n = (c_a - c_b) / |c_a - c_b|; coincident centres: 0.
+ *   No witness (the value is +inf; env == NULL for the env half): zeros.  A non-finite joint: NaN in all 2 * dim entries,
+ *     beside the NaN values.
+ * dc/dq is the forward-mode tangent of the robot's kinematic op tape as written (tools/gen_hip.py: tangent_tape):
+ * d(q_j)/dq_j = 1, d sin(q_j) = cos(q_j), d cos(q_j) = -sin(q_j) with the kernels' own sine and cosine, product and sum
+ * rules elsewhere (a prismatic joint is no special case), in fp32 without contraction.  A configuration's gradient does
+ * not depend on its batch, on its position in it, or on which of these calls computed it; the multi-environment call is
+ * bit for bit one call per environment.
+ * d_witness may be NULL (the call then uses scratch per (device, stream), released by vmv_release_staging).  Checks,
+ * their order and what is refused (point clouds, attachments) are those of vmv_clearance_batch / _multi; a NULL d_grad
+ * is VMV_ERR_INVALID_ARGUMENT like a NULL d_q or d_clearance.  A refused call writes nothing; n == 0 needs no device. */
+int vmv_clearance_grad_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance /* [n][2] */,
+                             float *d_grad /* [n][2][dim] */, uint32_t *d_witness /* [n][4], may be NULL */, void *stream);
+int vmv_clearance_grad_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, float *grad,
+                                  uint32_t *witness);
+/* One clearance launch plus one gradient launch, however many environments. */
+int vmv_clearance_grad_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                   const float *d_q, float *d_clearance, float *d_grad, uint32_t *d_witness, void *stream);
+int vmv_clearance_grad_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                        const float *q, float *clearance, float *grad, uint32_t *witness);
+
 /* sphere_environment_in_collision(environment, x, y, z, r) — collision/validity.hh:47-158, the predicate every fkcc
  * check is made of (and CAPT::collides / MVT::collides behind it, collision/capt.hh:374-415), for a batch of free
  * spheres: spheres [n][4] = x y z r, hits[i] = 1 iff sphere i collides with the environment.  Each sphere is its own

@@ -160,6 +160,224 @@ def eval_tape(m, q, batch=4096):
     return out
 
 
+def tangent_tape(m):
+    """Forward-mode derivative of the op tape with respect to the joints, for the fine spheres alone.
+
+    Returns {"ops": the primal ops the fine spheres depend on, in tape order,
+             "nz":  {op: joints whose tangent of that op is structurally non-zero, ascending},
+             "tan": {(op, joint): form}}; a form says how the tangent d[op][joint] is made of primal values v[.] and
+    earlier tangents of the same joint:
+        ("one",)            1                         (an `in`)
+        ("cos", a)          cos(v[a])                 (sin of the joint input a)
+        ("nsin", a)         -sin(v[a])                (cos of the joint input a)
+        ("copy", a)         d[a]                      (cadd; add / sub with one structurally zero side)
+        ("neg", a)          -d[a]
+        ("add", a, b)       d[a] + d[b]
+        ("sub", a, b)       d[a] - d[b]
+        ("cmul", c, b)      c * d[b]
+        ("mul", terms)      sum of d[x] * v[y] over the one or two (x, y) of terms (the product rule, zero terms left out)
+    sin and cos are applied to joint inputs only, in every model; anything else is refused here."""
+    ops = m["ops"]
+    want = set()
+    stack = [v for s in range(m["n_spheres"]) for (kind, v) in m["outputs"][s] if kind == "op"]
+    while stack:
+        i = stack.pop()
+        if i in want:
+            continue
+        want.add(i)
+        stack += deps(*ops[i])
+    nz, tan = {}, {}
+    for i in sorted(want):
+        op, a, b = ops[i]
+        js = set()
+        if op == "in":
+            js = {a}
+            tan[(i, a)] = ("one",)
+        elif op in ("sin", "cos"):
+            if ops[a][0] != "in":
+                raise ValueError(f"op {i}: {op} of something that is not a joint input")
+            js = {ops[a][1]}
+            tan[(i, ops[a][1])] = ("cos", a) if op == "sin" else ("nsin", a)
+        elif op == "neg":
+            js = set(nz[a])
+            for j in js:
+                tan[(i, j)] = ("neg", a)
+        elif op == "mul":
+            js = set(nz[a]) | set(nz[b])
+            for j in js:
+                tan[(i, j)] = ("mul", tuple(t for t, live in (((a, b), j in nz[a]), ((b, a), j in nz[b])) if live))
+        elif op in ("add", "sub"):
+            js = set(nz[a]) | set(nz[b])
+            for j in js:
+                if j in nz[a] and j in nz[b]:
+                    tan[(i, j)] = (op, a, b)
+                elif j in nz[a]:
+                    tan[(i, j)] = ("copy", a)
+                else:
+                    tan[(i, j)] = ("copy", b) if op == "add" else ("neg", b)
+        elif op == "cmul":
+            js = set(nz[b])
+            for j in js:
+                tan[(i, j)] = ("cmul", a, b)
+        elif op == "cadd":
+            js = set(nz[b])
+            for j in js:
+                tan[(i, j)] = ("copy", b)
+        elif op != "const":
+            raise ValueError(op)
+        nz[i] = sorted(js)
+    return {"ops": sorted(want), "nz": nz, "tan": tan}
+
+
+def tangent_op_count(m, tt=None):
+    """fp32 operations the tangent tape costs: copies and ones are names, a two-term product rule is three operations"""
+    tt = tt or tangent_tape(m)
+    cost = {"one": 0, "copy": 0, "cos": 0, "nsin": 1, "neg": 1, "add": 1, "sub": 1, "cmul": 1}
+    return sum(2 * len(f[1]) - 1 if f[0] == "mul" else cost[f[0]] for f in tt["tan"].values())
+
+
+def eval_tangent_tape(m, q, tt=None):
+    """float64 evaluation of tangent_tape for configurations q[N][dim] -> (centres [N][n_spheres][3] of the fine spheres,
+    their Jacobians [N][n_spheres][3][dim]); structurally zero entries are exact zeros.  (For the tests: the device
+    evaluates the emitted sphere_fk_grad.)"""
+    tt = tt or tangent_tape(m)
+    ops, tan = m["ops"], tt["tan"]
+    q = np.asarray(q, dtype=np.float64)
+    v, d = {}, {}
+    for i in tt["ops"]:
+        op, a, b = ops[i]
+        if op == "in":
+            v[i] = q[:, a]
+        elif op == "sin":
+            v[i] = np.sin(v[a])
+        elif op == "cos":
+            v[i] = np.cos(v[a])
+        elif op == "neg":
+            v[i] = -v[a]
+        elif op == "const":
+            v[i] = np.full(q.shape[0], float(a))
+        elif op == "mul":
+            v[i] = v[a] * v[b]
+        elif op == "add":
+            v[i] = v[a] + v[b]
+        elif op == "sub":
+            v[i] = v[a] - v[b]
+        elif op == "cmul":
+            v[i] = a * v[b]
+        else:
+            v[i] = a + v[b]
+        for j in tt["nz"][i]:
+            f = tan[(i, j)]
+            if f[0] == "one":
+                d[(i, j)] = np.ones(q.shape[0])
+            elif f[0] == "cos":
+                d[(i, j)] = np.cos(v[f[1]])
+            elif f[0] == "nsin":
+                d[(i, j)] = -np.sin(v[f[1]])
+            elif f[0] == "copy":
+                d[(i, j)] = d[(f[1], j)]
+            elif f[0] == "neg":
+                d[(i, j)] = -d[(f[1], j)]
+            elif f[0] == "add":
+                d[(i, j)] = d[(f[1], j)] + d[(f[2], j)]
+            elif f[0] == "sub":
+                d[(i, j)] = d[(f[1], j)] - d[(f[2], j)]
+            elif f[0] == "cmul":
+                d[(i, j)] = f[1] * d[(f[2], j)]
+            else:
+                d[(i, j)] = sum(d[(x, j)] * v[y] for x, y in f[1])
+    ns, dim = m["n_spheres"], m["dimension"]
+    c = np.zeros((q.shape[0], ns, 3))
+    jac = np.zeros((q.shape[0], ns, 3, dim))
+    for s in range(ns):
+        for k, (kind, x) in enumerate(m["outputs"][s]):
+            if kind != "op":
+                c[:, s, k] = x
+                continue
+            c[:, s, k] = v[x]
+            for j in tt["nz"][x]:
+                jac[:, s, k, j] = d[(x, j)]
+    return c, jac
+
+
+def emit_sphere_fk_grad(m):
+    """Robot::sphere_fk_grad: the centres of three fine spheres chosen per lane and their 3 x dim Jacobians (DESIGN.md §5j).
+    The primal ops are sphere_fk's, in tape order; each op's structurally non-zero tangents follow it; a sphere's centre and
+    tangents are captured with selects on `index == s` where the sphere is produced, so tangents die with their link."""
+    tt = tangent_tape(m)
+    ops, tan, nz = m["ops"], tt["tan"], tt["nz"]
+    pairs = [p for sg in m["self_groups"] for p in sg["pairs"]]
+    firsts, seconds = {a for a, _ in pairs}, {b for _, b in pairs}
+    L = []
+    L.append("    // Robot::sphere_fk with its joint-space tangents: c[i] = centre of fine sphere s[i], J[i][k][j] = d c[i][k] / d q[j],")
+    L.append("    // i = 0 the environment witness, 1 and 2 the first and second sphere of the self witness (a second sphere only ever")
+    L.append("    // names a pair's second, a first its first).  An index that names no sphere leaves its centre and Jacobian 0.")
+    L.append(f"    // {len(tt['ops'])} primal and {tangent_op_count(m, tt)} tangent operations (tools/gen_hip.py: tangent_tape).")
+    L.append("    __device__ __forceinline__ void sphere_fk_grad(const float (&q)[kDim], const unsigned se, const unsigned sa,")
+    L.append("                                                   const unsigned sb, float (&c)[3][3], float (&J)[3][3][kDim])")
+    L.append("    {")
+    L.append("        for (int i = 0; i < 3; ++i)")
+    L.append("            for (int k = 0; k < 3; ++k)")
+    L.append("            {")
+    L.append("                c[i][k] = 0.0f;")
+    L.append("                for (int j = 0; j < kDim; ++j) J[i][k][j] = 0.0f;")
+    L.append("            }")
+    name = {}
+
+    def tangent(i, j):
+        f = tan[(i, j)]
+        if f[0] == "one":
+            name[(i, j)] = "1.0f"
+            return
+        if f[0] == "copy":
+            name[(i, j)] = name[(f[1], j)]
+            return
+        if f[0] == "cos":
+            e = f"vmv::vcos(t{f[1]})"
+        elif f[0] == "nsin":
+            e = f"-vmv::vsin(t{f[1]})"
+        elif f[0] == "neg":
+            e = f"-{name[(f[1], j)]}"
+        elif f[0] in ("add", "sub"):
+            e = f"{name[(f[1], j)]} {'+' if f[0] == 'add' else '-'} {name[(f[2], j)]}"
+        elif f[0] == "cmul":
+            e = f"{flit(f[1])} * {name[(f[2], j)]}"
+        else:
+            e = " + ".join(f"t{y}" if name[(x, j)] == "1.0f" else f"{name[(x, j)]} * t{y}" for x, y in f[1])
+        name[(i, j)] = f"d{i}_{j}"
+        L.append(f"        const float d{i}_{j} = {e};")
+
+    done = set()
+    last = lambda s: max([v for kind, v in m["outputs"][s] if kind == "op"] + [-1])  # noqa: E731
+    for s in sorted(range(m["n_spheres"]), key=lambda s: (last(s), s)):
+        new = set()
+        stack = [v for kind, v in m["outputs"][s] if kind == "op"]
+        while stack:
+            i = stack.pop()
+            if i in new or i in done:
+                continue
+            new.add(i)
+            stack += deps(*ops[i])
+        for i in sorted(new):
+            op, a, b = ops[i]
+            L.append(f"        const float t{i} = {op_expr(op, a, b)};")
+            for j in nz[i]:
+                tangent(i, j)
+        done |= new
+        for slot, var, live in ((0, "se", True), (1, "sa", s in firsts), (2, "sb", s in seconds)):
+            if not live:
+                continue
+            L.append("        {")
+            L.append(f"            const bool take = {var} == {s}u;")
+            for k, (kind, v) in enumerate(m["outputs"][s]):
+                L.append(f"            c[{slot}][{k}] = take ? {f't{v}' if kind == 'op' else flit(v)} : c[{slot}][{k}];")
+                for j in (nz[v] if kind == "op" else []):
+                    L.append(f"            J[{slot}][{k}][{j}] = take ? {name[(v, j)]} : J[{slot}][{k}][{j}];")
+            L.append("        }")
+    L.append("    }")
+    return L
+
+
 LINK_SAMPLES_N = 48  # samples per joint of the per-link reach certificates
 
 
@@ -1385,6 +1603,8 @@ def emit_robot(m):
     for s in range(m["n_spheres"]):
         L.append(f"        out[{s}] = make_float4({em.coord(s, 0)}, {em.coord(s, 1)}, {em.coord(s, 2)}, {flit(radii[s])});")
     L.append("    }")
+    L.append("")
+    L += emit_sphere_fk_grad(m)
     L.append("}  // namespace " + n)
     L.append("")
     L.append(f"struct {n}_traits")
@@ -1451,6 +1671,11 @@ def emit_robot(m):
     L.append("    fkcc_attach(const vmv::EnvView &E, const float (&q)[kDim], vmv::lds_ptr slab, const bool skip)")
     L.append("    {")
     L.append(f"        return {n}::fkcc_attach<G>(E, q, slab, skip);")
+    L.append("    }")
+    L.append("    static __device__ __forceinline__ void sphere_fk_grad(const float (&q)[kDim], const unsigned se, const unsigned sa,")
+    L.append("                                                          const unsigned sb, float (&c)[3][3], float (&J)[3][3][kDim])")
+    L.append("    {")
+    L.append(f"        {n}::sphere_fk_grad(q, se, sa, sb, c, J);")
     L.append("    }")
     L.append("};")
     L.append("")

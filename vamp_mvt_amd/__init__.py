@@ -781,6 +781,95 @@ class _Robot(types.ModuleType):
               "vmv_clearance_batch_multi_host")
         return (out, wit) if witness else out
 
+    def clearance_grad(self, configuration, environment: Environment | None = None):
+        """((env, self), float32[2][dim]): one configuration's clearances and their joint-space gradients, as
+        clearance_grad_batch defines them."""
+        values, grad = self.clearance_grad_batch(_f32(configuration, (self._dim,))[None, :], environment)
+        return (float(values[0, 0]), float(values[0, 1])), grad[0]
+
+    def clearance_grad_batch(self, configurations, environment: Environment | None = None, witness: bool = False):
+        """(float32[n][2], float32[n][2][dim]): clearance_batch's values, bit for bit, and grad[i][0] = d env / d q,
+        grad[i][1] = d self / d q with the witness held fixed: the contact normal times the witness spheres' Jacobians
+        (include/vamp_mvt_amd.h: vmv_clearance_grad_batch).  Zeros where there is no witness (environment=None, an empty
+        environment; a robot without self pairs), and for a sphere centre inside a cuboid, where the value is flat; NaN
+        for a configuration with a non-finite joint.  witness=True appends clearance_batch's witness.  Shapes, types,
+        refused environments and the numpy / torch convention are clearance_batch's."""
+        if environment is not None and not isinstance(environment, Environment):
+            raise TypeError(f"expected Environment or None, got {type(environment).__name__}")
+        torch_in = _is_torch_cuda(configurations)
+        shape = tuple(configurations.shape) if torch_in else None
+        if not torch_in:
+            q = _f32(configurations)
+            shape = q.shape
+        if len(shape) != 2 or shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] configurations")
+        n = shape[0]
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(configurations.device):
+                h = None if environment is None else environment.handle()
+                qt = configurations.contiguous().float()
+                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
+                grad = torch.empty((n, 2, self._dim), dtype=torch.float32, device=qt.device)
+                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
+                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
+                check(lib.vmv_clearance_grad_batch(self._id, h, ctypes.c_void_p(qt.data_ptr()), n,
+                                                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+                                                   ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
+                      "vmv_clearance_grad_batch")
+                return (out, grad, wit) if witness else (out, grad)
+        h = None if environment is None else environment.handle()
+        out = np.zeros((n, 2), np.float32)
+        grad = np.zeros((n, 2, self._dim), np.float32)
+        wit = np.zeros((n, 4), np.uint32) if witness else None
+        check(lib.vmv_clearance_grad_batch_host(self._id, h, _fp(q), n, _fp(out), _fp(grad),
+                                                wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
+              "vmv_clearance_grad_batch_host")
+        return (out, grad, wit) if witness else (out, grad)
+
+    def clearance_grad_batch_multi(self, configurations, environments, counts, witness: bool = False):
+        """clearance_grad_batch for configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None =
+        the empty environment), in one call: one clearance launch and one gradient launch.  Bit for bit one
+        clearance_grad_batch per environment, concatenated."""
+        environments, offsets = _segments(environments, counts)
+        torch_in = _is_torch_cuda(configurations)
+        if torch_in:
+            shape = tuple(configurations.shape)
+        else:
+            q = _f32(configurations)
+            shape = q.shape
+        if len(shape) != 2 or shape[1] != self._dim:
+            raise TypeError(f"expected [n][{self._dim}] configurations")
+        n = shape[0]
+        if int(offsets[-1]) != n:
+            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
+        if torch_in:
+            import torch
+
+            with torch.cuda.device(configurations.device):
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+                qt = configurations.contiguous().float()
+                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
+                grad = torch.empty((n, 2, self._dim), dtype=torch.float32, device=qt.device)
+                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
+                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
+                check(lib.vmv_clearance_grad_batch_multi(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
+                                                         ctypes.c_void_p(qt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                         ctypes.c_void_p(grad.data_ptr()),
+                                                         ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
+                      "vmv_clearance_grad_batch_multi")
+                return (out, grad, wit) if witness else (out, grad)
+        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+        out = np.zeros((n, 2), np.float32)
+        grad = np.zeros((n, 2, self._dim), np.float32)
+        wit = np.zeros((n, 4), np.uint32) if witness else None
+        check(lib.vmv_clearance_grad_batch_multi_host(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
+                                                      _fp(q), _fp(out), _fp(grad),
+                                                      wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
+              "vmv_clearance_grad_batch_multi_host")
+        return (out, grad, wit) if witness else (out, grad)
+
     def prepare(self, environments):
         """Builds what each environment holds for this robot (broad-phase grids, reach certificates, static links) for
         all of them in one call, on the device, instead of one by one on their first use.  None = the empty

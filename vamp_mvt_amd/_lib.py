@@ -170,6 +170,11 @@ def _load():
         "vmv_clearance_batch_host": (I, [I, V, c_float_p, S, c_float_p, c_u32_p]),
         "vmv_clearance_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V, V]),
         "vmv_clearance_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_float_p, c_u32_p]),
+        "vmv_clearance_grad_batch": (I, [I, V, V, S, V, V, V, V]),
+        "vmv_clearance_grad_batch_host": (I, [I, V, c_float_p, S, c_float_p, c_float_p, c_u32_p]),
+        "vmv_clearance_grad_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V, V, V]),
+        "vmv_clearance_grad_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_float_p, c_float_p,
+                                                    c_u32_p]),
         "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
         "vmv_rrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(RrtcSettings),
                                ctypes.POINTER(V)]),

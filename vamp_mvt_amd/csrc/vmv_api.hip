@@ -1647,9 +1647,14 @@ extern "C"
         g_staging.trim();
         return rc;
     }
+    namespace
+    {
+        void release_witness_scratch();  // (the scratch of vmv_clearance_grad_batch, below)
+    }
     int vmv_release_staging(void)
     {
         g_staging.release();
+        release_witness_scratch();
         vmv::release_edge_scratch();  // (waits for the edge batches still in flight: hipFree synchronizes)
         vmv::release_multi_tables();
         return VMV_OK;
@@ -1780,6 +1785,120 @@ extern "C"
         if (int rc = multi_args(robot, envs, offsets, n_envs, q, q, clearance, &n, true); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return clearance_host_common(robot, nullptr, envs, offsets, n_envs, true, q, n, clearance, witness);
+    }
+
+    // ---- clearance gradients (include/vamp_mvt_amd.h: vmv_clearance_grad_batch) ----
+    // The gradient kernel reads the witness the clearance kernel wrote.  A caller without a witness buffer is lent scratch
+    // per (device, stream): calls on one stream run in order, so they share it; grow-only, a larger request frees the old
+    // buffer (hipFree waits for the calls still using it).  The lease holds the pool's lock until the call is enqueued.
+    namespace
+    {
+        struct WitnessScratch
+        {
+            void *p = nullptr;
+            size_t bytes = 0;
+        };
+        std::mutex g_witness_mutex;
+        std::map<std::pair<int, hipStream_t>, WitnessScratch> g_witness;  // never freed at exit (see vmv_release_staging)
+        struct WitnessLease
+        {
+            std::unique_lock<std::mutex> lock{g_witness_mutex, std::defer_lock};
+            int acquire(hipStream_t stream, size_t n, uint32_t **out)
+            {
+                int dev = -1;
+                VMV_HIP(hipGetDevice(&dev));
+                lock.lock();
+                WitnessScratch &w = g_witness[{dev, stream}];
+                if (w.bytes < n * 16)
+                {
+                    if (w.p) (void) hipFree(w.p);
+                    w.p = nullptr, w.bytes = 0;
+                    const size_t want = std::max<size_t>(n * 16, size_t{1} << 16);
+                    VMV_HIP(hipMalloc(&w.p, want));
+                    w.bytes = want;
+                }
+                *out = static_cast<uint32_t *>(w.p);
+                return VMV_OK;
+            }
+        };
+        void release_witness_scratch()
+        {
+            std::lock_guard<std::mutex> g(g_witness_mutex);
+            for (auto &kv : g_witness)
+                if (kv.second.p) (void) hipFree(kv.second.p);
+            g_witness.clear();
+        }
+    }  // namespace
+    // the clearance calls' checks in their order; a NULL d_grad joins the NULL d_q / d_clearance
+    int vmv_clearance_grad_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, float *d_grad,
+                                 uint32_t *d_witness, void *stream)
+    {
+        if (int rc = clearance_args(robot, env, d_q && d_grad ? d_q : nullptr, d_clearance); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (env)
+        {
+            if (int rc = check_device(env); rc != VMV_OK) return rc;
+            if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
+        }
+        WitnessLease lease;
+        if (!d_witness)
+            if (int rc = lease.acquire(static_cast<hipStream_t>(stream), n, &d_witness); rc != VMV_OK) return rc;
+        return kLaunchers[robot]->clearance_grad(env ? &env->launch[robot] : nullptr, d_q, n, d_clearance, d_grad, d_witness,
+                                                 static_cast<hipStream_t>(stream));
+    }
+    int vmv_clearance_grad_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                       const float *d_q, float *d_clearance, float *d_grad, uint32_t *d_witness, void *stream)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_grad, d_clearance, &n, true); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
+        std::vector<const vmv::EnvLaunch *> launch(n_envs);
+        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
+        WitnessLease lease;
+        if (!d_witness)
+            if (int rc = lease.acquire(static_cast<hipStream_t>(stream), n, &d_witness); rc != VMV_OK) return rc;
+        return kLaunchers[robot]->clearance_grad_multi(launch.data(), offsets, n_envs, d_q, d_clearance, d_grad, d_witness,
+                                                       static_cast<hipStream_t>(stream));
+    }
+    // staging of the two host forms: [configurations | clearances | gradients | witness] in the arena
+    static int clearance_grad_host_common(int robot, const vmv_env *env, const vmv_env *const *envs, const size_t *offsets,
+                                          size_t n_envs, bool multi, const float *q, size_t n, float *clearance, float *grad,
+                                          uint32_t *witness)
+    {
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255};
+        const size_t cb = (n * 8 + 255) & ~size_t{255}, gb = (2 * bytes + 255) & ~size_t{255}, wb = n * 16;
+        char *arena = static_cast<char *>(g_staging.get(qb + cb + gb + wb));
+        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
+        float *dq = reinterpret_cast<float *>(arena), *dc = reinterpret_cast<float *>(arena + qb);
+        float *dg = reinterpret_cast<float *>(arena + qb + cb);
+        uint32_t *dw = reinterpret_cast<uint32_t *>(arena + qb + cb + gb);
+        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
+        int rc = multi ? vmv_clearance_grad_batch_multi(robot, envs, offsets, n_envs, dq, dc, dg, dw, nullptr) :
+                         vmv_clearance_grad_batch(robot, env, dq, n, dc, dg, dw, nullptr);
+        if (rc == VMV_OK && hipMemcpy(clearance, dc, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        if (rc == VMV_OK && hipMemcpy(grad, dg, 2 * bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        if (rc == VMV_OK && witness && hipMemcpy(witness, dw, n * 16, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
+        g_staging.trim();
+        return rc;
+    }
+    int vmv_clearance_grad_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, float *grad,
+                                      uint32_t *witness)
+    {
+        if (int rc = clearance_args(robot, env, q && grad ? q : nullptr, clearance); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return clearance_grad_host_common(robot, env, nullptr, nullptr, 0, false, q, n, clearance, grad, witness);
+    }
+    int vmv_clearance_grad_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                            const float *q, float *clearance, float *grad, uint32_t *witness)
+    {
+        size_t n = 0;
+        if (int rc = multi_args(robot, envs, offsets, n_envs, q, grad, clearance, &n, true); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return clearance_grad_host_common(robot, nullptr, envs, offsets, n_envs, true, q, n, clearance, grad, witness);
     }
 
     // ---- multi-GPU sharding arithmetic (vamp_mvt_amd/sharding.py: shard_range) ----

@@ -89,6 +89,12 @@ namespace vmv
         // vmv_clearance_batch_multi: configurations [offsets[k], offsets[k + 1]) against *envs[k], as validate_multi
         int (*clearance_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
                                float *d_out, uint32_t *d_witness, hipStream_t);
+        // vmv_clearance_grad_batch(_multi): the clearance launch as it is, then d_grad [n][2][dim] from the witness it wrote;
+        // d_witness is never nullptr (the API lends per-stream scratch where the caller has none)
+        int (*clearance_grad)(const EnvLaunch *env, const float *d_q, size_t n, float *d_out, float *d_grad, uint32_t *d_witness,
+                              hipStream_t);
+        int (*clearance_grad_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                    float *d_out, float *d_grad, uint32_t *d_witness, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

@@ -1167,6 +1167,65 @@ namespace vmv
         }
     }
 
+    // ------------------------------------------------------------------------
+    // vmv_clearance_grad_batch (include/vamp_mvt_amd.h): c - p for one sphere centre c against ONE primitive
+    // record, p the closest point of the primitive, from prim_clearance's own closest-point arithmetic (the capsule's
+    // parameter through the stored rdv, the cuboid's axes as stored).  The contact normal is n = (c - p) / |c - p| and the
+    // clearance with that witness held fixed has the gradient n . dc/dq.  A centre inside a cuboid (where the value is the
+    // flat -r) gives 0.  The record comes in registers (a b c d = its float4s in order, as many as the kind has): the
+    // gradient kernel fetches its one record per lane before the kinematics and evaluates every kind's form on it
+    // unconditionally - selects between cheap values stay selects, while a form under a branch draws the whole capture
+    // chain of the sphere centre into that branch and with it every sphere's centre into registers.
+    // ------------------------------------------------------------------------
+    template <int T>
+    __device__ __forceinline__ void prim_offset(const v4f a, const v4f b, const v4f c, const v4f d, float x, float y, float z,
+                                                float &dx, float &dy, float &dz)
+    {
+        if constexpr (T == kSphere)  // x y z r | min_d
+        {
+            dx = x - a.x, dy = y - a.y, dz = z - a.z;
+        }
+        else if constexpr (T == kCapsule)  // x1 y1 z1 xv | yv zv r rdv
+        {
+            const float dot = dot3(x - a.x, y - a.y, z - a.z, a.w, b.x, b.y);
+            const float cdf = vclamp(dot * b.w, 0.F, 1.F);
+            dx = x - (a.x + a.w * cdf), dy = y - (a.y + b.x * cdf), dz = z - (a.z + b.y * cdf);
+        }
+        else if constexpr (T == kZCapsule)  // x1 y1 z1 zv | r rdv min_d 0
+        {
+            const float dot = (z - a.z) * a.w;
+            const float cdf = vclamp(dot * b.y, 0.F, 1.F);
+            dx = x - a.x, dy = y - a.y, dz = z - (a.z + a.w * cdf);
+        }
+        else if constexpr (T == kCuboid)  // x y z a1x | a1y a1z a2x a2y | a2z a3x a3y a3z | r1 r2 r3 min_d
+        {
+            const float xs = x - a.x, ys = y - a.y, zs = z - a.z;
+            // c - p in the box's axes: what each coordinate exceeds its half extent by, with the coordinate's sign
+            const float u1 = dot3(a.w, b.x, b.y, xs, ys, zs), u2 = dot3(b.z, b.w, c.x, xs, ys, zs);
+            const float u3 = dot3(c.y, c.z, c.w, xs, ys, zs);
+            const float a1 = x86_max(vabs(u1) - d.x, 0.f), a2 = x86_max(vabs(u2) - d.y, 0.f);
+            const float a3 = x86_max(vabs(u3) - d.z, 0.f);
+            const float s1 = u1 < 0.f ? -a1 : a1, s2 = u2 < 0.f ? -a2 : a2, s3 = u3 < 0.f ? -a3 : a3;
+            dx = dot3(s1, s2, s3, a.w, b.z, c.y), dy = dot3(s1, s2, s3, b.x, b.w, c.z), dz = dot3(s1, s2, s3, b.y, c.x, c.w);
+        }
+        else  // x y z a1x | a1y a2x a2y r1 | r2 r3 min_d 0
+        {
+            const float xs = x - a.x, ys = y - a.y, zs = z - a.z;
+            const float u1 = (a.w * xs) + (b.x * ys), u2 = (b.y * xs) + (b.z * ys);
+            const float a1 = x86_max(vabs(u1) - b.w, 0.f), a2 = x86_max(vabs(u2) - c.x, 0.f);
+            const float a3 = x86_max(vabs(zs) - c.y, 0.f);
+            const float s1 = u1 < 0.f ? -a1 : a1, s2 = u2 < 0.f ? -a2 : a2;
+            dx = (s1 * a.w) + (s2 * b.y), dy = (s1 * b.x) + (s2 * b.z), dz = zs < 0.f ? -a3 : a3;
+        }
+    }
+    // v / |v|, and 0 for v = 0 (the division is by +inf then: no select with a quotient on one side, see above)
+    __device__ __forceinline__ void unit3(float &x, float &y, float &z)
+    {
+        const float len = sqrtf(dot3(x, y, z, x, y, z));
+        const float by = len > 0.0f ? len : __builtin_inff();
+        x = x / by, y = y / by, z = z / by;
+    }
+
     // The list part of the environment header (counts, block offsets, candidate-word bases), fetched ONCE per gate /
     // fine call and pinned in SGPRs.  Read where they are used, each field was its own scalar load behind the branch
     // that first needs it, and — the wave-level LDS hand-offs between re-dealt rounds are memory fences to the compiler —

@@ -1140,6 +1140,128 @@ namespace VMV_ROBOT_NS
     }
 
     // ---------------------------------------------------------------------------------------------------------
+    // vmv_clearance_grad_batch: the joint-space gradients of the two clearances with the witness held fixed
+    // (include/vamp_mvt_amd.h, DESIGN.md 5j).  Runs behind the unchanged clearance kernel on the same stream and reads the
+    // witness that kernel wrote, so values and witness are the clearance call's by construction.  One lane = one
+    // configuration: Robot::sphere_fk_grad gives the centres and 3 x dim Jacobians of the three witness spheres, the ONE
+    // witness record is fetched per lane from the environment's HBM block (no staging, no LDS), the normal is
+    // prim_offset's c - p, normalised, and grad[i] = [env | self][dim] leaves through plain vector stores.  A witness that names nothing
+    // (and one that is out of range: never written by the clearance kernel, never followed) gives zeros; a non-finite
+    // joint gives 2 * dim NaNs.  Workgroups of one wave: the Jacobians alone are 9 * dim registers.
+    // ---------------------------------------------------------------------------------------------------------
+    constexpr uint32_t kGradBlock = (uint32_t) kWave;
+
+    __device__ __forceinline__ void clearance_grad_lane(const EnvDev *__restrict__ env, const float *__restrict__ q, const size_t i,
+                                                        const uint32_t *__restrict__ witness, float *__restrict__ grad)
+    {
+        constexpr uint32_t kNone = 0xffffffffu;
+        float cfg[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cfg[j] = q[i * R::kDim + j];
+        const bool finite = sanitize_config<R::kDim>(cfg);
+        const uint32_t w_sphere = witness[4 * i], w_kind = witness[4 * i + 1], w_index = witness[4 * i + 2];
+        const uint32_t w_pair = witness[4 * i + 3];
+
+        // which record, if any: kind and index checked against the environment's own counts; its float4s are fetched here,
+        // in front of the kinematics
+        const env_cptr D = (env_cptr) env;
+        bool has_env = false;
+        v4f ra = {0.f, 0.f, 0.f, 0.f}, rb = ra, rc = ra, rd = ra;
+        if (env != nullptr && w_sphere < (uint32_t) R::kNSpheres)
+        {
+            const uint32_t n_kind = w_kind == (uint32_t) kSphere ? D->n_sphere : w_kind == (uint32_t) kCapsule ? D->n_capsule :
+                                    w_kind == (uint32_t) kZCapsule ? D->n_zcapsule : w_kind == (uint32_t) kCuboid ? D->n_cuboid :
+                                    w_kind == (uint32_t) kZCuboid ? D->n_zcuboid :
+                                    w_kind == kClearanceHeightfield ? D->n_heightfield : 0u;
+            has_env = w_index < n_kind;
+            if (has_env && w_kind != kClearanceHeightfield)
+            {
+                const uint32_t off = w_kind == (uint32_t) kSphere ? D->off_sphere + w_index * (uint32_t) kSphereRec :
+                                     w_kind == (uint32_t) kCapsule ? D->off_capsule + w_index * (uint32_t) kCapsuleRec :
+                                     w_kind == (uint32_t) kZCapsule ? D->off_zcapsule + w_index * (uint32_t) kZCapsuleRec :
+                                     w_kind == (uint32_t) kCuboid ? D->off_cuboid + w_index * (uint32_t) kCuboidRec :
+                                                                    D->off_zcuboid + w_index * (uint32_t) kZCuboidRec;
+                const g_v4f *rec = (const g_v4f *) ((gf_cptr) D->prims + off);
+                ra = rec[0], rb = rec[1];  // (every record has two float4s)
+                if (w_kind == (uint32_t) kCapsule || w_kind == (uint32_t) kCuboid || w_kind == (uint32_t) kZCuboid) rc = rec[2];
+                if (w_kind == (uint32_t) kCuboid) rd = rec[3];
+            }
+        }
+        uint32_t sa = kNone, sb = kNone;
+        if constexpr (R::kNSelfPairs > 0)
+        {
+            const bool has_self = w_pair < (uint32_t) R::kNSelfPairs;
+            sa = has_self ? (uint32_t) VMV_ROBOT_NS::kSelfPairs[has_self ? w_pair : 0u][0] : kNone;
+            sb = has_self ? (uint32_t) VMV_ROBOT_NS::kSelfPairs[has_self ? w_pair : 0u][1] : kNone;
+        }
+
+        float c[3][3], J[3][3][R::kDim];
+        R::sphere_fk_grad(cfg, has_env ? w_sphere : kNone, sa, sb, c, J);
+
+        // c - p of every kind on the one record, the witness's kind picked by selects (vmv_device.h: prim_offset); a
+        // heightfield's value is z - r - height(cell) with the cell held fixed: (0, 0, 1); no witness: 0
+        float nx = 0.0f, ny = 0.0f, nz = has_env && w_kind == kClearanceHeightfield ? 1.0f : 0.0f;
+        {
+            const bool prim = has_env && w_kind != kClearanceHeightfield;
+            float x, y, z;
+            prim_offset<kSphere>(ra, rb, rc, rd, c[0][0], c[0][1], c[0][2], x, y, z);
+            nx = prim && w_kind == (uint32_t) kSphere ? x : nx, ny = prim && w_kind == (uint32_t) kSphere ? y : ny;
+            nz = prim && w_kind == (uint32_t) kSphere ? z : nz;
+            prim_offset<kCapsule>(ra, rb, rc, rd, c[0][0], c[0][1], c[0][2], x, y, z);
+            nx = prim && w_kind == (uint32_t) kCapsule ? x : nx, ny = prim && w_kind == (uint32_t) kCapsule ? y : ny;
+            nz = prim && w_kind == (uint32_t) kCapsule ? z : nz;
+            prim_offset<kZCapsule>(ra, rb, rc, rd, c[0][0], c[0][1], c[0][2], x, y, z);
+            nx = prim && w_kind == (uint32_t) kZCapsule ? x : nx, ny = prim && w_kind == (uint32_t) kZCapsule ? y : ny;
+            nz = prim && w_kind == (uint32_t) kZCapsule ? z : nz;
+            prim_offset<kCuboid>(ra, rb, rc, rd, c[0][0], c[0][1], c[0][2], x, y, z);
+            nx = prim && w_kind == (uint32_t) kCuboid ? x : nx, ny = prim && w_kind == (uint32_t) kCuboid ? y : ny;
+            nz = prim && w_kind == (uint32_t) kCuboid ? z : nz;
+            prim_offset<kZCuboid>(ra, rb, rc, rd, c[0][0], c[0][1], c[0][2], x, y, z);
+            nx = prim && w_kind == (uint32_t) kZCuboid ? x : nx, ny = prim && w_kind == (uint32_t) kZCuboid ? y : ny;
+            nz = prim && w_kind == (uint32_t) kZCuboid ? z : nz;
+        }
+        unit3(nx, ny, nz);
+        float mx = c[1][0] - c[2][0], my = c[1][1] - c[2][1], mz = c[1][2] - c[2][2];  // (no self witness: both centres are 0)
+        unit3(mx, my, mz);
+        // g + 0 = g (and +0 for -0), g + NaN = NaN: the non-finite configuration's NaNs without a branch around the sums
+        const float poison = finite ? 0.0f : __builtin_nanf("");
+        float *out = grad + i * (size_t) (2 * R::kDim);
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) out[j] = dot3(nx, ny, nz, J[0][0][j], J[0][1][j], J[0][2][j]) + poison;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+            out[R::kDim + j] = dot3(mx, my, mz, J[1][0][j] - J[2][0][j], J[1][1][j] - J[2][1][j], J[1][2][j] - J[2][2][j]) + poison;
+    }
+
+    // n is 32-bit: the launcher cuts larger batches into the clearance kernel's slices.  (Templates for their place in the
+    // code object, as the two kernels above.)
+    template <int = 0>
+    __global__ __launch_bounds__(kGradBlock) void clearance_grad_kernel(const EnvDev *__restrict__ env, const float *__restrict__ q,
+                                                                        const uint32_t n, const uint32_t *__restrict__ witness,
+                                                                        float *__restrict__ grad)
+    {
+        const uint32_t i = blockIdx.x * kGradBlock + threadIdx.x;
+        if (i < n) clearance_grad_lane(env, q, i, witness, grad);
+    }
+
+    // vmv_clearance_grad_batch_multi: the (segment, first configuration) tiles of clearance_multi_kernel, kGradBlock /
+    // kClrTile of them per workgroup; a lane finds its environment through its tile's segment.
+    template <int = 0>
+    __global__ __launch_bounds__(kGradBlock) void clearance_grad_multi_kernel(const MultiSeg *__restrict__ segs,
+                                                                              const MultiTile *__restrict__ tiles,
+                                                                              const uint32_t n_tiles, const float *__restrict__ q,
+                                                                              const uint32_t *__restrict__ witness,
+                                                                              float *__restrict__ grad)
+    {
+        const uint32_t t = blockIdx.x * (kGradBlock / kClrTile) + threadIdx.x / kClrTile;
+        if (t >= n_tiles) return;
+        const MultiTile tile = tiles[t];
+        const MultiSeg S = segs[tile.seg];
+        const uint32_t i = tile.word + threadIdx.x % kClrTile;
+        if (i < S.hi) clearance_grad_lane(S.env, q, i, witness, grad);
+    }
+
+    // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
     namespace
@@ -1780,10 +1902,29 @@ namespace VMV_ROBOT_NS
             return VMV_OK;
         }
 
+        // vmv_clearance_grad_batch: the clearance launch above as it is, then the gradient kernel on the same stream, which
+        // reads the witness that launch wrote (d_witness is never nullptr here: the API lends scratch)
+        int launch_clearance_grad(const EnvLaunch *env, const float *d_q, size_t n, float *d_out, float *d_grad,
+                                  uint32_t *d_witness, hipStream_t stream)
+        {
+            if (int rc = launch_clearance(env, d_q, n, d_out, d_witness, stream); rc != VMV_OK) return rc;
+            constexpr size_t kSlice = (size_t{1} << 20) * kClrTile;  // (the clearance launcher's slices)
+            for (size_t lo = 0; lo < n; lo += kSlice)
+            {
+                const uint32_t m = (uint32_t) (n - lo < kSlice ? n - lo : kSlice);
+                hipLaunchKernelGGL(clearance_grad_kernel<>, dim3((m + kGradBlock - 1u) / kGradBlock), dim3(kGradBlock), 0, stream,
+                                   env ? env->d_env : (const EnvDev *) nullptr, d_q + lo * R::kDim, m, d_witness + 4 * lo,
+                                   d_grad + 2 * lo * R::kDim);
+            }
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+
         // vmv_clearance_batch_multi: one launch, one workgroup per tile of kClrTile configurations of one segment.
-        // Table: [segments | tiles].
-        int launch_clearance_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
-                                   float *d_out, uint32_t *d_witness, hipStream_t stream)
+        // Table: [segments | tiles].  d_grad != nullptr (vmv_clearance_grad_batch_multi): the gradient kernel follows, on
+        // the same table.
+        int launch_clearance_multi_both(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                        float *d_out, float *d_grad, uint32_t *d_witness, hipStream_t stream)
         {
             constexpr size_t kMaxGrid = size_t{1} << 20;  // workgroups per launch
             if (offsets[n_envs] == 0) return VMV_OK;
@@ -1817,8 +1958,25 @@ namespace VMV_ROBOT_NS
             for (size_t t0 = 0; t0 < n_tiles; t0 += kMaxGrid)
                 hipLaunchKernelGGL(clearance_multi_kernel<>, dim3((uint32_t) std::min(n_tiles - t0, kMaxGrid)), dim3(kBlock), shmem,
                                    stream, d_segs, d_tiles + t0, d_q, d_out, d_witness);
+            constexpr size_t kGradTiles = kMaxGrid * (kGradBlock / kClrTile);  // tiles per launch of the gradient kernel
+            for (size_t t0 = 0; d_grad && t0 < n_tiles; t0 += kGradTiles)
+            {
+                const uint32_t m = (uint32_t) std::min(n_tiles - t0, kGradTiles);
+                hipLaunchKernelGGL(clearance_grad_multi_kernel<>, dim3((m + kGradBlock / kClrTile - 1u) / (kGradBlock / kClrTile)),
+                                   dim3(kGradBlock), 0, stream, d_segs, d_tiles + t0, m, d_q, d_witness, d_grad);
+            }
             VMV_HIP_TU(hipGetLastError());
             return VMV_OK;
+        }
+        int launch_clearance_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                   float *d_out, uint32_t *d_witness, hipStream_t stream)
+        {
+            return launch_clearance_multi_both(envs, offsets, n_envs, d_q, d_out, nullptr, d_witness, stream);
+        }
+        int launch_clearance_grad_multi(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
+                                        float *d_out, float *d_grad, uint32_t *d_witness, hipStream_t stream)
+        {
+            return launch_clearance_multi_both(envs, offsets, n_envs, d_q, d_out, d_grad, d_witness, stream);
         }
     }  // namespace
 
@@ -1832,6 +1990,8 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_prepare_multi,
                                                     VMV_ROBOT_NS::launch_eefk, VMV_ROBOT_NS::launch_contacts,
                                                     VMV_ROBOT_NS::R::kNSelfPairs,
-                                                    VMV_ROBOT_NS::launch_clearance, VMV_ROBOT_NS::launch_clearance_multi};
+                                                    VMV_ROBOT_NS::launch_clearance, VMV_ROBOT_NS::launch_clearance_multi,
+                                                    VMV_ROBOT_NS::launch_clearance_grad,
+                                                    VMV_ROBOT_NS::launch_clearance_grad_multi};
 #endif
 }  // namespace vmv

@@ -693,6 +693,72 @@ def path_clearance(robot, paths, environments, resolution=None):
 
 
 @dataclass
+class PushOut:
+    """push_out's answer: the configurations ([n][dim] float32), their (env, self) clearances ([n][2] float32, bit for bit
+    clearance_batch of those configurations), reached[i] = both clearances of configuration i are at least the margin,
+    and the number of clearance_grad_batch calls made"""
+    configurations: np.ndarray
+    clearances: np.ndarray
+    reached: np.ndarray
+    calls: int
+
+
+def push_out(robot, configurations, environment=None, margin=0.01, max_steps=32, max_step=0.05):
+    """Moves configurations that are in contact, or closer to it than `margin` (metres), along the clearance gradient
+    until both clearances reach `margin` -> PushOut.  A repair for grazing starts and goals, nothing more.
+
+    Every round is ONE robot.clearance_grad_batch call for the configurations still below the margin (the input first,
+    then after every step: at most max_steps + 1 calls).  With m the smaller of a configuration's two clearances and g
+    that value's gradient, the step is g * (margin - m) / |g|^2 - the first-order step to m = margin - shortened to
+    |step|_2 <= max_step (radians; metres for a prismatic joint), and the result is clipped to the joint bounds; host
+    arithmetic in float32.  A configuration with g = 0 (a sphere centre inside a cuboid, coincident centres) or a NaN
+    value (a non-finite joint) is left where it is and reported as not reached.  Per configuration the best min(env, self)
+    seen and the configuration that gave it are kept and returned, so the returned min(env, self) is never below the
+    input's, and the returned clearances were computed for exactly the returned configurations.
+
+    There is NO line search, and NO collision checking of the motion between the input and the output: the gradient is
+    that of the current witness, a step may bring another contact closer, and the straight line from input to output may
+    pass through an obstacle.  Validate the result, and the motion if it matters."""
+    dim = robot.dimension()
+    q = np.array(configurations, dtype=np.float32)
+    if q.ndim != 2 or q.shape[1] != dim:
+        raise TypeError(f"expected [n][{dim}] configurations")
+    if not (max_steps >= 0 and max_step > 0):
+        raise ValueError("max_steps must be at least 0 and max_step positive")
+    n = len(q)
+    margin, max_step = np.float32(margin), np.float32(max_step)
+    lower, upper = np.asarray(robot.lower_bounds(), np.float32), np.asarray(robot.upper_bounds(), np.float32)
+    best_q, best_v = q.copy(), np.full((n, 2), np.nan, np.float32)
+    best_m = np.full(n, -np.inf, np.float32)
+    reached = np.zeros(n, bool)
+    active = np.arange(n)
+    calls = 0
+    for step in range(int(max_steps) + 1):
+        if len(active) == 0:
+            break
+        values, grad = robot.clearance_grad_batch(q[active], environment)[:2]
+        values, grad = np.asarray(values, np.float32), np.asarray(grad, np.float32)
+        calls += 1
+        m = np.minimum(values[:, 0], values[:, 1])  # (NaN if either is)
+        better = (m > best_m[active]) | (step == 0)
+        at = active[better]
+        best_q[at], best_v[at], best_m[at] = q[at], values[better], m[better]
+        done = m >= margin
+        reached[active[done]] = True
+        g = np.where((values[:, 0] <= values[:, 1])[:, None], grad[:, 0], grad[:, 1])
+        gg = (g * g).sum(axis=1, dtype=np.float32)
+        go = ~done & ~np.isnan(m) & (gg > 0) & np.isfinite(gg)
+        active, m, g, gg = active[go], m[go], g[go], gg[go]
+        if step == int(max_steps) or len(active) == 0:
+            break
+        delta = g * ((margin - m) / gg)[:, None]
+        length = np.sqrt((delta * delta).sum(axis=1, dtype=np.float32))
+        delta *= np.where(length > max_step, max_step / np.maximum(length, np.float32(1e-30)), np.float32(1.0))[:, None]
+        q[active] = np.clip(q[active] + delta.astype(np.float32), lower, upper)
+    return PushOut(best_q, best_v, reached, calls)
+
+
+@dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
     edges: np.ndarray     # [m][2] index pairs (valid motions)
