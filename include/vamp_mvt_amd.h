@@ -326,8 +326,10 @@ int vmv_eefk_batch_host(int robot, const float *q, size_t n, float *out);
 int vmv_validate_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint64_t *bits);
 int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *start, const float *goal, size_t n,
                                    uint64_t *bits);
-/* The host-buffer variants stage through a per-thread device arena that is reused between calls (requests above 64 MiB
- * are not kept), and vmv_validate_motion_batch keeps 8 bytes of device scratch per edge per (device, stream) for its task
+/* Every call that takes host buffers (the *_host variants, vmv_contacts_batch_host and vmv_filter_self_from_pointcloud
+ * included) stages through a per-thread device arena that is reused between calls: a thread keeps up to 64 MiB of device
+ * memory after such a call (requests above 64 MiB are not kept beyond their call) until it calls this function.
+ * vmv_validate_motion_batch keeps 8 bytes of device scratch per edge per (device, stream) for its task
  * lists, the multi-environment calls their tables.  Frees the calling thread's arena and every stream's scratch and tables
  * (waits for the batches in flight); optional — none of this memory is touched at thread or process exit. */
 int vmv_release_staging(void);

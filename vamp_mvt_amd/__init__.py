@@ -11,6 +11,7 @@ no CPU path: without a HIP device every compute call raises VmvError(VMV_ERR_NO_
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import sys
@@ -493,6 +494,14 @@ class Environment:
 # ---------------------------------------------------------------------------------------------------------
 # per-robot modules (reference bindings/robot_helper.hh:326-597, path subset + batched calls)
 # ---------------------------------------------------------------------------------------------------------
+_NO_ENVIRONMENT = object()  # _Robot._batched: the call takes no environment
+_NO_CONTEXT = contextlib.nullcontext()
+# a zero-length ctypes array at a numpy buffer passes where the pointer type is declared, at half the cost of
+# ndarray.ctypes.data_as (which dominates the Python side of a one-configuration call); the caller holds the array
+_AT = {t: (t._type_ * 0).from_address for t in (_lib.c_float_p, _lib.c_u64_p, _lib.c_u32_p)}
+_OUTPUT_DTYPES = {"bits": ("int64", np.uint64), "f32": ("float32", np.float32), "u32": ("int32", np.uint32)}  # torch, numpy
+
+
 def _is_torch_cuda(x):
     t = sys.modules.get("torch")
     return t is not None and isinstance(x, t.Tensor) and x.is_cuda
@@ -654,12 +663,7 @@ class _Robot(types.ModuleType):
         return self.eefk_batch(_f32(configuration, (self._dim,))[None, :])[0]
 
     def eefk_batch(self, configurations):
-        q = _f32(configurations)
-        if q.ndim != 2 or q.shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        out = np.zeros((q.shape[0], 4, 4), np.float32)
-        check(lib.vmv_eefk_batch_host(self._id, _fp(q), q.shape[0], _fp(out)), "vmv_eefk_batch_host")
-        return out
+        return self._batched("vmv_eefk_batch", [configurations], [((4, 4), "f32", True)])[0]
 
     def fk(self, configuration):
         """<robot>.fk(q) -> list[Sphere] — robot_helper.hh:234-247."""
@@ -686,18 +690,77 @@ class _Robot(types.ModuleType):
             environment = _EMPTY_ENVIRONMENT
         return environment.handle()
 
+    def _batched(self, symbol, inputs, outputs, environment=_NO_ENVIRONMENT, nullable=False, environments=None, counts=None):
+        """The one path of the batched calls.  inputs: one or two [n][dim] arrays; outputs: (trailing shape, dtype,
+        wanted) each, dtype one of _OUTPUT_DTYPES; environment: None = the empty environment, or with `nullable` a NULL
+        handle; environments / counts: the multi-environment form.  Every Python-side check runs before any library
+        call (Environment.handle() is one).  numpy in: `symbol`_host, numpy out; torch CUDA tensors in: `symbol` on the
+        tensor's device and torch's current stream, torch out.  -> the outputs (None where not wanted), validity words
+        unpacked to bool[n]."""
+        multi = environments is not None
+        if multi:
+            environments, offsets = _segments(environments, counts)
+        elif nullable and environment is not None and not isinstance(environment, Environment):
+            raise TypeError(f"expected Environment or None, got {type(environment).__name__}")
+        torch_in = _is_torch_cuda(inputs[0])
+        if torch_in and not all(_is_torch_cuda(x) for x in inputs):
+            raise TypeError("starts is a torch CUDA tensor, goals is not")
+        if not torch_in:
+            inputs = [_f32(x) for x in inputs]
+        shape = tuple(inputs[0].shape)
+        if len(shape) != 2 or shape[1] != self._dim or tuple(inputs[-1].shape) != shape:
+            raise TypeError(f"expected [n][{self._dim}] configurations" if len(inputs) == 1 else
+                            f"expected two [n][{self._dim}] arrays")
+        n = shape[0]
+        if multi and int(offsets[-1]) != n:
+            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} " +
+                             ("configurations" if len(inputs) == 1 else "edges"))
+        if torch_in:
+            import torch
+
+            device = inputs[0].device
+        with torch.cuda.device(device) if torch_in else _NO_CONTEXT:
+            if multi:
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+                head = [handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs)]
+            elif environment is _NO_ENVIRONMENT:
+                head = []
+            else:
+                head = [None if nullable and environment is None else self._env(environment)]
+            name = symbol if torch_in else symbol + "_host"
+            fn = getattr(lib, name)
+            types = fn.argtypes
+            args = [self._id, *head]
+            if torch_in:
+                inputs = [x.to(device).contiguous().float() for x in inputs]  # (held until the call has returned)
+            for a in inputs:
+                args.append(ctypes.c_void_p(a.data_ptr()) if torch_in else _AT[types[len(args)]](a.ctypes.data))
+            if not multi:
+                args.append(n)
+            outs = []
+            for trailing, dtype, wanted in outputs:
+                shape = ((n + 63) // 64,) if dtype == "bits" else (n, *trailing)
+                if not wanted:
+                    out = None
+                elif torch_in:  # (validity words start at zero, as they always have; nothing else needs a fill)
+                    out = (torch.zeros if dtype == "bits" else torch.empty)(shape, dtype=getattr(torch, _OUTPUT_DTYPES[dtype][0]),
+                                                                            device=device)
+                else:
+                    out = np.zeros(shape, _OUTPUT_DTYPES[dtype][1])
+                args.append(None if out is None else ctypes.c_void_p(out.data_ptr()) if torch_in else
+                            _AT[types[len(args)]](out.ctypes.data))
+                outs.append(out)
+            if torch_in:
+                args.append(ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+            check(fn(*args), name)
+        for i, (_, dtype, _) in enumerate(outputs):
+            if dtype == "bits":
+                outs[i] = (_torch_unpack_bits if torch_in else unpack_bits)(outs[i], n)
+        return outs
+
     def validate_batch(self, configurations, environment: Environment | None = None):
         """bool[n] (numpy in -> numpy out; torch CUDA tensor in -> torch.bool CUDA tensor out)."""
-        if _is_torch_cuda(configurations):
-            return self._torch_bits(configurations, None, environment)
-        q = _f32(configurations)
-        if q.ndim != 2 or q.shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = q.shape[0]
-        bits = np.zeros((n + 63) // 64, np.uint64)
-        check(lib.vmv_validate_batch_host(self._id, self._env(environment), _fp(q), n,
-                                          bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_host")
-        return unpack_bits(bits, n)
+        return self._batched("vmv_validate_batch", [configurations], [((), "bits", True)], environment)[0]
 
     def clearance(self, configuration, environment: Environment | None = None):
         """(env, self): the signed distance from contact of one configuration, as clearance_batch defines it."""
@@ -713,72 +776,16 @@ class _Robot(types.ModuleType):
         3 cuboid, 4 z-cuboid, 5 heightfield, env_index the position in Environment.host_tables()'s sorted list of that
         kind.  Environments with a point cloud or an attachment are refused.  numpy in -> numpy out; a torch CUDA tensor
         in -> torch CUDA tensors out (the witness as int32: UINT32_MAX reads -1), launched on torch's current stream."""
-        if environment is not None and not isinstance(environment, Environment):
-            raise TypeError(f"expected Environment or None, got {type(environment).__name__}")
-        torch_in = _is_torch_cuda(configurations)
-        shape = tuple(configurations.shape) if torch_in else None
-        if not torch_in:
-            q = _f32(configurations)
-            shape = q.shape
-        if len(shape) != 2 or shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = shape[0]
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(configurations.device):
-                h = None if environment is None else environment.handle()
-                qt = configurations.contiguous().float()
-                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
-                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
-                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
-                check(lib.vmv_clearance_batch(self._id, h, ctypes.c_void_p(qt.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
-                                              ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
-                      "vmv_clearance_batch")
-                return (out, wit) if witness else out
-        h = None if environment is None else environment.handle()
-        out = np.zeros((n, 2), np.float32)
-        wit = np.zeros((n, 4), np.uint32) if witness else None
-        check(lib.vmv_clearance_batch_host(self._id, h, _fp(q), n, _fp(out),
-                                           wit.ctypes.data_as(_lib.c_u32_p) if witness else None), "vmv_clearance_batch_host")
+        out, wit = self._batched("vmv_clearance_batch", [configurations], [((2,), "f32", True), ((4,), "u32", witness)],
+                                 environment, nullable=True)
         return (out, wit) if witness else out
 
     def clearance_batch_multi(self, configurations, environments, counts, witness: bool = False):
         """clearance_batch for configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the
         empty environment: env = +inf), in one call and one launch.  Bit for bit one clearance_batch per environment,
         concatenated.  numpy in -> numpy out; a torch CUDA tensor in -> torch CUDA tensors out, as clearance_batch."""
-        environments, offsets = _segments(environments, counts)
-        torch_in = _is_torch_cuda(configurations)
-        if torch_in:
-            shape = tuple(configurations.shape)
-        else:
-            q = _f32(configurations)
-            shape = q.shape
-        if len(shape) != 2 or shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = shape[0]
-        if int(offsets[-1]) != n:
-            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(configurations.device):
-                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-                qt = configurations.contiguous().float()
-                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
-                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
-                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
-                check(lib.vmv_clearance_batch_multi(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
-                                                    ctypes.c_void_p(qt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                    ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
-                      "vmv_clearance_batch_multi")
-                return (out, wit) if witness else out
-        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-        out = np.zeros((n, 2), np.float32)
-        wit = np.zeros((n, 4), np.uint32) if witness else None
-        check(lib.vmv_clearance_batch_multi_host(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs), _fp(q),
-                                                 _fp(out), wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
-              "vmv_clearance_batch_multi_host")
+        out, wit = self._batched("vmv_clearance_batch_multi", [configurations], [((2,), "f32", True), ((4,), "u32", witness)],
+                                 environments=environments, counts=counts)
         return (out, wit) if witness else out
 
     def clearance_grad(self, configuration, environment: Environment | None = None):
@@ -794,81 +801,18 @@ class _Robot(types.ModuleType):
         environment; a robot without self pairs), and for a sphere centre inside a cuboid, where the value is flat; NaN
         for a configuration with a non-finite joint.  witness=True appends clearance_batch's witness.  Shapes, types,
         refused environments and the numpy / torch convention are clearance_batch's."""
-        if environment is not None and not isinstance(environment, Environment):
-            raise TypeError(f"expected Environment or None, got {type(environment).__name__}")
-        torch_in = _is_torch_cuda(configurations)
-        shape = tuple(configurations.shape) if torch_in else None
-        if not torch_in:
-            q = _f32(configurations)
-            shape = q.shape
-        if len(shape) != 2 or shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = shape[0]
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(configurations.device):
-                h = None if environment is None else environment.handle()
-                qt = configurations.contiguous().float()
-                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
-                grad = torch.empty((n, 2, self._dim), dtype=torch.float32, device=qt.device)
-                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
-                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
-                check(lib.vmv_clearance_grad_batch(self._id, h, ctypes.c_void_p(qt.data_ptr()), n,
-                                                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
-                                                   ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
-                      "vmv_clearance_grad_batch")
-                return (out, grad, wit) if witness else (out, grad)
-        h = None if environment is None else environment.handle()
-        out = np.zeros((n, 2), np.float32)
-        grad = np.zeros((n, 2, self._dim), np.float32)
-        wit = np.zeros((n, 4), np.uint32) if witness else None
-        check(lib.vmv_clearance_grad_batch_host(self._id, h, _fp(q), n, _fp(out), _fp(grad),
-                                                wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
-              "vmv_clearance_grad_batch_host")
-        return (out, grad, wit) if witness else (out, grad)
+        out = self._batched("vmv_clearance_grad_batch", [configurations],
+                            [((2,), "f32", True), ((2, self._dim), "f32", True), ((4,), "u32", witness)], environment, nullable=True)
+        return tuple(out) if witness else tuple(out[:2])
 
     def clearance_grad_batch_multi(self, configurations, environments, counts, witness: bool = False):
         """clearance_grad_batch for configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None =
         the empty environment), in one call: one clearance launch and one gradient launch.  Bit for bit one
         clearance_grad_batch per environment, concatenated."""
-        environments, offsets = _segments(environments, counts)
-        torch_in = _is_torch_cuda(configurations)
-        if torch_in:
-            shape = tuple(configurations.shape)
-        else:
-            q = _f32(configurations)
-            shape = q.shape
-        if len(shape) != 2 or shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = shape[0]
-        if int(offsets[-1]) != n:
-            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(configurations.device):
-                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-                qt = configurations.contiguous().float()
-                out = torch.empty((n, 2), dtype=torch.float32, device=qt.device)
-                grad = torch.empty((n, 2, self._dim), dtype=torch.float32, device=qt.device)
-                wit = torch.empty((n, 4), dtype=torch.int32, device=qt.device) if witness else None
-                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
-                check(lib.vmv_clearance_grad_batch_multi(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
-                                                         ctypes.c_void_p(qt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                         ctypes.c_void_p(grad.data_ptr()),
-                                                         ctypes.c_void_p(wit.data_ptr()) if witness else None, stream),
-                      "vmv_clearance_grad_batch_multi")
-                return (out, grad, wit) if witness else (out, grad)
-        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-        out = np.zeros((n, 2), np.float32)
-        grad = np.zeros((n, 2, self._dim), np.float32)
-        wit = np.zeros((n, 4), np.uint32) if witness else None
-        check(lib.vmv_clearance_grad_batch_multi_host(self._id, handles, offsets.ctypes.data_as(_lib.c_size_p), len(envs),
-                                                      _fp(q), _fp(out), _fp(grad),
-                                                      wit.ctypes.data_as(_lib.c_u32_p) if witness else None),
-              "vmv_clearance_grad_batch_multi_host")
-        return (out, grad, wit) if witness else (out, grad)
+        out = self._batched("vmv_clearance_grad_batch_multi", [configurations],
+                            [((2,), "f32", True), ((2, self._dim), "f32", True), ((4,), "u32", witness)],
+                            environments=environments, counts=counts)
+        return tuple(out) if witness else tuple(out[:2])
 
     def prepare(self, environments):
         """Builds what each environment holds for this robot (broad-phase grids, reach certificates, static links) for
@@ -1388,94 +1332,23 @@ class _Robot(types.ModuleType):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty
         environment), in one call.  The same answers as one validate_batch per environment, concatenated.  numpy in ->
         numpy out; torch CUDA tensor in -> torch.bool CUDA tensor out, launched on torch's current stream."""
-        environments, offsets = _segments(environments, counts)
-        torch_in = _is_torch_cuda(configurations)
-        if torch_in:
-            shape = tuple(configurations.shape)
-        else:
-            q = _f32(configurations)
-            shape = q.shape
-        if len(shape) != 2 or shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        n = shape[0]
-        if int(offsets[-1]) != n:
-            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} configurations")
-        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-        offs = offsets.ctypes.data_as(_lib.c_size_p)
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(configurations.device):
-                qt = configurations.contiguous().float()
-                bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=qt.device)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(qt.device).cuda_stream)
-                check(lib.vmv_validate_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(qt.data_ptr()),
-                                                   ctypes.c_void_p(bits.data_ptr()), stream), "vmv_validate_batch_multi")
-                return _torch_unpack_bits(bits, n)
-        bits = np.zeros((n + 63) // 64, np.uint64)
-        check(lib.vmv_validate_batch_multi_host(self._id, handles, offs, len(envs), _fp(q),
-                                                bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_batch_multi_host")
-        return unpack_bits(bits, n)
+        return self._batched("vmv_validate_batch_multi", [configurations], [((), "bits", True)],
+                             environments=environments, counts=counts)[0]
 
     def validate_motion_batch_multi(self, starts, goals, environments, counts):
         """bool[n]: edges starts[i] -> goals[i], [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None =
         the empty environment), in one call.  The same answers as one validate_motion_batch per environment,
         concatenated.  numpy in -> numpy out; torch CUDA tensors in -> torch.bool CUDA tensor out, launched on torch's
         current stream."""
-        environments, offsets = _segments(environments, counts)
-        torch_in = _is_torch_cuda(starts)
-        if torch_in:
-            if not _is_torch_cuda(goals):
-                raise TypeError("starts is a torch CUDA tensor, goals is not")
-            sa, sb = tuple(starts.shape), tuple(goals.shape)
-        else:
-            a, b = _f32(starts), _f32(goals)
-            sa, sb = a.shape, b.shape
-        if len(sa) != 2 or sa[1] != self._dim or sa != sb:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = sa[0]
-        if int(offsets[-1]) != n:
-            raise ValueError(f"counts sum to {int(offsets[-1])}, but there are {n} edges")
-        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-        offs = offsets.ctypes.data_as(_lib.c_size_p)
-        if torch_in:
-            import torch
-
-            with torch.cuda.device(starts.device):
-                at = starts.contiguous().float()
-                bt = goals.to(at.device).contiguous().float()
-                bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=at.device)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(at.device).cuda_stream)
-                check(lib.vmv_validate_motion_batch_multi(self._id, handles, offs, len(envs), ctypes.c_void_p(at.data_ptr()),
-                                                          ctypes.c_void_p(bt.data_ptr()), ctypes.c_void_p(bits.data_ptr()),
-                                                          stream), "vmv_validate_motion_batch_multi")
-                return _torch_unpack_bits(bits, n)
-        bits = np.zeros((n + 63) // 64, np.uint64)
-        check(lib.vmv_validate_motion_batch_multi_host(self._id, handles, offs, len(envs), _fp(a), _fp(b),
-                                                       bits.ctypes.data_as(_lib.c_u64_p)),
-              "vmv_validate_motion_batch_multi_host")
-        return unpack_bits(bits, n)
+        return self._batched("vmv_validate_motion_batch_multi", [starts, goals], [((), "bits", True)],
+                             environments=environments, counts=counts)[0]
 
     def validate_motion_batch(self, starts, goals, environment: Environment | None = None):
-        if _is_torch_cuda(starts):
-            return self._torch_bits(starts, goals, environment)
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        bits = np.zeros((n + 63) // 64, np.uint64)
-        check(lib.vmv_validate_motion_batch_host(self._id, self._env(environment), _fp(a), _fp(b), n,
-                                                 bits.ctypes.data_as(_lib.c_u64_p)), "vmv_validate_motion_batch_host")
-        return unpack_bits(bits, n)
+        return self._batched("vmv_validate_motion_batch", [starts, goals], [((), "bits", True)], environment)[0]
 
     def fk_batch(self, configurations):
         """float32 [n][n_spheres][4] = x y z r."""
-        q = _f32(configurations)
-        if q.ndim != 2 or q.shape[1] != self._dim:
-            raise TypeError(f"expected [n][{self._dim}] configurations")
-        out = np.zeros((q.shape[0], self._ns, 4), np.float32)
-        check(lib.vmv_fk_batch_host(self._id, _fp(q), q.shape[0], _fp(out)), "vmv_fk_batch_host")
-        return out
+        return self._batched("vmv_fk_batch", [configurations], [((self._ns, 4), "f32", True)])[0]
 
     def halton_device(self, n: int, skip: int = 0):
         """Samples skip+1 .. skip+n of the reference's Halton sequence (random/halton.hh), generated on the GPU.
@@ -1507,16 +1380,6 @@ class _Robot(types.ModuleType):
             check(lib.vmv_validate_motion_batch(self._id, env, ctypes.c_void_p(q.data_ptr()),
                                                 ctypes.c_void_p(goals.data_ptr()), n, ctypes.c_void_p(bits.data_ptr()),
                                                 stream), "vmv_validate_motion_batch")
-
-    def _torch_bits(self, a, b, environment):
-        import torch
-
-        with torch.cuda.device(a.device):
-            a = a.contiguous().float()
-            n = a.shape[0]
-            bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=a.device)
-            self.validate_bits_device(a, environment, bits, None if b is None else b.contiguous().float())
-            return _torch_unpack_bits(bits, n)
 
 
 _EMPTY_ENVIRONMENT = Environment()

@@ -1265,9 +1265,6 @@ namespace
         return VMV_OK;
     }
 
-    // the checks of vmv_validate_batch_multi(_host) and vmv_validate_motion_batch_multi(_host) that need no device, in the
-    // header's order; q and q2 are the input arrays (the configurations twice, or the starts and the goals);
-    // *n = offsets[n_envs]
     // vmv_clearance_batch*: the kinds a clearance is not defined for (include/vamp_mvt_amd.h), read from the host
     // builder, so the refusal needs neither a device nor a finalized environment; `who` names the argument
     int clearance_kinds(const vmv_env *env, const std::string &who)
@@ -1280,40 +1277,298 @@ namespace
         return VMV_ERR_INVALID_ARGUMENT;
     }
 
-    // (clearance: the vmv_clearance_batch_multi(_host) form - also refuses the kinds of clearance_kinds, by index)
-    int multi_args(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const void *q,
-                   const void *q2, const void *bits, size_t *n, bool clearance = false)
+    int refuse(int status, const std::string &message)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        std::string err;
-        if (!envs || !offsets || !q || !q2 || !bits)
-            err = "null pointer";
-        else if (n_envs >= vmv::kMultiMaxConfigs)
-            err = "n_envs must be below 2^31";
-        else if (offsets[0] != 0)
-            err = "offsets[0] must be 0";
-        else if (offsets[n_envs] >= vmv::kMultiMaxConfigs)
-            err = "offsets[n_envs] (the batch size) must be below 2^31";
-        for (size_t k = 0; err.empty() && k < n_envs; ++k)
-            if (offsets[k + 1] < offsets[k])
-                err = "offsets must be non-decreasing (offsets[" + std::to_string(k + 1) + "] < offsets[" + std::to_string(k) + "])";
+        g_last_error = message;
+        return status;
+    }
+
+    // What a prologue hands its entry point: `run` = launch; else return `rc` (an error, or VMV_OK: an empty batch).
+    struct EnvCall
+    {
+        int rc = VMV_OK;
+        bool run = false;
+        const vmv::EnvLaunch *launch = nullptr;  // nullptr: no environment
+    };
+    enum CallKind
+    {
+        kInspect,  // reads the robot's part of the environment: no batch, any current device
+        kDevice,   // device arrays in, launched on the caller's stream
+        kHost      // host arrays in: asks for a device at all before the environment's is compared
+    };
+
+    // The single-environment prologue, in this order: robot, NULL pointers (`pointers`: the entry point's own arrays are
+    // all there; a NULL `env` unless `optional`), finalized, n == 0, [kHost: a device at all,] the environment's device,
+    // the robot's part of the environment.  `clearance`: the clearance calls' messages, and clearance_kinds before the
+    // finalized check.
+    EnvCall env_call(int robot, const vmv_env *env, bool optional, bool pointers, size_t n, CallKind kind, bool clearance = false)
+    {
+        if (!robot_ok(robot)) return {VMV_ERR_UNKNOWN_ROBOT};
+        if (!pointers || (!env && !optional)) return {clearance ? refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer") : VMV_ERR_INVALID_ARGUMENT};
+        if (env && clearance)
+            if (int rc = clearance_kinds(env, "the environment"); rc != VMV_OK) return {rc};
+        if (env && !env->finalized)
+            return {clearance ? refuse(VMV_ERR_NOT_FINALIZED, "the environment is not finalized") : VMV_ERR_NOT_FINALIZED};
+        if (n == 0) return {VMV_OK};
+        if (kind == kHost)
+            if (int rc = require_device(); rc != VMV_OK) return {rc};
+        if (env && kind != kInspect)
+            if (int rc = check_device(env); rc != VMV_OK) return {rc};
+        if (env)
+            if (int rc = ensure_robot(env, robot); rc != VMV_OK) return {rc};
+        return {VMV_OK, true, env ? &env->launch[robot] : nullptr};
+    }
+
+    // per handle of a multi-environment call: NULL (and, given `offsets`, that they do not decrease), then for all of
+    // them the kinds a clearance refuses, then finalized; each names the index
+    int env_handles(const vmv_env *const *envs, size_t n_envs, const size_t *offsets, bool clearance)
+    {
+        for (size_t k = 0; k < n_envs; ++k)
+            if (offsets && offsets[k + 1] < offsets[k])
+                return refuse(VMV_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing (offsets[" + std::to_string(k + 1) +
+                                                            "] < offsets[" + std::to_string(k) + "])");
             else if (!envs[k])
-                err = "envs[" + std::to_string(k) + "] is NULL";
-        if (!err.empty())
-        {
-            g_last_error = err;
-            return VMV_ERR_INVALID_ARGUMENT;
-        }
+                return refuse(VMV_ERR_INVALID_ARGUMENT, "envs[" + std::to_string(k) + "] is NULL");
         for (size_t k = 0; clearance && k < n_envs; ++k)
             if (int rc = clearance_kinds(envs[k], "envs[" + std::to_string(k) + "]"); rc != VMV_OK) return rc;
         for (size_t k = 0; k < n_envs; ++k)
-            if (!envs[k]->finalized)
-            {
-                g_last_error = "envs[" + std::to_string(k) + "] is not finalized";
-                return VMV_ERR_NOT_FINALIZED;
-            }
-        *n = offsets[n_envs];
+            if (!envs[k]->finalized) return refuse(VMV_ERR_NOT_FINALIZED, "envs[" + std::to_string(k) + "] is not finalized");
         return VMV_OK;
+    }
+
+    // every environment on the current device, then the robot's parts of all of them (once per environment and robot)
+    int prepare_parts(int robot, const vmv_env *const *envs, size_t n_envs)
+    {
+        for (size_t k = 0; k < n_envs; ++k)
+            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
+        return build_robot_parts(envs, n_envs, robot);
+    }
+
+    struct MultiCall
+    {
+        int rc = VMV_OK;
+        bool run = false;
+        size_t n = 0;  // offsets[n_envs]
+        std::vector<const vmv::EnvLaunch *> launch;
+    };
+
+    // The multi-environment prologue: robot, NULL arrays (q, q2: the inputs; out: the required output), the offsets,
+    // env_handles, an empty batch; then the environments' device, the robot's parts and the launch vector - or, for a
+    // `host` form, a device at all (it runs the device form once its arrays are up).
+    MultiCall multi_call(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const void *q,
+                         const void *q2, const void *out, bool host, bool clearance = false)
+    {
+        MultiCall c;
+        if (!robot_ok(robot)) return c.rc = VMV_ERR_UNKNOWN_ROBOT, c;
+        const char *err = (!envs || !offsets || !q || !q2 || !out) ? "null pointer" :
+                          n_envs >= vmv::kMultiMaxConfigs ? "n_envs must be below 2^31" :
+                          offsets[0] != 0 ? "offsets[0] must be 0" :
+                          offsets[n_envs] >= vmv::kMultiMaxConfigs ? "offsets[n_envs] (the batch size) must be below 2^31" : nullptr;
+        c.rc = err ? refuse(VMV_ERR_INVALID_ARGUMENT, err) : env_handles(envs, n_envs, offsets, clearance);
+        if (c.rc != VMV_OK || (c.n = offsets[n_envs]) == 0) return c;
+        if ((c.rc = host ? require_device() : prepare_parts(robot, envs, n_envs)) != VMV_OK) return c;
+        for (size_t k = 0; !host && k < n_envs; ++k) c.launch.push_back(&envs[k]->launch[robot]);
+        c.run = true;
+        return c;
+    }
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------
+// device memory of the host-buffer entry points, and the gradient calls' witness scratch
+// ---------------------------------------------------------------------------------------------------------
+namespace
+{
+    // Device staging of the *_host entry points: one grow-only arena per thread, so that a planner's many small calls
+    // (one configuration, a handful of edges) do not pay hipMalloc / hipFree pairs each.  Never freed from a
+    // destructor: a thread_local of the main thread is destroyed during static destruction, possibly after the HIP
+    // runtime is gone (the memory goes back with the process).  Long-lived callers release it with
+    // vmv_release_staging(); a request above kStagingKeepBytes is not kept beyond its call, so one huge batch does not
+    // pin its memory for the thread's life.
+    constexpr size_t kStagingKeepBytes = size_t{64} << 20;
+    struct StagingArena
+    {
+        void *base = nullptr;
+        size_t capacity = 0;
+        int device = -1;
+        void release()
+        {
+            if (base) (void) hipFree(base);
+            base = nullptr;
+            capacity = 0;
+        }
+        void *get(size_t bytes)
+        {
+            int dev = -1;
+            if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+            if (base && (dev != device || bytes > capacity)) release();
+            if (!base)
+            {
+                const size_t want = std::max<size_t>(bytes, 1u << 16);
+                if (hipMalloc(&base, want) != hipSuccess)
+                {
+                    base = nullptr;
+                    return nullptr;
+                }
+                capacity = want;
+                device = dev;
+            }
+            return base;
+        }
+        void trim()
+        {
+            if (capacity > kStagingKeepBytes) release();
+        }
+    };
+    thread_local StagingArena g_staging;
+
+    // One host round trip through the arena.  The caller declares its device regions: in() is uploaded from host
+    // memory, out() is downloaded once the call has returned VMV_OK (dst NULL: a plain temporary; `room`: laid out,
+    // and with `zero` cleared, at least this large).  run() lays them out at 256-byte alignment in one arena request,
+    // uploads, runs `call` - which reads the device pointers with at() and launches on the null stream, so that the
+    // synchronous copies order with it - downloads, and trims the arena on every path.  A region without bytes is NULL.
+    struct Staged
+    {
+        struct Region
+        {
+            const void *src;
+            void *dst;
+            size_t bytes, room;
+            bool zero;
+            void *ptr;
+        };
+        Region regions[4];
+        int count = 0;
+        int add(const void *src, void *dst, size_t bytes, size_t room, bool zero)
+        {
+            regions[count] = {src, dst, bytes, std::max(bytes, room), zero, nullptr};
+            return count++;
+        }
+        int in(const void *src, size_t bytes) { return add(src, nullptr, bytes, 0, false); }
+        int out(void *dst, size_t bytes, size_t room = 0, bool zero = false) { return add(nullptr, dst, bytes, room, zero); }
+        template <typename T>
+        T *at(int region) const
+        {
+            return static_cast<T *>(regions[region].ptr);
+        }
+        template <typename F>
+        int run(F &&call)
+        {
+            const auto padded = [](const Region &r) { return (r.room + 255) & ~size_t{255}; };
+            size_t total = 0;
+            for (int i = 0; i < count; ++i) total += padded(regions[i]);
+            char *p = static_cast<char *>(g_staging.get(total));
+            if (!p) return hip_fail(hipErrorOutOfMemory, "staging arena");
+            bool ok = true;
+            for (int i = 0; i < count && ok; ++i)
+            {
+                Region &r = regions[i];
+                r.ptr = r.room ? p : nullptr;
+                p += padded(r);
+                if (r.src && r.bytes) ok = hipMemcpy(r.ptr, r.src, r.bytes, hipMemcpyHostToDevice) == hipSuccess;
+                if (r.zero && r.room) ok = ok && hipMemset(r.ptr, 0, r.room) == hipSuccess;
+            }
+            int rc = ok ? call() : VMV_ERR_HIP;
+            for (int i = 0; i < count && rc == VMV_OK; ++i)
+                if (const Region &r = regions[i]; r.dst && r.bytes && hipMemcpy(r.dst, r.ptr, r.bytes, hipMemcpyDeviceToHost) != hipSuccess)
+                    rc = VMV_ERR_HIP;
+            g_staging.trim();
+            return rc;
+        }
+    };
+
+    size_t config_bytes(int robot, size_t n) { return n * (size_t) kRobots[robot].dimension * sizeof(float); }
+
+    // The gradient kernel reads the witness the clearance kernel wrote.  A caller without a witness buffer is lent scratch
+    // per (device, stream): calls on one stream run in order, so they share it; grow-only, a larger request frees the old
+    // buffer (hipFree waits for the calls still using it).  The lease holds the pool's lock until the call is enqueued.
+    struct WitnessScratch
+    {
+        void *p = nullptr;
+        size_t bytes = 0;
+    };
+    std::mutex g_witness_mutex;
+    std::map<std::pair<int, hipStream_t>, WitnessScratch> g_witness;  // never freed at exit (see vmv_release_staging)
+    struct WitnessLease
+    {
+        std::unique_lock<std::mutex> lock{g_witness_mutex, std::defer_lock};
+        int acquire(hipStream_t stream, size_t n, uint32_t **out)
+        {
+            int dev = -1;
+            VMV_HIP(hipGetDevice(&dev));
+            lock.lock();
+            WitnessScratch &w = g_witness[{dev, stream}];
+            if (w.bytes < n * 16)
+            {
+                if (w.p) (void) hipFree(w.p);
+                w.p = nullptr, w.bytes = 0;
+                const size_t want = std::max<size_t>(n * 16, size_t{1} << 16);
+                VMV_HIP(hipMalloc(&w.p, want));
+                w.bytes = want;
+            }
+            *out = static_cast<uint32_t *>(w.p);
+            return VMV_OK;
+        }
+    };
+    void release_witness_scratch()
+    {
+        std::lock_guard<std::mutex> g(g_witness_mutex);
+        for (auto &kv : g_witness)
+            if (kv.second.p) (void) hipFree(kv.second.p);
+        g_witness.clear();
+    }
+    // the round trip of the four clearance host forms: [configurations | clearances | gradients | witness]; grad NULL: the values
+    // alone, and a witness only where the caller wants one; launch(d_q, d_clearance, d_grad, d_witness)
+    template <typename F>
+    int clearance_staged(int robot, const float *q, size_t n, float *clearance, float *grad, uint32_t *witness, F &&launch)
+    {
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), dc = s.out(clearance, n * 8), dg = s.out(grad, grad ? 2 * config_bytes(robot, n) : 0),
+                  dw = s.out(witness, grad || witness ? n * 16 : 0);
+        return s.run([&] { return launch(s.at<float>(dq), s.at<float>(dc), s.at<float>(dg), s.at<uint32_t>(dw)); });
+    }
+
+    // launch(the caller's witness buffer, or one lent until the call is enqueued)
+    template <typename F>
+    int with_witness(uint32_t *d_witness, size_t n, void *stream, F &&launch)
+    {
+        WitnessLease lease;
+        if (!d_witness)
+            if (int rc = lease.acquire(static_cast<hipStream_t>(stream), n, &d_witness); rc != VMV_OK) return rc;
+        return launch(d_witness);
+    }
+
+    // free spheres (and, given robot_spheres, one configuration's) against the environment: vmv::spheres_env_kernel
+    int launch_spheres(const vmv_env *env, const float *d_spheres, size_t n, uint8_t *d_hits, const float *d_robot_spheres,
+                       int n_robot, void *stream)
+    {
+        const size_t blocks = (n + vmv::kBlock - 1) / vmv::kBlock;
+        hipLaunchKernelGGL(vmv::spheres_env_kernel, dim3((unsigned) std::min<size_t>(blocks, 4096)), dim3(vmv::kBlock),
+                           (env->base.n_floats + vmv::kCaptFlagWords) * sizeof(float), static_cast<hipStream_t>(stream), env->launch[0].d_env,
+                           reinterpret_cast<const float4 *>(d_spheres), n, d_hits, reinterpret_cast<const float4 *>(d_robot_spheres), n_robot);
+        VMV_HIP(hipGetLastError());
+        return VMV_OK;
+    }
+
+    // bench / sampling input generators: uploads the robot's bounds, launches `kernel` on the stream, waits for it
+    using ConfigKernel = void (*)(float *, size_t, int, uint64_t, const float *, const float *);
+    int generate_configs(int robot, ConfigKernel kernel, uint64_t seed_or_skip, float *d_q, size_t n, void *stream)
+    {
+        const int dim = kRobots[robot].dimension;
+        float *d_bounds = nullptr;
+        VMV_HIP(hipMalloc((void **) &d_bounds, 32 * sizeof(float)));
+        const int rc = [&]() -> int
+        {
+            VMV_HIP(hipMemcpy(d_bounds, kRobots[robot].lower, 16 * sizeof(float), hipMemcpyHostToDevice));
+            VMV_HIP(hipMemcpy(d_bounds + 16, kRobots[robot].span, 16 * sizeof(float), hipMemcpyHostToDevice));
+            const size_t total = n * (size_t) dim;
+            hipLaunchKernelGGL(kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_q,
+                               total, dim, seed_or_skip, d_bounds, d_bounds + 16);
+            VMV_HIP(hipGetLastError());
+            VMV_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+            return VMV_OK;
+        }();
+        (void) hipFree(d_bounds);
+        return rc;
     }
 }  // namespace
 
@@ -1322,26 +1577,19 @@ namespace
 // ---------------------------------------------------------------------------------------------------------
 extern "C"
 {
+    static int validate_parts(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream, int parts)
+    {
+        const EnvCall c = env_call(robot, env, false, d_q && d_bits, n, kDevice);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->validate(*c.launch, d_q, n, d_bits, static_cast<hipStream_t>(stream), parts);
+    }
     int vmv_validate_batch(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !d_q || !d_bits) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (n == 0) return VMV_OK;
-        if (int rc = check_device(env); rc != VMV_OK) return rc;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        return kLaunchers[robot]->validate(env->launch[robot], d_q, n, d_bits, static_cast<hipStream_t>(stream), 7);
+        return validate_parts(robot, env, d_q, n, d_bits, stream, 7);
     }
-
     int vmv_validate_batch_env(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !d_q || !d_bits) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (n == 0) return VMV_OK;
-        if (int rc = check_device(env); rc != VMV_OK) return rc;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        return kLaunchers[robot]->validate(env->launch[robot], d_q, n, d_bits, static_cast<hipStream_t>(stream), 1);
+        return validate_parts(robot, env, d_q, n, d_bits, stream, 1);
     }
 
     int vmv_validate_batch_self(int robot, const float *d_q, size_t n, uint64_t *d_bits, void *stream)
@@ -1355,41 +1603,25 @@ extern "C"
     int vmv_validate_motion_batch(int robot, const vmv_env *env, const float *d_a, const float *d_b, size_t n,
                                   uint64_t *d_bits, void *stream)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !d_a || !d_b || !d_bits) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (n == 0) return VMV_OK;
-        if (int rc = check_device(env); rc != VMV_OK) return rc;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        return kLaunchers[robot]->validate_motion(env->launch[robot], d_a, d_b, n, d_bits, static_cast<hipStream_t>(stream));
+        const EnvCall c = env_call(robot, env, false, d_a && d_b && d_bits, n, kDevice);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->validate_motion(*c.launch, d_a, d_b, n, d_bits, static_cast<hipStream_t>(stream));
     }
 
     int vmv_validate_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                  const float *d_q, uint64_t *d_bits, void *stream)
     {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_q, d_bits, &n); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        for (size_t k = 0; k < n_envs; ++k)
-            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
-        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-        std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
-        return kLaunchers[robot]->validate_multi(launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_q, d_q, d_bits, false);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->validate_multi(c.launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
     }
 
     int vmv_validate_motion_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                         const float *d_start, const float *d_goal, uint64_t *d_bits, void *stream)
     {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, d_start, d_goal, d_bits, &n); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        for (size_t k = 0; k < n_envs; ++k)
-            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
-        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-        std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
-        return kLaunchers[robot]->validate_motion_multi(launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_start, d_goal, d_bits, false);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->validate_motion_multi(c.launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
                                                         static_cast<hipStream_t>(stream));
     }
 
@@ -1397,36 +1629,17 @@ extern "C"
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (n_envs == 0) return VMV_OK;
-        if (!envs)
-        {
-            g_last_error = "null pointer";
-            return VMV_ERR_INVALID_ARGUMENT;
-        }
-        for (size_t k = 0; k < n_envs; ++k)
-            if (!envs[k])
-            {
-                g_last_error = "envs[" + std::to_string(k) + "] is NULL";
-                return VMV_ERR_INVALID_ARGUMENT;
-            }
-        for (size_t k = 0; k < n_envs; ++k)
-            if (!envs[k]->finalized)
-            {
-                g_last_error = "envs[" + std::to_string(k) + "] is not finalized";
-                return VMV_ERR_NOT_FINALIZED;
-            }
-        for (size_t k = 0; k < n_envs; ++k)
-            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
-        return build_robot_parts(envs, n_envs, robot);
+        if (!envs) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = env_handles(envs, n_envs, nullptr, false); rc != VMV_OK) return rc;
+        return prepare_parts(robot, envs, n_envs);
     }
 
     int vmv_env_grid_info(const vmv_env *env, int robot, int grid_class, uint32_t *dims3, float *origin3, float *inv_cell,
                           uint32_t *words)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || grid_class < 0 || grid_class >= vmv::kGridClasses) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        const vmv::EnvDev &D = env->launch[robot].host;
+        const EnvCall c = env_call(robot, env, false, grid_class >= 0 && grid_class < vmv::kGridClasses, 1, kInspect);
+        if (!c.run) return c.rc;
+        const vmv::EnvDev &D = c.launch->host;
         const vmv::GridDev &g = D.grid[grid_class];
         const bool has = g.cells != nullptr;
         for (int k = 0; k < 3; ++k)
@@ -1440,11 +1653,9 @@ extern "C"
     }
     int vmv_env_grid_cells(const vmv_env *env, int robot, int grid_class, uint32_t *out, size_t capacity, size_t *n)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !n || grid_class < 0 || grid_class >= vmv::kGridClasses) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        const vmv::EnvDev &D = env->launch[robot].host;
+        const EnvCall c = env_call(robot, env, false, n && grid_class >= 0 && grid_class < vmv::kGridClasses, 1, kInspect);
+        if (!c.run) return c.rc;
+        const vmv::EnvDev &D = c.launch->host;
         const vmv::GridDev &g = D.grid[grid_class];
         *n = g.cells ? (size_t) g.dims[0] * g.dims[1] * g.dims[2] * D.grid_words : 0;
         const size_t m = std::min(capacity, *n);
@@ -1453,22 +1664,12 @@ extern "C"
     }
     int vmv_env_robot_flags(const vmv_env *env, int robot, uint64_t *link_skip, uint32_t *static_hit)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        if (link_skip) *link_skip = env->launch[robot].host.link_skip;
+        const EnvCall c = env_call(robot, env, false, true, 1, kInspect);
+        if (!c.run) return c.rc;
+        if (link_skip) *link_skip = c.launch->host.link_skip;
         if (static_hit)  // (the kernel's answer lives in the device image only)
-            VMV_HIP(hipMemcpy(static_hit, &env->launch[robot].d_env->static_hit, sizeof(uint32_t), hipMemcpyDeviceToHost));
+            VMV_HIP(hipMemcpy(static_hit, &c.launch->d_env->static_hit, sizeof(uint32_t), hipMemcpyDeviceToHost));
         return VMV_OK;
-    }
-
-    int vmv_fk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
-    {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!d_q || !d_out) return VMV_ERR_INVALID_ARGUMENT;
-        if (n == 0) return VMV_OK;
-        return kLaunchers[robot]->fk(d_q, n, d_out, static_cast<hipStream_t>(stream));
     }
 
     int vmv_robot_self_pairs(int robot, size_t *n_pairs, uint16_t *pairs2)
@@ -1493,36 +1694,14 @@ extern "C"
         }
         return VMV_OK;
     }
-    int vmv_contacts_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint32_t *env_words,
-                                uint32_t *pair_words)
+
+    int vmv_fk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !q || !env_words || !pair_words) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
+        if (!d_q || !d_out) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        if ((rc = check_device(env)) != VMV_OK) return rc;
-        if ((rc = ensure_robot(env, robot)) != VMV_OK) return rc;
-        const size_t ns = (size_t) kRobots[robot].n_spheres, npw = ((size_t) kLaunchers[robot]->n_self_pairs + 31) / 32;
-        const size_t qb = n * (size_t) kRobots[robot].dimension * 4, sb = n * ns * 16, eb = n * ns * (vmv::kReportWords + 1) * 4,
-                     pb = std::max<size_t>(n * npw * 4, 4);
-        char *d = nullptr;
-        VMV_HIP(hipMalloc((void **) &d, qb + sb + eb + pb + 1024));
-        float *dq = reinterpret_cast<float *>(d), *ds = reinterpret_cast<float *>(d + ((qb + 255) & ~size_t{255}));
-        uint32_t *de = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ds) + ((sb + 255) & ~size_t{255}));
-        uint32_t *dp = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(de) + ((eb + 255) & ~size_t{255}));
-        rc = VMV_OK;
-        if (hipMemcpy(dq, q, qb, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dp, 0, pb) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK) rc = kLaunchers[robot]->fk(dq, n, ds, nullptr);
-        if (rc == VMV_OK) rc = kLaunchers[robot]->contacts(env->launch[robot], ds, n, de, dp, nullptr);
-        if (rc == VMV_OK && (hipMemcpy(env_words, de, eb, hipMemcpyDeviceToHost) != hipSuccess ||
-                             (npw && hipMemcpy(pair_words, dp, n * npw * 4, hipMemcpyDeviceToHost) != hipSuccess)))
-            rc = VMV_ERR_HIP;
-        (void) hipFree(d);
-        return rc;
+        return kLaunchers[robot]->fk(d_q, n, d_out, static_cast<hipStream_t>(stream));
     }
-
     int vmv_eefk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
@@ -1530,127 +1709,84 @@ extern "C"
         if (n == 0) return VMV_OK;
         return kLaunchers[robot]->eefk(d_q, n, d_out, static_cast<hipStream_t>(stream));
     }
-    int vmv_eefk_batch_host(int robot, const float *q, size_t n, float *out)
-    {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!q || !out) return VMV_ERR_INVALID_ARGUMENT;
-        if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        const size_t qb = n * (size_t) kRobots[robot].dimension * 4, ob = n * 64;
-        float *dq = nullptr, *dout = nullptr;
-        VMV_HIP(hipMalloc((void **) &dq, qb));
-        if (hipMalloc((void **) &dout, ob) != hipSuccess)
-        {
-            (void) hipFree(dq);
-            return VMV_ERR_HIP;
-        }
-        rc = VMV_OK;
-        if (hipMemcpy(dq, q, qb, hipMemcpyHostToDevice) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK) rc = vmv_eefk_batch(robot, dq, n, dout, nullptr);
-        if (rc == VMV_OK && hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        (void) hipFree(dq);
-        (void) hipFree(dout);
-        return rc;
-    }
 
-    // ---- host-buffer variants ----
+    // ---- host-buffer variants: their own arrays and a device are checked here, the rest by the device form they run ----
     int vmv_fk_batch_host(int robot, const float *q, size_t n, float *out)
     {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!q || !out) return VMV_ERR_INVALID_ARGUMENT;
-        if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        const size_t qb = n * (size_t) kRobots[robot].dimension * 4, ob = n * (size_t) kRobots[robot].n_spheres * 16;
-        float *dq = nullptr, *dout = nullptr;
-        VMV_HIP(hipMalloc((void **) &dq, qb));
-        if (hipMalloc((void **) &dout, ob) != hipSuccess)
-        {
-            (void) hipFree(dq);
-            return VMV_ERR_HIP;
-        }
-        rc = VMV_OK;
-        if (hipMemcpy(dq, q, qb, hipMemcpyHostToDevice) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK) rc = vmv_fk_batch(robot, dq, n, dout, nullptr);
-        if (rc == VMV_OK && hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        (void) hipFree(dq);
-        (void) hipFree(dout);
-        return rc;
+        const EnvCall c = env_call(robot, nullptr, true, q && out, n, kHost);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), dout = s.out(out, n * (size_t) kRobots[robot].n_spheres * 16);
+        return s.run([&] { return vmv_fk_batch(robot, s.at<float>(dq), n, s.at<float>(dout), nullptr); });
+    }
+    int vmv_eefk_batch_host(int robot, const float *q, size_t n, float *out)
+    {
+        const EnvCall c = env_call(robot, nullptr, true, q && out, n, kHost);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), dout = s.out(out, n * 64);
+        return s.run([&] { return vmv_eefk_batch(robot, s.at<float>(dq), n, s.at<float>(dout), nullptr); });
+    }
+    int vmv_validate_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint64_t *bits)
+    {
+        const EnvCall c = env_call(robot, nullptr, true, q && bits, n, kHost);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), dbits = s.out(bits, (n + 63) / 64 * 8);
+        return s.run([&] { return vmv_validate_batch(robot, env, s.at<float>(dq), n, s.at<uint64_t>(dbits), nullptr); });
+    }
+    int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *a, const float *b, size_t n,
+                                       uint64_t *bits)
+    {
+        if (!b) return VMV_ERR_INVALID_ARGUMENT;
+        const EnvCall c = env_call(robot, nullptr, true, a && bits, n, kHost);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int da = s.in(a, config_bytes(robot, n)), db = s.in(b, config_bytes(robot, n)), dbits = s.out(bits, (n + 63) / 64 * 8);
+        return s.run([&]
+                     { return vmv_validate_motion_batch(robot, env, s.at<float>(da), s.at<float>(db), n, s.at<uint64_t>(dbits), nullptr); });
+    }
+    int vmv_validate_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                      const float *q, uint64_t *bits)
+    {
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, q, q, bits, true);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, c.n)), dbits = s.out(bits, (c.n + 63) / 64 * 8);
+        return s.run([&]
+                     { return vmv_validate_batch_multi(robot, envs, offsets, n_envs, s.at<float>(dq), s.at<uint64_t>(dbits), nullptr); });
+    }
+    int vmv_validate_motion_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
+                                             const float *start, const float *goal, uint64_t *bits)
+    {
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, start, goal, bits, true);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int da = s.in(start, config_bytes(robot, c.n)), db = s.in(goal, config_bytes(robot, c.n)),
+                  dbits = s.out(bits, (c.n + 63) / 64 * 8);
+        return s.run([&]
+                     {
+                         return vmv_validate_motion_batch_multi(robot, envs, offsets, n_envs, s.at<float>(da), s.at<float>(db),
+                                                                s.at<uint64_t>(dbits), nullptr);
+                     });
+    }
+    int vmv_contacts_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint32_t *env_words,
+                                uint32_t *pair_words)
+    {
+        const EnvCall c = env_call(robot, env, false, q && env_words && pair_words, n, kHost);
+        if (!c.run) return c.rc;
+        const size_t ns = (size_t) kRobots[robot].n_spheres, npw = ((size_t) kLaunchers[robot]->n_self_pairs + 31) / 32;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), ds = s.out(nullptr, n * ns * 16),
+                  de = s.out(env_words, n * ns * (vmv::kReportWords + 1) * 4), dp = s.out(pair_words, n * npw * 4, 4, true);
+        return s.run([&]
+                     {
+                         const int rc = kLaunchers[robot]->fk(s.at<float>(dq), n, s.at<float>(ds), nullptr);
+                         return rc != VMV_OK ? rc : kLaunchers[robot]->contacts(*c.launch, s.at<float>(ds), n, s.at<uint32_t>(de),
+                                                                              s.at<uint32_t>(dp), nullptr);
+                     });
     }
 
-    // Device staging of the host-buffer entry points: one grow-only arena per (thread, device), so that a planner's many
-    // small calls (one configuration, a handful of edges) do not pay three hipMalloc / hipFree pairs each.
-    namespace
-    {
-        // Device staging of the *_host entry points, per thread.  Never freed from a destructor: a thread_local of the
-        // main thread is destroyed during static destruction, possibly after the HIP runtime is gone (the memory goes
-        // back with the process).  Long-lived callers release it with vmv_release_staging(); a request above
-        // kStagingKeepBytes is not kept beyond its call, so one huge batch does not pin its memory for the thread's life.
-        constexpr size_t kStagingKeepBytes = size_t{64} << 20;
-        struct StagingArena
-        {
-            void *base = nullptr;
-            size_t capacity = 0;
-            int device = -1;
-            void release()
-            {
-                if (base) (void) hipFree(base);
-                base = nullptr;
-                capacity = 0;
-            }
-            void *get(size_t bytes)
-            {
-                int dev = -1;
-                if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-                if (base && (dev != device || bytes > capacity)) release();
-                if (!base)
-                {
-                    const size_t want = std::max<size_t>(bytes, 1u << 16);
-                    if (hipMalloc(&base, want) != hipSuccess)
-                    {
-                        base = nullptr;
-                        return nullptr;
-                    }
-                    capacity = want;
-                    device = dev;
-                }
-                return base;
-            }
-            void trim()
-            {
-                if (capacity > kStagingKeepBytes) release();
-            }
-        };
-        thread_local StagingArena g_staging;
-    }  // namespace
-
-    static int validate_host_common(int robot, const vmv_env *env, const float *a, const float *b, size_t n,
-                                    uint64_t *bits)
-    {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!a || !bits) return VMV_ERR_INVALID_ARGUMENT;
-        if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        const size_t qb = (n * (size_t) kRobots[robot].dimension * 4 + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
-        char *arena = static_cast<char *>(g_staging.get(2 * qb + wb));
-        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
-        float *da = reinterpret_cast<float *>(arena), *db = reinterpret_cast<float *>(arena + qb);
-        uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + 2 * qb);
-        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4;
-        if (hipMemcpy(da, a, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        if (b && hipMemcpy(db, b, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        rc = b ? vmv_validate_motion_batch(robot, env, da, db, n, dbits, nullptr) :
-                 vmv_validate_batch(robot, env, da, n, dbits, nullptr);
-        if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        g_staging.trim();
-        return rc;
-    }
-    namespace
-    {
-        void release_witness_scratch();  // (the scratch of vmv_clearance_grad_batch, below)
-    }
     int vmv_release_staging(void)
     {
         g_staging.release();
@@ -1659,246 +1795,75 @@ extern "C"
         vmv::release_multi_tables();
         return VMV_OK;
     }
-    int vmv_validate_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
-                                      const float *q, uint64_t *bits)
-    {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, q, q, bits, &n); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        if (int rc = require_device(); rc != VMV_OK) return rc;
-        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
-        char *arena = static_cast<char *>(g_staging.get(qb + wb));
-        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
-        float *dq = reinterpret_cast<float *>(arena);
-        uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + qb);
-        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        int rc = vmv_validate_batch_multi(robot, envs, offsets, n_envs, dq, dbits, nullptr);
-        if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        g_staging.trim();
-        return rc;
-    }
-    int vmv_validate_motion_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
-                                             const float *start, const float *goal, uint64_t *bits)
-    {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, start, goal, bits, &n); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        if (int rc = require_device(); rc != VMV_OK) return rc;
-        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255}, wb = ((n + 63) / 64) * 8;
-        char *arena = static_cast<char *>(g_staging.get(2 * qb + wb));
-        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
-        float *da = reinterpret_cast<float *>(arena), *db = reinterpret_cast<float *>(arena + qb);
-        uint64_t *dbits = reinterpret_cast<uint64_t *>(arena + 2 * qb);
-        if (hipMemcpy(da, start, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        if (hipMemcpy(db, goal, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        int rc = vmv_validate_motion_batch_multi(robot, envs, offsets, n_envs, da, db, dbits, nullptr);
-        if (rc == VMV_OK && hipMemcpy(bits, dbits, wb, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        g_staging.trim();
-        return rc;
-    }
-    int vmv_validate_batch_host(int robot, const vmv_env *env, const float *q, size_t n, uint64_t *bits)
-    {
-        return validate_host_common(robot, env, q, nullptr, n, bits);
-    }
-    int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *a, const float *b, size_t n,
-                                       uint64_t *bits)
-    {
-        if (!b) return VMV_ERR_INVALID_ARGUMENT;
-        return validate_host_common(robot, env, a, b, n, bits);
-    }
 
-    // ---- clearances (include/vamp_mvt_amd.h: vmv_clearance_batch) ----
-    // the checks of vmv_clearance_batch(_host) that need no device, in the header's order
-    static int clearance_args(int robot, const vmv_env *env, const void *q, const void *clearance)
-    {
-        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!q || !clearance)
-        {
-            g_last_error = "null pointer";
-            return VMV_ERR_INVALID_ARGUMENT;
-        }
-        if (!env) return VMV_OK;  // the self clearance alone
-        if (int rc = clearance_kinds(env, "the environment"); rc != VMV_OK) return rc;
-        if (!env->finalized)
-        {
-            g_last_error = "the environment is not finalized";
-            return VMV_ERR_NOT_FINALIZED;
-        }
-        return VMV_OK;
-    }
+    // ---- clearances and their gradients (include/vamp_mvt_amd.h: vmv_clearance_batch, vmv_clearance_grad_batch) ----
     int vmv_clearance_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, uint32_t *d_witness,
                             void *stream)
     {
-        if (int rc = clearance_args(robot, env, d_q, d_clearance); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        if (env)
-        {
-            if (int rc = check_device(env); rc != VMV_OK) return rc;
-            if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        }
-        return kLaunchers[robot]->clearance(env ? &env->launch[robot] : nullptr, d_q, n, d_clearance, d_witness,
-                                            static_cast<hipStream_t>(stream));
+        const EnvCall c = env_call(robot, env, true, d_q && d_clearance, n, kDevice, true);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->clearance(c.launch, d_q, n, d_clearance, d_witness, static_cast<hipStream_t>(stream));
     }
     int vmv_clearance_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
                                   float *d_clearance, uint32_t *d_witness, void *stream)
     {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_q, d_clearance, &n, true); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        for (size_t k = 0; k < n_envs; ++k)
-            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
-        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-        std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
-        return kLaunchers[robot]->clearance_multi(launch.data(), offsets, n_envs, d_q, d_clearance, d_witness,
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_q, d_q, d_clearance, false, true);
+        if (!c.run) return c.rc;
+        return kLaunchers[robot]->clearance_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance, d_witness,
                                                   static_cast<hipStream_t>(stream));
     }
-    // staging of the two host forms: [configurations | clearances | witness] in the arena; `multi`: envs / offsets / n_envs
-    static int clearance_host_common(int robot, const vmv_env *env, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
-                                     bool multi, const float *q, size_t n, float *clearance, uint32_t *witness)
-    {
-        if (int rc = require_device(); rc != VMV_OK) return rc;
-        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255};
-        const size_t cb = (n * 8 + 255) & ~size_t{255}, wb = witness ? n * 16 : 0;
-        char *arena = static_cast<char *>(g_staging.get(qb + cb + wb));
-        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
-        float *dq = reinterpret_cast<float *>(arena), *dc = reinterpret_cast<float *>(arena + qb);
-        uint32_t *dw = witness ? reinterpret_cast<uint32_t *>(arena + qb + cb) : nullptr;
-        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        int rc = multi ? vmv_clearance_batch_multi(robot, envs, offsets, n_envs, dq, dc, dw, nullptr) :
-                         vmv_clearance_batch(robot, env, dq, n, dc, dw, nullptr);
-        if (rc == VMV_OK && hipMemcpy(clearance, dc, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK && witness && hipMemcpy(witness, dw, n * 16, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        g_staging.trim();
-        return rc;
-    }
-    int vmv_clearance_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, uint32_t *witness)
-    {
-        if (int rc = clearance_args(robot, env, q, clearance); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        return clearance_host_common(robot, env, nullptr, nullptr, 0, false, q, n, clearance, witness);
-    }
-    int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
-                                       float *clearance, uint32_t *witness)
-    {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, q, q, clearance, &n, true); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        return clearance_host_common(robot, nullptr, envs, offsets, n_envs, true, q, n, clearance, witness);
-    }
-
-    // ---- clearance gradients (include/vamp_mvt_amd.h: vmv_clearance_grad_batch) ----
-    // The gradient kernel reads the witness the clearance kernel wrote.  A caller without a witness buffer is lent scratch
-    // per (device, stream): calls on one stream run in order, so they share it; grow-only, a larger request frees the old
-    // buffer (hipFree waits for the calls still using it).  The lease holds the pool's lock until the call is enqueued.
-    namespace
-    {
-        struct WitnessScratch
-        {
-            void *p = nullptr;
-            size_t bytes = 0;
-        };
-        std::mutex g_witness_mutex;
-        std::map<std::pair<int, hipStream_t>, WitnessScratch> g_witness;  // never freed at exit (see vmv_release_staging)
-        struct WitnessLease
-        {
-            std::unique_lock<std::mutex> lock{g_witness_mutex, std::defer_lock};
-            int acquire(hipStream_t stream, size_t n, uint32_t **out)
-            {
-                int dev = -1;
-                VMV_HIP(hipGetDevice(&dev));
-                lock.lock();
-                WitnessScratch &w = g_witness[{dev, stream}];
-                if (w.bytes < n * 16)
-                {
-                    if (w.p) (void) hipFree(w.p);
-                    w.p = nullptr, w.bytes = 0;
-                    const size_t want = std::max<size_t>(n * 16, size_t{1} << 16);
-                    VMV_HIP(hipMalloc(&w.p, want));
-                    w.bytes = want;
-                }
-                *out = static_cast<uint32_t *>(w.p);
-                return VMV_OK;
-            }
-        };
-        void release_witness_scratch()
-        {
-            std::lock_guard<std::mutex> g(g_witness_mutex);
-            for (auto &kv : g_witness)
-                if (kv.second.p) (void) hipFree(kv.second.p);
-            g_witness.clear();
-        }
-    }  // namespace
-    // the clearance calls' checks in their order; a NULL d_grad joins the NULL d_q / d_clearance
     int vmv_clearance_grad_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, float *d_grad,
                                  uint32_t *d_witness, void *stream)
     {
-        if (int rc = clearance_args(robot, env, d_q && d_grad ? d_q : nullptr, d_clearance); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        if (env)
-        {
-            if (int rc = check_device(env); rc != VMV_OK) return rc;
-            if (int rc = ensure_robot(env, robot); rc != VMV_OK) return rc;
-        }
-        WitnessLease lease;
-        if (!d_witness)
-            if (int rc = lease.acquire(static_cast<hipStream_t>(stream), n, &d_witness); rc != VMV_OK) return rc;
-        return kLaunchers[robot]->clearance_grad(env ? &env->launch[robot] : nullptr, d_q, n, d_clearance, d_grad, d_witness,
-                                                 static_cast<hipStream_t>(stream));
+        const EnvCall c = env_call(robot, env, true, d_q && d_grad && d_clearance, n, kDevice, true);
+        if (!c.run) return c.rc;
+        return with_witness(d_witness, n, stream, [&](uint32_t *witness)
+                            {
+                                return kLaunchers[robot]->clearance_grad(c.launch, d_q, n, d_clearance, d_grad, witness,
+                                                                         static_cast<hipStream_t>(stream));
+                            });
     }
     int vmv_clearance_grad_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                        const float *d_q, float *d_clearance, float *d_grad, uint32_t *d_witness, void *stream)
     {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, d_q, d_grad, d_clearance, &n, true); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        for (size_t k = 0; k < n_envs; ++k)
-            if (int rc = check_device(envs[k]); rc != VMV_OK) return rc;
-        if (int rc = build_robot_parts(envs, n_envs, robot); rc != VMV_OK) return rc;  // (once per environment and robot)
-        std::vector<const vmv::EnvLaunch *> launch(n_envs);
-        for (size_t k = 0; k < n_envs; ++k) launch[k] = &envs[k]->launch[robot];
-        WitnessLease lease;
-        if (!d_witness)
-            if (int rc = lease.acquire(static_cast<hipStream_t>(stream), n, &d_witness); rc != VMV_OK) return rc;
-        return kLaunchers[robot]->clearance_grad_multi(launch.data(), offsets, n_envs, d_q, d_clearance, d_grad, d_witness,
-                                                       static_cast<hipStream_t>(stream));
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_q, d_grad, d_clearance, false, true);
+        if (!c.run) return c.rc;
+        return with_witness(d_witness, c.n, stream, [&](uint32_t *witness)
+                            {
+                                return kLaunchers[robot]->clearance_grad_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance,
+                                                                               d_grad, witness, static_cast<hipStream_t>(stream));
+                            });
     }
-    // staging of the two host forms: [configurations | clearances | gradients | witness] in the arena
-    static int clearance_grad_host_common(int robot, const vmv_env *env, const vmv_env *const *envs, const size_t *offsets,
-                                          size_t n_envs, bool multi, const float *q, size_t n, float *clearance, float *grad,
-                                          uint32_t *witness)
+    int vmv_clearance_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, uint32_t *witness)
     {
-        if (int rc = require_device(); rc != VMV_OK) return rc;
-        const size_t bytes = n * (size_t) kRobots[robot].dimension * 4, qb = (bytes + 255) & ~size_t{255};
-        const size_t cb = (n * 8 + 255) & ~size_t{255}, gb = (2 * bytes + 255) & ~size_t{255}, wb = n * 16;
-        char *arena = static_cast<char *>(g_staging.get(qb + cb + gb + wb));
-        if (!arena) return hip_fail(hipErrorOutOfMemory, "staging arena");
-        float *dq = reinterpret_cast<float *>(arena), *dc = reinterpret_cast<float *>(arena + qb);
-        float *dg = reinterpret_cast<float *>(arena + qb + cb);
-        uint32_t *dw = reinterpret_cast<uint32_t *>(arena + qb + cb + gb);
-        if (hipMemcpy(dq, q, bytes, hipMemcpyHostToDevice) != hipSuccess) return VMV_ERR_HIP;
-        int rc = multi ? vmv_clearance_grad_batch_multi(robot, envs, offsets, n_envs, dq, dc, dg, dw, nullptr) :
-                         vmv_clearance_grad_batch(robot, env, dq, n, dc, dg, dw, nullptr);
-        if (rc == VMV_OK && hipMemcpy(clearance, dc, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK && hipMemcpy(grad, dg, 2 * bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK && witness && hipMemcpy(witness, dw, n * 16, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        g_staging.trim();
-        return rc;
+        const EnvCall c = env_call(robot, env, true, q && clearance, n, kHost, true);
+        if (!c.run) return c.rc;
+        return clearance_staged(robot, q, n, clearance, nullptr, witness, [&](float *dq, float *dc, float *, uint32_t *dw)
+                                { return kLaunchers[robot]->clearance(c.launch, dq, n, dc, dw, nullptr); });
+    }
+    int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
+                                       float *clearance, uint32_t *witness)
+    {
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, q, q, clearance, true, true);
+        if (!c.run) return c.rc;
+        return clearance_staged(robot, q, c.n, clearance, nullptr, witness, [&](float *dq, float *dc, float *, uint32_t *dw)
+                                { return vmv_clearance_batch_multi(robot, envs, offsets, n_envs, dq, dc, dw, nullptr); });
     }
     int vmv_clearance_grad_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, float *grad,
                                       uint32_t *witness)
     {
-        if (int rc = clearance_args(robot, env, q && grad ? q : nullptr, clearance); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        return clearance_grad_host_common(robot, env, nullptr, nullptr, 0, false, q, n, clearance, grad, witness);
+        const EnvCall c = env_call(robot, env, true, q && grad && clearance, n, kHost, true);
+        if (!c.run) return c.rc;
+        return clearance_staged(robot, q, n, clearance, grad, witness, [&](float *dq, float *dc, float *dg, uint32_t *dw)
+                                { return kLaunchers[robot]->clearance_grad(c.launch, dq, n, dc, dg, dw, nullptr); });
     }
     int vmv_clearance_grad_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                             const float *q, float *clearance, float *grad, uint32_t *witness)
     {
-        size_t n = 0;
-        if (int rc = multi_args(robot, envs, offsets, n_envs, q, grad, clearance, &n, true); rc != VMV_OK) return rc;
-        if (n == 0) return VMV_OK;
-        return clearance_grad_host_common(robot, nullptr, envs, offsets, n_envs, true, q, n, clearance, grad, witness);
+        const MultiCall c = multi_call(robot, envs, offsets, n_envs, q, grad, clearance, true, true);
+        if (!c.run) return c.rc;
+        return clearance_staged(robot, q, c.n, clearance, grad, witness, [&](float *dq, float *dc, float *dg, uint32_t *dw)
+                                { return vmv_clearance_grad_batch_multi(robot, envs, offsets, n_envs, dq, dc, dg, dw, nullptr); });
     }
 
     // ---- multi-GPU sharding arithmetic (vamp_mvt_amd/sharding.py: shard_range) ----
@@ -1917,69 +1882,47 @@ extern "C"
         return VMV_OK;
     }
 
-    // ---- free spheres against the environment ----
+    // ---- free spheres against the environment (any robot's image will do: the counted loops use no grid) ----
     int vmv_spheres_in_collision_batch(const vmv_env *env, const float *d_spheres, size_t n, uint8_t *d_hits, void *stream)
     {
-        if (!env || !d_spheres || !d_hits) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
-        if (n == 0) return VMV_OK;
-        if (int rc = check_device(env); rc != VMV_OK) return rc;
-        if (int rc = ensure_robot(env, 0); rc != VMV_OK) return rc;  // any robot's image: the counted loops use no grid
-        const size_t blocks = (n + vmv::kBlock - 1) / vmv::kBlock;
-        hipLaunchKernelGGL(vmv::spheres_env_kernel, dim3((unsigned) std::min<size_t>(blocks, 4096)), dim3(vmv::kBlock),
-                           (env->base.n_floats + vmv::kCaptFlagWords) * sizeof(float), static_cast<hipStream_t>(stream), env->launch[0].d_env,
-                           reinterpret_cast<const float4 *>(d_spheres), n, d_hits, (const float4 *) nullptr, 0);
-        VMV_HIP(hipGetLastError());
-        return VMV_OK;
+        const EnvCall c = env_call(0, env, false, d_spheres && d_hits, n, kDevice);
+        if (!c.run) return c.rc;
+        return launch_spheres(env, d_spheres, n, d_hits, nullptr, 0, stream);
+    }
+    int vmv_spheres_in_collision_batch_host(const vmv_env *env, const float *spheres, size_t n, uint8_t *hits)
+    {
+        const EnvCall c = env_call(0, nullptr, true, env && spheres && hits, n, kHost);
+        if (!c.run) return c.rc;
+        Staged s;
+        const int ds = s.in(spheres, n * 16), dh = s.out(hits, n);
+        return s.run([&] { return vmv_spheres_in_collision_batch(env, s.at<float>(ds), n, s.at<uint8_t>(dh), nullptr); });
     }
     int vmv_filter_self_from_pointcloud(int robot, const vmv_env *env, const float *q, const float *points_xyz, size_t n,
                                         float point_radius, float *out_xyz, size_t capacity, size_t *n_out)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!env || !q || (n && !points_xyz) || !n_out) return VMV_ERR_INVALID_ARGUMENT;
-        if (!env->finalized) return VMV_ERR_NOT_FINALIZED;
+        const EnvCall c = env_call(0, env, false, q && (!n || points_xyz) && n_out, n, kHost);
+        if (!c.run && c.rc != VMV_OK) return c.rc;
         *n_out = 0;
-        if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        if ((rc = check_device(env)) != VMV_OK) return rc;
-        if ((rc = ensure_robot(env, 0)) != VMV_OK) return rc;
-        const size_t dim = (size_t) kRobots[robot].dimension, ns = (size_t) kRobots[robot].n_spheres;
+        if (!c.run) return VMV_OK;
+        const size_t ns = (size_t) kRobots[robot].n_spheres;
         std::vector<float> spheres(4 * n);
         for (size_t i = 0; i < n; ++i)
         {
             std::memcpy(&spheres[4 * i], points_xyz + 3 * i, 12);
             spheres[4 * i + 3] = point_radius;
         }
-        float *dq = nullptr, *drs = nullptr, *ds = nullptr;
-        uint8_t *dh = nullptr;
         std::vector<uint8_t> hits(n);
-        auto release = [&]()
-        {
-            (void) hipFree(dq);
-            (void) hipFree(drs);
-            (void) hipFree(ds);
-            (void) hipFree(dh);
-        };
-        if (hipMalloc((void **) &dq, dim * 4) != hipSuccess || hipMalloc((void **) &drs, ns * 16) != hipSuccess ||
-            hipMalloc((void **) &ds, n * 16) != hipSuccess || hipMalloc((void **) &dh, n) != hipSuccess ||
-            hipMemcpy(dq, q, dim * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ds, spheres.data(), n * 16, hipMemcpyHostToDevice) != hipSuccess)
-        {
-            release();
-            return VMV_ERR_HIP;
-        }
-        rc = kLaunchers[robot]->fk(dq, 1, drs, nullptr);  // Robot::sphere_fk of the one configuration
-        if (rc == VMV_OK)
-        {
-            const size_t blocks = (n + vmv::kBlock - 1) / vmv::kBlock;
-            hipLaunchKernelGGL(vmv::spheres_env_kernel, dim3((unsigned) std::min<size_t>(blocks, 4096)), dim3(vmv::kBlock),
-                               (env->base.n_floats + vmv::kCaptFlagWords) * sizeof(float), nullptr, env->launch[0].d_env,
-                               reinterpret_cast<const float4 *>(ds), n, dh, reinterpret_cast<const float4 *>(drs), (int) ns);
-            if (hipGetLastError() != hipSuccess || hipMemcpy(hits.data(), dh, n, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = VMV_ERR_HIP;
-        }
-        release();
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, 1)), drs = s.out(nullptr, ns * 16), ds = s.in(spheres.data(), n * 16),
+                  dh = s.out(hits.data(), n);
+        const int rc = s.run([&]
+                             {
+                                 // Robot::sphere_fk of the one configuration
+                                 const int fk = kLaunchers[robot]->fk(s.at<float>(dq), 1, s.at<float>(drs), nullptr);
+                                 return fk != VMV_OK ? fk : launch_spheres(env, s.at<float>(ds), n, s.at<uint8_t>(dh), s.at<float>(drs),
+                                                                           (int) ns, nullptr);
+                             });
         if (rc != VMV_OK) return rc;
         size_t m = 0;
         for (size_t i = 0; i < n; ++i)
@@ -1990,27 +1933,6 @@ extern "C"
             }
         *n_out = m;
         return (out_xyz && m > capacity) ? VMV_ERR_CAPACITY : VMV_OK;
-    }
-    int vmv_spheres_in_collision_batch_host(const vmv_env *env, const float *spheres, size_t n, uint8_t *hits)
-    {
-        if (!env || !spheres || !hits) return VMV_ERR_INVALID_ARGUMENT;
-        if (n == 0) return VMV_OK;
-        int rc = require_device();
-        if (rc != VMV_OK) return rc;
-        float *ds = nullptr;
-        uint8_t *dh = nullptr;
-        VMV_HIP(hipMalloc((void **) &ds, n * 16));
-        if (hipMalloc((void **) &dh, n) != hipSuccess)
-        {
-            (void) hipFree(ds);
-            return VMV_ERR_HIP;
-        }
-        if (hipMemcpy(ds, spheres, n * 16, hipMemcpyHostToDevice) != hipSuccess) rc = VMV_ERR_HIP;
-        if (rc == VMV_OK) rc = vmv_spheres_in_collision_batch(env, ds, n, dh, nullptr);
-        if (rc == VMV_OK && hipMemcpy(hits, dh, n, hipMemcpyDeviceToHost) != hipSuccess) rc = VMV_ERR_HIP;
-        (void) hipFree(ds);
-        (void) hipFree(dh);
-        return rc;
     }
 
     // ---- measurement support ----
@@ -2041,37 +1963,14 @@ extern "C"
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q) return VMV_ERR_INVALID_ARGUMENT;
-        const int dim = kRobots[robot].dimension;
-        float *d_bounds = nullptr;
-        VMV_HIP(hipMalloc((void **) &d_bounds, 32 * sizeof(float)));
-        VMV_HIP(hipMemcpy(d_bounds, kRobots[robot].lower, 16 * sizeof(float), hipMemcpyHostToDevice));
-        VMV_HIP(hipMemcpy(d_bounds + 16, kRobots[robot].span, 16 * sizeof(float), hipMemcpyHostToDevice));
-        const size_t total = n * (size_t) dim;
-        hipLaunchKernelGGL(vmv::fill_uniform_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), d_q, total, dim, seed, d_bounds, d_bounds + 16);
-        VMV_HIP(hipGetLastError());
-        VMV_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        (void) hipFree(d_bounds);
-        return VMV_OK;
+        return generate_configs(robot, vmv::fill_uniform_kernel, seed, d_q, n, stream);
     }
-
     int vmv_halton_configs(int robot, uint64_t skip, float *d_q, size_t n, void *stream)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q || skip + n > 1000000ull) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
-        const int dim = kRobots[robot].dimension;
-        float *d_bounds = nullptr;
-        VMV_HIP(hipMalloc((void **) &d_bounds, 32 * sizeof(float)));
-        VMV_HIP(hipMemcpy(d_bounds, kRobots[robot].lower, 16 * sizeof(float), hipMemcpyHostToDevice));
-        VMV_HIP(hipMemcpy(d_bounds + 16, kRobots[robot].span, 16 * sizeof(float), hipMemcpyHostToDevice));
-        const size_t total = n * (size_t) dim;
-        hipLaunchKernelGGL(vmv::halton_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), d_q, total, dim, skip, d_bounds, d_bounds + 16);
-        VMV_HIP(hipGetLastError());
-        VMV_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        (void) hipFree(d_bounds);
-        return VMV_OK;
+        return generate_configs(robot, vmv::halton_kernel, skip, d_q, n, stream);
     }
 
     const char *vmv_kernel_name(int robot, const char *entry_point)
