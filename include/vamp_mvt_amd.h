@@ -306,6 +306,61 @@ int vmv_clearance_grad_batch_multi(int robot, const vmv_env *const *envs, const 
 int vmv_clearance_grad_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                         const float *q, float *clearance, float *grad, uint32_t *witness);
 
+/* ---- end-effector Jacobian and inverse kinematics (no counterpart in the reference) ------------------ */
+/* The end-effector frame and its geometric Jacobian in the world frame: d_frames [n][16] (may be NULL) are bit for bit
+ * those of vmv_eefk_batch; d_jac [n][6][dim] fp32: rows 0-2 are dt/dq_j, rows 3-5 the angular velocity omega_j: with
+ * A = (dR/dq_j) R^T, omega = 1/2 (A21 - A12, A02 - A20, A10 - A01), every 3-term product of A as ((a0 b0 + a1 b1) + a2 b2).
+ * dt/dq and dR/dq are the forward-mode tangents of the end-effector op tape as written (tools/gen_hip.py: ee_tangent_tape;
+ * the rules of vmv_clearance_grad_batch), fp32 without contraction; a joint that does not move the end effector has a
+ * zero column.  A configuration with a non-finite joint: the frame vmv_eefk_batch gives it and 6 * dim NaNs.  Checks:
+ * unknown robot; NULL d_q / d_jac (VMV_ERR_INVALID_ARGUMENT, "null pointer"); n == 0 is VMV_OK without a device. */
+int vmv_eefk_jacobian_batch(int robot, const float *d_q, size_t n, float *d_frames /* [n][16], may be NULL */,
+                            float *d_jac /* [n][6][dim] */, void *stream);
+int vmv_eefk_jacobian_batch_host(int robot, const float *q, size_t n, float *frames, float *jac);
+
+/* Numerical inverse kinematics for many targets at once: n_seeds independent damped least-squares (Levenberg-Marquardt)
+ * iterations per target, one lane per (target, seed).  Targets are frames as vmv_eefk_batch writes them.
+ *   Seeds: d_seeds [n_targets][n_seeds][dim] (a warm start along a trajectory, say), clipped to the joint bounds; or NULL:
+ *     seed s of every target is Halton sample halton_skip + s + 1 (vmv_halton_configs' sequence, generated on the stream
+ *     into scratch per (device, stream) that vmv_release_staging frees), valid while halton_skip + n_seeds <= 1,000,000.
+ *   Error of a state q with frame (R, t) against the target (R*, t*): e_p = t* - t; e_w = 1/2 sum_k R_k x R*_k over the
+ *     three columns, whose norm is sin(theta) of the rotation between the frames; where tr(R*^T R) <= 1 (theta >= 90
+ *     degrees) e_w enters the weighted error at unit length.  e = [e_p ; rot_weight e_w], E = 1/2 |e|^2.
+ *   Converged: |e_p| <= pos_tol and, unless position_only, tr(R*^T R) > 1 and |e_w| <= rot_tol (e_w as it is).
+ *   Iteration: evaluate the seed; then per iteration, with J the Jacobian above, its rotation rows times rot_weight and the
+ *     column of every joint that sits at a bound while the descent direction (J^T e)_j points out of the range set to
+ *     zero: A = J J^T + lambda I, A y = e (6 x 6 Cholesky), delta = J^T y scaled so that max_j |delta_j| <= max_step,
+ *     q' = q + delta clipped to [lower, lower + span] of vmv_robot_bounds; evaluate q'; E' < E: accept and lambda =
+ *     max(lambda / 4, 1e-5), else keep q and lambda = min(4 lambda, 1e6).  The converged test runs on the accepted state
+ *     after every evaluation; a converged lane stops changing; a wave stops when its lanes are done or at max_iterations.
+ *   Outputs per (target, seed): d_q the accepted state of smallest E - never worse than the (clipped) seed, always inside
+ *     the bounds; d_err (may be NULL) = |e_p|, |e_w| of that state; d_status: bit 31 converged, bit 30 invalid input (a
+ *     non-finite entry of the target or the seed: d_q is the seed as given, d_err NaN), the low bits the evaluations made
+ *     after the seed's.
+ * A lane's result depends on its own target, seed and settings alone, bit for bit - not on the batch, its position in it,
+ * the entry point, or whether its Halton seed was generated or passed in.  fp32 without contraction.
+ * Checks before any launch, those that need no device first: unknown robot; NULL d_targets / settings / d_q / d_status
+ * ("null pointer"); the limits of the settings in the struct's order; the Halton limit (d_seeds == NULL); n_targets *
+ * n_seeds >= 2^31 (all VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the check).  A refused call writes nothing;
+ * n_targets == 0 is VMV_OK without a device. */
+typedef struct
+{
+    uint32_t n_seeds;        /* seeds per target, 1 .. 1,024 */
+    uint32_t max_iterations; /* 1 .. 2^30 - 1 */
+    float pos_tol, rot_tol;  /* metres, radians; finite, > 0 */
+    float rot_weight;        /* metres per radian: weight of the three rotation rows; finite, > 0 */
+    float damping;           /* initial lambda; finite, > 0 */
+    float max_step;          /* limit on the largest joint change of one step; finite, > 0 */
+    int position_only;       /* 0 / 1: the rotation rows are zero and rot_tol is not tested */
+} vmv_ik_settings;
+int vmv_ik_batch(int robot, const float *d_targets /* [n_targets][16] */, size_t n_targets,
+                 const float *d_seeds /* [n_targets][n_seeds][dim], or NULL */, uint64_t halton_skip,
+                 const vmv_ik_settings *settings, float *d_q /* [n_targets][n_seeds][dim] */,
+                 float *d_err /* [n_targets][n_seeds][2]: position, rotation; may be NULL */,
+                 uint32_t *d_status /* [n_targets][n_seeds] */, void *stream);
+int vmv_ik_batch_host(int robot, const float *targets, size_t n_targets, const float *seeds, uint64_t halton_skip,
+                      const vmv_ik_settings *settings, float *q, float *err, uint32_t *status);
+
 /* sphere_environment_in_collision(environment, x, y, z, r) — collision/validity.hh:47-158, the predicate every fkcc
  * check is made of (and CAPT::collides / MVT::collides behind it, collision/capt.hh:374-415), for a batch of free
  * spheres: spheres [n][4] = x y z r, hits[i] = 1 iff sphere i collides with the environment.  Each sphere is its own
@@ -330,8 +385,8 @@ int vmv_validate_motion_batch_host(int robot, const vmv_env *env, const float *s
  * included) stages through a per-thread device arena that is reused between calls: a thread keeps up to 64 MiB of device
  * memory after such a call (requests above 64 MiB are not kept beyond their call) until it calls this function.
  * vmv_validate_motion_batch keeps 8 bytes of device scratch per edge per (device, stream) for its task
- * lists, the multi-environment calls their tables.  Frees the calling thread's arena and every stream's scratch and tables
- * (waits for the batches in flight); optional — none of this memory is touched at thread or process exit. */
+ * lists, the multi-environment calls their tables, vmv_ik_batch 64 KiB of Halton seeds.  Frees the calling thread's
+ * arena and every stream's scratch and tables (waits for the batches in flight); optional — none of this memory is touched at thread or process exit. */
 int vmv_release_staging(void);
 
 /* ---- multi-GPU: one process per GPU, every unit independent given the read-only environment ------- */

@@ -161,7 +161,8 @@ def eval_tape(m, q, batch=4096):
 
 
 def tangent_tape(m):
-    """Forward-mode derivative of the op tape with respect to the joints, for the fine spheres alone.
+    """Forward-mode derivative of the op tape with respect to the joints, for the fine spheres alone -
+    outputs 0 .. n_spheres - 1 of any model-shaped dict: ee_model(m) makes the end-effector tape one.
 
     Returns {"ops": the primal ops the fine spheres depend on, in tape order,
              "nz":  {op: joints whose tangent of that op is structurally non-zero, ascending},
@@ -298,6 +299,75 @@ def eval_tangent_tape(m, q, tt=None):
             for j in tt["nz"][x]:
                 jac[:, s, k, j] = d[(x, j)]
     return c, jac
+
+
+def ee_model(m):
+    """The end-effector tape as a model that tangent_tape, eval_tangent_tape and eval_tape take: four "spheres" of three
+    outputs each - the translation, then the three columns of the rotation (ee_frame's f[0..11] in order)."""
+    return dict(name=m["name"], dimension=m["dimension"], ops=m["ee_ops"], n_spheres=4,
+                outputs=[m["ee_outputs"][3 * i:3 * i + 3] for i in range(4)])
+
+
+def ee_tangent_tape(m):
+    """tangent_tape of the end-effector tape; evaluate it with eval_tangent_tape(ee_model(m), q, tt)."""
+    return tangent_tape(ee_model(m))
+
+
+def ee_joint_mask(m, tt=None):
+    """bit j: joint j moves the end-effector frame (some output of the ee tape has a structurally non-zero tangent)"""
+    tt = tt or ee_tangent_tape(m)
+    return sum(1 << j for j in {j for kind, v in m["ee_outputs"] if kind == "op" for j in tt["nz"][v]})
+
+
+def emit_ee_frame_jac(m):
+    """Robot::ee_frame_jac: ee_frame with the tangents of its twelve outputs (DESIGN.md §5k).  The primal ops are
+    ee_frame's, in tape order and under the same names; each op's structurally non-zero tangents follow it; df entries
+    without one are literal zeros."""
+    em = ee_model(m)
+    tt = tangent_tape(em)
+    ops, tan, nz = em["ops"], tt["tan"], tt["nz"]
+    L = []
+    L.append("    // ee_frame with its joint-space tangents: f as ee_frame writes it, df[i][j] = d f[i] / d q[j]; an entry whose")
+    L.append("    // tangent is structurally zero is a literal 0 (kEeJointMask: the joints that move the frame at all).")
+    L.append(f"    // {len(tt['ops'])} primal and {tangent_op_count(em, tt)} tangent operations (tools/gen_hip.py: ee_tangent_tape).")
+    L.append("    __device__ __forceinline__ void ee_frame_jac(const float (&q)[kDim], float (&f)[12], float (&df)[12][kDim])")
+    L.append("    {")
+    name = {}
+    for i in tt["ops"]:
+        op, a, b = ops[i]
+        L.append(f"        const float e{i} = {op_expr(op, a, b, prefix='e')};")
+        for j in nz[i]:
+            f = tan[(i, j)]
+            if f[0] == "one":
+                name[(i, j)] = "1.0f"
+                continue
+            if f[0] == "copy":
+                name[(i, j)] = name[(f[1], j)]
+                continue
+            if f[0] == "cos":
+                e = f"vmv::vcos(e{f[1]})"
+            elif f[0] == "nsin":
+                e = f"-vmv::vsin(e{f[1]})"
+            elif f[0] == "neg":
+                e = f"-{name[(f[1], j)]}"
+            elif f[0] in ("add", "sub"):
+                e = f"{name[(f[1], j)]} {'+' if f[0] == 'add' else '-'} {name[(f[2], j)]}"
+            elif f[0] == "cmul":
+                e = f"{flit(f[1])} * {name[(f[2], j)]}"
+            else:
+                e = " + ".join(f"e{y}" if name[(x, j)] == "1.0f" else f"{name[(x, j)]} * e{y}" for x, y in f[1])
+            name[(i, j)] = f"g{i}_{j}"
+            L.append(f"        const float g{i}_{j} = {e};")
+    for i, (kind, v) in enumerate(m["ee_outputs"]):
+        L.append(f"        f[{i}] = {f'e{v}' if kind == 'op' else flit(v)};")
+    for i, (kind, v) in enumerate(m["ee_outputs"]):
+        live = nz[v] if kind == "op" else []
+        for j in range(m["dimension"]):
+            L.append(f"        df[{i}][{j}] = {name[(v, j)] if j in live else '0.0f'};")
+    L.append("    }")
+    L.append(f"    constexpr unsigned kEeJointMask = {hex(ee_joint_mask(m, tt))}u;  // joints with a non-zero column of df")
+    L.append("")
+    return L
 
 
 def emit_sphere_fk_grad(m):
@@ -1495,6 +1565,7 @@ def emit_robot(m):
             L.append(f"        f[{3 * i + k}] = {em.coord(i, k)};")
     L.append("    }")
     L.append("")
+    L += emit_ee_frame_jac(m)
     L.append("    // The attachment part of Robot::fkcc_attach (robots/%s.hh; collision/attachments.hh, validity.hh:258-303):" % n)
     L.append("    // pose the attached spheres at the end-effector frame, test them against the environment and against the")
     L.append("    // links of the reference's \"Attachment vs. <link>\" blocks.  true = this rake collides.  The two frame")
@@ -1676,6 +1747,11 @@ def emit_robot(m):
     L.append("                                                          const unsigned sb, float (&c)[3][3], float (&J)[3][3][kDim])")
     L.append("    {")
     L.append(f"        {n}::sphere_fk_grad(q, se, sa, sb, c, J);")
+    L.append("    }")
+    L.append(f"    static constexpr unsigned kEeJointMask = {n}::kEeJointMask;")
+    L.append("    static __device__ __forceinline__ void ee_frame_jac(const float (&q)[kDim], float (&f)[12], float (&df)[12][kDim])")
+    L.append("    {")
+    L.append(f"        {n}::ee_frame_jac(q, f, df);")
     L.append("    }")
     L.append("};")
     L.append("")

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import VmvError, check, lib
 
 __all__ = ["robots", "Sphere", "Cuboid", "Cylinder", "Attachment", "filter_pointcloud", "HeightField", "make_heightfield", "png_to_heightfield", "Environment", "device_count", "set_device", "abi_version",
-           "VmvError", "unpack_bits", "POINT_RADIUS"]
+           "VmvError", "unpack_bits", "POINT_RADIUS", "IKSettings"]
 
 POINT_RADIUS = 0.0025  # reference src/vamp/constants.py:25
 
@@ -567,6 +567,26 @@ def _simplify_settings_struct(settings, longest=0):
                                float(settings.midpoint_interpolation), max_wp, w, every)
 
 
+class IKSettings:
+    """vmv_ik_settings (include/vamp_mvt_amd.h) with the defaults of <robot>.ik_batch: n_seeds seeds per target (1 ..
+    1,024), max_iterations, pos_tol (m), rot_tol (rad; the sine of the residual angle is compared), rot_weight (metres per
+    radian: the weight of the rotation rows), damping (the initial lambda), max_step (the largest joint change of one
+    step), position_only (the orientation is free)."""
+
+    def __init__(self, n_seeds=32, max_iterations=64, pos_tol=1e-4, rot_tol=1e-3, rot_weight=0.25, damping=1e-2,
+                 max_step=0.5, position_only=False):
+        self.n_seeds, self.max_iterations = n_seeds, max_iterations
+        self.pos_tol, self.rot_tol, self.rot_weight = pos_tol, rot_tol, rot_weight
+        self.damping, self.max_step, self.position_only = damping, max_step, position_only
+
+    def struct(self):
+        return _lib.IkSettings(int(self.n_seeds), int(self.max_iterations), float(self.pos_tol), float(self.rot_tol),
+                               float(self.rot_weight), float(self.damping), float(self.max_step), int(bool(self.position_only)))
+
+    def __repr__(self):
+        return "IKSettings(" + ", ".join(f"{k}={v!r}" for k, v in vars(self).items()) + ")"
+
+
 class _Robot(types.ModuleType):
     def __init__(self, name: str):
         super().__init__(f"{__name__}.{name}")
@@ -664,6 +684,68 @@ class _Robot(types.ModuleType):
 
     def eefk_batch(self, configurations):
         return self._batched("vmv_eefk_batch", [configurations], [((4, 4), "f32", True)])[0]
+
+    def eefk_jacobian(self, configuration):
+        """(4 x 4 frame, float32[6][dim]): eefk's frame and the end-effector Jacobian of one configuration, as
+        eefk_jacobian_batch defines it."""
+        frames, jac = self.eefk_jacobian_batch(_f32(configuration, (self._dim,))[None, :])
+        return frames[0], jac[0]
+
+    def eefk_jacobian_batch(self, configurations):
+        """(float32[n][4][4], float32[n][6][dim]): eefk_batch's frames, bit for bit, and the geometric Jacobian in the
+        world frame - rows 0-2 d translation / d q_j, rows 3-5 the angular velocity per unit of q_j (include/vamp_mvt_amd.h:
+        vmv_eefk_jacobian_batch).  A joint that does not move the end effector has a zero column; a configuration with a
+        non-finite joint has a NaN Jacobian.  numpy in -> numpy out; a torch CUDA tensor in -> torch CUDA tensors out."""
+        return tuple(self._batched("vmv_eefk_jacobian_batch", [configurations], [((4, 4), "f32", True), ((6, self._dim), "f32", True)]))
+
+    def ik_batch(self, targets, seeds=None, halton_skip=0, settings=None):
+        """Inverse kinematics for many end-effector targets at once (include/vamp_mvt_amd.h: vmv_ik_batch): targets
+        [n][4][4] (or [n][16]) frames as eefk_batch returns them; per target settings.n_seeds damped least-squares
+        iterations, from seeds [n][n_seeds][dim] or, with seeds=None, from Halton samples halton_skip + 1 .. + n_seeds.
+        -> (q float32[n][n_seeds][dim], err float32[n][n_seeds][2] = position (m) and rotation (sin of the angle)
+        residuals, converged bool[n][n_seeds], iterations int32[n][n_seeds]).  q is the best state the iteration accepted:
+        never worse than its seed, always inside the joint bounds.  A row whose target or seed has a non-finite entry
+        comes back as its seed with NaN errors, not converged.  numpy in -> numpy out; torch CUDA tensors in -> torch CUDA
+        tensors out, launched on torch's current stream."""
+        s = settings or IKSettings()
+        cs = s.struct()
+        n_seeds = int(s.n_seeds)
+        torch_in = _is_torch_cuda(targets)
+        if seeds is not None and _is_torch_cuda(seeds) != torch_in:
+            raise TypeError("targets and seeds must both be numpy arrays or both be torch CUDA tensors")
+        if torch_in:
+            import torch
+
+            device = targets.device
+            targets = targets.to(device).contiguous().float()
+            if seeds is not None:
+                seeds = seeds.to(device).contiguous().float()
+        else:
+            targets = _f32(targets)
+            if seeds is not None:
+                seeds = _f32(seeds)
+        if targets.ndim < 2 or int(np.prod(tuple(targets.shape[1:]))) != 16:
+            raise TypeError("expected targets as [n][4][4] (or [n][16]) frames")
+        n = int(targets.shape[0])
+        if seeds is not None and tuple(seeds.shape) != (n, n_seeds, self._dim):
+            raise TypeError(f"expected seeds as [{n}][{n_seeds}][{self._dim}] (n_targets, settings.n_seeds, dimension)")
+        shape = (n, n_seeds)
+        if torch_in:
+            with torch.cuda.device(device):
+                q = torch.empty((*shape, self._dim), dtype=torch.float32, device=device)
+                err = torch.empty((*shape, 2), dtype=torch.float32, device=device)
+                status = torch.zeros(shape, dtype=torch.int32, device=device)
+                ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+                check(lib.vmv_ik_batch(self._id, ptr(targets), n, None if seeds is None else ptr(seeds), int(halton_skip),
+                                       ctypes.byref(cs), ptr(q), ptr(err), ptr(status),
+                                       ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "vmv_ik_batch")
+            return q, err, status < 0, status & 0x3fffffff
+        q = np.zeros((*shape, self._dim), np.float32)
+        err = np.zeros((*shape, 2), np.float32)
+        status = np.zeros(shape, np.uint32)
+        check(lib.vmv_ik_batch_host(self._id, _fp(targets), n, None if seeds is None else _fp(seeds), int(halton_skip),
+                                    ctypes.byref(cs), _fp(q), _fp(err), status.ctypes.data_as(_lib.c_u32_p)), "vmv_ik_batch_host")
+        return q, err, (status >> 31).astype(bool), (status & 0x3fffffff).astype(np.int32)
 
     def fk(self, configuration):
         """<robot>.fk(q) -> list[Sphere] — robot_helper.hh:234-247."""

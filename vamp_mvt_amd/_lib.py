@@ -74,6 +74,13 @@ class AorrtcSettings(ctypes.Structure):
                 ("max_samples", ctypes.c_uint32), ("max_cost_bound_resamples", ctypes.c_uint32), ("max_searches", ctypes.c_uint32)]
 
 
+class IkSettings(ctypes.Structure):
+    """vmv_ik_settings"""
+    _fields_ = [("n_seeds", ctypes.c_uint32), ("max_iterations", ctypes.c_uint32), ("pos_tol", ctypes.c_float),
+                ("rot_tol", ctypes.c_float), ("rot_weight", ctypes.c_float), ("damping", ctypes.c_float),
+                ("max_step", ctypes.c_float), ("position_only", ctypes.c_int)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -175,6 +182,11 @@ def _load():
         "vmv_clearance_grad_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V, V, V]),
         "vmv_clearance_grad_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_float_p, c_float_p,
                                                     c_u32_p]),
+        "vmv_eefk_jacobian_batch": (I, [I, V, S, V, V, V]),
+        "vmv_eefk_jacobian_batch_host": (I, [I, c_float_p, S, c_float_p, c_float_p]),
+        "vmv_ik_batch": (I, [I, V, S, V, ctypes.c_uint64, ctypes.POINTER(IkSettings), V, V, V, V]),
+        "vmv_ik_batch_host": (I, [I, c_float_p, S, c_float_p, ctypes.c_uint64, ctypes.POINTER(IkSettings), c_float_p, c_float_p,
+                                  c_u32_p]),
         "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
         "vmv_rrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(RrtcSettings),
                                ctypes.POINTER(V)]),

@@ -1436,7 +1436,7 @@ namespace
             bool zero;
             void *ptr;
         };
-        Region regions[4];
+        Region regions[6];
         int count = 0;
         int add(const void *src, void *dst, size_t bytes, size_t room, bool zero)
         {
@@ -1546,6 +1546,74 @@ namespace
                            (env->base.n_floats + vmv::kCaptFlagWords) * sizeof(float), static_cast<hipStream_t>(stream), env->launch[0].d_env,
                            reinterpret_cast<const float4 *>(d_spheres), n, d_hits, reinterpret_cast<const float4 *>(d_robot_spheres), n_robot);
         VMV_HIP(hipGetLastError());
+        return VMV_OK;
+    }
+
+    // vmv_ik_batch without the caller's seeds: the robot's bounds and n_seeds Halton samples in scratch per (device,
+    // stream), [lower 16 | span 16 | seeds 1,024 x 16 floats] - its full size from the start, so it never moves.  Calls on
+    // one stream run in order and share it; the bounds are uploaded when the entry last served another robot.  The lease
+    // holds the pool's lock until the call is enqueued.
+    constexpr size_t kIkMaxSeeds = 1024;
+    struct IkSeedScratch
+    {
+        float *p = nullptr;
+        int robot = -1;
+    };
+    std::mutex g_ik_mutex;
+    std::map<std::pair<int, hipStream_t>, IkSeedScratch> g_ik_seeds;  // never freed at exit (see vmv_release_staging)
+    struct IkSeedLease
+    {
+        std::unique_lock<std::mutex> lock{g_ik_mutex, std::defer_lock};
+        int acquire(hipStream_t stream, int robot, float **out)
+        {
+            int dev = -1;
+            VMV_HIP(hipGetDevice(&dev));
+            lock.lock();
+            IkSeedScratch &w = g_ik_seeds[{dev, stream}];
+            if (!w.p) VMV_HIP(hipMalloc((void **) &w.p, (32 + kIkMaxSeeds * 16) * sizeof(float)));
+            if (w.robot != robot)
+            {
+                w.robot = -1;
+                VMV_HIP(hipMemcpyAsync(w.p, kRobots[robot].lower, 16 * sizeof(float), hipMemcpyHostToDevice, stream));
+                VMV_HIP(hipMemcpyAsync(w.p + 16, kRobots[robot].span, 16 * sizeof(float), hipMemcpyHostToDevice, stream));
+                w.robot = robot;
+            }
+            *out = w.p;
+            return VMV_OK;
+        }
+    };
+    void release_ik_scratch()
+    {
+        std::lock_guard<std::mutex> g(g_ik_mutex);
+        for (auto &kv : g_ik_seeds)
+            if (kv.second.p) (void) hipFree(kv.second.p);
+        g_ik_seeds.clear();
+    }
+
+    // The checks of vmv_ik_batch that need no device, in the header's order; fills the kernel's parameter block.
+    int ik_checks(int robot, const float *targets, size_t n_targets, const float *seeds, uint64_t halton_skip,
+                  const vmv_ik_settings *s, const float *q, const uint32_t *status, vmv::IkParams &P)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!targets || !s || !q || !status) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        const auto positive = [](float v) { return std::isfinite(v) && v > 0.0f; };
+        const char *err = (s->n_seeds < 1u || s->n_seeds > (uint32_t) kIkMaxSeeds) ? "n_seeds must be 1 .. 1024" :
+                          (s->max_iterations < 1u || s->max_iterations >= (1u << 30)) ? "max_iterations must be 1 .. 2^30 - 1" :
+                          !positive(s->pos_tol) ? "pos_tol must be finite and positive" :
+                          !positive(s->rot_tol) ? "rot_tol must be finite and positive" :
+                          !positive(s->rot_weight) ? "rot_weight must be finite and positive" :
+                          !positive(s->damping) ? "damping must be finite and positive" :
+                          !positive(s->max_step) ? "max_step must be finite and positive" :
+                          (s->position_only != 0 && s->position_only != 1) ? "position_only must be 0 or 1" :
+                          (!seeds && (halton_skip > 1000000ull || halton_skip + s->n_seeds > 1000000ull)) ?
+                          "halton_skip + n_seeds must not exceed 1,000,000" :
+                          n_targets > (vmv::kMultiMaxConfigs - 1) / s->n_seeds ? "n_targets * n_seeds must be below 2^31" : nullptr;
+        if (err) return refuse(VMV_ERR_INVALID_ARGUMENT, err);
+        P.n_seeds = s->n_seeds, P.max_iterations = s->max_iterations;
+        P.pos_tol = s->pos_tol, P.rot_tol = s->rot_tol, P.rot_weight = s->position_only ? 0.0f : s->rot_weight;
+        P.damping = s->damping, P.max_step = s->max_step;
+        P.position_only = (uint32_t) s->position_only, P.seeds_shared = seeds ? 0u : 1u;
+        for (int j = 0; j < 16; ++j) P.lower[j] = kRobots[robot].lower[j], P.upper[j] = kRobots[robot].lower[j] + kRobots[robot].span[j];
         return VMV_OK;
     }
 
@@ -1791,6 +1859,7 @@ extern "C"
     {
         g_staging.release();
         release_witness_scratch();
+        release_ik_scratch();
         vmv::release_edge_scratch();  // (waits for the edge batches still in flight: hipFree synchronizes)
         vmv::release_multi_tables();
         return VMV_OK;
@@ -1864,6 +1933,60 @@ extern "C"
         if (!c.run) return c.rc;
         return clearance_staged(robot, q, c.n, clearance, grad, witness, [&](float *dq, float *dc, float *dg, uint32_t *dw)
                                 { return vmv_clearance_grad_batch_multi(robot, envs, offsets, n_envs, dq, dc, dg, dw, nullptr); });
+    }
+
+    // ---- end-effector Jacobian and inverse kinematics (include/vamp_mvt_amd.h: vmv_eefk_jacobian_batch, vmv_ik_batch) ----
+    int vmv_eefk_jacobian_batch(int robot, const float *d_q, size_t n, float *d_frames, float *d_jac, void *stream)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!d_q || !d_jac) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        if (n == 0) return VMV_OK;
+        return kLaunchers[robot]->eefk_jacobian(d_q, n, d_frames, d_jac, static_cast<hipStream_t>(stream));
+    }
+    int vmv_eefk_jacobian_batch_host(int robot, const float *q, size_t n, float *frames, float *jac)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!q || !jac) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), df = s.out(frames, frames ? n * 64 : 0), dj = s.out(jac, 6 * config_bytes(robot, n));
+        return s.run([&] { return vmv_eefk_jacobian_batch(robot, s.at<float>(dq), n, s.at<float>(df), s.at<float>(dj), nullptr); });
+    }
+    int vmv_ik_batch(int robot, const float *d_targets, size_t n_targets, const float *d_seeds, uint64_t halton_skip,
+                     const vmv_ik_settings *settings, float *d_q, float *d_err, uint32_t *d_status, void *stream)
+    {
+        vmv::IkParams P;
+        if (int rc = ik_checks(robot, d_targets, n_targets, d_seeds, halton_skip, settings, d_q, d_status, P); rc != VMV_OK) return rc;
+        if (n_targets == 0) return VMV_OK;
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const size_t n = n_targets * (size_t) P.n_seeds;
+        if (d_seeds) return kLaunchers[robot]->ik(P, d_targets, d_seeds, n, d_q, d_err, d_status, st);
+        IkSeedLease lease;
+        float *scratch = nullptr;
+        if (int rc = lease.acquire(st, robot, &scratch); rc != VMV_OK) return rc;
+        const size_t total = (size_t) P.n_seeds * (size_t) kRobots[robot].dimension;
+        hipLaunchKernelGGL(vmv::halton_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, scratch + 32, total,
+                           kRobots[robot].dimension, halton_skip, scratch, scratch + 16);
+        VMV_HIP(hipGetLastError());
+        return kLaunchers[robot]->ik(P, d_targets, scratch + 32, n, d_q, d_err, d_status, st);
+    }
+    int vmv_ik_batch_host(int robot, const float *targets, size_t n_targets, const float *seeds, uint64_t halton_skip,
+                          const vmv_ik_settings *settings, float *q, float *err, uint32_t *status)
+    {
+        vmv::IkParams P;
+        if (int rc = ik_checks(robot, targets, n_targets, seeds, halton_skip, settings, q, status, P); rc != VMV_OK) return rc;
+        if (n_targets == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        const size_t n = n_targets * (size_t) P.n_seeds;
+        Staged s;
+        const int dt = s.in(targets, n_targets * 64), ds = s.in(seeds, seeds ? config_bytes(robot, n) : 0), dq = s.out(q, config_bytes(robot, n)),
+                  de = s.out(err, err ? n * 8 : 0), dst = s.out(status, n * 4);
+        return s.run([&]
+                     {
+                         return vmv_ik_batch(robot, s.at<float>(dt), n_targets, s.at<float>(ds), halton_skip, settings, s.at<float>(dq),
+                                             s.at<float>(de), s.at<uint32_t>(dst), nullptr);
+                     });
     }
 
     // ---- multi-GPU sharding arithmetic (vamp_mvt_amd/sharding.py: shard_range) ----

@@ -55,6 +55,17 @@ namespace vmv
     };
     void release_multi_tables();
 
+    // vmv_ik_batch: the kernel's parameter block - vmv_ik_settings as checked by the API (rot_weight is 0 for a
+    // position-only call, so the rotation rows vanish), where the seeds lie, and the robot's bounds [lower, lower + span]
+    struct IkParams
+    {
+        uint32_t n_seeds, max_iterations;
+        float pos_tol, rot_tol, rot_weight, damping, max_step;
+        uint32_t position_only;
+        uint32_t seeds_shared;  // 1: d_seeds is [n_seeds][dim], the same seeds for every target (the Halton seeds)
+        float lower[16], upper[16];
+    };
+
     // status codes are the VMV_* values of include/vamp_mvt_amd.h
     struct RobotLaunchers
     {
@@ -95,6 +106,12 @@ namespace vmv
                               hipStream_t);
         int (*clearance_grad_multi)(const EnvLaunch *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
                                     float *d_out, float *d_grad, uint32_t *d_witness, hipStream_t);
+        // vmv_eefk_jacobian_batch: d_frames [n][16] as eefk's or nullptr, d_jac [n][6][dim]
+        int (*eefk_jacobian)(const float *d_q, size_t n, float *d_frames, float *d_jac, hipStream_t);
+        // vmv_ik_batch: n = n_targets * n_seeds lanes (below 2^31), lane i = target i / n_seeds from seed i (or seed
+        // i % n_seeds with seeds_shared); d_q [n][dim], d_err [n][2] or nullptr, d_status [n]
+        int (*ik)(const IkParams &, const float *d_targets, const float *d_seeds, size_t n, float *d_q, float *d_err,
+                  uint32_t *d_status, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

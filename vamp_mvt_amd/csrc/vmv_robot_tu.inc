@@ -1262,6 +1262,282 @@ namespace VMV_ROBOT_NS
     }
 
     // ---------------------------------------------------------------------------------------------------------
+    // vmv_eefk_jacobian_batch and vmv_ik_batch (include/vamp_mvt_amd.h, DESIGN.md 5k).  One lane = one configuration
+    // (one (target, seed) pair), workgroups of one wave, no LDS, no atomics; Robot::ee_frame_jac gives the frame and the
+    // tangents of its twelve entries.  A joint outside R::kEeJointMask (Baxter's other arm) has literal-zero tangents and
+    // is left out of every sum at compile time.  Both kernels are templates for their place in the code object, as the
+    // clearance kernels above.
+    // ---------------------------------------------------------------------------------------------------------
+    constexpr uint32_t kIkBlock = (uint32_t) kWave;
+    constexpr float kIkLambdaFactor = 4.0f, kIkLambdaFloor = 1e-5f, kIkLambdaCeil = 1e6f;  // tests/ik_serial.py states the same
+    __host__ __device__ constexpr bool ee_joint(const int j) { return ((R::kEeJointMask >> j) & 1u) != 0u; }
+
+    // The geometric Jacobian in the world frame from a frame f (ee_frame's layout: f[3 + 3 k + a] = R[a][k]) and its
+    // tangents: rows 0-2 dt/dq_j, rows 3-5 the angular velocity omega_j = vee(A), A = (dR/dq_j) R^T, every entry of A as
+    // ((a0 b0 + a1 b1) + a2 b2).
+    __device__ __forceinline__ void ee_jacobian(const float (&f)[12], const float (&df)[12][R::kDim], float (&J)[6][R::kDim])
+    {
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            if (ee_joint(j))
+            {
+                const auto A = [&](const int a, const int b)
+                { return ((df[3 + a][j] * f[3 + b]) + (df[6 + a][j] * f[6 + b])) + (df[9 + a][j] * f[9 + b]); };
+                J[0][j] = df[0][j], J[1][j] = df[1][j], J[2][j] = df[2][j];
+                J[3][j] = 0.5f * (A(2, 1) - A(1, 2));
+                J[4][j] = 0.5f * (A(0, 2) - A(2, 0));
+                J[5][j] = 0.5f * (A(1, 0) - A(0, 1));
+            }
+            else
+                J[0][j] = J[1][j] = J[2][j] = J[3][j] = J[4][j] = J[5][j] = 0.0f;
+        }
+    }
+
+    // frames [n][16] (nullptr: not wanted) exactly as eefk_batch_kernel writes them - the same primal operations on the
+    // same joints, so a non-finite joint gives that kernel's frame - and jac [n][6][dim]; a non-finite joint: 6 * dim NaNs
+    // (J + 0 = J, J + NaN = NaN, as the clearance gradient's).
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void eefk_jacobian_kernel(const float *__restrict__ q, const uint32_t n,
+                                                                     float *__restrict__ frames, float *__restrict__ jac)
+    {
+        const uint32_t i = blockIdx.x * kIkBlock + threadIdx.x;
+        if (i >= n) return;
+        float cfg[R::kDim], f[12], df[12][R::kDim], J[6][R::kDim];
+        bool finite = true;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            cfg[j] = q[(size_t) i * R::kDim + j];
+            finite = finite && __builtin_isfinite(cfg[j]);
+        }
+        R::ee_frame_jac(cfg, f, df);
+        ee_jacobian(f, df, J);
+        if (frames != nullptr)
+        {
+            float *o = frames + 16 * (size_t) i;
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+            {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) o[4 * r + k] = f[3 + 3 * k + r];
+                o[4 * r + 3] = f[r];
+            }
+            o[12] = o[13] = o[14] = 0.0f;
+            o[15] = 1.0f;
+        }
+        const float poison = finite ? 0.0f : __builtin_nanf("");
+        float *out = jac + (size_t) i * (6 * R::kDim);
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) out[r * R::kDim + j] = J[r][j] + poison;
+    }
+
+    // The pose error of frame f against the target T (both in ee_frame's layout): e[0..2] = t* - t; e_w = 1/2 sum_k R_k x
+    // R*_k over the three columns, |e_w| = sin(theta); where tr(R*^T R) <= 1 (theta >= 90 degrees) the weighted error
+    // carries e_w at unit length.  e[3..5] = w * e_w (rescaled); n_p = |e_p|, n_w = |e_w| unrescaled.  The quotient stands
+    // outside the select (DESIGN.md 5j: a quotient on one side of a select makes a conditional region).
+    __device__ __forceinline__ void ik_error(const float (&f)[12], const float (&T)[12], const float w, float (&e)[6], float &n_p,
+                                             float &n_w, float &tr)
+    {
+        e[0] = T[0] - f[0], e[1] = T[1] - f[1], e[2] = T[2] - f[2];
+        float cx[3], cy[3], cz[3], d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            const float a0 = f[3 + 3 * k], a1 = f[4 + 3 * k], a2 = f[5 + 3 * k];
+            const float b0 = T[3 + 3 * k], b1 = T[4 + 3 * k], b2 = T[5 + 3 * k];
+            cx[k] = (a1 * b2) - (a2 * b1), cy[k] = (a2 * b0) - (a0 * b2), cz[k] = (a0 * b1) - (a1 * b0);
+            d[k] = dot3(a0, a1, a2, b0, b1, b2);
+        }
+        const float wx = 0.5f * ((cx[0] + cx[1]) + cx[2]), wy = 0.5f * ((cy[0] + cy[1]) + cy[2]), wz = 0.5f * ((cz[0] + cz[1]) + cz[2]);
+        tr = (d[0] + d[1]) + d[2];
+        n_p = sqrtf(dot3(e[0], e[1], e[2], e[0], e[1], e[2]));
+        n_w = sqrtf(dot3(wx, wy, wz, wx, wy, wz));
+        const float s = w / ((tr <= 1.0f && n_w > 0.0f) ? n_w : 1.0f);
+        e[3] = s * wx, e[4] = s * wy, e[5] = s * wz;
+    }
+
+    // y = A^-1 b for the symmetric positive definite A = Jm Jm^T + lambda I (its lower triangle), by a Cholesky
+    // factorisation in registers: every loop has constant bounds and unrolls.  A pivot that rounding took to zero or below
+    // is raised to 1e-12 (lambda >= kIkLambdaFloor keeps it away from there but for rounding).
+    __device__ __forceinline__ void chol6_solve(const float (&A)[6][6], const float (&b)[6], float (&y)[6])
+    {
+        float L[6][6], inv[6], z[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j)
+            {
+                float s = A[i][j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+                if (i == j)
+                {
+                    L[i][i] = sqrtf(fmaxf(s, 1e-12f));
+                    inv[i] = 1.0f / L[i][i];
+                }
+                else
+                    L[i][j] = s * inv[j];
+            }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+        {
+            float s = b[i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) s -= L[i][k] * z[k];
+            z[i] = s * inv[i];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i)
+        {
+            float s = z[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) s -= L[k][i] * y[k];
+            y[i] = s * inv[i];
+        }
+    }
+
+    // vmv_ik_batch: Levenberg-Marquardt from one seed towards one target per lane (lane i: target i / n_seeds, seed i, or
+    // seed i % n_seeds of the shared Halton seeds).  The loop body is ONE evaluation of a candidate - the seed first, then
+    // q + step - followed by selects into the accepted state (q, the weighted Jacobian, the error, E, lambda): a rejected
+    // step keeps the old Jacobian in registers and nothing is evaluated twice.  There is no branch in the body but the
+    // wave-uniform exit, so the compiler has no conditional region to sink the tape into.  A joint that sits at a bound
+    // while the descent direction g = Jw^T e points outward is left out of the step (its column of Jw reads as zero), so
+    // the other joints are not asked to make up for a motion the clip will take away.  A lane's result depends on its own
+    // target, seed and settings alone.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void ik_kernel(const IkParams P, const float *__restrict__ targets,
+                                                          const float *__restrict__ seeds, const uint32_t n,
+                                                          float *__restrict__ q_out, float *__restrict__ err_out,
+                                                          uint32_t *__restrict__ status_out)
+    {
+        const uint32_t i = blockIdx.x * kIkBlock + threadIdx.x;
+        const bool in_range = i < n;
+        const uint32_t row = in_range ? i : 0u;  // (a lane past the end works on row 0 and writes nothing)
+        const float *const tp = targets + 16 * (size_t) (row / P.n_seeds);
+        const float *const sp = seeds + (size_t) (P.seeds_shared != 0u ? row % P.n_seeds : row) * R::kDim;
+        float T[12], cand[R::kDim];
+        bool finite = true;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                const float v = tp[4 * r + k];
+                finite = finite && __builtin_isfinite(v);
+                if (r < 3) T[k < 3 ? 3 + 3 * k + r : r] = v;
+            }
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            cand[j] = sp[j];
+            finite = finite && __builtin_isfinite(cand[j]);
+        }
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = finite ? T[k] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cand[j] = fminf(fmaxf(finite ? cand[j] : 0.0f, P.lower[j]), P.upper[j]);
+
+        float q[R::kDim], Jw[6][R::kDim], e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float E = __builtin_inff(), lam = P.damping, err_p = 0.0f, err_w = 0.0f;
+        bool done = !in_range || !finite, converged = false;
+        uint32_t evals = 0;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            q[j] = cand[j];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) Jw[r][j] = 0.0f;
+        }
+        for (uint32_t it = 0;; ++it)
+        {
+            // ---- one evaluation: the candidate's frame, Jacobian, error and E
+            float f[12], df[12][R::kDim], Jc[6][R::kDim], ec[6], n_p, n_w, tr;
+            R::ee_frame_jac(cand, f, df);
+            ee_jacobian(f, df, Jc);
+            ik_error(f, T, P.rot_weight, ec, n_p, n_w, tr);
+            const float Ec = 0.5f * (dot3(ec[0], ec[1], ec[2], ec[0], ec[1], ec[2]) + dot3(ec[3], ec[4], ec[5], ec[3], ec[4], ec[5]));
+            const bool first = it == 0u;  // the seed's evaluation is taken whatever it gives and leaves lambda alone
+            const bool take = !done && (first || Ec < E);
+            const bool ok = n_p <= P.pos_tol && (P.position_only != 0u || (tr > 1.0f && n_w <= P.rot_tol));
+            const float lam_next = take ? fmaxf(lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(lam * kIkLambdaFactor, kIkLambdaCeil);
+            lam = (done || first) ? lam : lam_next;
+            evals += (done || first) ? 0u : 1u;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+            {
+                q[j] = take ? cand[j] : q[j];
+                if (ee_joint(j))
+                {
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) Jw[r][j] = take ? Jc[r][j] : Jw[r][j];
+#pragma unroll
+                    for (int r = 3; r < 6; ++r) Jw[r][j] = take ? P.rot_weight * Jc[r][j] : Jw[r][j];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) e[r] = take ? ec[r] : e[r];
+            E = take ? Ec : E;
+            err_p = take ? n_p : err_p, err_w = take ? n_w : err_w;
+            converged = converged || (take && ok);
+            done = done || (take && ok);
+            if (it == P.max_iterations || !wave_any(!done)) break;
+
+            // ---- the step from the accepted state: A = Jm Jm^T + lambda I, A y = e, delta = Jm^T y
+            float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+                if (ee_joint(j))
+                {
+                    float g = Jw[0][j] * e[0];
+#pragma unroll
+                    for (int r = 1; r < 6; ++r) g += Jw[r][j] * e[r];
+                    const bool hold = (q[j] <= P.lower[j] && g < 0.0f) || (q[j] >= P.upper[j] && g > 0.0f);
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : Jw[r][j];
+                }
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b <= a; ++b)
+                {
+                    float s = a == b ? lam : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < R::kDim; ++j)
+                        if (ee_joint(j)) s += Jm[a][j] * Jm[b][j];
+                    A[a][b] = s;
+                }
+            chol6_solve(A, e, y);
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+            {
+                delta[j] = 0.0f;
+                if (ee_joint(j))
+                {
+                    float s = Jm[0][j] * y[0];
+#pragma unroll
+                    for (int r = 1; r < 6; ++r) s += Jm[r][j] * y[r];
+                    delta[j] = s;
+                    big = fmaxf(big, fabsf(s));
+                }
+            }
+            const float scale = P.max_step / fmaxf(big, P.max_step);  // 1 while the largest joint change is within max_step
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+                cand[j] = ee_joint(j) ? fminf(fmaxf(q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : q[j];
+        }
+        if (!in_range) return;
+        // invalid input: the seed as given, NaN errors, bit 30
+        const float poison = finite ? 0.0f : __builtin_nanf("");
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) q_out[(size_t) i * R::kDim + j] = finite ? q[j] : sp[j];
+        if (err_out != nullptr) err_out[2 * (size_t) i] = err_p + poison, err_out[2 * (size_t) i + 1] = err_w + poison;
+        status_out[i] = (converged ? 0x80000000u : 0u) | (finite ? 0u : 0x40000000u) | evals;
+    }
+
+    // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
     namespace
@@ -1978,6 +2254,29 @@ namespace VMV_ROBOT_NS
         {
             return launch_clearance_multi_both(envs, offsets, n_envs, d_q, d_out, d_grad, d_witness, stream);
         }
+        // vmv_eefk_jacobian_batch: d_frames may be nullptr
+        int launch_eefk_jacobian(const float *d_q, size_t n, float *d_frames, float *d_jac, hipStream_t stream)
+        {
+            constexpr size_t kSlice = (size_t{1} << 20) * kIkBlock;  // 2^20 workgroups per launch
+            for (size_t lo = 0; lo < n; lo += kSlice)
+            {
+                const uint32_t m = (uint32_t) (n - lo < kSlice ? n - lo : kSlice);
+                hipLaunchKernelGGL(eefk_jacobian_kernel<>, dim3((m + kIkBlock - 1u) / kIkBlock), dim3(kIkBlock), 0, stream,
+                                   d_q + lo * R::kDim, m, d_frames ? d_frames + 16 * lo : (float *) nullptr, d_jac + 6 * lo * R::kDim);
+            }
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+
+        // vmv_ik_batch: n = n_targets * n_seeds lanes, below 2^31 (the API checks); d_err may be nullptr
+        int launch_ik(const IkParams &P, const float *d_targets, const float *d_seeds, size_t n, float *d_q, float *d_err,
+                      uint32_t *d_status, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(ik_kernel<>, dim3((uint32_t) ((n + kIkBlock - 1u) / kIkBlock)), dim3(kIkBlock), 0, stream, P, d_targets,
+                               d_seeds, (uint32_t) n, d_q, d_err, d_status);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
     }  // namespace
 
 }  // namespace VMV_ROBOT_NS
@@ -1992,6 +2291,7 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::R::kNSelfPairs,
                                                     VMV_ROBOT_NS::launch_clearance, VMV_ROBOT_NS::launch_clearance_multi,
                                                     VMV_ROBOT_NS::launch_clearance_grad,
-                                                    VMV_ROBOT_NS::launch_clearance_grad_multi};
+                                                    VMV_ROBOT_NS::launch_clearance_grad_multi,
+                                                    VMV_ROBOT_NS::launch_eefk_jacobian, VMV_ROBOT_NS::launch_ik};
 #endif
 }  // namespace vmv

@@ -758,6 +758,40 @@ def push_out(robot, configurations, environment=None, margin=0.01, max_steps=32,
     return PushOut(best_q, best_v, reached, calls)
 
 
+def ik_goals(robot, targets, envs, settings=None, dedup=1e-2):
+    """Goal sets for `rrtc_multi_goals` from end-effector targets: targets [P][4][4] frames as `robot.eefk_batch` returns
+    them, target p to be reached in envs[p] (an Environment or None; a single environment is broadcast to all targets).
+    -> (goal_sets, empty): goal_sets[p] a float32 [G_p][dim] array of collision-free IK solutions of target p, exactly what
+    `rrtc_multi_goals` takes; empty = the indices of the targets left with no goal (G_p = 0), which `rrtc_multi_goals`
+    refuses - leave those problems out.
+
+    ONE `robot.ik_batch` call (Halton seeds, `settings` = IKSettings), ONE `robot.validate_batch_multi` call over all
+    converged rows with target p's rows checked in envs[p], then on the host, per target in seed order, a solution within
+    `dedup` (L-infinity, radians; metres for a prismatic joint) of an earlier kept one of the same target is dropped.  No
+    checking of the way to a goal: that is the planner's part."""
+    targets = np.asarray(targets, np.float32)
+    if targets.ndim < 2 or int(np.prod(targets.shape[1:])) != 16:
+        raise TypeError("expected targets as [P][4][4] (or [P][16]) frames")
+    n = len(targets)
+    environments = list(envs) if isinstance(envs, (list, tuple)) else [envs] * n
+    if len(environments) != n:
+        raise ValueError(f"{n} targets, but {len(environments)} environments")
+    q, _, converged, _ = robot.ik_batch(targets, settings=settings)
+    q, converged = np.asarray(q, np.float32), np.asarray(converged, bool)
+    counts = converged.sum(axis=1).astype(np.int64)
+    rows = q[converged]  # target by target, in seed order
+    valid = np.asarray(robot.validate_batch_multi(rows, environments, counts), bool) if len(rows) else np.zeros(0, bool)
+    goal_sets, at = [], 0
+    for p in range(n):
+        kept = []
+        for g, ok in zip(rows[at:at + counts[p]], valid[at:at + counts[p]]):
+            if ok and all(np.abs(g - h).max() > dedup for h in kept):
+                kept.append(g)
+        at += int(counts[p])
+        goal_sets.append(np.array(kept, np.float32).reshape(len(kept), q.shape[2]))
+    return goal_sets, [p for p in range(n) if len(goal_sets[p]) == 0]
+
+
 @dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
