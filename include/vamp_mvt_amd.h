@@ -680,6 +680,90 @@ int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterati
 int vmv_paths_points(const vmv_paths *paths, float *out, size_t capacity_floats);
 int vmv_paths_destroy(vmv_paths *paths);
 
+/* ---- clearance-aware path optimisation: many independent paths in one call ------------------ */
+/* A covariant gradient iteration (CHOMP's update; its velocity-projection / curvature terms are LEFT OUT) on the
+ * waypoints of n_paths paths at once, the arguments those of vmv_simplify_multi: path p is points[offsets[p] ..
+ * offsets[p + 1]) in envs[p].  A path of N waypoints keeps its ends x_0, x_{N-1} (their bits are untouched) and N; its
+ * n = N - 2 inner waypoints move.  No counterpart in the reference.
+ *
+ * Cost of an iterate X, fp32:   U = sum over i = 0 .. N-2, ascending from 0.0f, of t_i,
+ *     t_i = w_smooth * (0.5f * s_i) + o_i,   s_i = sum over joints j, ascending from 0.0f, of (x_{i+1,j} - x_{i,j})^2,
+ *     o_0 = 0,   o_i = w_env * c(env_i; env_margin) + w_self * c(self_i; self_margin) for i >= 1,
+ * (env_i, self_i) the two values of vmv_clearance_grad_batch_multi at x_i, c CHOMP's hinge:
+ *     c(v; e) = (0 - v) + 0.5f * e for v < 0;  ((v - e) * (v - e)) / (2.0f * e) for 0 <= v <= e;  0 above (+inf, NaN: 0).
+ * Gradient at an inner waypoint, per joint, with g^env_i, g^self_i the two gradient rows of that call (the witness held
+ * fixed) and c'(v; e) = -1 for v < 0, (v - e) / e for 0 <= v <= e, 0 above:
+ *     G_ij = ((w_smooth * (((2.0f * x_ij) - x_{i-1,j}) - x_{i+1,j})) + (w_env * c'(env_i)) * g^env_ij) + (w_self * c'(self_i)) * g^self_ij.
+ * Step: per joint column solve A z = G, A the n x n tridiagonal (-1, 2, -1), by the Thomas recurrence on reciprocals
+ * r_0 = 0.5f, r_i = 1.0f / (2.0f - r_{i-1}) (computed on the host; IEEE division):
+ *     d_0 = G_0, d_i = G_i + r_{i-1} * d_{i-1};   z_{n-1} = d_{n-1} * r_{n-1}, z_i = (d_i + z_{i+1}) * r_i;
+ * D = (0 - step) * z;  m = the largest |D_ij| over the whole path (NaN ignored);  scale = max_step / max(m, max_step);
+ * x_ij <- clip(x_ij + D_ij * scale) to [lower, lower + span] of vmv_robot_bounds.  The step's size is m * scale.
+ * Every operation above is one fp32 operation with one rounding (no contraction), so a path's result depends on its own
+ * waypoints, its environment and the settings other than validate_every's effect described below - not on the batch, on
+ * the path's place in it, or on the other paths.  tests/optimize_serial.py states the same in numpy float32.
+ *
+ * Lockstep: all paths share the iteration counter k.  Per iteration ONE vmv_clearance_grad_batch_multi call (d_witness
+ * NULL) for the waypoints of all unfinished paths and one step kernel.  Iterates k = 0, v, 2v, ... and k = max_iterations
+ * (v = validate_every) are VALIDATED: their N - 1 consecutive edges go through ONE vmv_validate_motion_batch_multi call for
+ * all unfinished paths, and an accept kernel keeps a path's BEST: the validated iterate with every edge valid and the
+ * smallest U, the first such iterate among equal costs.  A path ends at the first validated iterate k > 0 whose step
+ * into it was smaller than min_change, or at k = max_iterations.  The host looks at the finished flags only at
+ * validated iterates and compacts the list of unfinished paths there; between two looks nothing synchronises.
+ * validate_every therefore chooses WHICH iterates can be returned and where a path can end; the iterates themselves do
+ * not depend on it.
+ *
+ * Result per path: the best iterate's waypoints; status VMV_OPT_OK (a valid iterate is returned), VMV_OPT_NO_VALID (no
+ * validated iterate was valid: the input comes back bit for bit) or VMV_OPT_NONFINITE (a non-finite waypoint: the input
+ * comes back and no question is asked); iterations run; best_iteration (0 without a best); U of iterate 0 and of the
+ * best; the smallest env and self over all N waypoints (-0 below +0, NaN ignored, +inf without a finite value) of
+ * iterate 0 and of the best (without a best: iterate 0's figures twice).  Paths of fewer than 3 waypoints come back as
+ * they are with 0 iterations, costs 0 and NaN clearances (no clearance question); a finite path of 2 waypoints has its one
+ * edge validated: VMV_OPT_OK or VMV_OPT_NO_VALID.  Consequence: a path whose input is valid edge by edge comes back
+ * valid edge by edge with cost <= cost_first.  The clearances are those of the WAYPOINTS, validity is
+ * vmv_validate_motion_batch's on the consecutive edges, the gradient is the current witness's.
+ *
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL envs / points / offsets / settings /
+ * out, n_paths >= 2^31, max_waypoints above 1,024, offsets not starting at 0 or decreasing, a path longer than
+ * max_waypoints, a NULL handle, step / max_step / env_margin / self_margin not finite or not positive, a weight negative
+ * or not finite, min_change NaN, validate_every == 0, offsets[n_paths] >= 2^31 (all VMV_ERR_INVALID_ARGUMENT); an
+ * environment holding a point cloud or an attachment, refused as vmv_clearance_batch_multi refuses it
+ * (VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the kind and the index; before the finalized check); an unfinalized
+ * environment (VMV_ERR_NOT_FINALIZED); an environment of another device (VMV_ERR_INVALID_ARGUMENT).  A call that fails
+ * leaves *out untouched.  n_paths == 0 is VMV_OK with an empty result.  Environments not yet prepared for the robot are
+ * prepared in one batch.  Synchronous, host buffers, on the default stream; repeated handles are allowed.
+ * Device memory per call: 4 copies of the waypoints, their clearances [2] and gradients [2][dim], the edges twice. */
+enum
+{
+    VMV_OPT_OK = 0,
+    VMV_OPT_NO_VALID = 1,
+    VMV_OPT_NONFINITE = 2
+};
+typedef struct
+{
+    uint32_t max_iterations; /* 0 = default (64) */
+    uint32_t validate_every; /* iterations between two validated iterates; must not be 0 (the study's default: 8) */
+    float step;              /* > 0 (1/40) */
+    float max_step;          /* > 0: cap on the largest joint change of one iteration over the whole path (0.1) */
+    float min_change;        /* a path ends once a step is smaller than this (1e-4); <= 0: only max_iterations ends it */
+    float smooth_weight, env_weight, self_weight; /* >= 0 (1, 1, 1) */
+    float env_margin, self_margin;                /* > 0, metres (0.05, 0.01) */
+    uint32_t max_waypoints;  /* cap on a path's waypoints, at most 1,024; 0 = default (1,024) */
+} vmv_optimize_settings;
+typedef struct vmv_optimized vmv_optimized;
+int vmv_optimize_multi(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                       const vmv_optimize_settings *settings, vmv_optimized **out);
+/* Per path (arrays of n_paths, any may be NULL): status (VMV_OPT_*), iterations, best_iteration, cost_first, cost,
+ * clearance_first [n][2] and clearance [n][2] (env, self).  Totals (may be NULL): the clearance-gradient calls and the
+ * validation calls the whole call made. */
+int vmv_optimized_summary(const vmv_optimized *result, uint8_t *status, uint32_t *iterations, uint32_t *best_iteration,
+                          float *cost_first, float *cost, float *clearance_first, float *clearance,
+                          uint64_t *clearance_calls, uint64_t *validation_calls);
+/* every path's waypoints, packed in path order with the input's offsets; VMV_ERR_CAPACITY if capacity_floats is too
+ * small (nothing is written) */
+int vmv_optimized_points(const vmv_optimized *result, float *out, size_t capacity_floats);
+int vmv_optimized_destroy(vmv_optimized *result);
+
 /* ---- lockstep AORRTC: cost-bounded RRT-Connect searches for many independent problems --------------------- */
 /* AORRTC (planning/aorrtc.hh, one goal, PHS sampling, no dynamic domain) for n_problems problems at once; the arguments
  * are those of vmv_rrtc_multi.  Per problem:

@@ -567,6 +567,31 @@ def _simplify_settings_struct(settings, longest=0):
                                float(settings.midpoint_interpolation), max_wp, w, every)
 
 
+def _optimize_settings_struct(settings, longest=0):
+    """vmv_optimize_settings from an OptimizeMultiSettings-shaped object, checked as the library checks it; longest: the
+    longest input path in waypoints"""
+    max_it, every, max_wp = int(settings.max_iterations), int(settings.validate_every), int(settings.max_waypoints)
+    if not (0 < max_it < 2 ** 32 and 0 < every < 2 ** 32):
+        raise ValueError("max_iterations and validate_every must be positive and fit 32 bits")
+    if not 0 < max_wp <= 1024:
+        raise ValueError("max_waypoints must be between 1 and 1,024")
+    if longest > max_wp:
+        raise ValueError(f"max_waypoints is below the longest path ({longest} waypoints)")
+    positive = {k: float(getattr(settings, k)) for k in ("step", "max_step", "env_margin", "self_margin")}
+    weights = {k: float(getattr(settings, k)) for k in ("smooth_weight", "env_weight", "self_weight")}
+    for k, v in positive.items():
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{k} must be positive and finite")
+    for k, v in weights.items():
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{k} must be finite and not negative")
+    if np.isnan(float(settings.min_change)):
+        raise ValueError("min_change must not be NaN")
+    return _lib.OptimizeSettings(max_it, every, positive["step"], positive["max_step"], float(settings.min_change),
+                                 weights["smooth_weight"], weights["env_weight"], weights["self_weight"],
+                                 positive["env_margin"], positive["self_margin"], max_wp)
+
+
 class IKSettings:
     """vmv_ik_settings (include/vamp_mvt_amd.h) with the defaults of <robot>.ik_batch: n_seeds seeds per target (1 ..
     1,024), max_iterations, pos_tol (m), rot_tol (rad; the sine of the residual angle is compared), rot_weight (metres per
@@ -1409,6 +1434,53 @@ class _Robot(types.ModuleType):
             lib.vmv_paths_destroy(out)
         return dict(status=status, iterations=iterations, lengths=lengths, questions=questions, points=points,
                     rounds=int(rounds.value), total_questions=int(total.value))
+
+    def optimize_multi_raw(self, paths, environments, settings):
+        """vmv_optimize_multi: the clearance-aware covariant gradient iteration for many paths in lockstep, path p
+        ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).  settings: max_iterations,
+        validate_every, step, max_step, min_change, smooth_weight, env_weight, self_weight, env_margin, self_margin,
+        max_waypoints.  -> dict of per-path numpy arrays (status, iterations, best_iteration, cost_first, cost,
+        clearance_first [n][2], clearance [n][2]), the packed waypoints (points, the input's layout) and the totals
+        clearance_calls and validation_calls.  planning.optimize_multi is the caller-facing form.  Every argument is
+        checked before any library call."""
+        environments = list(environments)
+        _check_environments(environments)
+        pts = []
+        for p in paths:
+            a = np.asarray(p, dtype=np.float32)
+            if a.size == 0:
+                a = np.zeros((0, self._dim), np.float32)
+            if a.ndim != 2 or a.shape[1] != self._dim:
+                raise TypeError(f"expected every path as [len][{self._dim}] waypoints")
+            pts.append(a)
+        n = len(pts)
+        if len(environments) != n:
+            raise ValueError(f"expected one environment per path, got {len(environments)} for {n} paths")
+        cs = _optimize_settings_struct(settings, max((len(a) for a in pts), default=0))
+        offsets = np.zeros(n + 1, np.uintp)
+        offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
+        packed = np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, self._dim), np.float32)]))
+        status, iterations, best = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        cost_first, cost = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        clr_first, clr = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        points = np.zeros_like(packed)
+        calls, validations = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if n > 0:
+            envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+            out = ctypes.c_void_p()
+            check(lib.vmv_optimize_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                         ctypes.byref(cs), ctypes.byref(out)), "vmv_optimize_multi")
+            try:
+                check(lib.vmv_optimized_summary(out, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                iterations.ctypes.data_as(_lib.c_u32_p), best.ctypes.data_as(_lib.c_u32_p),
+                                                _fp(cost_first), _fp(cost), _fp(clr_first), _fp(clr), ctypes.byref(calls),
+                                                ctypes.byref(validations)), "vmv_optimized_summary")
+                check(lib.vmv_optimized_points(out, _fp(points), points.size), "vmv_optimized_points")
+            finally:
+                lib.vmv_optimized_destroy(out)
+        return dict(status=status, iterations=iterations, best_iteration=best, cost_first=cost_first, cost=cost,
+                    clearance_first=clr_first, clearance=clr, points=points, offsets=offsets.astype(np.int64),
+                    clearance_calls=int(calls.value), validation_calls=int(validations.value))
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

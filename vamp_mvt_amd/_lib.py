@@ -66,6 +66,14 @@ class SimplifySettings(ctypes.Structure):
                 ("max_waypoints", ctypes.c_uint32), ("questions_per_round", ctypes.c_uint32), ("check_every", ctypes.c_uint32)]
 
 
+class OptimizeSettings(ctypes.Structure):
+    """vmv_optimize_settings"""
+    _fields_ = [("max_iterations", ctypes.c_uint32), ("validate_every", ctypes.c_uint32), ("step", ctypes.c_float),
+                ("max_step", ctypes.c_float), ("min_change", ctypes.c_float), ("smooth_weight", ctypes.c_float),
+                ("env_weight", ctypes.c_float), ("self_weight", ctypes.c_float), ("env_margin", ctypes.c_float),
+                ("self_margin", ctypes.c_float), ("max_waypoints", ctypes.c_uint32)]
+
+
 class AorrtcSettings(ctypes.Structure):
     """vmv_aorrtc_settings"""
     _fields_ = [("rrtc", RrtcSettings), ("simplify", SimplifySettings), ("optimize", ctypes.c_int),
@@ -221,6 +229,12 @@ def _load():
         "vmv_paths_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_paths_points": (I, [V, c_float_p, S]),
         "vmv_paths_destroy": (I, [V]),
+        "vmv_optimize_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(OptimizeSettings),
+                                   ctypes.POINTER(V)]),
+        "vmv_optimized_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_float_p, c_float_p, c_float_p,
+                                      c_float_p, c_u64_p, c_u64_p]),
+        "vmv_optimized_points": (I, [V, c_float_p, S]),
+        "vmv_optimized_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

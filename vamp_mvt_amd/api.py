@@ -506,6 +506,13 @@ def install(robot):
             out.append(res)
         return out
 
+    def optimize_multi(paths, environments, settings=None, resolution=None):
+        """planning.optimize_multi with this robot: the clearance-aware covariant gradient iteration for many paths in
+        lockstep on the device -> list[planning.OptimizedPath].  The clearances are those of the waypoints, validity is
+        validate_motion's on the consecutive edges, the gradient is the current witness's."""
+        return planning.optimize_multi(robot, paths, environments, settings, resolution)
+
+    robot.optimize_multi = optimize_multi
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals

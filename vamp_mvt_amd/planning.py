@@ -758,6 +758,108 @@ def push_out(robot, configurations, environment=None, margin=0.01, max_steps=32,
     return PushOut(best_q, best_v, reached, calls)
 
 
+OPTIMIZE_STATUS = ("ok", "no_valid", "nonfinite")  # VMV_OPT_*
+
+
+@dataclass
+class OptimizeMultiSettings:
+    """vmv_optimize_settings with the defaults of the float64 study: max_iterations, validate_every
+    (iterations between two validated iterates), step, max_step (the largest joint change of one iteration over the whole
+    path), min_change (a path ends once a step is smaller), the three weights, the two margins in metres, and
+    max_waypoints (at most 1,024)"""
+    max_iterations: int = 64
+    validate_every: int = 8
+    step: float = 1.0 / 40.0
+    max_step: float = 0.1
+    min_change: float = 1e-4
+    smooth_weight: float = 1.0
+    env_weight: float = 1.0
+    self_weight: float = 1.0
+    env_margin: float = 0.05
+    self_margin: float = 0.01
+    max_waypoints: int = 1024
+
+
+@dataclass
+class OptimizedPath:
+    """optimize_multi's answer for one path: the waypoints, `status` (one of OPTIMIZE_STATUS), the iterations run, the
+    iteration the returned iterate is from, the cost U of the input and of the returned iterate, and the smallest
+    (env, self) clearance over the WAYPOINTS of the input and of the returned iterate"""
+    path: list
+    status: str
+    iterations: int
+    best_iteration: int
+    cost_first: float
+    cost: float
+    clearance_first: tuple
+    clearance: tuple
+
+
+def densify_path(path, resolution):
+    """path_samples' rule with the duplicated inner waypoints dropped: segment (a, b) becomes a + (b - a) * k / m, k = 0..m,
+    m = max(1, ceil(|b - a| * resolution)), in float64 cast to fp32 - except that every former waypoint is copied, not
+    computed, so its bits are the input's.  -> float32 [n][dim]; a path of fewer than 2 waypoints comes back as it is."""
+    p32 = np.asarray(path, np.float32)
+    if p32.ndim != 2:
+        raise TypeError("expected a [len][dim] path")
+    if len(p32) < 2:
+        return p32.copy()
+    p = p32.astype(np.float64)
+    out = [p32[:1]]
+    for i in range(len(p) - 1):
+        a, b = p[i], p[i + 1]
+        m = max(1, int(np.ceil(np.sqrt(((b - a) ** 2).sum()) * resolution)))
+        seg = (a[None, :] + (b - a)[None, :] * (np.arange(1, m + 1) / m)[:, None]).astype(np.float32)
+        seg[-1] = p32[i + 1]
+        out.append(seg)
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def optimize_multi(robot, paths, environments, settings=None, resolution=None):
+    """Moves the inner waypoints of many independent paths away from contact, on the device: paths[p] ([len][dim]) in
+    environments[p] (None = the empty environment) -> list[OptimizedPath].  A covariant gradient iteration (CHOMP's
+    update without its velocity-projection terms) on the cost U = smoothness + hinge(env clearance; env_margin) +
+    hinge(self clearance; self_margin) summed over the inner waypoints; include/vamp_mvt_amd.h (vmv_optimize_multi) and
+    DESIGN §5l give every operation.  All paths advance in lockstep: ONE clearance_grad_batch_multi call and one step
+    kernel per iteration, ONE validate_motion_batch_multi call per validated iterate (every validate_every iterations and
+    the last).  What comes back per path is the cheapest validated iterate whose consecutive edges are all valid, so a
+    valid input gives a valid output with cost <= cost_first; status "no_valid" and "nonfinite" return the input.
+
+    resolution=None optimises the waypoints as given (the call never adds or removes one).  A number densifies every path
+    first with densify_path (the former waypoints stay among the new ones); a densified path longer than
+    settings.max_waypoints raises ValueError naming the path.
+
+    What this is and is not: the clearance is that of the WAYPOINTS (clearance / clearance_first are minima over them,
+    not over the motion between them); validity is validate_motion's on the consecutive edges; the gradient is the
+    current witness's, so a step may bring another contact closer, and the plain iteration does not decrease U
+    monotonically - which is why the best validated iterate is kept, not the last."""
+    s = settings if settings is not None else OptimizeMultiSettings()
+    dim = robot.dimension()
+    pts = []
+    for k, p in enumerate(paths):
+        a = np.asarray(p, np.float32)
+        if a.size == 0:
+            a = np.zeros((0, dim), np.float32)
+        if a.ndim != 2 or a.shape[1] != dim:
+            raise TypeError(f"expected every path as [len][{dim}] waypoints")
+        if resolution is not None:
+            a = densify_path(a, float(resolution))
+            if len(a) > int(s.max_waypoints):
+                raise ValueError(f"path {k} has {len(a)} waypoints at resolution {resolution}: more than max_waypoints "
+                                 f"({int(s.max_waypoints)})")
+        pts.append(a)
+    raw = robot.optimize_multi_raw(pts, environments, s)
+    off = raw["offsets"]
+    out = []
+    for p in range(len(pts)):
+        out.append(OptimizedPath(path=[q.copy() for q in raw["points"][off[p]:off[p + 1]]],
+                                 status=OPTIMIZE_STATUS[int(raw["status"][p])], iterations=int(raw["iterations"][p]),
+                                 best_iteration=int(raw["best_iteration"][p]), cost_first=float(raw["cost_first"][p]),
+                                 cost=float(raw["cost"][p]), clearance_first=tuple(float(v) for v in raw["clearance_first"][p]),
+                                 clearance=tuple(float(v) for v in raw["clearance"][p])))
+    return out
+
+
 def ik_goals(robot, targets, envs, settings=None, dedup=1e-2):
     """Goal sets for `rrtc_multi_goals` from end-effector targets: targets [P][4][4] frames as `robot.eefk_batch` returns
     them, target p to be reached in envs[p] (an Environment or None; a single environment is broadcast to all targets).
