@@ -64,6 +64,11 @@ def _fp(a):
     return a.ctypes.data_as(_lib.c_float_p)
 
 
+def _ptr(a, pointer_type):
+    """an optional array as the library takes it: NULL for None"""
+    return None if a is None else a.ctypes.data_as(pointer_type)
+
+
 _SIMPLIFY_OPS = {"BSPLINE": 0, "SHORTCUT": 2}  # VMV_SIMPLIFY_*: the routines vmv_simplify_multi runs
 
 
@@ -531,6 +536,120 @@ def _segments(environments, counts):
     return environments, np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint64)
 
 
+# the planner wrappers (<robot>.*_raw) are composed from the helpers below: one copy of every shared check and of the readout
+def _endpoints(dim, starts, goals):
+    """starts and goals as two float32 [n][dim] arrays -> (starts, goals, n)"""
+    a, b = _f32(starts), _f32(goals)
+    if a.ndim != 2 or a.shape[1] != dim or a.shape != b.shape:
+        raise TypeError(f"expected two [n][{dim}] arrays")
+    return a, b, a.shape[0]
+
+
+def _one_per(environments, n, what):
+    """one environment per `what` ("problem", "path")"""
+    if len(environments) != n:
+        raise ValueError(f"expected one environment per {what}, got {len(environments)} for {n} {what}s")
+
+
+def _skips(skips, n, what, draws=None):
+    """one Halton skip per `what` ("problem", "roadmap") -> uint64[n], None for None; draws: the samples a call takes
+    from the sequence, where it is held to the sequence's validity limit"""
+    if skips is None:
+        return None
+    sk = np.asarray(skips)
+    if sk.shape != (n,):
+        raise ValueError(f"expected one skip per {what}, got shape {sk.shape} for {n} {what}s")
+    if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
+        raise ValueError("skips must be non-negative integers")
+    if draws is not None and sk.size and int(sk.max()) + draws > 1000000:
+        raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
+    return np.ascontiguousarray(sk, np.uint64)
+
+
+def _samples(samples, n, ns, dim):
+    """the caller's samples, [ns][dim] for all or [n][ns][dim] -> float32 [n][ns][dim], None for None"""
+    if samples is None:
+        return None
+    sm = _f32(samples)
+    if sm.shape == (ns, dim):
+        sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, dim)))
+    if sm.shape != (n, ns, dim):
+        raise TypeError(f"expected samples as [{ns}][{dim}] or [{n}][{ns}][{dim}]")
+    return sm
+
+
+def _rrtc_settings_struct(settings, also=()):
+    """vmv_rrtc_settings from an RRTCMultiSettings-shaped object, checked as rrtc_multi_raw documents; also: further
+    fields of the settings that must fit 32 bits, named in the same refusal"""
+    rng, ratio = float(settings.range), float(settings.tree_ratio)
+    max_it, max_s, every = int(settings.max_iterations), int(settings.max_samples), int(getattr(settings, "check_every", 0))
+    if not (math.isfinite(rng) and rng > 0):
+        raise ValueError("range must be finite and positive")
+    if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32 and
+            all(0 <= int(getattr(settings, k)) < 2 ** 32 for k in also)):
+        raise ValueError("max_iterations, max_samples (>= 2)" + "".join(f", {k}" for k in also) +
+                         " and check_every must fit 32 bits")
+    return _lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every)
+
+
+def _cut_radius(settings):
+    """-> the radius beyond which no neighbour is taken, checked"""
+    radius = float(settings.radius)
+    if not radius > 0:
+        raise ValueError("radius must be positive (inf = no cut)")
+    return radius
+
+
+def _roadmap_sampling(settings):
+    """-> (n_samples, k, radius) of a PRMMultiSettings- or RoadmapsSettings-shaped object, checked"""
+    ns, k = int(settings.n_samples), int(settings.k)
+    if ns % 64 != 0 or not 64 <= ns <= 8128:
+        raise ValueError("n_samples must be a multiple of 64 from 64 to 8,128")
+    if not 1 <= k <= 16:
+        raise ValueError("k must be from 1 to 16")
+    return ns, k, _cut_radius(settings)
+
+
+def _waypoints(path, dim):
+    """one path -> float32 [len][dim] (an empty path: [0][dim])"""
+    a = np.asarray(path, dtype=np.float32)
+    if a.size == 0:
+        a = np.zeros((0, dim), np.float32)
+    if a.ndim != 2 or a.shape[1] != dim:
+        raise TypeError(f"expected every path as [len][{dim}] waypoints")
+    return a
+
+
+def _packed_paths(paths, dim):
+    """-> (the paths as a list of float32 [len][dim] arrays, their waypoints packed, uintp[n + 1] offsets into those)"""
+    pts = [_waypoints(p, dim) for p in paths]
+    offsets = np.zeros(len(pts) + 1, np.uintp)
+    offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
+    return pts, np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, dim), np.float32)])), offsets
+
+
+def _read_plans(plans, n, dim, extra=None):
+    """What every vmv_plans handle of n problems answers -> dict(status, iterations, sizes [n][2], path_lengths, paths
+    [sum(path_lengths)][dim], rounds, questions); extra(plans, out) adds the call's own part while the handle lives.
+    Destroys the handle, whatever happens."""
+    try:
+        status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
+        rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (iterations, sizes, lengths)]
+        totals = [ctypes.byref(rounds), ctypes.byref(questions)]
+        check(lib.vmv_plans_summary(plans, status.ctypes.data_as(_lib.c_u8_p), *counts, *totals), "vmv_plans_summary")
+        paths = np.zeros((int(lengths.sum()), dim), np.float32)
+        check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        out = dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
+                   rounds=int(rounds.value), questions=int(questions.value))
+        if extra is not None:
+            extra(plans, out)
+    finally:
+        lib.vmv_plans_destroy(plans)
+    return out
+
+
 def _torch_unpack_bits(bits, n):
     """unpack_bits for a torch int64 tensor of validity words -> torch.bool[n] on the same device"""
     import torch
@@ -939,46 +1058,15 @@ class _Robot(types.ModuleType):
         before any library call."""
         environments = list(environments)
         _check_environments(environments)
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
-        if skips is None:
-            sk = None
-        else:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            sk = np.ascontiguousarray(sk, np.uint64)
-        rng, ratio = float(settings.range), float(settings.tree_ratio)
-        max_it, max_s, every = int(settings.max_iterations), int(settings.max_samples), int(getattr(settings, "check_every", 0))
-        if not (math.isfinite(rng) and rng > 0):
-            raise ValueError("range must be finite and positive")
-        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32):
-            raise ValueError("max_iterations, max_samples (>= 2) and check_every must fit 32 bits")
-        cs = _lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every)
+        a, b, n = _endpoints(self._dim, starts, goals)
+        _one_per(environments, n, "problem")
+        sk = _skips(skips, n, "problem")
+        cs = _rrtc_settings_struct(settings)
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_rrtc_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
-                                 ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
-                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
-                  "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
-                    rounds=int(rounds.value), questions=int(questions.value))
+        check(lib.vmv_rrtc_multi(self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), ctypes.byref(cs),
+                                 ctypes.byref(plans)), "vmv_rrtc_multi")
+        return _read_plans(plans, n, self._dim)
 
     def rrtc_multi_goals_raw(self, starts, goals, goal_counts, environments, settings, skips=None):
         """vmv_rrtc_multi_goals: rrtc_multi_raw with goal sets, dynamic domain and start_tree_first.  goals: the goals of
@@ -1006,24 +1094,10 @@ class _Robot(types.ModuleType):
             np.cumsum(counts, out=offsets[1:])
             if int(offsets[n]) != b.shape[0]:
                 raise TypeError(f"expected {int(offsets[n])} packed goals, got {b.shape[0]}")
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
-        if skips is None:
-            sk = None
-        else:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            sk = np.ascontiguousarray(sk, np.uint64)
-        rng, ratio = float(settings.range), float(settings.tree_ratio)
-        max_it, max_s, every = int(settings.max_iterations), int(settings.max_samples), int(getattr(settings, "check_every", 0))
-        if not (math.isfinite(rng) and rng > 0):
-            raise ValueError("range must be finite and positive")
-        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32):
-            raise ValueError("max_iterations, max_samples (>= 2) and check_every must fit 32 bits")
-        if offsets is not None and n and int(np.diff(offsets).max()) + 1 > max_s:
+        _one_per(environments, n, "problem")
+        sk = _skips(skips, n, "problem")
+        base = _rrtc_settings_struct(settings)
+        if offsets is not None and n and int(np.diff(offsets).max()) + 1 > base.max_samples:
             raise ValueError("the start and the goals of a problem must fit max_samples")
         dynamic = bool(getattr(settings, "dynamic_domain", False))
         radius, alpha = float(getattr(settings, "radius", 4.0)), float(getattr(settings, "alpha", 0.0001))
@@ -1033,30 +1107,19 @@ class _Robot(types.ModuleType):
                 raise ValueError("radius and min_radius must be finite and positive")
             if not (math.isfinite(alpha) and 0 <= alpha < 1):
                 raise ValueError("alpha must be in [0, 1)")
-        cs = _lib.RrtcGoalsSettings(_lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every), int(dynamic),
-                                    radius, alpha, min_radius, int(bool(getattr(settings, "start_tree_first", False))))
+        cs = _lib.RrtcGoalsSettings(base, int(dynamic), radius, alpha, min_radius,
+                                    int(bool(getattr(settings, "start_tree_first", False))))
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_rrtc_multi_goals(self._id, handles, n, _fp(a), _fp(b),
-                                       None if offsets is None else offsets.ctypes.data_as(_lib.c_size_p),
-                                       None if sk is None else sk.ctypes.data_as(_lib.c_u64_p), ctypes.byref(cs),
-                                       ctypes.byref(plans)), "vmv_rrtc_multi_goals")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
-                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
-                  "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
-            goal_indices = np.zeros(n, np.uint32)
-            check(lib.vmv_plans_goal_indices(plans, goal_indices.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_goal_indices")
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
-                    rounds=int(rounds.value), questions=int(questions.value), goal_indices=goal_indices.view(np.int32).copy())
+        check(lib.vmv_rrtc_multi_goals(self._id, handles, n, _fp(a), _fp(b), _ptr(offsets, _lib.c_size_p),
+                                       _ptr(sk, _lib.c_u64_p), ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi_goals")
+
+        def goal_indices(plans, out):
+            indices = np.zeros(n, np.uint32)
+            check(lib.vmv_plans_goal_indices(plans, indices.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_goal_indices")
+            out["goal_indices"] = indices.view(np.int32).copy()
+
+        return _read_plans(plans, n, self._dim, goal_indices)
 
     def aorrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
         """vmv_aorrtc_multi: AORRTC for many problems (a first solution by rrtc_multi's contract, simplified by
@@ -1067,60 +1130,31 @@ class _Robot(types.ModuleType):
         problem.  planning.aorrtc_multi is the caller-facing form.  Every argument is checked before any library call."""
         environments = list(environments)
         _check_environments(environments)
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
-        if skips is None:
-            sk = None
-        else:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            sk = np.ascontiguousarray(sk, np.uint64)
-        rng, ratio = float(settings.range), float(settings.tree_ratio)
-        max_it, max_in, max_s = int(settings.max_iterations), int(settings.max_internal_iterations), int(settings.max_samples)
-        resamples, searches = int(settings.max_cost_bound_resamples), int(settings.max_searches)
-        every = int(getattr(settings, "check_every", 0))
-        if not (math.isfinite(rng) and rng > 0):
-            raise ValueError("range must be finite and positive")
-        if not (0 <= max_it < 2 ** 32 and 2 <= max_s < 2 ** 32 and 0 <= every < 2 ** 32 and 0 <= searches < 2 ** 32):
-            raise ValueError("max_iterations, max_samples (>= 2), max_searches and check_every must fit 32 bits")
+        a, b, n = _endpoints(self._dim, starts, goals)
+        _one_per(environments, n, "problem")
+        sk = _skips(skips, n, "problem")
+        max_in, resamples = int(settings.max_internal_iterations), int(settings.max_cost_bound_resamples)
+        base = _rrtc_settings_struct(settings, also=("max_searches",))
         if not 1 <= max_in < 2 ** 32:
             raise ValueError("max_internal_iterations must be positive and fit 32 bits")
         if not 0 <= resamples <= 64:
             raise ValueError("max_cost_bound_resamples must be from 0 to 64")
-        cs = _lib.AorrtcSettings(_lib.RrtcSettings(rng, int(bool(settings.balance)), ratio, max_it, max_s, every),
-                                 _simplify_settings_struct(settings.simplify), int(bool(settings.optimize)),
-                                 int(bool(settings.cost_bound_resample)), int(bool(settings.simplify_intermediate)), max_it,
-                                 max_in, max_s, resamples, searches)
+        cs = _lib.AorrtcSettings(base, _simplify_settings_struct(settings.simplify), int(bool(settings.optimize)),
+                                 int(bool(settings.cost_bound_resample)), int(bool(settings.simplify_intermediate)),
+                                 base.max_iterations, max_in, base.max_samples, resamples, int(settings.max_searches))
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_aorrtc_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
-                                   ctypes.byref(cs), ctypes.byref(plans)), "vmv_aorrtc_multi")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
-                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
-                  "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        check(lib.vmv_aorrtc_multi(self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), ctypes.byref(cs),
+                                   ctypes.byref(plans)), "vmv_aorrtc_multi")
+
+        def search_costs(plans, out):
             first, costs = np.zeros(n, np.float32), np.zeros(n, np.float32)
             n_searches, improvements = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
             check(lib.vmv_plans_costs(plans, _fp(first), _fp(costs), n_searches.ctypes.data_as(_lib.c_u32_p),
                                       improvements.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_costs")
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, first_costs=first,
-                    costs=costs, searches=n_searches, improvements=improvements, rounds=int(rounds.value),
-                    questions=int(questions.value))
+            out.update(first_costs=first, costs=costs, searches=n_searches, improvements=improvements)
+
+        return _read_plans(plans, n, self._dim, search_costs)
 
     def phs_samples(self, start, goal, max_cost, seed, counter, n):
         """vmv_phs_samples (test support): n successive samples of aorrtc_multi's device sampler for the foci start and
@@ -1129,7 +1163,7 @@ class _Robot(types.ModuleType):
         a, b = _f32(start, (self._dim,)), _f32(goal, (self._dim,))
         q, ok, c = np.zeros((int(n), self._dim), np.float32), np.zeros(int(n), np.uint8), ctypes.c_uint32(0)
         check(lib.vmv_phs_samples(self._id, _fp(a), _fp(b), float(max_cost), int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF,
-                                  int(n), _fp(q), ok.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(c)),
+                                  int(n), _fp(q), ok.ctypes.data_as(_lib.c_u8_p), ctypes.byref(c)),
               "vmv_phs_samples")
         return q, ok.astype(bool), int(c.value)
 
@@ -1144,73 +1178,39 @@ class _Robot(types.ModuleType):
         checked before any library call."""
         environments = list(environments)
         _check_environments(environments)
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
-        ns, k, radius = int(settings.n_samples), int(settings.k), float(settings.radius)
+        a, b, n = _endpoints(self._dim, starts, goals)
+        _one_per(environments, n, "problem")
+        ns, k, radius = _roadmap_sampling(settings)
         keep = bool(getattr(settings, "keep_roadmaps", False))
-        if ns % 64 != 0 or not 64 <= ns <= 8128:
-            raise ValueError("n_samples must be a multiple of 64 from 64 to 8,128")
-        if not 1 <= k <= 16:
-            raise ValueError("k must be from 1 to 16")
-        if not radius > 0:
-            raise ValueError("radius must be positive (inf = no cut)")
         if n * (ns + 2) * k >= 2 ** 31:
             raise ValueError("n_problems * (n_samples + 2) * k must stay below 2^31")
-        sk = sm = None
-        if samples is not None:
-            sm = _f32(samples)
-            if sm.shape == (ns, self._dim):
-                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
-            if sm.shape != (n, ns, self._dim):
-                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
-        if skips is not None:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
-                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
-            sk = np.ascontiguousarray(sk, np.uint64)
+        sm = _samples(samples, n, ns, self._dim)
+        sk = _skips(skips, n, "problem", draws=ns if sm is None else None)
         cs = _lib.PrmSettings(ns, k, radius, int(keep))
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        u8 = ctypes.POINTER(ctypes.c_uint8)
-        check(lib.vmv_prm_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
-                                None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(plans)), "vmv_prm_multi")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(u8), iterations.ctypes.data_as(_lib.c_u32_p),
-                                        sizes.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
-                                        ctypes.byref(rounds), ctypes.byref(questions)), "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        check(lib.vmv_prm_multi(self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), _ptr(sm, _lib.c_float_p),
+                                ctypes.byref(cs), ctypes.byref(plans)), "vmv_prm_multi")
+
+        def roadmaps(plans, out):
             candidates, costs = np.zeros(n, np.uint32), np.zeros(n, np.float32)
             check(lib.vmv_plans_roadmap_summary(plans, None, candidates.ctypes.data_as(_lib.c_u32_p), None, _fp(costs)),
                   "vmv_plans_roadmap_summary")
-            out = dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths,
-                       candidate_edges=candidates, costs=costs, rounds=int(rounds.value), questions=int(questions.value))
-            if keep:
-                roadmaps = []
-                for p in range(n):
-                    vertex = np.zeros(ns + 2, np.uint8)
-                    check(lib.vmv_plans_roadmap_vertices(plans, p, vertex.ctypes.data_as(u8)), "vmv_plans_roadmap_vertices")
-                    m = int(candidates[p])
-                    pairs, flags = np.zeros((m, 2), np.uint32), np.zeros(m, np.uint8)
-                    got = ctypes.c_size_t(0)
-                    check(lib.vmv_plans_roadmap_edges(plans, p, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(u8), m,
-                                                      ctypes.byref(got)), "vmv_plans_roadmap_edges")
-                    roadmaps.append((vertex.astype(bool), pairs[:got.value], flags[:got.value].astype(bool)))
-                out["roadmaps"] = roadmaps
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return out
+            out.update(candidate_edges=candidates, costs=costs)
+            if not keep:
+                return
+            out["roadmaps"] = []
+            for p in range(n):
+                vertex = np.zeros(ns + 2, np.uint8)
+                check(lib.vmv_plans_roadmap_vertices(plans, p, vertex.ctypes.data_as(_lib.c_u8_p)), "vmv_plans_roadmap_vertices")
+                m = int(candidates[p])
+                pairs, flags = np.zeros((m, 2), np.uint32), np.zeros(m, np.uint8)
+                got = ctypes.c_size_t(0)
+                check(lib.vmv_plans_roadmap_edges(plans, p, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(_lib.c_u8_p),
+                                                  m, ctypes.byref(got)), "vmv_plans_roadmap_edges")
+                out["roadmaps"].append((vertex.astype(bool), pairs[:got.value], flags[:got.value].astype(bool)))
+
+        return _read_plans(plans, n, self._dim, roadmaps)
 
     def roadmaps_build_raw(self, environments, settings, skips=None, samples=None):
         """vmv_roadmaps_build: one device-resident roadmap per environment (None = the empty environment) over the Halton
@@ -1221,36 +1221,16 @@ class _Robot(types.ModuleType):
         environments = list(environments)
         _check_environments(environments)
         n = len(environments)
-        ns, k, radius = int(settings.n_samples), int(settings.k), float(settings.radius)
-        if ns % 64 != 0 or not 64 <= ns <= 8128:
-            raise ValueError("n_samples must be a multiple of 64 from 64 to 8,128")
-        if not 1 <= k <= 16:
-            raise ValueError("k must be from 1 to 16")
-        if not radius > 0:
-            raise ValueError("radius must be positive (inf = no cut)")
+        ns, k, radius = _roadmap_sampling(settings)
         if n * ns * k >= 2 ** 31:
             raise ValueError("n_roadmaps * n_samples * k must stay below 2^31")
-        sk = sm = None
-        if samples is not None:
-            sm = _f32(samples)
-            if sm.shape == (ns, self._dim):
-                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
-            if sm.shape != (n, ns, self._dim):
-                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
-        if skips is not None:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per roadmap, got shape {sk.shape} for {n} roadmaps")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
-                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
-            sk = np.ascontiguousarray(sk, np.uint64)
+        sm = _samples(samples, n, ns, self._dim)
+        sk = _skips(skips, n, "roadmap", draws=ns if sm is None else None)
         cs = _lib.RoadmapSettings(ns, k, radius)
         envs, handles = _env_handles(environments)
         handle = ctypes.c_void_p()
-        check(lib.vmv_roadmaps_build(self._id, handles, n, None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
-                                     None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(handle)), "vmv_roadmaps_build")
+        check(lib.vmv_roadmaps_build(self._id, handles, n, _ptr(sk, _lib.c_u64_p), _ptr(sm, _lib.c_float_p), ctypes.byref(cs),
+                                     ctypes.byref(handle)), "vmv_roadmaps_build")
         return handle, envs
 
     def roadmaps_query_raw(self, handle, n_roadmaps, starts, goals, index=None, settings=None):
@@ -1259,15 +1239,11 @@ class _Robot(types.ModuleType):
         [n][2] = valid connection edges of the start and of the goal, path_lengths, costs, edges_checked), the packed
         waypoints (paths [sum(path_lengths)][dim]) and the totals rounds and questions.  DeviceRoadmaps.query is the
         caller-facing form.  Every argument is checked before any library call."""
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        kc, radius = int(settings.k_connect), float(settings.radius)
+        a, b, n = _endpoints(self._dim, starts, goals)
+        kc = int(settings.k_connect)
         if not 1 <= kc <= 32:
             raise ValueError("k_connect must be from 1 to 32")
-        if not radius > 0:
-            raise ValueError("radius must be positive (inf = no cut)")
+        radius = _cut_radius(settings)
         if n * (1 + 2 * kc) >= 2 ** 31:
             raise ValueError("n_queries * (1 + 2 * k_connect) must stay below 2^31")
         ix = None
@@ -1282,24 +1258,15 @@ class _Robot(types.ModuleType):
             raise ValueError("the handle holds no roadmap")
         cs = _lib.RoadmapQuerySettings(kc, radius)
         plans = ctypes.c_void_p()
-        u8 = ctypes.POINTER(ctypes.c_uint8)
-        check(lib.vmv_roadmaps_query(handle, n, None if ix is None else ix.ctypes.data_as(_lib.c_u32_p), _fp(a), _fp(b),
-                                     ctypes.byref(cs), ctypes.byref(plans)), "vmv_roadmaps_query")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(u8), iterations.ctypes.data_as(_lib.c_u32_p),
-                                        sizes.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
-                                        ctypes.byref(rounds), ctypes.byref(questions)), "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        check(lib.vmv_roadmaps_query(handle, n, _ptr(ix, _lib.c_u32_p), _fp(a), _fp(b), ctypes.byref(cs), ctypes.byref(plans)),
+              "vmv_roadmaps_query")
+
+        def connections(plans, out):
             costs, asked = np.zeros(n, np.float32), np.zeros(n, np.uint32)
             check(lib.vmv_plans_query_summary(plans, _fp(costs), asked.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_query_summary")
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, costs=costs,
-                    edges_checked=asked, rounds=int(rounds.value), questions=int(questions.value))
+            out.update(costs=costs, edges_checked=asked)
+
+        return _read_plans(plans, n, self._dim, connections)
 
     def roadmaps_summary_raw(self, handle, n_roadmaps):
         """vmv_roadmaps_summary -> (valid samples, candidate edges, valid edges), uint32[n_roadmaps] each"""
@@ -1310,14 +1277,13 @@ class _Robot(types.ModuleType):
     def roadmaps_roadmap_raw(self, handle, r, n_samples):
         """vmv_roadmaps_vertices and vmv_roadmaps_edges of roadmap r -> (samples [n_samples][dim], their flags bool[n_samples],
         candidate pairs uint32[m][2] of sample ids, their flags bool[m])"""
-        u8 = ctypes.POINTER(ctypes.c_uint8)
         samples, vertex = np.zeros((n_samples, self._dim), np.float32), np.zeros(n_samples, np.uint8)
-        check(lib.vmv_roadmaps_vertices(handle, r, _fp(samples), vertex.ctypes.data_as(u8)), "vmv_roadmaps_vertices")
+        check(lib.vmv_roadmaps_vertices(handle, r, _fp(samples), vertex.ctypes.data_as(_lib.c_u8_p)), "vmv_roadmaps_vertices")
         m = ctypes.c_size_t(0)
         check(lib.vmv_roadmaps_edges(handle, r, None, None, 0, ctypes.byref(m)), "vmv_roadmaps_edges")
         pairs, flags = np.zeros((m.value, 2), np.uint32), np.zeros(m.value, np.uint8)
-        check(lib.vmv_roadmaps_edges(handle, r, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(u8), m.value, None),
-              "vmv_roadmaps_edges")
+        check(lib.vmv_roadmaps_edges(handle, r, pairs.ctypes.data_as(_lib.c_u32_p), flags.ctypes.data_as(_lib.c_u8_p), m.value,
+                                     None), "vmv_roadmaps_edges")
         return samples, vertex.astype(bool), pairs, flags.astype(bool)
 
     def roadmaps_destroy_raw(self, handle):
@@ -1333,12 +1299,8 @@ class _Robot(types.ModuleType):
         library call."""
         environments = list(environments)
         _check_environments(environments)
-        a, b = _f32(starts), _f32(goals)
-        if a.ndim != 2 or a.shape[1] != self._dim or a.shape != b.shape:
-            raise TypeError(f"expected two [n][{self._dim}] arrays")
-        n = a.shape[0]
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per problem, got {len(environments)} for {n} problems")
+        a, b, n = _endpoints(self._dim, starts, goals)
+        _one_per(environments, n, "problem")
         ns, max_it = int(settings.n_samples), int(settings.max_iterations)
         per_round, every = int(settings.questions_per_round), int(getattr(settings, "check_every", 0))
         if ns % 64 != 0 or not 64 <= ns <= 2048:
@@ -1350,43 +1312,20 @@ class _Robot(types.ModuleType):
         if n * (ns + 2) * ((ns + 2 + 31) // 32) >= 2 ** 31 or n * per_round >= 2 ** 31:
             raise ValueError("n_problems * (n_samples + 2) * ceil((n_samples + 2) / 32) and n_problems * questions_per_round "
                              "must stay below 2^31")
-        sk = sm = None
-        if samples is not None:
-            sm = _f32(samples)
-            if sm.shape == (ns, self._dim):
-                sm = np.ascontiguousarray(np.broadcast_to(sm, (n, ns, self._dim)))
-            if sm.shape != (n, ns, self._dim):
-                raise TypeError(f"expected samples as [{ns}][{self._dim}] or [{n}][{ns}][{self._dim}]")
-        if skips is not None:
-            sk = np.asarray(skips)
-            if sk.shape != (n,):
-                raise ValueError(f"expected one skip per problem, got shape {sk.shape} for {n} problems")
-            if sk.size and (not np.issubdtype(sk.dtype, np.integer) or (sk < 0).any()):
-                raise ValueError("skips must be non-negative integers")
-            if sm is None and sk.size and int(sk.max()) + ns > 1000000:
-                raise ValueError("skip + n_samples may not exceed 1,000,000 (the Halton sequence's validity limit)")
-            sk = np.ascontiguousarray(sk, np.uint64)
+        sm = _samples(samples, n, ns, self._dim)
+        sk = _skips(skips, n, "problem", draws=ns if sm is None else None)
         cs = _lib.FcitSettings(ns, max_it, per_round, every)
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_fcit_multi(self._id, handles, n, _fp(a), _fp(b), None if sk is None else sk.ctypes.data_as(_lib.c_u64_p),
-                                 None if sm is None else _fp(sm), ctypes.byref(cs), ctypes.byref(plans)), "vmv_fcit_multi")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            sizes, lengths = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32)
-            rounds, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_plans_summary(plans, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                        iterations.ctypes.data_as(_lib.c_u32_p), sizes.ctypes.data_as(_lib.c_u32_p),
-                                        lengths.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(questions)),
-                  "vmv_plans_summary")
-            paths = np.zeros((int(lengths.sum()), self._dim), np.float32)
-            check(lib.vmv_plans_paths(plans, _fp(paths), paths.size), "vmv_plans_paths")
+        check(lib.vmv_fcit_multi(self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), _ptr(sm, _lib.c_float_p),
+                                 ctypes.byref(cs), ctypes.byref(plans)), "vmv_fcit_multi")
+
+        def searches(plans, out):
             costs, known = np.zeros(n, np.float32), np.zeros(n, np.uint32)
             check(lib.vmv_plans_fcit_summary(plans, _fp(costs), known.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_fcit_summary")
-        finally:
-            lib.vmv_plans_destroy(plans)
-        return dict(status=status, iterations=iterations, sizes=sizes, path_lengths=lengths, paths=paths, costs=costs,
-                    known_valid_edges=known, rounds=int(rounds.value), questions=int(questions.value))
+            out.update(costs=costs, known_valid_edges=known)
+
+        return _read_plans(plans, n, self._dim, searches)
 
     def simplify_multi_raw(self, paths, environments, settings):
         """vmv_simplify_multi: the reference's simplify() with the SHORTCUT and BSPLINE routines for many paths in
@@ -1398,21 +1337,10 @@ class _Robot(types.ModuleType):
         planning.simplify_multi is the caller-facing form.  Every argument is checked before any library call."""
         environments = list(environments)
         _check_environments(environments)
-        pts = []
-        for p in paths:
-            a = np.asarray(p, dtype=np.float32)
-            if a.size == 0:
-                a = np.zeros((0, self._dim), np.float32)
-            if a.ndim != 2 or a.shape[1] != self._dim:
-                raise TypeError(f"expected every path as [len][{self._dim}] waypoints")
-            pts.append(a)
+        pts, packed, offsets = _packed_paths(paths, self._dim)
         n = len(pts)
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per path, got {len(environments)} for {n} paths")
+        _one_per(environments, n, "path")
         cs = _simplify_settings_struct(settings, max((len(a) for a in pts), default=0))
-        offsets = np.zeros(n + 1, np.uintp)
-        offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
-        packed = np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, self._dim), np.float32)]))
         if n == 0:
             return dict(status=np.zeros(0, np.uint8), iterations=np.zeros(0, np.uint32), lengths=np.zeros(0, np.uint32),
                         questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0)
@@ -1424,10 +1352,9 @@ class _Robot(types.ModuleType):
             status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
             lengths, questions = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
             rounds, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            check(lib.vmv_paths_summary(out, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                        iterations.ctypes.data_as(_lib.c_u32_p), lengths.ctypes.data_as(_lib.c_u32_p),
-                                        questions.ctypes.data_as(_lib.c_u32_p), ctypes.byref(rounds), ctypes.byref(total)),
-                  "vmv_paths_summary")
+            check(lib.vmv_paths_summary(out, status.ctypes.data_as(_lib.c_u8_p), iterations.ctypes.data_as(_lib.c_u32_p),
+                                        lengths.ctypes.data_as(_lib.c_u32_p), questions.ctypes.data_as(_lib.c_u32_p),
+                                        ctypes.byref(rounds), ctypes.byref(total)), "vmv_paths_summary")
             points = np.zeros((int(lengths.sum()), self._dim), np.float32)
             check(lib.vmv_paths_points(out, _fp(points), points.size), "vmv_paths_points")
         finally:
@@ -1445,21 +1372,10 @@ class _Robot(types.ModuleType):
         checked before any library call."""
         environments = list(environments)
         _check_environments(environments)
-        pts = []
-        for p in paths:
-            a = np.asarray(p, dtype=np.float32)
-            if a.size == 0:
-                a = np.zeros((0, self._dim), np.float32)
-            if a.ndim != 2 or a.shape[1] != self._dim:
-                raise TypeError(f"expected every path as [len][{self._dim}] waypoints")
-            pts.append(a)
+        pts, packed, offsets = _packed_paths(paths, self._dim)
         n = len(pts)
-        if len(environments) != n:
-            raise ValueError(f"expected one environment per path, got {len(environments)} for {n} paths")
+        _one_per(environments, n, "path")
         cs = _optimize_settings_struct(settings, max((len(a) for a in pts), default=0))
-        offsets = np.zeros(n + 1, np.uintp)
-        offsets[1:] = np.cumsum([len(a) for a in pts], dtype=np.int64)
-        packed = np.ascontiguousarray(np.concatenate(pts + [np.zeros((0, self._dim), np.float32)]))
         status, iterations, best = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         cost_first, cost = np.zeros(n, np.float32), np.zeros(n, np.float32)
         clr_first, clr = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
@@ -1471,7 +1387,7 @@ class _Robot(types.ModuleType):
             check(lib.vmv_optimize_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
                                          ctypes.byref(cs), ctypes.byref(out)), "vmv_optimize_multi")
             try:
-                check(lib.vmv_optimized_summary(out, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                check(lib.vmv_optimized_summary(out, status.ctypes.data_as(_lib.c_u8_p),
                                                 iterations.ctypes.data_as(_lib.c_u32_p), best.ctypes.data_as(_lib.c_u32_p),
                                                 _fp(cost_first), _fp(cost), _fp(clr_first), _fp(clr), ctypes.byref(calls),
                                                 ctypes.byref(validations)), "vmv_optimized_summary")

@@ -18,6 +18,7 @@ c_float_p = ctypes.POINTER(ctypes.c_float)
 c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_u32_p = ctypes.POINTER(ctypes.c_uint32)
 c_size_p = ctypes.POINTER(ctypes.c_size_t)
+c_u8_p = ctypes.POINTER(ctypes.c_uint8)
 
 VMV_OK = 0
 STATUS_NAMES = {0: "VMV_OK", 1: "VMV_ERR_INVALID_ARGUMENT", 2: "VMV_ERR_NO_DEVICE", 3: "VMV_ERR_HIP",
@@ -174,7 +175,7 @@ def _load():
         "vmv_shard_range": (I, [S, I, I, c_size_p, c_size_p]),
         "vmv_shard_words": (S, [S, I]),
         "vmv_spheres_in_collision_batch": (I, [V, V, S, V, V]),
-        "vmv_spheres_in_collision_batch_host": (I, [V, c_float_p, S, ctypes.POINTER(ctypes.c_uint8)]),
+        "vmv_spheres_in_collision_batch_host": (I, [V, c_float_p, S, c_u8_p]),
         "vmv_validate_batch_host": (I, [I, V, c_float_p, S, c_u64_p]),
         "vmv_validate_batch_multi": (I, [I, ctypes.POINTER(V), c_size_p, S, V, V, V]),
         "vmv_validate_batch_multi_host": (I, [I, ctypes.POINTER(V), c_size_p, S, c_float_p, c_u64_p]),
@@ -201,20 +202,20 @@ def _load():
         "vmv_rrtc_multi_goals": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_size_p, c_u64_p,
                                      ctypes.POINTER(RrtcGoalsSettings), ctypes.POINTER(V)]),
         "vmv_plans_goal_indices": (I, [V, c_u32_p]),
-        "vmv_plans_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_plans_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_plans_paths": (I, [V, c_float_p, S]),
         "vmv_plans_destroy": (I, [V]),
         "vmv_prm_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, c_float_p, ctypes.POINTER(PrmSettings),
                               ctypes.POINTER(V)]),
         "vmv_plans_roadmap_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p, c_float_p]),
-        "vmv_plans_roadmap_vertices": (I, [V, S, ctypes.POINTER(ctypes.c_uint8)]),
-        "vmv_plans_roadmap_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
+        "vmv_plans_roadmap_vertices": (I, [V, S, c_u8_p]),
+        "vmv_plans_roadmap_edges": (I, [V, S, c_u32_p, c_u8_p, S, c_size_p]),
         "vmv_roadmaps_build": (I, [I, ctypes.POINTER(V), S, c_u64_p, c_float_p, ctypes.POINTER(RoadmapSettings), ctypes.POINTER(V)]),
         "vmv_roadmaps_query": (I, [V, S, c_u32_p, c_float_p, c_float_p, ctypes.POINTER(RoadmapQuerySettings), ctypes.POINTER(V)]),
         "vmv_plans_query_summary": (I, [V, c_float_p, c_u32_p]),
         "vmv_roadmaps_summary": (I, [V, c_u32_p, c_u32_p, c_u32_p]),
-        "vmv_roadmaps_vertices": (I, [V, S, c_float_p, ctypes.POINTER(ctypes.c_uint8)]),
-        "vmv_roadmaps_edges": (I, [V, S, c_u32_p, ctypes.POINTER(ctypes.c_uint8), S, c_size_p]),
+        "vmv_roadmaps_vertices": (I, [V, S, c_float_p, c_u8_p]),
+        "vmv_roadmaps_edges": (I, [V, S, c_u32_p, c_u8_p, S, c_size_p]),
         "vmv_roadmaps_destroy": (I, [V]),
         "vmv_aorrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
                                  ctypes.POINTER(V)]),
@@ -222,17 +223,15 @@ def _load():
         "vmv_fcit_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, c_float_p, ctypes.POINTER(FcitSettings),
                                ctypes.POINTER(V)]),
         "vmv_plans_fcit_summary": (I, [V, c_float_p, c_u32_p]),
-        "vmv_phs_samples": (I, [I, c_float_p, c_float_p, F, ctypes.c_uint32, ctypes.c_uint32, S, c_float_p,
-                                ctypes.POINTER(ctypes.c_uint8), c_u32_p]),
+        "vmv_phs_samples": (I, [I, c_float_p, c_float_p, F, ctypes.c_uint32, ctypes.c_uint32, S, c_float_p, c_u8_p, c_u32_p]),
         "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
                                    ctypes.POINTER(V)]),
-        "vmv_paths_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_paths_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_paths_points": (I, [V, c_float_p, S]),
         "vmv_paths_destroy": (I, [V]),
         "vmv_optimize_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(OptimizeSettings),
                                    ctypes.POINTER(V)]),
-        "vmv_optimized_summary": (I, [V, ctypes.POINTER(ctypes.c_uint8), c_u32_p, c_u32_p, c_float_p, c_float_p, c_float_p,
-                                      c_float_p, c_u64_p, c_u64_p]),
+        "vmv_optimized_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_float_p, c_float_p, c_float_p, c_float_p, c_u64_p, c_u64_p]),
         "vmv_optimized_points": (I, [V, c_float_p, S]),
         "vmv_optimized_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),

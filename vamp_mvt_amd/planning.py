@@ -25,6 +25,8 @@ from dataclasses import dataclass, field, replace
 
 import numpy as np
 
+from . import _waypoints
+
 _PRIMES = np.array([3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59], np.float32)
 
 
@@ -336,16 +338,27 @@ def _rrtc_additions_off(s):
                for k in ("dynamic_domain", "radius", "alpha", "min_radius", "start_tree_first"))
 
 
-def _rrtc_results(raw):
-    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
+def _planning_results(raw, lengths="path_lengths", points="paths", **fields):
+    """One PlanningResult per problem (or path) of a planner wrapper's dict `raw`: `path` = the rows of raw[points] that
+    raw[lengths] gives it, `iterations`, `size` where the dict has sizes, and each attribute named in `fields` as
+    (raw key, conversion), left at its default where the dict lacks the key.  status: one of PLAN_STATUS unless given."""
+    fields.setdefault("status", ("status", lambda s: PLAN_STATUS[int(s)]))
+    ends = np.cumsum(raw[lengths], dtype=np.int64)
     out = []
     for p in range(len(ends)):
-        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
-        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
-                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])],
-                                  status=PLAN_STATUS[int(raw["status"][p])]))
-        if "goal_indices" in raw:
-            out[-1].goal_index = int(raw["goal_indices"][p])
+        pts = raw[points][ends[p] - int(raw[lengths][p]):ends[p]]
+        res = PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]))
+        if "sizes" in raw:
+            res.size = [int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])]
+        for name, (key, convert) in fields.items():
+            if key in raw:
+                setattr(res, name, convert(raw[key][p]))
+        out.append(res)
+    return out
+
+
+def _rrtc_results(raw):
+    out = _planning_results(raw, goal_index=("goal_indices", int))
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
@@ -391,14 +404,8 @@ def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | N
     own inputs alone.  Agreement with the reference's incremental PRM is not claimed."""
     s = settings or PRMMultiSettings()
     raw = robot.prm_multi_raw(starts, goals, environments, s, skips, samples)
-    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
-    out = []
-    for p in range(len(ends)):
-        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
-        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
-                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
-                                  edges_checked=int(raw["candidate_edges"][p]), status=PLAN_STATUS[int(raw["status"][p])],
-                                  roadmap=raw["roadmaps"][p] if "roadmaps" in raw else None))
+    out = _planning_results(raw, cost=("costs", float), edges_checked=("candidate_edges", int),
+                            roadmap=("roadmaps", lambda r: r))
     if out:  # the call's validation calls ride on the first result
         out[0].validity_calls = raw["rounds"]
     return out
@@ -470,13 +477,7 @@ class DeviceRoadmaps:
         if stale:
             raise ValueError(f"the environments of roadmaps {stale} changed after the roadmaps were built")
         raw = self._robot.roadmaps_query_raw(handle, len(self), starts, goals, index, s)
-        ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
-        out = []
-        for q in range(len(ends)):
-            pts = raw["paths"][ends[q] - int(raw["path_lengths"][q]):ends[q]]
-            out.append(PlanningResult(path=[p.copy() for p in pts], iterations=int(raw["iterations"][q]),
-                                      size=[int(raw["sizes"][q, 0]), int(raw["sizes"][q, 1])], cost=float(raw["costs"][q]),
-                                      edges_checked=int(raw["edges_checked"][q]), status=PLAN_STATUS[int(raw["status"][q])]))
+        out = _planning_results(raw, cost=("costs", float), edges_checked=("edges_checked", int))
         if out:  # the call's validation calls ride on the first result
             out[0].validity_calls = raw["rounds"]
         return out
@@ -510,13 +511,7 @@ def fcit_multi(robot, starts, goals, environments, settings: FCITMultiSettings |
     Agreement with the reference's FCIT* (an edge-queue search) is not claimed."""
     s = settings or FCITMultiSettings()
     raw = robot.fcit_multi_raw(starts, goals, environments, s, skips, samples)
-    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
-    out = []
-    for p in range(len(ends)):
-        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
-        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
-                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
-                                  known_valid_edges=int(raw["known_valid_edges"][p]), status=PLAN_STATUS[int(raw["status"][p])]))
+    out = _planning_results(raw, cost=("costs", float), known_valid_edges=("known_valid_edges", int))
     if out:  # the call's totals ride on the first result (validity_calls: the vertices' call and one per round)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
@@ -543,14 +538,8 @@ def aorrtc_multi(robot, starts, goals, environments, settings: AORRTCMultiSettin
     if not isinstance(s.simplify, SimplifyMultiSettings):
         s = replace(s, simplify=_as_simplify_multi_settings(s.simplify))
     raw = robot.aorrtc_multi_raw(starts, goals, environments, s, skips)
-    ends = np.cumsum(raw["path_lengths"], dtype=np.int64)
-    out = []
-    for p in range(len(ends)):
-        pts = raw["paths"][ends[p] - int(raw["path_lengths"][p]):ends[p]]
-        out.append(PlanningResult(path=[q.copy() for q in pts], iterations=int(raw["iterations"][p]),
-                                  size=[int(raw["sizes"][p, 0]), int(raw["sizes"][p, 1])], cost=float(raw["costs"][p]),
-                                  first_cost=float(raw["first_costs"][p]), searches=int(raw["searches"][p]),
-                                  improvements=int(raw["improvements"][p]), status=PLAN_STATUS[int(raw["status"][p])]))
+    out = _planning_results(raw, cost=("costs", float), first_cost=("first_costs", float), searches=("searches", int),
+                            improvements=("improvements", int))
     if out:  # the call's totals over all stages ride on the first result
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
@@ -600,12 +589,10 @@ def simplify_multi(robot, paths, environments, settings=None):
     path still, with status "capacity"."""
     s = _as_simplify_multi_settings(settings)
     raw = robot.simplify_multi_raw(paths, environments, s)
-    ends = np.cumsum(raw["lengths"], dtype=np.int64)
-    out = []
-    for p in range(len(ends)):
-        pts = [q.copy() for q in raw["points"][ends[p] - int(raw["lengths"][p]):ends[p]]]
-        out.append(PlanningResult(path=pts, iterations=int(raw["iterations"][p]), cost=path_cost(pts),
-                                  edges_checked=int(raw["questions"][p]), status=SIMPLIFY_STATUS[int(raw["status"][p])]))
+    out = _planning_results(raw, "lengths", "points", edges_checked=("questions", int),
+                            status=("status", lambda k: SIMPLIFY_STATUS[int(k)]))
+    for res in out:
+        res.cost = path_cost(res.path)
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["total_questions"]
     return out
@@ -837,11 +824,7 @@ def optimize_multi(robot, paths, environments, settings=None, resolution=None):
     dim = robot.dimension()
     pts = []
     for k, p in enumerate(paths):
-        a = np.asarray(p, np.float32)
-        if a.size == 0:
-            a = np.zeros((0, dim), np.float32)
-        if a.ndim != 2 or a.shape[1] != dim:
-            raise TypeError(f"expected every path as [len][{dim}] waypoints")
+        a = _waypoints(p, dim)
         if resolution is not None:
             a = densify_path(a, float(resolution))
             if len(a) > int(s.max_waypoints):
