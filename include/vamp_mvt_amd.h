@@ -764,6 +764,76 @@ int vmv_optimized_summary(const vmv_optimized *result, uint8_t *status, uint32_t
 int vmv_optimized_points(const vmv_optimized *result, float *out, size_t capacity_floats);
 int vmv_optimized_destroy(vmv_optimized *result);
 
+/* ---- straight-line end-effector motions for many independent problems (no counterpart in the reference) -- */
+/* Problem p: a start configuration q0 (starts [n][dim]) and a target frame T1 (targets [n][16], vmv_eefk_batch's layout),
+ * in environment envs[p]; envs == NULL is the kinematics-only call (nothing is validated).  The end effector is led from
+ * q0's frame to T1 along a straight line in position and a rotation about one fixed axis, pose by pose, every pose
+ * tracked by vmv_ik_batch's iteration from the previous waypoint.  All problems are tracked by ONE kernel launch, one
+ * lane per problem.
+ *   Start frame: T0 = the frame vmv_eefk_batch gives q0, bit for bit.
+ *   Line (host, float64 from the fp32 frames): dp = p1 - p0; (a, theta), theta in [0, pi], the axis and angle of R0^T R1:
+ *     theta = atan2(|v|, (tr - 1) / 2), v = 1/2 (R21 - R12, R02 - R20, R10 - R01); a = v / |v| while (tr - 1) / 2 >= -1/2,
+ *     beyond that from the symmetric part: the largest column of 1/2 (R + R^T) - cos(theta) I, normalised, signed like v;
+ *     |v| < 1e-12: a = (0, 0, 1).  With position_only theta = 0.  Segments m = max(1, ceil(|dp| / pos_step),
+ *     ceil(theta / rot_step)).  m + 1 > max_waypoints: status VMV_CART_TOO_LONG, nothing is tracked or asked.
+ *   Pose k = 1 .. m (device, fp32, one rounding per operation): s = float(k) / float(m); p0 + s * dp;
+ *     R0 * Rot(a, s * theta), Rot by Rodrigues' formula with c = vcos(s theta), n = vsin(s theta) (the kernels' own sine
+ *     and cosine), u = (1 - c) * a: Rot_rr = c + u_r * a_r, Rot_rc = u_r * a_c -/+ n * a_t; every 3-term product as
+ *     ((x0 y0 + x1 y1) + x2 y2).
+ *   Tracking: waypoint k is what vmv_ik_batch's iteration (its error, weights, damping schedule, bound-hold rule, max_step
+ *     and clip to [lower, lower + span]; include above) gives from waypoint k - 1 towards pose k within max_iterations
+ *     evaluations after the first.  It is accepted if it converged (pos_tol, rot_tol; with position_only pos_tol alone)
+ *     and max_j |q_k - q_{k-1}| <= max_joint_step; otherwise the path stops at waypoint k - 1 with VMV_CART_IK_FAILED or
+ *     VMV_CART_JOINT_JUMP.  evaluations counts every evaluation after a waypoint's first, over all waypoints.
+ *   Validation (envs != NULL), after tracking: the starts of all tracked problems in ONE vmv_validate_batch_multi call,
+ *     every tracked edge (q_{k-1}, q_k) of every problem in ONE vmv_validate_motion_batch_multi call, each problem in its
+ *     own environment.  A start that is not valid: VMV_CART_INVALID_START, achieved 0.  Otherwise the path is cut in
+ *     front of its first invalid edge (VMV_CART_COLLISION).
+ *   A non-finite entry of a start or a target, or a finite start so large that vmv_eefk_batch gives it no finite frame:
+ *     VMV_CART_NON_FINITE, one waypoint (the start as passed), nothing tracked or asked.
+ * Result per problem: status; segments = m (0 for VMV_CART_NON_FINITE); achieved = the segments kept; evaluations; the
+ * achieved + 1 waypoints, the first being q0's bits.  Totals: the validation calls made (0 .. 2) and the questions asked
+ * (starts + edges).  A problem's result depends on its own start, target, environment and the settings alone, bit for
+ * bit - not on the batch or its place in it.
+ * Checks before anything is launched, device-free ones first: unknown robot; NULL starts / targets / settings /
+ * out; the settings in the struct's order (a non-finite value, max_iterations >= 2^30, max_waypoints above
+ * 1,024, position_only other than 0 / 1); n >= 2^31; then, with envs, vmv_validate_batch_multi's checks of the handles
+ * (NULL, finalized) with its messages (all VMV_ERR_INVALID_ARGUMENT but VMV_ERR_NOT_FINALIZED); n == 0 is VMV_OK with an
+ * empty result and no device; a device at all; the environments' device and the robot's parts (built in one batch).  A call
+ * that fails leaves *out untouched.  Synchronous, host buffers, default stream; repeated handles are allowed. */
+enum
+{
+    VMV_CART_COMPLETE = 0,
+    VMV_CART_IK_FAILED = 1,
+    VMV_CART_JOINT_JUMP = 2,
+    VMV_CART_COLLISION = 3,
+    VMV_CART_INVALID_START = 4,
+    VMV_CART_TOO_LONG = 5,
+    VMV_CART_NON_FINITE = 6
+};
+typedef struct
+{
+    float pos_step, rot_step; /* metres, radians per segment; <= 0: default (0.01, 0.05) */
+    uint32_t max_iterations;  /* evaluations per waypoint after the first; 0: default (16); below 2^30 */
+    float pos_tol, rot_tol;   /* <= 0: default (1e-4, 1e-3) */
+    float rot_weight;         /* <= 0: default (0.25) */
+    float damping;            /* <= 0: default (1e-2) */
+    float max_step;           /* <= 0: default (0.5) */
+    float max_joint_step;     /* largest joint change between two waypoints; <= 0: default (0.3) */
+    uint32_t max_waypoints;   /* cap on m + 1, at most 1,024; 0: default (1,024) */
+    int position_only;        /* 0 / 1 */
+} vmv_cartesian_settings;
+typedef struct vmv_cartesian vmv_cartesian;
+int vmv_cartesian_multi(int robot, const vmv_env *const *envs /* [n] or NULL */, size_t n, const float *starts /* [n][dim] */,
+                        const float *targets /* [n][16] */, const vmv_cartesian_settings *settings, vmv_cartesian **out);
+/* Per problem (arrays of n, any may be NULL): status (VMV_CART_*), segments, achieved, evaluations.  Totals (may be NULL). */
+int vmv_cartesian_summary(const vmv_cartesian *result, uint8_t *status, uint32_t *segments, uint32_t *achieved,
+                          uint32_t *evaluations, uint64_t *validation_calls, uint64_t *questions);
+/* every problem's achieved + 1 waypoints, packed in problem order; VMV_ERR_CAPACITY if capacity_floats is too small
+ * (nothing is written) */
+int vmv_cartesian_points(const vmv_cartesian *result, float *out, size_t capacity_floats);
+int vmv_cartesian_destroy(vmv_cartesian *result);
+
 /* ---- lockstep AORRTC: cost-bounded RRT-Connect searches for many independent problems --------------------- */
 /* AORRTC (planning/aorrtc.hh, one goal, PHS sampling, no dynamic domain) for n_problems problems at once; the arguments
  * are those of vmv_rrtc_multi.  Per problem:

@@ -711,6 +711,24 @@ def _optimize_settings_struct(settings, longest=0):
                                  positive["env_margin"], positive["self_margin"], max_wp)
 
 
+def _cartesian_settings_struct(settings):
+    """vmv_cartesian_settings from a CartesianSettings-shaped object, checked as the library checks it (0 or a negative
+    number asks for the library's default)"""
+    names = ("pos_step", "rot_step", "pos_tol", "rot_tol", "rot_weight", "damping", "max_step", "max_joint_step")
+    values = {k: float(getattr(settings, k)) for k in names}
+    for k, v in values.items():
+        if not np.isfinite(v):
+            raise ValueError(f"{k} must be finite")
+    max_it, max_wp = int(settings.max_iterations), int(settings.max_waypoints)
+    if not 0 <= max_it < 2 ** 30:
+        raise ValueError("max_iterations must be from 0 (default) to 2^30 - 1")
+    if not 0 <= max_wp <= 1024:
+        raise ValueError("max_waypoints must be from 0 (default) to 1,024")
+    return _lib.CartesianSettings(values["pos_step"], values["rot_step"], max_it, values["pos_tol"], values["rot_tol"],
+                                  values["rot_weight"], values["damping"], values["max_step"], values["max_joint_step"],
+                                  max_wp, int(bool(settings.position_only)))
+
+
 class IKSettings:
     """vmv_ik_settings (include/vamp_mvt_amd.h) with the defaults of <robot>.ik_batch: n_seeds seeds per target (1 ..
     1,024), max_iterations, pos_tol (m), rot_tol (rad; the sine of the residual angle is compared), rot_weight (metres per
@@ -1397,6 +1415,49 @@ class _Robot(types.ModuleType):
         return dict(status=status, iterations=iterations, best_iteration=best, cost_first=cost_first, cost=cost,
                     clearance_first=clr_first, clearance=clr, points=points, offsets=offsets.astype(np.int64),
                     clearance_calls=int(calls.value), validation_calls=int(validations.value))
+
+    def cartesian_multi_raw(self, starts, targets, environments, settings):
+        """vmv_cartesian_multi: straight-line end-effector motions for many problems in one call, problem p from
+        starts[p] ([dim]) to the frame targets[p] ([4][4] or [16]) in environments[p] (None = the empty environment);
+        environments=None is the kinematics-only call.  settings: the fields of planning.CartesianSettings.  -> dict of
+        per-problem numpy arrays (status, segments, achieved, evaluations), the packed waypoints (points) with their
+        offsets, and the totals validation_calls and questions.  planning.cartesian_multi is the caller-facing form.
+        Every argument is checked before any library call."""
+        a = _f32(starts)
+        if a.ndim != 2 or a.shape[1] != self._dim:
+            raise TypeError(f"expected starts as [n][{self._dim}] configurations")
+        n = a.shape[0]
+        t = _f32(targets)
+        if t.ndim < 2 or t.shape[0] != n or int(np.prod(t.shape[1:])) != 16:
+            raise TypeError(f"expected targets as [{n}][4][4] (or [{n}][16]) frames")
+        if environments is not None:
+            environments = list(environments)
+            _check_environments(environments)
+            _one_per(environments, n, "problem")
+        cs = _cartesian_settings_struct(settings)
+        status, segments = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        achieved, evaluations = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        points = np.zeros((0, self._dim), np.float32)
+        calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if n > 0:
+            handles = None
+            if environments is not None:
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+            out = ctypes.c_void_p()
+            check(lib.vmv_cartesian_multi(self._id, handles, n, _fp(a), _fp(t), ctypes.byref(cs), ctypes.byref(out)),
+                  "vmv_cartesian_multi")
+            try:
+                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (segments, achieved, evaluations)]
+                check(lib.vmv_cartesian_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, ctypes.byref(calls),
+                                                ctypes.byref(questions)), "vmv_cartesian_summary")
+                points = np.zeros((int(achieved.sum()) + n, self._dim), np.float32)
+                check(lib.vmv_cartesian_points(out, _fp(points), points.size), "vmv_cartesian_points")
+            finally:
+                lib.vmv_cartesian_destroy(out)
+        offsets = np.zeros(n + 1, np.int64)
+        offsets[1:] = np.cumsum(achieved.astype(np.int64) + 1)
+        return dict(status=status, segments=segments, achieved=achieved, evaluations=evaluations, points=points,
+                    offsets=offsets, validation_calls=int(calls.value), questions=int(questions.value))
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

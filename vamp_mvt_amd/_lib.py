@@ -90,6 +90,14 @@ class IkSettings(ctypes.Structure):
                 ("max_step", ctypes.c_float), ("position_only", ctypes.c_int)]
 
 
+class CartesianSettings(ctypes.Structure):
+    """vmv_cartesian_settings"""
+    _fields_ = [("pos_step", ctypes.c_float), ("rot_step", ctypes.c_float), ("max_iterations", ctypes.c_uint32),
+                ("pos_tol", ctypes.c_float), ("rot_tol", ctypes.c_float), ("rot_weight", ctypes.c_float),
+                ("damping", ctypes.c_float), ("max_step", ctypes.c_float), ("max_joint_step", ctypes.c_float),
+                ("max_waypoints", ctypes.c_uint32), ("position_only", ctypes.c_int)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -234,6 +242,11 @@ def _load():
         "vmv_optimized_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_float_p, c_float_p, c_float_p, c_float_p, c_u64_p, c_u64_p]),
         "vmv_optimized_points": (I, [V, c_float_p, S]),
         "vmv_optimized_destroy": (I, [V]),
+        "vmv_cartesian_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, ctypes.POINTER(CartesianSettings),
+                                    ctypes.POINTER(V)]),
+        "vmv_cartesian_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_cartesian_points": (I, [V, c_float_p, S]),
+        "vmv_cartesian_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

@@ -512,7 +512,13 @@ def install(robot):
         validate_motion's on the consecutive edges, the gradient is the current witness's."""
         return planning.optimize_multi(robot, paths, environments, settings, resolution)
 
+    def cartesian_multi(starts, targets, environments=None, settings=None):
+        """planning.cartesian_multi with this robot: straight-line end-effector motions for many problems in one call on
+        the device -> list[planning.CartesianPath]."""
+        return planning.cartesian_multi(robot, starts, targets, environments, settings)
+
     robot.optimize_multi = optimize_multi
+    robot.cartesian_multi = cartesian_multi
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals

@@ -66,6 +66,33 @@ namespace vmv
         float lower[16], upper[16];
     };
 
+    // vmv_cartesian_multi: the tracking kernel's parameter block (vmv_cartesian_settings as checked, rot_weight 0 for a
+    // position-only call), one record per problem and one result per problem.  A problem that does not take part
+    // (non-finite input, a line that is too long) has m == 0 and a zeroed record: its lane does nothing.
+    struct CartParams
+    {
+        uint32_t max_iterations;
+        uint32_t max_k;  // the largest m of the call: the bound of the kernel's outer loop
+        float pos_tol, rot_tol, rot_weight, damping, max_step, max_joint_step;
+        uint32_t position_only;
+        float lower[16], upper[16];
+    };
+    struct CartLine
+    {
+        float p0[3], dp[3];  // pose k: p0 + (k / m) dp
+        float R0[9];         // row-major; pose k: R0 Rot(axis, (k / m) theta)
+        float axis[3], theta;
+        uint32_t m;       // segments; 0: the lane does nothing
+        uint64_t offset;  // first row of the problem's m + 1 rows in the packed output
+    };
+    static_assert(sizeof(CartLine) == 88, "19 floats, m, the offset");
+    struct CartResult
+    {
+        uint32_t tracked;  // waypoints 1 .. tracked were accepted and written
+        uint32_t status;   // VMV_CART_COMPLETE, VMV_CART_IK_FAILED or VMV_CART_JOINT_JUMP
+        uint32_t evaluations, pad;
+    };
+
     // status codes are the VMV_* values of include/vamp_mvt_amd.h
     struct RobotLaunchers
     {
@@ -112,6 +139,10 @@ namespace vmv
         // i % n_seeds with seeds_shared); d_q [n][dim], d_err [n][2] or nullptr, d_status [n]
         int (*ik)(const IkParams &, const float *d_targets, const float *d_seeds, size_t n, float *d_q, float *d_err,
                   uint32_t *d_status, hipStream_t);
+        // vmv_cartesian_multi's tracking: one lane per problem (n below 2^31), d_starts [n][dim], d_points the packed
+        // rows (row 0 of a problem is the host's), d_results [n]
+        int (*cartesian)(const CartParams &, const CartLine *d_lines, const float *d_starts, size_t n, float *d_points,
+                         CartResult *d_results, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

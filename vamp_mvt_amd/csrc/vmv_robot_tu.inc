@@ -1537,6 +1537,162 @@ namespace VMV_ROBOT_NS
         status_out[i] = (converged ? 0x80000000u : 0u) | (finite ? 0u : 0x40000000u) | evals;
     }
 
+    // vmv_cartesian_multi's tracking (include/vamp_mvt_amd.h, DESIGN.md 5m): one lane walks one line.  The outer loop
+    // runs over the poses k = 1 .. m of the lane's line, the inner loop is ik_kernel's iteration from waypoint k - 1
+    // towards pose k - the same evaluation, selects, damping schedule, bound-hold rule, step cap and clip.  Both loops
+    // have bounds of their own (P.max_k <= 1,023 poses, P.max_iterations evaluations after the first) and both end on a
+    // wave-uniform test; a lane whose line is shorter, has stopped or has converged rides along through selects, so a
+    // lane's result depends on its own record, start and settings alone.  The host hands only finite records and starts
+    // (a problem with a non-finite entry has m == 0), so there is nothing to poison.  The only conditional code is the
+    // store of an accepted waypoint: plain vector stores under the lane mask, no form of the tape.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void cartesian_track_kernel(const CartParams P, const CartLine *__restrict__ lines,
+                                                                       const float *__restrict__ starts, const uint32_t n,
+                                                                       float *__restrict__ points, CartResult *__restrict__ results)
+    {
+        const uint32_t i = blockIdx.x * kIkBlock + threadIdx.x;
+        const bool in_range = i < n;
+        const uint32_t row = in_range ? i : 0u;  // (a lane past the end reads row 0 and writes nothing)
+        const CartLine L = lines[row];
+        const uint32_t m = in_range ? L.m : 0u;
+        const float mf = (float) (m > 0u ? m : 1u);
+        float *const out = points + (size_t) L.offset * R::kDim;
+        float prev[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) prev[j] = starts[(size_t) row * R::kDim + j];
+        const float ax = L.axis[0], ay = L.axis[1], az = L.axis[2];
+        bool stopped = false;
+        uint32_t tracked = 0u, status = (uint32_t) VMV_CART_COMPLETE, evals = 0u;
+
+        for (uint32_t k = 1u; k <= P.max_k; ++k)
+        {
+            const bool active = !stopped && k <= m;
+            if (!wave_any(active)) break;
+
+            // ---- pose k of the line in ee_frame's layout: p0 + s dp, R0 Rot(axis, s theta) by Rodrigues' formula
+            const float s = (float) k / mf;
+            const float ang = s * L.theta, sn = vsin(ang), cs = vcos(ang), vs = 1.0f - cs;
+            const float vx = vs * ax, vy = vs * ay, vz = vs * az;
+            float Q[3][3], T[12];
+            Q[0][0] = cs + vx * ax, Q[0][1] = vx * ay - sn * az, Q[0][2] = vx * az + sn * ay;
+            Q[1][0] = vy * ax + sn * az, Q[1][1] = cs + vy * ay, Q[1][2] = vy * az - sn * ax;
+            Q[2][0] = vz * ax - sn * ay, Q[2][1] = vz * ay + sn * ax, Q[2][2] = cs + vz * az;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+            {
+                T[a] = L.p0[a] + s * L.dp[a];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    T[3 + 3 * c + a] = dot3(L.R0[3 * a], L.R0[3 * a + 1], L.R0[3 * a + 2], Q[0][c], Q[1][c], Q[2][c]);
+            }
+
+            // ---- ik_kernel's iteration from waypoint k - 1 (clipped to the bounds, as ik_kernel clips a seed)
+            float cand[R::kDim], q[R::kDim], Jw[6][R::kDim], e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float E = __builtin_inff(), lam = P.damping;
+            bool done = !active, converged = false;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+            {
+                cand[j] = fminf(fmaxf(prev[j], P.lower[j]), P.upper[j]);
+                q[j] = cand[j];
+#pragma unroll
+                for (int r = 0; r < 6; ++r) Jw[r][j] = 0.0f;
+            }
+            for (uint32_t it = 0;; ++it)
+            {
+                float f[12], df[12][R::kDim], Jc[6][R::kDim], ec[6], n_p, n_w, tr;
+                R::ee_frame_jac(cand, f, df);
+                ee_jacobian(f, df, Jc);
+                ik_error(f, T, P.rot_weight, ec, n_p, n_w, tr);
+                const float Ec = 0.5f * (dot3(ec[0], ec[1], ec[2], ec[0], ec[1], ec[2]) + dot3(ec[3], ec[4], ec[5], ec[3], ec[4], ec[5]));
+                const bool first = it == 0u;
+                const bool take = !done && (first || Ec < E);
+                const bool ok = n_p <= P.pos_tol && (P.position_only != 0u || (tr > 1.0f && n_w <= P.rot_tol));
+                const float lam_next = take ? fmaxf(lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(lam * kIkLambdaFactor, kIkLambdaCeil);
+                lam = (done || first) ? lam : lam_next;
+                evals += (done || first) ? 0u : 1u;
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j)
+                {
+                    q[j] = take ? cand[j] : q[j];
+                    if (ee_joint(j))
+                    {
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) Jw[r][j] = take ? Jc[r][j] : Jw[r][j];
+#pragma unroll
+                        for (int r = 3; r < 6; ++r) Jw[r][j] = take ? P.rot_weight * Jc[r][j] : Jw[r][j];
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 6; ++r) e[r] = take ? ec[r] : e[r];
+                E = take ? Ec : E;
+                converged = converged || (take && ok);
+                done = done || (take && ok);
+                if (it == P.max_iterations || !wave_any(!done)) break;
+
+                float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j)
+                    if (ee_joint(j))
+                    {
+                        float g = Jw[0][j] * e[0];
+#pragma unroll
+                        for (int r = 1; r < 6; ++r) g += Jw[r][j] * e[r];
+                        const bool hold = (q[j] <= P.lower[j] && g < 0.0f) || (q[j] >= P.upper[j] && g > 0.0f);
+#pragma unroll
+                        for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : Jw[r][j];
+                    }
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = 0; b <= a; ++b)
+                    {
+                        float sum = a == b ? lam : 0.0f;
+#pragma unroll
+                        for (int j = 0; j < R::kDim; ++j)
+                            if (ee_joint(j)) sum += Jm[a][j] * Jm[b][j];
+                        A[a][b] = sum;
+                    }
+                chol6_solve(A, e, y);
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j)
+                {
+                    delta[j] = 0.0f;
+                    if (ee_joint(j))
+                    {
+                        float sum = Jm[0][j] * y[0];
+#pragma unroll
+                        for (int r = 1; r < 6; ++r) sum += Jm[r][j] * y[r];
+                        delta[j] = sum;
+                        big = fmaxf(big, fabsf(sum));
+                    }
+                }
+                const float scale = P.max_step / fmaxf(big, P.max_step);
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j)
+                    cand[j] = ee_joint(j) ? fminf(fmaxf(q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : q[j];
+            }
+
+            // ---- the waypoint is accepted if it converged within max_joint_step of waypoint k - 1
+            float jump = 0.0f;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) jump = fmaxf(jump, fabsf(q[j] - prev[j]));
+            const bool good = converged && jump <= P.max_joint_step;
+            const bool keep = active && good;
+            status = (active && !good) ? (uint32_t) (converged ? VMV_CART_JOINT_JUMP : VMV_CART_IK_FAILED) : status;
+            stopped = stopped || (active && !good);
+            tracked += keep ? 1u : 0u;
+            if (keep)  // k <= m: inside the problem's m + 1 rows
+            {
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j) out[(size_t) k * R::kDim + j] = q[j];
+            }
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) prev[j] = keep ? q[j] : prev[j];
+        }
+        if (in_range) results[i] = CartResult{tracked, status, evals, 0u};
+    }
+
     // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
@@ -2277,6 +2433,16 @@ namespace VMV_ROBOT_NS
             VMV_HIP_TU(hipGetLastError());
             return VMV_OK;
         }
+
+        // vmv_cartesian_multi: n lanes, below 2^31 (the API checks)
+        int launch_cartesian(const CartParams &P, const CartLine *d_lines, const float *d_starts, size_t n, float *d_points,
+                             CartResult *d_results, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(cartesian_track_kernel<>, dim3((uint32_t) ((n + kIkBlock - 1u) / kIkBlock)), dim3(kIkBlock), 0, stream,
+                               P, d_lines, d_starts, (uint32_t) n, d_points, d_results);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
     }  // namespace
 
 }  // namespace VMV_ROBOT_NS
@@ -2292,6 +2458,7 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_clearance, VMV_ROBOT_NS::launch_clearance_multi,
                                                     VMV_ROBOT_NS::launch_clearance_grad,
                                                     VMV_ROBOT_NS::launch_clearance_grad_multi,
-                                                    VMV_ROBOT_NS::launch_eefk_jacobian, VMV_ROBOT_NS::launch_ik};
+                                                    VMV_ROBOT_NS::launch_eefk_jacobian, VMV_ROBOT_NS::launch_ik,
+                                                    VMV_ROBOT_NS::launch_cartesian};
 #endif
 }  // namespace vmv

@@ -877,6 +877,119 @@ def ik_goals(robot, targets, envs, settings=None, dedup=1e-2):
     return goal_sets, [p for p in range(n) if len(goal_sets[p]) == 0]
 
 
+CARTESIAN_STATUS = ("complete", "ik_failed", "joint_jump", "collision", "invalid_start", "too_long", "non_finite")  # VMV_CART_*
+
+
+@dataclass
+class CartesianSettings:
+    """vmv_cartesian_settings with its defaults: pos_step (m) and rot_step (rad) per segment of the line, max_iterations
+    evaluations per waypoint, the tolerances and the Levenberg-Marquardt constants of IKSettings (a converged waypoint is
+    a solution for ik_batch too), max_joint_step (rad: the largest joint change between two waypoints), max_waypoints (at
+    most 1,024) and position_only.  The two steps and max_joint_step are choices, not measurements."""
+    pos_step: float = 0.01
+    rot_step: float = 0.05
+    max_iterations: int = 16
+    pos_tol: float = 1e-4
+    rot_tol: float = 1e-3
+    rot_weight: float = 0.25
+    damping: float = 1e-2
+    max_step: float = 0.5
+    max_joint_step: float = 0.3
+    max_waypoints: int = 1024
+    position_only: bool = False
+
+
+@dataclass
+class CartesianPath:
+    """cartesian_multi's answer for one problem: the waypoints kept (achieved + 1 of them, the first the start's bits),
+    `status` (one of CARTESIAN_STATUS), the segments of the line, the segments kept, fraction = achieved / segments (0
+    where there is no segment) and the evaluations the tracking made after each waypoint's first"""
+    path: np.ndarray
+    status: str
+    segments: int
+    achieved: int
+    fraction: float
+    evaluations: int
+
+    @property
+    def complete(self):
+        return self.status == "complete"
+
+
+def cartesian_multi(robot, starts, targets, environments=None, settings=None):
+    """Straight-line end-effector motions for many problems in one call, on the device: problem p leads the end effector
+    from the frame of starts[p] ([dim]) to targets[p] ([4][4] or [16], robot.eefk_batch's layout) along a straight line in
+    position and a rotation about one fixed axis, in environments[p] (None = the empty environment; environments=None:
+    kinematics only, nothing is validated) -> list[CartesianPath].  The line is cut into segments of at most pos_step and
+    rot_step; each pose is tracked from the previous waypoint by ik_batch's iteration; the path stops where a pose is not
+    reached ("ik_failed"), where a waypoint jumps by more than max_joint_step ("joint_jump"), or in front of the first
+    edge validate_motion rejects ("collision").  include/vamp_mvt_amd.h (vmv_cartesian_multi) gives every step."""
+    s = settings if settings is not None else CartesianSettings()
+    raw = robot.cartesian_multi_raw(starts, targets, environments, s)
+    # (plain lists: a thousand results cost a third of the call when every field is converted from its numpy scalar)
+    off, points = raw["offsets"].tolist(), raw["points"]
+    status, segments = raw["status"].tolist(), raw["segments"].tolist()
+    achieved, evaluations = raw["achieved"].tolist(), raw["evaluations"].tolist()
+    return [CartesianPath(path=points[off[p]:off[p + 1]].copy(), status=CARTESIAN_STATUS[status[p]], segments=segments[p],
+                          achieved=achieved[p], fraction=achieved[p] / segments[p] if segments[p] else 0.0,
+                          evaluations=evaluations[p]) for p in range(len(status))]
+
+
+def approach_poses(targets, distance, axis=(0, 0, 1)):
+    """The pre-poses of straight approaches: target . translate(-distance * axis), the axis in the tool frame (its length
+    is normalised) -> float32 [P][4][4]"""
+    t = np.asarray(targets, np.float64)
+    if t.ndim < 2 or int(np.prod(t.shape[1:])) != 16:
+        raise TypeError("expected targets as [P][4][4] (or [P][16]) frames")
+    t = t.reshape(-1, 4, 4)
+    a = np.asarray(axis, np.float64)
+    if a.shape != (3,) or not np.isfinite(a).all() or not np.linalg.norm(a) > 0:
+        raise ValueError("axis must be a finite, non-zero 3-vector")
+    d = float(distance)
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError("distance must be positive and finite")
+    pre = t.copy()
+    pre[:, :3, 3] = t[:, :3, 3] - d * (t[:, :3, :3] @ (a / np.linalg.norm(a)))
+    return pre.astype(np.float32)
+
+
+@dataclass
+class Approach:
+    """approach_multi's answer for one target: goals [G][dim], the pre-pose configurations whose straight approach is
+    complete (what rrtc_multi_goals takes), and paths, one float32 [len][dim] approach path per goal, from the goal to
+    the target"""
+    goals: np.ndarray
+    paths: list
+
+
+def approach_multi(robot, targets, environments, distance, axis=(0, 0, 1), ik_settings=None, settings=None):
+    """Straight tool-frame approaches to many targets: per target the pre-pose is approach_poses' (the target moved back
+    by `distance` along `axis` in the tool frame); ONE ik_goals call over the pre-poses (ik_settings) gives each target's
+    collision-free pre-pose configurations, ONE cartesian_multi call leads every one of them to its target (settings),
+    and a goal is kept if its approach is complete.  environments: one per target, or a single Environment / None for
+    all.  -> list[Approach], one per target; Approach.goals goes straight into rrtc_multi_goals (leave out the targets
+    whose goals are empty), Approach.paths are the motions that follow the plan.  A retreat is an approach reversed."""
+    targets = np.asarray(targets, np.float32)
+    pre = approach_poses(targets, distance, axis)
+    targets = targets.reshape(-1, 4, 4)
+    n = len(targets)
+    envs = list(environments) if isinstance(environments, (list, tuple)) else [environments] * n
+    if len(envs) != n:
+        raise ValueError(f"{n} targets, but {len(envs)} environments")
+    goal_sets, _ = ik_goals(robot, pre, envs, settings=ik_settings)
+    counts = [len(g) for g in goal_sets]
+    dim = robot.dimension()
+    starts = np.concatenate(goal_sets + [np.zeros((0, dim), np.float32)])
+    which = np.repeat(np.arange(n), counts)
+    lines = cartesian_multi(robot, starts, targets[which], [envs[p] for p in which], settings) if len(starts) else []
+    out = [Approach(np.zeros((0, dim), np.float32), []) for _ in range(n)]
+    for p, line in zip(which, lines):
+        if line.complete:
+            out[p].goals = np.concatenate([out[p].goals, line.path[:1]])
+            out[p].paths.append(line.path)
+    return out
+
+
 @dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
