@@ -834,6 +834,87 @@ int vmv_cartesian_summary(const vmv_cartesian *result, uint8_t *status, uint32_t
 int vmv_cartesian_points(const vmv_cartesian *result, float *out, size_t capacity_floats);
 int vmv_cartesian_destroy(vmv_cartesian *result);
 
+/* ---- time-optimal trajectories along many independent paths (no counterpart in the reference) ----------- */
+/* Path p: waypoints points[offsets[p] .. offsets[p+1]) ([dim] each), in environment envs[p]; envs == NULL: nothing is
+ * validated.  vel_limits, acc_limits: [dim], finite and > 0 (no robot model here carries any).  Per path the call gives a
+ * C1 path of straight pieces with parabolic blends at the corners, the time-optimal rest-to-rest velocity profile along it
+ * under |qdot_j| <= vel_limits[j] (at the grid points) and |qddot_j| <= acc_limits[j] (everywhere), and that trajectory
+ * sampled every dt.  No jerk limits, no torque limits, no non-zero end velocities.
+ *   Set-up (host, float64 from the fp32 waypoints): a waypoint equal to its predecessor is dropped; edge lengths L_e are L2
+ *     norms summed over the joints in order, u_e the unit directions; blend half-length d_i = min(blend, L_{i-1} / 2,
+ *     L_i / 2) at every inner waypoint, 0 with stop_at_waypoints.  Pieces in order: the line of edge e from w_e + d_e u_e,
+ *     span L_e - d_e - d_{e+1}, left out when it is not above 1e-9; the blend at waypoint i (d_i > 0) from w_i - d_i u_in,
+ *     span 2 d_i, q(s) = base + u_in s + 1/2 q'' s^2 with q'' = (u_out - u_in) / (2 d_i).  A corner with d_i = 0 is a stop
+ *     point, as are the first and the last grid point.  Every piece is cut into n = max(2, ceil(span / grid_step)) equal
+ *     intervals; N = their sum; N > max_grid: VMV_RETIME_TOO_LONG.  The piece records (base, u_in, u_out, d, span, n,
+ *     first grid index, stop flag) go to the device rounded to fp32.
+ *   Profile (device, fp32, one rounding per written operation; x = sdot^2, u = sddot constant per interval): per piece
+ *     Delta = span / float(n), q''_j = (u_out_j - u_in_j) / (d + d) (0 on a line); interval k of a piece has s0 =
+ *     float(k) Delta, s1 = float(k + 1) Delta, tangents a0 = u_in + q'' s0, a1 = u_in + q'' s1.  Per joint two constraints
+ *     |c u + e x| <= A_j with (c, e) = (a0_j, q''_j) and (a1_j + (2 Delta) q''_j, q''_j): with |c| > 1e-6 the band
+ *     |u - s x| <= g, s = (-e) / c, g = A_j / |c|; else, with e != 0, the cap x <= A_j / |e|.  Velocity caps
+ *     (V_j / |a_j|)^2 over both tangents that meet at a grid point and have |a_j| > 1e-6; 0 at a stop point.  The reach
+ *     lines are u >= -x / (2 Delta) and u <= (K_{i+1} - x) / (2 Delta).  Backward from K_N = 0: K_i = max(0, min(caps,
+ *     velocity caps, (g_p + g_q) / (s_p - s_q) over all bands with s_p - s_q > 0, and the reach lines against every band
+ *     with both sides of the quotient multiplied by 2 Delta, so that an interval of 1e-9 costs no digit:
+ *     (g_q (2 Delta)) / (-1 - s_q (2 Delta)) where that denominator is > 0, (K_{i+1} + g_p (2 Delta)) / (1 + s_p (2 Delta))
+ *     where that is > 0)).  A minimum of non-NaN values does not depend on its order.  Forward from x_0 = 0: u_i =
+ *     max(min(min_q (g_q + s_q x), (K_{i+1} - x) / (2 Delta)), max(max_p (s_p x - g_p), (-x) / (2 Delta))), x_{i+1} =
+ *     min(max(x + (2 Delta) u_i, 0), K_{i+1}), T_{i+1} = T_i + (2 Delta) / (sqrt(x_i) + sqrt(x_{i+1})).  u_i stays the
+ *     value chosen (it is NOT recomputed from x_{i+1} - x_i: on a line of 1e-8 between two blends one ulp of x over
+ *     2 Delta is several times the acceleration limit).  A non-finite time: VMV_RETIME_STALLED.
+ *   Samples: samples = ceil(T / dt) + 1 in float64; above max_samples: VMV_RETIME_TOO_LONG.  Sample k (device, fp32):
+ *     t = min(float(k) dt, T); i = the last interval with T_i <= t; tau = t - T_i; sigma = min(max(sqrt(x_i) tau +
+ *     (u_i / 2) (tau tau), 0), Delta); s = s0 + sigma; x(s) = max(x_i + (u_i + u_i) sigma, 0); position (base + u_in s) +
+ *     (q'' / 2) (s s); velocity q'(s) sqrt(x(s)) with q'(s) = u_in + q'' s; acceleration q'(s) u_i + q'' x(s).  Row 0 and
+ *     the last row carry the first and the last waypoint's own bits, with zero velocity.
+ *   Validation (envs != NULL): all consecutive sample pairs of all sampled paths in ONE
+ *     vmv_validate_motion_batch_multi call, each path in its own environment; a path with an invalid pair is
+ *     VMV_RETIME_COLLISION with first_invalid = the first invalid pair's index.  The samples are returned whole.
+ *   A NaN or infinite waypoint: VMV_RETIME_NON_FINITE.  A path without waypoints: no samples; a path of one distinct
+ *     waypoint (or one whose lines are all at most 1e-9 long): one sample, duration 0, VMV_RETIME_COMPLETE.  Paths that
+ *     are TOO_LONG, NON_FINITE or STALLED have no samples.
+ * A path's result depends on its own waypoints, environment, the limits and the settings alone, bit for bit - not on the
+ * batch or its place in it.
+ * Checks before anything is launched, device-free ones first, vmv_last_error() names the argument: unknown robot; NULL
+ * settings / out / vel_limits / acc_limits / offsets; blend, grid_step or dt NaN or infinite; grid_step or dt in (0, 1e-6);
+ * max_grid above 4,096; stop_at_waypoints other than 0 / 1; a limit that is not finite and > 0; n >= 2^31; offsets[0] != 0
+ * or decreasing offsets; 2^31 waypoints or more; NULL points with waypoints (all VMV_ERR_INVALID_ARGUMENT); then, with
+ * envs, vmv_validate_batch_multi's checks of the handles (NULL, finalized) with its messages; n == 0 is VMV_OK with an
+ * empty result and no device; a device at all; the environments' device and the robot's parts (built in one batch).  A call
+ * that fails leaves *out untouched.  Synchronous, host buffers, default stream; repeated handles are allowed. */
+enum
+{
+    VMV_RETIME_COMPLETE = 0,
+    VMV_RETIME_COLLISION = 1,
+    VMV_RETIME_TOO_LONG = 2,
+    VMV_RETIME_NON_FINITE = 3,
+    VMV_RETIME_STALLED = 4
+};
+#define VMV_RETIME_NONE 0xffffffffu /* first_invalid of a path without an invalid sample pair */
+typedef struct
+{
+    float blend;           /* largest blend half-length, in joint-space distance; <= 0: default (0.1) */
+    float grid_step;       /* largest interval of the profile's grid; <= 0: default (0.02); else at least 1e-6 */
+    float dt;              /* sampling period in seconds; <= 0: default (0.01); else at least 1e-6 */
+    uint32_t max_grid;     /* cap on a path's intervals, at most 4,096; 0: default (4,096) */
+    uint32_t max_samples;  /* cap on a path's samples; 0: default (65,536) */
+    int stop_at_waypoints; /* 0 / 1: no blends, the trajectory rests at every waypoint and stays on the polyline */
+} vmv_retime_settings;
+typedef struct vmv_trajectories vmv_trajectories;
+int vmv_retime_multi(int robot, const vmv_env *const *envs /* [n] or NULL */, size_t n, const float *points,
+                     const size_t *offsets /* [n + 1] */, const float *vel_limits /* [dim] */, const float *acc_limits /* [dim] */,
+                     const vmv_retime_settings *settings, vmv_trajectories **out);
+/* Per path (arrays of n, any may be NULL): status (VMV_RETIME_*), intervals, samples, duration, first_invalid.  Totals (may
+ * be NULL): the validation calls made (0 or 1) and the sample pairs asked. */
+int vmv_retime_summary(const vmv_trajectories *result, uint8_t *status, uint32_t *intervals, uint32_t *samples, float *duration,
+                       uint32_t *first_invalid, uint64_t *validation_calls, uint64_t *questions);
+/* every path's samples, packed in path order: times [S], positions, velocities, accelerations [S][dim]; VMV_ERR_CAPACITY
+ * if capacity_samples is below S (nothing is written) */
+int vmv_retime_samples(const vmv_trajectories *result, float *times, float *positions, float *velocities, float *accelerations,
+                       size_t capacity_samples);
+int vmv_retime_destroy(vmv_trajectories *result);
+
 /* ---- lockstep AORRTC: cost-bounded RRT-Connect searches for many independent problems --------------------- */
 /* AORRTC (planning/aorrtc.hh, one goal, PHS sampling, no dynamic domain) for n_problems problems at once; the arguments
  * are those of vmv_rrtc_multi.  Per problem:

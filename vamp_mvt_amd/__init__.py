@@ -729,6 +729,35 @@ def _cartesian_settings_struct(settings):
                                   max_wp, int(bool(settings.position_only)))
 
 
+def _retime_settings_struct(settings):
+    """vmv_retime_settings from a RetimeSettings-shaped object, checked as the library checks it (0 or a negative number
+    asks for the library's default)"""
+    values = {k: float(getattr(settings, k)) for k in ("blend", "grid_step", "dt")}
+    for k, v in values.items():
+        if not np.isfinite(v):
+            raise ValueError(f"{k} must be finite")
+    for k in ("grid_step", "dt"):
+        if 0 < values[k] < 1e-6:
+            raise ValueError(f"{k} must be at least 1e-6 (0 = default)")
+    max_grid, max_samples = int(settings.max_grid), int(settings.max_samples)
+    if not 0 <= max_grid <= 4096:
+        raise ValueError("max_grid must be from 0 (default) to 4,096")
+    if not 0 <= max_samples < 2 ** 32:
+        raise ValueError("max_samples must be from 0 (default) and fit 32 bits")
+    return _lib.RetimeSettings(values["blend"], values["grid_step"], values["dt"], max_grid, max_samples,
+                               int(bool(settings.stop_at_waypoints)))
+
+
+def _joint_limits(limits, dim, name):
+    """-> float32 [dim], every entry finite and positive"""
+    a = _f32(limits)
+    if a.shape != (dim,):
+        raise TypeError(f"expected {name} as [{dim}] values")
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError(f"{name} must be finite and positive")
+    return a
+
+
 class IKSettings:
     """vmv_ik_settings (include/vamp_mvt_amd.h) with the defaults of <robot>.ik_batch: n_seeds seeds per target (1 ..
     1,024), max_iterations, pos_tol (m), rot_tol (rad; the sine of the residual angle is compared), rot_weight (metres per
@@ -1458,6 +1487,49 @@ class _Robot(types.ModuleType):
         offsets[1:] = np.cumsum(achieved.astype(np.int64) + 1)
         return dict(status=status, segments=segments, achieved=achieved, evaluations=evaluations, points=points,
                     offsets=offsets, validation_calls=int(calls.value), questions=int(questions.value))
+
+    def retime_multi_raw(self, paths, vel_limits, acc_limits, environments, settings):
+        """vmv_retime_multi: time-optimal trajectories along many paths in one call, path p ([len][dim] waypoints, any
+        length) in environments[p] (None = the empty environment); environments=None: nothing is validated.  vel_limits,
+        acc_limits: [dim], finite and positive.  settings: the fields of planning.RetimeSettings.  -> dict of per-path
+        numpy arrays (status, intervals, samples, duration, first_invalid; UINT32_MAX = none), the packed samples (times,
+        positions, velocities, accelerations) with their offsets, and the totals validation_calls and questions.
+        planning.retime_multi is the caller-facing form.  Every argument is checked before any library call."""
+        if environments is not None:
+            environments = list(environments)
+            _check_environments(environments)
+        pts, packed, offsets = _packed_paths(paths, self._dim)
+        n = len(pts)
+        if environments is not None:
+            _one_per(environments, n, "path")
+        vel, acc = _joint_limits(vel_limits, self._dim, "vel_limits"), _joint_limits(acc_limits, self._dim, "acc_limits")
+        cs = _retime_settings_struct(settings)
+        status, intervals, samples = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        duration, first_invalid = np.zeros(n, np.float32), np.full(n, 0xffffffff, np.uint32)
+        arrays = [np.zeros(0, np.float32)] + [np.zeros((0, self._dim), np.float32) for _ in range(3)]
+        calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if n > 0:
+            handles = None
+            if environments is not None:
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+            out = ctypes.c_void_p()
+            check(lib.vmv_retime_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p), _fp(vel),
+                                       _fp(acc), ctypes.byref(cs), ctypes.byref(out)), "vmv_retime_multi")
+            try:
+                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (intervals, samples)]
+                check(lib.vmv_retime_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, _fp(duration),
+                                             first_invalid.ctypes.data_as(_lib.c_u32_p), ctypes.byref(calls),
+                                             ctypes.byref(questions)), "vmv_retime_summary")
+                total = int(samples.sum())
+                arrays = [np.zeros(total, np.float32)] + [np.zeros((total, self._dim), np.float32) for _ in range(3)]
+                check(lib.vmv_retime_samples(out, *[_fp(x) for x in arrays], total), "vmv_retime_samples")
+            finally:
+                lib.vmv_retime_destroy(out)
+        sample_offsets = np.zeros(n + 1, np.int64)
+        sample_offsets[1:] = np.cumsum(samples.astype(np.int64))
+        return dict(status=status, intervals=intervals, samples=samples, duration=duration, first_invalid=first_invalid,
+                    times=arrays[0], positions=arrays[1], velocities=arrays[2], accelerations=arrays[3],
+                    offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value))
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

@@ -98,6 +98,12 @@ class CartesianSettings(ctypes.Structure):
                 ("max_waypoints", ctypes.c_uint32), ("position_only", ctypes.c_int)]
 
 
+class RetimeSettings(ctypes.Structure):
+    """vmv_retime_settings"""
+    _fields_ = [("blend", ctypes.c_float), ("grid_step", ctypes.c_float), ("dt", ctypes.c_float),
+                ("max_grid", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("stop_at_waypoints", ctypes.c_int)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -247,6 +253,11 @@ def _load():
         "vmv_cartesian_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_cartesian_points": (I, [V, c_float_p, S]),
         "vmv_cartesian_destroy": (I, [V]),
+        "vmv_retime_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, c_float_p, c_float_p,
+                                 ctypes.POINTER(RetimeSettings), ctypes.POINTER(V)]),
+        "vmv_retime_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_float_p, c_u32_p, c_u64_p, c_u64_p]),
+        "vmv_retime_samples": (I, [V, c_float_p, c_float_p, c_float_p, c_float_p, S]),
+        "vmv_retime_destroy": (I, [V]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

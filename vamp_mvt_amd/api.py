@@ -517,8 +517,14 @@ def install(robot):
         the device -> list[planning.CartesianPath]."""
         return planning.cartesian_multi(robot, starts, targets, environments, settings)
 
+    def retime_multi(paths, vel_limits, acc_limits, environments=None, settings=None):
+        """planning.retime_multi with this robot: time-optimal trajectories along many paths in one call on the device
+        -> list[planning.Trajectory]."""
+        return planning.retime_multi(robot, paths, vel_limits, acc_limits, environments, settings)
+
     robot.optimize_multi = optimize_multi
     robot.cartesian_multi = cartesian_multi
+    robot.retime_multi = retime_multi
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals

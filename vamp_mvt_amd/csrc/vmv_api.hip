@@ -92,6 +92,12 @@ namespace vmv
 {
     int hip_status(hipError_t e, const char *what) { return hip_fail(e, what); }
 
+    int refuse_argument(const char *message)
+    {
+        g_last_error = message;
+        return VMV_ERR_INVALID_ARGUMENT;
+    }
+
     // ---- per-(device, stream) tables of vmv_validate_batch_multi (vmv_common.h: MultiTableLease) ----
     namespace
     {

@@ -148,6 +148,7 @@ namespace vmv
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;
 
     int hip_status(hipError_t e, const char *what);  // records vmv_last_error(), maps to VMV_ERR_*
+    int refuse_argument(const char *message);        // records vmv_last_error(), returns VMV_ERR_INVALID_ARGUMENT
 
     // Element j of Halton sample number k (1-based) of the reference's sequence (random/halton.hh:75-108): the
     // incremental float arithmetic there keeps exact integers n, d = b^digits, so the value is n / d with n the

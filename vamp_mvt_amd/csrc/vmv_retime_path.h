@@ -1,0 +1,157 @@
+// vmv_retime_path.h — the host steps of vmv_retime_multi that make no device call (include/vamp_mvt_amd.h):
+// the float64 set-up of a blended path from fp32 waypoints (its pieces, their grid) and the sample count of a duration.
+// Plain C++ without a HIP header, so that tests/native/retime_sanitize.cc compiles it on its own.
+#pragma once
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace vmv
+{
+    constexpr uint32_t kRetimeMaxDim = 16;
+    constexpr uint32_t kRetimeMaxGrid = 4096;        // the cap of max_grid: K of a whole path fits the profile kernel's LDS
+    constexpr double kRetimeMinSpan = 1e-9;          // a line that is not longer is left out
+    constexpr uint32_t kRetimeMinIntervals = 2;      // per piece: a stretch between two stops needs an inner grid point
+
+    // One piece of the blended path as the kernels read it (fp32): q(s) = base + u_in s + 1/2 q'' s^2 for s in [0, span],
+    // q'' = (u_out - u_in) / (2 d) on a blend (d > 0) and 0 on a line (d == 0, u_in == u_out).
+    struct RetimePiece
+    {
+        float base[kRetimeMaxDim], u_in[kRetimeMaxDim], u_out[kRetimeMaxDim];
+        float d, span;
+        uint32_t n;      // equal intervals of the piece, at least 2
+        uint32_t first;  // grid index of its first point within the path
+        uint32_t stop;   // 1: its first point is a stop point
+        uint32_t pad;
+    };
+    static_assert(sizeof(RetimePiece) == 216, "48 floats, d, span, n, first, stop, pad");
+
+    enum RetimeSetup
+    {
+        kRetimeOk = 0,       // pieces and intervals are set
+        kRetimeTrivial = 1,  // fewer than two distinct waypoints, or no piece: `distinct` says how many samples (0 or 1)
+        kRetimeTooLong = 2,  // more than max_grid intervals: `intervals` is set, no pieces
+        kRetimeNonFinite = 3
+    };
+
+    struct RetimePath
+    {
+        RetimeSetup what = kRetimeTrivial;
+        uint32_t distinct = 0;   // distinct waypoints
+        uint64_t intervals = 0;  // N
+        std::vector<RetimePiece> pieces;
+    };
+
+    // waypoints [count][dim] (fp32, any values); blend, grid_step positive and finite; dim <= 16
+    inline RetimePath retime_path(const float *waypoints, size_t count, size_t dim, double blend, double grid_step,
+                                  uint32_t max_grid, bool stop_at_waypoints)
+    {
+        RetimePath P;
+        for (size_t k = 0; k < count * dim; ++k)
+            if (!std::isfinite(waypoints[k]))
+            {
+                P.what = kRetimeNonFinite;
+                return P;
+            }
+        std::vector<size_t> keep;  // a waypoint equal to its predecessor is dropped
+        for (size_t i = 0; i < count; ++i)
+        {
+            bool same = !keep.empty();
+            for (size_t j = 0; same && j < dim; ++j) same = waypoints[i * dim + j] == waypoints[keep.back() * dim + j];
+            if (!same) keep.push_back(i);
+        }
+        const size_t m = keep.size();
+        P.distinct = (uint32_t) (m < 2 ? m : 2);
+        if (m < 2) return P;
+
+        const size_t edges = m - 1;
+        std::vector<double> L(edges), u(edges * dim), d(m, 0.0);
+        for (size_t e = 0; e < edges; ++e)
+        {
+            const float *a = waypoints + keep[e] * dim, *b = waypoints + keep[e + 1] * dim;
+            double sum = 0.0;
+            for (size_t j = 0; j < dim; ++j)
+            {
+                const double diff = (double) b[j] - (double) a[j];
+                u[e * dim + j] = diff;
+                sum += diff * diff;
+            }
+            L[e] = std::sqrt(sum);
+            for (size_t j = 0; j < dim; ++j) u[e * dim + j] /= L[e];
+        }
+        if (!stop_at_waypoints)
+            for (size_t i = 1; i + 1 < m; ++i) d[i] = std::fmin(blend, std::fmin(0.5 * L[i - 1], 0.5 * L[i]));
+
+        uint64_t grid = 0;
+        bool stop_next = true;  // the first grid point is a stop point
+        const auto add = [&](const double *base, const double *uin, const double *uout, double half, double span) {
+            RetimePiece R{};
+            for (size_t j = 0; j < dim; ++j) R.base[j] = (float) base[j], R.u_in[j] = (float) uin[j], R.u_out[j] = (float) uout[j];
+            R.d = (float) half, R.span = (float) span;
+            const double need = std::ceil(span / grid_step);
+            const uint64_t n = need < (double) kRetimeMinIntervals ? kRetimeMinIntervals :
+                               need < 4294967295.0 ? (uint64_t) need : 4294967295ull;  // (the quotient may be huge; never NaN)
+            R.n = (uint32_t) n, R.first = (uint32_t) (grid < 4294967295ull ? grid : 4294967295ull), R.stop = stop_next ? 1u : 0u;
+            grid += n, stop_next = false;
+            if (grid <= max_grid) P.pieces.push_back(R);
+        };
+        std::vector<double> base(dim);
+        for (size_t e = 0; e < edges; ++e)
+        {
+            const double *ue = u.data() + e * dim;
+            const float *w = waypoints + keep[e] * dim, *w1 = waypoints + keep[e + 1] * dim;
+            const double span = L[e] - d[e] - d[e + 1];
+            if (span > kRetimeMinSpan)
+            {
+                for (size_t j = 0; j < dim; ++j) base[j] = (double) w[j] + d[e] * ue[j];
+                add(base.data(), ue, ue, 0.0, span);
+            }
+            if (e + 1 < edges)
+            {
+                if (d[e + 1] > 0.0)
+                {
+                    for (size_t j = 0; j < dim; ++j) base[j] = (double) w1[j] - d[e + 1] * ue[j];
+                    add(base.data(), ue, ue + dim, d[e + 1], 2.0 * d[e + 1]);
+                }
+                else
+                    stop_next = true;  // a corner without a blend
+            }
+        }
+        P.intervals = grid;
+        if (grid > max_grid)
+        {
+            P.what = kRetimeTooLong;
+            P.pieces.clear();
+            return P;
+        }
+        if (P.pieces.empty())  // every line at most 1e-9 long and no blend: the path is its first waypoint
+        {
+            P.distinct = 1;
+            return P;
+        }
+        P.what = kRetimeOk;
+        return P;
+    }
+
+    // samples of a trajectory of duration T sampled every dt (both fp32 values, T >= 0 finite, dt > 0): ceil(T / dt) + 1 in
+    // float64, saturated at 2^32 - 1
+    inline uint64_t retime_samples(float T, float dt)
+    {
+        const double need = std::ceil((double) T / (double) dt) + 1.0;
+        return need < 4294967295.0 ? (uint64_t) need : 4294967295ull;
+    }
+
+    // The first invalid edge [first, first + edges) of a path among the packed answers of vmv_validate_motion_batch_multi,
+    // or `none`.
+    inline uint32_t retime_first_invalid(const uint64_t *bits, uint64_t first, uint32_t edges, uint32_t none)
+    {
+        for (uint32_t e = 0; e < edges; ++e)
+        {
+            const uint64_t b = first + e;
+            if (!((bits[b >> 6] >> (b & 63u)) & 1ull)) return e;
+        }
+        return none;
+    }
+}  // namespace vmv

@@ -990,6 +990,63 @@ def approach_multi(robot, targets, environments, distance, axis=(0, 0, 1), ik_se
     return out
 
 
+RETIME_STATUS = ("complete", "collision", "too_long", "non_finite", "stalled")  # VMV_RETIME_*
+
+
+@dataclass
+class RetimeSettings:
+    """vmv_retime_settings with its defaults: blend (the largest blend half-length at a corner, in joint-space distance),
+    grid_step (the largest interval of the velocity profile's grid), dt (the sampling period, s), max_grid (intervals per
+    path, at most 4,096), max_samples and stop_at_waypoints (no blends: the trajectory rests at every waypoint and stays on
+    the polyline).  blend, grid_step and dt are choices, not measurements."""
+    blend: float = 0.1
+    grid_step: float = 0.02
+    dt: float = 0.01
+    max_grid: int = 4096
+    max_samples: int = 65536
+    stop_at_waypoints: bool = False
+
+
+@dataclass
+class Trajectory:
+    """retime_multi's answer for one path: times [S], positions / velocities / accelerations [S][dim] sampled every dt
+    (the last sample at `duration`), `status` (one of RETIME_STATUS), the intervals of the profile's grid and
+    first_invalid, the first sample pair validate_motion rejects (-1: none)"""
+    times: np.ndarray
+    positions: np.ndarray
+    velocities: np.ndarray
+    accelerations: np.ndarray
+    duration: float
+    status: str
+    intervals: int
+    first_invalid: int
+
+    @property
+    def complete(self):
+        return self.status == "complete"
+
+
+def retime_multi(robot, paths, vel_limits, acc_limits, environments=None, settings=None):
+    """Time-optimal trajectories along many paths in one call, on the device: path p ([len][dim] waypoints) becomes a C1
+    path of straight pieces with parabolic blends at the corners, traversed from rest to rest as fast as |qdot_j| <=
+    vel_limits[j] and |qddot_j| <= acc_limits[j] allow, and sampled every dt -> list[Trajectory].  environments[p] (None =
+    the empty environment) is where the sampled trajectory is validated, because the blends leave the polyline;
+    environments=None: nothing is validated.  A "collision" comes with first_invalid and the whole trajectory: lower
+    `blend` or set stop_at_waypoints.  No jerk limits, no torque limits, no non-zero end velocities; velocity is bounded
+    at the grid points and acceleration everywhere on the path.  include/vamp_mvt_amd.h (vmv_retime_multi) gives every
+    step."""
+    s = settings if settings is not None else RetimeSettings()
+    raw = robot.retime_multi_raw(paths, vel_limits, acc_limits, environments, s)
+    off = raw["offsets"].tolist()
+    status, intervals = raw["status"].tolist(), raw["intervals"].tolist()
+    duration, bad = raw["duration"].tolist(), raw["first_invalid"].tolist()
+    return [Trajectory(times=raw["times"][off[p]:off[p + 1]].copy(), positions=raw["positions"][off[p]:off[p + 1]].copy(),
+                       velocities=raw["velocities"][off[p]:off[p + 1]].copy(),
+                       accelerations=raw["accelerations"][off[p]:off[p + 1]].copy(), duration=duration[p],
+                       status=RETIME_STATUS[status[p]], intervals=intervals[p],
+                       first_invalid=-1 if bad[p] == 0xffffffff else bad[p]) for p in range(len(status))]
+
+
 @dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
