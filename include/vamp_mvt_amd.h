@@ -361,6 +361,71 @@ int vmv_ik_batch(int robot, const float *d_targets /* [n_targets][16] */, size_t
 int vmv_ik_batch_host(int robot, const float *targets, size_t n_targets, const float *seeds, uint64_t halton_skip,
                       const vmv_ik_settings *settings, float *q, float *err, uint32_t *status);
 
+/* ---- end-effector constraints (no counterpart in the reference) -------------------------------------- */
+/* A tolerance band on the end-effector frame (R, t) of a configuration: a position box in a frame C and a cone for one
+ * tool axis, each optional.  csrc/vmv_constraint.h states the set-up, the residual, the band test, the projection and
+ * the edge test in full; in short:
+ *   position  p = C_R^T (t - C_t) with pos_lo <= p <= pos_hi per axis;
+ *   axis      the angle between R tool_axis and C_R ref_axis is at most max_angle (axes normalised by the set-up);
+ *   band test the nominal band widened by pos_tol and rot_tol: everyone - the projection's converged test, the check of a
+ *             configuration, every sample of an edge - asks this one test, in fp32 on the frame vmv_eefk_batch computes;
+ *   residual  v_k = p_k - clamp(p_k, lo_k, hi_k) and the sine of the angle beyond max_angle, about a x d.
+ * The constraint records are HOST memory in every entry point (the set-up runs on the host in float64); n_constraints is
+ * 1 (shared by all lanes) or n (one per lane). */
+typedef struct
+{
+    float frame[16];            /* rigid frame C in the world, row-major 4 x 4 (R^T R = I within 1e-4) */
+    float pos_lo[3], pos_hi[3]; /* bounds on p = C_R^T (t - C_t); -inf / +inf = free; lo == hi allowed (a plane, a line) */
+    float tool_axis[3];         /* in the end-effector frame */
+    float ref_axis[3];          /* in C */
+    float max_angle;            /* bound on the angle between R tool_axis and C_R ref_axis; 0 = orientation free; <= pi/2 */
+} vmv_ee_constraint;
+typedef struct
+{
+    uint32_t max_iterations;               /* 0 = 16: evaluations after the first; below 2^30 */
+    float pos_tol, rot_tol;                /* 0 = 1e-4 m, 1e-3 rad: the band everyone tests is the nominal one widened by these */
+    float rot_weight, damping, max_step;   /* 0 = vmv_ik_settings' defaults (0.25, 1e-2, 0.5) */
+    float check_step;                      /* 0 = 0.05: joint-space distance between two band samples of an edge */
+} vmv_constraint_settings;
+/* The layout of vmv_constraint_settings is final at these seven fields (28 bytes) for vmv_abi_version() 1: it is passed by
+ * pointer without a size, so it never grows.  A later call that needs more settings (a planner's, say) takes a struct of
+ * its own that holds this one as its first member `base`, as vmv_rrtc_goals_settings holds vmv_rrtc_settings. */
+/* Projection into the band: vmv_ik_batch's damped least-squares iteration (its Jacobian, Cholesky solve, bound-hold rule,
+ * step cap, clip to the joint bounds and damping schedule) on the residual above, one lane per configuration.  d_q_out
+ * [n][dim] is the accepted state of smallest residual energy, inside the joint bounds but for the two kinds of rows below that come
+ * back as given, which are not clipped; only joints that move the end effector change.  d_residuals [n][2] (may be NULL): |v| in metres and the angle beyond max_angle in radians of that
+ * state.  d_status [n]: bit 31 converged (the band test passes), bit 30 a non-finite joint (the row comes back as given
+ * with NaN residuals), the low bits the evaluations after the first.  A configuration inside the joint bounds and in
+ * the band comes back bit for bit with 0 evaluations; one whose axes are antiparallel once clipped to the joint bounds
+ * comes back as given (unclipped, so outside the bounds if it was), not converged, with 0 evaluations.  A lane's result depends on its own configuration, constraint and settings alone, bit for bit.  d_q_out
+ * must not overlap d_q.
+ * Checks before any launch, in this order: unknown robot; NULL d_q / constraints / settings / d_q_out / d_status ("null
+ * pointer"); n_constraints not 1 and not n; the settings in the struct's order (finite, not negative); n >= 2^31; then
+ * every constraint in order: non-finite frame, NaN bounds, pos_lo > pos_hi, non-finite axes, NaN max_angle, a frame that
+ * is not rigid within 1e-4, max_angle outside [0, pi/2], a zero axis with max_angle > 0 (all VMV_ERR_INVALID_ARGUMENT,
+ * vmv_last_error() names the check and the constraint's index).  A refused call writes nothing; n == 0 is VMV_OK without
+ * a device. */
+int vmv_constraint_project_batch(int robot, const float *d_q /* [n][dim] */, size_t n, const vmv_ee_constraint *constraints,
+                                 size_t n_constraints, const vmv_constraint_settings *settings, float *d_q_out /* [n][dim] */,
+                                 float *d_residuals /* [n][2], may be NULL */, uint32_t *d_status /* [n] */, void *stream);
+int vmv_constraint_project_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints,
+                                      size_t n_constraints, const vmv_constraint_settings *settings, float *q_out,
+                                      float *residuals, uint32_t *status);
+/* The band test of n configurations: bit i of d_bits (ceil(n / 64) words, the unused bits 0) is 1 iff configuration i is
+ * in the band; d_residuals [n][2] (may be NULL) as above, NaN for a non-finite row.  The checks of the projection, with
+ * d_bits in place of the outputs. */
+int vmv_constraint_check_batch(int robot, const float *d_q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                               const vmv_constraint_settings *settings, uint64_t *d_bits, float *d_residuals, void *stream);
+int vmv_constraint_check_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                    const vmv_constraint_settings *settings, uint64_t *bits, float *residuals);
+/* The band test of n edges a -> b: n_c = max(1, ceil(|b - a| / check_step)) samples a + (b - a) * (i / n_c), i = 1 .. n_c,
+ * d_ok[e] = 1 iff all of them are in the band, else 0; an edge of more than 1,024 samples or of non-finite length answers
+ * 0.  One wave per edge.  The checks of the projection, with d_a, d_b and d_ok as the arrays. */
+int vmv_constraint_check_motion_batch(int robot, const float *d_a, const float *d_b, size_t n, const vmv_ee_constraint *constraints,
+                                      size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *d_ok, void *stream);
+int vmv_constraint_check_motion_batch_host(int robot, const float *a, const float *b, size_t n, const vmv_ee_constraint *constraints,
+                                           size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *ok);
+
 /* sphere_environment_in_collision(environment, x, y, z, r) — collision/validity.hh:47-158, the predicate every fkcc
  * check is made of (and CAPT::collides / MVT::collides behind it, collision/capt.hh:374-415), for a batch of free
  * spheres: spheres [n][4] = x y z r, hits[i] = 1 iff sphere i collides with the environment.  Each sphere is its own
@@ -483,6 +548,38 @@ int vmv_rrtc_multi_goals(int robot, const vmv_env *const *envs, size_t n_problem
                          vmv_plans **out);
 /* Per problem of a vmv_rrtc_multi_goals result (n_problems, may be NULL): the index, within its own set, of the goal its
  * path ends in; UINT32_MAX = unsolved.  VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
+/* RRT-Connect under an end-effector constraint: vmv_rrtc_multi_goals - its arguments, its checks in its
+ * order, its state machine (extension, connect march, dynamic domain, goal sets, start_tree_first, the limits, the trace)
+ * and its result - with every tree node projected into the band of the problem's constraint and every edge band-checked.
+ *   Before the rounds ONE band test (vmv_constraint_check_batch's) runs over all starts and goals.  A problem whose start
+ *     is out of band or that has no in-band goal ends VMV_PLAN_INVALID_ENDPOINT with no path and no question; the
+ *     out-of-band goals of a set are never roots and never asked (goal indices still count within the caller's set).
+ *   A round: the step kernel writes each problem's question; then one launch per round projects the question's far end
+ *     where it is a new node (the extension's `new`, a march step's point; vmv_constraint_project_batch's lane, bit for
+ *     bit) and writes it back to the question and to the tree.  A projection that does not converge, or lands farther
+ *     than max_stretch * range from the question's near end, leaves both as they were and answers 0.  Then the edge's band
+ *     test (vmv_constraint_check_motion_batch's, bit for bit).  The answer the state machine consumes is validity AND
+ *     that.  A direct question start -> goal is band-checked only.
+ *   The path: its waypoints are in the band and its edges pass the edge test at check_step; the last point of a connect
+ *     march lies within one fp32 rounding of the node it reaches, and that closing step is not asked, as in
+ *     vmv_rrtc_multi.  With a constraint that restricts nothing the result is vmv_rrtc_multi_goals's byte for byte while
+ *     every node lies inside the joint bounds (the projection clips to them).
+ * Further checks, after vmv_rrtc_multi_goals's and before any device call: NULL constraints / constraint_settings ("null
+ * pointer"); n_constraints not 1 and not n_problems; the settings as the batch calls check them; max_stretch (finite, not
+ * negative); every constraint (VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the check).  A problem's result is its
+ * own, whatever the batch, its order and check_every.  Readouts: vmv_plans_summary / _paths / _goal_indices / _destroy. */
+typedef struct
+{
+    vmv_constraint_settings base;
+    float max_stretch; /* 0 = 2: a projected far end farther than max_stretch * range from its near end is answered invalid */
+} vmv_constraint_plan_settings;
+int vmv_rrtc_multi_constrained(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                               const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings,
+                               const vmv_ee_constraint *constraints /* host, [n_constraints] */, size_t n_constraints,
+                               const vmv_constraint_plan_settings *constraint_settings, vmv_plans **out);
+/* refused [n_problems]: per problem the questions the constraint answered 0 (a failed or overstretched projection, an edge
+ * out of band), whatever validity said.  VMV_ERR_INVALID_ARGUMENT on plans not made by vmv_rrtc_multi_constrained. */
+int vmv_plans_band_refused(const vmv_plans *plans, uint32_t *refused);
 int vmv_plans_goal_indices(const vmv_plans *plans, uint32_t *goal_index);
 
 /* ---- batched PRM: many independent roadmap problems in one call ------------------------------------------ */

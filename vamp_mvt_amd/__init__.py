@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import VmvError, check, lib
 
 __all__ = ["robots", "Sphere", "Cuboid", "Cylinder", "Attachment", "filter_pointcloud", "HeightField", "make_heightfield", "png_to_heightfield", "Environment", "device_count", "set_device", "abi_version",
-           "VmvError", "unpack_bits", "POINT_RADIUS", "IKSettings"]
+           "VmvError", "unpack_bits", "POINT_RADIUS", "IKSettings", "EEConstraint", "ConstraintSettings"]
 
 POINT_RADIUS = 0.0025  # reference src/vamp/constants.py:25
 
@@ -778,6 +778,73 @@ class IKSettings:
         return "IKSettings(" + ", ".join(f"{k}={v!r}" for k, v in vars(self).items()) + ")"
 
 
+class EEConstraint:
+    """vmv_ee_constraint (include/vamp_mvt_amd.h): a tolerance band on the end-effector frame (R, t).  frame: the rigid
+    4 x 4 frame C in the world (None = the world itself); pos_lo / pos_hi: bounds on p = C_R^T (t - C_t) per axis (None =
+    free; equal bounds are a plane or a line); the angle between R tool_axis and C_R ref_axis is at most max_angle (rad, at
+    most pi/2; 0 = the orientation is free).  The library normalises the axes and refuses what is not a constraint."""
+
+    def __init__(self, frame=None, pos_lo=None, pos_hi=None, tool_axis=(0.0, 0.0, 1.0), ref_axis=(0.0, 0.0, 1.0), max_angle=0.0):
+        self.frame = np.eye(4, dtype=np.float32) if frame is None else _f32(frame).reshape(-1)
+        if self.frame.size != 16:
+            raise TypeError("expected frame as a 4 x 4 matrix")
+        self.frame = self.frame.reshape(4, 4)
+        self.pos_lo = np.full(3, -np.inf, np.float32) if pos_lo is None else _f32(pos_lo, (3,))
+        self.pos_hi = np.full(3, np.inf, np.float32) if pos_hi is None else _f32(pos_hi, (3,))
+        self.tool_axis, self.ref_axis = _f32(tool_axis, (3,)), _f32(ref_axis, (3,))
+        self.max_angle = float(max_angle)
+
+    @classmethod
+    def upright(cls, tool_axis, max_angle, frame=None):
+        """tool_axis (in the end-effector frame) stays within max_angle of the z axis of `frame` (None = the world's)"""
+        return cls(frame=frame, tool_axis=tool_axis, ref_axis=(0.0, 0.0, 1.0), max_angle=max_angle)
+
+    @classmethod
+    def box(cls, lo, hi, frame=None):
+        """the end-effector position stays within [lo, hi] along the axes of `frame` (None = the world)"""
+        return cls(frame=frame, pos_lo=lo, pos_hi=hi)
+
+    def struct(self):
+        c = _lib.EeConstraint()
+        c.frame[:] = self.frame.reshape(-1).tolist()
+        c.pos_lo[:], c.pos_hi[:] = self.pos_lo.tolist(), self.pos_hi.tolist()
+        c.tool_axis[:], c.ref_axis[:] = self.tool_axis.tolist(), self.ref_axis.tolist()
+        c.max_angle = self.max_angle
+        return c
+
+    def __repr__(self):
+        return "EEConstraint(" + ", ".join(f"{k}={np.asarray(v).tolist()!r}" for k, v in vars(self).items()) + ")"
+
+
+class ConstraintSettings:
+    """vmv_constraint_settings (include/vamp_mvt_amd.h) with its defaults: max_iterations evaluations after the first;
+    pos_tol (m) and rot_tol (rad) widen the nominal band into the one every test asks; rot_weight, damping and max_step
+    as IKSettings'; check_step: the joint-space distance between two band samples of an edge."""
+
+    def __init__(self, max_iterations=16, pos_tol=1e-4, rot_tol=1e-3, rot_weight=0.25, damping=1e-2, max_step=0.5,
+                 check_step=0.05):
+        self.max_iterations, self.pos_tol, self.rot_tol = max_iterations, pos_tol, rot_tol
+        self.rot_weight, self.damping, self.max_step = rot_weight, damping, max_step
+        self.check_step = check_step
+
+    def struct(self):
+        return _lib.ConstraintSettings(int(self.max_iterations), float(self.pos_tol), float(self.rot_tol), float(self.rot_weight),
+                                       float(self.damping), float(self.max_step), float(self.check_step))
+
+    def __repr__(self):
+        return "ConstraintSettings(" + ", ".join(f"{k}={v!r}" for k, v in vars(self).items()) + ")"
+
+
+def _constraint_records(constraints, n):
+    """one EEConstraint (shared) or a sequence of n -> (ctypes array, count)"""
+    items = [constraints] if isinstance(constraints, EEConstraint) else list(constraints)
+    if not all(isinstance(c, EEConstraint) for c in items):
+        raise TypeError("expected an EEConstraint or a sequence of them")
+    if len(items) != 1 and len(items) != n:
+        raise ValueError(f"expected 1 constraint or {n} (one per row), got {len(items)}")
+    return (_lib.EeConstraint * len(items))(*[c.struct() for c in items]), len(items)
+
+
 class _Robot(types.ModuleType):
     def __init__(self, name: str):
         super().__init__(f"{__name__}.{name}")
@@ -937,6 +1004,70 @@ class _Robot(types.ModuleType):
         check(lib.vmv_ik_batch_host(self._id, _fp(targets), n, None if seeds is None else _fp(seeds), int(halton_skip),
                                     ctypes.byref(cs), _fp(q), _fp(err), status.ctypes.data_as(_lib.c_u32_p)), "vmv_ik_batch_host")
         return q, err, (status >> 31).astype(bool), (status & 0x3fffffff).astype(np.int32)
+
+    def _constraint_call(self, symbol, inputs, constraints, settings, outputs):
+        """The one path of the constraint calls.  inputs: one or two [n][dim] arrays (numpy -> `symbol`_host; torch CUDA ->
+        `symbol` on torch's current stream); constraints: one EEConstraint or n; outputs: (trailing shape, numpy dtype,
+        torch dtype name) each, "bits" as trailing shape for ceil(n / 64) validity words.  -> the output arrays."""
+        cs = (settings or ConstraintSettings()).struct()
+        torch_in = _is_torch_cuda(inputs[0])
+        if not all(_is_torch_cuda(x) == torch_in for x in inputs):
+            raise TypeError("the arrays must all be numpy arrays or all be torch CUDA tensors")
+        if not torch_in:
+            inputs = [_f32(x) for x in inputs]
+        shape = tuple(inputs[0].shape)
+        if len(shape) != 2 or shape[1] != self._dim or any(tuple(x.shape) != shape for x in inputs):
+            raise TypeError(f"expected [n][{self._dim}] configurations" if len(inputs) == 1 else f"expected two [n][{self._dim}] arrays")
+        n = shape[0]
+        records, count = _constraint_records(constraints, n)
+        shapes = [((n + 63) // 64,) if trailing == "bits" else (n, *trailing) for trailing, _, _ in outputs]
+        if torch_in:
+            import torch
+
+            device = inputs[0].device
+            with torch.cuda.device(device):
+                inputs = [x.to(device).contiguous().float() for x in inputs]
+                outs = [torch.zeros(s, dtype=getattr(torch, t), device=device) for s, (_, _, t) in zip(shapes, outputs)]
+                ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+                check(getattr(lib, symbol)(self._id, *[ptr(x) for x in inputs], n, records, count, ctypes.byref(cs),
+                                           *[ptr(o) for o in outs], ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                      symbol)
+            return outs
+        outs = [np.zeros(s, d) for s, (_, d, _) in zip(shapes, outputs)]
+        fn = getattr(lib, symbol + "_host")
+        types = fn.argtypes[len(fn.argtypes) - len(outs):]
+        check(fn(self._id, *[_fp(x) for x in inputs], n, records, count, ctypes.byref(cs),
+                 *[o.ctypes.data_as(t) for o, t in zip(outs, types)]), symbol + "_host")
+        return outs
+
+    def project_batch(self, configurations, constraint, settings=None):
+        """Projects configurations [n][dim] into the band of an end-effector constraint (include/vamp_mvt_amd.h:
+        vmv_constraint_project_batch): ik_batch's damped least-squares iteration on the constraint's residual.  constraint:
+        one EEConstraint for all rows, or n of them.  -> (q float32[n][dim], residuals float32[n][2] = metres outside the
+        box and radians beyond the cone, converged bool[n], evaluations int32[n]).  A row inside the joint bounds and in
+        the band comes back bit for bit with 0 evaluations; a row with a non-finite joint comes back as given with NaN
+        residuals.  numpy in -> numpy out; a torch CUDA tensor in -> torch CUDA tensors out."""
+        q, res, status = self._constraint_call("vmv_constraint_project_batch", [configurations], constraint, settings,
+                                               [((self._dim,), np.float32, "float32"), ((2,), np.float32, "float32"), ((), np.uint32, "int32")])
+        if _is_torch_cuda(status):
+            return q, res, status < 0, status & 0x3fffffff
+        return q, res, (status >> 31).astype(bool), (status & 0x3fffffff).astype(np.int32)
+
+    def constraint_check_batch(self, configurations, constraint, settings=None, residuals=False):
+        """bool[n]: configuration i is in the band of its constraint (the nominal band widened by settings.pos_tol and
+        rot_tol; a non-finite row is not).  residuals=True: also float32[n][2] as project_batch's."""
+        bits, res = self._constraint_call("vmv_constraint_check_batch", [configurations], constraint, settings,
+                                          [("bits", np.uint64, "int64"), ((2,), np.float32, "float32")])
+        n = int(res.shape[0])
+        ok = _torch_unpack_bits(bits, n) if _is_torch_cuda(bits) else unpack_bits(bits, n)
+        return (ok, res) if residuals else ok
+
+    def constraint_check_motion_batch(self, starts, goals, constraint, settings=None):
+        """bool[n]: every band sample of the edge starts[e] -> goals[e] is in the band - max(1, ceil(|b - a| /
+        settings.check_step)) samples a + (b - a) * (i / n_c); an edge of more than 1,024 samples is not."""
+        (ok,) = self._constraint_call("vmv_constraint_check_motion_batch", [starts, goals], constraint, settings,
+                                      [((), np.uint8, "uint8")])
+        return ok != 0
 
     def fk(self, configuration):
         """<robot>.fk(q) -> list[Sphere] — robot_helper.hh:234-247."""
@@ -1115,7 +1246,17 @@ class _Robot(types.ModuleType):
                                  ctypes.byref(plans)), "vmv_rrtc_multi")
         return _read_plans(plans, n, self._dim)
 
-    def rrtc_multi_goals_raw(self, starts, goals, goal_counts, environments, settings, skips=None):
+    def rrtc_multi_constrained_raw(self, starts, goals, goal_counts, environments, constraints, settings, constraint_settings=None,
+                                   max_stretch=2.0, skips=None):
+        """vmv_rrtc_multi_constrained: rrtc_multi_goals_raw under end-effector constraints - one EEConstraint for all
+        problems or one per problem; constraint_settings: a ConstraintSettings (None = defaults); max_stretch: a projected
+        node farther than max_stretch * range from the edge's near end is answered invalid.  -> rrtc_multi_goals_raw's dict
+        plus band_refused per problem (the questions the constraint answered 0);
+        status 4 (invalid_endpoint) where the start is out of band or no goal is in band."""
+        return self.rrtc_multi_goals_raw(starts, goals, goal_counts, environments, settings, skips,
+                                         constrained=(constraints, constraint_settings, float(max_stretch)))
+
+    def rrtc_multi_goals_raw(self, starts, goals, goal_counts, environments, settings, skips=None, constrained=None):
         """vmv_rrtc_multi_goals: rrtc_multi_raw with goal sets, dynamic domain and start_tree_first.  goals: the goals of
         all problems packed, [sum(goal_counts)][dim]; goal_counts: goals per problem (each at least 1), None = one each.
         settings: those of rrtc_multi_raw and dynamic_domain, radius, alpha, min_radius, start_tree_first.
@@ -1156,15 +1297,29 @@ class _Robot(types.ModuleType):
                 raise ValueError("alpha must be in [0, 1)")
         cs = _lib.RrtcGoalsSettings(base, int(dynamic), radius, alpha, min_radius,
                                     int(bool(getattr(settings, "start_tree_first", False))))
+        if constrained is not None:  # (every Python-side check before any library call)
+            records, count = _constraint_records(constrained[0], n)
+            if not (math.isfinite(constrained[2]) and constrained[2] >= 0):
+                raise ValueError("max_stretch must be finite and not negative")
+            ps = _lib.ConstraintPlanSettings((constrained[1] or ConstraintSettings()).struct(), constrained[2])
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_rrtc_multi_goals(self._id, handles, n, _fp(a), _fp(b), _ptr(offsets, _lib.c_size_p),
-                                       _ptr(sk, _lib.c_u64_p), ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi_goals")
+        if constrained is not None:
+            check(lib.vmv_rrtc_multi_constrained(self._id, handles, n, _fp(a), _fp(b), _ptr(offsets, _lib.c_size_p), _ptr(sk, _lib.c_u64_p),
+                                                 ctypes.byref(cs), records, count, ctypes.byref(ps), ctypes.byref(plans)),
+                  "vmv_rrtc_multi_constrained")
+        else:
+            check(lib.vmv_rrtc_multi_goals(self._id, handles, n, _fp(a), _fp(b), _ptr(offsets, _lib.c_size_p),
+                                           _ptr(sk, _lib.c_u64_p), ctypes.byref(cs), ctypes.byref(plans)), "vmv_rrtc_multi_goals")
 
         def goal_indices(plans, out):
             indices = np.zeros(n, np.uint32)
             check(lib.vmv_plans_goal_indices(plans, indices.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_goal_indices")
             out["goal_indices"] = indices.view(np.int32).copy()
+            if constrained is not None:
+                refused = np.zeros(n, np.uint32)
+                check(lib.vmv_plans_band_refused(plans, refused.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_band_refused")
+                out["band_refused"] = refused
 
         return _read_plans(plans, n, self._dim, goal_indices)
 

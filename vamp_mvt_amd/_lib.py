@@ -90,6 +90,24 @@ class IkSettings(ctypes.Structure):
                 ("max_step", ctypes.c_float), ("position_only", ctypes.c_int)]
 
 
+class EeConstraint(ctypes.Structure):
+    """vmv_ee_constraint"""
+    _fields_ = [("frame", ctypes.c_float * 16), ("pos_lo", ctypes.c_float * 3), ("pos_hi", ctypes.c_float * 3),
+                ("tool_axis", ctypes.c_float * 3), ("ref_axis", ctypes.c_float * 3), ("max_angle", ctypes.c_float)]
+
+
+class ConstraintSettings(ctypes.Structure):
+    """vmv_constraint_settings"""
+    _fields_ = [("max_iterations", ctypes.c_uint32), ("pos_tol", ctypes.c_float), ("rot_tol", ctypes.c_float),
+                ("rot_weight", ctypes.c_float), ("damping", ctypes.c_float), ("max_step", ctypes.c_float),
+                ("check_step", ctypes.c_float)]
+
+
+class ConstraintPlanSettings(ctypes.Structure):
+    """vmv_constraint_plan_settings"""
+    _fields_ = [("base", ConstraintSettings), ("max_stretch", ctypes.c_float)]
+
+
 class CartesianSettings(ctypes.Structure):
     """vmv_cartesian_settings"""
     _fields_ = [("pos_step", ctypes.c_float), ("rot_step", ctypes.c_float), ("max_iterations", ctypes.c_uint32),
@@ -210,12 +228,25 @@ def _load():
         "vmv_ik_batch": (I, [I, V, S, V, ctypes.c_uint64, ctypes.POINTER(IkSettings), V, V, V, V]),
         "vmv_ik_batch_host": (I, [I, c_float_p, S, c_float_p, ctypes.c_uint64, ctypes.POINTER(IkSettings), c_float_p, c_float_p,
                                   c_u32_p]),
+        "vmv_constraint_project_batch": (I, [I, V, S, ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings), V, V, V, V]),
+        "vmv_constraint_project_batch_host": (I, [I, c_float_p, S, ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings),
+                                                  c_float_p, c_float_p, c_u32_p]),
+        "vmv_constraint_check_batch": (I, [I, V, S, ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings), V, V, V]),
+        "vmv_constraint_check_batch_host": (I, [I, c_float_p, S, ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings),
+                                                c_u64_p, c_float_p]),
+        "vmv_constraint_check_motion_batch": (I, [I, V, V, S, ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings), V, V]),
+        "vmv_constraint_check_motion_batch_host": (I, [I, c_float_p, c_float_p, S, ctypes.POINTER(EeConstraint), S,
+                                                       ctypes.POINTER(ConstraintSettings), c_u8_p]),
         "vmv_env_prepare_multi": (I, [I, ctypes.POINTER(V), S]),
         "vmv_rrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(RrtcSettings),
                                ctypes.POINTER(V)]),
         "vmv_rrtc_multi_goals": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_size_p, c_u64_p,
                                      ctypes.POINTER(RrtcGoalsSettings), ctypes.POINTER(V)]),
+        "vmv_rrtc_multi_constrained": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_size_p, c_u64_p,
+                                           ctypes.POINTER(RrtcGoalsSettings), ctypes.POINTER(EeConstraint), S,
+                                           ctypes.POINTER(ConstraintPlanSettings), ctypes.POINTER(V)]),
         "vmv_plans_goal_indices": (I, [V, c_u32_p]),
+        "vmv_plans_band_refused": (I, [V, c_u32_p]),
         "vmv_plans_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_plans_paths": (I, [V, c_float_p, S]),
         "vmv_plans_destroy": (I, [V]),

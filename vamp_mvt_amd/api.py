@@ -332,6 +332,14 @@ def install(robot):
         t0 = time.perf_counter_ns()
         return timed_results(planning.rrtc_multi_goals(robot, starts, goal_sets, environments, multi_settings(settings), skips), t0)
 
+    def rrtc_multi_constrained(starts, goal_sets, environments, constraints, settings, constraint_settings=None, skips=None,
+                               max_stretch=2.0):
+        """planning.rrtc_multi_constrained with this robot: rrtc_multi_goals under end-effector constraints ->
+        list[PlanningResult] (each with `status` and `goal_index`).  The settings are taken as rrtc_multi takes them."""
+        t0 = time.perf_counter_ns()
+        return timed_results(planning.rrtc_multi_constrained(robot, starts, goal_sets, environments, constraints,
+                                                             multi_settings(settings), constraint_settings, skips, max_stretch), t0)
+
     def aorrtc_multi(starts, goals, environments, settings, skips=None):
         """planning.aorrtc_multi with this robot and the reference-shaped AORRTCSettings -> list[PlanningResult] (each
         with `status`, `first_cost`, `searches`, `improvements`; nanoseconds is the whole call's time divided by the
@@ -528,6 +536,7 @@ def install(robot):
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals
+    robot.rrtc_multi_constrained = rrtc_multi_constrained
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
     robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]

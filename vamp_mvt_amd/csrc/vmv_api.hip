@@ -1623,6 +1623,44 @@ namespace
         return VMV_OK;
     }
 
+    // The checks of the vmv_constraint_*_batch calls, none of which needs a device, in the header's order; fills the
+    // kernels' parameter block; the device records (one, or one per lane) are built once the call holds its pinned table.
+    struct ConstraintCall
+    {
+        vmv::ConstraintParams P;
+        const vmv_ee_constraint *constraints;
+        size_t count;
+    };
+    int constraint_checks(int robot, bool arrays, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                          const vmv_constraint_settings *settings, ConstraintCall &c)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!arrays || !constraints || !settings) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        if (n_constraints != 1 && n_constraints != n) return refuse(VMV_ERR_INVALID_ARGUMENT, "n_constraints must be 1 or n");
+        if (const char *err = vmv::constraint_settings(*settings, c.P)) return refuse(VMV_ERR_INVALID_ARGUMENT, err);
+        if (n >= vmv::kMultiMaxConfigs) return refuse(VMV_ERR_INVALID_ARGUMENT, "n must be below 2^31");
+        c.P.shared = n_constraints == 1 ? 1u : 0u;
+        for (int j = 0; j < 16; ++j) c.P.lower[j] = kRobots[robot].lower[j], c.P.upper[j] = kRobots[robot].lower[j] + kRobots[robot].span[j];
+        c.constraints = constraints, c.count = n_constraints;
+        for (size_t k = 0; k < n_constraints; ++k)
+            if (const char *err = vmv::constraint_refusal(constraints[k]))
+                return refuse(VMV_ERR_INVALID_ARGUMENT, "constraints[" + std::to_string(k) + "]: " + err);
+        return VMV_OK;
+    }
+    // the records built straight into the stream's pinned table, uploaded, then launch(d_records, stream); the _host forms
+    // come here after their own prologue (the null stream, so that the staged copies order with the launch)
+    template <typename F>
+    int constraint_launch(const ConstraintCall &c, hipStream_t stream, F &&launch)
+    {
+        vmv::MultiTableLease lease;
+        const size_t bytes = c.count * sizeof(vmv::ConstraintDev);
+        if (int rc = lease.acquire(stream, bytes); rc != VMV_OK) return rc;
+        vmv::ConstraintDev *records = static_cast<vmv::ConstraintDev *>(lease.host);
+        for (size_t k = 0; k < c.count; ++k) vmv::constraint_record(c.constraints[k], (double) c.P.pos_tol, (double) c.P.rot_tol, records[k]);
+        if (int rc = lease.upload(stream, bytes); rc != VMV_OK) return rc;
+        return launch(static_cast<const vmv::ConstraintDev *>(lease.dev), stream);
+    }
+
     // bench / sampling input generators: uploads the robot's bounds, launches `kernel` on the stream, waits for it
     using ConfigKernel = void (*)(float *, size_t, int, uint64_t, const float *, const float *);
     int generate_configs(int robot, ConfigKernel kernel, uint64_t seed_or_skip, float *d_q, size_t n, void *stream)
@@ -1992,6 +2030,86 @@ extern "C"
                      {
                          return vmv_ik_batch(robot, s.at<float>(dt), n_targets, s.at<float>(ds), halton_skip, settings, s.at<float>(dq),
                                              s.at<float>(de), s.at<uint32_t>(dst), nullptr);
+                     });
+    }
+
+    // ---- end-effector constraints (include/vamp_mvt_amd.h: vmv_constraint_*_batch; csrc/vmv_constraint.h) ----
+    int vmv_constraint_project_batch(int robot, const float *d_q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                     const vmv_constraint_settings *settings, float *d_q_out, float *d_residuals, uint32_t *d_status,
+                                     void *stream)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, d_q && d_q_out && d_status, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
+                                 { return kLaunchers[robot]->constraint_project(c.P, d_cons, d_q, n, d_q_out, d_residuals, d_status, st); });
+    }
+    int vmv_constraint_project_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                          const vmv_constraint_settings *settings, float *q_out, float *residuals, uint32_t *status)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, q && q_out && status, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), dout = s.out(q_out, config_bytes(robot, n)),
+                  dr = s.out(residuals, residuals ? n * 8 : 0), dst = s.out(status, n * 4);
+        return s.run([&]
+                     {
+                         return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
+                             return kLaunchers[robot]->constraint_project(c.P, d_cons, s.at<float>(dq), n, s.at<float>(dout), s.at<float>(dr),
+                                                                          s.at<uint32_t>(dst), st);
+                         });
+                     });
+    }
+    int vmv_constraint_check_batch(int robot, const float *d_q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                   const vmv_constraint_settings *settings, uint64_t *d_bits, float *d_residuals, void *stream)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, d_q && d_bits, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
+                                 { return kLaunchers[robot]->constraint_check(c.P, d_cons, d_q, n, d_bits, d_residuals, st); });
+    }
+    int vmv_constraint_check_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                        const vmv_constraint_settings *settings, uint64_t *bits, float *residuals)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, q && bits, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        Staged s;
+        const int dq = s.in(q, config_bytes(robot, n)), db = s.out(bits, (n + 63) / 64 * 8), dr = s.out(residuals, residuals ? n * 8 : 0);
+        return s.run([&]
+                     {
+                         return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
+                             return kLaunchers[robot]->constraint_check(c.P, d_cons, s.at<float>(dq), n, s.at<uint64_t>(db), s.at<float>(dr), st);
+                         });
+                     });
+    }
+    int vmv_constraint_check_motion_batch(int robot, const float *d_a, const float *d_b, size_t n, const vmv_ee_constraint *constraints,
+                                          size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *d_ok, void *stream)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, d_a && d_b && d_ok, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
+                                 { return kLaunchers[robot]->constraint_edges(c.P, d_cons, d_a, d_b, n, d_ok, st); });
+    }
+    int vmv_constraint_check_motion_batch_host(int robot, const float *a, const float *b, size_t n, const vmv_ee_constraint *constraints,
+                                               size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *ok)
+    {
+        ConstraintCall c;
+        if (int rc = constraint_checks(robot, a && b && ok, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
+        if (n == 0) return VMV_OK;
+        if (int rc = require_device(); rc != VMV_OK) return rc;
+        Staged s;
+        const int da = s.in(a, config_bytes(robot, n)), db = s.in(b, config_bytes(robot, n)), dk = s.out(ok, n);
+        return s.run([&]
+                     {
+                         return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
+                             return kLaunchers[robot]->constraint_edges(c.P, d_cons, s.at<float>(da), s.at<float>(db), n, s.at<uint8_t>(dk), st);
+                         });
                      });
     }
 

@@ -7,6 +7,7 @@
 
 #include <mutex>
 
+#include "vmv_constraint.h"
 #include "vmv_device.h"
 
 namespace vmv
@@ -143,6 +144,20 @@ namespace vmv
         // rows (row 0 of a problem is the host's), d_results [n]
         int (*cartesian)(const CartParams &, const CartLine *d_lines, const float *d_starts, size_t n, float *d_points,
                          CartResult *d_results, hipStream_t);
+        // vmv_constraint_*_batch (vmv_constraint.h): n below 2^31 lanes / edges; d_cons one record (P.shared) or [n];
+        // d_res [n][2] may be nullptr; d_bits ceil(n / 64) words; d_ok one byte per edge
+        int (*constraint_project)(const ConstraintParams &, const ConstraintDev *d_cons, const float *d_q, size_t n, float *d_q_out,
+                                  float *d_res, uint32_t *d_status, hipStream_t);
+        int (*constraint_check)(const ConstraintParams &, const ConstraintDev *d_cons, const float *d_q, size_t n, uint64_t *d_bits,
+                                float *d_res, hipStream_t);
+        int (*constraint_edges)(const ConstraintParams &, const ConstraintDev *d_cons, const float *d_a, const float *d_b, size_t n,
+                                uint8_t *d_ok, hipStream_t);
+        // vmv_rrtc_multi_constrained's part of a round, after the step kernel on the same stream: per active slot the
+        // pending node (d_pending[a] = its pool element, ~0 = none) projected and written back, then the band test of
+        // the edge into d_c_ok[a]; d_cons one record (P.shared) or one per PROBLEM (indexed through d_active)
+        int (*constraint_round)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_active, const float *d_q_start,
+                                float *d_q_goal, const uint64_t *d_pending, float *d_pool, float stretch, uint8_t *d_c_ok,
+                                uint32_t *d_refused /* [n_problems], += 1 per question answered 0 */, uint32_t na, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

@@ -20,6 +20,10 @@ struct vmv_plans
     bool rrtc_goals = false;
     std::vector<uint32_t> goal_indices;  // [n] the goal, within its own set, a solved path ends in; UINT32_MAX = unsolved
 
+    // vmv_rrtc_multi_constrained only (vmv_plans_band_refused)
+    bool constrained = false;
+    std::vector<uint32_t> band_refused;  // [n] questions the constraint's round answered 0 (projection or band test)
+
     // vmv_prm_multi only (vmv_plans_roadmap_*)
     bool prm = false, kept = false;  // made by vmv_prm_multi; with keep_roadmaps
     uint32_t n_samples = 0;

@@ -1694,6 +1694,341 @@ namespace VMV_ROBOT_NS
     }
 
     // ---------------------------------------------------------------------------------------------------------
+    // End-effector constraints (include/vamp_mvt_amd.h: vmv_constraint_*_batch, DESIGN.md 5o).  csrc/vmv_constraint.h
+    // states the residual, the band test, the projection and the edge test; the functions below are that statement in
+    // fp32, and every kernel asks them, so a question has one answer wherever it is asked.  Templates for their place in
+    // the code object, as the kernels above.
+    // ---------------------------------------------------------------------------------------------------------
+    struct ConstraintState  // what constraint_residual reads off one frame
+    {
+        float v[3];        // p - clamp(p, lo, hi) along C's axes
+        float a[3], n[3];  // the tool axis in the world; c / |c|, c = a x d
+        float s;           // the excess: sin(angle - max_angle), 1 beyond 90 degrees of excess
+        float sn, cs;      // |a x d|, a . d
+        bool tilted;       // the axis part is active: cos < cos_m
+        bool anti;         // antiparallel axes: no direction to turn in
+        bool band;         // the band test
+    };
+    __device__ __forceinline__ void constraint_residual(const float (&f)[12], const ConstraintDev &C, ConstraintState &S)
+    {
+        const float d0 = f[0] - C.t[0], d1 = f[1] - C.t[1], d2 = f[2] - C.t[2];
+        bool in = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            const float p = dot3(C.R[k], C.R[3 + k], C.R[6 + k], d0, d1, d2);
+            S.v[k] = p - fminf(fmaxf(p, C.lo[k]), C.hi[k]);
+            in = in && p >= C.lo_band[k] && p <= C.hi_band[k];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) S.a[r] = dot3(f[3 + r], f[6 + r], f[9 + r], C.u[0], C.u[1], C.u[2]);
+        const float cx = (S.a[1] * C.d[2]) - (S.a[2] * C.d[1]), cy = (S.a[2] * C.d[0]) - (S.a[0] * C.d[2]),
+                    cz = (S.a[0] * C.d[1]) - (S.a[1] * C.d[0]);
+        S.sn = sqrtf(dot3(cx, cy, cz, cx, cy, cz));
+        S.cs = dot3(S.a[0], S.a[1], S.a[2], C.d[0], C.d[1], C.d[2]);
+        const float inv = 1.0f / (S.sn > 0.0f ? S.sn : 1.0f);  // (the quotient stands outside the select, as ik_error's)
+        S.n[0] = cx * inv, S.n[1] = cy * inv, S.n[2] = cz * inv;
+        const float far = (S.cs * C.cos_m) + (S.sn * C.sin_m);
+        const float near = (S.sn * C.cos_m) - (S.cs * C.sin_m);
+        S.s = far <= 0.0f ? 1.0f : near;
+        const bool axis = C.axis != 0u;
+        S.tilted = axis && S.cs < C.cos_m;
+        S.anti = axis && S.sn == 0.0f && S.cs < 0.0f;
+        S.band = in && (!axis || S.cs >= C.cos_band);
+    }
+    // the residual pair of a state: |v| (m), the angle beyond max_angle (rad)
+    __device__ __forceinline__ void constraint_report(const ConstraintState &S, const ConstraintDev &C, float &res_p, float &res_w)
+    {
+        res_p = sqrtf(dot3(S.v[0], S.v[1], S.v[2], S.v[0], S.v[1], S.v[2]));
+        const float over = atan2f((S.sn * C.cos_m) - (S.cs * C.sin_m), (S.cs * C.cos_m) + (S.sn * C.sin_m));
+        res_w = S.tilted ? over : 0.0f;
+    }
+
+    // The projection of one lane's configuration `in` (vmv_constraint.h): ik_kernel's loop - one evaluation per pass,
+    // selects into the accepted state, no branch but the wave-uniform exit - with the constraint's rows.  Every lane of
+    // the wave calls it; a lane with `live` false rides along and its outputs mean nothing.  q: the result (`in` itself
+    // for a non-finite or antiparallel input); status as the kernel writes it.
+    __device__ __forceinline__ void constraint_project_lane(const ConstraintParams &P, const ConstraintDev &C, const float (&in)[R::kDim],
+                                                            const bool live, float (&q_out)[R::kDim], float &res_p, float &res_w,
+                                                            uint32_t &status)
+    {
+        float cand[R::kDim];
+        bool finite = true;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) finite = finite && __builtin_isfinite(in[j]);
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cand[j] = fminf(fmaxf(finite ? in[j] : 0.0f, P.lower[j]), P.upper[j]);
+
+        float q[R::kDim], Jw[6][R::kDim], e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float E = __builtin_inff(), lam = P.damping;
+        ConstraintState acc{};
+        bool done = !live || !finite, converged = false, given = !finite;
+        uint32_t evals = 0;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            q[j] = cand[j];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) Jw[r][j] = 0.0f;
+        }
+        for (uint32_t it = 0;; ++it)
+        {
+            // ---- one evaluation: the candidate's frame, Jacobian, residual and E
+            float f[12], df[12][R::kDim], Jc[6][R::kDim], ec[6];
+            ConstraintState S;
+            R::ee_frame_jac(cand, f, df);
+            ee_jacobian(f, df, Jc);
+            constraint_residual(f, C, S);
+            const float b0 = (S.a[1] * S.n[2]) - (S.a[2] * S.n[1]), b1 = (S.a[2] * S.n[0]) - (S.a[0] * S.n[2]),
+                        b2 = (S.a[0] * S.n[1]) - (S.a[1] * S.n[0]);  // a x n
+            ec[0] = -S.v[0], ec[1] = -S.v[1], ec[2] = -S.v[2];
+            ec[3] = S.tilted ? P.rot_weight * S.s : 0.0f, ec[4] = 0.0f, ec[5] = 0.0f;
+            const float Ec = 0.5f * (dot3(ec[0], ec[1], ec[2], ec[0], ec[1], ec[2]) + (ec[3] * ec[3]));
+            const bool first = it == 0u;  // the input's evaluation is taken whatever it gives and leaves lambda alone
+            const bool stuck = first && S.anti && !done;  // antiparallel input: as given, not converged
+            const bool take = !done && (first || Ec < E);
+            const float lam_next = take ? fmaxf(lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(lam * kIkLambdaFactor, kIkLambdaCeil);
+            lam = (done || first) ? lam : lam_next;
+            evals += (done || first) ? 0u : 1u;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+            {
+                q[j] = take ? cand[j] : q[j];
+                if (ee_joint(j))
+                {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                    {
+                        const float row = dot3(C.R[k], C.R[3 + k], C.R[6 + k], Jc[0][j], Jc[1][j], Jc[2][j]);
+                        Jw[k][j] = take ? (S.v[k] != 0.0f ? row : 0.0f) : Jw[k][j];
+                    }
+                    const float r3 = P.rot_weight * dot3(S.n[0], S.n[1], S.n[2], Jc[3][j], Jc[4][j], Jc[5][j]);
+                    const float r4 = P.rot_weight * dot3(b0, b1, b2, Jc[3][j], Jc[4][j], Jc[5][j]);
+                    Jw[3][j] = take ? (S.tilted ? r3 : 0.0f) : Jw[3][j];
+                    Jw[4][j] = take ? (S.tilted ? r4 : 0.0f) : Jw[4][j];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) e[r] = take ? ec[r] : e[r];
+            E = take ? Ec : E;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc.v[k] = take ? S.v[k] : acc.v[k];
+            acc.sn = take ? S.sn : acc.sn, acc.cs = take ? S.cs : acc.cs, acc.tilted = take ? S.tilted : acc.tilted;
+            converged = converged || (take && S.band && !stuck);
+            given = given || stuck;
+            done = done || (take && S.band) || stuck;
+            if (it == P.max_iterations || !wave_any(!done)) break;
+
+            // ---- the step from the accepted state: A = Jm Jm^T + lambda I, A y = e, delta = Jm^T y
+            float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+                if (ee_joint(j))
+                {
+                    float g = Jw[0][j] * e[0];
+#pragma unroll
+                    for (int r = 1; r < 6; ++r) g += Jw[r][j] * e[r];
+                    const bool hold = (q[j] <= P.lower[j] && g < 0.0f) || (q[j] >= P.upper[j] && g > 0.0f);
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : Jw[r][j];
+                }
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b <= a; ++b)
+                {
+                    float s = a == b ? lam : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < R::kDim; ++j)
+                        if (ee_joint(j)) s += Jm[a][j] * Jm[b][j];
+                    A[a][b] = s;
+                }
+            chol6_solve(A, e, y);
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+            {
+                delta[j] = 0.0f;
+                if (ee_joint(j))
+                {
+                    float s = Jm[0][j] * y[0];
+#pragma unroll
+                    for (int r = 1; r < 6; ++r) s += Jm[r][j] * y[r];
+                    delta[j] = s;
+                    big = fmaxf(big, fabsf(s));
+                }
+            }
+            const float scale = P.max_step / fmaxf(big, P.max_step);
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j)
+                cand[j] = ee_joint(j) ? fminf(fmaxf(q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : q[j];
+        }
+        const float poison = finite ? 0.0f : __builtin_nanf("");
+        constraint_report(acc, C, res_p, res_w);
+        res_p += poison, res_w += poison;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) q_out[j] = given ? in[j] : q[j];
+        status = (converged ? 0x80000000u : 0u) | (finite ? 0u : 0x40000000u) | evals;
+    }
+
+    // the band test of one configuration by the primal frame alone; finite: no joint is NaN or infinite
+    __device__ __forceinline__ bool constraint_band(const float (&cfg)[R::kDim], const ConstraintDev &C, ConstraintState &S)
+    {
+        float f[12];
+        bool finite = true;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) finite = finite && __builtin_isfinite(cfg[j]);
+        R::ee_frame(cfg, f);
+        constraint_residual(f, C, S);
+        return finite && S.band;
+    }
+
+    // The band test of the edge a -> b, asked by a whole wave (vmv_constraint.h): sample i = 1 + lane + 64 r of the n_c, the
+    // AND over the wave by a ballot.  The result does not depend on the order, so the wave stops at the first round with
+    // a failing sample.  `live` false (wave-uniform): no edge, answers false.
+    __device__ __forceinline__ bool constraint_band_edge(const ConstraintParams &P, const ConstraintDev &C, const float (&qa)[R::kDim],
+                                                         const float (&qb)[R::kDim], const bool live)
+    {
+        float dq[R::kDim], sq = 0.0f;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            dq[j] = qb[j] - qa[j];
+            sq = j == 0 ? dq[j] * dq[j] : sq + dq[j] * dq[j];
+        }
+        const float count = fmaxf(1.0f, ceilf(sqrtf(sq) / P.check_step));
+        const bool fits = live && count <= (float) kConstraintMaxSamples;  // (a NaN length: one sample, itself NaN, out of band)
+        const uint32_t n_c = fits ? (uint32_t) count : 0u;
+        const uint32_t lane = threadIdx.x % (uint32_t) kWave;
+        bool ok = fits;
+        for (uint32_t base = 0; base < n_c && ok; base += (uint32_t) kWave)  // wave-uniform: n_c and ok are
+        {
+            const uint32_t i = base + lane + 1u;
+            const float t = (float) (i <= n_c ? i : n_c) / (float) n_c;  // (a lane past the end repeats the last sample)
+            float cfg[R::kDim];
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) cfg[j] = qa[j] + dq[j] * t;
+            ConstraintState S;
+            const bool in = constraint_band(cfg, C, S);
+            ok = __ballot(!in) == 0ull;
+        }
+        return ok;
+    }
+
+    // vmv_constraint_project_batch: one lane per configuration, workgroups of one wave, no LDS, no atomics
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void constraint_project_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                          const float *__restrict__ q_in, const uint32_t n,
+                                                                          float *__restrict__ q_out, float *__restrict__ res_out,
+                                                                          uint32_t *__restrict__ status_out)
+    {
+        const uint32_t i = blockIdx.x * kIkBlock + threadIdx.x;
+        const bool in_range = i < n;
+        const uint32_t row = in_range ? i : 0u;  // (a lane past the end works on row 0 and writes nothing)
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : row];
+        float in[R::kDim], q[R::kDim], res_p, res_w;
+        uint32_t status;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) in[j] = q_in[(size_t) row * R::kDim + j];
+        constraint_project_lane(P, C, in, in_range, q, res_p, res_w, status);
+        if (!in_range) return;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) q_out[(size_t) i * R::kDim + j] = q[j];
+        if (res_out != nullptr) res_out[2 * (size_t) i] = res_p, res_out[2 * (size_t) i + 1] = res_w;
+        status_out[i] = status;
+    }
+
+    // vmv_constraint_check_batch: one lane per configuration, one ballot word per wave (a plain store by lane 0)
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void constraint_check_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                        const float *__restrict__ q, const uint32_t n,
+                                                                        uint64_t *__restrict__ bits, float *__restrict__ res_out)
+    {
+        const uint32_t i = blockIdx.x * kIkBlock + threadIdx.x;
+        const bool in_range = i < n;
+        const uint32_t row = in_range ? i : 0u;
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : row];
+        float cfg[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) cfg[j] = q[(size_t) row * R::kDim + j];
+        ConstraintState S;
+        const bool in = constraint_band(cfg, C, S);
+        const uint64_t word = __ballot(in_range && in);
+        if (threadIdx.x == 0u) bits[blockIdx.x] = word;
+        if (in_range && res_out != nullptr)
+        {
+            bool finite = true;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) finite = finite && __builtin_isfinite(cfg[j]);
+            const float poison = finite ? 0.0f : __builtin_nanf("");
+            float res_p, res_w;
+            constraint_report(S, C, res_p, res_w);
+            res_out[2 * (size_t) i] = res_p + poison, res_out[2 * (size_t) i + 1] = res_w + poison;
+        }
+    }
+
+    // vmv_constraint_check_motion_batch: one wave per edge, one byte per edge (a plain store by lane 0)
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void constraint_edge_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                       const float *__restrict__ a, const float *__restrict__ b,
+                                                                       const uint32_t n, uint8_t *__restrict__ ok_out)
+    {
+        const uint32_t e = blockIdx.x;  // the grid has n workgroups
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : e];
+        float qa[R::kDim], qb[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) qa[j] = a[(size_t) e * R::kDim + j], qb[j] = b[(size_t) e * R::kDim + j];
+        const bool ok = constraint_band_edge(P, C, qa, qb, e < n);
+        if (threadIdx.x == 0u) ok_out[e] = ok ? 1u : 0u;
+    }
+
+    // The constraint's part of a planner round (vmv_rrtc_multi_constrained), one wave per active slot a, after the step
+    // kernel on the same stream.  Where the step kernel named a pending node (the far end of an extension or of a march
+    // step, just written to q_goal[a] and to that pool element), q_goal[a] is projected - every lane of the wave runs the
+    // same projection, so the result is the lane's of constraint_project_kernel bit for bit - and, converged and no
+    // farther than `stretch` (max_stretch * range) from q_start[a], replaces both; else both stay and the answer is 0.
+    // Then the band test of the edge q_start[a] -> q_goal[a] as constraint_edge_kernel makes it.  c_ok[a]: the answer the
+    // step kernel ANDs into the validity bit; refused[problem] counts the questions answered 0 here.  Plain stores by lane 0;
+    // problem = active[a] picks the record.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void constraint_round_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                        const uint32_t *__restrict__ active, const float *__restrict__ q_start,
+                                                                        float *q_goal, const uint64_t *__restrict__ pending, float *pool,
+                                                                        const float stretch, uint8_t *__restrict__ c_ok,
+                                                                        uint32_t *__restrict__ refused)
+    {
+        const uint32_t a = blockIdx.x;  // the grid has one workgroup per active slot
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : active[a]];
+        const uint64_t pend = pending[a];
+        const bool has = pend != ~0ull;
+        float qs[R::kDim], qg[R::kDim], q[R::kDim], res_p, res_w;
+        uint32_t status;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) qs[j] = q_start[(size_t) a * R::kDim + j], qg[j] = q_goal[(size_t) a * R::kDim + j];
+        constraint_project_lane(P, C, qg, has, q, res_p, res_w, status);  // (no pending node: the lanes ride along)
+        float sq = 0.0f;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            const float d = q[j] - qs[j];
+            sq = j == 0 ? d * d : sq + d * d;
+        }
+        const bool good = has && (status >> 31) != 0u && sqrtf(sq) <= stretch;
+        if (good && threadIdx.x == 0u)
+        {
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) q_goal[(size_t) a * R::kDim + j] = q[j], pool[pend * R::kDim + j] = q[j];
+        }
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) qg[j] = good ? q[j] : qg[j];
+        const bool edge = constraint_band_edge(P, C, qs, qg, !has || good);
+        if (threadIdx.x == 0u)
+        {
+            c_ok[a] = edge ? 1u : 0u;
+            if (!edge) refused[active[a]] += 1u;  // (this wave owns its problem's counter; the null question is in band)
+        }
+    }
+
+    // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
     namespace
@@ -2443,6 +2778,42 @@ namespace VMV_ROBOT_NS
             VMV_HIP_TU(hipGetLastError());
             return VMV_OK;
         }
+
+        // vmv_constraint_*_batch: n lanes / edges, below 2^31 (the API checks); d_res may be nullptr
+        int launch_constraint_project(const ConstraintParams &P, const ConstraintDev *d_cons, const float *d_q, size_t n, float *d_q_out,
+                                      float *d_res, uint32_t *d_status, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(constraint_project_kernel<>, dim3((uint32_t) ((n + kIkBlock - 1u) / kIkBlock)), dim3(kIkBlock), 0, stream,
+                               P, d_cons, d_q, (uint32_t) n, d_q_out, d_res, d_status);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+        int launch_constraint_check(const ConstraintParams &P, const ConstraintDev *d_cons, const float *d_q, size_t n, uint64_t *d_bits,
+                                    float *d_res, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(constraint_check_kernel<>, dim3((uint32_t) ((n + kIkBlock - 1u) / kIkBlock)), dim3(kIkBlock), 0, stream, P,
+                               d_cons, d_q, (uint32_t) n, d_bits, d_res);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+        int launch_constraint_edges(const ConstraintParams &P, const ConstraintDev *d_cons, const float *d_a, const float *d_b, size_t n,
+                                    uint8_t *d_ok, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(constraint_edge_kernel<>, dim3((uint32_t) n), dim3(kIkBlock), 0, stream, P, d_cons, d_a, d_b, (uint32_t) n,
+                               d_ok);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
+        // the constraint's part of a planner round: na active slots (vmv_rrtc_multi_constrained)
+        int launch_constraint_round(const ConstraintParams &P, const ConstraintDev *d_cons, const uint32_t *d_active, const float *d_q_start,
+                                    float *d_q_goal, const uint64_t *d_pending, float *d_pool, float stretch, uint8_t *d_c_ok,
+                                    uint32_t *d_refused, uint32_t na, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(constraint_round_kernel<>, dim3(na), dim3(kIkBlock), 0, stream, P, d_cons, d_active, d_q_start, d_q_goal,
+                               d_pending, d_pool, stretch, d_c_ok, d_refused);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
     }  // namespace
 
 }  // namespace VMV_ROBOT_NS
@@ -2459,6 +2830,10 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_clearance_grad,
                                                     VMV_ROBOT_NS::launch_clearance_grad_multi,
                                                     VMV_ROBOT_NS::launch_eefk_jacobian, VMV_ROBOT_NS::launch_ik,
-                                                    VMV_ROBOT_NS::launch_cartesian};
+                                                    VMV_ROBOT_NS::launch_cartesian,
+                                                    VMV_ROBOT_NS::launch_constraint_project,
+                                                    VMV_ROBOT_NS::launch_constraint_check,
+                                                    VMV_ROBOT_NS::launch_constraint_edges,
+                                                    VMV_ROBOT_NS::launch_constraint_round};
 #endif
 }  // namespace vmv

@@ -81,7 +81,14 @@ namespace vmv
             float *q_start, *q_goal;   // [n_active][dim] the round's questions
             const uint64_t *bits;      // answers of the previous round
             uint8_t *done;             // [n_problems]
+            // vmv_rrtc_multi_constrained only, both NULL otherwise (exactly as radii): pending[a] = the pool element (over all
+            // problems) of the node the question's far end was written to - A's next slot for an extension, B's next slot for
+            // a march step - or kNoPending for a direct and for the null question; c_ok[slot] = the constraint round's answer
+            // to the previous question, ANDed into the validity bit
+            uint64_t *pending;         // [n_active]
+            const uint8_t *c_ok;       // [n_active]
         };
+        constexpr uint64_t kNoPending = ~0ull;
 
         __device__ __forceinline__ uint32_t first_goal(const RrtcArrays &D, uint32_t p) { return D.goal_offsets ? D.goal_offsets[p] : p; }
         __device__ __forceinline__ uint32_t goal_count(const RrtcArrays &D, uint32_t p)
@@ -145,11 +152,12 @@ namespace vmv
                 if (tid < dim) qs[tid] = start[tid], qg[tid] = goals[tid];
                 st.phase = kPhaseDirect, st.slot = a, st.questions = 1, st.k = 0;
                 if (tid == 0) D.state[p] = st;
+                if (D.pending && tid == 0) D.pending[a] = kNoPending;
                 return;
             }
             else
             {
-                const bool ans = (D.bits[st.slot >> 6] >> (st.slot & 63u)) & 1ull;
+                const bool ans = ((D.bits[st.slot >> 6] >> (st.slot & 63u)) & 1ull) && (!D.c_ok || D.c_ok[st.slot] != 0);
                 const uint32_t sa = st.a_side, sb = sa ^ 1u;
                 if (st.phase == kPhaseDirect)
                 {
@@ -161,6 +169,7 @@ namespace vmv
                         if (tid < dim) qs[tid] = start[tid], qg[tid] = goals[(size_t) st.k * dim + tid];
                         st.slot = a, ++st.questions;
                         if (tid == 0) D.state[p] = st;
+                        if (D.pending && tid == 0) D.pending[a] = kNoPending;
                         return;
                     }
                     else
@@ -228,6 +237,7 @@ namespace vmv
                     {
                         parent[node_at(sb, count_of(st.n, sb), M)] = st.prev, D.state[p] = st;
                         if (radii) radii[node_at(sb, count_of(st.n, sb), M)] = kRadiusUnset;
+                        if (D.pending) D.pending[a] = (uint64_t) p * M + node_at(sb, count_of(st.n, sb), M);
                     }
                     return;
                 }
@@ -267,6 +277,7 @@ namespace vmv
                     {
                         parent[node_at(sa, count_of(st.n, sa), M)] = ni, D.state[p] = st;
                         if (radii) radii[node_at(sa, count_of(st.n, sa), M)] = kRadiusUnset;
+                        if (D.pending) D.pending[a] = (uint64_t) p * M + node_at(sa, count_of(st.n, sa), M);
                     }
                     return;
                 }
@@ -274,6 +285,7 @@ namespace vmv
 
             // finished (now or in an earlier round)
             ask_nothing(qs, qg, start, dim);
+            if (D.pending && tid == 0) D.pending[a] = kNoPending;
             if (st.phase != kPhaseDone && tid == 0)
             {
                 st.phase = kPhaseDone, st.slot = a;
@@ -309,12 +321,23 @@ namespace vmv
                                   D.parent + (size_t) p * P.max_samples, P.dim, P.max_samples, out);
         }
 
+        const RobotLaunchers *const kRrtcLaunchers[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
+
+        // vmv_rrtc_multi_constrained: what a round needs beside the step kernel - the resolved settings, the records on the
+        // device (one, or one per problem of the run) and max_stretch * range
+        struct ConstraintRound
+        {
+            ConstraintParams P;
+            const ConstraintDev *d_cons;
+            float stretch;
+        };
+
     // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
     // robot's part built.  lower / span: the robot's joint bounds (Robot::s_a, s_m).  goal_offsets: NULL = goals is
     // [n][dim], one goal per problem.  `call` names the entry point in vmv_last_error().
     int rrtc_multi_run(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
                        const float *starts, const float *goals, const size_t *goal_offsets, const uint64_t *skips,
-                       const vmv_rrtc_goals_settings &GS, const char *call, vmv_plans *plans)
+                       const vmv_rrtc_goals_settings &GS, const char *call, vmv_plans *plans, const ConstraintRound *cr = nullptr)
     {
         const vmv_rrtc_settings &S = GS.base;
         RrtcParams P{};
@@ -334,6 +357,16 @@ namespace vmv
         VMV_LOCKSTEP_HIP(mem.alloc(&D.parent, n * (size_t) S.max_samples));
         if (int rc = B.alloc(mem, n, n, 1, (size_t) dim, stream); rc != VMV_OK) return rc;
         if (P.dynamic_domain) VMV_LOCKSTEP_HIP(mem.alloc(&D.radii, n * (size_t) S.max_samples));
+        uint8_t *d_c_ok = nullptr;
+        uint32_t *d_refused = nullptr;
+        if (cr)
+        {
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_refused, n));
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(d_refused, 0, std::max<size_t>(n * 4, 16), stream));
+            VMV_LOCKSTEP_HIP(mem.alloc(&D.pending, n));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_c_ok, n));
+            D.c_ok = d_c_ok;
+        }
         size_t max_goals = 1;  // of one problem: its direct questions
         if (!goal_offsets)
         {
@@ -372,7 +405,12 @@ namespace vmv
         // to a new iteration or adds a node): a bound on the rounds that does not depend on the device's answers
         const uint64_t max_rounds = 1ull + max_goals + (uint64_t) S.max_iterations + (uint64_t) S.max_samples + check_every;
         uint64_t rounds = 0;
-        const auto step = [&](uint32_t na) { hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D); };
+        const auto step = [&](uint32_t na) {
+            hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D);
+            if (cr)  // the pending node projected and written back, the edge's band test: before the round's validation
+                (void) kRrtcLaunchers[robot]->constraint_round(cr->P, cr->d_cons, B.active, B.q_start, B.q_goal, D.pending, D.pool,
+                                                               cr->stretch, d_c_ok, d_refused, na, stream);
+        };
         if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), call,
                                      "rrtc_step_kernel", step, rounds);
             rc != VMV_OK)
@@ -384,6 +422,11 @@ namespace vmv
         plans->n = n, plans->dim = dim, plans->rounds = rounds, plans->questions = 0;
         plans->status.resize(n), plans->iterations.resize(n), plans->sizes2.resize(2 * n), plans->path_lengths.resize(n);
         plans->goal_indices.resize(n);
+        if (cr)
+        {
+            plans->band_refused.resize(n);
+            VMV_LOCKSTEP_HIP(hipMemcpy(plans->band_refused.data(), d_refused, n * 4, hipMemcpyDeviceToHost));
+        }
         for (size_t k = 0; k < n; ++k)
         {
             const RrtcState &st = states[k];
@@ -400,6 +443,134 @@ namespace vmv
                                                  P, D, n32, d_offsets, d_paths);
                           },
                           plans->paths);
+    }
+    // vmv_rrtc_multi's checks in its order, then those of the goal table and of the dynamic domain's values
+    int check_goals_call(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                         const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings, vmv_plans **out,
+                         int *dim_out)
+    {
+        int dim = 0;
+        if (int rc = check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
+        const vmv_rrtc_settings &base = settings->base;
+        if (!std::isfinite(base.range) || !(base.range > 0.f) || base.max_samples < 2) return VMV_ERR_INVALID_ARGUMENT;
+        if (!halton_skips_ok(halton_skips, n_problems, base.max_iterations)) return VMV_ERR_INVALID_ARGUMENT;
+        if (goal_offsets && n_problems > 0)
+        {
+            if (goal_offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
+            for (size_t k = 0; k < n_problems; ++k)
+            {
+                if (goal_offsets[k + 1] <= goal_offsets[k]) return VMV_ERR_INVALID_ARGUMENT;  // decreasing, or an empty set
+                if (goal_offsets[k + 1] - goal_offsets[k] > (size_t) base.max_samples - 1) return VMV_ERR_INVALID_ARGUMENT;
+            }
+            if (goal_offsets[n_problems] >= (1ull << 31)) return VMV_ERR_INVALID_ARGUMENT;
+        }
+        if (settings->dynamic_domain)
+        {
+            if (!std::isfinite(settings->radius) || !(settings->radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
+            if (!std::isfinite(settings->min_radius) || !(settings->min_radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
+            if (!std::isfinite(settings->alpha) || !(settings->alpha >= 0.f) || !(settings->alpha < 1.f)) return VMV_ERR_INVALID_ARGUMENT;
+        }
+        *dim_out = dim;
+        return VMV_OK;
+    }
+
+    // vmv_rrtc_multi_constrained behind its checks: ONE constraint_check launch over all starts and goals; a problem whose
+    // start is out of band or that has no in-band goal ends VMV_PLAN_INVALID_ENDPOINT and takes no part; the others run
+    // as a call of their own (a problem's result is its own) with their in-band goals, the round kernel in every round.
+    int rrtc_constrained_run(int robot, int dim, const vmv_env *const *envs, size_t n, const float *starts, const float *goals,
+                             const size_t *goal_offsets, const uint64_t *skips, const vmv_rrtc_goals_settings &GS,
+                             const vmv_ee_constraint *constraints, size_t n_constraints, ConstraintParams CP, float max_stretch,
+                             vmv_plans *plans)
+    {
+        float lower[16], span[16], descale[16];
+        if (int rc = vmv_robot_bounds(robot, lower, span, descale); rc != VMV_OK) return rc;
+        for (int j = 0; j < 16; ++j) CP.lower[j] = j < dim ? lower[j] : 0.f, CP.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
+        CP.shared = n_constraints == 1 ? 1u : 0u;
+        const RobotLaunchers &L = *kRrtcLaunchers[robot];
+        hipStream_t stream = nullptr;
+        std::vector<ConstraintDev> recs(n_constraints);
+        for (size_t k = 0; k < n_constraints; ++k) constraint_record(constraints[k], (double) CP.pos_tol, (double) CP.rot_tol, recs[k]);
+        const auto first = [&](size_t p) { return goal_offsets ? goal_offsets[p] : p; };
+        const size_t G = first(n), lanes = n + G;
+
+        // ---- the endpoints' band test: lanes [0, n) the starts, [n, n + G) the goals, each with its problem's record
+        std::vector<uint64_t> bits((lanes + 63) / 64);
+        {
+            DeviceBuffers mem;
+            float *d_q = nullptr;
+            ConstraintDev *d_recs = nullptr;
+            uint64_t *d_bits = nullptr;
+            std::vector<ConstraintDev> per_lane;
+            if (!CP.shared)
+            {
+                per_lane.resize(lanes);
+                for (size_t p = 0; p < n; ++p)
+                {
+                    per_lane[p] = recs[p];
+                    for (size_t g = first(p); g < first(p + 1); ++g) per_lane[n + g] = recs[p];
+                }
+            }
+            const std::vector<ConstraintDev> &up = CP.shared ? recs : per_lane;
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_q, lanes * (size_t) dim));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, up.size()));
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, bits.size()));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_q, starts, n * (size_t) dim * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_q + n * (size_t) dim, goals, G * (size_t) dim * 4, hipMemcpyHostToDevice));
+            VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, up.data(), up.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+            if (int rc = L.constraint_check(CP, d_recs, d_q, lanes, d_bits, nullptr, stream); rc != VMV_OK) return rc;
+            VMV_LOCKSTEP_HIP(hipMemcpy(bits.data(), d_bits, bits.size() * 8, hipMemcpyDeviceToHost));
+        }
+        const auto in_band = [&](size_t lane) { return ((bits[lane >> 6] >> (lane & 63u)) & 1ull) != 0; };
+
+        // ---- the problems that take part, with their in-band goals (goal_of: the goal's index within its own set)
+        std::vector<size_t> kept, offsets(1, 0);
+        std::vector<uint32_t> goal_of;
+        std::vector<float> k_starts, k_goals;
+        std::vector<uint64_t> k_skips;
+        std::vector<const vmv_env *> k_envs;
+        std::vector<ConstraintDev> k_recs;
+        for (size_t p = 0; p < n; ++p)
+        {
+            const size_t before = goal_of.size();
+            for (size_t g = first(p); in_band(p) && g < first(p + 1); ++g)
+                if (in_band(n + g))
+                {
+                    goal_of.push_back((uint32_t) (g - first(p)));
+                    k_goals.insert(k_goals.end(), goals + g * (size_t) dim, goals + (g + 1) * (size_t) dim);
+                }
+            if (goal_of.size() == before) continue;
+            kept.push_back(p), offsets.push_back(goal_of.size()), k_envs.push_back(envs[p]);
+            k_starts.insert(k_starts.end(), starts + p * (size_t) dim, starts + (p + 1) * (size_t) dim);
+            if (skips) k_skips.push_back(skips[p]);
+            if (!CP.shared) k_recs.push_back(recs[p]);
+        }
+        plans->n = n, plans->dim = dim, plans->rounds = 0, plans->questions = 0;
+        plans->status.assign(n, (uint8_t) VMV_PLAN_INVALID_ENDPOINT), plans->iterations.assign(n, 0u), plans->sizes2.assign(2 * n, 0u);
+        plans->path_lengths.assign(n, 0u), plans->goal_indices.assign(n, UINT32_MAX), plans->paths.clear();
+        plans->band_refused.assign(n, 0u);
+        if (kept.empty()) return VMV_OK;
+
+        DeviceBuffers mem;
+        ConstraintDev *d_recs = nullptr;
+        const std::vector<ConstraintDev> &up = CP.shared ? recs : k_recs;
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, up.size()));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, up.data(), up.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+        const ConstraintRound cr{CP, d_recs, max_stretch * GS.base.range};
+        vmv_plans sub;
+        if (int rc = rrtc_multi_run(robot, dim, lower, span, k_envs.data(), kept.size(), k_starts.data(), k_goals.data(), offsets.data(),
+                                    skips ? k_skips.data() : nullptr, GS, "vmv_rrtc_multi_constrained", &sub, &cr);
+            rc != VMV_OK)
+            return rc;
+        for (size_t k = 0; k < kept.size(); ++k)  // (the others have no waypoints: the packed paths are the run's as they are)
+        {
+            const size_t p = kept[k];
+            plans->status[p] = sub.status[k], plans->iterations[p] = sub.iterations[k], plans->path_lengths[p] = sub.path_lengths[k];
+            plans->sizes2[2 * p] = sub.sizes2[2 * k], plans->sizes2[2 * p + 1] = sub.sizes2[2 * k + 1];
+            if (sub.goal_indices[k] != UINT32_MAX) plans->goal_indices[p] = goal_of[offsets[k] + sub.goal_indices[k]];
+            plans->band_refused[p] = sub.band_refused[k];
+        }
+        plans->paths = std::move(sub.paths), plans->rounds = sub.rounds, plans->questions = sub.questions;
+        return VMV_OK;
     }
     }  // namespace
 }  // namespace vmv
@@ -430,28 +601,9 @@ extern "C"
                              const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings,
                              vmv_plans **out)
     {
-        // vmv_rrtc_multi's checks in its order, then those of the goal table and of the dynamic domain's values
         int dim = 0;
-        if (int rc = vmv::check_planner_call(robot, settings, out, envs, n_problems, starts, goals, &dim); rc != VMV_OK) return rc;
-        const vmv_rrtc_settings &base = settings->base;
-        if (!std::isfinite(base.range) || !(base.range > 0.f) || base.max_samples < 2) return VMV_ERR_INVALID_ARGUMENT;
-        if (!vmv::halton_skips_ok(halton_skips, n_problems, base.max_iterations)) return VMV_ERR_INVALID_ARGUMENT;
-        if (goal_offsets && n_problems > 0)
-        {
-            if (goal_offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
-            for (size_t k = 0; k < n_problems; ++k)
-            {
-                if (goal_offsets[k + 1] <= goal_offsets[k]) return VMV_ERR_INVALID_ARGUMENT;  // decreasing, or an empty set
-                if (goal_offsets[k + 1] - goal_offsets[k] > (size_t) base.max_samples - 1) return VMV_ERR_INVALID_ARGUMENT;
-            }
-            if (goal_offsets[n_problems] >= (1ull << 31)) return VMV_ERR_INVALID_ARGUMENT;
-        }
-        if (settings->dynamic_domain)
-        {
-            if (!std::isfinite(settings->radius) || !(settings->radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
-            if (!std::isfinite(settings->min_radius) || !(settings->min_radius > 0.f)) return VMV_ERR_INVALID_ARGUMENT;
-            if (!std::isfinite(settings->alpha) || !(settings->alpha >= 0.f) || !(settings->alpha < 1.f)) return VMV_ERR_INVALID_ARGUMENT;
-        }
+        if (int rc = vmv::check_goals_call(robot, envs, n_problems, starts, goals, goal_offsets, halton_skips, settings, out, &dim); rc != VMV_OK)
+            return rc;
         const int rc = vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
             float lower[16], span[16], descale[16];
             const int rc = vmv_robot_bounds(robot, lower, span, descale);
@@ -461,6 +613,39 @@ extern "C"
         });
         if (rc == VMV_OK) (*out)->rrtc_goals = true;
         return rc;
+    }
+
+    int vmv_rrtc_multi_constrained(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                                   const size_t *goal_offsets, const uint64_t *halton_skips, const vmv_rrtc_goals_settings *settings,
+                                   const vmv_ee_constraint *constraints, size_t n_constraints,
+                                   const vmv_constraint_plan_settings *constraint_settings, vmv_plans **out)
+    {
+        // vmv_rrtc_multi_goals's checks in its order, then the constraint's own; none needs a device
+        int dim = 0;
+        if (int rc = vmv::check_goals_call(robot, envs, n_problems, starts, goals, goal_offsets, halton_skips, settings, out, &dim); rc != VMV_OK)
+            return rc;
+        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
+        if (n_constraints != 1 && n_constraints != n_problems) return vmv::refuse_argument("n_constraints must be 1 or n_problems");
+        vmv::ConstraintParams CP{};
+        if (const char *err = vmv::constraint_settings(constraint_settings->base, CP)) return vmv::refuse_argument(err);
+        const float ms = constraint_settings->max_stretch;
+        if (!(std::isfinite(ms) && ms >= 0.f)) return vmv::refuse_argument("max_stretch must be finite and not negative (0 = default)");
+        for (size_t k = 0; k < n_constraints; ++k)
+            if (const char *err = vmv::constraint_refusal(constraints[k]))
+                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
+        const int rc = vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
+            return vmv::rrtc_constrained_run(robot, dim, envs, n_problems, starts, goals, goal_offsets, halton_skips, *settings, constraints,
+                                             n_constraints, CP, ms > 0.f ? ms : 2.f, plans);
+        });
+        if (rc == VMV_OK) (*out)->rrtc_goals = (*out)->constrained = true, (*out)->band_refused.resize(n_problems);
+        return rc;
+    }
+
+    int vmv_plans_band_refused(const vmv_plans *plans, uint32_t *refused)
+    {
+        if (!plans || !plans->constrained) return VMV_ERR_INVALID_ARGUMENT;
+        if (refused && plans->n) std::memcpy(refused, plans->band_refused.data(), plans->n * 4);
+        return VMV_OK;
     }
 
     int vmv_plans_goal_indices(const vmv_plans *plans, uint32_t *goal_index)

@@ -358,7 +358,7 @@ def _planning_results(raw, lengths="path_lengths", points="paths", **fields):
 
 
 def _rrtc_results(raw):
-    out = _planning_results(raw, goal_index=("goal_indices", int))
+    out = _planning_results(raw, goal_index=("goal_indices", int), band_refused=("band_refused", int))  # (the latter: constrained calls)
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
@@ -385,6 +385,30 @@ def rrtc_multi_goals(robot, starts, goal_sets, environments, settings: RRTCMulti
     packed = np.concatenate(sets) if sets else np.zeros((0, robot.dimension()), np.float32)
     counts = np.array([len(g) for g in sets], np.int64)
     return _rrtc_results(robot.rrtc_multi_goals_raw(starts, packed, counts, environments, s, skips))
+
+
+def rrtc_multi_constrained(robot, starts, goal_sets, environments, constraints, settings: RRTCMultiSettings | None = None,
+                           constraint_settings=None, skips=None, max_stretch=2.0):
+    """`rrtc_multi_goals` under end-effector constraints (vmv_rrtc_multi_constrained): constraints is one
+    EEConstraint for all problems or one per problem; every tree node is projected into its band and every edge is
+    band-checked inside the rounds, one extra launch per round.  Endpoints come from `project_goals`: a problem whose
+    start is out of band, or none of whose goals is in band, ends "invalid_endpoint" with no path and no question, and
+    out-of-band goals of a set are never used (goal_index still counts within the caller's set).  constraint_settings: a
+    ConstraintSettings (its check_step spaces the band samples of an edge); max_stretch: a projected node farther than
+    max_stretch * range from the edge's near end is refused.  -> list[PlanningResult] as `rrtc_multi_goals`'s.  The path's
+    edges pass `constraint_check_motion_batch`; a later shortcut or optimisation does not know the constraint - ask
+    `validate_paths_constrained` of it.  Each result also carries `band_refused`: the questions the constraint answered 0."""
+    s = settings or RRTCMultiSettings()
+    sets = []
+    for g in goal_sets:
+        g = np.asarray(g, np.float32)
+        if g.ndim != 2 or g.shape[0] < 1 or g.shape[1] != robot.dimension():
+            raise TypeError(f"expected every goal set as a [G][{robot.dimension()}] array with G >= 1, got shape {g.shape}")
+        sets.append(g)
+    packed = np.concatenate(sets) if sets else np.zeros((0, robot.dimension()), np.float32)
+    counts = np.array([len(g) for g in sets], np.int64)
+    return _rrtc_results(robot.rrtc_multi_constrained_raw(starts, packed, counts, environments, constraints, s, constraint_settings,
+                                                          max_stretch, skips))
 
 
 def prm_multi(robot, starts, goals, environments, settings: PRMMultiSettings | None = None, skips=None, samples=None):
@@ -875,6 +899,67 @@ def ik_goals(robot, targets, envs, settings=None, dedup=1e-2):
         at += int(counts[p])
         goal_sets.append(np.array(kept, np.float32).reshape(len(kept), q.shape[2]))
     return goal_sets, [p for p in range(n) if len(goal_sets[p]) == 0]
+
+
+def _per_problem(items, n, what):
+    """a list or tuple of n, or anything else broadcast to the n problems"""
+    items = list(items) if isinstance(items, (list, tuple)) else [items] * n
+    if len(items) != n:
+        raise ValueError(f"{n} problems, but {len(items)} {what}")
+    return items
+
+
+def validate_paths_constrained(robot, paths, envs, constraints, settings=None):
+    """-> (valid bool[len(paths)], in_band bool[len(paths)]): path p's consecutive pairs against envs[p] (validate_paths)
+    and against the band of constraints[p] (an EEConstraint; one is shared by all paths), in TWO batched calls:
+    `robot.validate_motion_batch_multi` and `robot.constraint_check_motion_batch`, the latter with `settings` = a
+    ConstraintSettings whose check_step spaces the band samples.  A path of fewer than 2 waypoints is valid and in band.
+    What a shortcut, a smoothing or an optimisation returns is to be asked here: none of them knows the constraint."""
+    dim = robot.dimension()
+    pts = [np.asarray(p, np.float32).reshape(-1, dim) for p in paths]
+    n = len(pts)
+    environments = _per_problem(envs, n, "environments")
+    records = _per_problem(constraints, n, "constraints")
+    counts = [max(len(p) - 1, 0) for p in pts]
+    empty = np.zeros((0, dim), np.float32)
+    a, b = np.concatenate([p[:-1] for p in pts] + [empty]), np.concatenate([p[1:] for p in pts] + [empty])
+    if n == 0:
+        return np.zeros(0, bool), np.zeros(0, bool)
+    per_edge = [records[p] for p in range(n) for _ in range(counts[p])]
+    ends = np.concatenate([[0], np.cumsum(counts)])
+
+    def whole(ok):  # path p holds no failing edge (prefix counts: empty segments need no special case)
+        bad = np.concatenate([[0], np.cumsum(~np.asarray(ok, bool))])
+        return bad[ends[1:]] == bad[ends[:-1]]
+
+    valid = whole(robot.validate_motion_batch_multi(a, b, environments, counts))
+    return valid, whole(robot.constraint_check_motion_batch(a, b, per_edge, settings))
+
+
+def project_goals(robot, goals, constraints, envs, settings=None):
+    """Endpoints for planning under a constraint: goals[p] a [G_p][dim] set of configurations of problem p (a start is a
+    set of one), projected into the band of constraints[p] (an EEConstraint; one is shared) and checked in envs[p] (an
+    Environment or None; one is shared).  ONE `robot.project_batch` call over all rows and ONE `robot.validate_batch_multi`
+    call over the converged ones; a row whose projection did not converge or collides is dropped.  -> per problem a
+    float32 [G'_p][dim] array, in the rows' order - what `rrtc_multi_goals` takes as goal sets."""
+    dim = robot.dimension()
+    sets = [np.asarray(g, np.float32).reshape(-1, dim) for g in goals]
+    n = len(sets)
+    environments = _per_problem(envs, n, "environments")
+    records = _per_problem(constraints, n, "constraints")
+    if n == 0:
+        return []
+    rows = np.concatenate(sets)
+    owner = np.repeat(np.arange(n), [len(g) for g in sets])
+    if len(rows) == 0:
+        return [np.zeros((0, dim), np.float32) for _ in sets]
+    q, _, converged, _ = robot.project_batch(rows, [records[p] for p in owner], settings)
+    q, converged = np.asarray(q, np.float32), np.asarray(converged, bool)
+    counts = np.bincount(owner[converged], minlength=n).astype(np.int64)
+    valid = np.asarray(robot.validate_batch_multi(q[converged], environments, counts), bool) if converged.any() else np.zeros(0, bool)
+    keep = converged.copy()
+    keep[converged] = valid
+    return [q[keep & (owner == p)].reshape(-1, dim) for p in range(n)]
 
 
 CARTESIAN_STATUS = ("complete", "ik_failed", "joint_jump", "collision", "invalid_start", "too_long", "non_finite")  # VMV_CART_*
