@@ -157,18 +157,12 @@ def project(robot, q_in, constraints, s=None):
     for _ in range(s.max_iterations):
         if done.all():
             break
-        g = np.einsum("nij,ni->nj", Jw, e)
-        Jm = np.where((((q <= lo) & (g < 0.0)) | ((q >= hi) & (g > 0.0)))[:, None, :], 0.0, Jw)
-        A = np.einsum("nij,nkj->nik", Jm, Jm) + lam[:, None, None] * np.eye(6)[None]
-        y = np.linalg.solve(A, e[:, :, None])[:, :, 0]
-        d = np.einsum("nij,ni->nj", Jm, y)
-        d *= (s.max_step / np.maximum(np.abs(d).max(axis=1), s.max_step))[:, None]
-        cand = np.where(moves[None, :], np.clip(q + d, lo, hi), q)
+        cand = np.where(moves[None, :], K.step(q, Jw, e, lam, lo, hi, s.max_step), q)
         Jc, ec, Ec, rc = evaluate(cand)
         live = ~done
         acc = live & (Ec < E)
         evals += live
-        lam = np.where(live, np.where(acc, np.maximum(lam / K.LAMBDA_FACTOR, K.LAMBDA_FLOOR), np.minimum(lam * K.LAMBDA_FACTOR, K.LAMBDA_CEIL)), lam)
+        lam = K.damped(lam, live, acc)
         q[acc], Jw[acc], e[acc], E[acc], res[acc] = cand[acc], Jc[acc], ec[acc], Ec[acc], rc["res"][acc]
         converged = converged | (acc & rc["band"])
         done = done | (acc & rc["band"])

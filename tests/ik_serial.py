@@ -115,6 +115,21 @@ def energy(robot, q, target, s):
     return 0.5 * (weighted(e_p, e_w, tr, s) ** 2).sum(axis=1)
 
 
+def step(q, Jw, e, lam, lo, hi, max_step, hold=True):
+    """lm_step (csrc/vmv_robot_tu.inc): the candidates clip(q + delta), delta = Jm^T (Jm Jm^T + lam I)^-1 e capped at max_step"""
+    g = np.einsum("nij,ni->nj", Jw, e)  # a joint at a bound whose descent direction g_j points outward sits this step out
+    held = (((q <= lo) & (g < 0.0)) | ((q >= hi) & (g > 0.0))) & hold
+    Jm = np.where(held[:, None, :], 0.0, Jw)
+    A = np.einsum("nij,nkj->nik", Jm, Jm) + lam[:, None, None] * np.eye(6)[None]
+    d = np.einsum("nij,ni->nj", Jm, np.linalg.solve(A, e[:, :, None])[:, :, 0])
+    return np.clip(q + d * (max_step / np.maximum(np.abs(d).max(axis=1), max_step))[:, None], lo, hi)
+
+
+def damped(lam, live, acc, factor=LAMBDA_FACTOR, floor=LAMBDA_FLOOR, ceil=LAMBDA_CEIL):
+    """lm_accept's schedule: a live lane's lambda falls by `factor` after an accepted step, rises after a rejected one"""
+    return np.where(live, np.where(acc, np.maximum(lam / factor, floor), np.minimum(lam * factor, ceil)), lam)
+
+
 def solve(robot, targets, seeds, s, factor=LAMBDA_FACTOR, floor=LAMBDA_FLOOR, ceil=LAMBDA_CEIL, hold=True):
     """targets [n][4][4] (or [n][16]), seeds [n][dim], one lane each -> dict(q, err [n][2], converged, iterations, E, E_seed).
     hold=False: the iteration without the bound rule (DESIGN.md 5k records the comparison)."""
@@ -140,21 +155,12 @@ def solve(robot, targets, seeds, s, factor=LAMBDA_FACTOR, floor=LAMBDA_FLOOR, ce
     for _ in range(s.max_iterations):
         if done.all():
             break
-        Jm = Jw
-        if hold:  # a joint at a bound whose descent direction g_j = (Jw^T e)_j points outward sits this step out
-            g = np.einsum("nij,ni->nj", Jw, e)
-            Jm = np.where((((q <= lo) & (g < 0.0)) | ((q >= hi) & (g > 0.0)))[:, None, :], 0.0, Jw)
-        A = np.einsum("nij,nkj->nik", Jm, Jm) + lam[:, None, None] * np.eye(6)[None]
-        y = np.linalg.solve(A, e[:, :, None])[:, :, 0]
-        d = np.einsum("nij,ni->nj", Jm, y)
-        big = np.abs(d).max(axis=1)
-        d *= (s.max_step / np.maximum(big, s.max_step))[:, None]
-        cand = np.clip(q + d, lo, hi)
+        cand = step(q, Jw, e, lam, lo, hi, s.max_step, hold)
         Jc, ec, Ec, errc, okc = evaluate(cand)
         live = ~done
         acc = live & (Ec < E)
         its += live
-        lam = np.where(live, np.where(acc, np.maximum(lam / factor, floor), np.minimum(lam * factor, ceil)), lam)
+        lam = damped(lam, live, acc, factor, floor, ceil)
         q[acc], Jw[acc], e[acc], E[acc], err[acc] = cand[acc], Jc[acc], ec[acc], Ec[acc], errc[acc]
         done = done | (acc & okc)
     return dict(q=q, err=err, converged=done, iterations=its, E=E, E_seed=E_seed)

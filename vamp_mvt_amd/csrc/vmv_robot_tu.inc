@@ -1359,6 +1359,18 @@ namespace VMV_ROBOT_NS
         e[3] = s * wx, e[4] = s * wy, e[5] = s * wz;
     }
 
+    // the rows of ik_error's weighted error: the Jacobian's, the angular ones times w
+    __device__ __forceinline__ void ik_weigh(const float w, float (&J)[6][R::kDim])
+    {
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+            if (ee_joint(j))
+            {
+#pragma unroll
+                for (int r = 3; r < 6; ++r) J[r][j] = w * J[r][j];
+            }
+    }
+
     // y = A^-1 b for the symmetric positive definite A = Jm Jm^T + lambda I (its lower triangle), by a Cholesky
     // factorisation in registers: every loop has constant bounds and unrolls.  A pivot that rounding took to zero or below
     // is raised to 1e-12 (lambda >= kIkLambdaFloor keeps it away from there but for rounding).
@@ -1399,14 +1411,117 @@ namespace VMV_ROBOT_NS
         }
     }
 
-    // vmv_ik_batch: Levenberg-Marquardt from one seed towards one target per lane (lane i: target i / n_seeds, seed i, or
-    // seed i % n_seeds of the shared Halton seeds).  The loop body is ONE evaluation of a candidate - the seed first, then
-    // q + step - followed by selects into the accepted state (q, the weighted Jacobian, the error, E, lambda): a rejected
-    // step keeps the old Jacobian in registers and nothing is evaluated twice.  There is no branch in the body but the
-    // wave-uniform exit, so the compiler has no conditional region to sink the tape into.  A joint that sits at a bound
-    // while the descent direction g = Jw^T e points outward is left out of the step (its column of Jw reads as zero), so
-    // the other joints are not asked to make up for a motion the clip will take away.  A lane's result depends on its own
-    // target, seed and settings alone.
+    // The damped least-squares (Levenberg-Marquardt) iteration, stated once for ik_kernel and cartesian_track_kernel
+    // (DESIGN.md 5k; constraint_project_lane writes the same out, see there); tests/ik_serial.py states it in float64
+    // (step, damped).  A loop body is ONE evaluation of a candidate - the start first, then lm_step's - followed by
+    // lm_accept's selects into the accepted state: a rejected step keeps the old rows in registers and nothing is
+    // evaluated twice.  The three functions hold no branch, so with the caller's wave-uniform exit the compiler has no
+    // conditional region to sink the tape into; every fp32 operation stands in the order the callers' results are
+    // pinned to.
+    struct LmState  // the accepted state
+    {
+        float q[R::kDim];      // the configuration
+        float Jw[6][R::kDim];  // its weighted rows: the caller's error e has the Jacobian de/dq = -Jw
+        float e[6], E, lam;    // the weighted error, E = 1/2 |e|^2, the damping lambda
+    };
+
+    // the start: the candidate clipped to the bounds; no rows, E = inf, lambda = damping
+    template <class Params>
+    __device__ __forceinline__ void lm_start(const Params &P, float (&cand)[R::kDim], LmState &S)
+    {
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            cand[j] = fminf(fmaxf(cand[j], P.lower[j]), P.upper[j]);
+            S.q[j] = cand[j];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) S.Jw[r][j] = 0.0f;
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) S.e[r] = 0.0f;
+        S.E = __builtin_inff(), S.lam = P.damping;
+    }
+
+    // the accept: the candidate (its weighted rows Jc, its error ec and Ec) is taken if it lowers E - the first whatever
+    // it gives, which leaves lambda alone; a lane that is done takes nothing.  lambda falls by kIkLambdaFactor after a step
+    // that was taken and rises after one that was not; evals counts the candidates after the first.  -> taken
+    __device__ __forceinline__ bool lm_accept(const bool first, const bool done, const float (&cand)[R::kDim], const float (&Jc)[6][R::kDim],
+                                              const float (&ec)[6], const float Ec, LmState &S, uint32_t &evals)
+    {
+        const bool take = !done && (first || Ec < S.E);
+        const float lam_next = take ? fmaxf(S.lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(S.lam * kIkLambdaFactor, kIkLambdaCeil);
+        S.lam = (done || first) ? S.lam : lam_next;
+        evals += (done || first) ? 0u : 1u;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            S.q[j] = take ? cand[j] : S.q[j];
+            if (ee_joint(j))
+            {
+#pragma unroll
+                for (int r = 0; r < 6; ++r) S.Jw[r][j] = take ? Jc[r][j] : S.Jw[r][j];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) S.e[r] = take ? ec[r] : S.e[r];
+        S.E = take ? Ec : S.E;
+        return take;
+    }
+
+    // the step from the accepted state: A = Jm Jm^T + lambda I, A y = e, delta = Jm^T y, capped at max_step; the next
+    // candidate is q + delta clipped to the bounds.  Jm: a joint that sits at a bound while the descent direction g = Jw^T e
+    // points outward is left out of the step (its column of Jw reads as zero), so the other joints are not asked to make
+    // up for a motion the clip will take away.
+    template <class Params>
+    __device__ __forceinline__ void lm_step(const Params &P, const LmState &S, float (&cand)[R::kDim])
+    {
+        float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+            if (ee_joint(j))
+            {
+                float g = S.Jw[0][j] * S.e[0];
+#pragma unroll
+                for (int r = 1; r < 6; ++r) g += S.Jw[r][j] * S.e[r];
+                const bool hold = (S.q[j] <= P.lower[j] && g < 0.0f) || (S.q[j] >= P.upper[j] && g > 0.0f);
+#pragma unroll
+                for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : S.Jw[r][j];
+            }
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b <= a; ++b)
+            {
+                float s = a == b ? S.lam : 0.0f;
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j)
+                    if (ee_joint(j)) s += Jm[a][j] * Jm[b][j];
+                A[a][b] = s;
+            }
+        chol6_solve(A, S.e, y);
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            delta[j] = 0.0f;
+            if (ee_joint(j))
+            {
+                float s = Jm[0][j] * y[0];
+#pragma unroll
+                for (int r = 1; r < 6; ++r) s += Jm[r][j] * y[r];
+                delta[j] = s;
+                big = fmaxf(big, fabsf(s));
+            }
+        }
+        const float scale = P.max_step / fmaxf(big, P.max_step);  // 1 while the largest joint change is within max_step
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+            cand[j] = ee_joint(j) ? fminf(fmaxf(S.q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : S.q[j];
+    }
+
+    // vmv_ik_batch: the iteration above from one seed towards one target per lane (lane i: target i / n_seeds, seed i, or
+    // seed i % n_seeds of the shared Halton seeds), its rows the Jacobian's with rot_weight on the angular ones.  There is
+    // no branch in the loop but the wave-uniform exit.  A lane's result depends on its own target, seed and settings
+    // alone.
     template <int = 0>
     __global__ __launch_bounds__(kIkBlock) void ik_kernel(const IkParams P, const float *__restrict__ targets,
                                                           const float *__restrict__ seeds, const uint32_t n,
@@ -1438,108 +1553,42 @@ namespace VMV_ROBOT_NS
 #pragma unroll
         for (int k = 0; k < 12; ++k) T[k] = finite ? T[k] : 0.0f;
 #pragma unroll
-        for (int j = 0; j < R::kDim; ++j) cand[j] = fminf(fmaxf(finite ? cand[j] : 0.0f, P.lower[j]), P.upper[j]);
+        for (int j = 0; j < R::kDim; ++j) cand[j] = finite ? cand[j] : 0.0f;
 
-        float q[R::kDim], Jw[6][R::kDim], e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float E = __builtin_inff(), lam = P.damping, err_p = 0.0f, err_w = 0.0f;
+        LmState W;
+        lm_start(P, cand, W);
+        float err_p = 0.0f, err_w = 0.0f;
         bool done = !in_range || !finite, converged = false;
         uint32_t evals = 0;
-#pragma unroll
-        for (int j = 0; j < R::kDim; ++j)
-        {
-            q[j] = cand[j];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) Jw[r][j] = 0.0f;
-        }
         for (uint32_t it = 0;; ++it)
         {
-            // ---- one evaluation: the candidate's frame, Jacobian, error and E
+            // ---- one evaluation: the candidate's frame, weighted Jacobian, error and E
             float f[12], df[12][R::kDim], Jc[6][R::kDim], ec[6], n_p, n_w, tr;
             R::ee_frame_jac(cand, f, df);
             ee_jacobian(f, df, Jc);
             ik_error(f, T, P.rot_weight, ec, n_p, n_w, tr);
+            ik_weigh(P.rot_weight, Jc);
             const float Ec = 0.5f * (dot3(ec[0], ec[1], ec[2], ec[0], ec[1], ec[2]) + dot3(ec[3], ec[4], ec[5], ec[3], ec[4], ec[5]));
-            const bool first = it == 0u;  // the seed's evaluation is taken whatever it gives and leaves lambda alone
-            const bool take = !done && (first || Ec < E);
+            const bool take = lm_accept(it == 0u, done, cand, Jc, ec, Ec, W, evals);
             const bool ok = n_p <= P.pos_tol && (P.position_only != 0u || (tr > 1.0f && n_w <= P.rot_tol));
-            const float lam_next = take ? fmaxf(lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(lam * kIkLambdaFactor, kIkLambdaCeil);
-            lam = (done || first) ? lam : lam_next;
-            evals += (done || first) ? 0u : 1u;
-#pragma unroll
-            for (int j = 0; j < R::kDim; ++j)
-            {
-                q[j] = take ? cand[j] : q[j];
-                if (ee_joint(j))
-                {
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) Jw[r][j] = take ? Jc[r][j] : Jw[r][j];
-#pragma unroll
-                    for (int r = 3; r < 6; ++r) Jw[r][j] = take ? P.rot_weight * Jc[r][j] : Jw[r][j];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) e[r] = take ? ec[r] : e[r];
-            E = take ? Ec : E;
             err_p = take ? n_p : err_p, err_w = take ? n_w : err_w;
             converged = converged || (take && ok);
             done = done || (take && ok);
             if (it == P.max_iterations || !wave_any(!done)) break;
-
-            // ---- the step from the accepted state: A = Jm Jm^T + lambda I, A y = e, delta = Jm^T y
-            float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
-#pragma unroll
-            for (int j = 0; j < R::kDim; ++j)
-                if (ee_joint(j))
-                {
-                    float g = Jw[0][j] * e[0];
-#pragma unroll
-                    for (int r = 1; r < 6; ++r) g += Jw[r][j] * e[r];
-                    const bool hold = (q[j] <= P.lower[j] && g < 0.0f) || (q[j] >= P.upper[j] && g > 0.0f);
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : Jw[r][j];
-                }
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = 0; b <= a; ++b)
-                {
-                    float s = a == b ? lam : 0.0f;
-#pragma unroll
-                    for (int j = 0; j < R::kDim; ++j)
-                        if (ee_joint(j)) s += Jm[a][j] * Jm[b][j];
-                    A[a][b] = s;
-                }
-            chol6_solve(A, e, y);
-#pragma unroll
-            for (int j = 0; j < R::kDim; ++j)
-            {
-                delta[j] = 0.0f;
-                if (ee_joint(j))
-                {
-                    float s = Jm[0][j] * y[0];
-#pragma unroll
-                    for (int r = 1; r < 6; ++r) s += Jm[r][j] * y[r];
-                    delta[j] = s;
-                    big = fmaxf(big, fabsf(s));
-                }
-            }
-            const float scale = P.max_step / fmaxf(big, P.max_step);  // 1 while the largest joint change is within max_step
-#pragma unroll
-            for (int j = 0; j < R::kDim; ++j)
-                cand[j] = ee_joint(j) ? fminf(fmaxf(q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : q[j];
+            lm_step(P, W, cand);
         }
         if (!in_range) return;
         // invalid input: the seed as given, NaN errors, bit 30
         const float poison = finite ? 0.0f : __builtin_nanf("");
 #pragma unroll
-        for (int j = 0; j < R::kDim; ++j) q_out[(size_t) i * R::kDim + j] = finite ? q[j] : sp[j];
+        for (int j = 0; j < R::kDim; ++j) q_out[(size_t) i * R::kDim + j] = finite ? W.q[j] : sp[j];
         if (err_out != nullptr) err_out[2 * (size_t) i] = err_p + poison, err_out[2 * (size_t) i + 1] = err_w + poison;
         status_out[i] = (converged ? 0x80000000u : 0u) | (finite ? 0u : 0x40000000u) | evals;
     }
 
     // vmv_cartesian_multi's tracking (include/vamp_mvt_amd.h, DESIGN.md 5m): one lane walks one line.  The outer loop
-    // runs over the poses k = 1 .. m of the lane's line, the inner loop is ik_kernel's iteration from waypoint k - 1
-    // towards pose k - the same evaluation, selects, damping schedule, bound-hold rule, step cap and clip.  Both loops
+    // runs over the poses k = 1 .. m of the lane's line, the inner loop is ik_kernel's from waypoint k - 1 towards pose
+    // k: the same evaluation and the same lm_start, lm_accept and lm_step, so a waypoint is ik_kernel's answer.  Both loops
     // have bounds of their own (P.max_k <= 1,023 poses, P.max_iterations evaluations after the first) and both end on a
     // wave-uniform test; a lane whose line is shorter, has stopped or has converged rides along through selects, so a
     // lane's result depends on its own record, start and settings alone.  The host hands only finite records and starts
@@ -1586,97 +1635,33 @@ namespace VMV_ROBOT_NS
                     T[3 + 3 * c + a] = dot3(L.R0[3 * a], L.R0[3 * a + 1], L.R0[3 * a + 2], Q[0][c], Q[1][c], Q[2][c]);
             }
 
-            // ---- ik_kernel's iteration from waypoint k - 1 (clipped to the bounds, as ik_kernel clips a seed)
-            float cand[R::kDim], q[R::kDim], Jw[6][R::kDim], e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            float E = __builtin_inff(), lam = P.damping;
+            // ---- ik_kernel's loop from waypoint k - 1 (clipped to the bounds, as a seed is)
+            float cand[R::kDim];
+            LmState W;
             bool done = !active, converged = false;
 #pragma unroll
-            for (int j = 0; j < R::kDim; ++j)
-            {
-                cand[j] = fminf(fmaxf(prev[j], P.lower[j]), P.upper[j]);
-                q[j] = cand[j];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) Jw[r][j] = 0.0f;
-            }
+            for (int j = 0; j < R::kDim; ++j) cand[j] = prev[j];
+            lm_start(P, cand, W);
             for (uint32_t it = 0;; ++it)
             {
                 float f[12], df[12][R::kDim], Jc[6][R::kDim], ec[6], n_p, n_w, tr;
                 R::ee_frame_jac(cand, f, df);
                 ee_jacobian(f, df, Jc);
                 ik_error(f, T, P.rot_weight, ec, n_p, n_w, tr);
+                ik_weigh(P.rot_weight, Jc);
                 const float Ec = 0.5f * (dot3(ec[0], ec[1], ec[2], ec[0], ec[1], ec[2]) + dot3(ec[3], ec[4], ec[5], ec[3], ec[4], ec[5]));
-                const bool first = it == 0u;
-                const bool take = !done && (first || Ec < E);
+                const bool take = lm_accept(it == 0u, done, cand, Jc, ec, Ec, W, evals);
                 const bool ok = n_p <= P.pos_tol && (P.position_only != 0u || (tr > 1.0f && n_w <= P.rot_tol));
-                const float lam_next = take ? fmaxf(lam * (1.0f / kIkLambdaFactor), kIkLambdaFloor) : fminf(lam * kIkLambdaFactor, kIkLambdaCeil);
-                lam = (done || first) ? lam : lam_next;
-                evals += (done || first) ? 0u : 1u;
-#pragma unroll
-                for (int j = 0; j < R::kDim; ++j)
-                {
-                    q[j] = take ? cand[j] : q[j];
-                    if (ee_joint(j))
-                    {
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) Jw[r][j] = take ? Jc[r][j] : Jw[r][j];
-#pragma unroll
-                        for (int r = 3; r < 6; ++r) Jw[r][j] = take ? P.rot_weight * Jc[r][j] : Jw[r][j];
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) e[r] = take ? ec[r] : e[r];
-                E = take ? Ec : E;
                 converged = converged || (take && ok);
                 done = done || (take && ok);
                 if (it == P.max_iterations || !wave_any(!done)) break;
-
-                float Jm[6][R::kDim], A[6][6], y[6], delta[R::kDim], big = 0.0f;
-#pragma unroll
-                for (int j = 0; j < R::kDim; ++j)
-                    if (ee_joint(j))
-                    {
-                        float g = Jw[0][j] * e[0];
-#pragma unroll
-                        for (int r = 1; r < 6; ++r) g += Jw[r][j] * e[r];
-                        const bool hold = (q[j] <= P.lower[j] && g < 0.0f) || (q[j] >= P.upper[j] && g > 0.0f);
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) Jm[r][j] = hold ? 0.0f : Jw[r][j];
-                    }
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int b = 0; b <= a; ++b)
-                    {
-                        float sum = a == b ? lam : 0.0f;
-#pragma unroll
-                        for (int j = 0; j < R::kDim; ++j)
-                            if (ee_joint(j)) sum += Jm[a][j] * Jm[b][j];
-                        A[a][b] = sum;
-                    }
-                chol6_solve(A, e, y);
-#pragma unroll
-                for (int j = 0; j < R::kDim; ++j)
-                {
-                    delta[j] = 0.0f;
-                    if (ee_joint(j))
-                    {
-                        float sum = Jm[0][j] * y[0];
-#pragma unroll
-                        for (int r = 1; r < 6; ++r) sum += Jm[r][j] * y[r];
-                        delta[j] = sum;
-                        big = fmaxf(big, fabsf(sum));
-                    }
-                }
-                const float scale = P.max_step / fmaxf(big, P.max_step);
-#pragma unroll
-                for (int j = 0; j < R::kDim; ++j)
-                    cand[j] = ee_joint(j) ? fminf(fmaxf(q[j] + delta[j] * scale, P.lower[j]), P.upper[j]) : q[j];
+                lm_step(P, W, cand);
             }
 
             // ---- the waypoint is accepted if it converged within max_joint_step of waypoint k - 1
             float jump = 0.0f;
 #pragma unroll
-            for (int j = 0; j < R::kDim; ++j) jump = fmaxf(jump, fabsf(q[j] - prev[j]));
+            for (int j = 0; j < R::kDim; ++j) jump = fmaxf(jump, fabsf(W.q[j] - prev[j]));
             const bool good = converged && jump <= P.max_joint_step;
             const bool keep = active && good;
             status = (active && !good) ? (uint32_t) (converged ? VMV_CART_JOINT_JUMP : VMV_CART_IK_FAILED) : status;
@@ -1685,10 +1670,10 @@ namespace VMV_ROBOT_NS
             if (keep)  // k <= m: inside the problem's m + 1 rows
             {
 #pragma unroll
-                for (int j = 0; j < R::kDim; ++j) out[(size_t) k * R::kDim + j] = q[j];
+                for (int j = 0; j < R::kDim; ++j) out[(size_t) k * R::kDim + j] = W.q[j];
             }
 #pragma unroll
-            for (int j = 0; j < R::kDim; ++j) prev[j] = keep ? q[j] : prev[j];
+            for (int j = 0; j < R::kDim; ++j) prev[j] = keep ? W.q[j] : prev[j];
         }
         if (in_range) results[i] = CartResult{tracked, status, evals, 0u};
     }
@@ -1745,7 +1730,11 @@ namespace VMV_ROBOT_NS
     }
 
     // The projection of one lane's configuration `in` (vmv_constraint.h): ik_kernel's loop - one evaluation per pass,
-    // selects into the accepted state, no branch but the wave-uniform exit - with the constraint's rows.  Every lane of
+    // selects into the accepted state, no branch but the wave-uniform exit - with the constraint's rows.  The loop is
+    // written out here, statement for statement what lm_start, lm_accept and lm_step state.  Calling all three from this
+    // lane made project_batch 1 - 3 % and the constrained planner 2 - 6 % slower on the MI355X, calling the schedule and
+    // lm_step alone about 1 % (registers as now; DESIGN.md 5o has both measurements), each outside the parent's spread.
+    // tests/test_lm_pins_gpu.py holds this copy and the shared statement to the same recorded outputs.  Every lane of
     // the wave calls it; a lane with `live` false rides along and its outputs mean nothing.  q: the result (`in` itself
     // for a non-finite or antiparallel input); status as the kernel writes it.
     __device__ __forceinline__ void constraint_project_lane(const ConstraintParams &P, const ConstraintDev &C, const float (&in)[R::kDim],
