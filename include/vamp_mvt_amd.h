@@ -777,6 +777,51 @@ int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterati
 int vmv_paths_points(const vmv_paths *paths, float *out, size_t capacity_floats);
 int vmv_paths_destroy(vmv_paths *paths);
 
+/* ---- lockstep simplifier under end-effector constraints ------------------------------------- */
+/* vmv_simplify_multi inside the band of an end-effector constraint: the arguments are vmv_simplify_multi's, then one
+ * constraint for every path or one per path (n_constraints = 1 or n_paths) and the vmv_constraint_settings of the
+ * vmv_constraint_*_batch calls.  The contract per path is vmv_simplify_multi's (simplify.hh's control flow, fp32, one
+ * rounding per operation) with three changes:
+ *  1. Every question (a, b) is validate_motion(a, b) AND band_edge(a, b).  band_edge is vmv_constraint_check_motion_batch's
+ *     answer for that edge under the path's constraint and constraint_settings: the same samples, the same check_step,
+ *     the same 1,024-sample cap.
+ *  2. A B-spline candidate is projected before it is asked.  mid is computed as in vmv_simplify_multi, the min_change test
+ *     on the unprojected mid included; then mid is replaced by mid_p, vmv_constraint_project_batch's result for it bit for
+ *     bit (a mid already in the band and inside the joint bounds comes back unchanged with 0 evaluations).  Where the
+ *     projection does not converge both motions of the candidate are answered 0 and the waypoint stays.  Where it does,
+ *     the motions asked are (path[index - 1], mid_p) and (mid_p, path[index + 1]), and the waypoint is replaced by mid_p
+ *     iff both answers are 1 AND distance(path[index], mid_p) > bspline_min_change, distance being the fp32 function of
+ *     the first test.  There is no bound on how far the projection moves mid: the two motions asked bound the move.
+ *  3. The input is looked at before the rounds: one band test over the first waypoint of every path and one edge band
+ *     test over every input edge.  A path of 3 waypoints or more that fails either ends VMV_SIMPLIFY_OUT_OF_BAND: it comes
+ *     back with its input bytes, 0 iterations and 0 questions and does not disturb the other paths.  (A non-finite
+ *     waypoint is out of band.)  Paths of fewer than 3 waypoints come back as they are without any test.
+ * As in vmv_simplify_multi a subdivision does not ask the halves of an edge.  So every point of a returned OK or
+ * CAPACITY path lies on an asked in-band edge or on a half of one: within check_step / 2 of joint-space length of a
+ * passing sample, not necessarily on one.
+ * vmv_paths_band_refused: per path, of the questions the SERIAL loop asks - the shortcut candidates of a waypoint from
+ * the far end down to and including the first accepted one, the first motion of every B-spline candidate and the second
+ * only where the first was answered 1, the direct question - those the constraint answered 0 (a failed projection, an
+ * out-of-band edge), whatever validity said.  It does not depend on questions_per_round; `questions` in
+ * vmv_paths_summary keeps its windowed meaning.
+ * A path's waypoints, status, iterations and band_refused depend on its own input, environment, constraint and the
+ * settings other than questions_per_round and check_every alone, bit for bit.  With a constraint that restricts nothing
+ * (all bounds infinite, max_angle 0) and finite input the result is vmv_simplify_multi's byte for byte, rounds and
+ * questions included.
+ * Checks: vmv_simplify_multi's in its order, then NULL constraints / constraint_settings, n_constraints other than 1 or
+ * n_paths, the settings' and the constraints' own checks in vmv_constraint_project_batch's order
+ * (VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the field); then the environments' checks.  A call that fails
+ * leaves *out untouched.  Per round one more launch than vmv_simplify_multi: one wave per question slot. */
+enum
+{
+    VMV_SIMPLIFY_OUT_OF_BAND = 2 /* vmv_simplify_multi_constrained: the input's first waypoint or an input edge is out of band */
+};
+int vmv_simplify_multi_constrained(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                                   const vmv_simplify_settings *settings, const vmv_ee_constraint *constraints,
+                                   size_t n_constraints, const vmv_constraint_settings *constraint_settings, vmv_paths **out);
+/* refused [n_paths] (may be NULL); VMV_ERR_INVALID_ARGUMENT for paths not made by vmv_simplify_multi_constrained */
+int vmv_paths_band_refused(const vmv_paths *paths, uint32_t *refused);
+
 /* ---- clearance-aware path optimisation: many independent paths in one call ------------------ */
 /* A covariant gradient iteration (CHOMP's update; its velocity-projection / curvature terms are LEFT OUT) on the
  * waypoints of n_paths paths at once, the arguments those of vmv_simplify_multi: path p is points[offsets[p] ..

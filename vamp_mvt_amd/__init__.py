@@ -1529,7 +1529,14 @@ class _Robot(types.ModuleType):
 
         return _read_plans(plans, n, self._dim, searches)
 
-    def simplify_multi_raw(self, paths, environments, settings):
+    def simplify_multi_constrained_raw(self, paths, environments, constraints, settings, constraint_settings=None):
+        """vmv_simplify_multi_constrained: simplify_multi_raw inside the band of end-effector constraints - one
+        EEConstraint for all paths or one per path; constraint_settings: a ConstraintSettings (None = defaults).
+        -> simplify_multi_raw's dict plus band_refused per path (the questions of the serial loop the constraint answered
+        0); status 2 (out_of_band) where the input's first waypoint or one of its edges is out of band."""
+        return self.simplify_multi_raw(paths, environments, settings, constrained=(constraints, constraint_settings))
+
+    def simplify_multi_raw(self, paths, environments, settings, constrained=None):
         """vmv_simplify_multi: the reference's simplify() with the SHORTCUT and BSPLINE routines for many paths in
         lockstep, path p ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).
         settings: max_iterations, operations (a list of "SHORTCUT" / "BSPLINE"), max_steps, min_change,
@@ -1543,13 +1550,23 @@ class _Robot(types.ModuleType):
         n = len(pts)
         _one_per(environments, n, "path")
         cs = _simplify_settings_struct(settings, max((len(a) for a in pts), default=0))
+        extra = {}
+        if constrained is not None:  # (every Python-side check before any library call)
+            records, count = _constraint_records(constrained[0], n)
+            ps = (constrained[1] or ConstraintSettings()).struct()
+            extra["band_refused"] = np.zeros(n, np.uint32)
         if n == 0:
             return dict(status=np.zeros(0, np.uint8), iterations=np.zeros(0, np.uint32), lengths=np.zeros(0, np.uint32),
-                        questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0)
+                        questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0, **extra)
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         out = ctypes.c_void_p()
-        check(lib.vmv_simplify_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                     ctypes.byref(cs), ctypes.byref(out)), "vmv_simplify_multi")
+        if constrained is not None:
+            check(lib.vmv_simplify_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                                     ctypes.byref(cs), records, count, ctypes.byref(ps), ctypes.byref(out)),
+                  "vmv_simplify_multi_constrained")
+        else:
+            check(lib.vmv_simplify_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                         ctypes.byref(cs), ctypes.byref(out)), "vmv_simplify_multi")
         try:
             status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
             lengths, questions = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
@@ -1559,10 +1576,12 @@ class _Robot(types.ModuleType):
                                         ctypes.byref(rounds), ctypes.byref(total)), "vmv_paths_summary")
             points = np.zeros((int(lengths.sum()), self._dim), np.float32)
             check(lib.vmv_paths_points(out, _fp(points), points.size), "vmv_paths_points")
+            if constrained is not None:
+                check(lib.vmv_paths_band_refused(out, extra["band_refused"].ctypes.data_as(_lib.c_u32_p)), "vmv_paths_band_refused")
         finally:
             lib.vmv_paths_destroy(out)
         return dict(status=status, iterations=iterations, lengths=lengths, questions=questions, points=points,
-                    rounds=int(rounds.value), total_questions=int(total.value))
+                    rounds=int(rounds.value), total_questions=int(total.value), **extra)
 
     def optimize_multi_raw(self, paths, environments, settings):
         """vmv_optimize_multi: the clearance-aware covariant gradient iteration for many paths in lockstep, path p

@@ -271,6 +271,10 @@ def _load():
         "vmv_phs_samples": (I, [I, c_float_p, c_float_p, F, ctypes.c_uint32, ctypes.c_uint32, S, c_float_p, c_u8_p, c_u32_p]),
         "vmv_simplify_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
                                    ctypes.POINTER(V)]),
+        "vmv_simplify_multi_constrained": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(SimplifySettings),
+                                               ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings),
+                                               ctypes.POINTER(V)]),
+        "vmv_paths_band_refused": (I, [V, c_u32_p]),
         "vmv_paths_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_paths_points": (I, [V, c_float_p, S]),
         "vmv_paths_destroy": (I, [V]),

@@ -514,6 +514,11 @@ def install(robot):
             out.append(res)
         return out
 
+    def simplify_multi_constrained(paths, environments, constraints, settings=None, constraint_settings=None):
+        """planning.simplify_multi_constrained with this robot: `simplify_multi` inside the band of end-effector
+        constraints -> list[planning.PlanningResult] (each with `status`, `cost` and `band_refused`)."""
+        return planning.simplify_multi_constrained(robot, paths, environments, constraints, settings, constraint_settings)
+
     def optimize_multi(paths, environments, settings=None, resolution=None):
         """planning.optimize_multi with this robot: the clearance-aware covariant gradient iteration for many paths in
         lockstep on the device -> list[planning.OptimizedPath].  The clearances are those of the waypoints, validity is
@@ -537,6 +542,7 @@ def install(robot):
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals
     robot.rrtc_multi_constrained = rrtc_multi_constrained
+    robot.simplify_multi_constrained = simplify_multi_constrained
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
     robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]

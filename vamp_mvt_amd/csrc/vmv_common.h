@@ -158,6 +158,14 @@ namespace vmv
         int (*constraint_round)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_active, const float *d_q_start,
                                 float *d_q_goal, const uint64_t *d_pending, float *d_pool, float stretch, uint8_t *d_c_ok,
                                 uint32_t *d_refused /* [n_problems], += 1 per question answered 0 */, uint32_t na, hipStream_t);
+        // vmv_simplify_multi_constrained's part of a round, after the step kernel on the same stream: one wave per slot
+        // a * w + s of the na active paths.  d_pending[slot]: 0 null (answered 1), 1 band-check the edge, 2 / 3 project the
+        // B-spline midpoint in d_q_goal / d_q_start[slot] first, write it back there (2: into d_proj[path][s / 2] too, paths
+        // proj_stride floats apart) and answer 0 where it does not converge; the answers go to d_c_ok[slot].  d_cons one
+        // record (P.shared) or one per PATH (indexed through d_active)
+        int (*simplify_band_round)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_active, float *d_q_start,
+                                   float *d_q_goal, const uint8_t *d_pending, float *d_proj, uint32_t proj_stride, uint8_t *d_c_ok,
+                                   uint32_t na, uint32_t w, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

@@ -2017,6 +2017,64 @@ namespace VMV_ROBOT_NS
         }
     }
 
+    // The constraint's part of a simplifier round (vmv_simplify_multi_constrained, DESIGN.md 5p), one wave per slot of
+    // every active path - slot = a * w + s - after the step kernel on the same stream.  pending[slot] says what the step
+    // kernel wrote there: 0 a null question (answered 1, nothing is read), 1 an edge to band-check as constraint_edge_kernel
+    // does, 2 / 3 the first / second motion of a B-spline candidate, whose midpoint sits in q_goal[slot] / q_start[slot].
+    // That midpoint is projected - every lane of the wave runs the same projection, so the result is the lane's of
+    // constraint_project_kernel bit for bit, and the two slots of a candidate compute the same bits independently - and,
+    // converged, replaces the midpoint in the slot's own question array (code 2 also stores it in proj[path][s / 2], which
+    // the next step kernel reads); then the edge is band-checked.  Not converged: nothing is stored, the answer is 0.
+    // The branches are taken by the whole wave (the code is the workgroup's).  Plain stores by lane 0; path = active[a]
+    // picks the record.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void simplify_band_round_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                           const uint32_t *__restrict__ active, float *q_start, float *q_goal,
+                                                                           const uint8_t *__restrict__ pending, float *proj,
+                                                                           const uint32_t proj_stride, const uint32_t w,
+                                                                           uint8_t *__restrict__ c_ok)
+    {
+        const uint32_t slot = blockIdx.x;  // the grid has one workgroup per slot
+        const uint32_t code = pending[slot];
+        if (code == 0u)
+        {
+            if (threadIdx.x == 0u) c_ok[slot] = 1u;
+            return;
+        }
+        const uint32_t a = slot / w, s = slot - a * w, path = active[a];
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : path];
+        float qs[R::kDim], qg[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) qs[j] = q_start[(size_t) slot * R::kDim + j], qg[j] = q_goal[(size_t) slot * R::kDim + j];
+        bool live = true;
+        if (code >= 2u)
+        {
+            const bool goal = code == 2u;
+            float mid[R::kDim], q[R::kDim], res_p, res_w;
+            uint32_t status;
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) mid[j] = goal ? qg[j] : qs[j];
+            constraint_project_lane(P, C, mid, true, q, res_p, res_w, status);
+            live = (status >> 31) != 0u;
+            if (live && threadIdx.x == 0u)
+            {
+                float *own = (goal ? q_goal : q_start) + (size_t) slot * R::kDim;
+#pragma unroll
+                for (int j = 0; j < R::kDim; ++j) own[j] = q[j];
+                if (goal)
+                {
+                    float *keep = proj + (size_t) path * proj_stride + (size_t) (s >> 1) * R::kDim;
+#pragma unroll
+                    for (int j = 0; j < R::kDim; ++j) keep[j] = q[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) qs[j] = goal ? qs[j] : q[j], qg[j] = goal ? q[j] : qg[j];
+        }
+        const bool edge = constraint_band_edge(P, C, qs, qg, live);
+        if (threadIdx.x == 0u) c_ok[slot] = edge ? 1u : 0u;
+    }
+
     // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------
@@ -2803,6 +2861,16 @@ namespace VMV_ROBOT_NS
             VMV_HIP_TU(hipGetLastError());
             return VMV_OK;
         }
+        // the constraint's part of a simplifier round: na active paths of w slots each (vmv_simplify_multi_constrained)
+        int launch_simplify_band_round(const ConstraintParams &P, const ConstraintDev *d_cons, const uint32_t *d_active, float *d_q_start,
+                                       float *d_q_goal, const uint8_t *d_pending, float *d_proj, uint32_t proj_stride, uint8_t *d_c_ok,
+                                       uint32_t na, uint32_t w, hipStream_t stream)
+        {
+            hipLaunchKernelGGL(simplify_band_round_kernel<>, dim3(na * w), dim3(kIkBlock), 0, stream, P, d_cons, d_active, d_q_start,
+                               d_q_goal, d_pending, d_proj, proj_stride, w, d_c_ok);
+            VMV_HIP_TU(hipGetLastError());
+            return VMV_OK;
+        }
     }  // namespace
 
 }  // namespace VMV_ROBOT_NS
@@ -2823,6 +2891,7 @@ namespace VMV_ROBOT_NS
                                                     VMV_ROBOT_NS::launch_constraint_project,
                                                     VMV_ROBOT_NS::launch_constraint_check,
                                                     VMV_ROBOT_NS::launch_constraint_edges,
-                                                    VMV_ROBOT_NS::launch_constraint_round};
+                                                    VMV_ROBOT_NS::launch_constraint_round,
+                                                    VMV_ROBOT_NS::launch_simplify_band_round};
 #endif
 }  // namespace vmv

@@ -16,6 +16,13 @@
 // A path owns two buffers of max_waypoints waypoints: an erase moves the tail down in place (read, barrier, write, chunk
 // by chunk), a subdivision writes into the other buffer.  Every store is a plain vector store by the owning wave; no
 // atomics.
+//
+// vmv_simplify_multi_constrained (include/vamp_mvt_amd.h states the contract in full) runs the same state
+// machine inside the band of an end-effector constraint: simplify_step_kernel<true> ANDs the answers of the band round
+// (simplify_band_round_kernel of the robot's translation unit, launched right behind it) into the validity bits, names per
+// slot what that round is to do (nothing, band-check the edge, project the B-spline midpoint first), takes the projected
+// midpoints from a per-path buffer and counts the serial loop's refused questions from the consumed window.
+// simplify_step_kernel<false> is the kernel vmv_simplify_multi always ran.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
@@ -31,6 +38,8 @@ struct vmv_paths
     std::vector<uint32_t> iterations, lengths, questions;
     std::vector<float> points;  // packed in path order
     uint64_t rounds = 0, total_questions = 0;
+    bool constrained = false;            // made by vmv_simplify_multi_constrained
+    std::vector<uint32_t> band_refused;  // [n] then
 };
 
 namespace vmv
@@ -72,7 +81,8 @@ namespace vmv
             uint32_t step;    // B-spline step
             uint32_t pos;     // B-spline: next index to look at; 0 = the step has not begun (no subdivision yet)
             uint32_t questions;
-            uint32_t pad0, pad1;
+            uint32_t refused;  // vmv_simplify_multi_constrained: questions of the serial loop the constraint answered 0
+            uint32_t pad1;
         };
         static_assert(sizeof(SimplifyState) == 64, "one cache line half per path");
 
@@ -97,6 +107,21 @@ namespace vmv
             uint8_t *done;            // [n_paths]
         };
 
+        // vmv_simplify_multi_constrained only (every pointer NULL otherwise; the unconstrained kernels never read them)
+        enum : uint8_t
+        {
+            kBandNull = 0,      // a null slot: answered 1 without a test
+            kBandEdge = 1,      // the edge's band test alone
+            kBandProjGoal = 2,  // even B-spline slot: q_goal (the midpoint) is projected first
+            kBandProjStart = 3  // odd B-spline slot: q_start (the midpoint) is projected first
+        };
+        struct SimplifyBand
+        {
+            uint8_t *pending;            // [n_active][w] what the band round is to do with each slot
+            const uint8_t *c_ok;         // [n_active][w] its answers, ANDed into the validity bits
+            const float *proj;           // [n_paths][kSimpMaxCandidates][dim] the projected midpoints of the window in flight
+        };
+
         __device__ __forceinline__ float interpolate(float a, float b, float t) { return a + (b - a) * t; }
 
         // joint d of smooth_bspline's midpoint for waypoint idx (simplify.hh:33-35)
@@ -108,7 +133,8 @@ namespace vmv
             return interpolate(t1, t2, 0.5f);
         }
 
-        __global__ __launch_bounds__(kSimpBlock) void simplify_init_kernel(const SimplifyParams P, const SimplifyArrays D)
+        __global__ __launch_bounds__(kSimpBlock) void simplify_init_kernel(const SimplifyParams P, const SimplifyArrays D,
+                                                                           const uint8_t *__restrict__ out_of_band)
         {
             const uint32_t p = blockIdx.x, lane = threadIdx.x;
             const uint64_t lo = D.offsets[p];
@@ -119,16 +145,23 @@ namespace vmv
             if (lane == 0)
             {
                 SimplifyState st{};
-                st.phase = len > 2 ? kPhaseInit : kPhaseDone;  // below 3 waypoints: returned as it is, without a question
-                st.status = VMV_SIMPLIFY_OK, st.size = len;
+                const bool out = out_of_band != nullptr && out_of_band[p] != 0;  // (never set below 3 waypoints)
+                const bool runs = len > 2 && !out;  // below 3 waypoints: returned as it is, without a question
+                st.phase = runs ? kPhaseInit : kPhaseDone;
+                st.status = out ? VMV_SIMPLIFY_OUT_OF_BAND : VMV_SIMPLIFY_OK, st.size = len;
                 D.state[p] = st;
-                D.done[p] = len > 2 ? 0 : 1;
+                D.done[p] = runs ? 0 : 1;
             }
         }
 
         // One wave per active path; every branch below is taken by the whole wave (its conditions are values every lane
-        // holds alike), so the barriers and the ballot are safe.
-        __global__ __launch_bounds__(kSimpBlock) void simplify_step_kernel(const SimplifyParams P, const SimplifyArrays D)
+        // holds alike), so the barriers and the ballot are safe.  Constrained (vmv_simplify_multi_constrained, the contract
+        // at that entry point): the band round's answers are ANDed into the validity bits, the serial loop's refused
+        // questions are counted from the consumed window, a B-spline replacement takes the projected midpoint and passes
+        // the second min_change test, and every slot written carries its code for the band round.
+        template <bool Constrained>
+        __global__ __launch_bounds__(kSimpBlock) void simplify_step_kernel(const SimplifyParams P, const SimplifyArrays D,
+                                                                           const SimplifyBand X)
         {
             __shared__ uint32_t s_cand[kSimpMaxCandidates];
             const uint32_t a = blockIdx.x, p = D.active[a], lane = threadIdx.x, dim = P.dim, M = P.max_waypoints, W = P.w;
@@ -148,9 +181,16 @@ namespace vmv
             else if (!was_done)
             {
                 const uint32_t s0 = st.slot * W;  // W divides 64: the path's answers sit in one word
-                const uint64_t ans = D.bits[s0 >> 6] >> (s0 & 63u);
+                uint64_t ans = D.bits[s0 >> 6] >> (s0 & 63u);
+                uint64_t band = ~0ull;  // bit s: the band round answered slot s with 1
+                if constexpr (Constrained)
+                {
+                    band = __ballot(lane < W && X.c_ok[(size_t) s0 + lane] != 0);
+                    ans &= band;
+                }
                 if (st.phase == kPhaseDirect)
                 {
+                    if constexpr (Constrained) st.refused += (band & 1ull) ? 0u : 1u;
                     if (ans & 1ull)  // the straight line is valid: (front, back)
                     {
                         float v = 0.f;
@@ -167,6 +207,11 @@ namespace vmv
                 else if (st.phase == kPhaseShortcut)
                 {
                     const uint64_t m = st.cnt >= 64u ? ans : ans & ((1ull << st.cnt) - 1ull);
+                    if constexpr (Constrained)  // the serial scan asks the slots below the found one (all of them if none)
+                    {
+                        const uint64_t asked = m ? (m & (0ull - m)) - 1ull : (st.cnt >= 64u ? ~0ull : (1ull << st.cnt) - 1ull);
+                        st.refused += (uint32_t) __popcll(~band & asked);
+                    }
                     if (m)  // the lowest set bit is the largest valid j: erase (i, j) exclusive
                     {
                         const uint32_t j = st.jtop - (uint32_t) __builtin_ctzll(m);
@@ -189,15 +234,43 @@ namespace vmv
                 }
                 else  // kPhaseBspline: a candidate is replaced iff both its motions are valid
                 {
-                    const uint64_t both = ans & (ans >> 1) & 0x5555555555555555ull &
-                                          (st.cnt >= 32u ? ~0ull : ((1ull << (2u * st.cnt)) - 1ull));
+                    uint64_t both = ans & (ans >> 1) & 0x5555555555555555ull &
+                                    (st.cnt >= 32u ? ~0ull : ((1ull << (2u * st.cnt)) - 1ull));
+                    if constexpr (Constrained)
+                    {
+                        const uint64_t real = st.cnt >= 32u ? ~0ull : ((1ull << (2u * st.cnt)) - 1ull);
+                        // the serial loop asks the first motion of every candidate, the second where the first was answered 1
+                        const uint64_t asked = (0x5555555555555555ull | ((ans & 0x5555555555555555ull) << 1)) & real;
+                        st.refused += (uint32_t) __popcll(~band & asked);
+                        // the second min_change test, candidate `lane`: distance(path[index], mid_p) > min_change
+                        bool moves = false;
+                        if (lane < st.cnt && ((both >> (2u * lane)) & 1ull))
+                        {
+                            const float *mp = X.proj + ((size_t) p * kSimpMaxCandidates + lane) * dim;
+                            const float *own = path + (size_t) cand[lane] * dim;
+                            float sum = 0.f;
+                            for (uint32_t d = 0; d < dim; ++d)
+                            {
+                                const float df = mp[d] - own[d];
+                                sum = sum + df * df;
+                            }
+                            moves = sqrtf(sum) > P.min_change;  // false for NaN
+                        }
+                        const uint64_t keep = __ballot(moves);  // bit c: candidate c
+                        uint64_t spread = 0;
+                        for (uint64_t rest = keep; rest; rest &= rest - 1ull) spread |= 1ull << (2u * (uint32_t) __builtin_ctzll(rest));
+                        both = spread;
+                    }
                     for (uint32_t e = lane; e < st.cnt * dim; e += kSimpBlock)  // (element e is read and written by this lane alone)
                     {
                         const uint32_t c = e / dim, d = e - c * dim;
                         if ((both >> (2u * c)) & 1ull)
                         {
                             const uint32_t idx = cand[c];
-                            path[(size_t) idx * dim + d] = bspline_midpoint(path, idx, d, dim, P.midpoint);
+                            if constexpr (Constrained)
+                                path[(size_t) idx * dim + d] = X.proj[((size_t) p * kSimpMaxCandidates + c) * dim + d];
+                            else
+                                path[(size_t) idx * dim + d] = bspline_midpoint(path, idx, d, dim, P.midpoint);
                         }
                     }
                     if (both) st.flags |= kFlagUpdated | kFlagResult;
@@ -361,6 +434,20 @@ namespace vmv
                 }
                 qs[e] = vs, qg[e] = vg;
             }
+            if constexpr (Constrained)
+            {
+                if (lane < W)
+                {
+                    uint8_t code = kBandNull;
+                    if (emit == kEmitDirect)
+                        code = lane == 0 ? kBandEdge : kBandNull;
+                    else if (emit == kEmitShortcut)
+                        code = lane < st.cnt ? kBandEdge : kBandNull;
+                    else if (emit == kEmitBspline)
+                        code = (lane >> 1) < st.cnt ? ((lane & 1u) ? kBandProjStart : kBandProjGoal) : kBandNull;
+                    X.pending[(size_t) a * W + lane] = code;
+                }
+            }
             if (!was_done && lane == 0)
             {
                 st.slot = a;
@@ -401,13 +488,96 @@ namespace vmv
             return sat_add(sat_mul(P.max_iterations, per_iteration), 2ull + check_every);
         }
 
+        const RobotLaunchers *const kSimpLaunchers[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
+
+        struct SimplifyConstraints  // vmv_simplify_multi_constrained: the caller's constraints (1 or n_paths), the resolved settings
+        {
+            ConstraintParams P;
+            const vmv_ee_constraint *constraints;
+            size_t count;
+        };
+
+        // The constrained call's look at its input, before the rounds: ONE band test over the first waypoint of every path
+        // and ONE edge band test over every consecutive pair of the packed input (the pairs that straddle two paths are
+        // asked too and not looked at), each with its path's record.  out_of_band[p] = 1: a path of 3 waypoints or more
+        // with its first waypoint or an edge out of band.  d_recs: one record (shared) or one per path, for the rounds.
+        int simplify_band_input(int robot, const SimplifyConstraints &cb, DeviceBuffers &mem, size_t n, const float *points,
+                                const float *d_points, const size_t *offsets, size_t dim, hipStream_t stream, ConstraintDev **d_recs,
+                                std::vector<uint8_t> &out_of_band)
+        {
+            const RobotLaunchers &L = *kSimpLaunchers[robot];
+            const size_t total = offsets[n], n_edges = total > 0 ? total - 1 : 0;
+            std::vector<ConstraintDev> recs(cb.count);
+            for (size_t k = 0; k < cb.count; ++k) constraint_record(cb.constraints[k], (double) cb.P.pos_tol, (double) cb.P.rot_tol, recs[k]);
+            VMV_LOCKSTEP_HIP(mem.alloc(d_recs, cb.count));
+            VMV_LOCKSTEP_HIP(hipMemcpy(*d_recs, recs.data(), cb.count * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+            out_of_band.assign(n, 0);
+
+            std::vector<float> firsts(n * dim, 0.0f);
+            for (size_t p = 0; p < n; ++p)
+                if (offsets[p + 1] > offsets[p]) std::memcpy(&firsts[p * dim], points + offsets[p] * dim, dim * 4);
+            DeviceBuffers tmp;  // what only this look needs
+            float *d_firsts = nullptr;
+            uint64_t *d_bits = nullptr;
+            uint8_t *d_ok = nullptr;
+            const ConstraintDev *d_edge_recs = *d_recs;
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_firsts, n * dim));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_bits, (n + 63) / 64));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_ok, n_edges));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_firsts, firsts.data(), n * dim * 4, hipMemcpyHostToDevice, stream));
+            if (!cb.P.shared && n_edges)  // edge e begins at packed waypoint e: its path's record
+            {
+                std::vector<ConstraintDev> per_edge(n_edges);
+                for (size_t p = 0; p < n; ++p)
+                    for (size_t e = offsets[p]; e < offsets[p + 1] && e < n_edges; ++e) per_edge[e] = recs[p];
+                ConstraintDev *d = nullptr;
+                VMV_LOCKSTEP_HIP(tmp.alloc(&d, n_edges));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d, per_edge.data(), n_edges * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                d_edge_recs = d;
+            }
+            if (int rc = L.constraint_check(cb.P, *d_recs, d_firsts, n, d_bits, nullptr, stream); rc != VMV_OK) return rc;
+            if (n_edges)
+                if (int rc = L.constraint_edges(cb.P, d_edge_recs, d_points, d_points + dim, n_edges, d_ok, stream); rc != VMV_OK) return rc;
+            std::vector<uint64_t> bits((n + 63) / 64);
+            std::vector<uint8_t> ok(n_edges);
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(bits.data(), d_bits, bits.size() * 8, hipMemcpyDeviceToHost, stream));
+            if (n_edges) VMV_LOCKSTEP_HIP(hipMemcpyAsync(ok.data(), d_ok, n_edges, hipMemcpyDeviceToHost, stream));
+            VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+            for (size_t p = 0; p < n; ++p)
+            {
+                if (offsets[p + 1] - offsets[p] < 3) continue;  // returned as it is, whatever the tests said
+                bool in = ((bits[p >> 6] >> (p & 63u)) & 1ull) != 0;
+                for (size_t e = offsets[p]; in && e + 1 < offsets[p + 1]; ++e) in = ok[e] != 0;
+                out_of_band[p] = in ? 0 : 1;
+            }
+            return VMV_OK;
+        }
+
         // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
         // robot's part built.
+        // cb: vmv_simplify_multi_constrained's constraints and resolved settings (NULL: vmv_simplify_multi).
         int simplify_multi_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
-                               const SimplifyParams &P, uint32_t check_every, vmv_paths *paths)
+                               const SimplifyParams &P, uint32_t check_every, vmv_paths *paths, const SimplifyConstraints *cb = nullptr)
         {
             const size_t dim = P.dim, W = P.w, total_in = offsets[n];
             hipStream_t stream = nullptr;
+
+            DeviceBuffers mem;
+            float *d_points = nullptr;
+            VMV_LOCKSTEP_HIP(mem.alloc(&d_points, total_in * dim));
+            if (total_in) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, total_in * dim * 4, hipMemcpyHostToDevice, stream));
+
+            // the constrained call's look at the input: which paths take part, and the records of all paths on the device
+            std::vector<uint8_t> out_of_band;
+            ConstraintDev *d_recs = nullptr;
+            uint8_t *d_out_of_band = nullptr;
+            if (cb)
+            {
+                if (int rc = simplify_band_input(robot, *cb, mem, n, points, d_points, offsets, dim, stream, &d_recs, out_of_band); rc != VMV_OK)
+                    return rc;
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_out_of_band, n));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_out_of_band, out_of_band.data(), n, hipMemcpyHostToDevice));
+            }
 
             std::vector<uint32_t> active;
             std::vector<const vmv_env *> active_envs;
@@ -418,36 +588,55 @@ namespace vmv
                 const size_t len = offsets[k + 1] - offsets[k];
                 offsets64[k] = offsets[k];
                 longest = std::max(longest, len);
-                if (len > 2) active.push_back((uint32_t) k), active_envs.push_back(envs[k]);  // shorter ones ask nothing
+                if (len > 2 && !(cb && out_of_band[k])) active.push_back((uint32_t) k), active_envs.push_back(envs[k]);  // the others ask nothing
             }
             offsets64[n] = total_in;
             const size_t na0 = active.size();
 
-            DeviceBuffers mem;
             LockstepBuffers B;
             SimplifyArrays D{};
-            float *d_points = nullptr;
+            SimplifyBand X{};
             uint64_t *d_offsets = nullptr;
             VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.buf, n * 2u * (size_t) P.max_waypoints * dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.cand, n * kSimpMaxCandidates));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_points, total_in * dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&d_offsets, n + 1));
             if (int rc = B.alloc(mem, n, na0, W, dim, stream); rc != VMV_OK) return rc;
             D.points = d_points, D.offsets = d_offsets, D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits;
             D.done = B.done;
+            uint8_t *d_c_ok = nullptr;
+            float *d_proj = nullptr;
+            if (cb)
+            {
+                const size_t slots = std::max<size_t>(na0, 1) * W;
+                VMV_LOCKSTEP_HIP(mem.alloc(&X.pending, slots));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_c_ok, slots + kSimpBlock));  // (a wave's worth of room behind the last slot)
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_proj, n * kSimpMaxCandidates * dim));
+                VMV_LOCKSTEP_HIP(hipMemsetAsync(d_c_ok, 0, slots + kSimpBlock, stream));
+                X.c_ok = d_c_ok, X.proj = d_proj;
+            }
 
-            if (total_in) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, total_in * dim * 4, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
             const uint32_t n32 = (uint32_t) n;
-            hipLaunchKernelGGL(simplify_init_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D);
+            hipLaunchKernelGGL(simplify_init_kernel, dim3(n32), dim3(kSimpBlock), 0, stream, P, D, (const uint8_t *) d_out_of_band);
             VMV_LOCKSTEP_HIP(hipGetLastError());
             if (na0) VMV_LOCKSTEP_HIP(hipMemcpy(B.active, active.data(), na0 * 4, hipMemcpyHostToDevice));
 
             uint64_t rounds = 0;
-            const auto step = [&](uint32_t na) { hipLaunchKernelGGL(simplify_step_kernel, dim3(na), dim3(kSimpBlock), 0, stream, P, D); };
+            const auto step = [&](uint32_t na) {
+                if (!cb)
+                {
+                    hipLaunchKernelGGL(simplify_step_kernel<false>, dim3(na), dim3(kSimpBlock), 0, stream, P, D, X);
+                    return;
+                }
+                // the step kernel names what each slot needs; the band round projects the B-spline midpoints in place and
+                // answers every slot's band question before the round's validation reads the edges
+                hipLaunchKernelGGL(simplify_step_kernel<true>, dim3(na), dim3(kSimpBlock), 0, stream, P, D, X);
+                (void) kSimpLaunchers[robot]->simplify_band_round(cb->P, d_recs, B.active, B.q_start, B.q_goal, X.pending, d_proj,
+                                                                   (uint32_t) (kSimpMaxCandidates * dim), d_c_ok, na, (uint32_t) W, stream);
+            };
             if (int rc = lockstep_rounds(robot, stream, check_every, round_bound(P, longest, check_every), W, active, active_envs, B.arrays(),
-                                         "vmv_simplify_multi", "simplify_step_kernel", step, rounds);
+                                         cb ? "vmv_simplify_multi_constrained" : "vmv_simplify_multi", "simplify_step_kernel", step, rounds);
                 rc != VMV_OK)
                 return rc;
 
@@ -456,9 +645,11 @@ namespace vmv
             VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(SimplifyState), hipMemcpyDeviceToHost));
             paths->n = n, paths->dim = (int) dim, paths->rounds = rounds, paths->total_questions = 0;
             paths->status.resize(n), paths->iterations.resize(n), paths->lengths.resize(n), paths->questions.resize(n);
+            if (cb) paths->band_refused.resize(n);
             for (size_t k = 0; k < n; ++k)
             {
                 const SimplifyState &st = states[k];
+                if (cb) paths->band_refused[k] = st.refused;
                 paths->status[k] = (uint8_t) st.status;
                 paths->iterations[k] = st.iterations;
                 paths->lengths[k] = st.size;
@@ -472,23 +663,20 @@ namespace vmv
                               paths->points);
         }
     }  // namespace
-}  // namespace vmv
 
-extern "C"
-{
-    int vmv_simplify_multi(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
-                           const vmv_simplify_settings *settings, vmv_paths **out)
+    // vmv_simplify_multi's checks, none of which needs a device, in the header's order -> the resolved settings
+    int simplify_checks(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                        const vmv_simplify_settings *settings, vmv_paths *const *out, SimplifyParams &P, uint32_t &check_every)
     {
         // device-free checks first; the environments' own (NULL handles again, unfinalized, another device) are those of
         // vmv_env_prepare_multi, which then builds the parts not yet built in one batch
         const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
         if (!settings || !out || (n_paths > 0 && (!envs || !offsets))) return VMV_ERR_INVALID_ARGUMENT;
         const vmv_simplify_settings &S = *settings;
-        const uint32_t W = S.questions_per_round ? S.questions_per_round : vmv::kSimpDefaultQuestions;
+        const uint32_t W = S.questions_per_round ? S.questions_per_round : kSimpDefaultQuestions;
         if (W != 2 && W != 4 && W != 8 && W != 16 && W != 32 && W != 64) return VMV_ERR_INVALID_ARGUMENT;
         if (S.interpolate != 0 || S.n_operations > 8) return VMV_ERR_INVALID_ARGUMENT;
-        vmv::SimplifyParams P{};
         for (uint32_t k = 0; k < S.n_operations; ++k)
         {
             if (S.operations[k] == VMV_SIMPLIFY_BSPLINE)
@@ -496,9 +684,9 @@ extern "C"
             else if (S.operations[k] != VMV_SIMPLIFY_SHORTCUT)
                 return VMV_ERR_INVALID_ARGUMENT;
         }
-        if (n_paths >= vmv::kMultiMaxConfigs || n_paths * (size_t) W >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        const uint32_t max_waypoints = S.max_waypoints ? S.max_waypoints : vmv::kSimpDefaultWaypoints;
-        if (max_waypoints > vmv::kSimpMaxWaypoints) return VMV_ERR_INVALID_ARGUMENT;
+        if (n_paths >= kMultiMaxConfigs || n_paths * (size_t) W >= kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+        const uint32_t max_waypoints = S.max_waypoints ? S.max_waypoints : kSimpDefaultWaypoints;
+        if (max_waypoints > kSimpMaxWaypoints) return VMV_ERR_INVALID_ARGUMENT;
         if (n_paths > 0 && offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
         for (size_t k = 0; k < n_paths; ++k)
         {
@@ -511,10 +699,55 @@ extern "C"
         P.dim = (uint32_t) dim, P.max_waypoints = max_waypoints, P.max_iterations = S.max_iterations, P.n_ops = S.n_operations;
         P.max_steps = S.bspline_max_steps, P.w = W;
         P.min_change = S.bspline_min_change, P.midpoint = S.bspline_midpoint_interpolation;
-        const uint32_t check_every = S.check_every ? S.check_every : vmv::kSimpDefaultCheckEvery;
-        return vmv::lockstep_call(robot, envs, n_paths, dim, out, [&](vmv_paths *paths) {
+        check_every = S.check_every ? S.check_every : kSimpDefaultCheckEvery;
+        return VMV_OK;
+    }
+}  // namespace vmv
+
+extern "C"
+{
+    int vmv_simplify_multi(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                           const vmv_simplify_settings *settings, vmv_paths **out)
+    {
+        vmv::SimplifyParams P{};
+        uint32_t check_every = 0;
+        if (int rc = vmv::simplify_checks(robot, envs, n_paths, points, offsets, settings, out, P, check_every); rc != VMV_OK) return rc;
+        return vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_paths *paths) {
             return vmv::simplify_multi_run(robot, envs, n_paths, points, offsets, P, check_every, paths);
         });
+    }
+
+    int vmv_simplify_multi_constrained(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                                       const vmv_simplify_settings *settings, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                       const vmv_constraint_settings *constraint_settings, vmv_paths **out)
+    {
+        // vmv_simplify_multi's checks in its order, then the constraint's own in vmv_constraint_project_batch's; none needs a device
+        vmv::SimplifyParams P{};
+        uint32_t check_every = 0;
+        if (int rc = vmv::simplify_checks(robot, envs, n_paths, points, offsets, settings, out, P, check_every); rc != VMV_OK) return rc;
+        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
+        if (n_constraints != 1 && n_constraints != n_paths) return vmv::refuse_argument("n_constraints must be 1 or n_paths");
+        vmv::SimplifyConstraints cb{};
+        if (const char *err = vmv::constraint_settings(*constraint_settings, cb.P)) return vmv::refuse_argument(err);
+        for (size_t k = 0; k < n_constraints; ++k)
+            if (const char *err = vmv::constraint_refusal(constraints[k]))
+                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
+        cb.constraints = constraints, cb.count = n_constraints, cb.P.shared = n_constraints == 1 ? 1u : 0u;
+        const int rc = vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_paths *paths) {
+            float lower[16], span[16], descale[16];
+            if (int rb = vmv_robot_bounds(robot, lower, span, descale); rb != VMV_OK) return rb;
+            for (uint32_t j = 0; j < 16; ++j) cb.P.lower[j] = j < P.dim ? lower[j] : 0.f, cb.P.upper[j] = j < P.dim ? lower[j] + span[j] : 0.f;
+            return vmv::simplify_multi_run(robot, envs, n_paths, points, offsets, P, check_every, paths, &cb);
+        });
+        if (rc == VMV_OK) (*out)->constrained = true, (*out)->band_refused.resize(n_paths);
+        return rc;
+    }
+
+    int vmv_paths_band_refused(const vmv_paths *paths, uint32_t *refused)
+    {
+        if (!paths || !paths->constrained) return VMV_ERR_INVALID_ARGUMENT;
+        if (refused && paths->n) std::memcpy(refused, paths->band_refused.data(), paths->n * 4);
+        return VMV_OK;
     }
 
     int vmv_paths_summary(const vmv_paths *paths, uint8_t *status, uint32_t *iterations, uint32_t *lengths, uint32_t *questions,

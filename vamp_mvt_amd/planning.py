@@ -172,7 +172,7 @@ class AORRTCMultiSettings:
 
 
 PLAN_STATUS = ("solved", "max_iterations", "max_samples", "no_path", "invalid_endpoint")  # VMV_PLAN_*
-SIMPLIFY_STATUS = ("ok", "capacity")  # VMV_SIMPLIFY_*
+SIMPLIFY_STATUS = ("ok", "capacity", "out_of_band")  # VMV_SIMPLIFY_* (the last: simplify_multi_constrained only)
 
 
 @dataclass
@@ -396,8 +396,9 @@ def rrtc_multi_constrained(robot, starts, goal_sets, environments, constraints, 
     out-of-band goals of a set are never used (goal_index still counts within the caller's set).  constraint_settings: a
     ConstraintSettings (its check_step spaces the band samples of an edge); max_stretch: a projected node farther than
     max_stretch * range from the edge's near end is refused.  -> list[PlanningResult] as `rrtc_multi_goals`'s.  The path's
-    edges pass `constraint_check_motion_batch`; a later shortcut or optimisation does not know the constraint - ask
-    `validate_paths_constrained` of it.  Each result also carries `band_refused`: the questions the constraint answered 0."""
+    edges pass `constraint_check_motion_batch`; `simplify_multi_constrained` simplifies it inside the band, while
+    `simplify_multi`, `optimize_multi` and `aorrtc_multi` do not know the constraint - ask `validate_paths_constrained` of
+    what they return.  Each result also carries `band_refused`: the questions the constraint answered 0."""
     s = settings or RRTCMultiSettings()
     sets = []
     for g in goal_sets:
@@ -612,14 +613,40 @@ def simplify_multi(robot, paths, environments, settings=None):
     max_waypoints waypoints; where a B-spline subdivision would need more, the path comes back as it stood, a valid
     path still, with status "capacity"."""
     s = _as_simplify_multi_settings(settings)
-    raw = robot.simplify_multi_raw(paths, environments, s)
-    out = _planning_results(raw, "lengths", "points", edges_checked=("questions", int),
-                            status=("status", lambda k: SIMPLIFY_STATUS[int(k)]))
+    return _simplify_results(robot.simplify_multi_raw(paths, environments, s))
+
+
+def _simplify_results(raw):
+    out = _planning_results(raw, "lengths", "points", edges_checked=("questions", int), band_refused=("band_refused", int),
+                            status=("status", lambda k: SIMPLIFY_STATUS[int(k)]))  # (band_refused: the constrained call)
     for res in out:
         res.cost = path_cost(res.path)
     if out:  # the call's totals ride on the first result (a round = one validate_motion_batch_multi call)
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["total_questions"]
     return out
+
+
+def simplify_multi_constrained(robot, paths, environments, constraints, settings=None, constraint_settings=None):
+    """`simplify_multi` inside the band of end-effector constraints (vmv_simplify_multi_constrained):
+    constraints is one EEConstraint for all paths or one per path, constraint_settings a ConstraintSettings (its check_step
+    spaces the band samples of an edge).  paths takes the paths of `rrtc_multi_constrained`'s results as they are.
+    -> list[PlanningResult] as `simplify_multi`'s, each with `band_refused` and `status` "ok", "capacity" or "out_of_band".
+
+    The contract is `simplify_multi`'s with three changes.  Every question is validate_motion AND the band test of the
+    edge (`constraint_check_motion_batch`'s answer).  A B-spline candidate is projected into the band before it is asked
+    (`project_batch`'s result bit for bit); a projection that does not converge answers both motions 0, and the waypoint
+    is replaced by the projected point iff both motions are answered 1 and the projected point is farther than
+    min_change from the waypoint.  And the input is looked at first: a path of 3 waypoints or more whose first waypoint
+    or one of whose edges is out of band comes back as it is with status "out_of_band", 0 iterations and 0 questions,
+    without disturbing the others.  `band_refused` counts, of the questions the one-question-at-a-time loop asks, those
+    the constraint answered 0 whatever validity said; it does not depend on questions_per_round.
+
+    As in `simplify_multi` the halves of a subdivided edge are not asked again: every point of a returned path lies on
+    an asked in-band edge or on a half of one, so within check_step / 2 of joint-space length of a passing sample.  With
+    a constraint that restricts nothing the result is `simplify_multi`'s byte for byte.  One more launch per round than
+    `simplify_multi`: one wave per question slot."""
+    s = _as_simplify_multi_settings(settings)
+    return _simplify_results(robot.simplify_multi_constrained_raw(paths, environments, constraints, s, constraint_settings))
 
 
 def validate_path(robot, path, environment) -> bool:
