@@ -70,7 +70,7 @@ def test_validate_motion_batch_bit_exact(vamp, oracle, name, kind):
 @pytest.mark.parametrize("kind", ["shell64", "mixed", "capt", "clouds", "attach", "heightfield"])
 @pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_edge_schedules_are_bit_exact(vamp, oracle, monkeypatch, name, kind, mode):
-    """vmv_validate_motion_batch runs (edge, rake) tasks in two passes (csrc/vmv_robot_tu.inc: launch_validate_motion)
+    """vmv_validate_motion_batch runs (edge, rake) tasks in two passes (csrc/vmv_robot_launch.inc: launch_validate_motion)
     through two task kernels (VMV_EDGE_TASKS=1) or, by default for small batches, the fused one-FK kernel (3; Panda / UR5
     vs primitives; elsewhere it is 1).  Any other value is ignored: 0 and 2, which once selected the edge walk and
     doubling passes, must fall back to the default choice.  Each is set here on edges of every length — zero-length

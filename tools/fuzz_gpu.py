@@ -118,7 +118,7 @@ def main():
             os.environ["VMV_SELF_GROUP"] = str(group)
         else:
             os.environ.pop("VMV_SELF_GROUP", None)
-        # the edge task kernels (vmv_robot_tu.inc: launch_validate_motion): chosen by batch size, or either one forced
+        # the edge task kernels (vmv_robot_launch.inc: launch_validate_motion): chosen by batch size, or either one forced
         sched = rng.choice(["", "1", "3"])
         if sched:
             os.environ["VMV_EDGE_TASKS"] = str(sched)

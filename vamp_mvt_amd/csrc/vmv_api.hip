@@ -83,9 +83,7 @@ namespace
     }
 
     using vmv::kMaxPrimFloats;
-
-    const vmv::RobotLaunchers *const kLaunchers[] = {&vmv::kPandaLaunchers, &vmv::kUr5Launchers, &vmv::kFetchLaunchers,
-                                                     &vmv::kBaxterLaunchers};
+    using vmv::robot_launchers;
 }  // namespace
 
 namespace vmv
@@ -1010,7 +1008,7 @@ namespace
         const vmv::EnvDev *d_env = nullptr;
         if ((rc = upload(env, one, &d_env)) != VMV_OK) return rc;
         env->launch[r].d_env = d_env;
-        rc = kLaunchers[r]->prepare(env->launch[r], const_cast<vmv::EnvDev *>(d_env));
+        rc = robot_launchers(r).prepare(env->launch[r], const_cast<vmv::EnvDev *>(d_env));
         if (dev != env->device) (void) hipSetDevice(dev);
         return rc;
     }
@@ -1237,7 +1235,7 @@ namespace
                 launch[k].d_env = d_images + k, launch[k].host = images[k];
                 launch_p[k] = &launch[k], image_p[k] = d_images + k;
             }
-            if (int rc = kLaunchers[r]->prepare_multi(launch_p.data(), image_p.data(), n, status.data()); rc != VMV_OK) return rc;
+            if (int rc = robot_launchers(r).prepare_multi(launch_p.data(), image_p.data(), n, status.data()); rc != VMV_OK) return rc;
             VMV_HIP(hipDeviceSynchronize());
             return VMV_OK;
         }();
@@ -1693,7 +1691,7 @@ extern "C"
     {
         const EnvCall c = env_call(robot, env, false, d_q && d_bits, n, kDevice);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->validate(*c.launch, d_q, n, d_bits, static_cast<hipStream_t>(stream), parts);
+        return robot_launchers(robot).validate(*c.launch, d_q, n, d_bits, static_cast<hipStream_t>(stream), parts);
     }
     int vmv_validate_batch(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream)
     {
@@ -1709,7 +1707,7 @@ extern "C"
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q || !d_bits) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
-        return kLaunchers[robot]->validate(vmv::EnvLaunch{}, d_q, n, d_bits, static_cast<hipStream_t>(stream), 2);
+        return robot_launchers(robot).validate(vmv::EnvLaunch{}, d_q, n, d_bits, static_cast<hipStream_t>(stream), 2);
     }
 
     int vmv_validate_motion_batch(int robot, const vmv_env *env, const float *d_a, const float *d_b, size_t n,
@@ -1717,7 +1715,7 @@ extern "C"
     {
         const EnvCall c = env_call(robot, env, false, d_a && d_b && d_bits, n, kDevice);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->validate_motion(*c.launch, d_a, d_b, n, d_bits, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).validate_motion(*c.launch, d_a, d_b, n, d_bits, static_cast<hipStream_t>(stream));
     }
 
     int vmv_validate_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
@@ -1725,7 +1723,7 @@ extern "C"
     {
         const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_q, d_q, d_bits, false);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->validate_multi(c.launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).validate_multi(c.launch.data(), offsets, n_envs, d_q, d_bits, static_cast<hipStream_t>(stream));
     }
 
     int vmv_validate_motion_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
@@ -1733,8 +1731,8 @@ extern "C"
     {
         const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_start, d_goal, d_bits, false);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->validate_motion_multi(c.launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
-                                                        static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).validate_motion_multi(c.launch.data(), offsets, n_envs, d_start, d_goal, d_bits,
+                                                            static_cast<hipStream_t>(stream));
     }
 
     int vmv_env_prepare_multi(int robot, const vmv_env *const *envs, size_t n_envs)
@@ -1812,14 +1810,14 @@ extern "C"
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q || !d_out) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
-        return kLaunchers[robot]->fk(d_q, n, d_out, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).fk(d_q, n, d_out, static_cast<hipStream_t>(stream));
     }
     int vmv_eefk_batch(int robot, const float *d_q, size_t n, float *d_out, void *stream)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q || !d_out) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
-        return kLaunchers[robot]->eefk(d_q, n, d_out, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).eefk(d_q, n, d_out, static_cast<hipStream_t>(stream));
     }
 
     // ---- host-buffer variants: their own arrays and a device are checked here, the rest by the device form they run ----
@@ -1887,15 +1885,15 @@ extern "C"
     {
         const EnvCall c = env_call(robot, env, false, q && env_words && pair_words, n, kHost);
         if (!c.run) return c.rc;
-        const size_t ns = (size_t) kRobots[robot].n_spheres, npw = ((size_t) kLaunchers[robot]->n_self_pairs + 31) / 32;
+        const size_t ns = (size_t) kRobots[robot].n_spheres, npw = ((size_t) robot_launchers(robot).n_self_pairs + 31) / 32;
         Staged s;
         const int dq = s.in(q, config_bytes(robot, n)), ds = s.out(nullptr, n * ns * 16),
                   de = s.out(env_words, n * ns * (vmv::kReportWords + 1) * 4), dp = s.out(pair_words, n * npw * 4, 4, true);
         return s.run([&]
                      {
-                         const int rc = kLaunchers[robot]->fk(s.at<float>(dq), n, s.at<float>(ds), nullptr);
-                         return rc != VMV_OK ? rc : kLaunchers[robot]->contacts(*c.launch, s.at<float>(ds), n, s.at<uint32_t>(de),
-                                                                              s.at<uint32_t>(dp), nullptr);
+                         const int rc = robot_launchers(robot).fk(s.at<float>(dq), n, s.at<float>(ds), nullptr);
+                         return rc != VMV_OK ? rc : robot_launchers(robot).contacts(*c.launch, s.at<float>(ds), n, s.at<uint32_t>(de),
+                                                                                  s.at<uint32_t>(dp), nullptr);
                      });
     }
 
@@ -1915,15 +1913,15 @@ extern "C"
     {
         const EnvCall c = env_call(robot, env, true, d_q && d_clearance, n, kDevice, true);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->clearance(c.launch, d_q, n, d_clearance, d_witness, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).clearance(c.launch, d_q, n, d_clearance, d_witness, static_cast<hipStream_t>(stream));
     }
     int vmv_clearance_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *d_q,
                                   float *d_clearance, uint32_t *d_witness, void *stream)
     {
         const MultiCall c = multi_call(robot, envs, offsets, n_envs, d_q, d_q, d_clearance, false, true);
         if (!c.run) return c.rc;
-        return kLaunchers[robot]->clearance_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance, d_witness,
-                                                  static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).clearance_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance, d_witness,
+                                                      static_cast<hipStream_t>(stream));
     }
     int vmv_clearance_grad_batch(int robot, const vmv_env *env, const float *d_q, size_t n, float *d_clearance, float *d_grad,
                                  uint32_t *d_witness, void *stream)
@@ -1932,8 +1930,8 @@ extern "C"
         if (!c.run) return c.rc;
         return with_witness(d_witness, n, stream, [&](uint32_t *witness)
                             {
-                                return kLaunchers[robot]->clearance_grad(c.launch, d_q, n, d_clearance, d_grad, witness,
-                                                                         static_cast<hipStream_t>(stream));
+                                return robot_launchers(robot).clearance_grad(c.launch, d_q, n, d_clearance, d_grad, witness,
+                                                                             static_cast<hipStream_t>(stream));
                             });
     }
     int vmv_clearance_grad_batch_multi(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
@@ -1943,8 +1941,8 @@ extern "C"
         if (!c.run) return c.rc;
         return with_witness(d_witness, c.n, stream, [&](uint32_t *witness)
                             {
-                                return kLaunchers[robot]->clearance_grad_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance,
-                                                                               d_grad, witness, static_cast<hipStream_t>(stream));
+                                return robot_launchers(robot).clearance_grad_multi(c.launch.data(), offsets, n_envs, d_q, d_clearance,
+                                                                                   d_grad, witness, static_cast<hipStream_t>(stream));
                             });
     }
     int vmv_clearance_batch_host(int robot, const vmv_env *env, const float *q, size_t n, float *clearance, uint32_t *witness)
@@ -1952,7 +1950,7 @@ extern "C"
         const EnvCall c = env_call(robot, env, true, q && clearance, n, kHost, true);
         if (!c.run) return c.rc;
         return clearance_staged(robot, q, n, clearance, nullptr, witness, [&](float *dq, float *dc, float *, uint32_t *dw)
-                                { return kLaunchers[robot]->clearance(c.launch, dq, n, dc, dw, nullptr); });
+                                { return robot_launchers(robot).clearance(c.launch, dq, n, dc, dw, nullptr); });
     }
     int vmv_clearance_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs, const float *q,
                                        float *clearance, uint32_t *witness)
@@ -1968,7 +1966,7 @@ extern "C"
         const EnvCall c = env_call(robot, env, true, q && grad && clearance, n, kHost, true);
         if (!c.run) return c.rc;
         return clearance_staged(robot, q, n, clearance, grad, witness, [&](float *dq, float *dc, float *dg, uint32_t *dw)
-                                { return kLaunchers[robot]->clearance_grad(c.launch, dq, n, dc, dg, dw, nullptr); });
+                                { return robot_launchers(robot).clearance_grad(c.launch, dq, n, dc, dg, dw, nullptr); });
     }
     int vmv_clearance_grad_batch_multi_host(int robot, const vmv_env *const *envs, const size_t *offsets, size_t n_envs,
                                             const float *q, float *clearance, float *grad, uint32_t *witness)
@@ -1985,7 +1983,7 @@ extern "C"
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
         if (!d_q || !d_jac) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
         if (n == 0) return VMV_OK;
-        return kLaunchers[robot]->eefk_jacobian(d_q, n, d_frames, d_jac, static_cast<hipStream_t>(stream));
+        return robot_launchers(robot).eefk_jacobian(d_q, n, d_frames, d_jac, static_cast<hipStream_t>(stream));
     }
     int vmv_eefk_jacobian_batch_host(int robot, const float *q, size_t n, float *frames, float *jac)
     {
@@ -2005,7 +2003,7 @@ extern "C"
         if (n_targets == 0) return VMV_OK;
         const hipStream_t st = static_cast<hipStream_t>(stream);
         const size_t n = n_targets * (size_t) P.n_seeds;
-        if (d_seeds) return kLaunchers[robot]->ik(P, d_targets, d_seeds, n, d_q, d_err, d_status, st);
+        if (d_seeds) return robot_launchers(robot).ik(P, d_targets, d_seeds, n, d_q, d_err, d_status, st);
         IkSeedLease lease;
         float *scratch = nullptr;
         if (int rc = lease.acquire(st, robot, &scratch); rc != VMV_OK) return rc;
@@ -2013,7 +2011,7 @@ extern "C"
         hipLaunchKernelGGL(vmv::halton_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, scratch + 32, total,
                            kRobots[robot].dimension, halton_skip, scratch, scratch + 16);
         VMV_HIP(hipGetLastError());
-        return kLaunchers[robot]->ik(P, d_targets, scratch + 32, n, d_q, d_err, d_status, st);
+        return robot_launchers(robot).ik(P, d_targets, scratch + 32, n, d_q, d_err, d_status, st);
     }
     int vmv_ik_batch_host(int robot, const float *targets, size_t n_targets, const float *seeds, uint64_t halton_skip,
                           const vmv_ik_settings *settings, float *q, float *err, uint32_t *status)
@@ -2042,7 +2040,7 @@ extern "C"
         if (int rc = constraint_checks(robot, d_q && d_q_out && d_status, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
-                                 { return kLaunchers[robot]->constraint_project(c.P, d_cons, d_q, n, d_q_out, d_residuals, d_status, st); });
+                                 { return robot_launchers(robot).constraint_project(c.P, d_cons, d_q, n, d_q_out, d_residuals, d_status, st); });
     }
     int vmv_constraint_project_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
                                           const vmv_constraint_settings *settings, float *q_out, float *residuals, uint32_t *status)
@@ -2057,8 +2055,8 @@ extern "C"
         return s.run([&]
                      {
                          return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
-                             return kLaunchers[robot]->constraint_project(c.P, d_cons, s.at<float>(dq), n, s.at<float>(dout), s.at<float>(dr),
-                                                                          s.at<uint32_t>(dst), st);
+                             return robot_launchers(robot).constraint_project(c.P, d_cons, s.at<float>(dq), n, s.at<float>(dout), s.at<float>(dr),
+                                                                              s.at<uint32_t>(dst), st);
                          });
                      });
     }
@@ -2069,7 +2067,7 @@ extern "C"
         if (int rc = constraint_checks(robot, d_q && d_bits, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
-                                 { return kLaunchers[robot]->constraint_check(c.P, d_cons, d_q, n, d_bits, d_residuals, st); });
+                                 { return robot_launchers(robot).constraint_check(c.P, d_cons, d_q, n, d_bits, d_residuals, st); });
     }
     int vmv_constraint_check_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
                                         const vmv_constraint_settings *settings, uint64_t *bits, float *residuals)
@@ -2083,7 +2081,7 @@ extern "C"
         return s.run([&]
                      {
                          return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
-                             return kLaunchers[robot]->constraint_check(c.P, d_cons, s.at<float>(dq), n, s.at<uint64_t>(db), s.at<float>(dr), st);
+                             return robot_launchers(robot).constraint_check(c.P, d_cons, s.at<float>(dq), n, s.at<uint64_t>(db), s.at<float>(dr), st);
                          });
                      });
     }
@@ -2094,7 +2092,7 @@ extern "C"
         if (int rc = constraint_checks(robot, d_a && d_b && d_ok, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
-                                 { return kLaunchers[robot]->constraint_edges(c.P, d_cons, d_a, d_b, n, d_ok, st); });
+                                 { return robot_launchers(robot).constraint_edges(c.P, d_cons, d_a, d_b, n, d_ok, st); });
     }
     int vmv_constraint_check_motion_batch_host(int robot, const float *a, const float *b, size_t n, const vmv_ee_constraint *constraints,
                                                size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *ok)
@@ -2108,7 +2106,7 @@ extern "C"
         return s.run([&]
                      {
                          return constraint_launch(c, nullptr, [&](const vmv::ConstraintDev *d_cons, hipStream_t st) {
-                             return kLaunchers[robot]->constraint_edges(c.P, d_cons, s.at<float>(da), s.at<float>(db), n, s.at<uint8_t>(dk), st);
+                             return robot_launchers(robot).constraint_edges(c.P, d_cons, s.at<float>(da), s.at<float>(db), n, s.at<uint8_t>(dk), st);
                          });
                      });
     }
@@ -2166,7 +2164,7 @@ extern "C"
         const int rc = s.run([&]
                              {
                                  // Robot::sphere_fk of the one configuration
-                                 const int fk = kLaunchers[robot]->fk(s.at<float>(dq), 1, s.at<float>(drs), nullptr);
+                                 const int fk = robot_launchers(robot).fk(s.at<float>(dq), 1, s.at<float>(drs), nullptr);
                                  return fk != VMV_OK ? fk : launch_spheres(env, s.at<float>(ds), n, s.at<uint8_t>(dh), s.at<float>(drs),
                                                                            (int) ns, nullptr);
                              });

@@ -31,7 +31,6 @@ namespace vmv
     namespace
     {
         constexpr uint32_t kCartMaxWaypoints = 1024;
-        const RobotLaunchers *const kCartLaunchers[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
 
         struct CartHostSettings
         {
@@ -122,7 +121,7 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_lines, lines.data(), n * sizeof(CartLine), hipMemcpyHostToDevice, stream));
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_starts, clean.data(), n * dim * 4, hipMemcpyHostToDevice, stream));
                 VMV_LOCKSTEP_HIP(hipMemsetAsync(d_points, 0, rows * dim * 4, stream));
-                if (int rc = kCartLaunchers[robot]->cartesian(P, d_lines, d_starts, n, d_points, d_results, stream); rc != VMV_OK)
+                if (int rc = robot_launchers(robot).cartesian(P, d_lines, d_starts, n, d_points, d_results, stream); rc != VMV_OK)
                     return (void) hipDeviceSynchronize(), rc;
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(results.data(), d_results, n * sizeof(CartResult), hipMemcpyDeviceToHost, stream));
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(tracked_rows.data(), d_points, rows * dim * 4, hipMemcpyDeviceToHost, stream));

@@ -56,6 +56,32 @@ namespace vmv
     };
     void release_multi_tables();
 
+    // The table of a multi-environment launch, [segments | tiles ..] in one lease: the tiles start on a 16-byte boundary
+    // behind the segments.  The same offsets hold in the lease's host and device buffer.
+    struct MultiTableLayout
+    {
+        size_t tiles_at, bytes;  // byte offset of the first tile; size of [segments | tiles]
+        MultiTableLayout(size_t n_segs, size_t n_tiles)
+            : tiles_at((n_segs * sizeof(MultiSeg) + 15u) & ~size_t{15}), bytes(tiles_at + n_tiles * sizeof(MultiTile))
+        {
+        }
+        static MultiSeg *segs(void *base) { return static_cast<MultiSeg *>(base); }
+        MultiTile *tiles(void *base) const { return reinterpret_cast<MultiTile *>(static_cast<char *>(base) + tiles_at); }
+    };
+
+    // Which kernel variant an environment runs, as the index of every per-robot kernel table (vmv_robot_launch.inc):
+    // 0 kEnvZOnly, 1 kEnvPrims, 2 kEnvFull, 3 kEnvClouds.  The primitive-only variants (merged gates, no cloud / heightfield
+    // code) serve environments of WELL-FORMED primitives only, kEnvZOnly those without capsules and cuboids; kEnvClouds
+    // (no list code, no gate calls in the paired walk) serves point clouds and nothing else; everything else takes the
+    // variant that keeps the reference's groups (EnvDev::ill_formed).  (vmv_device.h's "clouds_only" is class 3 here.)
+    constexpr int kEnvClasses = 4;
+    inline int env_class(const EnvLaunch &e)
+    {
+        const EnvDev &D = e.host;
+        if (D.n_capt + D.n_mvt + D.n_heightfield == 0 && D.ill_formed == 0) return D.n_capsule + D.n_cuboid == 0 ? 0 : 1;
+        return D.n_capt != 0 && D.n_floats + D.n_mvt + D.n_heightfield == 0 ? 3 : 2;
+    }
+
     // vmv_ik_batch: the kernel's parameter block - vmv_ik_settings as checked by the API (rot_weight is 0 for a
     // position-only call, so the rotation rows vanish), where the seeds lie, and the robot's bounds [lower, lower + span]
     struct IkParams
@@ -169,6 +195,11 @@ namespace vmv
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;
+    inline const RobotLaunchers &robot_launchers(int robot)  // robot: a VMV_ROBOT_* value the caller has checked
+    {
+        const RobotLaunchers *const all[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
+        return *all[robot];
+    }
 
     int hip_status(hipError_t e, const char *what);  // records vmv_last_error(), maps to VMV_ERR_*
     int refuse_argument(const char *message);        // records vmv_last_error(), returns VMV_ERR_INVALID_ARGUMENT
@@ -257,7 +288,7 @@ namespace vmv
     // launch_edge_multi_tiles writes chunk[c] = tasks per tile (a multiple of 32, at least sum / grid[c]) and
     // starts[at[c] + c + j] = tiles of the class's entries before j (m[c] + 1 values), so that the class has at most
     // grid[c] + m[c] tiles and a tile never spans two segments.
-    constexpr int kEdgeMultiClasses = 4;
+    constexpr int kEdgeMultiClasses = kEnvClasses;
     struct EdgeMultiPlan
     {
         uint32_t at[kEdgeMultiClasses], m[kEdgeMultiClasses], grid[kEdgeMultiClasses];

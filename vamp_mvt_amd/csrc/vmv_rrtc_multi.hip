@@ -321,8 +321,6 @@ namespace vmv
                                   D.parent + (size_t) p * P.max_samples, P.dim, P.max_samples, out);
         }
 
-        const RobotLaunchers *const kRrtcLaunchers[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
-
         // vmv_rrtc_multi_constrained: what a round needs beside the step kernel - the resolved settings, the records on the
         // device (one, or one per problem of the run) and max_stretch * range
         struct ConstraintRound
@@ -408,7 +406,7 @@ namespace vmv
         const auto step = [&](uint32_t na) {
             hipLaunchKernelGGL(rrtc_step_kernel, dim3(na), dim3(kRrtcBlock), 0, stream, P, D);
             if (cr)  // the pending node projected and written back, the edge's band test: before the round's validation
-                (void) kRrtcLaunchers[robot]->constraint_round(cr->P, cr->d_cons, B.active, B.q_start, B.q_goal, D.pending, D.pool,
+                (void) robot_launchers(robot).constraint_round(cr->P, cr->d_cons, B.active, B.q_start, B.q_goal, D.pending, D.pool,
                                                                cr->stretch, d_c_ok, d_refused, na, stream);
         };
         if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), call,
@@ -486,7 +484,7 @@ namespace vmv
         if (int rc = vmv_robot_bounds(robot, lower, span, descale); rc != VMV_OK) return rc;
         for (int j = 0; j < 16; ++j) CP.lower[j] = j < dim ? lower[j] : 0.f, CP.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
         CP.shared = n_constraints == 1 ? 1u : 0u;
-        const RobotLaunchers &L = *kRrtcLaunchers[robot];
+        const RobotLaunchers &L = robot_launchers(robot);
         hipStream_t stream = nullptr;
         std::vector<ConstraintDev> recs(n_constraints);
         for (size_t k = 0; k < n_constraints; ++k) constraint_record(constraints[k], (double) CP.pos_tol, (double) CP.rot_tol, recs[k]);

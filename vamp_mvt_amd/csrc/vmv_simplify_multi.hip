@@ -488,8 +488,6 @@ namespace vmv
             return sat_add(sat_mul(P.max_iterations, per_iteration), 2ull + check_every);
         }
 
-        const RobotLaunchers *const kSimpLaunchers[] = {&kPandaLaunchers, &kUr5Launchers, &kFetchLaunchers, &kBaxterLaunchers};
-
         struct SimplifyConstraints  // vmv_simplify_multi_constrained: the caller's constraints (1 or n_paths), the resolved settings
         {
             ConstraintParams P;
@@ -505,7 +503,7 @@ namespace vmv
                                 const float *d_points, const size_t *offsets, size_t dim, hipStream_t stream, ConstraintDev **d_recs,
                                 std::vector<uint8_t> &out_of_band)
         {
-            const RobotLaunchers &L = *kSimpLaunchers[robot];
+            const RobotLaunchers &L = robot_launchers(robot);
             const size_t total = offsets[n], n_edges = total > 0 ? total - 1 : 0;
             std::vector<ConstraintDev> recs(cb.count);
             for (size_t k = 0; k < cb.count; ++k) constraint_record(cb.constraints[k], (double) cb.P.pos_tol, (double) cb.P.rot_tol, recs[k]);
@@ -632,7 +630,7 @@ namespace vmv
                 // the step kernel names what each slot needs; the band round projects the B-spline midpoints in place and
                 // answers every slot's band question before the round's validation reads the edges
                 hipLaunchKernelGGL(simplify_step_kernel<true>, dim3(na), dim3(kSimpBlock), 0, stream, P, D, X);
-                (void) kSimpLaunchers[robot]->simplify_band_round(cb->P, d_recs, B.active, B.q_start, B.q_goal, X.pending, d_proj,
+                (void) robot_launchers(robot).simplify_band_round(cb->P, d_recs, B.active, B.q_start, B.q_goal, X.pending, d_proj,
                                                                    (uint32_t) (kSimpMaxCandidates * dim), d_c_ok, na, (uint32_t) W, stream);
             };
             if (int rc = lockstep_rounds(robot, stream, check_every, round_bound(P, longest, check_every), W, active, active_envs, B.arrays(),
