@@ -906,6 +906,54 @@ int vmv_optimized_summary(const vmv_optimized *result, uint8_t *status, uint32_t
 int vmv_optimized_points(const vmv_optimized *result, float *out, size_t capacity_floats);
 int vmv_optimized_destroy(vmv_optimized *result);
 
+/* ---- clearance-aware path optimisation under end-effector constraints ----------------------- */
+/* vmv_optimize_multi inside the band of an end-effector constraint: the arguments are vmv_optimize_multi's, then one
+ * constraint for every path or one per path (n_constraints = 1 or n_paths) and the vmv_constraint_settings of the
+ * vmv_constraint_*_batch calls.  The contract per path is vmv_optimize_multi's - the same U, gradient, Thomas solve, cap,
+ * clip, lockstep counter and validate_every rule, fp32 with one rounding per operation - with four changes:
+ *  1. The input is looked at first.  A path with a non-finite waypoint ends VMV_OPT_NONFINITE as before.  Of a finite path
+ *     of N >= 2 both end waypoints are band-tested: vmv_constraint_check_batch's answer under the path's constraint and
+ *     constraint_settings.  For N >= 3 every inner waypoint is projected: vmv_constraint_project_batch's lane bit for bit
+ *     (a row already in the band and inside the joint bounds comes back unchanged with 0 evaluations).  Iterate 0 is the
+ *     input with its inner waypoints replaced by their projections.  An end out of band, or an inner waypoint whose
+ *     projection does not converge, ends the path VMV_OPT_OUT_OF_BAND: it comes back with its input bytes, 0 iterations,
+ *     costs 0 and NaN clearances, asks no question and does not disturb the other paths, which run as in a call of their
+ *     own.  Paths of fewer than 2 waypoints come back as they are without any test.
+ *  2. Every new iterate is projected.  The step gives x'_i = clip(x_i + D_i * scale) as in vmv_optimize_multi; then every
+ *     inner waypoint becomes project(x'_i) where that projection converged, and keeps its value of iterate k where it did
+ *     not (that value is in the band by induction; the waypoint is HELD).  U, the clearances and the gradient of iterate
+ *     k + 1 are those of the projected waypoints.  The step's size for the min_change rule stays m * scale, computed before
+ *     the projection.  There is no bound on how far a projection moves a waypoint: max_step bounds the step, and the
+ *     validated edges bound what is returned.
+ *  3. A validated iterate's question for edge (a, b) is validate_motion(a, b) AND band_edge(a, b), band_edge being
+ *     vmv_constraint_check_motion_batch's answer: the same samples, check_step and 1,024-sample cap.  A path's best is the
+ *     validated iterate whose edges all answer 1 with the smallest U, the first among equals.  A finite path of 2 waypoints
+ *     with both ends in band has its one edge asked this way: VMV_OPT_OK or VMV_OPT_NO_VALID.
+ *  4. Results as in vmv_optimized_summary, and vmv_optimized_held: per path the number of (iteration, inner waypoint)
+ *     projections that did not converge over the iterations the path ran - the steps out of iterates 0 .. iterations - 1 -
+ *     so it does not depend on the batch.  VMV_OPT_NO_VALID returns the input's bytes, not iterate 0.
+ * Consequences: every waypoint of every iterate is in the band; every edge of a VMV_OPT_OK result has been asked afresh,
+ * so vmv_validate_motion_batch and vmv_constraint_check_motion_batch answer 1 for each of them; an input whose waypoints
+ * are all in the band and whose edges are all valid and in band comes back the same way with cost <= cost_first.  With a
+ * constraint that restricts nothing (all bounds infinite, max_angle 0) and finite input inside the joint bounds the result
+ * is vmv_optimize_multi's byte for byte, clearance_calls and validation_calls included, and held is 0.
+ * Checks: vmv_optimize_multi's argument checks in its order, then NULL constraints / constraint_settings, n_constraints
+ * other than 1 or n_paths, the settings' and the constraints' own checks in vmv_constraint_project_batch's order
+ * (VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the field); then the environments' checks as in vmv_optimize_multi (a
+ * point cloud or an attachment, unfinalized, another device).  None needs a device.  A call that fails leaves *out untouched.  Per iteration one more launch than vmv_optimize_multi
+ * (one lane per waypoint of the unfinished paths), per validated iterate one more (one wave per edge), and two launches
+ * and one synchronisation for the look at the input.  With one constraint per path the edge band test reads one 136-byte
+ * record per edge; the per-iteration kernel reads one per path. */
+enum
+{
+    VMV_OPT_OUT_OF_BAND = 3 /* vmv_optimize_multi_constrained: an end out of band or an inner waypoint that cannot be projected */
+};
+int vmv_optimize_multi_constrained(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                                   const vmv_optimize_settings *settings, const vmv_ee_constraint *constraints,
+                                   size_t n_constraints, const vmv_constraint_settings *constraint_settings, vmv_optimized **out);
+/* held [n_paths] (may be NULL); VMV_ERR_INVALID_ARGUMENT for results not made by vmv_optimize_multi_constrained */
+int vmv_optimized_held(const vmv_optimized *result, uint32_t *held);
+
 /* ---- straight-line end-effector motions for many independent problems (no counterpart in the reference) -- */
 /* Problem p: a start configuration q0 (starts [n][dim]) and a target frame T1 (targets [n][16], vmv_eefk_batch's layout),
  * in environment envs[p]; envs == NULL is the kinematics-only call (nothing is validated).  The end effector is led from

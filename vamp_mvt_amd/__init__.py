@@ -1583,7 +1583,14 @@ class _Robot(types.ModuleType):
         return dict(status=status, iterations=iterations, lengths=lengths, questions=questions, points=points,
                     rounds=int(rounds.value), total_questions=int(total.value), **extra)
 
-    def optimize_multi_raw(self, paths, environments, settings):
+    def optimize_multi_constrained_raw(self, paths, environments, constraints, settings, constraint_settings=None):
+        """vmv_optimize_multi_constrained: optimize_multi_raw inside the band of end-effector constraints - one
+        EEConstraint for all paths or one per path; constraint_settings: a ConstraintSettings (None = defaults).
+        -> optimize_multi_raw's dict plus held per path (the projections of its iterations that did not converge);
+        status 3 (out_of_band) where an end of the input is out of band or an inner waypoint cannot be projected."""
+        return self.optimize_multi_raw(paths, environments, settings, constrained=(constraints, constraint_settings))
+
+    def optimize_multi_raw(self, paths, environments, settings, constrained=None):
         """vmv_optimize_multi: the clearance-aware covariant gradient iteration for many paths in lockstep, path p
         ([len][dim] waypoints, any length) in environments[p] (None = the empty environment).  settings: max_iterations,
         validate_every, step, max_step, min_change, smooth_weight, env_weight, self_weight, env_margin, self_margin,
@@ -1602,12 +1609,24 @@ class _Robot(types.ModuleType):
         clr_first, clr = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
         points = np.zeros_like(packed)
         calls, validations = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        extra = {}
+        if constrained is not None:  # (every Python-side check before any library call)
+            records, count = _constraint_records(constrained[0], n)
+            ps = (constrained[1] or ConstraintSettings()).struct()
+            extra["held"] = np.zeros(n, np.uint32)
         if n > 0:
             envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
             out = ctypes.c_void_p()
-            check(lib.vmv_optimize_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                         ctypes.byref(cs), ctypes.byref(out)), "vmv_optimize_multi")
+            if constrained is not None:
+                check(lib.vmv_optimize_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                                         ctypes.byref(cs), records, count, ctypes.byref(ps), ctypes.byref(out)),
+                      "vmv_optimize_multi_constrained")
+            else:
+                check(lib.vmv_optimize_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                             ctypes.byref(cs), ctypes.byref(out)), "vmv_optimize_multi")
             try:
+                if constrained is not None:
+                    check(lib.vmv_optimized_held(out, extra["held"].ctypes.data_as(_lib.c_u32_p)), "vmv_optimized_held")
                 check(lib.vmv_optimized_summary(out, status.ctypes.data_as(_lib.c_u8_p),
                                                 iterations.ctypes.data_as(_lib.c_u32_p), best.ctypes.data_as(_lib.c_u32_p),
                                                 _fp(cost_first), _fp(cost), _fp(clr_first), _fp(clr), ctypes.byref(calls),
@@ -1617,7 +1636,7 @@ class _Robot(types.ModuleType):
                 lib.vmv_optimized_destroy(out)
         return dict(status=status, iterations=iterations, best_iteration=best, cost_first=cost_first, cost=cost,
                     clearance_first=clr_first, clearance=clr, points=points, offsets=offsets.astype(np.int64),
-                    clearance_calls=int(calls.value), validation_calls=int(validations.value))
+                    clearance_calls=int(calls.value), validation_calls=int(validations.value), **extra)
 
     def cartesian_multi_raw(self, starts, targets, environments, settings):
         """vmv_cartesian_multi: straight-line end-effector motions for many problems in one call, problem p from

@@ -283,6 +283,10 @@ def _load():
         "vmv_optimized_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_float_p, c_float_p, c_float_p, c_float_p, c_u64_p, c_u64_p]),
         "vmv_optimized_points": (I, [V, c_float_p, S]),
         "vmv_optimized_destroy": (I, [V]),
+        "vmv_optimize_multi_constrained": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, ctypes.POINTER(OptimizeSettings),
+                                               ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintSettings),
+                                               ctypes.POINTER(V)]),
+        "vmv_optimized_held": (I, [V, c_u32_p]),
         "vmv_cartesian_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, ctypes.POINTER(CartesianSettings),
                                     ctypes.POINTER(V)]),
         "vmv_cartesian_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p, c_u64_p, c_u64_p]),

@@ -525,6 +525,11 @@ def install(robot):
         validate_motion's on the consecutive edges, the gradient is the current witness's."""
         return planning.optimize_multi(robot, paths, environments, settings, resolution)
 
+    def optimize_multi_constrained(paths, environments, constraints, settings=None, constraint_settings=None, resolution=None):
+        """planning.optimize_multi_constrained with this robot: `optimize_multi` inside the band of end-effector
+        constraints -> list[planning.OptimizedPath] (each with `held`; `status` may be "out_of_band")."""
+        return planning.optimize_multi_constrained(robot, paths, environments, constraints, settings, constraint_settings, resolution)
+
     def cartesian_multi(starts, targets, environments=None, settings=None):
         """planning.cartesian_multi with this robot: straight-line end-effector motions for many problems in one call on
         the device -> list[planning.CartesianPath]."""
@@ -543,6 +548,7 @@ def install(robot):
     robot.rrtc_multi_goals = rrtc_multi_goals
     robot.rrtc_multi_constrained = rrtc_multi_constrained
     robot.simplify_multi_constrained = simplify_multi_constrained
+    robot.optimize_multi_constrained = optimize_multi_constrained
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
     robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]

@@ -120,6 +120,26 @@ namespace vmv
         uint32_t evaluations, pad;
     };
 
+    // vmv_optimize_multi_constrained (vmv_optimize_multi.hip): where opt_band_kernel finds the waypoint of a packed row.
+    // Row r of the active paths' packed waypoints belongs to active path a = row_path[r], path p = active[a]; it is
+    // waypoint i = r - act_off[a] of the path's offsets[p + 1] - offsets[p].  The host rebuilds row_path with the active list.
+    struct OptBand
+    {
+        const uint32_t *row_path;   // [rows]
+        const uint32_t *active;     // [n_active]
+        const uint64_t *act_off;    // [n_active] first row of the path in q
+        const uint64_t *edge_off;   // [n_active] first edge of the path in e_start / e_goal
+        const uint64_t *offsets;    // [n_paths + 1] in waypoints
+        float *x;                   // [2][total][dim] the iterates, double-buffered
+        float *q;                   // [rows][dim] the packed copy the clearance call reads
+        float *e_start, *e_goal;    // [edges][dim]
+        const float *change_in;     // path p's step into the current iterate at change_in[p * state_stride]
+        uint32_t state_stride;      // in floats
+        uint32_t *held;             // [n_paths] += 1 per projection of an iteration that did not converge
+        uint8_t *unconverged;       // [n_paths] = 1 where a projection of the input did not converge (initial)
+        size_t total;               // waypoints of the call
+    };
+
     // status codes are the VMV_* values of include/vamp_mvt_amd.h
     struct RobotLaunchers
     {
@@ -192,6 +212,10 @@ namespace vmv
         int (*simplify_band_round)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_active, float *d_q_start,
                                    float *d_q_goal, const uint8_t *d_pending, float *d_proj, uint32_t proj_stride, uint8_t *d_c_ok,
                                    uint32_t na, uint32_t w, hipStream_t);
+        // vmv_optimize_multi_constrained's part of an iteration, after the step kernel on the same stream: one lane per
+        // packed waypoint of the active paths (rows below 2^31).  d_cons one record (P.shared) or one per PATH
+        int (*opt_band)(const ConstraintParams &, const ConstraintDev *d_cons, const OptBand &, uint32_t rows, uint32_t cur,
+                        uint32_t initial, uint32_t edges, uint32_t may_end, float min_change, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

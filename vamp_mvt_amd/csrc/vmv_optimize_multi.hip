@@ -21,6 +21,14 @@
 //    both copies, opt_pack_kernel rebuilds the packed copy after the host compacted the active list.
 // Every store is a plain vector store by the owning workgroup; the only atomics are on LDS words (order-independent
 // minima / maxima of integer keys).  Every loop is bounded by a waypoint count the host checked against max_waypoints.
+//
+// vmv_optimize_multi_constrained (include/vamp_mvt_amd.h states the contract in full) runs the same iteration
+// inside the band of an end-effector constraint.  The input's ends are band-tested and its inner waypoints projected
+// before the first iteration; per iteration the robot's opt_band_kernel (vmv_robot_tu.inc), one lane per packed waypoint,
+// follows the step kernel and replaces every inner waypoint of the new iterate by its projection, or by its value in the
+// current iterate where the projection does not converge; at validated iterates ONE launch of the edge band test runs
+// next to the validation call and opt_accept_kernel<true> ANDs its answers into the edge test.  The step kernel is the
+// same for both calls: the cost of an iterate is computed from x[cur], which the band kernel has already written.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
@@ -37,6 +45,8 @@ struct vmv_optimized
     std::vector<float> cost_first, cost, clearance_first, clearance;  // clearances: [n][2] = env, self
     std::vector<float> points;                                        // packed in path order, the input's layout
     uint64_t clearance_calls = 0, validation_calls = 0;
+    bool constrained = false;    // made by vmv_optimize_multi_constrained
+    std::vector<uint32_t> held;  // [n] its projections that did not converge
 };
 
 namespace vmv
@@ -81,6 +91,7 @@ namespace vmv
             const float *grad;         // [active waypoints][2][dim]
             float *e_start, *e_goal;   // [edges][dim]
             const uint64_t *bits;      // answers of the validated iterate
+            const uint8_t *band_ok;    // [edges] vmv_optimize_multi_constrained: the band's answers (NULL otherwise, never read)
             const float *recip;        // [longest - 2] reciprocals of the solve's pivots
             uint8_t *done;             // [n_paths]
             size_t total;              // waypoints of the call
@@ -250,6 +261,8 @@ namespace vmv
         }
 
         // One wave per active path, after the step kernel of validated iterate k (in x[cur]) and its validation.
+        // Constrained: an edge counts where the band's answer is 1 as well.
+        template <bool Constrained>
         __global__ __launch_bounds__(kOptAcceptBlock) void opt_accept_kernel(const OptParams P, const OptArrays D, const uint32_t cur,
                                                                              const uint32_t k)
         {
@@ -262,6 +275,7 @@ namespace vmv
             {
                 const uint64_t b = eo + e;
                 ok = ok && ((D.bits[b >> 6] >> (b & 63u)) & 1ull);
+                if constexpr (Constrained) ok = ok && D.band_ok[b] != 0u;
             }
             const bool valid = __ballot(!ok) == 0ull;
             OptState st = D.state[p];
@@ -312,10 +326,111 @@ namespace vmv
             return hip_status(e, what);
         }
 
+        struct OptConstraints  // vmv_optimize_multi_constrained: the caller's constraints (1 or n_paths), the resolved settings
+        {
+            ConstraintParams P;
+            const vmv_ee_constraint *constraints;
+            size_t count;
+        };
+
+        // row -> active index of the packed waypoints of `active` (OptBand::row_path)
+        std::vector<uint32_t> rows_of(const std::vector<uint32_t> &active, const size_t *offsets)
+        {
+            std::vector<uint32_t> rows;
+            for (size_t a = 0; a < active.size(); ++a) rows.insert(rows.end(), offsets[active[a] + 1] - offsets[active[a]], (uint32_t) a);
+            return rows;
+        }
+
+        // The constrained call's look at its input, before the iterations.  ONE band test over both ends of every path in
+        // `finite` (finite paths of 2 waypoints and more), each with its path's record; then ONE launch of the band kernel
+        // in its initial mode over the waypoints of the paths of 3 and more whose ends passed, which projects their inner
+        // waypoints in place.  out_of_band[p] = 1: an end out of band or a projection that did not converge.  x0: the
+        // input with the inner waypoints of the other paths projected (iterate 0).  d_recs: one record (shared) or one per path.
+        int optimize_band_input(int robot, const OptConstraints &cb, const ConstraintDev *d_recs, const std::vector<ConstraintDev> &recs,
+                                const std::vector<uint32_t> &finite, size_t n, const float *points, const size_t *offsets,
+                                const std::vector<uint64_t> &offsets64, size_t dim, hipStream_t stream, std::vector<uint8_t> &out_of_band,
+                                std::vector<float> &x0)
+        {
+            const RobotLaunchers &L = robot_launchers(robot);
+            const size_t total = offsets[n], m = finite.size();
+            out_of_band.assign(n, 0);
+            x0.assign(points, points + total * dim);
+            if (m == 0) return VMV_OK;
+
+            DeviceBuffers tmp;  // what only this look needs
+            std::vector<float> ends(2 * m * dim);
+            for (size_t s = 0; s < m; ++s)
+            {
+                std::memcpy(&ends[2 * s * dim], points + offsets[finite[s]] * dim, dim * 4);
+                std::memcpy(&ends[(2 * s + 1) * dim], points + (offsets[finite[s] + 1] - 1) * dim, dim * 4);
+            }
+            float *d_ends = nullptr;
+            uint64_t *d_bits = nullptr;
+            const ConstraintDev *d_end_recs = d_recs;
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_ends, ends.size()));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_bits, (2 * m + 63) / 64));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_ends, ends.data(), ends.size() * 4, hipMemcpyHostToDevice, stream));
+            if (!cb.P.shared)
+            {
+                std::vector<ConstraintDev> per_end(2 * m);
+                for (size_t s = 0; s < m; ++s) per_end[2 * s] = per_end[2 * s + 1] = recs[finite[s]];
+                ConstraintDev *d = nullptr;
+                VMV_LOCKSTEP_HIP(tmp.alloc(&d, 2 * m));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d, per_end.data(), 2 * m * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                d_end_recs = d;
+            }
+            if (int rc = L.constraint_check(cb.P, d_end_recs, d_ends, 2 * m, d_bits, nullptr, stream); rc != VMV_OK) return rc;
+            std::vector<uint64_t> bits((2 * m + 63) / 64);
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(bits.data(), d_bits, bits.size() * 8, hipMemcpyDeviceToHost, stream));
+            VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+            std::vector<uint32_t> inner;  // the paths whose inner waypoints are projected
+            for (size_t s = 0; s < m; ++s)
+            {
+                const uint32_t p = finite[s];
+                if (((bits[s >> 5] >> (2 * (s & 31u))) & 3ull) != 3ull)
+                    out_of_band[p] = 1;
+                else if (offsets[p + 1] - offsets[p] > 2)
+                    inner.push_back(p);
+            }
+            if (inner.empty()) return VMV_OK;
+
+            const std::vector<uint32_t> rows = rows_of(inner, offsets);
+            std::vector<uint64_t> act_off(inner.size());
+            for (size_t a = 0, at = 0; a < inner.size(); ++a) act_off[a] = at, at += offsets[inner[a] + 1] - offsets[inner[a]];
+            OptBand B{};
+            uint32_t *d_rows = nullptr, *d_active = nullptr;
+            uint64_t *d_act_off = nullptr, *d_offsets = nullptr;
+            float *d_scratch = nullptr;  // the packed copy and the edges of this launch, which nobody reads
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_rows, rows.size()));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_active, inner.size()));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_act_off, inner.size()));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_offsets, n + 1));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&B.x, total * dim));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&d_scratch, rows.size() * dim));
+            VMV_LOCKSTEP_HIP(tmp.alloc(&B.unconverged, n));
+            VMV_LOCKSTEP_HIP(hipMemsetAsync(B.unconverged, 0, std::max<size_t>(n, 16), stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(B.x, points, total * dim * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_active, inner.data(), inner.size() * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_act_off, act_off.data(), inner.size() * 8, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
+            B.row_path = d_rows, B.active = d_active, B.act_off = d_act_off, B.edge_off = d_act_off, B.offsets = d_offsets;
+            B.q = d_scratch, B.e_start = d_scratch, B.e_goal = d_scratch, B.change_in = B.x, B.state_stride = 0, B.held = nullptr;
+            B.total = total;
+            if (int rc = L.opt_band(cb.P, d_recs, B, (uint32_t) rows.size(), 0u, 1u, 0u, 0u, 0.f, stream); rc != VMV_OK) return rc;
+            std::vector<uint8_t> unconverged(n);
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(x0.data(), B.x, total * dim * 4, hipMemcpyDeviceToHost, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(unconverged.data(), B.unconverged, n, hipMemcpyDeviceToHost, stream));
+            VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+            for (const uint32_t p : inner) out_of_band[p] = unconverged[p];
+            return VMV_OK;
+        }
+
         // The caller has checked every argument, n > 0, and every environment is finalized on the current device with the
         // robot's part built.
+        // cb: vmv_optimize_multi_constrained's constraints and resolved settings (NULL: vmv_optimize_multi).
         int optimize_multi_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
-                               const OptParams &P, uint32_t validate_every, vmv_optimized *res)
+                               const OptParams &P, uint32_t validate_every, vmv_optimized *res, const OptConstraints *cb = nullptr)
         {
             const size_t dim = P.dim, total = offsets[n];
             hipStream_t stream = nullptr;
@@ -345,6 +460,39 @@ namespace vmv
                     active.push_back((uint32_t) k), active_envs.push_back(envs[k]), longest = std::max(longest, len);
             }
             offsets64[n] = total;
+
+            // the constrained call's look at the input: the paths out of band leave, the others start from iterate 0
+            DeviceBuffers mem;
+            ConstraintDev *d_recs = nullptr;
+            std::vector<ConstraintDev> recs;
+            std::vector<float> x0;
+            if (cb)
+            {
+                res->held.assign(n, 0);
+                recs.resize(cb->count);
+                for (size_t k = 0; k < cb->count; ++k) constraint_record(cb->constraints[k], (double) cb->P.pos_tol, (double) cb->P.rot_tol, recs[k]);
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, cb->count));
+                VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, recs.data(), cb->count * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                std::vector<uint32_t> finite(two);
+                finite.insert(finite.end(), active.begin(), active.end());
+                std::vector<uint8_t> out_of_band;
+                if (int rc = optimize_band_input(robot, *cb, d_recs, recs, finite, n, points, offsets, offsets64, dim, stream, out_of_band, x0);
+                    rc != VMV_OK)
+                    return rc;
+                const auto stays = [&](std::vector<uint32_t> &list) {
+                    size_t kept = 0;
+                    for (const uint32_t p : list)
+                        if (out_of_band[p])
+                            res->status[p] = VMV_OPT_OUT_OF_BAND;
+                        else
+                            list[kept++] = p;
+                    list.resize(kept);
+                };
+                stays(two), stays(active);
+                active_envs.clear(), longest = 0;
+                for (const uint32_t p : active) active_envs.push_back(envs[p]), longest = std::max(longest, offsets[p + 1] - offsets[p]);
+            }
+            const float *first = cb ? x0.data() : points;  // iterate 0
             const size_t na0 = active.size();
             if (na0 == 0 && two.empty()) return VMV_OK;
 
@@ -376,12 +524,25 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(opt_step_kernel),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
 
-            DeviceBuffers mem;
             OptArrays D{};
             uint64_t *d_offsets = nullptr, *d_act_off = nullptr, *d_edge_off = nullptr, *d_bits = nullptr;
             uint32_t *d_active = nullptr;
             float *d_clr = nullptr, *d_grad = nullptr, *d_recip = nullptr;
             const size_t words = (all_edges + 63) / 64 + 1;
+            // the constrained call's own: the band's answer per edge, the row -> active-path index of the band kernel, the
+            // counts of held waypoints and, with one record per path, the record of every edge for the edge band test
+            uint8_t *d_band_ok = nullptr;
+            uint32_t *d_rows = nullptr, *d_held = nullptr;
+            ConstraintDev *d_edge_recs = nullptr;
+            std::vector<ConstraintDev> edge_recs;
+            if (cb)
+            {
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_band_ok, all_edges));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_rows, act_total));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_held, n));
+                VMV_LOCKSTEP_HIP(hipMemsetAsync(d_held, 0, std::max<size_t>(n * 4, 16), stream));
+                if (!cb->P.shared) VMV_LOCKSTEP_HIP(mem.alloc(&d_edge_recs, all_edges));
+            }
             VMV_LOCKSTEP_HIP(mem.alloc(&D.state, n));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.x, 2 * total * dim));
             VMV_LOCKSTEP_HIP(mem.alloc(&D.best, total * dim));
@@ -400,12 +561,12 @@ namespace vmv
             VMV_LOCKSTEP_HIP(hipHostMalloc(&mem.pinned, std::max<size_t>(n, 16), hipHostMallocDefault));
             uint8_t *h_done = static_cast<uint8_t *>(mem.pinned);
             D.offsets = d_offsets, D.active = d_active, D.act_off = d_act_off, D.edge_off = d_edge_off, D.clr = d_clr, D.grad = d_grad;
-            D.bits = d_bits, D.recip = d_recip, D.total = total;
+            D.bits = d_bits, D.recip = d_recip, D.total = total, D.band_ok = d_band_ok;
 
             VMV_LOCKSTEP_HIP(hipMemsetAsync(D.state, 0, n * sizeof(OptState), stream));
             VMV_LOCKSTEP_HIP(hipMemsetAsync(D.done, 0, std::max<size_t>(n, 16), stream));
             VMV_LOCKSTEP_HIP(hipMemsetAsync(d_bits, 0, words * 8, stream));
-            VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.x, points, total * dim * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.x, first, total * dim * 4, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(D.best, points, total * dim * 4, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_offsets, offsets64.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_recip, recip.data(), recip.size() * 4, hipMemcpyHostToDevice, stream));
@@ -420,11 +581,37 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(hipMemcpy(d_active, active.data(), na * 4, hipMemcpyHostToDevice));
                 VMV_LOCKSTEP_HIP(hipMemcpy(d_act_off, act_off.data(), na * 8, hipMemcpyHostToDevice));
                 VMV_LOCKSTEP_HIP(hipMemcpy(d_edge_off, edge_off.data(), na * 8, hipMemcpyHostToDevice));
+                if (cb && na)
+                {
+                    const std::vector<uint32_t> rows = rows_of(active, offsets);
+                    VMV_LOCKSTEP_HIP(hipMemcpy(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+                }
+                if (d_edge_recs)  // edge e of active path a: the path's record; behind them the 2-waypoint paths' (first validation)
+                {
+                    edge_recs.clear();
+                    for (size_t a = 0; a < na; ++a)
+                        edge_recs.insert(edge_recs.end(), offsets[active[a] + 1] - offsets[active[a]] - 1, recs[active[a]]);
+                    if (na == na0)
+                        for (const uint32_t p : two) edge_recs.push_back(recs[p]);
+                    if (!edge_recs.empty())
+                        VMV_LOCKSTEP_HIP(hipMemcpy(d_edge_recs, edge_recs.data(), edge_recs.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                }
                 return VMV_OK;
             };
             const auto validated = [&](uint32_t k) { return k % validate_every == 0 || k == P.max_iterations; };
+            OptBand band{};
+            if (cb)
+            {
+                band.row_path = d_rows, band.active = d_active, band.act_off = d_act_off, band.edge_off = d_edge_off, band.offsets = d_offsets;
+                band.x = D.x, band.q = D.q, band.e_start = D.e_start, band.e_goal = D.e_goal;
+                band.change_in = reinterpret_cast<const float *>(reinterpret_cast<const char *>(D.state) + offsetof(OptState, change_in));
+                band.state_stride = (uint32_t) (sizeof(OptState) / sizeof(float));
+                band.held = d_held, band.unconverged = nullptr, band.total = total;
+            }
 
             uint32_t cur = 0;
+            if (na0 == 0 && d_edge_recs)  // (the 2-waypoint paths' records)
+                if (int rc = upload_active(); rc != VMV_OK) return rc;
             if (na0)
             {
                 if (int rc = upload_active(); rc != VMV_OK) return rc;
@@ -432,6 +619,7 @@ namespace vmv
                 if (int rc = launched(hipGetLastError(), "opt_pack_kernel"); rc != VMV_OK) return rc;
             }
             std::vector<uint64_t> h_bits;
+            std::vector<uint8_t> h_band;
             for (uint32_t k = 0; k <= P.max_iterations && (!active.empty() || (k == 0 && !two.empty())); ++k)
             {
                 const size_t na = active.size();
@@ -452,24 +640,43 @@ namespace vmv
                         rc != VMV_OK)
                         return (void) hipDeviceSynchronize(), rc;
                     ++res->validation_calls;
+                    if (cb)  // the band's answer for the same edges, next to the validation
+                        if (int rc = robot_launchers(robot).constraint_edges(cb->P, d_edge_recs ? d_edge_recs : d_recs, D.e_start, D.e_goal,
+                                                                             edge_seg[segs], d_band_ok, stream);
+                            rc != VMV_OK)
+                            return (void) hipDeviceSynchronize(), rc;
                 }
                 if (na)
                 {
                     hipLaunchKernelGGL(opt_step_kernel, dim3((uint32_t) na), dim3(kOptBlock), lds, stream, P, D, cur, k,
                                        update ? 1u : 0u, update && validated(k + 1u) ? 1u : 0u);
                     if (int rc = launched(hipGetLastError(), "opt_step_kernel"); rc != VMV_OK) return rc;
+                    if (cb && update)  // every inner waypoint of iterate k + 1 becomes its projection, or stays as in iterate k
+                        if (int rc = robot_launchers(robot).opt_band(cb->P, d_recs, band, (uint32_t) wp_seg[na], cur, 0u,
+                                                                     validated(k + 1u) ? 1u : 0u, check && k > 0u ? 1u : 0u, P.min_change,
+                                                                     stream);
+                            rc != VMV_OK)
+                            return (void) hipDeviceSynchronize(), rc;
                 }
                 if (check)
                 {
                     if (na)
                     {
-                        hipLaunchKernelGGL(opt_accept_kernel, dim3((uint32_t) na), dim3(kOptAcceptBlock), 0, stream, P, D, cur, k);
+                        if (cb)
+                            hipLaunchKernelGGL(opt_accept_kernel<true>, dim3((uint32_t) na), dim3(kOptAcceptBlock), 0, stream, P, D, cur, k);
+                        else
+                            hipLaunchKernelGGL(opt_accept_kernel<false>, dim3((uint32_t) na), dim3(kOptAcceptBlock), 0, stream, P, D, cur, k);
                         if (int rc = launched(hipGetLastError(), "opt_accept_kernel"); rc != VMV_OK) return rc;
                     }
                     if (k == 0 && !two.empty())
                     {
                         h_bits.resize(words);
                         VMV_LOCKSTEP_HIP(hipMemcpyAsync(h_bits.data(), d_bits, words * 8, hipMemcpyDeviceToHost, stream));
+                        if (cb)
+                        {
+                            h_band.resize(two.size());
+                            VMV_LOCKSTEP_HIP(hipMemcpyAsync(h_band.data(), d_band_ok + act_edges, two.size(), hipMemcpyDeviceToHost, stream));
+                        }
                     }
                     VMV_LOCKSTEP_HIP(hipMemcpyAsync(h_done, D.done, n, hipMemcpyDeviceToHost, stream));
                     VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
@@ -477,7 +684,8 @@ namespace vmv
                         for (size_t s = 0; s < two.size(); ++s)
                         {
                             const size_t b = act_edges + s;
-                            res->status[two[s]] = ((h_bits[b >> 6] >> (b & 63)) & 1ull) ? VMV_OPT_OK : VMV_OPT_NO_VALID;
+                            const bool ok = ((h_bits[b >> 6] >> (b & 63)) & 1ull) != 0 && (!cb || h_band[s] != 0);
+                            res->status[two[s]] = ok ? VMV_OPT_OK : VMV_OPT_NO_VALID;
                         }
                     size_t kept = 0;
                     for (size_t a = 0; a < na; ++a)
@@ -507,9 +715,10 @@ namespace vmv
                 std::vector<OptState> states(n);
                 VMV_LOCKSTEP_HIP(hipMemcpy(states.data(), D.state, n * sizeof(OptState), hipMemcpyDeviceToHost));
                 VMV_LOCKSTEP_HIP(hipMemcpy(res->points.data(), D.best, total * dim * 4, hipMemcpyDeviceToHost));
+                if (cb) VMV_LOCKSTEP_HIP(hipMemcpy(res->held.data(), d_held, n * 4, hipMemcpyDeviceToHost));
                 for (size_t k = 0; k < n; ++k)
                 {
-                    if (offsets[k + 1] - offsets[k] < 3 || res->status[k] == VMV_OPT_NONFINITE) continue;
+                    if (offsets[k + 1] - offsets[k] < 3 || res->status[k] == VMV_OPT_NONFINITE || res->status[k] == VMV_OPT_OUT_OF_BAND) continue;
                     const OptState &st = states[k];
                     res->status[k] = (uint8_t) st.status;
                     res->iterations[k] = st.iterations, res->best_iteration[k] = st.best_iteration;
@@ -521,6 +730,58 @@ namespace vmv
             }
             return VMV_OK;
         }
+
+        // The checks of both entry points, none of which needs a device, in the header's order -> the resolved settings
+        int optimize_checks(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                            const vmv_optimize_settings *settings, vmv_optimized *const *out, OptParams &P)
+        {
+            // device-free checks, in vmv_simplify_multi's order; the refused kinds follow (optimize_env_kinds), the rest of
+            // the environments' checks are vmv_env_prepare_multi's
+            const int dim = vmv_robot_dimension(robot);
+            if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+            if (!settings || !out || (n_paths > 0 && (!envs || !offsets))) return VMV_ERR_INVALID_ARGUMENT;
+            const vmv_optimize_settings &S = *settings;
+            if (n_paths >= kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+            const uint32_t max_waypoints = S.max_waypoints ? S.max_waypoints : kOptDefaultWaypoints;
+            if (max_waypoints > kOptMaxWaypoints) return VMV_ERR_INVALID_ARGUMENT;
+            if (n_paths > 0 && offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
+            for (size_t k = 0; k < n_paths; ++k)
+            {
+                if (offsets[k + 1] < offsets[k]) return VMV_ERR_INVALID_ARGUMENT;
+                if (offsets[k + 1] - offsets[k] > max_waypoints) return VMV_ERR_INVALID_ARGUMENT;
+            }
+            if (n_paths > 0 && offsets[n_paths] > 0 && !points) return VMV_ERR_INVALID_ARGUMENT;
+            for (size_t k = 0; k < n_paths; ++k)
+                if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
+            const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+            const auto weight = [](float v) { return std::isfinite(v) && v >= 0.f; };
+            if (!positive(S.step) || !positive(S.max_step) || !positive(S.env_margin) || !positive(S.self_margin))
+                return VMV_ERR_INVALID_ARGUMENT;
+            if (!weight(S.smooth_weight) || !weight(S.env_weight) || !weight(S.self_weight)) return VMV_ERR_INVALID_ARGUMENT;
+            if (std::isnan(S.min_change)) return VMV_ERR_INVALID_ARGUMENT;
+            if (S.validate_every == 0) return VMV_ERR_INVALID_ARGUMENT;
+            if (n_paths > 0 && offsets[n_paths] >= kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
+            P.dim = (uint32_t) dim, P.max_iterations = S.max_iterations ? S.max_iterations : kOptDefaultIterations;
+            P.step = S.step, P.max_step = S.max_step, P.min_change = S.min_change;
+            P.w_smooth = S.smooth_weight, P.w_env = S.env_weight, P.w_self = S.self_weight;
+            P.eps_env = S.env_margin, P.eps_self = S.self_margin;
+            {
+                float lower[kPlanMaxDim] = {}, span[kPlanMaxDim] = {}, descale[kPlanMaxDim] = {};
+                if (int rc = vmv_robot_bounds(robot, lower, span, descale); rc != VMV_OK) return rc;
+                for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.upper[j] = lower[j] + span[j];
+            }
+            return VMV_OK;
+        }
+
+        // The environments' kinds, behind the argument checks of both entry points: vmv_clearance_batch_multi's own check
+        // through an empty batch of it (no device, no element read or written)
+        int optimize_env_kinds(int robot, const vmv_env *const *envs, size_t n_paths)
+        {
+            if (n_paths == 0) return VMV_OK;
+            static float nothing[2] = {0.f, 0.f};
+            const std::vector<size_t> zeros(n_paths + 1, 0);
+            return vmv_clearance_batch_multi(robot, envs, zeros.data(), n_paths, nothing, nothing, nullptr, nullptr);
+        }
     }  // namespace
 }  // namespace vmv
 
@@ -529,52 +790,43 @@ extern "C"
     int vmv_optimize_multi(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
                            const vmv_optimize_settings *settings, vmv_optimized **out)
     {
-        // device-free checks first, in vmv_simplify_multi's order; the refused kinds are vmv_clearance_batch_multi's own
-        // check (an empty batch of it: no device), the rest of the environments' checks vmv_env_prepare_multi's
-        const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings || !out || (n_paths > 0 && (!envs || !offsets))) return VMV_ERR_INVALID_ARGUMENT;
-        const vmv_optimize_settings &S = *settings;
-        if (n_paths >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        const uint32_t max_waypoints = S.max_waypoints ? S.max_waypoints : vmv::kOptDefaultWaypoints;
-        if (max_waypoints > vmv::kOptMaxWaypoints) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_paths > 0 && offsets[0] != 0) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_paths; ++k)
-        {
-            if (offsets[k + 1] < offsets[k]) return VMV_ERR_INVALID_ARGUMENT;
-            if (offsets[k + 1] - offsets[k] > max_waypoints) return VMV_ERR_INVALID_ARGUMENT;
-        }
-        if (n_paths > 0 && offsets[n_paths] > 0 && !points) return VMV_ERR_INVALID_ARGUMENT;
-        for (size_t k = 0; k < n_paths; ++k)
-            if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
-        const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-        const auto weight = [](float v) { return std::isfinite(v) && v >= 0.f; };
-        if (!positive(S.step) || !positive(S.max_step) || !positive(S.env_margin) || !positive(S.self_margin))
-            return VMV_ERR_INVALID_ARGUMENT;
-        if (!weight(S.smooth_weight) || !weight(S.env_weight) || !weight(S.self_weight)) return VMV_ERR_INVALID_ARGUMENT;
-        if (std::isnan(S.min_change)) return VMV_ERR_INVALID_ARGUMENT;
-        if (S.validate_every == 0) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_paths > 0 && offsets[n_paths] >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_paths > 0)
-        {
-            static float nothing[2] = {0.f, 0.f};  // (an empty batch reads and writes no element)
-            const std::vector<size_t> zeros(n_paths + 1, 0);
-            if (int rc = vmv_clearance_batch_multi(robot, envs, zeros.data(), n_paths, nothing, nothing, nullptr, nullptr); rc != VMV_OK)
-                return rc;
-        }
         vmv::OptParams P{};
-        P.dim = (uint32_t) dim, P.max_iterations = S.max_iterations ? S.max_iterations : vmv::kOptDefaultIterations;
-        P.step = S.step, P.max_step = S.max_step, P.min_change = S.min_change;
-        P.w_smooth = S.smooth_weight, P.w_env = S.env_weight, P.w_self = S.self_weight;
-        P.eps_env = S.env_margin, P.eps_self = S.self_margin;
-        {
-            float lower[vmv::kPlanMaxDim] = {}, span[vmv::kPlanMaxDim] = {}, descale[vmv::kPlanMaxDim] = {};
-            if (int rc = vmv_robot_bounds(robot, lower, span, descale); rc != VMV_OK) return rc;
-            for (int j = 0; j < dim; ++j) P.lower[j] = lower[j], P.upper[j] = lower[j] + span[j];
-        }
-        return vmv::lockstep_call(robot, envs, n_paths, dim, out, [&](vmv_optimized *res) {
-            return vmv::optimize_multi_run(robot, envs, n_paths, points, offsets, P, S.validate_every, res);
+        if (int rc = vmv::optimize_checks(robot, envs, n_paths, points, offsets, settings, out, P); rc != VMV_OK) return rc;
+        if (int rc = vmv::optimize_env_kinds(robot, envs, n_paths); rc != VMV_OK) return rc;
+        return vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_optimized *res) {
+            return vmv::optimize_multi_run(robot, envs, n_paths, points, offsets, P, settings->validate_every, res);
         });
+    }
+
+    int vmv_optimize_multi_constrained(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
+                                       const vmv_optimize_settings *settings, const vmv_ee_constraint *constraints, size_t n_constraints,
+                                       const vmv_constraint_settings *constraint_settings, vmv_optimized **out)
+    {
+        // vmv_optimize_multi's checks in its order, then the constraint's own in vmv_constraint_project_batch's; none needs a device
+        vmv::OptParams P{};
+        if (int rc = vmv::optimize_checks(robot, envs, n_paths, points, offsets, settings, out, P); rc != VMV_OK) return rc;
+        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
+        if (n_constraints != 1 && n_constraints != n_paths) return vmv::refuse_argument("n_constraints must be 1 or n_paths");
+        vmv::OptConstraints cb{};
+        if (const char *err = vmv::constraint_settings(*constraint_settings, cb.P)) return vmv::refuse_argument(err);
+        for (size_t k = 0; k < n_constraints; ++k)
+            if (const char *err = vmv::constraint_refusal(constraints[k]))
+                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
+        cb.constraints = constraints, cb.count = n_constraints, cb.P.shared = n_constraints == 1 ? 1u : 0u;
+        for (uint32_t j = 0; j < 16; ++j) cb.P.lower[j] = j < P.dim ? P.lower[j] : 0.f, cb.P.upper[j] = j < P.dim ? P.upper[j] : 0.f;
+        if (int rc = vmv::optimize_env_kinds(robot, envs, n_paths); rc != VMV_OK) return rc;
+        const int rc = vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_optimized *res) {
+            return vmv::optimize_multi_run(robot, envs, n_paths, points, offsets, P, settings->validate_every, res, &cb);
+        });
+        if (rc == VMV_OK) (*out)->constrained = true, (*out)->held.resize(n_paths);
+        return rc;
+    }
+
+    int vmv_optimized_held(const vmv_optimized *result, uint32_t *held)
+    {
+        if (!result || !result->constrained) return VMV_ERR_INVALID_ARGUMENT;
+        if (held && result->n) std::memcpy(held, result->held.data(), result->n * 4);
+        return VMV_OK;
     }
 
     int vmv_optimized_summary(const vmv_optimized *result, uint8_t *status, uint32_t *iterations, uint32_t *best_iteration,

@@ -742,6 +742,13 @@
             return launch_flat(simplify_band_round_kernel<>, na * w, kIkBlock, stream, P, d_cons, d_active, d_q_start, d_q_goal, d_pending,
                                d_proj, proj_stride, w, d_c_ok);
         }
+        // the constraint's part of an optimiser iteration: `rows` packed waypoints (vmv_optimize_multi_constrained)
+        int launch_opt_band(const ConstraintParams &P, const ConstraintDev *d_cons, const OptBand &B, uint32_t rows, uint32_t cur,
+                            uint32_t initial, uint32_t edges, uint32_t may_end, float min_change, hipStream_t stream)
+        {
+            return launch_flat(opt_band_kernel<>, lane_grid(rows), kIkBlock, stream, P, d_cons, B, rows, cur, initial, edges, may_end,
+                               min_change);
+        }
 
         // every member by its name: a launcher added to RobotLaunchers is added here, wherever it stands in the struct
         constexpr RobotLaunchers make_launchers()
@@ -771,6 +778,7 @@
             L.constraint_edges = launch_constraint_edges;
             L.constraint_round = launch_constraint_round;
             L.simplify_band_round = launch_simplify_band_round;
+            L.opt_band = launch_opt_band;
             return L;
         }
     }  // namespace

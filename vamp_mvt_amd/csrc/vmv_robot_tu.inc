@@ -2075,6 +2075,58 @@ namespace VMV_ROBOT_NS
         if (threadIdx.x == 0u) c_ok[slot] = edge ? 1u : 0u;
     }
 
+    // The constraint's part of an optimiser iteration (vmv_optimize_multi_constrained, DESIGN.md 5q), one lane per packed
+    // waypoint of the active paths, after the step kernel on the same stream.  Row r is waypoint i of active path a =
+    // row_path[r] (OptBand, vmv_common.h); path = active[a] picks the record.  The lane projects its waypoint of the new
+    // iterate x[cur ^ 1] as constraint_project_kernel's lane does, bit for bit, and writes the projection - or, where it
+    // did not converge, the waypoint of iterate x[cur], counted in held[path] - to x[cur ^ 1], to the packed copy q and,
+    // with `edges`, to its two places among the edges.  End waypoints, rows past the last one and the rows of a path
+    // that ends at this validated iterate (may_end and its step in below min_change: the accept kernel's rule) ride along
+    // and write nothing.  initial: the same on the input in x[cur], in place; a lane that does not converge flags its path
+    // in unconverged[path] and leaves the waypoint as it is.  Plain vector stores by the owning lane; held by a vector
+    // atomicAdd (an integer sum, whatever the order); no LDS.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void opt_band_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons, const OptBand B,
+                                                                const uint32_t rows, const uint32_t cur, const uint32_t initial,
+                                                                const uint32_t edges, const uint32_t may_end, const float min_change)
+    {
+        const uint32_t r = blockIdx.x * kIkBlock + threadIdx.x;
+        const bool has = r < rows;
+        const uint32_t row = has ? r : 0u;  // (a lane past the end works on row 0 and writes nothing)
+        const uint32_t a = B.row_path[row], path = B.active[a];
+        const uint64_t lo = B.offsets[path], ao = B.act_off[a];
+        const uint32_t N = (uint32_t) (B.offsets[path + 1] - lo), i = (uint32_t) (row - ao);
+        const bool ends = may_end != 0u && B.change_in[(size_t) path * B.state_stride] < min_change;
+        const bool in_range = has && i >= 1u && i + 1u < N && !ends;
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : path];
+        float *xn = B.x + ((size_t) (initial != 0u ? cur : cur ^ 1u) * B.total + lo + i) * R::kDim;
+        const float *xk = B.x + ((size_t) cur * B.total + lo + i) * R::kDim;
+        float in[R::kDim], q[R::kDim], res_p, res_w;
+        uint32_t status;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j) in[j] = xn[j];
+        constraint_project_lane(P, C, in, in_range, q, res_p, res_w, status);
+        if (!in_range) return;
+        const bool converged = (status >> 31) != 0u;
+        if (!converged)
+        {
+            if (initial != 0u)
+                B.unconverged[path] = 1u;
+            else
+                atomicAdd(&B.held[path], 1u);
+        }
+        float *qp = B.q + (size_t) row * R::kDim;
+        const uint64_t e = B.edge_off[a] + i;  // the edge that starts at this waypoint; the one that ends here is e - 1
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            const float v = converged ? q[j] : xk[j];
+            xn[j] = v;
+            qp[j] = v;
+            if (edges != 0u) B.e_start[e * R::kDim + j] = v, B.e_goal[(e - 1u) * R::kDim + j] = v;
+        }
+    }
+
     // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------

@@ -396,9 +396,9 @@ def rrtc_multi_constrained(robot, starts, goal_sets, environments, constraints, 
     out-of-band goals of a set are never used (goal_index still counts within the caller's set).  constraint_settings: a
     ConstraintSettings (its check_step spaces the band samples of an edge); max_stretch: a projected node farther than
     max_stretch * range from the edge's near end is refused.  -> list[PlanningResult] as `rrtc_multi_goals`'s.  The path's
-    edges pass `constraint_check_motion_batch`; `simplify_multi_constrained` simplifies it inside the band, while
-    `simplify_multi`, `optimize_multi` and `aorrtc_multi` do not know the constraint - ask `validate_paths_constrained` of
-    what they return.  Each result also carries `band_refused`: the questions the constraint answered 0."""
+    edges pass `constraint_check_motion_batch`; `simplify_multi_constrained` simplifies it and
+    `optimize_multi_constrained` optimises it inside the band, while `simplify_multi`, `optimize_multi` and
+    `aorrtc_multi` do not know the constraint - ask `validate_paths_constrained` of what they return.  Each result also carries `band_refused`: the questions the constraint answered 0."""
     s = settings or RRTCMultiSettings()
     sets = []
     for g in goal_sets:
@@ -797,6 +797,7 @@ def push_out(robot, configurations, environment=None, margin=0.01, max_steps=32,
 
 
 OPTIMIZE_STATUS = ("ok", "no_valid", "nonfinite")  # VMV_OPT_*
+OPTIMIZE_CONSTRAINED_STATUS = OPTIMIZE_STATUS + ("out_of_band",)  # optimize_multi_constrained: VMV_OPT_OUT_OF_BAND too
 
 
 @dataclass
@@ -831,6 +832,13 @@ class OptimizedPath:
     cost: float
     clearance_first: tuple
     clearance: tuple
+
+
+@dataclass
+class ConstrainedOptimizedPath(OptimizedPath):
+    """optimize_multi_constrained's answer for one path: an OptimizedPath whose `status` is one of
+    OPTIMIZE_CONSTRAINED_STATUS, with `held`: the projections of the path's iterations that did not converge"""
+    held: int = 0
 
 
 def densify_path(path, resolution):
@@ -872,6 +880,12 @@ def optimize_multi(robot, paths, environments, settings=None, resolution=None):
     current witness's, so a step may bring another contact closer, and the plain iteration does not decrease U
     monotonically - which is why the best validated iterate is kept, not the last."""
     s = settings if settings is not None else OptimizeMultiSettings()
+    pts = _optimize_inputs(robot, paths, s, resolution)
+    return _optimize_results(robot.optimize_multi_raw(pts, environments, s), len(pts))
+
+
+def _optimize_inputs(robot, paths, s, resolution):
+    """the waypoint arrays of an optimiser call, densified where `resolution` is a number"""
     dim = robot.dimension()
     pts = []
     for k, p in enumerate(paths):
@@ -882,16 +896,40 @@ def optimize_multi(robot, paths, environments, settings=None, resolution=None):
                 raise ValueError(f"path {k} has {len(a)} waypoints at resolution {resolution}: more than max_waypoints "
                                  f"({int(s.max_waypoints)})")
         pts.append(a)
-    raw = robot.optimize_multi_raw(pts, environments, s)
+    return pts
+
+
+def _optimize_results(raw, n, constrained=False):
+    """the raw dict of an optimiser call -> one OptimizedPath per path (ConstrainedOptimizedPath with `held`)"""
     off = raw["offsets"]
     out = []
-    for p in range(len(pts)):
-        out.append(OptimizedPath(path=[q.copy() for q in raw["points"][off[p]:off[p + 1]]],
-                                 status=OPTIMIZE_STATUS[int(raw["status"][p])], iterations=int(raw["iterations"][p]),
-                                 best_iteration=int(raw["best_iteration"][p]), cost_first=float(raw["cost_first"][p]),
-                                 cost=float(raw["cost"][p]), clearance_first=tuple(float(v) for v in raw["clearance_first"][p]),
-                                 clearance=tuple(float(v) for v in raw["clearance"][p])))
+    for p in range(n):
+        fields = dict(path=[q.copy() for q in raw["points"][off[p]:off[p + 1]]],
+                      status=OPTIMIZE_CONSTRAINED_STATUS[int(raw["status"][p])], iterations=int(raw["iterations"][p]),
+                      best_iteration=int(raw["best_iteration"][p]), cost_first=float(raw["cost_first"][p]),
+                      cost=float(raw["cost"][p]), clearance_first=tuple(float(v) for v in raw["clearance_first"][p]),
+                      clearance=tuple(float(v) for v in raw["clearance"][p]))
+        out.append(ConstrainedOptimizedPath(held=int(raw["held"][p]), **fields) if constrained else OptimizedPath(**fields))
     return out
+
+
+def optimize_multi_constrained(robot, paths, environments, constraints, settings=None, constraint_settings=None, resolution=None):
+    """`optimize_multi` inside the band of end-effector constraints (vmv_optimize_multi_constrained):
+    constraints is one EEConstraint for all paths or one per path, constraint_settings a ConstraintSettings (None =
+    defaults).  -> list[ConstrainedOptimizedPath]: optimize_multi's fields, `held`, and `status` "ok", "no_valid",
+    "nonfinite" or "out_of_band".
+
+    Three things change.  The input is looked at first: both ends of a path must pass `constraint_check_batch`, and every
+    inner waypoint is replaced by its `project_batch` projection (unchanged where it is in the band already) - which is
+    what repairs the points `resolution=` puts on a chord between two in-band waypoints; an end out of band or an inner
+    waypoint that cannot be projected gives "out_of_band": the input comes back and nothing is asked.  Every new iterate is
+    projected waypoint by waypoint; a waypoint whose projection does not converge keeps its previous value (`held` counts
+    these).  And an iterate counts as valid only where every edge passes `validate_motion` AND
+    `constraint_check_motion_batch`, so every "ok" result gets (True, True) from `validate_paths_constrained`.
+    A constraint that restricts nothing gives `optimize_multi`'s results."""
+    s = settings if settings is not None else OptimizeMultiSettings()
+    pts = _optimize_inputs(robot, paths, s, resolution)
+    return _optimize_results(robot.optimize_multi_constrained_raw(pts, environments, constraints, s, constraint_settings), len(pts), True)
 
 
 def ik_goals(robot, targets, envs, settings=None, dedup=1e-2):
