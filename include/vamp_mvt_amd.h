@@ -1079,7 +1079,8 @@ enum
     VMV_RETIME_COLLISION = 1,
     VMV_RETIME_TOO_LONG = 2,
     VMV_RETIME_NON_FINITE = 3,
-    VMV_RETIME_STALLED = 4
+    VMV_RETIME_STALLED = 4,
+    VMV_RETIME_OUT_OF_BAND = 5 /* vmv_retime_multi_constrained only: the first failing sample pair is valid and leaves the band */
 };
 #define VMV_RETIME_NONE 0xffffffffu /* first_invalid of a path without an invalid sample pair */
 typedef struct
@@ -1104,6 +1105,59 @@ int vmv_retime_summary(const vmv_trajectories *result, uint8_t *status, uint32_t
 int vmv_retime_samples(const vmv_trajectories *result, float *times, float *positions, float *velocities, float *accelerations,
                        size_t capacity_samples);
 int vmv_retime_destroy(vmv_trajectories *result);
+
+/* ---- retiming that repairs its own blends: valid and inside the band -------------------------------- */
+/* vmv_retime_multi with a level h_i in 0 .. H + 1 (H = blend_halvings) at every corner (inner distinct waypoint), all 0 at
+ * the start, all H + 1 with base.stop_at_waypoints.  The blend half-length, float64: d_i = min(blend, L_{i-1} / 2, L_i / 2)
+ * 2^-h_i for h_i <= H (an exact scaling: every level halves, also where the edge length clamps) and 0 at H + 1, which is
+ * the stop vmv_retime_multi makes of a corner with d_i = 0.  Set-up, profile and samples are otherwise vmv_retime_multi's.
+ * constraints: NULL / n_constraints 0 (no band), one for all paths, or one per path; constraint_settings as in
+ * vmv_constraint_check_motion_batch (needed with constraints).  Rounds, all unfinished paths together:
+ *   1. set-up with the path's levels (host), retime_profile_kernel, retime_sample_kernel; TOO_LONG, STALLED and NON_FINITE
+ *      by vmv_retime_multi's rules - in a later round too, since smaller blends change the interval count - end the path
+ *      with that status and no samples.  Rows 0 and last become the end waypoints at rest, as in vmv_retime_multi.
+ *   2. every consecutive pair of the samples as returned gets two answers: valid = validate_motion's in the path's
+ *      environment (1 without envs), band = vmv_constraint_check_motion_batch's under the path's constraint (the same
+ *      samples, check_step and sample cap, bit for bit; 1 without constraints).  The pair fails where valid AND band is 0.
+ *   3. with piece(k) the piece sample k was evaluated on (the last interval with T_i <= t, then the last piece with first
+ *      <= i), a failing pair k blames every blend piece in [piece(k), piece(k + 1)]; a blend piece is one corner's.
+ *   4. no failing pair: VMV_RETIME_COMPLETE.  Some failing pair that blames no blend (it lies on lines and stops, no level
+ *      moves it), or round max_rounds: the path ends with first_invalid = its first failing pair and VMV_RETIME_COLLISION
+ *      where that pair's valid is 0, else VMV_RETIME_OUT_OF_BAND; the samples come back whole.  Otherwise every blamed
+ *      corner's level goes up by one and the path takes another round.
+ * Everything reported is the last round's; `questions` counts the pairs put to step 2 and validation_calls the
+ * vmv_validate_motion_batch_multi calls, over all rounds.  A path's result depends on its own waypoints, environment,
+ * constraint, the limits and the settings alone, bit for bit.  Hence: every COMPLETE result passes validate_motion and the
+ * band test on every returned pair; where vmv_retime_multi is COMPLETE (and no constraint restricts) the result is its
+ * bytes, rounds 1, levels 0; where round 1's failing pairs include one that blames no blend the result is round 1's, which
+ * without constraints is vmv_retime_multi's COLLISION, first_invalid and bytes; a path whose corners are all at H + 1 has
+ * the samples of vmv_retime_multi with stop_at_waypoints.
+ * Corners are repaired, edges are not: a failing pair on a line ends the path.  A blend at a lower level is not proven
+ * faster than a stop.  blend_halvings 3 and max_rounds 8 are choices, not measurements.
+ * On the device per round: the samples stay there and vmv_validate_motion_batch_multi and retime_band_kernel (one lane per
+ * pair) read them in place, one segment per path; retime_blame_kernel (one wave per path) makes the round record - first
+ * failing pair, what failed there, the ended flag, the blamed pieces - which, with the grid times, is all that comes to the
+ * host; a path's samples are downloaded once, in the round it ends.
+ * Checks: vmv_retime_multi's, in its order, on `base`; blend_halvings above 8; n_constraints neither 0, 1 nor n; with
+ * constraints, NULL constraints / constraint_settings, then vmv_constraint_project_batch's checks of the settings and of
+ * every constraint (all VMV_ERR_INVALID_ARGUMENT, vmv_last_error() names the argument); the rest as vmv_retime_multi.  A
+ * call that fails leaves *out untouched.  The result is a vmv_trajectories: vmv_retime_summary, vmv_retime_samples and
+ * vmv_retime_destroy read it unchanged. */
+typedef struct
+{
+    vmv_retime_settings base;
+    uint32_t blend_halvings; /* H: levels that halve a corner's blend before the stop; 0: default (3); at most 8 */
+    uint32_t max_rounds;     /* rounds before an unfinished path ends; 0: default (8) */
+} vmv_retime_constrained_settings;
+int vmv_retime_multi_constrained(int robot, const vmv_env *const *envs /* [n] or NULL */, size_t n, const float *points,
+                                 const size_t *offsets /* [n + 1] */, const float *vel_limits /* [dim] */,
+                                 const float *acc_limits /* [dim] */, const vmv_ee_constraint *constraints /* NULL, 1 or n */,
+                                 size_t n_constraints, const vmv_retime_constrained_settings *settings,
+                                 const vmv_constraint_settings *constraint_settings, vmv_trajectories **out);
+/* Any may be NULL.  levels: one byte per input waypoint (offsets[n] of them), the corner's level of the last round, 0 for
+ * the ends and for dropped duplicates; per path: rounds taken, repaired = corners with level > 0, stops = corners at
+ * H + 1.  A result of vmv_retime_multi is refused (VMV_ERR_INVALID_ARGUMENT). */
+int vmv_retime_levels(const vmv_trajectories *result, uint8_t *levels, uint32_t *rounds, uint32_t *repaired, uint32_t *stops);
 
 /* ---- lockstep AORRTC: cost-bounded RRT-Connect searches for many independent problems --------------------- */
 /* AORRTC (planning/aorrtc.hh, one goal, PHS sampling, no dynamic domain) for n_problems problems at once; the arguments

@@ -748,6 +748,17 @@ def _retime_settings_struct(settings):
                                int(bool(settings.stop_at_waypoints)))
 
 
+def _retime_constrained_settings_struct(settings):
+    """vmv_retime_constrained_settings from a RetimeConstrainedSettings-shaped object, checked as the library checks it"""
+    base = _retime_settings_struct(settings)
+    halvings, max_rounds = int(settings.blend_halvings), int(settings.max_rounds)
+    if not 0 <= halvings <= 8:
+        raise ValueError("blend_halvings must be from 0 (default) to 8")
+    if not 0 <= max_rounds < 2 ** 32:
+        raise ValueError("max_rounds must be from 0 (default) and fit 32 bits")
+    return _lib.RetimeConstrainedSettings(base, halvings, max_rounds)
+
+
 def _joint_limits(limits, dim, name):
     """-> float32 [dim], every entry finite and positive"""
     a = _f32(limits)
@@ -1723,6 +1734,77 @@ class _Robot(types.ModuleType):
         return dict(status=status, intervals=intervals, samples=samples, duration=duration, first_invalid=first_invalid,
                     times=arrays[0], positions=arrays[1], velocities=arrays[2], accelerations=arrays[3],
                     offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value))
+
+    def retime_multi_constrained_raw(self, paths, vel_limits, acc_limits, environments, constraints, settings,
+                                     constraint_settings=None):
+        """vmv_retime_multi_constrained: retime_multi_raw whose corners carry levels, raised round by round until every
+        returned sample pair is valid in environments[p] and inside the band of the path's constraint.  constraints: None,
+        one EEConstraint for all paths or one per path; settings: the fields of planning.RetimeConstrainedSettings.
+        -> retime_multi_raw's dict (status 5 = out_of_band) plus rounds, repaired, stops (per path) and levels (one
+        uint8 per input waypoint, packed) with level_offsets.  planning.retime_multi_constrained is the caller-facing
+        form.  Every argument is checked before any library call."""
+        if environments is not None:
+            environments = list(environments)
+            _check_environments(environments)
+        pts, packed, offsets = _packed_paths(paths, self._dim)
+        n = len(pts)
+        if environments is not None:
+            _one_per(environments, n, "path")
+        vel, acc = _joint_limits(vel_limits, self._dim, "vel_limits"), _joint_limits(acc_limits, self._dim, "acc_limits")
+        cs = _retime_constrained_settings_struct(settings)
+        records, count, ps = None, 0, None
+        if constraints is not None:
+            records, count = _constraint_records(constraints, n)
+            ps = ctypes.byref((constraint_settings or ConstraintSettings()).struct())
+        status, intervals, samples = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        duration, first_invalid = np.zeros(n, np.float32), np.full(n, 0xffffffff, np.uint32)
+        rounds, repaired, stops = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        levels = np.zeros(int(offsets[-1]) if n else 0, np.uint8)
+        arrays = [np.zeros(0, np.float32)] + [np.zeros((0, self._dim), np.float32) for _ in range(3)]
+        calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if n > 0:
+            handles = None
+            if environments is not None:
+                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+            out = ctypes.c_void_p()
+            check(lib.vmv_retime_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
+                                                   _fp(vel), _fp(acc), records, count, ctypes.byref(cs), ps, ctypes.byref(out)),
+                  "vmv_retime_multi_constrained")
+            try:
+                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (intervals, samples)]
+                check(lib.vmv_retime_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, _fp(duration),
+                                             first_invalid.ctypes.data_as(_lib.c_u32_p), ctypes.byref(calls),
+                                             ctypes.byref(questions)), "vmv_retime_summary")
+                check(lib.vmv_retime_levels(out, levels.ctypes.data_as(_lib.c_u8_p),
+                                            *[x.ctypes.data_as(_lib.c_u32_p) for x in (rounds, repaired, stops)]),
+                      "vmv_retime_levels")
+                total = int(samples.sum())
+                arrays = [np.zeros(total, np.float32)] + [np.zeros((total, self._dim), np.float32) for _ in range(3)]
+                check(lib.vmv_retime_samples(out, *[_fp(x) for x in arrays], total), "vmv_retime_samples")
+            finally:
+                lib.vmv_retime_destroy(out)
+        sample_offsets = np.zeros(n + 1, np.int64)
+        sample_offsets[1:] = np.cumsum(samples.astype(np.int64))
+        return dict(status=status, intervals=intervals, samples=samples, duration=duration, first_invalid=first_invalid,
+                    times=arrays[0], positions=arrays[1], velocities=arrays[2], accelerations=arrays[3],
+                    offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value),
+                    rounds=rounds, repaired=repaired, stops=stops, levels=levels, level_offsets=offsets.astype(np.int64))
+
+    def _retime_band_pairs(self, positions, sample_offsets, constraints, constraint_settings=None):
+        """NOT part of the supported interface (the library's vmv_retime_band_pairs_host is not in the public header
+        either): for the test that compares the band kernel with constraint_check_motion_batch.  The answers of retime_multi_constrained's band kernel for the
+        consecutive pairs of packed sample lists -> uint8 [rows], 1 in every list's last row"""
+        pos = np.ascontiguousarray(_f32(positions)).reshape(-1, self._dim)
+        off = np.ascontiguousarray(sample_offsets, dtype=np.uintp)
+        n = len(off) - 1
+        if n < 1 or int(off[-1]) != len(pos):
+            raise ValueError("sample_offsets must list at least one path and end at the row count")
+        records, count = _constraint_records(constraints, n)
+        ps = (constraint_settings or ConstraintSettings()).struct()
+        ok = np.zeros(len(pos), np.uint8)
+        check(lib.vmv_retime_band_pairs_host(self._id, _fp(pos), off.ctypes.data_as(_lib.c_size_p), n, records, count,
+                                             ctypes.byref(ps), ok.ctypes.data_as(_lib.c_u8_p)), "vmv_retime_band_pairs_host")
+        return ok
 
     def validate_batch_multi(self, configurations, environments, counts):
         """bool[n]: configurations [sum(counts[:k]), sum(counts[:k + 1])) against environments[k] (None = the empty

@@ -122,6 +122,11 @@ class RetimeSettings(ctypes.Structure):
                 ("max_grid", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("stop_at_waypoints", ctypes.c_int)]
 
 
+class RetimeConstrainedSettings(ctypes.Structure):
+    """vmv_retime_constrained_settings"""
+    _fields_ = [("base", RetimeSettings), ("blend_halvings", ctypes.c_uint32), ("max_rounds", ctypes.c_uint32)]
+
+
 class VmvError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -297,6 +302,13 @@ def _load():
         "vmv_retime_summary": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_float_p, c_u32_p, c_u64_p, c_u64_p]),
         "vmv_retime_samples": (I, [V, c_float_p, c_float_p, c_float_p, c_float_p, S]),
         "vmv_retime_destroy": (I, [V]),
+        "vmv_retime_multi_constrained": (I, [I, ctypes.POINTER(V), S, c_float_p, c_size_p, c_float_p, c_float_p,
+                                             ctypes.POINTER(EeConstraint), S, ctypes.POINTER(RetimeConstrainedSettings),
+                                             ctypes.POINTER(ConstraintSettings), ctypes.POINTER(V)]),
+        "vmv_retime_levels": (I, [V, c_u8_p, c_u32_p, c_u32_p, c_u32_p]),
+        # (exported for the tests only; not declared in the public header)
+        "vmv_retime_band_pairs_host": (I, [I, c_float_p, c_size_p, S, ctypes.POINTER(EeConstraint), S,
+                                           ctypes.POINTER(ConstraintSettings), c_u8_p]),
         "vmv_env_grid_info": (I, [V, I, I, c_u32_p, c_float_p, c_float_p, c_u32_p]),
         "vmv_env_grid_cells": (I, [V, I, I, c_u32_p, S, c_size_p]),
         "vmv_env_robot_flags": (I, [V, I, c_u64_p, c_u32_p]),

@@ -540,9 +540,17 @@ def install(robot):
         -> list[planning.Trajectory]."""
         return planning.retime_multi(robot, paths, vel_limits, acc_limits, environments, settings)
 
+    def retime_multi_constrained(paths, vel_limits, acc_limits, environments=None, constraints=None, settings=None,
+                                 constraint_settings=None):
+        """planning.retime_multi_constrained with this robot: `retime_multi` whose blends are halved, corner by corner,
+        until every sample pair is valid and inside the band -> list[planning.RepairedTrajectory]."""
+        return planning.retime_multi_constrained(robot, paths, vel_limits, acc_limits, environments, constraints, settings,
+                                                 constraint_settings)
+
     robot.optimize_multi = optimize_multi
     robot.cartesian_multi = cartesian_multi
     robot.retime_multi = retime_multi
+    robot.retime_multi_constrained = retime_multi_constrained
     robot.rrtc, robot.fcit, robot.prm, robot.simplify = rrtc, fcit, prm, simplify
     robot.rrtc_multi, robot.simplify_multi, robot.prm_multi = rrtc_multi, simplify_multi, prm_multi
     robot.rrtc_multi_goals = rrtc_multi_goals

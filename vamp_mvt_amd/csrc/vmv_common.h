@@ -216,6 +216,12 @@ namespace vmv
         // packed waypoint of the active paths (rows below 2^31).  d_cons one record (P.shared) or one per PATH
         int (*opt_band)(const ConstraintParams &, const ConstraintDev *d_cons, const OptBand &, uint32_t rows, uint32_t cur,
                         uint32_t initial, uint32_t edges, uint32_t may_end, float min_change, hipStream_t);
+        // vmv_retime_multi_constrained's band test of a round: one LANE per packed sample row g < rows (below 2^31), the
+        // pair g -> g + 1 of d_pos.  Row g belongs to listed path a, the last with sample_lo[a] <= g (sample_lo
+        // [n_paths + 1], as retime_sample_kernel reads it); a path's last row has no pair and answers 1 unread.  d_cons one
+        // record (P.shared) or record rec_of[a].  d_ok [rows]: constraint_edge_kernel's answer for the pair, bit for bit.
+        int (*retime_band)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_rec_of, const uint32_t *d_sample_lo,
+                           uint32_t n_paths, const float *d_pos, uint32_t rows, uint8_t *d_ok, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

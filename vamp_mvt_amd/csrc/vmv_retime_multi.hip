@@ -10,6 +10,7 @@
 // NULL, finalized; no device), then the device, then the environments' device and robot parts by vmv_env_prepare_multi.
 #include "../../include/vamp_mvt_amd.h"
 
+#include "vmv_constraint.h"
 #include "vmv_lockstep.h"
 #include "vmv_retime_path.h"
 
@@ -25,6 +26,9 @@ struct vmv_trajectories
     std::vector<float> duration;
     std::vector<float> times, positions, velocities, accelerations;  // packed in path order
     uint64_t validation_calls = 0, questions = 0;
+    bool levelled = false;                    // vmv_retime_multi_constrained's result: the four below are set
+    std::vector<uint8_t> levels;              // one byte per input waypoint
+    std::vector<uint32_t> rounds, repaired, stops;
 };
 
 namespace vmv
@@ -192,7 +196,8 @@ namespace vmv
         }
 
         // One lane per (path, sample).  sample_lo: [n_paths + 1] first sample of each path of the list; the outputs are
-        // packed in the list's order.
+        // packed in the list's order.  (The time of a sample and the two searches below stand a second time in
+        // retime_sample_piece, vmv_retime_path.h, for retime_blame_kernel: the two texts must stay word for word.)
         __global__ __launch_bounds__(256) void retime_sample_kernel(const RetimePathDev *__restrict__ paths,
                                                                      const RetimePiece *__restrict__ pieces,
                                                                      const uint32_t *__restrict__ sample_lo, uint32_t n_paths,
@@ -439,44 +444,427 @@ namespace vmv
             }
             return VMV_OK;
         }
+
+        // ---- vmv_retime_multi_constrained ----------------------------------------------------------------
+        constexpr uint32_t kRetimeMarkWords = 64;  // one bit per piece: a path has at most kRetimeMaxGrid / 2 = 2,048
+        static_assert(kRetimeMarkWords * 32u * kRetimeMinIntervals >= kRetimeMaxGrid, "a mark bit for every piece of a path");
+
+        struct RetimeRound  // what a round says about one path
+        {
+            uint32_t first_fail;  // the first failing sample pair, VMV_RETIME_NONE: none fails
+            uint32_t flags;       // bit 0: that pair's validity answer is 0; bit 1: some failing pair blames no blend
+        };
+
+        // Rows 0 and last of every listed path's samples become its end waypoints at rest, on the device: lane 2 a + end.
+        // ends [n_paths][2]: the packed index of the path's first and last input waypoint.  A path of one sample keeps
+        // its first waypoint.
+        __global__ __launch_bounds__(256) void retime_ends_kernel(const uint32_t *__restrict__ sample_lo, uint32_t n_paths, uint32_t dim,
+                                                                   const float *__restrict__ points, const uint32_t *__restrict__ ends,
+                                                                   float *__restrict__ pos, float *__restrict__ vel)
+        {
+            const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+            if (g >= 2u * n_paths) return;
+            const uint32_t a = g >> 1, end = g & 1u;
+            const uint32_t lo = sample_lo[a], hi = sample_lo[a + 1u];
+            if (hi == lo || (end && hi - lo == 1u)) return;
+            const size_t row = (size_t) (end ? hi - 1u : lo) * dim, src = (size_t) ends[g] * dim;
+            for (uint32_t j = 0; j < dim; ++j) pos[row + j] = points[src + j], vel[row + j] = 0.0f;
+        }
+
+        // One wave per listed path, lanes striding over its sample pairs.  valid: vmv_validate_motion_batch_multi's bits,
+        // band: retime_band_kernel's bytes, both indexed by the packed row of the pair's first sample; either may be NULL
+        // (all 1).  A failing pair (valid AND band is 0) blames the blend pieces from its first sample's piece to its
+        // second's (vmv_retime_path.h).  marks [n_paths][kRetimeMarkWords]: one bit per blamed piece.  The outer trip count
+        // comes from the host's sample layout and the inner one is the wave's largest range, so every lane reaches every
+        // shuffle; the marks are ORed into LDS words and leave by plain stores, as the round record does by lane 0.
+        __global__ __launch_bounds__(64) void retime_blame_kernel(const RetimePathDev *__restrict__ paths,
+                                                                  const RetimePiece *__restrict__ pieces,
+                                                                  const uint32_t *__restrict__ sample_lo, float dt,
+                                                                  const float *__restrict__ gT, const uint64_t *__restrict__ valid,
+                                                                  const uint8_t *__restrict__ band, RetimeRound *__restrict__ rounds,
+                                                                  uint32_t *__restrict__ marks)
+        {
+            __shared__ uint32_t mark[kRetimeMarkWords];
+            const uint32_t a = blockIdx.x, lane = threadIdx.x;
+            const RetimePathDev P = paths[a];
+            const uint32_t lo = sample_lo[a], count = sample_lo[a + 1u] - lo, pairs = count ? count - 1u : 0u;
+            const RetimePiece *pc = pieces + P.piece_lo;
+            const float *pT = gT + P.grid_lo;
+            mark[lane] = 0u;
+            __syncthreads();
+            uint32_t best = 0xffffffffu;  // (pair << 1) | its validity answer, the smallest over the failing pairs
+            bool orphan = false;
+            for (uint32_t base = 0; base < pairs; base += 64u)
+            {
+                const uint32_t k = base + lane;
+                const bool in = k < pairs;
+                const uint32_t g = lo + (in ? k : 0u);
+                const bool ok_v = valid == nullptr || ((valid[g >> 6] >> (g & 63u)) & 1ull) != 0ull;
+                const bool ok_b = band == nullptr || band[g] != 0u;
+                const bool fails = in && !(ok_v && ok_b);
+                uint32_t pa = 0u, pb = 0u;
+                if (fails)
+                {
+                    pa = retime_sample_piece(pc, P.n_pieces, pT, P.N, k, dt);
+                    pb = retime_sample_piece(pc, P.n_pieces, pT, P.N, k + 1u, dt);
+                }
+                uint32_t range = (fails && pb >= pa) ? pb - pa + 1u : 0u, longest = range;
+                for (int m = 1; m < 64; m <<= 1) longest = max(longest, (uint32_t) __shfl_xor((int) longest, m));
+                bool any = false;
+                for (uint32_t r = 0; r < longest; ++r)
+                {
+                    uint32_t piece;
+                    if (r < range && retime_blame_step(pc, pa, pb, r, piece))
+                    {
+                        atomicOr(&mark[piece >> 5], 1u << (piece & 31u));
+                        any = true;
+                    }
+                }
+                orphan = orphan || (fails && !any);
+                if (fails) best = min(best, (k << 1) | (ok_v ? 1u : 0u));
+            }
+            for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t) __shfl_xor((int) best, m));
+            const bool ended = __ballot(orphan) != 0ull;
+            __syncthreads();
+            marks[(size_t) a * kRetimeMarkWords + lane] = mark[lane];
+            if (lane == 0u)
+            {
+                RetimeRound out;
+                out.first_fail = best == 0xffffffffu ? VMV_RETIME_NONE : best >> 1;
+                out.flags = (best != 0xffffffffu && (best & 1u) == 0u ? 1u : 0u) | (ended ? 2u : 0u);
+                rounds[a] = out;
+            }
+        }
+
+        struct RetimeConstrained  // the constrained call's own settings, resolved, and the caller's constraints (0, 1 or n)
+        {
+            ConstraintParams P;
+            const vmv_ee_constraint *constraints;
+            size_t count;
+            uint32_t halvings, max_rounds;
+        };
+
+        // The caller has checked every argument, n > 0, and (with envs) every environment is finalized on the current
+        // device with the robot's part built.
+        int retime_constrained_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
+                                   const float *vel_limits, const float *acc_limits, const RetimeHostSettings &S, const RetimeConstrained &C,
+                                   vmv_trajectories *res)
+        {
+            const size_t dim = (size_t) res->dim;
+            const RobotLaunchers &L = robot_launchers(robot);
+            const bool asks = envs != nullptr || C.count != 0;
+            const uint8_t stop_level = (uint8_t) (C.halvings + 1u);
+            hipStream_t stream = nullptr;
+            res->n = n;
+            res->status.assign(n, VMV_RETIME_COMPLETE), res->intervals.assign(n, 0), res->samples.assign(n, 0);
+            res->first_invalid.assign(n, VMV_RETIME_NONE), res->duration.assign(n, 0.0f);
+            res->levels.assign(offsets[n], 0), res->rounds.assign(n, 0), res->repaired.assign(n, 0), res->stops.assign(n, 0);
+
+            int device = 0;
+            VMV_LOCKSTEP_HIP(hipGetDevice(&device));
+            DeviceBuffers call;  // what lives through the rounds: the waypoints, the limits, the constraints' records
+            float *d_points = nullptr, *d_limits = nullptr;
+            ConstraintDev *d_recs = nullptr;
+            VMV_LOCKSTEP_HIP(call.alloc(&d_points, offsets[n] * dim));
+            VMV_LOCKSTEP_HIP(call.alloc(&d_limits, 32));
+            float limits[32] = {};
+            for (size_t j = 0; j < dim; ++j) limits[j] = vel_limits[j], limits[16 + j] = acc_limits[j];
+            if (offsets[n]) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, offsets[n] * dim * 4, hipMemcpyHostToDevice, stream));
+            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_limits, limits, sizeof(limits), hipMemcpyHostToDevice, stream));
+            std::vector<ConstraintDev> cons(C.count);
+            if (C.count)
+            {
+                for (size_t k = 0; k < C.count; ++k) constraint_record(C.constraints[k], (double) C.P.pos_tol, (double) C.P.rot_tol, cons[k]);
+                VMV_LOCKSTEP_HIP(call.alloc(&d_recs, C.count));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_recs, cons.data(), C.count * sizeof(ConstraintDev), hipMemcpyHostToDevice, stream));
+            }
+            VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+
+            // per path: the level of every distinct waypoint (its input count of bytes suffices), the samples it ended with
+            std::vector<std::vector<uint8_t>> level(n);
+            std::vector<std::vector<uint32_t>> kept(n);
+            std::vector<std::vector<float>> o_t(n), o_p(n), o_v(n), o_a(n);
+            std::vector<uint32_t> live(n);
+            for (size_t p = 0; p < n; ++p)
+                live[p] = (uint32_t) p, level[p].assign(offsets[p + 1] - offsets[p], S.stop_at_waypoints ? stop_level : (uint8_t) 0);
+
+            for (uint32_t round = 1; !live.empty(); ++round)
+            {
+                // 1. set up, profile, sample
+                std::vector<RetimePiece> pieces;
+                std::vector<uint32_t> corner;  // per piece of the round
+                std::vector<RetimePathDev> recs;
+                std::vector<uint32_t> part;
+                uint64_t grid = 0;
+                for (const uint32_t p : live)
+                {
+                    const size_t count = offsets[p + 1] - offsets[p];
+                    RetimePath H = retime_path(count ? points + offsets[p] * dim : nullptr, count, dim, S.blend, S.grid_step, S.max_grid,
+                                               false, level[p].data(), C.halvings);
+                    res->rounds[p] = round, res->status[p] = VMV_RETIME_COMPLETE, res->samples[p] = 0, res->duration[p] = 0.0f;
+                    res->intervals[p] = (uint32_t) std::min<uint64_t>(H.intervals, 0xffffffffull);
+                    kept[p].swap(H.kept);
+                    if (H.what == kRetimeNonFinite) res->status[p] = VMV_RETIME_NON_FINITE;
+                    else if (H.what == kRetimeTooLong) res->status[p] = VMV_RETIME_TOO_LONG;
+                    else if (H.what == kRetimeTrivial)
+                    {
+                        res->samples[p] = H.distinct ? 1u : 0u;
+                        if (H.distinct)
+                        {
+                            o_t[p].assign(1, 0.0f), o_v[p].assign(dim, 0.0f), o_a[p].assign(dim, 0.0f);
+                            o_p[p].assign(points + offsets[p] * dim, points + (offsets[p] + 1) * dim);
+                        }
+                    }
+                    else
+                    {
+                        recs.push_back(RetimePathDev{(uint32_t) pieces.size(), (uint32_t) H.pieces.size(), (uint32_t) H.intervals, (uint32_t) grid});
+                        pieces.insert(pieces.end(), H.pieces.begin(), H.pieces.end());
+                        corner.insert(corner.end(), H.corner.begin(), H.corner.end());
+                        grid += H.intervals + 1u;
+                        part.push_back(p);
+                        if (grid >= kMultiMaxConfigs || pieces.size() >= kMultiMaxConfigs)
+                            return refuse_argument("vmv_retime_multi_constrained: the paths' grids together have 2^31 points or more");
+                    }
+                }
+                live.clear();
+                if (part.empty()) break;
+
+                const size_t np = part.size();
+                DeviceBuffers mem;  // the round's: a level changes the grid and the sample count either way, so no round bounds the next
+                RetimePathDev *d_paths = nullptr;
+                RetimePiece *d_pieces = nullptr;
+                float *d_x = nullptr, *d_u = nullptr, *d_T = nullptr;
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_paths, np));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_pieces, pieces.size()));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_x, grid));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_u, grid));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_T, grid));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_paths, recs.data(), np * sizeof(RetimePathDev), hipMemcpyHostToDevice, stream));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(RetimePiece), hipMemcpyHostToDevice, stream));
+                VMV_LOCKSTEP_HIP(hipMemsetAsync(d_T, 0, grid * 4, stream));
+                hipLaunchKernelGGL(retime_profile_kernel, dim3((uint32_t) np), dim3(64), 0, stream, d_paths, d_pieces, d_limits,
+                                   (uint32_t) dim, d_x, d_u, d_T);
+                VMV_LOCKSTEP_HIP(hipGetLastError());
+                std::vector<float> T(grid);
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(T.data(), d_T, grid * 4, hipMemcpyDeviceToHost, stream));
+                VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+
+                std::vector<RetimePathDev> srecs;
+                std::vector<uint32_t> sampled, sample_lo, ends;
+                uint64_t rows = 0;
+                for (size_t a = 0; a < np; ++a)
+                {
+                    const uint32_t p = part[a];
+                    bool finite = true;
+                    for (uint32_t i = 0; i <= recs[a].N && finite; ++i) finite = std::isfinite(T[recs[a].grid_lo + i]);
+                    if (!finite)
+                    {
+                        res->status[p] = VMV_RETIME_STALLED;
+                        continue;
+                    }
+                    const float Tp = T[recs[a].grid_lo + recs[a].N];
+                    res->duration[p] = Tp;
+                    const uint64_t count = retime_samples(Tp, S.dt);
+                    if (count > S.max_samples)
+                    {
+                        res->status[p] = VMV_RETIME_TOO_LONG;
+                        continue;
+                    }
+                    res->samples[p] = (uint32_t) count;
+                    sample_lo.push_back((uint32_t) rows), sampled.push_back(p), srecs.push_back(recs[a]);
+                    ends.push_back((uint32_t) offsets[p]), ends.push_back((uint32_t) (offsets[p + 1] - 1));
+                    rows += count;
+                    if (rows >= kMultiMaxConfigs)
+                        return refuse_argument("vmv_retime_multi_constrained: the trajectories together have 2^31 samples or more");
+                }
+                sample_lo.push_back((uint32_t) rows);
+                if (sampled.empty()) break;
+
+                const size_t ns = sampled.size();
+                uint32_t *d_slo = nullptr, *d_ends = nullptr, *d_rec_of = nullptr, *d_marks = nullptr;
+                float *d_t = nullptr, *d_p = nullptr, *d_v = nullptr, *d_a = nullptr;
+                uint64_t *d_bits = nullptr;
+                uint8_t *d_band = nullptr;
+                RetimeRound *d_rounds = nullptr;
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_slo, ns + 1));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_ends, 2 * ns));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_t, rows));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_p, rows * dim));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_v, rows * dim));
+                VMV_LOCKSTEP_HIP(mem.alloc(&d_a, rows * dim));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_paths, srecs.data(), ns * sizeof(RetimePathDev), hipMemcpyHostToDevice, stream));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_slo, sample_lo.data(), (ns + 1) * 4, hipMemcpyHostToDevice, stream));
+                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_ends, ends.data(), 2 * ns * 4, hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(retime_sample_kernel, dim3((uint32_t) ((rows + 255) / 256)), dim3(256), 0, stream, d_paths, d_pieces,
+                                   d_slo, (uint32_t) ns, (uint32_t) dim, S.dt, d_x, d_u, d_T, d_t, d_p, d_v, d_a);
+                VMV_LOCKSTEP_HIP(hipGetLastError());
+                hipLaunchKernelGGL(retime_ends_kernel, dim3((uint32_t) ((2 * ns + 255) / 256)), dim3(256), 0, stream, d_slo, (uint32_t) ns,
+                                   (uint32_t) dim, d_points, d_ends, d_p, d_v);
+                VMV_LOCKSTEP_HIP(hipGetLastError());
+
+                // 2. ask every consecutive sample pair, in place: pair g is rows g -> g + 1.  The pair behind a path's last
+                // row runs into the next path; it is asked in the path's environment like the others and never looked at.
+                std::vector<RetimeRound> rr(ns, RetimeRound{VMV_RETIME_NONE, 0u});
+                std::vector<uint32_t> marks(ns * kRetimeMarkWords, 0u);
+                uint64_t pairs = 0;
+                for (size_t a = 0; a < ns; ++a) pairs += res->samples[sampled[a]] - 1u;
+                if (asks && rows > 1)
+                {
+                    if (envs)
+                    {
+                        std::vector<const vmv_env *> seg_envs(ns);
+                        std::vector<size_t> edge_seg(sample_lo.begin(), sample_lo.end());
+                        edge_seg[ns] = rows - 1;
+                        for (size_t a = 0; a < ns; ++a) seg_envs[a] = envs[sampled[a]];
+                        VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, (rows + 63) / 64 + 1));
+                        if (int rc = vmv_validate_motion_batch_multi(robot, seg_envs.data(), edge_seg.data(), ns, d_p, d_p + dim, d_bits, stream);
+                            rc != VMV_OK)
+                            return rc;
+                        ++res->validation_calls;
+                    }
+                    if (C.count)
+                    {
+                        VMV_LOCKSTEP_HIP(mem.alloc(&d_band, rows));
+                        if (!C.P.shared)
+                        {
+                            VMV_LOCKSTEP_HIP(mem.alloc(&d_rec_of, ns));
+                            VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_rec_of, sampled.data(), ns * 4, hipMemcpyHostToDevice, stream));
+                        }
+                        if (int rc = L.retime_band(C.P, d_recs, d_rec_of, d_slo, (uint32_t) ns, d_p, (uint32_t) rows, d_band, stream); rc != VMV_OK)
+                            return rc;
+                    }
+                    res->questions += pairs;
+
+                    // 3. blame
+                    VMV_LOCKSTEP_HIP(mem.alloc(&d_rounds, ns));
+                    VMV_LOCKSTEP_HIP(mem.alloc(&d_marks, ns * kRetimeMarkWords));
+                    hipLaunchKernelGGL(retime_blame_kernel, dim3((uint32_t) ns), dim3(64), 0, stream, d_paths, d_pieces, d_slo, S.dt, d_T,
+                                       d_bits, d_band, d_rounds, d_marks);
+                    VMV_LOCKSTEP_HIP(hipGetLastError());
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(rr.data(), d_rounds, ns * sizeof(RetimeRound), hipMemcpyDeviceToHost, stream));
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(marks.data(), d_marks, marks.size() * 4, hipMemcpyDeviceToHost, stream));
+                    VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+                }
+
+                // 4. the outcome of every path; the samples of those that end come to the host, runs of neighbours together
+                std::vector<uint8_t> ends_now(ns, 0);
+                for (size_t a = 0; a < ns; ++a)
+                {
+                    const uint32_t p = sampled[a];
+                    const RetimeRound &Q = rr[a];
+                    if (Q.first_fail == VMV_RETIME_NONE) ends_now[a] = 1;
+                    else if ((Q.flags & 2u) || round >= C.max_rounds)
+                    {
+                        ends_now[a] = 1;
+                        res->status[p] = (Q.flags & 1u) ? VMV_RETIME_COLLISION : VMV_RETIME_OUT_OF_BAND;
+                        res->first_invalid[p] = Q.first_fail;
+                    }
+                    else
+                    {
+                        const uint32_t *w = marks.data() + a * kRetimeMarkWords;
+                        for (uint32_t q = 0; q < srecs[a].n_pieces; ++q)
+                            if ((w[q >> 5] >> (q & 31u)) & 1u) ++level[p][corner[srecs[a].piece_lo + q]];
+                        live.push_back(p);
+                    }
+                }
+                // (each run of neighbours into its place in one host buffer per array, ONE wait for all of them, then the
+                // rows go to their paths)
+                std::vector<size_t> stage_at(ns + 1, 0);
+                for (size_t a = 0; a < ns; ++a) stage_at[a + 1] = stage_at[a] + (ends_now[a] ? sample_lo[a + 1] - sample_lo[a] : 0u);
+                const size_t staged = stage_at[ns];
+                std::vector<float> t(staged), pp(staged * dim), vv(staged * dim), aa(staged * dim);
+                for (size_t a = 0; a < ns;)
+                {
+                    if (!ends_now[a])
+                    {
+                        ++a;
+                        continue;
+                    }
+                    size_t b = a;
+                    while (b < ns && ends_now[b]) ++b;
+                    const size_t from = sample_lo[a], count = sample_lo[b] - from, to = stage_at[a];
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(t.data() + to, d_t + from, count * 4, hipMemcpyDeviceToHost, stream));
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(pp.data() + to * dim, d_p + from * dim, count * dim * 4, hipMemcpyDeviceToHost, stream));
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(vv.data() + to * dim, d_v + from * dim, count * dim * 4, hipMemcpyDeviceToHost, stream));
+                    VMV_LOCKSTEP_HIP(hipMemcpyAsync(aa.data() + to * dim, d_a + from * dim, count * dim * 4, hipMemcpyDeviceToHost, stream));
+                    a = b;
+                }
+                VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
+                for (size_t c = 0; c < ns; ++c)
+                {
+                    if (!ends_now[c]) continue;
+                    const uint32_t p = sampled[c];
+                    const size_t at = stage_at[c], m = stage_at[c + 1] - at;
+                    o_t[p].assign(t.begin() + at, t.begin() + at + m);
+                    o_p[p].assign(pp.begin() + at * dim, pp.begin() + (at + m) * dim);
+                    o_v[p].assign(vv.begin() + at * dim, vv.begin() + (at + m) * dim);
+                    o_a[p].assign(aa.begin() + at * dim, aa.begin() + (at + m) * dim);
+                }
+            }
+
+            // the packed result; the levels per input waypoint (0 for the ends and for dropped duplicates)
+            size_t total = 0;
+            for (size_t p = 0; p < n; ++p) total += res->samples[p];
+            res->times.reserve(total), res->positions.reserve(total * dim), res->velocities.reserve(total * dim);
+            res->accelerations.reserve(total * dim);
+            for (size_t p = 0; p < n; ++p)
+            {
+                if (res->samples[p])
+                {
+                    res->times.insert(res->times.end(), o_t[p].begin(), o_t[p].end());
+                    res->positions.insert(res->positions.end(), o_p[p].begin(), o_p[p].end());
+                    res->velocities.insert(res->velocities.end(), o_v[p].begin(), o_v[p].end());
+                    res->accelerations.insert(res->accelerations.end(), o_a[p].begin(), o_a[p].end());
+                }
+                for (size_t i = 1; i + 1 < kept[p].size(); ++i)
+                {
+                    const uint8_t h = level[p][i];
+                    res->levels[offsets[p] + kept[p][i]] = h;
+                    res->repaired[p] += h > 0 ? 1u : 0u, res->stops[p] += h == stop_level ? 1u : 0u;
+                }
+            }
+            return VMV_OK;
+        }
     }  // namespace
 }  // namespace vmv
 
 extern "C"
 {
-    int vmv_retime_multi(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
-                         const float *vel_limits, const float *acc_limits, const vmv_retime_settings *settings, vmv_trajectories **out)
+    // The checks both retiming calls make before anything is launched, in the header's order; `who` names the call in
+    // the messages.  -> VMV_OK with the robot's dimension and the resolved settings, or the first failing check's code.
+    static int retime_checks(const std::string &who, int robot, const vmv_env *const *envs, size_t n, const float *points,
+                             const size_t *offsets, const float *vel_limits, const float *acc_limits, const vmv_retime_settings *settings,
+                             const void *out, int &dim, vmv::RetimeHostSettings &H)
     {
-        using vmv::refuse_argument;
-        const int dim = vmv_robot_dimension(robot);
+        const auto refuse_argument = [&](const std::string &what) { return vmv::refuse_argument((who + ": " + what).c_str()); };
+        dim = vmv_robot_dimension(robot);
         if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kRetimeMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings) return refuse_argument("vmv_retime_multi: settings is NULL");
-        if (!out) return refuse_argument("vmv_retime_multi: out is NULL");
-        if (!vel_limits) return refuse_argument("vmv_retime_multi: vel_limits is NULL");
-        if (!acc_limits) return refuse_argument("vmv_retime_multi: acc_limits is NULL");
-        if (n > 0 && !offsets) return refuse_argument("vmv_retime_multi: offsets is NULL");
+        if (!settings) return refuse_argument("settings is NULL");
+        if (!out) return refuse_argument("out is NULL");
+        if (!vel_limits) return refuse_argument("vel_limits is NULL");
+        if (!acc_limits) return refuse_argument("acc_limits is NULL");
+        if (n > 0 && !offsets) return refuse_argument("offsets is NULL");
         const vmv_retime_settings &S = *settings;
-        if (!std::isfinite(S.blend)) return refuse_argument("vmv_retime_multi: blend is not finite");
-        if (!std::isfinite(S.grid_step)) return refuse_argument("vmv_retime_multi: grid_step is not finite");
-        if (!std::isfinite(S.dt)) return refuse_argument("vmv_retime_multi: dt is not finite");
-        if (S.grid_step > 0.0f && S.grid_step < 1e-6f) return refuse_argument("vmv_retime_multi: grid_step is below 1e-6");
-        if (S.dt > 0.0f && S.dt < 1e-6f) return refuse_argument("vmv_retime_multi: dt is below 1e-6");
-        if (S.max_grid > vmv::kRetimeMaxGrid) return refuse_argument("vmv_retime_multi: max_grid is above 4,096");
-        if (S.stop_at_waypoints != 0 && S.stop_at_waypoints != 1) return refuse_argument("vmv_retime_multi: stop_at_waypoints is neither 0 nor 1");
+        if (!std::isfinite(S.blend)) return refuse_argument("blend is not finite");
+        if (!std::isfinite(S.grid_step)) return refuse_argument("grid_step is not finite");
+        if (!std::isfinite(S.dt)) return refuse_argument("dt is not finite");
+        if (S.grid_step > 0.0f && S.grid_step < 1e-6f) return refuse_argument("grid_step is below 1e-6");
+        if (S.dt > 0.0f && S.dt < 1e-6f) return refuse_argument("dt is below 1e-6");
+        if (S.max_grid > vmv::kRetimeMaxGrid) return refuse_argument("max_grid is above 4,096");
+        if (S.stop_at_waypoints != 0 && S.stop_at_waypoints != 1) return refuse_argument("stop_at_waypoints is neither 0 nor 1");
         for (int j = 0; j < dim; ++j)
         {
             if (!(std::isfinite(vel_limits[j]) && vel_limits[j] > 0.0f))
-                return refuse_argument(("vmv_retime_multi: vel_limits[" + std::to_string(j) + "] is not finite and positive").c_str());
+                return refuse_argument("vel_limits[" + std::to_string(j) + "] is not finite and positive");
             if (!(std::isfinite(acc_limits[j]) && acc_limits[j] > 0.0f))
-                return refuse_argument(("vmv_retime_multi: acc_limits[" + std::to_string(j) + "] is not finite and positive").c_str());
+                return refuse_argument("acc_limits[" + std::to_string(j) + "] is not finite and positive");
         }
-        if (n >= vmv::kMultiMaxConfigs) return refuse_argument("vmv_retime_multi: n is 2^31 or more");
-        if (n > 0 && offsets[0] != 0) return refuse_argument("vmv_retime_multi: offsets[0] is not 0");
+        if (n >= vmv::kMultiMaxConfigs) return refuse_argument("n is 2^31 or more");
+        if (n > 0 && offsets[0] != 0) return refuse_argument("offsets[0] is not 0");
         for (size_t k = 0; k < n; ++k)
-            if (offsets[k + 1] < offsets[k])
-                return refuse_argument(("vmv_retime_multi: offsets decrease at " + std::to_string(k + 1)).c_str());
-        if (n > 0 && offsets[n] >= vmv::kMultiMaxConfigs) return refuse_argument("vmv_retime_multi: 2^31 waypoints or more");
-        if (n > 0 && offsets[n] > 0 && !points) return refuse_argument("vmv_retime_multi: points is NULL");
+            if (offsets[k + 1] < offsets[k]) return refuse_argument("offsets decrease at " + std::to_string(k + 1));
+        if (n > 0 && offsets[n] >= vmv::kMultiMaxConfigs) return refuse_argument("2^31 waypoints or more");
+        if (n > 0 && offsets[n] > 0 && !points) return refuse_argument("points is NULL");
         if (envs && n > 0)
         {
             static float nothing[2] = {0.f, 0.f};  // (an empty batch reads and writes no element)
@@ -485,9 +873,19 @@ extern "C"
             if (int rc = vmv_validate_batch_multi(robot, envs, zeros.data(), n, nothing, no_bits, nullptr); rc != VMV_OK) return rc;
         }
         const auto or_default = [](float v, float d) { return v > 0.0f ? v : d; };
-        const vmv::RetimeHostSettings H{(double) or_default(S.blend, 0.1f), (double) or_default(S.grid_step, 0.02f), or_default(S.dt, 0.01f),
-                                        S.max_grid ? S.max_grid : vmv::kRetimeMaxGrid, S.max_samples ? S.max_samples : 65536u,
-                                        S.stop_at_waypoints != 0};
+        H = vmv::RetimeHostSettings{(double) or_default(S.blend, 0.1f), (double) or_default(S.grid_step, 0.02f), or_default(S.dt, 0.01f),
+                                    S.max_grid ? S.max_grid : vmv::kRetimeMaxGrid, S.max_samples ? S.max_samples : 65536u,
+                                    S.stop_at_waypoints != 0};
+        return VMV_OK;
+    }
+
+    int vmv_retime_multi(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
+                         const float *vel_limits, const float *acc_limits, const vmv_retime_settings *settings, vmv_trajectories **out)
+    {
+        int dim = 0;
+        vmv::RetimeHostSettings H;
+        if (int rc = retime_checks("vmv_retime_multi", robot, envs, n, points, offsets, vel_limits, acc_limits, settings, out, dim, H); rc != VMV_OK)
+            return rc;
 
         vmv_trajectories *result = new (std::nothrow) vmv_trajectories;
         if (!result) return VMV_ERR_HIP;
@@ -504,6 +902,124 @@ extern "C"
             return rc;
         }
         *out = result;
+        return VMV_OK;
+    }
+
+    int vmv_retime_multi_constrained(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
+                                     const float *vel_limits, const float *acc_limits, const vmv_ee_constraint *constraints,
+                                     size_t n_constraints, const vmv_retime_constrained_settings *settings,
+                                     const vmv_constraint_settings *constraint_settings, vmv_trajectories **out)
+    {
+        // vmv_retime_multi's checks in its order, then this call's own, then the constraint's in vmv_constraint_project_batch's
+        // order; none needs a device
+        const std::string who = "vmv_retime_multi_constrained";
+        const auto refuse_argument = [&](const std::string &what) { return vmv::refuse_argument((who + ": " + what).c_str()); };
+        int dim = 0;
+        vmv::RetimeHostSettings H;
+        if (int rc = retime_checks(who, robot, envs, n, points, offsets, vel_limits, acc_limits, settings ? &settings->base : nullptr, out, dim, H);
+            rc != VMV_OK)
+            return rc;
+        if (settings->blend_halvings > vmv::kRetimeMaxHalvings) return refuse_argument("blend_halvings is above 8");
+        vmv::RetimeConstrained C{};
+        C.halvings = settings->blend_halvings ? settings->blend_halvings : 3u;
+        C.max_rounds = settings->max_rounds ? settings->max_rounds : 8u;
+        if (n_constraints != 0 && n_constraints != 1 && n_constraints != n) return refuse_argument("n_constraints is neither 0, 1 nor n");
+        if (n_constraints)
+        {
+            if (!constraints) return refuse_argument("constraints is NULL");
+            if (!constraint_settings) return refuse_argument("constraint_settings is NULL");
+            if (const char *err = vmv::constraint_settings(*constraint_settings, C.P)) return refuse_argument(err);
+            for (size_t k = 0; k < n_constraints; ++k)
+                if (const char *err = vmv::constraint_refusal(constraints[k]))
+                    return refuse_argument("constraints[" + std::to_string(k) + "]: " + err);
+            C.constraints = constraints, C.count = n_constraints, C.P.shared = n_constraints == 1 ? 1u : 0u;
+            float lower[16], span[16], descale[16];
+            if (int rb = vmv_robot_bounds(robot, lower, span, descale); rb != VMV_OK) return rb;
+            for (int j = 0; j < 16; ++j) C.P.lower[j] = j < dim ? lower[j] : 0.f, C.P.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
+        }
+
+        vmv_trajectories *result = new (std::nothrow) vmv_trajectories;
+        if (!result) return VMV_ERR_HIP;
+        result->dim = dim, result->levelled = true;
+        int rc = VMV_OK;
+        if (n > 0)
+        {
+            if (envs) rc = vmv_env_prepare_multi(robot, envs, n);
+            if (rc == VMV_OK) rc = vmv::retime_constrained_run(robot, envs, n, points, offsets, vel_limits, acc_limits, H, C, result);
+        }
+        if (rc != VMV_OK)
+        {
+            delete result;
+            return rc;
+        }
+        *out = result;
+        return VMV_OK;
+    }
+
+    // NOT part of the supported interface and not in the public header: retime_band_kernel on its own, for the test that
+    // compares its answers with vmv_constraint_check_motion_batch.  The band answers of the consecutive pairs of n_paths
+    // packed sample lists, list a = positions rows [sample_offsets[a], sample_offsets[a + 1]) under constraint 0
+    // (n_constraints 1) or a.  ok: one byte per ROW, 1 in a list's last row.  Synchronous, host buffers.
+    int vmv_retime_band_pairs_host(int robot, const float *positions, const size_t *sample_offsets, size_t n_paths,
+                                   const vmv_ee_constraint *constraints, size_t n_constraints, const vmv_constraint_settings *settings,
+                                   uint8_t *ok)
+    {
+        using vmv::hip_status;
+        const auto refuse_argument = [](const std::string &what) { return vmv::refuse_argument(("vmv_retime_band_pairs_host: " + what).c_str()); };
+        const int dim = vmv_robot_dimension(robot);
+        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!positions || !sample_offsets || !constraints || !settings || !ok) return refuse_argument("null pointer");
+        if (n_paths == 0 || n_paths >= vmv::kMultiMaxConfigs) return refuse_argument("n_paths must be 1 .. 2^31 - 1");
+        if (n_constraints != 1 && n_constraints != n_paths) return refuse_argument("n_constraints must be 1 or n_paths");
+        if (sample_offsets[0] != 0) return refuse_argument("sample_offsets[0] is not 0");
+        for (size_t a = 0; a < n_paths; ++a)
+            if (sample_offsets[a + 1] <= sample_offsets[a]) return refuse_argument("every list needs a row");
+        const size_t rows = sample_offsets[n_paths];
+        if (rows >= vmv::kMultiMaxConfigs) return refuse_argument("2^31 rows or more");
+        vmv::ConstraintParams P{};
+        if (const char *err = vmv::constraint_settings(*settings, P)) return refuse_argument(err);
+        std::vector<vmv::ConstraintDev> cons(n_constraints);
+        for (size_t k = 0; k < n_constraints; ++k)
+        {
+            if (const char *err = vmv::constraint_refusal(constraints[k])) return refuse_argument("constraints[" + std::to_string(k) + "]: " + err);
+            vmv::constraint_record(constraints[k], (double) P.pos_tol, (double) P.rot_tol, cons[k]);
+        }
+        P.shared = n_constraints == 1 ? 1u : 0u;
+        std::vector<uint32_t> slo(n_paths + 1), rec_of(n_paths);
+        for (size_t a = 0; a <= n_paths; ++a) slo[a] = (uint32_t) sample_offsets[a];
+        for (size_t a = 0; a < n_paths; ++a) rec_of[a] = (uint32_t) a;
+        int device = 0;
+        VMV_LOCKSTEP_HIP(hipGetDevice(&device));
+        vmv::DeviceBuffers mem;
+        vmv::ConstraintDev *d_recs = nullptr;
+        uint32_t *d_slo = nullptr, *d_rec_of = nullptr;
+        float *d_p = nullptr;
+        uint8_t *d_ok = nullptr;
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, n_constraints));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_slo, n_paths + 1));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_rec_of, n_paths));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_p, rows * (size_t) dim));
+        VMV_LOCKSTEP_HIP(mem.alloc(&d_ok, rows));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, cons.data(), n_constraints * sizeof(vmv::ConstraintDev), hipMemcpyHostToDevice));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_slo, slo.data(), (n_paths + 1) * 4, hipMemcpyHostToDevice));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_rec_of, rec_of.data(), n_paths * 4, hipMemcpyHostToDevice));
+        VMV_LOCKSTEP_HIP(hipMemcpy(d_p, positions, rows * (size_t) dim * 4, hipMemcpyHostToDevice));
+        if (int rc = vmv::robot_launchers(robot).retime_band(P, d_recs, d_rec_of, d_slo, (uint32_t) n_paths, d_p, (uint32_t) rows, d_ok, nullptr);
+            rc != VMV_OK)
+            return rc;
+        VMV_LOCKSTEP_HIP(hipMemcpy(ok, d_ok, rows, hipMemcpyDeviceToHost));
+        return VMV_OK;
+    }
+
+    int vmv_retime_levels(const vmv_trajectories *result, uint8_t *levels, uint32_t *rounds, uint32_t *repaired, uint32_t *stops)
+    {
+        if (!result) return VMV_ERR_INVALID_ARGUMENT;
+        if (!result->levelled) return vmv::refuse_argument("vmv_retime_levels: the result is not vmv_retime_multi_constrained's");
+        const size_t n = result->n;
+        if (levels && !result->levels.empty()) std::memcpy(levels, result->levels.data(), result->levels.size());
+        if (rounds && n) std::memcpy(rounds, result->rounds.data(), n * 4);
+        if (repaired && n) std::memcpy(repaired, result->repaired.data(), n * 4);
+        if (stops && n) std::memcpy(stops, result->stops.data(), n * 4);
         return VMV_OK;
     }
 

@@ -1,5 +1,8 @@
 // vmv_retime_path.h — the host steps of vmv_retime_multi that make no device call (include/vamp_mvt_amd.h):
 // the float64 set-up of a blended path from fp32 waypoints (its pieces, their grid) and the sample count of a duration.
+// For vmv_retime_multi_constrained the set-up takes a level per corner, and the two searches that place a
+// sample on the grid and the blame rule of one failing sample pair stand here as host-and-device functions, so that
+// retime_blame_kernel and a host program run the same text.
 // Plain C++ without a HIP header, so that tests/native/retime_sanitize.cc compiles it on its own.
 #pragma once
 
@@ -7,6 +10,12 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#if defined(__HIPCC__)
+#define VMV_RETIME_HD __host__ __device__
+#else
+#define VMV_RETIME_HD
+#endif
 
 namespace vmv
 {
@@ -42,11 +51,18 @@ namespace vmv
         uint32_t distinct = 0;   // distinct waypoints
         uint64_t intervals = 0;  // N
         std::vector<RetimePiece> pieces;
+        std::vector<uint32_t> corner;  // per piece: the distinct waypoint a blend rounds; 0 for a line
+        std::vector<uint32_t> kept;    // per distinct waypoint: its index among the input waypoints
     };
 
-    // waypoints [count][dim] (fp32, any values); blend, grid_step positive and finite; dim <= 16
+    constexpr uint32_t kRetimeMaxHalvings = 8;  // the cap of blend_halvings
+
+    // waypoints [count][dim] (fp32, any values); blend, grid_step positive and finite; dim <= 16.
+    // levels (may be nullptr: every corner at level 0, or a stop with stop_at_waypoints): one byte per DISTINCT waypoint,
+    // so `count` bytes always suffice; corner i has the half-length min(blend, L_{i-1} / 2, L_i / 2) * 2^-levels[i] up to
+    // level `halvings` (the scaling is exact) and 0, a stop, above it.  With levels, stop_at_waypoints is not looked at.
     inline RetimePath retime_path(const float *waypoints, size_t count, size_t dim, double blend, double grid_step,
-                                  uint32_t max_grid, bool stop_at_waypoints)
+                                  uint32_t max_grid, bool stop_at_waypoints, const uint8_t *levels, uint32_t halvings)
     {
         RetimePath P;
         for (size_t k = 0; k < count * dim; ++k)
@@ -64,6 +80,7 @@ namespace vmv
         }
         const size_t m = keep.size();
         P.distinct = (uint32_t) (m < 2 ? m : 2);
+        P.kept.assign(keep.begin(), keep.end());
         if (m < 2) return P;
 
         const size_t edges = m - 1;
@@ -81,12 +98,17 @@ namespace vmv
             L[e] = std::sqrt(sum);
             for (size_t j = 0; j < dim; ++j) u[e * dim + j] /= L[e];
         }
-        if (!stop_at_waypoints)
+        if (levels)
+        {
+            for (size_t i = 1; i + 1 < m; ++i)
+                if (levels[i] <= halvings) d[i] = std::ldexp(std::fmin(blend, std::fmin(0.5 * L[i - 1], 0.5 * L[i])), -(int) levels[i]);
+        }
+        else if (!stop_at_waypoints)
             for (size_t i = 1; i + 1 < m; ++i) d[i] = std::fmin(blend, std::fmin(0.5 * L[i - 1], 0.5 * L[i]));
 
         uint64_t grid = 0;
         bool stop_next = true;  // the first grid point is a stop point
-        const auto add = [&](const double *base, const double *uin, const double *uout, double half, double span) {
+        const auto add = [&](const double *base, const double *uin, const double *uout, double half, double span, size_t corner) {
             RetimePiece R{};
             for (size_t j = 0; j < dim; ++j) R.base[j] = (float) base[j], R.u_in[j] = (float) uin[j], R.u_out[j] = (float) uout[j];
             R.d = (float) half, R.span = (float) span;
@@ -95,7 +117,7 @@ namespace vmv
                                need < 4294967295.0 ? (uint64_t) need : 4294967295ull;  // (the quotient may be huge; never NaN)
             R.n = (uint32_t) n, R.first = (uint32_t) (grid < 4294967295ull ? grid : 4294967295ull), R.stop = stop_next ? 1u : 0u;
             grid += n, stop_next = false;
-            if (grid <= max_grid) P.pieces.push_back(R);
+            if (grid <= max_grid) P.pieces.push_back(R), P.corner.push_back((uint32_t) corner);
         };
         std::vector<double> base(dim);
         for (size_t e = 0; e < edges; ++e)
@@ -106,14 +128,14 @@ namespace vmv
             if (span > kRetimeMinSpan)
             {
                 for (size_t j = 0; j < dim; ++j) base[j] = (double) w[j] + d[e] * ue[j];
-                add(base.data(), ue, ue, 0.0, span);
+                add(base.data(), ue, ue, 0.0, span, 0);
             }
             if (e + 1 < edges)
             {
                 if (d[e + 1] > 0.0)
                 {
                     for (size_t j = 0; j < dim; ++j) base[j] = (double) w1[j] - d[e + 1] * ue[j];
-                    add(base.data(), ue, ue + dim, d[e + 1], 2.0 * d[e + 1]);
+                    add(base.data(), ue, ue + dim, d[e + 1], 2.0 * d[e + 1], e + 1);
                 }
                 else
                     stop_next = true;  // a corner without a blend
@@ -123,7 +145,7 @@ namespace vmv
         if (grid > max_grid)
         {
             P.what = kRetimeTooLong;
-            P.pieces.clear();
+            P.pieces.clear(), P.corner.clear();
             return P;
         }
         if (P.pieces.empty())  // every line at most 1e-9 long and no blend: the path is its first waypoint
@@ -133,6 +155,12 @@ namespace vmv
         }
         P.what = kRetimeOk;
         return P;
+    }
+
+    inline RetimePath retime_path(const float *waypoints, size_t count, size_t dim, double blend, double grid_step,
+                                  uint32_t max_grid, bool stop_at_waypoints)
+    {
+        return retime_path(waypoints, count, dim, blend, grid_step, max_grid, stop_at_waypoints, nullptr, 0u);
     }
 
     // samples of a trajectory of duration T sampled every dt (both fp32 values, T >= 0 finite, dt > 0): ceil(T / dt) + 1 in
@@ -153,5 +181,53 @@ namespace vmv
             if (!((bits[b >> 6] >> (b & 63u)) & 1ull)) return e;
         }
         return none;
+    }
+
+    // ---- vmv_retime_multi_constrained: where a sample lies, and what a failing sample pair blames ---------------------
+    // The time of sample k and the two searches of retime_sample_kernel (vmv_retime_multi.hip), which keeps its own text
+    // because its code is not to change: the two must STAY word for word, or piece(k) differs from the piece the sample
+    // was evaluated on.  T [N + 1] the grid times of the path, pieces [n_pieces] its records.  -> the piece of sample k.
+    VMV_RETIME_HD inline uint32_t retime_sample_piece(const RetimePiece *pieces, uint32_t n_pieces, const float *T, uint32_t N,
+                                                      uint32_t k, float dt)
+    {
+        const float t = fminf((float) k * dt, T[N]);
+        uint32_t i = 0u, hi = N - 1u;  // the last interval that starts at or before t
+        while (i < hi)
+        {
+            const uint32_t mid = (i + hi + 1u) >> 1;
+            if (T[mid] <= t) i = mid;
+            else hi = mid - 1u;
+        }
+        uint32_t a = 0u;  // its piece
+        hi = n_pieces - 1u;
+        while (a < hi)
+        {
+            const uint32_t mid = (a + hi + 1u) >> 1;
+            if (pieces[mid].first <= i) a = mid;
+            else hi = mid - 1u;
+        }
+        return a;
+    }
+
+    // The blame rule.  A failing pair whose samples lie on the pieces pa <= pb blames every blend piece in [pa, pb]; this
+    // is step r of the walk over that range: -> true where piece pa + r is in the range and is a blend (`piece` is set to
+    // it either way).  The steps r = 0 .. pb - pa make the whole rule; retime_blame_kernel runs them in a loop whose trip
+    // count is the wave's largest range, a host program in retime_blame_pair below.
+    VMV_RETIME_HD inline bool retime_blame_step(const RetimePiece *pieces, uint32_t pa, uint32_t pb, uint32_t r, uint32_t &piece)
+    {
+        piece = pa + r;
+        return piece <= pb && pieces[piece].d > 0.0f;
+    }
+
+    // marks [ceil(n_pieces / 32)] words, one bit per piece, ORed into.  -> whether the pair blames any blend.
+    inline bool retime_blame_pair(const RetimePiece *pieces, uint32_t pa, uint32_t pb, uint32_t *marks)
+    {
+        bool any = false;
+        for (uint32_t r = 0; pa + r <= pb; ++r)
+        {
+            uint32_t piece;
+            if (retime_blame_step(pieces, pa, pb, r, piece)) marks[piece >> 5] |= 1u << (piece & 31u), any = true;
+        }
+        return any;
     }
 }  // namespace vmv

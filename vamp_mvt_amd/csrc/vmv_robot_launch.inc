@@ -749,6 +749,13 @@
             return launch_flat(opt_band_kernel<>, lane_grid(rows), kIkBlock, stream, P, d_cons, B, rows, cur, initial, edges, may_end,
                                min_change);
         }
+        // the band test of a retiming round: `rows` packed sample rows of n_paths listed paths (vmv_retime_multi_constrained)
+        int launch_retime_band(const ConstraintParams &P, const ConstraintDev *d_cons, const uint32_t *d_rec_of, const uint32_t *d_sample_lo,
+                               uint32_t n_paths, const float *d_pos, uint32_t rows, uint8_t *d_ok, hipStream_t stream)
+        {
+            return launch_flat(retime_band_kernel<>, lane_grid(rows), kIkBlock, stream, P, d_cons, d_rec_of, d_sample_lo, n_paths, d_pos,
+                               rows, d_ok);
+        }
 
         // every member by its name: a launcher added to RobotLaunchers is added here, wherever it stands in the struct
         constexpr RobotLaunchers make_launchers()
@@ -779,6 +786,7 @@
             L.constraint_round = launch_constraint_round;
             L.simplify_band_round = launch_simplify_band_round;
             L.opt_band = launch_opt_band;
+            L.retime_band = launch_retime_band;
             return L;
         }
     }  // namespace

@@ -2127,6 +2127,70 @@ namespace VMV_ROBOT_NS
         }
     }
 
+    // The band test of the edge a -> b asked by ONE lane: constraint_band_edge's count, its t = i / n_c and its
+    // constraint_band per sample, i = 1 .. n_c in turn, ANDed.  The AND does not depend on the order and the wave form's
+    // repeated last sample adds nothing, so the answer is the wave form's bit for bit.  `live` false: no edge, nothing
+    // is evaluated, answers false.
+    __device__ __forceinline__ bool constraint_band_edge_lane(const ConstraintParams &P, const ConstraintDev &C, const float (&qa)[R::kDim],
+                                                              const float (&qb)[R::kDim], const bool live)
+    {
+        float dq[R::kDim], sq = 0.0f;
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            dq[j] = qb[j] - qa[j];
+            sq = j == 0 ? dq[j] * dq[j] : sq + dq[j] * dq[j];
+        }
+        const float count = fmaxf(1.0f, ceilf(sqrtf(sq) / P.check_step));
+        const bool fits = live && count <= (float) kConstraintMaxSamples;
+        const uint32_t n_c = fits ? (uint32_t) count : 0u;
+        bool ok = fits;
+        for (uint32_t i = 1u; i <= n_c && ok; ++i)
+        {
+            const float t = (float) i / (float) n_c;
+            float cfg[R::kDim];
+#pragma unroll
+            for (int j = 0; j < R::kDim; ++j) cfg[j] = qa[j] + dq[j] * t;
+            ConstraintState S;
+            ok = constraint_band(cfg, C, S);
+        }
+        return ok;
+    }
+
+    // The band test of a retiming round (vmv_retime_multi_constrained, DESIGN.md 5r), one LANE per packed sample row g:
+    // the pair of rows g -> g + 1 of pos, read in place.  A pair of samples dt apart is a few centimetres of joint space,
+    // n_c is 1 or 2, and a wave per pair would idle 63 lanes.  Row g belongs to listed path a, the last whose first
+    // sample is not behind g (retime_sample_kernel's search); the path's last row has no pair: its lane answers 1 and
+    // reads nothing, so no lane reads past row rows - 1.  The record is cons[0] (P.shared) or cons[rec_of[a]].  One byte
+    // per row, a plain store by the owning lane; no LDS, no atomics.
+    template <int = 0>
+    __global__ __launch_bounds__(kIkBlock) void retime_band_kernel(const ConstraintParams P, const ConstraintDev *__restrict__ cons,
+                                                                   const uint32_t *__restrict__ rec_of, const uint32_t *__restrict__ sample_lo,
+                                                                   const uint32_t n_paths, const float *__restrict__ pos, const uint32_t rows,
+                                                                   uint8_t *__restrict__ ok_out)
+    {
+        const uint32_t g = blockIdx.x * kIkBlock + threadIdx.x;
+        if (g >= rows) return;
+        uint32_t lo = 0u, hi = n_paths - 1u;
+        while (lo < hi)
+        {
+            const uint32_t mid = (lo + hi + 1u) >> 1;
+            if (sample_lo[mid] <= g) lo = mid;
+            else hi = mid - 1u;
+        }
+        const bool pair = g + 1u < sample_lo[lo + 1u];
+        const ConstraintDev C = cons[P.shared != 0u ? 0u : rec_of[lo]];
+        float qa[R::kDim], qb[R::kDim];
+#pragma unroll
+        for (int j = 0; j < R::kDim; ++j)
+        {
+            qa[j] = pair ? pos[(size_t) g * R::kDim + j] : 0.0f;
+            qb[j] = pair ? pos[((size_t) g + 1u) * R::kDim + j] : 0.0f;
+        }
+        const bool ok = constraint_band_edge_lane(P, C, qa, qb, pair);
+        ok_out[g] = (!pair || ok) ? 1u : 0u;
+    }
+
     // ---------------------------------------------------------------------------------------------------------
     // launchers
     // ---------------------------------------------------------------------------------------------------------

@@ -1197,6 +1197,58 @@ def retime_multi(robot, paths, vel_limits, acc_limits, environments=None, settin
                        first_invalid=-1 if bad[p] == 0xffffffff else bad[p]) for p in range(len(status))]
 
 
+RETIME_CONSTRAINED_STATUS = RETIME_STATUS + ("out_of_band",)  # VMV_RETIME_*, with VMV_RETIME_OUT_OF_BAND
+
+
+@dataclass
+class RetimeConstrainedSettings(RetimeSettings):
+    """vmv_retime_constrained_settings with its defaults: RetimeSettings' fields, blend_halvings (H: how often a corner's
+    blend is halved before the corner becomes a stop, at most 8) and max_rounds (after which an unfinished path ends with
+    its last round's samples).  3 and 8 are choices, not measurements."""
+    blend_halvings: int = 3
+    max_rounds: int = 8
+
+
+@dataclass
+class RepairedTrajectory(Trajectory):
+    """retime_multi_constrained's answer for one path: a Trajectory (`status` one of RETIME_CONSTRAINED_STATUS) with the
+    rounds it took, levels (one per input waypoint: how often that corner's blend was halved, blend_halvings + 1 = a stop,
+    0 for the ends and dropped duplicates), repaired (corners with a level above 0) and stops (corners that became stops)"""
+    rounds: int = 0
+    levels: np.ndarray = None
+    repaired: int = 0
+    stops: int = 0
+
+
+def retime_multi_constrained(robot, paths, vel_limits, acc_limits, environments=None, constraints=None, settings=None,
+                             constraint_settings=None):
+    """`retime_multi` whose blends stay valid and inside the band (vmv_retime_multi_constrained): every
+    corner carries a level, 0 at first; a level halves the corner's blend, and above blend_halvings the corner is a stop.
+    Per round every unfinished path is set up with its levels, profiled and sampled as `retime_multi` does, every
+    consecutive sample pair is put to validate_motion in environments[p] and to the band test of the path's constraint
+    (`constraint_check_motion_batch`'s answer; constraints: None, one EEConstraint for all paths or one per path), and
+    every corner whose blend a failing pair touches goes up one level.  -> list[RepairedTrajectory].
+
+    "complete" means every returned sample pair passed both tests.  A failing pair that touches no blend - it lies on the
+    polyline itself - ends the path at once, "collision" where validate_motion refused it and "out_of_band" otherwise, as
+    does round max_rounds.  Where `retime_multi` is complete and no constraint restricts, the result is `retime_multi`'s
+    byte for byte, in one round.  Corners are repaired, edges are not; a blend at a lower level is not proven faster than a
+    stop (tools/bench_retime_constrained.py measures it); `aorrtc_multi` still does not know the constraint."""
+    s = settings if settings is not None else RetimeConstrainedSettings()
+    raw = robot.retime_multi_constrained_raw(paths, vel_limits, acc_limits, environments, constraints, s, constraint_settings)
+    off, lev = raw["offsets"].tolist(), raw["level_offsets"].tolist()
+    status, intervals = raw["status"].tolist(), raw["intervals"].tolist()
+    duration, bad = raw["duration"].tolist(), raw["first_invalid"].tolist()
+    rounds, repaired, stops = raw["rounds"].tolist(), raw["repaired"].tolist(), raw["stops"].tolist()
+    return [RepairedTrajectory(times=raw["times"][off[p]:off[p + 1]].copy(), positions=raw["positions"][off[p]:off[p + 1]].copy(),
+                               velocities=raw["velocities"][off[p]:off[p + 1]].copy(),
+                               accelerations=raw["accelerations"][off[p]:off[p + 1]].copy(), duration=duration[p],
+                               status=RETIME_CONSTRAINED_STATUS[status[p]], intervals=intervals[p],
+                               first_invalid=-1 if bad[p] == 0xffffffff else bad[p], rounds=rounds[p],
+                               levels=raw["levels"][lev[p]:lev[p + 1]].copy(), repaired=repaired[p], stops=stops[p])
+            for p in range(len(status))]
+
+
 @dataclass
 class Roadmap:
     vertices: np.ndarray  # [n][dim] valid samples
