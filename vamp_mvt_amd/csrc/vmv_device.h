@@ -1719,6 +1719,28 @@ namespace vmv
     //      owner's flag on a hit.  The answer per item is the OR of the same pure per-pair predicates: same bits.
     // tools/experiments/pair_fine_study.py: pair_rounds is this dealing, counted per wave of the bench workload.
     constexpr int kPairEntries = kWave;
+
+    // neg(md - ext) for ext = sqrtf(nsq) + r, the max_extent test of a pair, without the correctly rounded root where its
+    // last bits cannot matter.  sqrtf is the bare instruction plus some eighteen that scale it and fix its last bit; a round
+    // of pairs pays them per pair, a third of its arithmetic.  The bare root (1 ulp) puts ext_fast within 3 ulp of ext,
+    // so wherever md lies more than 1e-6 * ext_fast (over 8 ulp) away from ext_fast, md - ext has the sign of
+    // md - ext_fast and is not zero: the same sign bit.  If any lane of the wave lies closer, or its numbers are not
+    // finite (the comparison is false for NaN and for an infinite ext_fast), all lanes take the expression as it was.
+    // Below the normal range the bare root and the true one both stay under 2^-63, far inside the tolerance: r > 0, the
+    // robot's sphere radii.
+    __device__ __forceinline__ bool within_extent(const float md, const float nsq, const float r)
+    {
+        const float ext_fast = __builtin_amdgcn_sqrtf(nsq) + r;
+        const float gap = md - ext_fast;
+        if (wave_any(!(vabs(gap) > 1e-6f * ext_fast)))
+        {
+            float n = nsq;
+            asm volatile("" : "+v"(n));  // (keeps this side behind its branch: flattened into selects, both roots run per pair)
+            return neg(md - (sqrtf(n) + r));
+        }
+        return neg(gap);
+    }
+
     template <int T, bool SHARED, int C>
     __device__ __forceinline__ void pairs_list(const EnvView &E, const uint32_t n, const uint32_t off, const uint32_t wbase,
                                                const uint32_t shift, const uint32_t (&cw)[kMaskWords], const uint32_t tag,
@@ -1768,10 +1790,11 @@ namespace vmv
                 const int slot = s * k + (int) j;
                 const float x = items[slot], y = items[C + slot], z = items[2 * C + slot];
                 const float r = E.radii[radii_offset + s0 + s];
-                const float ext = sqrtf(dot3(x, y, z, x, y, z)) + r, rsq = r * r;
+                const float nsq = dot3(x, y, z, x, y, z), rsq = r * r;
                 float v, md, reach;
                 prim_eval<T>(E.lds + off + (en & 0xffu) * REC, x, y, z, r, rsq, v, md, reach);
-                if (act && neg(md - ext) && neg(v)) flags[src] = 1u;
+                const bool within = within_extent(md, nsq, r);  // (every lane: it holds a ballot)
+                if (act && within && neg(v)) flags[src] = 1u;
             }
             first += (uint32_t) kPairEntries;
             if (first < total) wave_lds_sync();  // (the next fill overwrites the entries)
@@ -1792,10 +1815,13 @@ namespace vmv
         lds_u32 *mask_lane = list + 2 * kWave + 4 + lane;
         const lds_cptr items = uniform((lds_cptr) items_);
         const int fill = uniform(fill_), done = uniform(done_), k = uniform(k_), radii_offset = uniform(radii_offset_);
-        // spheres staged and spheres of the link run before (exact: see env_fine_packed)
-        const float inv_k = 1.0f / (float) k;
+        // spheres staged and spheres of the link run before (exact: see env_fine_packed).  The reciprocals are the bare
+        // instruction (1 ulp), not the division's dozen per call: a quotient (i + 0.5) / d taken with them, here and in
+        // pairs_list, stays 0.5 / d away from a whole number, and 1 ulp and the product's rounding move it by under
+        // i * 2^-22 / d with i < 2^12.
+        const float inv_k = __builtin_amdgcn_rcpf((float) k);
         const int S = uniform((int) (((float) fill + 0.5f) * inv_k)), s0 = uniform((int) (((float) done + 0.5f) * inv_k));
-        const float inv_S = 1.0f / (float) S;
+        const float inv_S = __builtin_amdgcn_rcpf((float) S);
         const bool passed = rank_ >= 0;
         uint32_t cw[kMaskWords];
 #pragma unroll
