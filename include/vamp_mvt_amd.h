@@ -163,6 +163,16 @@ int vmv_validate_batch(int robot, const vmv_env *env, const float *d_q, size_t n
  * into words already written.  vmv_validate_batch == _env then _self on the same stream. */
 int vmv_validate_batch_env(int robot, const vmv_env *env, const float *d_q, size_t n, uint64_t *d_bits, void *stream);
 int vmv_validate_batch_self(int robot, const float *d_q, size_t n, uint64_t *d_bits, void *stream);
+/* Probes of the self-collision kernel's first round ("Gate screen"), for tests and measurement.
+ * vmv_self_screen_flags: bit i of d_words (ceil(n / 64) words, every one written, bits at and beyond n zero) = the screen
+ * flags configuration i, whatever its validity: mode 0 the exact screen (the gates' own arithmetic), mode 1 the default
+ * screen on the hardware's sine and cosine, which flags a superset.  Robots without a screen answer with the exact gates
+ * for both modes.  n < 2^31, else VMV_ERR_INVALID_ARGUMENT.
+ * vmv_bare_trig_error: over every fp32 value whose bit pattern lies in [lo_bits, hi_bits] (positive, finite) and its
+ * negative, out2[0] = max |hardware sine - the reference's sine|, out2[1] = the same for the cosines, as the kernels
+ * compute the four.  out2 is a HOST array; the call waits for its kernels. */
+int vmv_self_screen_flags(int robot, const float *d_q, size_t n, int mode, uint64_t *d_words, void *stream);
+int vmv_bare_trig_error(uint32_t lo_bits, uint32_t hi_bits, float *out2, void *stream);
 /* Many environments in one call: configurations [offsets[k], offsets[k+1]) against envs[k]; offsets: host array of
  * n_envs + 1, offsets[0] == 0, non-decreasing, offsets[n_envs] == n.  Bit i of d_bits = configuration i is collision
  * free (flat layout: the same words as concatenating one vmv_validate_batch per environment, and the same bits).  Empty

@@ -121,23 +121,156 @@ class Emitter:
         return f"{self.prefix}{v}" if kind == "op" else flit(v)
 
 
+class FmaEmitter(Emitter):
+    """The walk of fkcc_self_prescreen: sin and cos are the bare hardware ones, and a product that feeds an add or a
+    subtraction is folded into it with an explicit __builtin_fmaf (the translation unit keeps -ffp-contract=off, so
+    nothing else contracts).  A product is written out on its own only where something else reads it.  tape_error counts
+    one rounding for the product and one for the sum, so its bound covers either form."""
+
+    def __init__(self, m, qname="q", prefix="f", indent="        "):
+        super().__init__(m, qname, prefix, indent)
+        self.product = {}  # op index -> (factor, factor) of a mul / cmul not written out (yet)
+
+    def _name(self, i):
+        """the value of op i as an operand: a product still folded away is written out first"""
+        if i in self.product:
+            x, y = self.product.pop(i)
+            self.lines.append(f"{self.indent}const float {self.prefix}{i} = {x} * {y};")
+        return f"{self.prefix}{i}"
+
+    def need(self, spheres):
+        want = self.closure(spheres)
+        t = self.prefix
+        for i in sorted(want):
+            if self.done[i]:
+                continue
+            self.done[i] = True
+            op, a, b = self.ops[i]
+            if op == "mul":
+                self.product[i] = (self._name(a), self._name(b))
+                continue
+            if op == "cmul":
+                self.product[i] = (flit(a), self._name(b))
+                continue
+            if op in ("add", "sub", "cadd"):
+                neg = "-" if op == "sub" else ""
+                if b in self.product and (op == "cadd" or a != b):  # a +- x * y  (cadd: the constant a)
+                    x, y = self.product.pop(b)
+                    c = flit(a) if op == "cadd" else self._name(a)
+                    expr = f"__builtin_fmaf({neg}{x}, {y}, {c})"
+                elif op != "cadd" and a in self.product and a != b:  # x * y +- b
+                    x, y = self.product.pop(a)
+                    expr = f"__builtin_fmaf({x}, {y}, {neg}{self._name(b)})"
+                else:
+                    c = flit(a) if op == "cadd" else self._name(a)
+                    expr = f"{c} {'-' if op == 'sub' else '+'} {self._name(b)}"
+            elif op in ("sin", "cos", "neg"):
+                self._name(a)
+                expr = op_expr(op, a, b, sin="vmv::bare_sin", cos="vmv::bare_cos", qname=self.qname, prefix=t)
+            else:
+                expr = op_expr(op, a, b, qname=self.qname, prefix=t)
+            self.lines.append(f"{self.indent}const float {t}{i} = {expr};")
+        for s in spheres:  # the centres themselves are read by name
+            for kind, v in self.m["outputs"][s]:
+                if kind == "op":
+                    self._name(v)
+
+
 def f32(x):
     return np.float32(x)
 
 
-def eval_tape(m, q, batch=4096):
+# fkcc_self_prescreen (emit_robot): the screen of the self-collision half on the hardware's sine and cosine.
+# BARE_TRIG_EPS bounds |vmv::bare_sin(x) - vmv::vsin(x)| and |vmv::bare_cos(x) - vmv::vcos(x)| for |x| <= Q_MAX: twice the
+# maximum measured over every fp32 value of that domain (vmv_bare_trig_error; tests/test_self_prescreen_gpu.py writes the
+# measurement to profiles/r33_bare_trig_error.txt: 4.41e-6 and 4.47e-6), rounded up to one significant digit.
+BARE_TRIG_EPS = 9e-6
+# the domain of that bound: 4 pi.  Every joint bound of a screened robot, +- pi / 2, lies inside it (asserted where the
+# prescreen is emitted); a configuration with a joint outside it is flagged without a look at its trigonometry.
+Q_MAX = float(np.float32(4.0 * np.pi))
+assert Q_MAX >= 4.0 * np.pi
+FP32_U = 2.0 ** -24  # one rounding to nearest, relative
+
+
+def tape_error(m):
+    """Running-error evaluation of the op tape: per op (magnitude bound, error bound), in float64.  The error is that of
+    the prescreen's fp32 value (bare sin / cos, products contracted or not) against the exact screen's fp32 value
+    (vsin / vcos, no contraction), for any configuration with every |q_j| <= Q_MAX.  Magnitudes are bounds over that
+    whole domain, not samples: |sin|, |cos| <= 1 + BARE_TRIG_EPS, constants are exact.  Every fp32 operation adds one
+    rounding of its magnitude bound on either side.  -> (list of (M, E) per op, {sphere: E_c}), E_c the Euclidean norm
+    of the three coordinates' error bounds."""
+    u2 = 2.0 * FP32_U
+    out = []
+    for op, a, b in m["ops"]:
+        if op == "in":
+            M, E = Q_MAX, 0.0
+        elif op in ("sin", "cos"):
+            assert m["ops"][a][0] == "in", "the trigonometry is taken of the joints themselves (BARE_TRIG_EPS's domain)"
+            M, E = 1.0 + BARE_TRIG_EPS, BARE_TRIG_EPS
+        elif op == "neg":
+            M, E = out[a]
+        elif op == "const":
+            M, E = abs(float(f32(a))), 0.0
+        elif op == "mul":
+            (Ma, Ea), (Mb, Eb) = out[a], out[b]
+            M = Ma * Mb * (1.0 + FP32_U)
+            E = Ma * Eb + Mb * Ea + Ea * Eb + u2 * M
+        elif op in ("add", "sub"):
+            (Ma, Ea), (Mb, Eb) = out[a], out[b]
+            M = (Ma + Mb) * (1.0 + FP32_U)
+            E = Ea + Eb + u2 * M
+        elif op == "cmul":
+            c, (Mb, Eb) = abs(float(f32(a))), out[b]
+            M = c * Mb * (1.0 + FP32_U)
+            E = c * Eb + u2 * M
+        elif op == "cadd":
+            c, (Mb, Eb) = abs(float(f32(a))), out[b]
+            M = (c + Mb) * (1.0 + FP32_U)
+            E = Eb + u2 * M
+        else:
+            raise ValueError(op)
+        out.append((M, E))
+    centre = {}
+    for s, o in enumerate(m["outputs"]):
+        centre[s] = float(np.sqrt(sum(out[v][1] ** 2 for kind, v in o if kind == "op")))
+    return out, centre
+
+
+def prescreen_margin(m, sg, centre_err):
+    """(rs_g, delta_g, thr'_g) of one self-collision group's gate in fkcc_self_prescreen.  rs_g: the f32 sum of the two
+    bounding radii, as gate_term forms it.  delta_g = 2 * (E_A + E_B + the roundings of sql2_3 and of the two thresholds
+    at that distance), never below SELF_MARGIN.  thr'_g = (rs_g + delta_g)^2 rounded up to fp32.
+    Why that suffices: the exact gate fires where fl(d_e^2) < fl(rs^2); sql2_3 is three differences, three products and
+    two sums, so fl(d^2) = d^2 (1 + t), |t| < 8 u, and fl(rs^2) <= rs^2 (1 + u): d_e < rs (1 + 5 u).  The prescreen's
+    centres lie within E_A and E_B of the exact ones, so d_f < rs (1 + 5 u) + E_A + E_B and fl(d_f^2) <= d_f^2 (1 + 8 u)
+    < (rs + E_A + E_B + 16 u (rs + E_A + E_B))^2 <= thr'."""
+    env_bound = {g["link"]: g["bound"] for g in m["env_groups"]}
+    ba, bb = sg["bound_a"], env_bound[sg["b"]]
+    rs = float(f32(f32(m["radii"][ba]) + f32(m["radii"][bb])))
+    e = centre_err[ba] + centre_err[bb]
+    delta = max(2.0 * (e + 16.0 * FP32_U * (rs + e)), SELF_MARGIN)
+    t = (rs + delta) ** 2
+    thr = f32(t)
+    if float(thr) < t:
+        thr = np.nextafter(thr, f32(np.inf))
+    return rs, delta, float(thr)
+
+
+def eval_tape(m, q, batch=4096, trig_offset=None):
     """float64 evaluation of the model's op tape for configurations q[N][dim] -> sphere centres [N][n_total][3]
-    (code-shape statistics and the clearance tables; the device code evaluates the tape itself)."""
+    (code-shape statistics and the clearance tables; the device code evaluates the tape itself).
+    trig_offset: {op index: value or [N] array} added to the result of that sin / cos op (the tests of tape_error)."""
     if q.shape[0] > batch:  # keep the intermediates in cache
+        assert trig_offset is None
         return np.concatenate([eval_tape(m, q[i:i + batch], batch) for i in range(0, q.shape[0], batch)])
     vals = [None] * len(m["ops"])
     for i, (op, a, b) in enumerate(m["ops"]):
         if op == "in":
             v = q[:, a]
         elif op == "sin":
-            v = np.sin(vals[a])
+            v = np.sin(vals[a]) + (trig_offset.get(i, 0.0) if trig_offset else 0.0)
         elif op == "cos":
-            v = np.cos(vals[a])
+            v = np.cos(vals[a]) + (trig_offset.get(i, 0.0) if trig_offset else 0.0)
         elif op == "neg":
             v = -vals[a]
         elif op == "mul":
@@ -1516,6 +1649,41 @@ def emit_robot(m):
     L.append("        return any;")
     L.append("    }")
     L.append("")
+    if screen:
+        # ---- the same screen on the hardware's sine and cosine: a superset of the exact screen's flags ------------
+        for lo_j, sp_j in zip(m["lower"], m["span"]):
+            assert max(abs(lo_j), abs(lo_j + sp_j)) + np.pi / 2 <= Q_MAX, "a joint bound +- pi / 2 outside Q_MAX"
+        _, centre_err = tape_error(m)
+        L.append("    // fkcc_self_screen on bare trigonometry: the same walk, groups, table loads and table bits, with the FK of the")
+        L.append("    // bounding centres on vmv::bare_sin / bare_cos and explicit fused multiply-adds, and every gate's threshold")
+        L.append("    // widened from rs^2 to thr' = (rs + delta)^2, rounded up.  delta is twice what the centres' computed error bounds")
+        L.append("    // (tools/gen_hip.py: tape_error, from BARE_TRIG_EPS and one fp32 rounding per operation on either side) and the")
+        L.append(f"    // gate's own roundings add up to, never below {SELF_MARGIN} m (prescreen_margin): wherever a gate of fkcc_self_screen")
+        L.append("    // fires, the same gate fires here.  A configuration with a joint outside |q| <= Q_MAX (NaN and +-inf too) is")
+        L.append("    // flagged without a look at its trigonometry: BARE_TRIG_EPS is a bound inside that domain only.  No LDS.")
+        L.append(f"    // BARE_TRIG_EPS = {BARE_TRIG_EPS!r}, Q_MAX = {Q_MAX!r}")
+        L.append("    __device__ __forceinline__ bool fkcc_self_prescreen(const float (&q)[kDim])")
+        L.append("    {")
+        L.extend(table_loads)
+        em = FmaEmitter(m, prefix="f", indent="        ")
+        em.lines.append("        bool any = false;")
+        for j in range(dim):
+            em.lines.append(f"        any |= !(__builtin_fabsf(q[{j}]) <= {flit(Q_MAX)});  // Q_MAX (false for NaN too)")
+        for ln in links:
+            for sg in self_by_b.get(ln, []):
+                ba, bb = sg["bound_a"], env_by_link[ln]["bound"]
+                em.need([ba, bb])
+                rs, delta, thr = prescreen_margin(m, sg, centre_err)
+                exact = gate_term(em, sg)
+                head, tail = exact.rsplit(" - ", 1)
+                tbit = tail[tail.index(")") + 1:]
+                assert float.fromhex(tail[:tail.index(")")].rstrip("f")) == float(f32(f32(rs) * f32(rs))) <= thr
+                em.lines.append(f"        any |= {head} - {flit(thr)}){tbit};  // {sg['a']} vs. {ln}: rs = {rs!r}, "
+                                f"delta = {delta!r} (E_A = {centre_err[ba]!r}, E_B = {centre_err[bb]!r}; BARE_TRIG_EPS = {BARE_TRIG_EPS!r})")
+        L += em.lines
+        L.append("        return any;")
+        L.append("    }")
+        L.append("")
 
     # ---- both halves in one walk of the chain (one FK per configuration) -------------------------------------------
     # Only for robots whose self-collision half needs a single pass (all A-side spheres fit the registers).
@@ -1728,6 +1896,13 @@ def emit_robot(m):
     L.append("    static __device__ __forceinline__ bool fkcc_self_screen(const float (&q)[kDim])")
     L.append("    {")
     L.append(f"        return {n}::fkcc_self_screen(q);")
+    L.append("    }")
+    L.append("    static __device__ __forceinline__ bool fkcc_self_prescreen(const float (&q)[kDim])")
+    L.append("    {")
+    if any_gate_rate < SELF_SCREEN_MAX_RATE:
+        L.append(f"        return {n}::fkcc_self_prescreen(q);")
+    else:
+        L.append(f"        return {n}::fkcc_self_screen(q);  // (no kSelfScreen: the robot has the exact screen only, and launches neither)")
     L.append("    }")
     L.append("    static __device__ __forceinline__ void sphere_fk(const float (&q)[kDim], float4 *out)")
     L.append("    {")

@@ -199,6 +199,8 @@ def _load():
         "vmv_validate_batch": (I, [I, V, V, S, V, V]),
         "vmv_validate_batch_env": (I, [I, V, V, S, V, V]),
         "vmv_validate_batch_self": (I, [I, V, S, V, V]),
+        "vmv_self_screen_flags": (I, [I, V, S, I, V, V]),
+        "vmv_bare_trig_error": (I, [ctypes.c_uint32, ctypes.c_uint32, c_float_p, V]),
         "vmv_validate_motion_batch": (I, [I, V, V, V, S, V, V]),
         "vmv_fk_batch_host": (I, [I, c_float_p, S, c_float_p]),
         "vmv_eefk_batch": (I, [I, V, S, V, V]),

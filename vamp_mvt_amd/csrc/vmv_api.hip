@@ -191,6 +191,48 @@ namespace vmv
         q[i] = lower[j] + span[j] * u;
     }
 
+    // vmv_bare_trig_error: the workgroups stride over the fp32 bit patterns lo .. hi (positive floats) and take each with
+    // both signs; per lane the maxima of |bare_sin - vsin| and |bare_cos - vcos| (a NaN difference wins and stays),
+    // reduced over the wave by shuffles, over the workgroup through LDS, and stored as partial[2 * block + {0, 1}];
+    // trig_error_final_kernel (one workgroup) folds the `blocks` partials into out[0..1].
+    constexpr uint32_t kTrigBlocks = 2048;
+    __device__ __forceinline__ float nan_max(float m, float d) { return (d > m || d != d) ? d : m; }
+    __device__ __forceinline__ void trig_block_max(float &ms, float &mc, float (&part)[2][kBlock / kWave])
+    {
+        for (int o = kWave / 2; o > 0; o /= 2)
+        {
+            ms = nan_max(ms, __shfl_xor(ms, o));
+            mc = nan_max(mc, __shfl_xor(mc, o));
+        }
+        if (threadIdx.x % kWave == 0) part[0][threadIdx.x / kWave] = ms, part[1][threadIdx.x / kWave] = mc;
+        __syncthreads();
+        for (int w = 0; w < kBlock / kWave; ++w) ms = nan_max(ms, part[0][w]), mc = nan_max(mc, part[1][w]);
+    }
+    __global__ __launch_bounds__(kBlock) void trig_error_kernel(const uint32_t lo, const uint32_t hi, float *__restrict__ partial)
+    {
+        __shared__ float part[2][kBlock / kWave];
+        float ms = 0.0f, mc = 0.0f;
+        for (uint64_t b = (uint64_t) lo + blockIdx.x * (uint64_t) kBlock + threadIdx.x; b <= (uint64_t) hi;
+             b += (uint64_t) gridDim.x * kBlock)
+            for (uint32_t sign = 0u; sign < 2u; ++sign)
+            {
+                const float x = u2f((uint32_t) b | sign << 31);
+                ms = nan_max(ms, vabs(bare_sin(x) - vsin(x)));
+                mc = nan_max(mc, vabs(bare_cos(x) - vcos(x)));
+            }
+        trig_block_max(ms, mc, part);
+        if (threadIdx.x == 0) partial[2 * blockIdx.x] = ms, partial[2 * blockIdx.x + 1] = mc;
+    }
+    __global__ __launch_bounds__(kBlock) void trig_error_final_kernel(const float *__restrict__ partial, const uint32_t blocks,
+                                                                       float *__restrict__ out)
+    {
+        __shared__ float part[2][kBlock / kWave];
+        float ms = 0.0f, mc = 0.0f;
+        for (uint32_t i = threadIdx.x; i < blocks; i += kBlock) ms = nan_max(ms, partial[2 * i]), mc = nan_max(mc, partial[2 * i + 1]);
+        trig_block_max(ms, mc, part);
+        if (threadIdx.x == 0) out[0] = ms, out[1] = mc;
+    }
+
     // Halton sample (skip + 1 + row) of the reference's sequence, element j (halton_element, vmv_common.h)
     __global__ void halton_kernel(float *q, size_t total, int dim, uint64_t skip, const float *lower, const float *span)
     {
@@ -1708,6 +1750,36 @@ extern "C"
         if (!d_q || !d_bits) return VMV_ERR_INVALID_ARGUMENT;
         if (n == 0) return VMV_OK;
         return robot_launchers(robot).validate(vmv::EnvLaunch{}, d_q, n, d_bits, static_cast<hipStream_t>(stream), 2);
+    }
+
+    int vmv_self_screen_flags(int robot, const float *d_q, size_t n, int mode, uint64_t *d_words, void *stream)
+    {
+        if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
+        if (!d_q || !d_words || (mode != 0 && mode != 1) || n >= (size_t{1} << 31)) return VMV_ERR_INVALID_ARGUMENT;
+        if (n == 0) return VMV_OK;
+        return robot_launchers(robot).self_screen_flags(d_q, n, mode, d_words, static_cast<hipStream_t>(stream));
+    }
+
+    int vmv_bare_trig_error(uint32_t lo_bits, uint32_t hi_bits, float *out2, void *stream)
+    {
+        // positive, finite, ordered: the bit patterns of positive floats are ordered as the floats are
+        if (!out2 || lo_bits > hi_bits || hi_bits >= 0x7f800000u) return VMV_ERR_INVALID_ARGUMENT;
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        const uint64_t count = (uint64_t) hi_bits - lo_bits + 1u;
+        const uint32_t blocks = (uint32_t) std::min<uint64_t>((count + vmv::kBlock - 1) / vmv::kBlock, vmv::kTrigBlocks);
+        float *d = nullptr;  // [2 * blocks] partials, then the two results
+        VMV_HIP(hipMalloc((void **) &d, (2 * (size_t) blocks + 2) * sizeof(float)));
+        const int rc = [&]() -> int
+        {
+            hipLaunchKernelGGL(vmv::trig_error_kernel, dim3(blocks), dim3(vmv::kBlock), 0, s, lo_bits, hi_bits, d);
+            hipLaunchKernelGGL(vmv::trig_error_final_kernel, dim3(1), dim3(vmv::kBlock), 0, s, (const float *) d, blocks, d + 2 * (size_t) blocks);
+            VMV_HIP(hipGetLastError());
+            VMV_HIP(hipMemcpyAsync(out2, d + 2 * (size_t) blocks, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+            VMV_HIP(hipStreamSynchronize(s));
+            return VMV_OK;
+        }();
+        (void) hipFree(d);
+        return rc;
     }
 
     int vmv_validate_motion_batch(int robot, const vmv_env *env, const float *d_a, const float *d_b, size_t n,

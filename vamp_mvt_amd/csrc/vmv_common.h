@@ -222,6 +222,9 @@ namespace vmv
         // record (P.shared) or record rec_of[a].  d_ok [rows]: constraint_edge_kernel's answer for the pair, bit for bit.
         int (*retime_band)(const ConstraintParams &, const ConstraintDev *d_cons, const uint32_t *d_rec_of, const uint32_t *d_sample_lo,
                            uint32_t n_paths, const float *d_pos, uint32_t rows, uint8_t *d_ok, hipStream_t);
+        // vmv_self_screen_flags: bit i of d_words [ceil(n / 64)] = the self-collision screen flags row i; mode 0 the exact
+        // screen, 1 the prescreen (robots without either: the exact gates both times); n below 2^31
+        int (*self_screen_flags)(const float *d_q, size_t n, int mode, uint64_t *d_words, hipStream_t);
     };
 
     extern const RobotLaunchers kPandaLaunchers, kUr5Launchers, kFetchLaunchers, kBaxterLaunchers;

@@ -93,6 +93,13 @@ namespace vmv
         return vsin(v_sq - sub);
     }
 
+    // The hardware's sine and cosine (v_sin_f32 / v_cos_f32: input in revolutions, valid over +-256), for the one place
+    // whose result does not depend on their last bits: the generated fkcc_self_prescreen, whose gates carry a margin
+    // computed from BARE_TRIG_EPS (tools/gen_hip.py), the measured bound of |bare_sin - vsin| and |bare_cos - vcos| over
+    // |x| <= Q_MAX.  Outside that domain the prescreen does not look at them.  1/2pi is an inline constant of the ISA.
+    __device__ __forceinline__ float bare_sin(float x) { return __builtin_amdgcn_sinf(x * 0.15915494f); }
+    __device__ __forceinline__ float bare_cos(float x) { return __builtin_amdgcn_cosf(x * 0.15915494f); }
+
     // ------------------------------------------------------------------------
     // wave / rake-group helpers.  G = 1: every lane is its own rake (one configuration replicated over
     // the reference's 8 lanes).  G = 8: lanes 8k..8k+7 form one reference rake (planning/validate.hh).

@@ -20,15 +20,19 @@
         // the order the code objects have always had, so that the tables below can stand in class order.  Nothing reads it.
         template <class... K>
         constexpr int named(K *...) { return 0; }
+        // the self-collision kernel's instances: [VMV_SELF_SCREEN] 0 no screen, 1 (and unset) the prescreen, 2 the exact
+        // screen; robots without R::kSelfScreen have the unscreened instance only
+        constexpr int self_default() { return R::kSelfScreen ? kSelfPrescreen : kSelfUnscreened; }
+        constexpr int self_exact() { return R::kSelfScreen ? kSelfExactScreen : kSelfUnscreened; }
         [[maybe_unused]] constexpr int kVariantKernelOrder = named(
             validate_env_kernel<kEnvClouds>, validate_env_kernel<kEnvFull>, validate_env_kernel<kEnvZOnly>,
             validate_env_kernel<kEnvPrims>, validate_env_kernel<kEnvZOnly, R::kFinePairs>,
-            validate_env_kernel<kEnvPrims, R::kFinePairs>, validate_self_kernel<R::kSelfScreen>, validate_self_kernel<false>,
+            validate_env_kernel<kEnvPrims, R::kFinePairs>, validate_self_kernel<self_default()>, validate_self_kernel<kSelfUnscreened>,
             validate_env_multi_kernel<kEnvZOnly, R::kFinePairs>, validate_env_multi_kernel<kEnvPrims, R::kFinePairs>,
             validate_env_multi_kernel<kEnvZOnly>, validate_env_multi_kernel<kEnvPrims>, validate_env_multi_kernel<kEnvFull>,
             validate_env_multi_kernel<kEnvClouds>, rake_tasks_env_kernel<kEnvClouds>, rake_tasks_env_kernel<kEnvFull>,
             rake_tasks_env_kernel<kEnvZOnly>, rake_tasks_env_kernel<kEnvPrims>, rake_tasks_fused_kernel<kEnvZOnly>,
-            rake_tasks_fused_kernel<kEnvPrims>);
+            rake_tasks_fused_kernel<kEnvPrims>, validate_self_kernel<self_exact()>);
 
         // LDS of the environment kernels: [primitive block | CAPT split planes | hit flags, radius table | one slab per
         // wave | control words]; of the clearance kernels the same head without planes.  The float offset of wave 0's slab:
@@ -184,7 +188,7 @@
                 static const size_t resident = []
                 {
                     int per_cu = 0, dev = 0, cus = 256;
-                    const void *k = (const void *) validate_self_kernel<R::kSelfScreen>;
+                    const void *k = (const void *) validate_self_kernel<self_default()>;
                     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0) != hipSuccess || per_cu < 1)
                         per_cu = R::kSelfBlocks;
                     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -195,9 +199,12 @@
                 uint32_t group = (uint32_t) ((words + resident - 1) / resident);
                 if (const char *e = getenv("VMV_SELF_GROUP")) group = (uint32_t) strtoul(e, nullptr, 10);
                 group = group < 1u ? 1u : (group > 8u ? 8u : group);
-                auto self_kernel = validate_self_kernel<R::kSelfScreen>;
-                if (const char *e = getenv("VMV_SELF_SCREEN"))  // "0": the unscreened instance (measurement and test aid)
-                    if (strtoul(e, nullptr, 10) == 0ul) self_kernel = validate_self_kernel<false>;
+                // [VMV_SELF_SCREEN]; every other value, and the variable unset: the default (measurement and test aid)
+                static constexpr decltype(&validate_self_kernel<kSelfUnscreened>) self_kernels[3] = {
+                    validate_self_kernel<kSelfUnscreened>, validate_self_kernel<self_default()>, validate_self_kernel<self_exact()>};
+                auto self_kernel = self_kernels[1];
+                if (const char *e = getenv("VMV_SELF_SCREEN"))
+                    if (const unsigned long mode = strtoul(e, nullptr, 10); mode == 0ul || mode == 2ul) self_kernel = self_kernels[mode];
                 int rc = VMV_OK;  // (of the stamps: measurement builds only)
                 for_slices(n, kSlice, [&](size_t lo, uint32_t m)
                            {
@@ -582,6 +589,13 @@
                                reinterpret_cast<const float4 *>(d_spheres), n, d_pair_words, (uint32_t) ((R::kNSelfPairs + 31) / 32));
         }
 
+        // vmv_self_screen_flags: n below 2^31
+        int launch_self_screen_flags(const float *d_q, size_t n, int mode, uint64_t *d_words, hipStream_t stream)
+        {
+            const auto kernel = mode == 0 ? self_screen_flags_kernel<true> : self_screen_flags_kernel<false>;
+            return launch_flat(kernel, (n + kBlock - 1) / kBlock, kBlock, stream, d_q, (uint32_t) n, d_words);
+        }
+
         int launch_eefk(const float *d_q, size_t n, float *d_out, hipStream_t stream)
         {
             return launch_flat(eefk_batch_kernel, (n + kBlock - 1) / kBlock, kBlock, stream, d_q, n, d_out);
@@ -787,6 +801,7 @@
             L.simplify_band_round = launch_simplify_band_round;
             L.opt_band = launch_opt_band;
             L.retime_band = launch_retime_band;
+            L.self_screen_flags = launch_self_screen_flags;
             return L;
         }
     }  // namespace

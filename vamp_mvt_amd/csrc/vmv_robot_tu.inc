@@ -417,15 +417,27 @@ namespace VMV_ROBOT_NS
     // words themselves (no list in memory, no device-scope atomics: the words are edited in LDS and stored once).  The
     // launcher picks `group` so that the grid is one round of resident workgroups.
     //
-    // SCREEN (robots with R::kSelfScreen; VMV_SELF_SCREEN=0 selects the other instance: measurement and test aid): a share
-    // runs two rounds of passes.  The first runs R::fkcc_self_screen - table bits, the FK of the bounding centres, every
-    // group's gate - on the valid configurations and collects the flagged ones in flag words (LDS atomicOr); one wave then
-    // makes the flag words the enumeration, and the second round runs fkcc_self on the flagged configurations alone, packed
-    // 64 to a pass.  An unflagged configuration has every gate of fkcc_self false, so fkcc_self would have returned `skip`
-    // for it: the words are the same.  The flag words lie in wave 0's slab, which no wave touches before the second round.
-    // The second round deals the flagged configurations evenly over the workgroup's waves (at most 64 per pass).
+    // SCREEN != kSelfUnscreened (robots with R::kSelfScreen): a share runs two rounds of passes.  The first runs a screen -
+    // table bits, the FK of the bounding centres, every group's gate - on the valid configurations and collects the
+    // flagged ones in flag words (LDS atomicOr); one wave then makes the flag words the enumeration, and the second round
+    // runs fkcc_self on the flagged configurations alone, packed 64 to a pass.  An unflagged configuration has every gate
+    // of fkcc_self false, so fkcc_self would have returned `skip` for it: the words are the same.  The flag words lie in
+    // wave 0's slab, which no wave touches before the second round.  The second round deals the flagged configurations
+    // evenly over the workgroup's waves (at most 64 per pass).
+    // The screen of kSelfExactScreen is R::fkcc_self_screen, the gates' own arithmetic.  That of kSelfPrescreen, the
+    // default, is R::fkcc_self_prescreen: the hardware's sine and cosine, fused multiply-adds, and thresholds widened by a
+    // margin the generator computes from the measured error of those instructions, so that it flags a superset of what the
+    // exact screen flags (and every configuration with a joint outside |q| <= Q_MAX).  Which configurations run fkcc_self
+    // changes, what fkcc_self answers does not.  VMV_SELF_SCREEN = 2 / 0 selects the exact screen / no screen
+    // (measurement and test aid).
+    enum SelfScreenMode : int
+    {
+        kSelfUnscreened = 0,
+        kSelfPrescreen = 1,
+        kSelfExactScreen = 2
+    };
     static_assert(kSelfShareWords == (uint32_t) kWavesPerBlock * 8u, "a share holds group <= 8 words per wave");
-    template <bool SCREEN>
+    template <int SCREEN>
     __global__ __launch_bounds__(kBlock, R::kSelfBlocks) void validate_self_kernel(const float *__restrict__ q, const uint32_t n,
                                                                     uint64_t *__restrict__ bits, const uint32_t group)
     {
@@ -436,7 +448,7 @@ namespace VMV_ROBOT_NS
         const uint32_t wave = uniform(threadIdx.x / kWave);
         lds_ptr wave_slab = (lds_ptr) stage + kSelfRadiiFloats + wave * self_slab_floats();
         static_assert(kSelfRadiiFloats % 2u == 0u && self_slab_floats() >= 2u * kSelfShareWords, "the flag words fit a slab");
-        unsigned long long *const flag = (unsigned long long *) (stage + kSelfRadiiFloats);  // [kSelfShareWords], SCREEN only
+        unsigned long long *const flag = (unsigned long long *) (stage + kSelfRadiiFloats);  // [kSelfShareWords], screened instances only
         const uint32_t words = (n + (uint32_t) kWave - 1u) / (uint32_t) kWave;
         const uint32_t share = group * (uint32_t) kWavesPerBlock;  // <= kSelfShareWords (the launcher clamps group)
         const uint32_t tail = n % (uint32_t) kWave;
@@ -448,12 +460,12 @@ namespace VMV_ROBOT_NS
             if (wave == 0u)
             {
                 self_share_load(S, bits, w0, nw, words - 1u, tail, opaque_lane_id());
-                if (SCREEN && opaque_lane_id() < kSelfShareWords) flag[opaque_lane_id()] = 0ull;
+                if (SCREEN != kSelfUnscreened && opaque_lane_id() < kSelfShareWords) flag[opaque_lane_id()] = 0ull;
             }
             __syncthreads();
             uint32_t total = uniform(S.before[nw]);
             uint32_t width = (uint32_t) kWave;  // configurations per pass of the (second) round
-            if constexpr (SCREEN)
+            if constexpr (SCREEN != kSelfUnscreened)
             {
                 for (;;)
                 {
@@ -464,7 +476,8 @@ namespace VMV_ROBOT_NS
                     float cfg[R::kDim];
 #pragma unroll
                     for (int d = 0; d < R::kDim; ++d) cfg[d] = q[(size_t) idx * R::kDim + d];
-                    if (R::fkcc_self_screen(cfg) && at != ~0u)
+                    const bool flagged = SCREEN == kSelfPrescreen ? R::fkcc_self_prescreen(cfg) : R::fkcc_self_screen(cfg);
+                    if (flagged && at != ~0u)
                         atomicOr(&flag[at / (uint32_t) kWave], 1ull << (at % (uint32_t) kWave));  // LDS atomic
                 }
                 __syncthreads();
@@ -482,7 +495,7 @@ namespace VMV_ROBOT_NS
                 if (pass >= total) break;  // wave-uniform: the share is used up
                 VMV_STAMP_PASS;
                 const uint32_t lane = opaque_lane_id();
-                const uint32_t at = (!SCREEN || lane < width) ? self_share_locate(S, nw, pass + lane, total) : ~0u;
+                const uint32_t at = (SCREEN == kSelfUnscreened || lane < width) ? self_share_locate(S, nw, pass + lane, total) : ~0u;
                 const uint32_t idx = w0 * (uint32_t) kWave + (at != ~0u ? at : 0u);  // (a valid bit always lies below n <= 2^31)
                 float cfg[R::kDim];
 #pragma unroll
@@ -496,6 +509,23 @@ namespace VMV_ROBOT_NS
             __syncthreads();  // (the next share rewrites the tables)
         }
         VMV_STAMP_END;
+    }
+
+    // vmv_self_screen_flags: bit i of the words = the exact screen (EXACT) or the prescreen flags row i; one lane per
+    // row, one word per wave, whatever the validity of the row (probe of the screens: tests/test_self_prescreen_gpu.py).
+    // The grid covers n; n >= 1.
+    template <bool EXACT>
+    __global__ __launch_bounds__(kBlock) void self_screen_flags_kernel(const float *__restrict__ q, const uint32_t n,
+                                                                        uint64_t *__restrict__ words)
+    {
+        const uint32_t i = blockIdx.x * (uint32_t) kBlock + threadIdx.x;
+        const uint32_t row = i < n ? i : 0u;
+        float cfg[R::kDim];
+#pragma unroll
+        for (int d = 0; d < R::kDim; ++d) cfg[d] = q[(size_t) row * R::kDim + d];
+        const bool flagged = EXACT ? R::fkcc_self_screen(cfg) : R::fkcc_self_prescreen(cfg);
+        const uint64_t word = __ballot(flagged && i < n);
+        if (__lane_id() == 0u && i < n) words[i / (uint32_t) kWave] = word;  // (lane 0 of a wave below n: word <= (n - 1) / 64)
     }
 
     // hsum + exact sqrt of a configuration-sized vector (vector/avx.hh:441-452, interface.hh:397-410)
