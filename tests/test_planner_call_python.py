@@ -1,10 +1,11 @@
-"""The Python side of the nine planner calls, characterised: what `<robot>.*_raw` and the `planning.*` functions above
+"""The Python side of the planner and path calls, characterised: what `<robot>.*_raw` and the `planning.*` functions above
 them refuse and with which words, which check wins where two apply, what an accepted call hands to the library, and
 what it makes of the library's answer.
 
 Table-driven: `_base` gives each wrapper's good arguments, REFUSALS / PLAN_REFUSALS the ways to spoil them, ACCEPTED the
 calls that go through.  The expectation of every (wrapper, case) is recorded in tests/golden/planner_call_python.json
-(`python tests/test_planner_call_python.py --record` rewrites it).  No case reaches the real library, so the test
+(`python tests/test_planner_call_python.py --record` rewrites it) and, for the constrained, cartesian and retime wrappers,
+in tests/golden/planner_call_python_paths.json next to it.  No case reaches the real library, so the test
 behaves the same with or without a device:
 
   * a refusal runs against a library that raises on any use; the record is the exception's type and words.  A spoiled
@@ -28,12 +29,15 @@ import numpy as np
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "planner_call_python.json")
+GOLDEN_PATHS = GOLDEN[:-5] + "_paths.json"  # the constrained, cartesian and retime wrappers, characterised later
 DIM = 7  # panda
 N = 3    # problems or paths of a call
 GOAL_COUNTS = (1, 2, 1)
 PLANS_HANDLE, ROADMAPS_HANDLE = 0xBEEF, 0x77
 WRAPPERS = ("rrtc_multi_raw", "rrtc_multi_goals_raw", "aorrtc_multi_raw", "prm_multi_raw", "fcit_multi_raw",
-            "roadmaps_build_raw", "roadmaps_query_raw", "simplify_multi_raw", "optimize_multi_raw")
+            "roadmaps_build_raw", "roadmaps_query_raw", "simplify_multi_raw", "optimize_multi_raw",
+            "rrtc_multi_constrained_raw", "simplify_multi_constrained_raw", "optimize_multi_constrained_raw",
+            "cartesian_multi_raw", "retime_multi_raw", "retime_multi_constrained_raw")
 # per wrapper: the symbols an accepted call goes through, the entry first (prm: with keep_roadmaps)
 SYMBOLS = {
     "rrtc_multi_raw": ("vmv_rrtc_multi", "vmv_plans_summary", "vmv_plans_paths"),
@@ -46,13 +50,27 @@ SYMBOLS = {
     "roadmaps_query_raw": ("vmv_roadmaps_query", "vmv_plans_summary", "vmv_plans_paths", "vmv_plans_query_summary"),
     "simplify_multi_raw": ("vmv_simplify_multi", "vmv_paths_summary", "vmv_paths_points"),
     "optimize_multi_raw": ("vmv_optimize_multi", "vmv_optimized_summary", "vmv_optimized_points"),
+    "rrtc_multi_constrained_raw": ("vmv_rrtc_multi_constrained", "vmv_plans_summary", "vmv_plans_paths", "vmv_plans_goal_indices",
+                                   "vmv_plans_band_refused"),
+    "simplify_multi_constrained_raw": ("vmv_simplify_multi_constrained", "vmv_paths_summary", "vmv_paths_points",
+                                       "vmv_paths_band_refused"),
+    "optimize_multi_constrained_raw": ("vmv_optimize_multi_constrained", "vmv_optimized_held", "vmv_optimized_summary",
+                                       "vmv_optimized_points"),
+    "cartesian_multi_raw": ("vmv_cartesian_multi", "vmv_cartesian_summary", "vmv_cartesian_points"),
+    "retime_multi_raw": ("vmv_retime_multi", "vmv_retime_summary", "vmv_retime_samples"),
+    "retime_multi_constrained_raw": ("vmv_retime_multi_constrained", "vmv_retime_summary", "vmv_retime_levels", "vmv_retime_samples"),
 }
 DESTROY = {w: "vmv_plans_destroy" for w in WRAPPERS}
-DESTROY.update(roadmaps_build_raw=None, simplify_multi_raw="vmv_paths_destroy", optimize_multi_raw="vmv_optimized_destroy")
+DESTROY.update(roadmaps_build_raw=None, simplify_multi_raw="vmv_paths_destroy", optimize_multi_raw="vmv_optimized_destroy",
+               simplify_multi_constrained_raw="vmv_paths_destroy", optimize_multi_constrained_raw="vmv_optimized_destroy",
+               cartesian_multi_raw="vmv_cartesian_destroy", retime_multi_raw="vmv_retime_destroy",
+               retime_multi_constrained_raw="vmv_retime_destroy")
 # the arguments of every entry symbol, by kind
 _PROBLEMS = ("robot", "envs", "n", "starts", "goals", "skips", "settings", "handle")
 _SAMPLED = ("robot", "envs", "n", "starts", "goals", "skips", "samples", "settings", "handle")
 _PATHS = ("robot", "envs", "n", "points", "offsets", "settings", "handle")
+_BAND = ("constraints", "n_constraints", "constraint_settings", "handle")
+_TIMED = ("robot", "envs", "n", "points", "offsets", "vel", "acc")
 ENTRIES = {
     "vmv_rrtc_multi": _PROBLEMS,
     "vmv_rrtc_multi_goals": ("robot", "envs", "n", "starts", "packed_goals", "goal_offsets", "skips", "settings", "handle"),
@@ -63,6 +81,12 @@ ENTRIES = {
     "vmv_roadmaps_query": ("roadmaps", "n", "index", "starts", "goals", "settings", "handle"),
     "vmv_simplify_multi": _PATHS,
     "vmv_optimize_multi": _PATHS,
+    "vmv_rrtc_multi_constrained": ("robot", "envs", "n", "starts", "packed_goals", "goal_offsets", "skips", "settings") + _BAND,
+    "vmv_simplify_multi_constrained": _PATHS[:-1] + _BAND,
+    "vmv_optimize_multi_constrained": _PATHS[:-1] + _BAND,
+    "vmv_cartesian_multi": ("robot", "envs", "n", "starts", "targets", "settings", "handle"),
+    "vmv_retime_multi": _TIMED + ("settings", "handle"),
+    "vmv_retime_multi_constrained": _TIMED + ("constraints", "n_constraints", "settings", "constraint_settings", "handle"),
 }
 
 
@@ -128,15 +152,20 @@ class _Recorder:
         cs = a["settings"]._obj
         self.ns = int(getattr(cs, "n_samples", 0))
         offsets = next((a[k] for k in ("goal_offsets", "offsets") if a.get(k) is not None), None)
-        total = n if offsets is None else int(_get(offsets, n + 1)[-1])
+        total = self.total = n if offsets is None else int(_get(offsets, n + 1)[-1])
         counts = {"starts": n * DIM, "goals": n * DIM, "packed_goals": total * DIM, "points": total * DIM,
-                  "goal_offsets": n + 1, "offsets": n + 1, "skips": n, "index": n, "samples": n * self.ns * DIM}
+                  "goal_offsets": n + 1, "offsets": n + 1, "skips": n, "index": n, "samples": n * self.ns * DIM,
+                  "targets": n * 16, "vel": DIM, "acc": DIM}
         rec = {"symbol": name, "settings": [type(cs).__name__, bytes(cs).hex()]}
         for kind, v in a.items():
-            if kind in ("robot", "n"):
+            if kind in ("robot", "n", "n_constraints"):
                 rec[kind] = int(v)
             elif kind == "envs":
-                rec[kind] = {"array length": len(v), "handles": list(v)[:n]}
+                rec[kind] = None if v is None else {"array length": len(v), "handles": list(v)[:n]}
+            elif kind == "constraints":  # (the wrapper hands the ctypes array itself)
+                rec[kind] = None if v is None else {"array length": len(v), "bytes": bytes(v).hex()}
+            elif kind == "constraint_settings":
+                rec[kind] = None if v is None else [type(v._obj).__name__, bytes(v._obj).hex()]
             elif kind == "roadmaps":
                 rec[kind] = v.value
             elif kind == "handle":
@@ -223,6 +252,56 @@ class _Recorder:
     def _vmv_optimized_points(self, out, points, size):
         _put(points, np.arange(size) * 0.25)
 
+    def _vmv_plans_band_refused(self, plans, refused):
+        assert plans.value == PLANS_HANDLE
+        _put(refused, 40 + np.arange(self.n))
+
+    def _vmv_paths_band_refused(self, out, refused):
+        assert out.value == PLANS_HANDLE
+        _put(refused, 50 + np.arange(self.n))
+
+    def _vmv_optimized_held(self, out, held):
+        assert out.value == PLANS_HANDLE
+        _put(held, 60 + np.arange(self.n))
+
+    def _vmv_cartesian_summary(self, out, status, segments, achieved, evaluations, calls, questions):
+        assert out.value == PLANS_HANDLE
+        k = np.arange(self.n)
+        self.lengths = np.array([2, 0, 3])[k % 3] + 1  # achieved + 1 waypoints
+        _put(status, k % 7)
+        _put(segments, 4 * (k % 2))
+        _put(achieved, self.lengths - 1)
+        _put(evaluations, 70 + k)
+        calls._obj.value, questions._obj.value = 55, 66
+
+    def _vmv_cartesian_points(self, out, points, size):
+        assert size == int(self.lengths.sum()) * DIM
+        _put(points, np.arange(size) * 0.75)
+
+    def _vmv_retime_summary(self, out, status, intervals, samples, duration, first_invalid, calls, questions):
+        assert out.value == PLANS_HANDLE
+        k = np.arange(self.n)
+        self.lengths = np.array([2, 0, 3])[k % 3]
+        _put(status, k % 6)
+        _put(intervals, 80 + k)
+        _put(samples, self.lengths)
+        _put(duration, 1.5 + k)
+        _put(first_invalid, np.array([0xFFFFFFFF, 0, 1], np.uint32)[k % 3])
+        calls._obj.value, questions._obj.value = 77, 88
+
+    def _vmv_retime_levels(self, out, levels, rounds, repaired, stops):
+        k = np.arange(self.n)
+        _put(levels, np.arange(self.total) % 5)
+        _put(rounds, 1 + k)
+        _put(repaired, 2 * k)
+        _put(stops, k)
+
+    def _vmv_retime_samples(self, out, times, positions, velocities, accelerations, total):
+        assert total == int(self.lengths.sum())
+        _put(times, np.arange(total) * 0.01)
+        for scale, rows in ((0.5, positions), (0.25, velocities), (0.125, accelerations)):
+            _put(rows, np.arange(total * DIM) * scale)
+
 
 # ---------------------------------------------------------------------------------------------------------
 # arguments
@@ -258,7 +337,23 @@ def _base(vamp, wrapper, n):
         a["resolution"] = None
         a["settings"] = P.SimplifyMultiSettings(questions_per_round=4) if wrapper == "simplify_multi_raw" else \
             P.OptimizeMultiSettings()
+    elif wrapper == "rrtc_multi_constrained_raw":
+        a.update(_base(vamp, "rrtc_multi_goals_raw", n), constraints=_constraint(vamp), constraint_settings=None, max_stretch=2.0)
+    elif wrapper in ("simplify_multi_constrained_raw", "optimize_multi_constrained_raw"):
+        a.update(_base(vamp, wrapper.replace("_constrained", ""), n), constraints=_constraint(vamp), constraint_settings=None)
+    elif wrapper == "cartesian_multi_raw":
+        a["targets"] = (np.eye(4, dtype=np.float32)[None] + (np.arange(n * 16).reshape(n, 4, 4) * 0.001).astype(np.float32))
+        a["settings"] = P.CartesianSettings()
+    elif wrapper in ("retime_multi_raw", "retime_multi_constrained_raw"):
+        a["paths"] = [(np.arange(m * DIM).reshape(m, DIM) * 0.125).astype(np.float32) for m in (4, 0, 2)[:n]]
+        a["vel_limits"], a["acc_limits"] = np.full(DIM, 1.5, np.float32), np.arange(1, DIM + 1) * 0.5
+        a["settings"] = P.RetimeSettings() if wrapper == "retime_multi_raw" else P.RetimeConstrainedSettings()
+        a.update(constraints=None, constraint_settings=None)
     return a
+
+
+def _constraint(vamp, k=0):
+    return vamp.EEConstraint.box([-1.0, -1.0, 0.25 * k], [1.0, 1.0, 2.0], frame=np.eye(4))
 
 
 def _replaced(obj, path, value):
@@ -292,6 +387,17 @@ def _raw(vamp, w, a):
         return {"handle": handle.value, "the environments given": [e is g for e, g in zip(envs, a["environments"])]}
     if w == "roadmaps_query_raw":
         return f(a["handle"], a["n_roadmaps"], a["starts"], a["goals"], a["index"], a["settings"])
+    if w == "rrtc_multi_constrained_raw":
+        return f(a["starts"], a["goals"], a["goal_counts"], a["environments"], a["constraints"], a["settings"], a["constraint_settings"],
+                 a["max_stretch"], a["skips"])
+    if w in ("simplify_multi_constrained_raw", "optimize_multi_constrained_raw"):
+        return f(a["paths"], a["environments"], a["constraints"], a["settings"], a["constraint_settings"])
+    if w == "cartesian_multi_raw":
+        return f(a["starts"], a["targets"], a["environments"], a["settings"])
+    if w == "retime_multi_raw":
+        return f(a["paths"], a["vel_limits"], a["acc_limits"], a["environments"], a["settings"])
+    if w == "retime_multi_constrained_raw":
+        return f(a["paths"], a["vel_limits"], a["acc_limits"], a["environments"], a["constraints"], a["settings"], a["constraint_settings"])
     return f(a["paths"], a["environments"], a["settings"])
 
 
@@ -328,6 +434,22 @@ def _plan(vamp, w, a):
             roadmaps.close()
     if w == "simplify_multi_raw":
         return P.simplify_multi(r, a["paths"], a["environments"], a["settings"])
+    if w == "rrtc_multi_constrained_raw":
+        sets = np.split(a["goals"], np.cumsum(a["goal_counts"])[:-1]) if len(a["goal_counts"]) else []
+        return P.rrtc_multi_constrained(r, a["starts"], sets, a["environments"], a["constraints"], a["settings"], a["constraint_settings"],
+                                        a["skips"], a["max_stretch"])
+    if w == "simplify_multi_constrained_raw":
+        return P.simplify_multi_constrained(r, a["paths"], a["environments"], a["constraints"], a["settings"], a["constraint_settings"])
+    if w == "optimize_multi_constrained_raw":
+        return P.optimize_multi_constrained(r, a["paths"], a["environments"], a["constraints"], a["settings"], a["constraint_settings"],
+                                            a["resolution"])
+    if w == "cartesian_multi_raw":
+        return P.cartesian_multi(r, a["starts"], a["targets"], a["environments"], a["settings"])
+    if w == "retime_multi_raw":
+        return P.retime_multi(r, a["paths"], a["vel_limits"], a["acc_limits"], a["environments"], a["settings"])
+    if w == "retime_multi_constrained_raw":
+        return P.retime_multi_constrained(r, a["paths"], a["vel_limits"], a["acc_limits"], a["environments"], a["constraints"],
+                                          a["settings"], a["constraint_settings"])
     return P.optimize_multi(r, a["paths"], a["environments"], a["settings"], a["resolution"])
 
 
@@ -544,6 +666,99 @@ REFUSALS = {
     ],
 }
 
+_NO_ENVIRONMENTS = {"environments": None}
+_TWO_CONSTRAINTS = {"constraints": lambda a: [_constraint(a["vamp"], k) for k in range(2)]}
+_CONSTRAINTS = [
+    ("a string as the constraint", {"constraints": "upright"}),
+    ("a string among the constraints", {"constraints": lambda a: [_constraint(a["vamp"]), "upright", _constraint(a["vamp"])]}),
+    ("no constraints", {"constraints": []}),
+    ("two constraints", _TWO_CONSTRAINTS),
+    ("four constraints", {"constraints": lambda a: [_constraint(a["vamp"], k) for k in range(4)]}),
+    ("a string as the constraint settings", {"constraint_settings": "fine"}),
+    ("a string among the environments, two constraints", {**_BAD_ENVIRONMENT, **_TWO_CONSTRAINTS}),
+    ("two environments, two constraints", {**_BAD_COUNT, **_TWO_CONSTRAINTS}),
+    ("two constraints, a string as the constraint settings", {**_TWO_CONSTRAINTS, "constraint_settings": "fine"}),
+]
+_LIMITS = [
+    ("vel_limits of 6", {"vel_limits": np.ones(6)}),
+    ("vel_limits of rank 2", {"vel_limits": np.ones((1, DIM))}),
+    ("a vel_limit of 0", {"vel_limits": [1, 1, 1, 0, 1, 1, 1]}),
+    ("a vel_limit of inf", {"vel_limits": [1, 1, 1, INF, 1, 1, 1]}),
+    ("acc_limits of 8", {"acc_limits": np.ones(8)}),
+    ("an acc_limit of nan", {"acc_limits": [1, 1, 1, 1, 1, 1, NAN]}),
+    ("a negative acc_limit", {"acc_limits": [-1, 1, 1, 1, 1, 1, 1]}),
+]
+_RETIME_SETTINGS = (_floats("blend", NAN, INF, 0.0, -1.0) + _floats("grid_step", NAN, 0.0, 1e-7, 1e-6) + _floats("dt", INF, 0.0, 1e-7, 1e-6) +
+                    _ints("max_grid", 0, 4096) + _ints("max_samples", 0, U32))
+_RETIME = _PATH_CASES + _LIMITS + _RETIME_SETTINGS + [
+    ("no environments, a path of dim 6", {**_NO_ENVIRONMENTS, **_PATH_CASES[0][1]}),
+    ("no environments, vel_limits of 6", {**_NO_ENVIRONMENTS, "vel_limits": np.ones(6)}),
+    ("two environments, vel_limits of 6", {**_BAD_COUNT, "vel_limits": np.ones(6)}),
+    ("vel_limits of 6, a negative acc_limit", {"vel_limits": np.ones(6), "acc_limits": [-1, 1, 1, 1, 1, 1, 1]}),
+    ("a negative acc_limit, blend=nan", {"acc_limits": [-1, 1, 1, 1, 1, 1, 1], "settings.blend": NAN}),
+    ("blend=nan, grid_step=1e-7", {"settings.blend": NAN, "settings.grid_step": 1e-7}),
+    ("dt=1e-7, max_grid=4097", {"settings.dt": 1e-7, "settings.max_grid": 4097}),
+    ("max_grid=4097, max_samples=-1", {"settings.max_grid": 4097, "settings.max_samples": -1}),
+]
+REFUSALS.update({
+    "rrtc_multi_constrained_raw": _ENVIRONMENTS + _SKIPS + _CONSTRAINTS + [
+        ("starts of dim 6", _BAD_SHAPE),
+        ("a goal count of 0", {"goal_counts": [2, 0, 2]}),
+        ("range=0", {"settings.range": 0.0}),
+        ("a set of 2 goals, max_samples=2", {"settings.max_samples": 2}),
+        ("dynamic_domain, radius=0", {"settings.dynamic_domain": True, "settings.radius": 0.0}),
+    ] + [(f"max_stretch={v!r}", {"max_stretch": v}) for v in (NAN, INF, -1.0, -0.0, 0.0, 1e-6)] + [
+        ("a negative skip, two constraints", {**_BAD_SKIPS, **_TWO_CONSTRAINTS}),
+        ("range=0, two constraints", {"settings.range": 0.0, **_TWO_CONSTRAINTS}),
+        ("dynamic_domain with radius=0, two constraints", {"settings.dynamic_domain": True, "settings.radius": 0.0, **_TWO_CONSTRAINTS}),
+        ("two constraints, max_stretch=nan", {**_TWO_CONSTRAINTS, "max_stretch": NAN}),
+        ("max_stretch=nan, a string as the constraint settings", {"max_stretch": NAN, "constraint_settings": "fine"}),
+    ],
+    "simplify_multi_constrained_raw": _PATH_CASES + _CONSTRAINTS + [
+        ("REDUCE", {"settings.operations": ["SHORTCUT", "REDUCE"]}),
+        ("questions_per_round=3", {"settings.questions_per_round": 3}),
+        ("a path of 4 waypoints, max_waypoints=3", {"settings.max_waypoints": 3}),
+        ("a path of dim 6, two constraints", {**_PATH_CASES[0][1], **_TWO_CONSTRAINTS}),
+        ("REDUCE, two constraints", {"settings.operations": ["REDUCE"], **_TWO_CONSTRAINTS}),
+    ],
+    "optimize_multi_constrained_raw": _PATH_CASES + _CONSTRAINTS + [
+        ("step=0", {"settings.step": 0.0}),
+        ("max_iterations=0", {"settings.max_iterations": 0}),
+        ("a path of 4 waypoints, max_waypoints=3", {"settings.max_waypoints": 3}),
+        ("a path of dim 6, two constraints", {**_PATH_CASES[0][1], **_TWO_CONSTRAINTS}),
+        ("step=0, two constraints", {"settings.step": 0.0, **_TWO_CONSTRAINTS}),
+    ],
+    "cartesian_multi_raw": _ENVIRONMENTS + [
+        ("starts of rank 1", {"starts": lambda a: a["starts"][0]}),
+        ("starts of dim 6", _BAD_SHAPE),
+        ("two targets", {"targets": lambda a: a["targets"][:2]}),
+        ("targets as [n][16]", {"targets": lambda a: a["targets"].reshape(N, 16)}),
+        ("targets as [n][15]", {"targets": lambda a: a["targets"].reshape(N, 16)[:, :15]}),
+        ("targets of rank 1", {"targets": lambda a: a["targets"].reshape(-1)}),
+    ] + [case for k in ("pos_step", "rot_step", "pos_tol", "rot_tol", "rot_weight", "damping", "max_step", "max_joint_step")
+         for case in _floats(k, NAN, INF, 0.0, -1.0)] + _ints("max_iterations", 0, 2 ** 30 - 1) + _ints("max_waypoints", 0, 1024) + [
+        ("no environments, starts of dim 6", {**_NO_ENVIRONMENTS, **_BAD_SHAPE}),
+        ("no environments, pos_step=nan", {**_NO_ENVIRONMENTS, "settings.pos_step": NAN}),
+        ("starts of dim 6, two targets", {**_BAD_SHAPE, "targets": lambda a: a["targets"][:2]}),
+        ("two targets, a string among the environments", {"targets": lambda a: a["targets"][:2], **_BAD_ENVIRONMENT}),
+        ("a string among the environments, two environments", {"environments": lambda a: [a["environments"][0], "env"]}),
+        ("two environments, pos_step=nan", {**_BAD_COUNT, "settings.pos_step": NAN}),
+        ("pos_step=nan, rot_step=inf", {"settings.pos_step": NAN, "settings.rot_step": INF}),
+        ("max_joint_step=nan, max_iterations=-1", {"settings.max_joint_step": NAN, "settings.max_iterations": -1}),
+        ("max_iterations=-1, max_waypoints=1025", {"settings.max_iterations": -1, "settings.max_waypoints": 1025}),
+    ],
+    "retime_multi_raw": _RETIME,
+    "retime_multi_constrained_raw": _RETIME + _ints("blend_halvings", 0, 8) + _ints("max_rounds", 0, U32) + [
+        (name, {"constraints": lambda a: _constraint(a["vamp"]), **changes}) for name, changes in _CONSTRAINTS] + [
+        ("constraints=None, a string as the constraint settings", {"constraint_settings": "fine"}),
+        ("max_samples=-1, blend_halvings=9", {"settings.max_samples": -1, "settings.blend_halvings": 9}),
+        ("blend_halvings=9, max_rounds=-1", {"settings.blend_halvings": 9, "settings.max_rounds": -1}),
+        ("max_rounds=-1, two constraints", {"settings.max_rounds": -1, **_TWO_CONSTRAINTS}),
+        ("a negative acc_limit, two constraints", {"acc_limits": [-1, 1, 1, 1, 1, 1, 1], **_TWO_CONSTRAINTS}),
+        ("no environments, two constraints", {**_NO_ENVIRONMENTS, **_TWO_CONSTRAINTS}),
+    ],
+})
+
 # refusals of the planning.* functions themselves (their own checks, and the wrapper's words coming through)
 PLAN_REFUSALS = {
     "rrtc_multi_raw": [("two environments", _BAD_COUNT), ("range=0 with dynamic_domain", {"settings.range": 0.0,
@@ -568,6 +783,17 @@ PLAN_REFUSALS = {
         ("a densified path as long as max_waypoints", {"resolution": 0.1, "settings.max_waypoints": 4}),
         ("step=0", {"settings.step": 0.0}),
     ],
+    "rrtc_multi_constrained_raw": [("two constraints", _TWO_CONSTRAINTS), ("max_stretch=nan", {"max_stretch": NAN}),
+                                   ("two environments", _BAD_COUNT)],
+    "simplify_multi_constrained_raw": [("REDUCE", {"settings.operations": ["REDUCE"]}), ("two constraints", _TWO_CONSTRAINTS)],
+    "optimize_multi_constrained_raw": [
+        ("a path of dim 6", _PATH_CASES[0][1]),
+        ("a densified path longer than max_waypoints", {"resolution": 8.0, "settings.max_waypoints": 8}),
+        ("two constraints", _TWO_CONSTRAINTS),
+    ],
+    "cartesian_multi_raw": [("two targets", {"targets": lambda a: a["targets"][:2]}), ("pos_step=nan", {"settings.pos_step": NAN})],
+    "retime_multi_raw": [("vel_limits of 6", {"vel_limits": np.ones(6)}), ("dt=1e-7", {"settings.dt": 1e-7})],
+    "retime_multi_constrained_raw": [("two constraints", _TWO_CONSTRAINTS), ("blend_halvings=9", {"settings.blend_halvings": 9})],
 }
 
 # accepted calls: (case name, changes, n, the symbol that fails or None)
@@ -598,6 +824,31 @@ ACCEPTED["roadmaps_query_raw"] += [("index given", {"index": [1, 0, 1]}, N, None
 ACCEPTED["simplify_multi_raw"] += [("one operation, library defaults", {
     "settings.operations": ["bspline"], "settings.max_waypoints": 0, "settings.questions_per_round": 0}, N, None)]
 ACCEPTED["optimize_multi_raw"] += [("densified", {"resolution": 1.0}, N, None)]
+_PER_ITEM = {"constraints": lambda a: [_constraint(a["vamp"], k) for k in range(N)]}
+_OWN_BAND_SETTINGS = {"constraint_settings": lambda a: a["vamp"].ConstraintSettings(max_iterations=5, pos_tol=0.002, check_step=0.125)}
+for _w in ("rrtc_multi_constrained_raw", "simplify_multi_constrained_raw", "optimize_multi_constrained_raw"):
+    ACCEPTED[_w] += [("one constraint per item", _PER_ITEM, N, None), ("one constraint per item, n = 0", {"constraints": []}, 0, None),
+                     ("constraint settings given", _OWN_BAND_SETTINGS, N, None)]
+ACCEPTED["rrtc_multi_constrained_raw"] += [("skips given, max_stretch=3", {**_GIVEN_SKIPS, "max_stretch": 3}, N, None),
+                                           ("max_stretch=0", {"max_stretch": 0.0}, N, None)]
+ACCEPTED["optimize_multi_constrained_raw"] += [("densified", {"resolution": 1.0}, N, None)]
+for _w in ("cartesian_multi_raw", "retime_multi_raw", "retime_multi_constrained_raw"):
+    ACCEPTED[_w] += [("no environments", _NO_ENVIRONMENTS, N, None), ("no environments, n = 0", _NO_ENVIRONMENTS, 0, None)] + [
+        (f"no environments, fails at {s}", _NO_ENVIRONMENTS, N, s) for s in SYMBOLS[_w]]
+ACCEPTED["cartesian_multi_raw"] += [("position_only, library defaults", {
+    "settings.position_only": True, "settings.pos_step": 0.0, "settings.max_iterations": 0, "settings.max_waypoints": 0}, N, None),
+    ("targets as [n][16]", {"targets": lambda a: a["targets"].reshape(N, 16)}, N, None)]
+ACCEPTED["retime_multi_raw"] += [("stop_at_waypoints, library defaults", {
+    "settings.stop_at_waypoints": True, "settings.blend": 0.0, "settings.dt": -1.0, "settings.max_grid": 0}, N, None)]
+_ONE = {"constraints": lambda a: _constraint(a["vamp"])}
+ACCEPTED["retime_multi_constrained_raw"] += [
+    ("one constraint", _ONE, N, None), ("one constraint in a list", {"constraints": lambda a: [_constraint(a["vamp"])]}, N, None),
+    ("one constraint per path", _PER_ITEM, N, None), ("one constraint, n = 0", _ONE, 0, None),
+    ("no environments, one constraint per path", {**_NO_ENVIRONMENTS, **_PER_ITEM}, N, None),
+    ("one constraint, constraint settings given", {**_ONE, **_OWN_BAND_SETTINGS}, N, None),
+    ("constraints=None, constraint settings given", _OWN_BAND_SETTINGS, N, None),
+    ("blend_halvings and max_rounds of its own", {"settings.blend_halvings": 8, "settings.max_rounds": 2}, N, None)] + [
+    (f"one constraint per path, fails at {s}", _PER_ITEM, N, s) for s in SYMBOLS["retime_multi_constrained_raw"]]
 
 ALL = ([f"refused / {w} / {name}" for w in WRAPPERS for name, _ in REFUSALS[w]] +
        [f"refused / planning above {w} / {name}" for w in WRAPPERS for name, _ in PLAN_REFUSALS[w]] +
@@ -618,7 +869,13 @@ def _refused(vamp, install, wrapper, changes, call):
     return None
 
 
-def _accepted(vamp, install, wrapper, changes, n, fail):
+def _whole(wrapper, name):
+    """whether the record of an accepted call is kept as it is; else what the entry was given and what came back are kept
+    as digests of their JSON (as exact, a fiftieth of the size): the wrappers added later, but for their "plain" case"""
+    return WRAPPERS.index(wrapper) < 9 or name == "plain"
+
+
+def _accepted(vamp, install, wrapper, changes, n, fail, whole=True):
     """-> {"raw": the wrapper's record, "plan": that of the planning.* function above it}"""
     record = {}
     for level, call in (("raw", _raw), ("plan", _plan)):
@@ -631,9 +888,13 @@ def _accepted(vamp, install, wrapper, changes, n, fail):
         except vamp.VmvError as e:
             out["error"] = [type(e).__name__, e.status, str(e).split(" (")[0]]
         finally:
-            for e in a["environments"]:  # give the fake handles up while the stand-in still answers
+            for e in a["environments"] or ():  # give the fake handles up while the stand-in still answers
                 e._dirty()
         out.update(calls=lib.calls, entry=lib.entry, destroyed=lib.destroyed)
+        for part in ("entry", "result"):
+            if not whole and out.get(part) is not None:
+                print(f"{wrapper} / {level} / {part}: {json.dumps(out[part], sort_keys=True)}")  # (what the digest is of)
+                out[part] = {"sha256 of the JSON": hashlib.sha256(json.dumps(out[part], sort_keys=True).encode()).hexdigest()}
         if DESTROY[wrapper]:  # whatever the readout did, the handle the entry gave is destroyed once
             assert lib.destroyed.get(DESTROY[wrapper], 0) == (1 if lib.entry is not None else 0), (wrapper, level)
         record[level] = out
@@ -646,8 +907,8 @@ def _same(got, want):
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
+    with open(GOLDEN) as f, open(GOLDEN_PATHS) as g:
+        return {**json.load(f), **json.load(g)}
 
 
 def test_the_table_covers_every_recorded_case(golden):
@@ -669,7 +930,7 @@ def test_refusals(vamp, monkeypatch, golden, wrapper):
 def test_accepted_calls(vamp, monkeypatch, golden, wrapper):
     install = lambda lib: monkeypatch.setattr(vamp, "lib", lib)  # noqa: E731
     for name, changes, n, fail in ACCEPTED[wrapper]:
-        got = _accepted(vamp, install, wrapper, changes, n, fail)
+        got = _accepted(vamp, install, wrapper, changes, n, fail, _whole(wrapper, name))
         want = golden[f"accepted / {wrapper} / {name}"]
         for level in ("raw", "plan"):
             for part in sorted(set(got[level]) | set(want[level])):
@@ -694,10 +955,12 @@ if __name__ == "__main__":
             for case, spoiled in PLAN_REFUSALS[w]:
                 table[f"refused / planning above {w} / {case}"] = _refused(vamp_mvt_amd, put, w, spoiled, _plan)
             for case, changed, count, failing in ACCEPTED[w]:
-                table[f"accepted / {w} / {case}"] = _accepted(vamp_mvt_amd, put, w, changed, count, failing)
+                table[f"accepted / {w} / {case}"] = _accepted(vamp_mvt_amd, put, w, changed, count, failing, _whole(w, case))
     finally:
         vamp_mvt_amd.lib = real
     assert sorted(table) == sorted(ALL)
-    with open(GOLDEN, "w") as f:  # one case per line
-        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(table[k], sort_keys=True)}" for k in sorted(table)) + "\n}\n")
+    for path, wrappers in ((GOLDEN, WRAPPERS[:9]), (GOLDEN_PATHS, WRAPPERS[9:])):  # one case per line
+        keys = sorted(k for k in table if k.split(" / ")[1].replace("planning above ", "") in wrappers)
+        with open(path, "w") as f:
+            f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(table[k], sort_keys=True)}" for k in keys) + "\n}\n")
     print(len(table), "cases recorded")

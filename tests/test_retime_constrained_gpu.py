@@ -290,3 +290,27 @@ def test_every_corner_stopped_has_the_samples_of_stop_at_waypoints(vamp, sets):
                                               vamp.planning.RetimeSettings(blend=S.blend, grid_step=S.grid_step, dt=S.dt, max_grid=S.max_grid,
                                                                            max_samples=S.max_samples, stop_at_waypoints=True))[0]
             assert same_samples(g, stop) and g.intervals == stop.intervals
+
+
+def test_one_constraint_for_all_paths_equals_the_same_constraint_per_path(vamp):
+    """panda, paths of 4, 3 and 5 waypoints, one obstacle sphere: the smallest call in which the band kernel reads its
+    record both ways (one for all; one per path, found through the sampled path's index) over paths of uneven length"""
+    import constraint_serial as S
+
+    mod, P = vamp.panda, vamp.planning
+    constraint = vamp.EEConstraint.upright((0, 0, 1), 0.2)
+    env = vamp.Environment()
+    env.add_sphere(vamp.Sphere([0.55, 0.0, 0.6], 0.08))
+    (rows,) = P.project_goals(mod, [S.configs("panda", 96)], constraint, env)
+    assert len(rows) >= 12
+    paths = [rows[0:4], rows[4:7], rows[7:12]]
+    V, A = C.limits("panda")
+    s = P.RetimeConstrainedSettings()
+    once = mod.retime_multi_constrained_raw(paths, V, A, [env] * 3, constraint, s)
+    each = mod.retime_multi_constrained_raw(paths, V, A, [env] * 3, [constraint] * 3, s)
+    print("status", once["status"], "rounds", once["rounds"], "samples", once["samples"], "questions", once["questions"])
+    assert once["questions"] > 0 and (once["samples"] > 1).all()  # every path was sampled and its pairs were asked
+    assert sorted(once) == sorted(each)
+    for k in once:
+        a, b = np.asarray(once[k]), np.asarray(each[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k

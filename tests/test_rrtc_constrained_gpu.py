@@ -183,3 +183,24 @@ def test_other_robots(vamp, oracle, robot):
     trees, direct, worst = c.check_paths(got)
     print(f"{robot}: {trees} through the trees, {direct} direct; largest angle beyond the band {worst:.3e} rad")
     assert trees + direct >= 1
+
+
+def test_one_constraint_for_all_problems_equals_the_same_constraint_per_problem(vamp):
+    """panda, three problems with 1, 2 and 1 goals, one obstacle sphere: the smallest call in which the endpoint test
+    and the rounds read the records both ways (one for all; one per lane, expanded over goal sets of uneven size)"""
+    mod, P = vamp.panda, vamp.planning
+    constraint = vamp.EEConstraint.upright((0, 0, 1), ANGLE)
+    env = vamp.Environment()
+    env.add_sphere(vamp.Sphere([0.55, 0.0, 0.6], 0.08))
+    (rows,) = P.project_goals(mod, [S.configs("panda", 96)], constraint, env)
+    assert len(rows) >= 7
+    starts, goals, counts = rows[[0, 2, 5]], rows[[1, 3, 4, 6]], [1, 2, 1]
+    s = P.RRTCMultiSettings(range=RANGE, max_iterations=1500, max_samples=256)
+    once = mod.rrtc_multi_constrained_raw(starts, goals, counts, [env] * 3, constraint, s, skips=[0, 1000, 2000])
+    each = mod.rrtc_multi_constrained_raw(starts, goals, counts, [env] * 3, [constraint] * 3, s, skips=[0, 1000, 2000])
+    print("status", once["status"], "iterations", once["iterations"], "rounds", once["rounds"], "band_refused", once["band_refused"])
+    assert (once["status"] != INVALID_ENDPOINT).all() and once["iterations"].max() > 0  # all take part, one grows its trees
+    assert sorted(once) == sorted(each)
+    for k in once:
+        a, b = np.asarray(once[k]), np.asarray(each[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k

@@ -650,6 +650,20 @@ def _read_plans(plans, n, dim, extra=None):
     return out
 
 
+def _read_result(n, entry, readout, destroy):
+    """The life cycle of a path call's result handle, as `_read_plans` has it for the planners: nothing for n == 0 (->
+    None: the caller's zeros stand and the library is not touched); else entry(byref(handle)), the checked entry call,
+    then -> readout(handle) while the handle lives; `destroy` (a symbol's name) runs whatever happens."""
+    if n == 0:
+        return None
+    out = ctypes.c_void_p()
+    entry(ctypes.byref(out))
+    try:
+        return readout(out)
+    finally:
+        getattr(lib, destroy)(out)
+
+
 def _torch_unpack_bits(bits, n):
     """unpack_bits for a torch int64 tensor of validity words -> torch.bool[n] on the same device"""
     import torch
@@ -1561,27 +1575,24 @@ class _Robot(types.ModuleType):
         n = len(pts)
         _one_per(environments, n, "path")
         cs = _simplify_settings_struct(settings, max((len(a) for a in pts), default=0))
+        status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        lengths, questions = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        rounds, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
         extra = {}
         if constrained is not None:  # (every Python-side check before any library call)
             records, count = _constraint_records(constrained[0], n)
             ps = (constrained[1] or ConstraintSettings()).struct()
             extra["band_refused"] = np.zeros(n, np.uint32)
-        if n == 0:
-            return dict(status=np.zeros(0, np.uint8), iterations=np.zeros(0, np.uint32), lengths=np.zeros(0, np.uint32),
-                        questions=np.zeros(0, np.uint32), points=packed, rounds=0, total_questions=0, **extra)
-        envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-        out = ctypes.c_void_p()
-        if constrained is not None:
-            check(lib.vmv_simplify_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                                     ctypes.byref(cs), records, count, ctypes.byref(ps), ctypes.byref(out)),
-                  "vmv_simplify_multi_constrained")
-        else:
-            check(lib.vmv_simplify_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                         ctypes.byref(cs), ctypes.byref(out)), "vmv_simplify_multi")
-        try:
-            status, iterations = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
-            lengths, questions = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-            rounds, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+        def entry(out):
+            envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
+            given = (self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p), ctypes.byref(cs))
+            if constrained is not None:
+                check(lib.vmv_simplify_multi_constrained(*given, records, count, ctypes.byref(ps), out), "vmv_simplify_multi_constrained")
+            else:
+                check(lib.vmv_simplify_multi(*given, out), "vmv_simplify_multi")
+
+        def readout(out):
             check(lib.vmv_paths_summary(out, status.ctypes.data_as(_lib.c_u8_p), iterations.ctypes.data_as(_lib.c_u32_p),
                                         lengths.ctypes.data_as(_lib.c_u32_p), questions.ctypes.data_as(_lib.c_u32_p),
                                         ctypes.byref(rounds), ctypes.byref(total)), "vmv_paths_summary")
@@ -1589,10 +1600,11 @@ class _Robot(types.ModuleType):
             check(lib.vmv_paths_points(out, _fp(points), points.size), "vmv_paths_points")
             if constrained is not None:
                 check(lib.vmv_paths_band_refused(out, extra["band_refused"].ctypes.data_as(_lib.c_u32_p)), "vmv_paths_band_refused")
-        finally:
-            lib.vmv_paths_destroy(out)
-        return dict(status=status, iterations=iterations, lengths=lengths, questions=questions, points=points,
-                    rounds=int(rounds.value), total_questions=int(total.value), **extra)
+            return points
+
+        points = _read_result(n, entry, readout, "vmv_paths_destroy")
+        return dict(status=status, iterations=iterations, lengths=lengths, questions=questions,
+                    points=packed if points is None else points, rounds=int(rounds.value), total_questions=int(total.value), **extra)
 
     def optimize_multi_constrained_raw(self, paths, environments, constraints, settings, constraint_settings=None):
         """vmv_optimize_multi_constrained: optimize_multi_raw inside the band of end-effector constraints - one
@@ -1625,26 +1637,25 @@ class _Robot(types.ModuleType):
             records, count = _constraint_records(constrained[0], n)
             ps = (constrained[1] or ConstraintSettings()).struct()
             extra["held"] = np.zeros(n, np.uint32)
-        if n > 0:
+
+        def entry(out):
             envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-            out = ctypes.c_void_p()
+            given = (self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p), ctypes.byref(cs))
             if constrained is not None:
-                check(lib.vmv_optimize_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                                         ctypes.byref(cs), records, count, ctypes.byref(ps), ctypes.byref(out)),
-                      "vmv_optimize_multi_constrained")
+                check(lib.vmv_optimize_multi_constrained(*given, records, count, ctypes.byref(ps), out), "vmv_optimize_multi_constrained")
             else:
-                check(lib.vmv_optimize_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                             ctypes.byref(cs), ctypes.byref(out)), "vmv_optimize_multi")
-            try:
-                if constrained is not None:
-                    check(lib.vmv_optimized_held(out, extra["held"].ctypes.data_as(_lib.c_u32_p)), "vmv_optimized_held")
-                check(lib.vmv_optimized_summary(out, status.ctypes.data_as(_lib.c_u8_p),
-                                                iterations.ctypes.data_as(_lib.c_u32_p), best.ctypes.data_as(_lib.c_u32_p),
-                                                _fp(cost_first), _fp(cost), _fp(clr_first), _fp(clr), ctypes.byref(calls),
-                                                ctypes.byref(validations)), "vmv_optimized_summary")
-                check(lib.vmv_optimized_points(out, _fp(points), points.size), "vmv_optimized_points")
-            finally:
-                lib.vmv_optimized_destroy(out)
+                check(lib.vmv_optimize_multi(*given, out), "vmv_optimize_multi")
+
+        def readout(out):
+            if constrained is not None:
+                check(lib.vmv_optimized_held(out, extra["held"].ctypes.data_as(_lib.c_u32_p)), "vmv_optimized_held")
+            check(lib.vmv_optimized_summary(out, status.ctypes.data_as(_lib.c_u8_p),
+                                            iterations.ctypes.data_as(_lib.c_u32_p), best.ctypes.data_as(_lib.c_u32_p),
+                                            _fp(cost_first), _fp(cost), _fp(clr_first), _fp(clr), ctypes.byref(calls),
+                                            ctypes.byref(validations)), "vmv_optimized_summary")
+            check(lib.vmv_optimized_points(out, _fp(points), points.size), "vmv_optimized_points")
+
+        _read_result(n, entry, readout, "vmv_optimized_destroy")
         return dict(status=status, iterations=iterations, best_iteration=best, cost_first=cost_first, cost=cost,
                     clearance_first=clr_first, clearance=clr, points=points, offsets=offsets.astype(np.int64),
                     clearance_calls=int(calls.value), validation_calls=int(validations.value), **extra)
@@ -1670,29 +1681,29 @@ class _Robot(types.ModuleType):
         cs = _cartesian_settings_struct(settings)
         status, segments = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
         achieved, evaluations = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        points = np.zeros((0, self._dim), np.float32)
         calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if n > 0:
-            handles = None
-            if environments is not None:
-                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-            out = ctypes.c_void_p()
-            check(lib.vmv_cartesian_multi(self._id, handles, n, _fp(a), _fp(t), ctypes.byref(cs), ctypes.byref(out)),
-                  "vmv_cartesian_multi")
-            try:
-                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (segments, achieved, evaluations)]
-                check(lib.vmv_cartesian_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, ctypes.byref(calls),
-                                                ctypes.byref(questions)), "vmv_cartesian_summary")
-                points = np.zeros((int(achieved.sum()) + n, self._dim), np.float32)
-                check(lib.vmv_cartesian_points(out, _fp(points), points.size), "vmv_cartesian_points")
-            finally:
-                lib.vmv_cartesian_destroy(out)
+
+        def entry(out):
+            envs, handles = (None, None) if environments is None else _env_handles(environments)  # (`envs` lives through the call)
+            check(lib.vmv_cartesian_multi(self._id, handles, n, _fp(a), _fp(t), ctypes.byref(cs), out), "vmv_cartesian_multi")
+
+        def readout(out):
+            counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (segments, achieved, evaluations)]
+            check(lib.vmv_cartesian_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, ctypes.byref(calls),
+                                            ctypes.byref(questions)), "vmv_cartesian_summary")
+            points = np.zeros((int(achieved.sum()) + n, self._dim), np.float32)
+            check(lib.vmv_cartesian_points(out, _fp(points), points.size), "vmv_cartesian_points")
+            return points
+
+        points = _read_result(n, entry, readout, "vmv_cartesian_destroy")
+        if points is None:
+            points = np.zeros((0, self._dim), np.float32)
         offsets = np.zeros(n + 1, np.int64)
         offsets[1:] = np.cumsum(achieved.astype(np.int64) + 1)
         return dict(status=status, segments=segments, achieved=achieved, evaluations=evaluations, points=points,
                     offsets=offsets, validation_calls=int(calls.value), questions=int(questions.value))
 
-    def retime_multi_raw(self, paths, vel_limits, acc_limits, environments, settings):
+    def retime_multi_raw(self, paths, vel_limits, acc_limits, environments, settings, constrained=None):
         """vmv_retime_multi: time-optimal trajectories along many paths in one call, path p ([len][dim] waypoints, any
         length) in environments[p] (None = the empty environment); environments=None: nothing is validated.  vel_limits,
         acc_limits: [dim], finite and positive.  settings: the fields of planning.RetimeSettings.  -> dict of per-path
@@ -1707,33 +1718,51 @@ class _Robot(types.ModuleType):
         if environments is not None:
             _one_per(environments, n, "path")
         vel, acc = _joint_limits(vel_limits, self._dim, "vel_limits"), _joint_limits(acc_limits, self._dim, "acc_limits")
-        cs = _retime_settings_struct(settings)
         status, intervals, samples = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         duration, first_invalid = np.zeros(n, np.float32), np.full(n, 0xffffffff, np.uint32)
-        arrays = [np.zeros(0, np.float32)] + [np.zeros((0, self._dim), np.float32) for _ in range(3)]
         calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if n > 0:
-            handles = None
-            if environments is not None:
-                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-            out = ctypes.c_void_p()
-            check(lib.vmv_retime_multi(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p), _fp(vel),
-                                       _fp(acc), ctypes.byref(cs), ctypes.byref(out)), "vmv_retime_multi")
-            try:
-                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (intervals, samples)]
-                check(lib.vmv_retime_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, _fp(duration),
-                                             first_invalid.ctypes.data_as(_lib.c_u32_p), ctypes.byref(calls),
-                                             ctypes.byref(questions)), "vmv_retime_summary")
-                total = int(samples.sum())
-                arrays = [np.zeros(total, np.float32)] + [np.zeros((total, self._dim), np.float32) for _ in range(3)]
-                check(lib.vmv_retime_samples(out, *[_fp(x) for x in arrays], total), "vmv_retime_samples")
-            finally:
-                lib.vmv_retime_destroy(out)
+        extra = {}
+        if constrained is None:
+            cs = _retime_settings_struct(settings)
+        else:  # (every Python-side check before any library call)
+            cs = _retime_constrained_settings_struct(settings)
+            records, count, ps = None, 0, None
+            if constrained[0] is not None:
+                records, count = _constraint_records(constrained[0], n)
+                ps = ctypes.byref((constrained[1] or ConstraintSettings()).struct())
+            extra = dict(rounds=np.zeros(n, np.uint32), repaired=np.zeros(n, np.uint32), stops=np.zeros(n, np.uint32),
+                         levels=np.zeros(int(offsets[-1]) if n else 0, np.uint8), level_offsets=offsets.astype(np.int64))
+
+        def entry(out):
+            envs, handles = (None, None) if environments is None else _env_handles(environments)  # (`envs` lives through the call)
+            given = (self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p), _fp(vel), _fp(acc))
+            if constrained is not None:
+                check(lib.vmv_retime_multi_constrained(*given, records, count, ctypes.byref(cs), ps, out), "vmv_retime_multi_constrained")
+            else:
+                check(lib.vmv_retime_multi(*given, ctypes.byref(cs), out), "vmv_retime_multi")
+
+        def readout(out):
+            counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (intervals, samples)]
+            check(lib.vmv_retime_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, _fp(duration),
+                                         first_invalid.ctypes.data_as(_lib.c_u32_p), ctypes.byref(calls),
+                                         ctypes.byref(questions)), "vmv_retime_summary")
+            if constrained is not None:
+                check(lib.vmv_retime_levels(out, extra["levels"].ctypes.data_as(_lib.c_u8_p),
+                                            *[extra[k].ctypes.data_as(_lib.c_u32_p) for k in ("rounds", "repaired", "stops")]),
+                      "vmv_retime_levels")
+            total = int(samples.sum())
+            arrays = [np.zeros(total, np.float32)] + [np.zeros((total, self._dim), np.float32) for _ in range(3)]
+            check(lib.vmv_retime_samples(out, *[_fp(x) for x in arrays], total), "vmv_retime_samples")
+            return arrays
+
+        arrays = _read_result(n, entry, readout, "vmv_retime_destroy")
+        if arrays is None:
+            arrays = [np.zeros(0, np.float32)] + [np.zeros((0, self._dim), np.float32) for _ in range(3)]
         sample_offsets = np.zeros(n + 1, np.int64)
         sample_offsets[1:] = np.cumsum(samples.astype(np.int64))
         return dict(status=status, intervals=intervals, samples=samples, duration=duration, first_invalid=first_invalid,
                     times=arrays[0], positions=arrays[1], velocities=arrays[2], accelerations=arrays[3],
-                    offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value))
+                    offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value), **extra)
 
     def retime_multi_constrained_raw(self, paths, vel_limits, acc_limits, environments, constraints, settings,
                                      constraint_settings=None):
@@ -1743,52 +1772,7 @@ class _Robot(types.ModuleType):
         -> retime_multi_raw's dict (status 5 = out_of_band) plus rounds, repaired, stops (per path) and levels (one
         uint8 per input waypoint, packed) with level_offsets.  planning.retime_multi_constrained is the caller-facing
         form.  Every argument is checked before any library call."""
-        if environments is not None:
-            environments = list(environments)
-            _check_environments(environments)
-        pts, packed, offsets = _packed_paths(paths, self._dim)
-        n = len(pts)
-        if environments is not None:
-            _one_per(environments, n, "path")
-        vel, acc = _joint_limits(vel_limits, self._dim, "vel_limits"), _joint_limits(acc_limits, self._dim, "acc_limits")
-        cs = _retime_constrained_settings_struct(settings)
-        records, count, ps = None, 0, None
-        if constraints is not None:
-            records, count = _constraint_records(constraints, n)
-            ps = ctypes.byref((constraint_settings or ConstraintSettings()).struct())
-        status, intervals, samples = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        duration, first_invalid = np.zeros(n, np.float32), np.full(n, 0xffffffff, np.uint32)
-        rounds, repaired, stops = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        levels = np.zeros(int(offsets[-1]) if n else 0, np.uint8)
-        arrays = [np.zeros(0, np.float32)] + [np.zeros((0, self._dim), np.float32) for _ in range(3)]
-        calls, questions = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if n > 0:
-            handles = None
-            if environments is not None:
-                envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
-            out = ctypes.c_void_p()
-            check(lib.vmv_retime_multi_constrained(self._id, handles, n, _fp(packed), offsets.ctypes.data_as(_lib.c_size_p),
-                                                   _fp(vel), _fp(acc), records, count, ctypes.byref(cs), ps, ctypes.byref(out)),
-                  "vmv_retime_multi_constrained")
-            try:
-                counts = [x.ctypes.data_as(_lib.c_u32_p) for x in (intervals, samples)]
-                check(lib.vmv_retime_summary(out, status.ctypes.data_as(_lib.c_u8_p), *counts, _fp(duration),
-                                             first_invalid.ctypes.data_as(_lib.c_u32_p), ctypes.byref(calls),
-                                             ctypes.byref(questions)), "vmv_retime_summary")
-                check(lib.vmv_retime_levels(out, levels.ctypes.data_as(_lib.c_u8_p),
-                                            *[x.ctypes.data_as(_lib.c_u32_p) for x in (rounds, repaired, stops)]),
-                      "vmv_retime_levels")
-                total = int(samples.sum())
-                arrays = [np.zeros(total, np.float32)] + [np.zeros((total, self._dim), np.float32) for _ in range(3)]
-                check(lib.vmv_retime_samples(out, *[_fp(x) for x in arrays], total), "vmv_retime_samples")
-            finally:
-                lib.vmv_retime_destroy(out)
-        sample_offsets = np.zeros(n + 1, np.int64)
-        sample_offsets[1:] = np.cumsum(samples.astype(np.int64))
-        return dict(status=status, intervals=intervals, samples=samples, duration=duration, first_invalid=first_invalid,
-                    times=arrays[0], positions=arrays[1], velocities=arrays[2], accelerations=arrays[3],
-                    offsets=sample_offsets, validation_calls=int(calls.value), questions=int(questions.value),
-                    rounds=rounds, repaired=repaired, stops=stops, levels=levels, level_offsets=offsets.astype(np.int64))
+        return self.retime_multi_raw(paths, vel_limits, acc_limits, environments, settings, constrained=(constraints, constraint_settings))
 
     def _retime_band_pairs(self, positions, sample_offsets, constraints, constraint_settings=None):
         """NOT part of the supported interface (the library's vmv_retime_band_pairs_host is not in the public header

@@ -1665,38 +1665,26 @@ namespace
 
     // The checks of the vmv_constraint_*_batch calls, none of which needs a device, in the header's order; fills the
     // kernels' parameter block; the device records (one, or one per lane) are built once the call holds its pinned table.
-    struct ConstraintCall
-    {
-        vmv::ConstraintParams P;
-        const vmv_ee_constraint *constraints;
-        size_t count;
-    };
     int constraint_checks(int robot, bool arrays, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
-                          const vmv_constraint_settings *settings, ConstraintCall &c)
+                          const vmv_constraint_settings *settings, vmv::ConstraintBand &c)
     {
         if (!robot_ok(robot)) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!arrays || !constraints || !settings) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
-        if (n_constraints != 1 && n_constraints != n) return refuse(VMV_ERR_INVALID_ARGUMENT, "n_constraints must be 1 or n");
-        if (const char *err = vmv::constraint_settings(*settings, c.P)) return refuse(VMV_ERR_INVALID_ARGUMENT, err);
-        if (n >= vmv::kMultiMaxConfigs) return refuse(VMV_ERR_INVALID_ARGUMENT, "n must be below 2^31");
-        c.P.shared = n_constraints == 1 ? 1u : 0u;
-        for (int j = 0; j < 16; ++j) c.P.lower[j] = kRobots[robot].lower[j], c.P.upper[j] = kRobots[robot].lower[j] + kRobots[robot].span[j];
-        c.constraints = constraints, c.count = n_constraints;
-        for (size_t k = 0; k < n_constraints; ++k)
-            if (const char *err = vmv::constraint_refusal(constraints[k]))
-                return refuse(VMV_ERR_INVALID_ARGUMENT, "constraints[" + std::to_string(k) + "]: " + err);
+        if (!arrays) return refuse(VMV_ERR_INVALID_ARGUMENT, "null pointer");
+        const std::string err = vmv::constraint_band_checks(constraints, n_constraints, settings, n, "n",
+                                                            n >= vmv::kMultiMaxConfigs ? "n must be below 2^31" : nullptr, c);
+        if (!err.empty()) return refuse(VMV_ERR_INVALID_ARGUMENT, err);
+        vmv::constraint_band_bounds(c, kRobots[robot].lower, kRobots[robot].span, kRobots[robot].dimension);
         return VMV_OK;
     }
     // the records built straight into the stream's pinned table, uploaded, then launch(d_records, stream); the _host forms
     // come here after their own prologue (the null stream, so that the staged copies order with the launch)
     template <typename F>
-    int constraint_launch(const ConstraintCall &c, hipStream_t stream, F &&launch)
+    int constraint_launch(const vmv::ConstraintBand &c, hipStream_t stream, F &&launch)
     {
         vmv::MultiTableLease lease;
         const size_t bytes = c.count * sizeof(vmv::ConstraintDev);
         if (int rc = lease.acquire(stream, bytes); rc != VMV_OK) return rc;
-        vmv::ConstraintDev *records = static_cast<vmv::ConstraintDev *>(lease.host);
-        for (size_t k = 0; k < c.count; ++k) vmv::constraint_record(c.constraints[k], (double) c.P.pos_tol, (double) c.P.rot_tol, records[k]);
+        vmv::constraint_band_records(c, static_cast<vmv::ConstraintDev *>(lease.host));
         if (int rc = lease.upload(stream, bytes); rc != VMV_OK) return rc;
         return launch(static_cast<const vmv::ConstraintDev *>(lease.dev), stream);
     }
@@ -2108,7 +2096,7 @@ extern "C"
                                      const vmv_constraint_settings *settings, float *d_q_out, float *d_residuals, uint32_t *d_status,
                                      void *stream)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, d_q && d_q_out && d_status, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
@@ -2117,7 +2105,7 @@ extern "C"
     int vmv_constraint_project_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
                                           const vmv_constraint_settings *settings, float *q_out, float *residuals, uint32_t *status)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, q && q_out && status, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         if (int rc = require_device(); rc != VMV_OK) return rc;
@@ -2135,7 +2123,7 @@ extern "C"
     int vmv_constraint_check_batch(int robot, const float *d_q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
                                    const vmv_constraint_settings *settings, uint64_t *d_bits, float *d_residuals, void *stream)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, d_q && d_bits, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
@@ -2144,7 +2132,7 @@ extern "C"
     int vmv_constraint_check_batch_host(int robot, const float *q, size_t n, const vmv_ee_constraint *constraints, size_t n_constraints,
                                         const vmv_constraint_settings *settings, uint64_t *bits, float *residuals)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, q && bits, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         if (int rc = require_device(); rc != VMV_OK) return rc;
@@ -2160,7 +2148,7 @@ extern "C"
     int vmv_constraint_check_motion_batch(int robot, const float *d_a, const float *d_b, size_t n, const vmv_ee_constraint *constraints,
                                           size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *d_ok, void *stream)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, d_a && d_b && d_ok, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         return constraint_launch(c, static_cast<hipStream_t>(stream), [&](const vmv::ConstraintDev *d_cons, hipStream_t st)
@@ -2169,7 +2157,7 @@ extern "C"
     int vmv_constraint_check_motion_batch_host(int robot, const float *a, const float *b, size_t n, const vmv_ee_constraint *constraints,
                                                size_t n_constraints, const vmv_constraint_settings *settings, uint8_t *ok)
     {
-        ConstraintCall c;
+        vmv::ConstraintBand c;
         if (int rc = constraint_checks(robot, a && b && ok, n, constraints, n_constraints, settings, c); rc != VMV_OK) return rc;
         if (n == 0) return VMV_OK;
         if (int rc = require_device(); rc != VMV_OK) return rc;

@@ -219,13 +219,7 @@ extern "C"
         if (S.max_waypoints > vmv::kCartMaxWaypoints) return VMV_ERR_INVALID_ARGUMENT;
         if (S.position_only != 0 && S.position_only != 1) return VMV_ERR_INVALID_ARGUMENT;
         if (n >= vmv::kMultiMaxConfigs) return VMV_ERR_INVALID_ARGUMENT;
-        if (envs && n > 0)
-        {
-            static float nothing[2] = {0.f, 0.f};  // (an empty batch reads and writes no element)
-            static uint64_t no_bits[2] = {0, 0};
-            const std::vector<size_t> zeros(n + 1, 0);
-            if (int rc = vmv_validate_batch_multi(robot, envs, zeros.data(), n, nothing, no_bits, nullptr); rc != VMV_OK) return rc;
-        }
+        if (int rc = vmv::check_env_kinds(robot, envs, n, false); rc != VMV_OK) return rc;
         const auto or_default = [](float v, float d) { return v > 0.0f ? v : d; };
         vmv::CartParams P{};
         P.max_iterations = S.max_iterations ? S.max_iterations : 16u;
@@ -241,23 +235,9 @@ extern "C"
         }
         const vmv::CartHostSettings H{(double) or_default(S.pos_step, 0.01f), (double) or_default(S.rot_step, 0.05f),
                                       S.max_waypoints ? S.max_waypoints : vmv::kCartMaxWaypoints, S.position_only != 0};
-
-        vmv_cartesian *result = new (std::nothrow) vmv_cartesian;
-        if (!result) return VMV_ERR_HIP;
-        result->dim = dim;
-        int rc = VMV_OK;
-        if (n > 0)
-        {
-            if (envs) rc = vmv_env_prepare_multi(robot, envs, n);
-            if (rc == VMV_OK) rc = vmv::cartesian_multi_run(robot, envs, n, starts, targets, P, H, result);
-        }
-        if (rc != VMV_OK)
-        {
-            delete result;
-            return rc;
-        }
-        *out = result;
-        return VMV_OK;
+        return vmv::lockstep_call(robot, envs, n, dim, out, [&](vmv_cartesian *result) {
+            return vmv::cartesian_multi_run(robot, envs, n, starts, targets, P, H, result);
+        });
     }
 
     int vmv_cartesian_summary(const vmv_cartesian *result, uint8_t *status, uint32_t *segments, uint32_t *achieved,

@@ -56,6 +56,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <vector>
 
 namespace vmv
 {
@@ -174,5 +176,60 @@ namespace vmv
         if (const char *err = constraint_refusal(c)) return err;
         constraint_record(c, pos_tol, rot_tol, out);
         return nullptr;
+    }
+
+    // THE BAND OF ONE CALL on the host, as every constraint-taking entry point sets it up: the resolved settings and the
+    // robot's bounds (P), and the caller's constraints - one for every item of the call (P.shared) or one per item; none
+    // (count 0) only where the call allows it (vmv_retime_multi_constrained).
+    struct ConstraintBand
+    {
+        ConstraintParams P;
+        const vmv_ee_constraint *constraints;
+        size_t count;
+    };
+
+    // The checks behind a call's NULL and count checks, in the order every call makes them: the settings, the call's own
+    // check (own_refusal: what it found, nullptr = nothing), every constraint in order.  -> "" with B filled but for its
+    // bounds, or what is wrong; the caller puts its own prefix in front and refuses.
+    inline std::string constraint_band_resolve(const vmv_ee_constraint *constraints, size_t n_constraints,
+                                               const vmv_constraint_settings &settings, const char *own_refusal, ConstraintBand &B)
+    {
+        if (const char *err = constraint_settings(settings, B.P)) return err;
+        if (own_refusal) return own_refusal;
+        for (size_t k = 0; k < n_constraints; ++k)
+            if (const char *err = constraint_refusal(constraints[k])) return "constraints[" + std::to_string(k) + "]: " + err;
+        B.constraints = constraints, B.count = n_constraints, B.P.shared = n_constraints == 1 ? 1u : 0u;
+        return std::string();
+    }
+    // The whole of it for a call whose words are the common ones: "null pointer", then "n_constraints must be 1 or
+    // <items>" (items: the header's name of the call's count n), then constraint_band_resolve.
+    inline std::string constraint_band_checks(const vmv_ee_constraint *constraints, size_t n_constraints,
+                                              const vmv_constraint_settings *settings, size_t n, const char *items,
+                                              const char *own_refusal, ConstraintBand &B)
+    {
+        if (!constraints || !settings) return "null pointer";
+        if (n_constraints != 1 && n_constraints != n) return std::string("n_constraints must be 1 or ") + items;
+        return constraint_band_resolve(constraints, n_constraints, *settings, own_refusal, B);
+    }
+
+    // The robot's joint bounds [lower, lower + span] into the band; the entries from `dim` on are 0.
+    inline void constraint_band_bounds(ConstraintBand &B, const float *lower, const float *span, int dim)
+    {
+        for (int j = 0; j < 16; ++j) B.P.lower[j] = j < dim ? lower[j] : 0.f, B.P.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
+    }
+
+    // The band's records into out [B.count], which the caller provides: pinned memory, a vector's storage.
+    inline void constraint_band_records(const ConstraintBand &B, ConstraintDev *out)
+    {
+        for (size_t k = 0; k < B.count; ++k) constraint_record(B.constraints[k], (double) B.P.pos_tol, (double) B.P.rot_tol, out[k]);
+    }
+
+    // One record per lane from one per item: lane i gets the record of item owner[i].  What a kernel that reads "one record
+    // or one per lane" needs where an item has several lanes (its goals, its edges, its two ends).
+    inline std::vector<ConstraintDev> constraint_band_expand(const ConstraintDev *records, const std::vector<uint32_t> &owner)
+    {
+        std::vector<ConstraintDev> out(owner.size());
+        for (size_t i = 0; i < owner.size(); ++i) out[i] = records[owner[i]];
+        return out;
     }
 }  // namespace vmv

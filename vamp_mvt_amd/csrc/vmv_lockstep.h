@@ -1,6 +1,10 @@
-// vmv_lockstep.h — the host side the lockstep calls share (vmv_rrtc_multi, vmv_simplify_multi, vmv_aorrtc_multi,
-// vmv_fcit_multi; DESIGN §5c "A round"), and the host steps every planner call has around its kernels: the device-free
-// argument checks, the problem uploads and the packed paths of a result (vmv_prm_multi and vmv_roadmaps_* as well).
+// vmv_lockstep.h — the host side the lockstep calls share (vmv_rrtc_multi, vmv_rrtc_multi_goals, vmv_simplify_multi,
+// vmv_aorrtc_multi, vmv_fcit_multi and the _constrained forms of the first three; DESIGN §5c "A round"), and the host steps
+// every planner and path call has around its kernels: the device-free argument checks, the problem uploads and the packed
+// paths of a result (vmv_prm_multi and vmv_roadmaps_* as well), the result object's life cycle (lockstep_call: those, and
+// vmv_optimize_multi, vmv_cartesian_multi, vmv_retime_multi with their _constrained forms), the refusal of the
+// environments' kinds (check_env_kinds: the last three) and a band's records on the device (upload_records: every
+// _constrained call and vmv_retime_band_pairs_host; the band itself is vmv_constraint.h's ConstraintBand).
 //
 // Every item of a call (a planning problem, a path) is a state machine in device memory.  One round = the call's step
 // kernel (one workgroup per unfinished item: consumes the answers to the item's previous questions, advances its state and
@@ -52,6 +56,14 @@ namespace vmv
         const hipError_t e_ = (call);                         \
         if (e_ != hipSuccess) return hip_status(e_, #call);   \
     } while (0)
+
+    // `count` constraint records on the device, in memory of `mem`; a set-up copy, synchronous (the host array may go)
+    inline int upload_records(DeviceBuffers &mem, const ConstraintDev *records, size_t count, ConstraintDev **d_records)
+    {
+        VMV_LOCKSTEP_HIP(mem.alloc(d_records, count));
+        if (count) VMV_LOCKSTEP_HIP(hipMemcpy(*d_records, records, count * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+        return VMV_OK;
+    }
 
     struct LockstepArrays  // what the rounds of one call read and write (LockstepBuffers::arrays())
     {
@@ -171,6 +183,18 @@ namespace vmv
             if (!envs[k]) return VMV_ERR_INVALID_ARGUMENT;
         return VMV_OK;
     }
+    // The kinds of environment a call refuses, behind its argument checks: the checks vmv_validate_batch_multi - or, with
+    // `clearance`, vmv_clearance_batch_multi, which refuses more kinds - makes of its handles, through an empty batch of it
+    // (no device, no element read or written).  NULL envs: nothing to check.
+    inline int check_env_kinds(int robot, const vmv_env *const *envs, size_t n, bool clearance)
+    {
+        if (!envs || n == 0) return VMV_OK;
+        static float nothing[2] = {0.f, 0.f};
+        static uint64_t no_bits[2] = {0, 0};
+        const std::vector<size_t> zeros(n + 1, 0);
+        return clearance ? vmv_clearance_batch_multi(robot, envs, zeros.data(), n, nothing, nothing, nullptr, nullptr)
+                         : vmv_validate_batch_multi(robot, envs, zeros.data(), n, nothing, no_bits, nullptr);
+    }
     // whether `draws` Halton elements after every skip stay within the sequence's limit (NULL skips = zeros)
     inline bool halton_skips_ok(const uint64_t *skips, size_t n, uint64_t draws)
     {
@@ -234,8 +258,8 @@ namespace vmv
     }
 
     // What follows an entry point's own argument checks: the result object, vmv_env_prepare_multi (the environments' own
-    // checks; builds the robot parts not yet built in one batch), then run(result) if there is an item at all.  *out is
-    // written on success only.
+    // checks; builds the robot parts not yet built in one batch; not with envs == NULL, where the call allows that), then
+    // run(result) if there is an item at all.  *out is written on success only.
     template <typename Result, typename Run>
     int lockstep_call(int robot, const vmv_env *const *envs, size_t n_items, int dim, Result **out, Run &&run)
     {
@@ -245,7 +269,7 @@ namespace vmv
         int rc = VMV_OK;
         if (n_items > 0)
         {
-            rc = vmv_env_prepare_multi(robot, envs, n_items);
+            if (envs) rc = vmv_env_prepare_multi(robot, envs, n_items);
             if (rc == VMV_OK) rc = run(result);
         }
         if (rc != VMV_OK)

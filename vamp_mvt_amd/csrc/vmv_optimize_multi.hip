@@ -326,13 +326,6 @@ namespace vmv
             return hip_status(e, what);
         }
 
-        struct OptConstraints  // vmv_optimize_multi_constrained: the caller's constraints (1 or n_paths), the resolved settings
-        {
-            ConstraintParams P;
-            const vmv_ee_constraint *constraints;
-            size_t count;
-        };
-
         // row -> active index of the packed waypoints of `active` (OptBand::row_path)
         std::vector<uint32_t> rows_of(const std::vector<uint32_t> &active, const size_t *offsets)
         {
@@ -346,7 +339,7 @@ namespace vmv
         // in its initial mode over the waypoints of the paths of 3 and more whose ends passed, which projects their inner
         // waypoints in place.  out_of_band[p] = 1: an end out of band or a projection that did not converge.  x0: the
         // input with the inner waypoints of the other paths projected (iterate 0).  d_recs: one record (shared) or one per path.
-        int optimize_band_input(int robot, const OptConstraints &cb, const ConstraintDev *d_recs, const std::vector<ConstraintDev> &recs,
+        int optimize_band_input(int robot, const ConstraintBand &cb, const ConstraintDev *d_recs, const std::vector<ConstraintDev> &recs,
                                 const std::vector<uint32_t> &finite, size_t n, const float *points, const size_t *offsets,
                                 const std::vector<uint64_t> &offsets64, size_t dim, hipStream_t stream, std::vector<uint8_t> &out_of_band,
                                 std::vector<float> &x0)
@@ -372,11 +365,10 @@ namespace vmv
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_ends, ends.data(), ends.size() * 4, hipMemcpyHostToDevice, stream));
             if (!cb.P.shared)
             {
-                std::vector<ConstraintDev> per_end(2 * m);
-                for (size_t s = 0; s < m; ++s) per_end[2 * s] = per_end[2 * s + 1] = recs[finite[s]];
+                std::vector<uint32_t> owner(2 * m);
+                for (size_t s = 0; s < m; ++s) owner[2 * s] = owner[2 * s + 1] = finite[s];
                 ConstraintDev *d = nullptr;
-                VMV_LOCKSTEP_HIP(tmp.alloc(&d, 2 * m));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d, per_end.data(), 2 * m * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                if (int rc = upload_records(tmp, constraint_band_expand(recs.data(), owner).data(), 2 * m, &d); rc != VMV_OK) return rc;
                 d_end_recs = d;
             }
             if (int rc = L.constraint_check(cb.P, d_end_recs, d_ends, 2 * m, d_bits, nullptr, stream); rc != VMV_OK) return rc;
@@ -430,7 +422,7 @@ namespace vmv
         // robot's part built.
         // cb: vmv_optimize_multi_constrained's constraints and resolved settings (NULL: vmv_optimize_multi).
         int optimize_multi_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
-                               const OptParams &P, uint32_t validate_every, vmv_optimized *res, const OptConstraints *cb = nullptr)
+                               const OptParams &P, uint32_t validate_every, vmv_optimized *res, const ConstraintBand *cb = nullptr)
         {
             const size_t dim = P.dim, total = offsets[n];
             hipStream_t stream = nullptr;
@@ -470,9 +462,8 @@ namespace vmv
             {
                 res->held.assign(n, 0);
                 recs.resize(cb->count);
-                for (size_t k = 0; k < cb->count; ++k) constraint_record(cb->constraints[k], (double) cb->P.pos_tol, (double) cb->P.rot_tol, recs[k]);
-                VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, cb->count));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, recs.data(), cb->count * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                constraint_band_records(*cb, recs.data());
+                if (int rc = upload_records(mem, recs.data(), cb->count, &d_recs); rc != VMV_OK) return rc;
                 std::vector<uint32_t> finite(two);
                 finite.insert(finite.end(), active.begin(), active.end());
                 std::vector<uint8_t> out_of_band;
@@ -534,7 +525,6 @@ namespace vmv
             uint8_t *d_band_ok = nullptr;
             uint32_t *d_rows = nullptr, *d_held = nullptr;
             ConstraintDev *d_edge_recs = nullptr;
-            std::vector<ConstraintDev> edge_recs;
             if (cb)
             {
                 VMV_LOCKSTEP_HIP(mem.alloc(&d_band_ok, all_edges));
@@ -588,13 +578,12 @@ namespace vmv
                 }
                 if (d_edge_recs)  // edge e of active path a: the path's record; behind them the 2-waypoint paths' (first validation)
                 {
-                    edge_recs.clear();
-                    for (size_t a = 0; a < na; ++a)
-                        edge_recs.insert(edge_recs.end(), offsets[active[a] + 1] - offsets[active[a]] - 1, recs[active[a]]);
-                    if (na == na0)
-                        for (const uint32_t p : two) edge_recs.push_back(recs[p]);
-                    if (!edge_recs.empty())
-                        VMV_LOCKSTEP_HIP(hipMemcpy(d_edge_recs, edge_recs.data(), edge_recs.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                    std::vector<uint32_t> owner;
+                    for (size_t a = 0; a < na; ++a) owner.insert(owner.end(), offsets[active[a] + 1] - offsets[active[a]] - 1, active[a]);
+                    if (na == na0) owner.insert(owner.end(), two.begin(), two.end());
+                    if (!owner.empty())
+                        VMV_LOCKSTEP_HIP(hipMemcpy(d_edge_recs, constraint_band_expand(recs.data(), owner).data(),
+                                                   owner.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
                 }
                 return VMV_OK;
             };
@@ -735,7 +724,7 @@ namespace vmv
         int optimize_checks(int robot, const vmv_env *const *envs, size_t n_paths, const float *points, const size_t *offsets,
                             const vmv_optimize_settings *settings, vmv_optimized *const *out, OptParams &P)
         {
-            // device-free checks, in vmv_simplify_multi's order; the refused kinds follow (optimize_env_kinds), the rest of
+            // device-free checks, in vmv_simplify_multi's order; the refused kinds follow (check_env_kinds), the rest of
             // the environments' checks are vmv_env_prepare_multi's
             const int dim = vmv_robot_dimension(robot);
             if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
@@ -773,15 +762,6 @@ namespace vmv
             return VMV_OK;
         }
 
-        // The environments' kinds, behind the argument checks of both entry points: vmv_clearance_batch_multi's own check
-        // through an empty batch of it (no device, no element read or written)
-        int optimize_env_kinds(int robot, const vmv_env *const *envs, size_t n_paths)
-        {
-            if (n_paths == 0) return VMV_OK;
-            static float nothing[2] = {0.f, 0.f};
-            const std::vector<size_t> zeros(n_paths + 1, 0);
-            return vmv_clearance_batch_multi(robot, envs, zeros.data(), n_paths, nothing, nothing, nullptr, nullptr);
-        }
     }  // namespace
 }  // namespace vmv
 
@@ -792,7 +772,7 @@ extern "C"
     {
         vmv::OptParams P{};
         if (int rc = vmv::optimize_checks(robot, envs, n_paths, points, offsets, settings, out, P); rc != VMV_OK) return rc;
-        if (int rc = vmv::optimize_env_kinds(robot, envs, n_paths); rc != VMV_OK) return rc;
+        if (int rc = vmv::check_env_kinds(robot, envs, n_paths, true); rc != VMV_OK) return rc;
         return vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_optimized *res) {
             return vmv::optimize_multi_run(robot, envs, n_paths, points, offsets, P, settings->validate_every, res);
         });
@@ -805,16 +785,11 @@ extern "C"
         // vmv_optimize_multi's checks in its order, then the constraint's own in vmv_constraint_project_batch's; none needs a device
         vmv::OptParams P{};
         if (int rc = vmv::optimize_checks(robot, envs, n_paths, points, offsets, settings, out, P); rc != VMV_OK) return rc;
-        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
-        if (n_constraints != 1 && n_constraints != n_paths) return vmv::refuse_argument("n_constraints must be 1 or n_paths");
-        vmv::OptConstraints cb{};
-        if (const char *err = vmv::constraint_settings(*constraint_settings, cb.P)) return vmv::refuse_argument(err);
-        for (size_t k = 0; k < n_constraints; ++k)
-            if (const char *err = vmv::constraint_refusal(constraints[k]))
-                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
-        cb.constraints = constraints, cb.count = n_constraints, cb.P.shared = n_constraints == 1 ? 1u : 0u;
+        vmv::ConstraintBand cb{};
+        const std::string err = vmv::constraint_band_checks(constraints, n_constraints, constraint_settings, n_paths, "n_paths", nullptr, cb);
+        if (!err.empty()) return vmv::refuse_argument(err.c_str());
         for (uint32_t j = 0; j < 16; ++j) cb.P.lower[j] = j < P.dim ? P.lower[j] : 0.f, cb.P.upper[j] = j < P.dim ? P.upper[j] : 0.f;
-        if (int rc = vmv::optimize_env_kinds(robot, envs, n_paths); rc != VMV_OK) return rc;
+        if (int rc = vmv::check_env_kinds(robot, envs, n_paths, true); rc != VMV_OK) return rc;
         const int rc = vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_optimized *res) {
             return vmv::optimize_multi_run(robot, envs, n_paths, points, offsets, P, settings->validate_every, res, &cb);
         });

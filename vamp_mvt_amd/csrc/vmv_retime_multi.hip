@@ -264,6 +264,83 @@ namespace vmv
             bool stop_at_waypoints;
         };
 
+        // What the profile and sample kernels of one pass over some paths read, as the host lays it out
+        struct RetimeLayout
+        {
+            std::vector<RetimePiece> pieces;
+            std::vector<uint32_t> corner;  // per piece: the distinct waypoint its blend rounds (the constrained call's blame)
+            std::vector<RetimePathDev> recs, srecs;  // of the paths that take part; of those that are sampled
+            std::vector<uint32_t> part, sampled, sample_lo, ends;  // ends: per sampled path its first and last input waypoint
+            uint64_t grid = 0, rows = 0;
+        };
+
+        // Host only: the paths of `list` set up (levels(p): a path's corner levels or nullptr) -> pieces, records and the
+        // packed grid of those that take part; the others get their status and sample count.  each(p, H): the caller's own
+        // look at a path's set-up, before anything of H is moved from.  `call` names the entry point in the message.
+        template <typename Levels, typename Each>
+        int retime_lay_out_paths(const std::vector<uint32_t> &list, const float *points, const size_t *offsets, size_t dim,
+                                 const RetimeHostSettings &S, bool stop_at_waypoints, uint32_t halvings, const char *call, Levels &&levels,
+                                 Each &&each, vmv_trajectories *res, RetimeLayout &L)
+        {
+            for (const uint32_t p : list)
+            {
+                const size_t count = offsets[p + 1] - offsets[p];
+                RetimePath H = retime_path(count ? points + offsets[p] * dim : nullptr, count, dim, S.blend, S.grid_step, S.max_grid,
+                                           stop_at_waypoints, levels(p), halvings);
+                res->intervals[p] = (uint32_t) std::min<uint64_t>(H.intervals, 0xffffffffull);
+                each(p, H);
+                if (H.what == kRetimeNonFinite) res->status[p] = VMV_RETIME_NON_FINITE;
+                else if (H.what == kRetimeTooLong) res->status[p] = VMV_RETIME_TOO_LONG;
+                else if (H.what == kRetimeTrivial) res->samples[p] = H.distinct ? 1u : 0u;
+                else
+                {
+                    L.recs.push_back(RetimePathDev{(uint32_t) L.pieces.size(), (uint32_t) H.pieces.size(), (uint32_t) H.intervals, (uint32_t) L.grid});
+                    L.pieces.insert(L.pieces.end(), H.pieces.begin(), H.pieces.end());
+                    L.corner.insert(L.corner.end(), H.corner.begin(), H.corner.end());
+                    L.grid += H.intervals + 1u;
+                    L.part.push_back(p);
+                    if (L.grid >= kMultiMaxConfigs || L.pieces.size() >= kMultiMaxConfigs)
+                        return refuse_argument((std::string(call) + ": the paths' grids together have 2^31 points or more").c_str());
+                }
+            }
+            return VMV_OK;
+        }
+
+        // Host only: from the profile's T [L.grid] the durations, the sample counts and rows of the paths that are sampled,
+        // the status of those that are not.
+        inline int retime_lay_out_samples(const std::vector<float> &T, const size_t *offsets, const RetimeHostSettings &S, const char *call,
+                                          vmv_trajectories *res, RetimeLayout &L)
+        {
+            for (size_t a = 0; a < L.part.size(); ++a)
+            {
+                const uint32_t p = L.part[a];
+                const RetimePathDev &R = L.recs[a];
+                bool finite = true;
+                for (uint32_t i = 0; i <= R.N && finite; ++i) finite = std::isfinite(T[R.grid_lo + i]);
+                if (!finite)
+                {
+                    res->status[p] = VMV_RETIME_STALLED;
+                    continue;
+                }
+                const float Tp = T[R.grid_lo + R.N];
+                res->duration[p] = Tp;
+                const uint64_t count = retime_samples(Tp, S.dt);
+                if (count > S.max_samples)
+                {
+                    res->status[p] = VMV_RETIME_TOO_LONG;
+                    continue;
+                }
+                res->samples[p] = (uint32_t) count;
+                L.sample_lo.push_back((uint32_t) L.rows), L.sampled.push_back(p), L.srecs.push_back(R);
+                L.ends.push_back((uint32_t) offsets[p]), L.ends.push_back((uint32_t) (offsets[p + 1] - 1));
+                L.rows += count;
+                if (L.rows >= kMultiMaxConfigs)
+                    return refuse_argument((std::string(call) + ": the trajectories together have 2^31 samples or more").c_str());
+            }
+            L.sample_lo.push_back((uint32_t) L.rows);
+            return VMV_OK;
+        }
+
         // The caller has checked every argument, n > 0, and (with envs) every environment is finalized on the current
         // device with the robot's part built.
         int retime_multi_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
@@ -276,34 +353,21 @@ namespace vmv
             res->first_invalid.assign(n, VMV_RETIME_NONE), res->duration.assign(n, 0.0f);
 
             // the paths: every N, the packed grid, who takes part
-            std::vector<RetimePiece> pieces;
-            std::vector<RetimePathDev> recs;
-            std::vector<uint32_t> part;
-            uint64_t grid = 0;
-            for (size_t p = 0; p < n; ++p)
-            {
-                const size_t count = offsets[p + 1] - offsets[p];
-                const RetimePath H = retime_path(count ? points + offsets[p] * dim : nullptr, count, dim, S.blend, S.grid_step,
-                                                 S.max_grid, S.stop_at_waypoints);
-                res->intervals[p] = (uint32_t) std::min<uint64_t>(H.intervals, 0xffffffffull);
-                if (H.what == kRetimeNonFinite) res->status[p] = VMV_RETIME_NON_FINITE;
-                else if (H.what == kRetimeTooLong) res->status[p] = VMV_RETIME_TOO_LONG;
-                else if (H.what == kRetimeTrivial) res->samples[p] = H.distinct ? 1u : 0u;
-                else
-                {
-                    recs.push_back(RetimePathDev{(uint32_t) pieces.size(), (uint32_t) H.pieces.size(), (uint32_t) H.intervals, (uint32_t) grid});
-                    pieces.insert(pieces.end(), H.pieces.begin(), H.pieces.end());
-                    grid += H.intervals + 1u;
-                    part.push_back((uint32_t) p);
-                    if (grid >= kMultiMaxConfigs || pieces.size() >= kMultiMaxConfigs)
-                        return refuse_argument("vmv_retime_multi: the paths' grids together have 2^31 points or more");
-                }
-            }
+            RetimeLayout Y;
+            std::vector<uint32_t> all(n);
+            for (size_t p = 0; p < n; ++p) all[p] = (uint32_t) p;
+            if (int rc = retime_lay_out_paths(all, points, offsets, dim, S, S.stop_at_waypoints, 0u, "vmv_retime_multi",
+                                              [](uint32_t) -> const uint8_t * { return nullptr; }, [](uint32_t, RetimePath &) {}, res, Y);
+                rc != VMV_OK)
+                return rc;
+            const std::vector<RetimePiece> &pieces = Y.pieces;
+            const std::vector<RetimePathDev> &recs = Y.recs, &srecs = Y.srecs;
+            const std::vector<uint32_t> &part = Y.part, &sampled = Y.sampled, &sample_lo = Y.sample_lo;
+            const uint64_t grid = Y.grid;
 
             int device = 0;
             VMV_LOCKSTEP_HIP(hipGetDevice(&device));  // (a call whose paths are all trivial needs a device as well)
             std::vector<float> s_times, s_pos, s_vel, s_acc;  // the sampled paths' rows, in `sampled` order
-            std::vector<uint32_t> sampled, sample_lo;
             if (!part.empty())
             {
                 const auto padded = [](size_t bytes) { return (bytes + 255) & ~size_t{255}; };
@@ -332,32 +396,8 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
 
                 // the durations, the samples' layout, who is sampled
-                std::vector<RetimePathDev> srecs;
-                uint64_t rows = 0;
-                for (size_t a = 0; a < np; ++a)
-                {
-                    const uint32_t p = part[a];
-                    bool finite = true;
-                    for (uint32_t i = 0; i <= recs[a].N && finite; ++i) finite = std::isfinite(T[recs[a].grid_lo + i]);
-                    if (!finite)
-                    {
-                        res->status[p] = VMV_RETIME_STALLED;
-                        continue;
-                    }
-                    const float Tp = T[recs[a].grid_lo + recs[a].N];
-                    res->duration[p] = Tp;
-                    const uint64_t count = retime_samples(Tp, S.dt);
-                    if (count > S.max_samples)
-                    {
-                        res->status[p] = VMV_RETIME_TOO_LONG;
-                        continue;
-                    }
-                    res->samples[p] = (uint32_t) count;
-                    sample_lo.push_back((uint32_t) rows), sampled.push_back(p), srecs.push_back(recs[a]);
-                    rows += count;
-                    if (rows >= kMultiMaxConfigs) return refuse_argument("vmv_retime_multi: the trajectories together have 2^31 samples or more");
-                }
-                sample_lo.push_back((uint32_t) rows);
+                if (int rc = retime_lay_out_samples(T, offsets, S, "vmv_retime_multi", res, Y); rc != VMV_OK) return rc;
+                const uint64_t rows = Y.rows;
                 if (!sampled.empty())
                 {
                     const size_t ns = sampled.size();
@@ -538,9 +578,7 @@ namespace vmv
 
         struct RetimeConstrained  // the constrained call's own settings, resolved, and the caller's constraints (0, 1 or n)
         {
-            ConstraintParams P;
-            const vmv_ee_constraint *constraints;
-            size_t count;
+            ConstraintBand band;
             uint32_t halvings, max_rounds;
         };
 
@@ -552,7 +590,8 @@ namespace vmv
         {
             const size_t dim = (size_t) res->dim;
             const RobotLaunchers &L = robot_launchers(robot);
-            const bool asks = envs != nullptr || C.count != 0;
+            const ConstraintBand &band = C.band;
+            const bool asks = envs != nullptr || band.count != 0;
             const uint8_t stop_level = (uint8_t) (C.halvings + 1u);
             hipStream_t stream = nullptr;
             res->n = n;
@@ -571,12 +610,11 @@ namespace vmv
             for (size_t j = 0; j < dim; ++j) limits[j] = vel_limits[j], limits[16 + j] = acc_limits[j];
             if (offsets[n]) VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_points, points, offsets[n] * dim * 4, hipMemcpyHostToDevice, stream));
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_limits, limits, sizeof(limits), hipMemcpyHostToDevice, stream));
-            std::vector<ConstraintDev> cons(C.count);
-            if (C.count)
+            std::vector<ConstraintDev> cons(band.count);
+            if (band.count)
             {
-                for (size_t k = 0; k < C.count; ++k) constraint_record(C.constraints[k], (double) C.P.pos_tol, (double) C.P.rot_tol, cons[k]);
-                VMV_LOCKSTEP_HIP(call.alloc(&d_recs, C.count));
-                VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_recs, cons.data(), C.count * sizeof(ConstraintDev), hipMemcpyHostToDevice, stream));
+                constraint_band_records(band, cons.data());
+                if (int rc = upload_records(call, cons.data(), band.count, &d_recs); rc != VMV_OK) return rc;
             }
             VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
 
@@ -591,41 +629,26 @@ namespace vmv
             for (uint32_t round = 1; !live.empty(); ++round)
             {
                 // 1. set up, profile, sample
-                std::vector<RetimePiece> pieces;
-                std::vector<uint32_t> corner;  // per piece of the round
-                std::vector<RetimePathDev> recs;
-                std::vector<uint32_t> part;
-                uint64_t grid = 0;
-                for (const uint32_t p : live)
-                {
-                    const size_t count = offsets[p + 1] - offsets[p];
-                    RetimePath H = retime_path(count ? points + offsets[p] * dim : nullptr, count, dim, S.blend, S.grid_step, S.max_grid,
-                                               false, level[p].data(), C.halvings);
-                    res->rounds[p] = round, res->status[p] = VMV_RETIME_COMPLETE, res->samples[p] = 0, res->duration[p] = 0.0f;
-                    res->intervals[p] = (uint32_t) std::min<uint64_t>(H.intervals, 0xffffffffull);
-                    kept[p].swap(H.kept);
-                    if (H.what == kRetimeNonFinite) res->status[p] = VMV_RETIME_NON_FINITE;
-                    else if (H.what == kRetimeTooLong) res->status[p] = VMV_RETIME_TOO_LONG;
-                    else if (H.what == kRetimeTrivial)
-                    {
-                        res->samples[p] = H.distinct ? 1u : 0u;
-                        if (H.distinct)
-                        {
-                            o_t[p].assign(1, 0.0f), o_v[p].assign(dim, 0.0f), o_a[p].assign(dim, 0.0f);
-                            o_p[p].assign(points + offsets[p] * dim, points + (offsets[p] + 1) * dim);
-                        }
-                    }
-                    else
-                    {
-                        recs.push_back(RetimePathDev{(uint32_t) pieces.size(), (uint32_t) H.pieces.size(), (uint32_t) H.intervals, (uint32_t) grid});
-                        pieces.insert(pieces.end(), H.pieces.begin(), H.pieces.end());
-                        corner.insert(corner.end(), H.corner.begin(), H.corner.end());
-                        grid += H.intervals + 1u;
-                        part.push_back(p);
-                        if (grid >= kMultiMaxConfigs || pieces.size() >= kMultiMaxConfigs)
-                            return refuse_argument("vmv_retime_multi_constrained: the paths' grids together have 2^31 points or more");
-                    }
-                }
+                RetimeLayout Y;
+                if (int rc = retime_lay_out_paths(
+                        live, points, offsets, dim, S, false, C.halvings, "vmv_retime_multi_constrained",
+                        [&](uint32_t p) -> const uint8_t * { return level[p].data(); },
+                        [&](uint32_t p, RetimePath &H) {
+                            res->rounds[p] = round, res->status[p] = VMV_RETIME_COMPLETE, res->samples[p] = 0, res->duration[p] = 0.0f;
+                            kept[p].swap(H.kept);
+                            if (H.what == kRetimeTrivial && H.distinct)
+                            {
+                                o_t[p].assign(1, 0.0f), o_v[p].assign(dim, 0.0f), o_a[p].assign(dim, 0.0f);
+                                o_p[p].assign(points + offsets[p] * dim, points + (offsets[p] + 1) * dim);
+                            }
+                        },
+                        res, Y);
+                    rc != VMV_OK)
+                    return rc;
+                const std::vector<RetimePiece> &pieces = Y.pieces;
+                const std::vector<uint32_t> &corner = Y.corner, &part = Y.part, &sampled = Y.sampled, &sample_lo = Y.sample_lo, &ends = Y.ends;
+                const std::vector<RetimePathDev> &recs = Y.recs, &srecs = Y.srecs;
+                const uint64_t grid = Y.grid;
                 live.clear();
                 if (part.empty()) break;
 
@@ -649,35 +672,8 @@ namespace vmv
                 VMV_LOCKSTEP_HIP(hipMemcpyAsync(T.data(), d_T, grid * 4, hipMemcpyDeviceToHost, stream));
                 VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
 
-                std::vector<RetimePathDev> srecs;
-                std::vector<uint32_t> sampled, sample_lo, ends;
-                uint64_t rows = 0;
-                for (size_t a = 0; a < np; ++a)
-                {
-                    const uint32_t p = part[a];
-                    bool finite = true;
-                    for (uint32_t i = 0; i <= recs[a].N && finite; ++i) finite = std::isfinite(T[recs[a].grid_lo + i]);
-                    if (!finite)
-                    {
-                        res->status[p] = VMV_RETIME_STALLED;
-                        continue;
-                    }
-                    const float Tp = T[recs[a].grid_lo + recs[a].N];
-                    res->duration[p] = Tp;
-                    const uint64_t count = retime_samples(Tp, S.dt);
-                    if (count > S.max_samples)
-                    {
-                        res->status[p] = VMV_RETIME_TOO_LONG;
-                        continue;
-                    }
-                    res->samples[p] = (uint32_t) count;
-                    sample_lo.push_back((uint32_t) rows), sampled.push_back(p), srecs.push_back(recs[a]);
-                    ends.push_back((uint32_t) offsets[p]), ends.push_back((uint32_t) (offsets[p + 1] - 1));
-                    rows += count;
-                    if (rows >= kMultiMaxConfigs)
-                        return refuse_argument("vmv_retime_multi_constrained: the trajectories together have 2^31 samples or more");
-                }
-                sample_lo.push_back((uint32_t) rows);
+                if (int rc = retime_lay_out_samples(T, offsets, S, "vmv_retime_multi_constrained", res, Y); rc != VMV_OK) return rc;
+                const uint64_t rows = Y.rows;
                 if (sampled.empty()) break;
 
                 const size_t ns = sampled.size();
@@ -722,15 +718,15 @@ namespace vmv
                             return rc;
                         ++res->validation_calls;
                     }
-                    if (C.count)
+                    if (band.count)
                     {
                         VMV_LOCKSTEP_HIP(mem.alloc(&d_band, rows));
-                        if (!C.P.shared)
+                        if (!band.P.shared)
                         {
                             VMV_LOCKSTEP_HIP(mem.alloc(&d_rec_of, ns));
                             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_rec_of, sampled.data(), ns * 4, hipMemcpyHostToDevice, stream));
                         }
-                        if (int rc = L.retime_band(C.P, d_recs, d_rec_of, d_slo, (uint32_t) ns, d_p, (uint32_t) rows, d_band, stream); rc != VMV_OK)
+                        if (int rc = L.retime_band(band.P, d_recs, d_rec_of, d_slo, (uint32_t) ns, d_p, (uint32_t) rows, d_band, stream); rc != VMV_OK)
                             return rc;
                     }
                     res->questions += pairs;
@@ -865,13 +861,7 @@ extern "C"
             if (offsets[k + 1] < offsets[k]) return refuse_argument("offsets decrease at " + std::to_string(k + 1));
         if (n > 0 && offsets[n] >= vmv::kMultiMaxConfigs) return refuse_argument("2^31 waypoints or more");
         if (n > 0 && offsets[n] > 0 && !points) return refuse_argument("points is NULL");
-        if (envs && n > 0)
-        {
-            static float nothing[2] = {0.f, 0.f};  // (an empty batch reads and writes no element)
-            static uint64_t no_bits[2] = {0, 0};
-            const std::vector<size_t> zeros(n + 1, 0);
-            if (int rc = vmv_validate_batch_multi(robot, envs, zeros.data(), n, nothing, no_bits, nullptr); rc != VMV_OK) return rc;
-        }
+        if (int rc = vmv::check_env_kinds(robot, envs, n, false); rc != VMV_OK) return rc;
         const auto or_default = [](float v, float d) { return v > 0.0f ? v : d; };
         H = vmv::RetimeHostSettings{(double) or_default(S.blend, 0.1f), (double) or_default(S.grid_step, 0.02f), or_default(S.dt, 0.01f),
                                     S.max_grid ? S.max_grid : vmv::kRetimeMaxGrid, S.max_samples ? S.max_samples : 65536u,
@@ -886,23 +876,9 @@ extern "C"
         vmv::RetimeHostSettings H;
         if (int rc = retime_checks("vmv_retime_multi", robot, envs, n, points, offsets, vel_limits, acc_limits, settings, out, dim, H); rc != VMV_OK)
             return rc;
-
-        vmv_trajectories *result = new (std::nothrow) vmv_trajectories;
-        if (!result) return VMV_ERR_HIP;
-        result->dim = dim;
-        int rc = VMV_OK;
-        if (n > 0)
-        {
-            if (envs) rc = vmv_env_prepare_multi(robot, envs, n);
-            if (rc == VMV_OK) rc = vmv::retime_multi_run(robot, envs, n, points, offsets, vel_limits, acc_limits, H, result);
-        }
-        if (rc != VMV_OK)
-        {
-            delete result;
-            return rc;
-        }
-        *out = result;
-        return VMV_OK;
+        return vmv::lockstep_call(robot, envs, n, dim, out, [&](vmv_trajectories *result) {
+            return vmv::retime_multi_run(robot, envs, n, points, offsets, vel_limits, acc_limits, H, result);
+        });
     }
 
     int vmv_retime_multi_constrained(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
@@ -924,36 +900,21 @@ extern "C"
         C.halvings = settings->blend_halvings ? settings->blend_halvings : 3u;
         C.max_rounds = settings->max_rounds ? settings->max_rounds : 8u;
         if (n_constraints != 0 && n_constraints != 1 && n_constraints != n) return refuse_argument("n_constraints is neither 0, 1 nor n");
-        if (n_constraints)
+        if (n_constraints)  // (this call's words for the pointers and the count, the band's for the rest)
         {
             if (!constraints) return refuse_argument("constraints is NULL");
             if (!constraint_settings) return refuse_argument("constraint_settings is NULL");
-            if (const char *err = vmv::constraint_settings(*constraint_settings, C.P)) return refuse_argument(err);
-            for (size_t k = 0; k < n_constraints; ++k)
-                if (const char *err = vmv::constraint_refusal(constraints[k]))
-                    return refuse_argument("constraints[" + std::to_string(k) + "]: " + err);
-            C.constraints = constraints, C.count = n_constraints, C.P.shared = n_constraints == 1 ? 1u : 0u;
+            const std::string err = vmv::constraint_band_resolve(constraints, n_constraints, *constraint_settings, nullptr, C.band);
+            if (!err.empty()) return refuse_argument(err);
             float lower[16], span[16], descale[16];
             if (int rb = vmv_robot_bounds(robot, lower, span, descale); rb != VMV_OK) return rb;
-            for (int j = 0; j < 16; ++j) C.P.lower[j] = j < dim ? lower[j] : 0.f, C.P.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
+            vmv::constraint_band_bounds(C.band, lower, span, dim);
         }
-
-        vmv_trajectories *result = new (std::nothrow) vmv_trajectories;
-        if (!result) return VMV_ERR_HIP;
-        result->dim = dim, result->levelled = true;
-        int rc = VMV_OK;
-        if (n > 0)
-        {
-            if (envs) rc = vmv_env_prepare_multi(robot, envs, n);
-            if (rc == VMV_OK) rc = vmv::retime_constrained_run(robot, envs, n, points, offsets, vel_limits, acc_limits, H, C, result);
-        }
-        if (rc != VMV_OK)
-        {
-            delete result;
-            return rc;
-        }
-        *out = result;
-        return VMV_OK;
+        const int rc = vmv::lockstep_call(robot, envs, n, dim, out, [&](vmv_trajectories *result) {
+            return vmv::retime_constrained_run(robot, envs, n, points, offsets, vel_limits, acc_limits, H, C, result);
+        });
+        if (rc == VMV_OK) (*out)->levelled = true;
+        return rc;
     }
 
     // NOT part of the supported interface and not in the public header: retime_band_kernel on its own, for the test that
@@ -976,15 +937,12 @@ extern "C"
             if (sample_offsets[a + 1] <= sample_offsets[a]) return refuse_argument("every list needs a row");
         const size_t rows = sample_offsets[n_paths];
         if (rows >= vmv::kMultiMaxConfigs) return refuse_argument("2^31 rows or more");
-        vmv::ConstraintParams P{};
-        if (const char *err = vmv::constraint_settings(*settings, P)) return refuse_argument(err);
+        vmv::ConstraintBand band{};  // (the band kernel reads no joint bounds: they stay 0)
+        const std::string err = vmv::constraint_band_resolve(constraints, n_constraints, *settings, nullptr, band);
+        if (!err.empty()) return refuse_argument(err);
+        const vmv::ConstraintParams &P = band.P;
         std::vector<vmv::ConstraintDev> cons(n_constraints);
-        for (size_t k = 0; k < n_constraints; ++k)
-        {
-            if (const char *err = vmv::constraint_refusal(constraints[k])) return refuse_argument("constraints[" + std::to_string(k) + "]: " + err);
-            vmv::constraint_record(constraints[k], (double) P.pos_tol, (double) P.rot_tol, cons[k]);
-        }
-        P.shared = n_constraints == 1 ? 1u : 0u;
+        vmv::constraint_band_records(band, cons.data());
         std::vector<uint32_t> slo(n_paths + 1), rec_of(n_paths);
         for (size_t a = 0; a <= n_paths; ++a) slo[a] = (uint32_t) sample_offsets[a];
         for (size_t a = 0; a < n_paths; ++a) rec_of[a] = (uint32_t) a;
@@ -995,12 +953,11 @@ extern "C"
         uint32_t *d_slo = nullptr, *d_rec_of = nullptr;
         float *d_p = nullptr;
         uint8_t *d_ok = nullptr;
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, n_constraints));
+        if (int rc = vmv::upload_records(mem, cons.data(), n_constraints, &d_recs); rc != VMV_OK) return rc;
         VMV_LOCKSTEP_HIP(mem.alloc(&d_slo, n_paths + 1));
         VMV_LOCKSTEP_HIP(mem.alloc(&d_rec_of, n_paths));
         VMV_LOCKSTEP_HIP(mem.alloc(&d_p, rows * (size_t) dim));
         VMV_LOCKSTEP_HIP(mem.alloc(&d_ok, rows));
-        VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, cons.data(), n_constraints * sizeof(vmv::ConstraintDev), hipMemcpyHostToDevice));
         VMV_LOCKSTEP_HIP(hipMemcpy(d_slo, slo.data(), (n_paths + 1) * 4, hipMemcpyHostToDevice));
         VMV_LOCKSTEP_HIP(hipMemcpy(d_rec_of, rec_of.data(), n_paths * 4, hipMemcpyHostToDevice));
         VMV_LOCKSTEP_HIP(hipMemcpy(d_p, positions, rows * (size_t) dim * 4, hipMemcpyHostToDevice));

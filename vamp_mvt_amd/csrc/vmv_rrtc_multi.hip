@@ -477,17 +477,16 @@ namespace vmv
     // as a call of their own (a problem's result is its own) with their in-band goals, the round kernel in every round.
     int rrtc_constrained_run(int robot, int dim, const vmv_env *const *envs, size_t n, const float *starts, const float *goals,
                              const size_t *goal_offsets, const uint64_t *skips, const vmv_rrtc_goals_settings &GS,
-                             const vmv_ee_constraint *constraints, size_t n_constraints, ConstraintParams CP, float max_stretch,
-                             vmv_plans *plans)
+                             ConstraintBand band, float max_stretch, vmv_plans *plans)
     {
         float lower[16], span[16], descale[16];
         if (int rc = vmv_robot_bounds(robot, lower, span, descale); rc != VMV_OK) return rc;
-        for (int j = 0; j < 16; ++j) CP.lower[j] = j < dim ? lower[j] : 0.f, CP.upper[j] = j < dim ? lower[j] + span[j] : 0.f;
-        CP.shared = n_constraints == 1 ? 1u : 0u;
+        constraint_band_bounds(band, lower, span, dim);
+        const ConstraintParams &CP = band.P;
         const RobotLaunchers &L = robot_launchers(robot);
         hipStream_t stream = nullptr;
-        std::vector<ConstraintDev> recs(n_constraints);
-        for (size_t k = 0; k < n_constraints; ++k) constraint_record(constraints[k], (double) CP.pos_tol, (double) CP.rot_tol, recs[k]);
+        std::vector<ConstraintDev> recs(band.count);
+        constraint_band_records(band, recs.data());
         const auto first = [&](size_t p) { return goal_offsets ? goal_offsets[p] : p; };
         const size_t G = first(n), lanes = n + G;
 
@@ -498,23 +497,18 @@ namespace vmv
             float *d_q = nullptr;
             ConstraintDev *d_recs = nullptr;
             uint64_t *d_bits = nullptr;
-            std::vector<ConstraintDev> per_lane;
-            if (!CP.shared)
+            std::vector<uint32_t> owner(CP.shared ? 0 : lanes);  // of a lane: its problem
+            for (size_t p = 0; p < n && !CP.shared; ++p)
             {
-                per_lane.resize(lanes);
-                for (size_t p = 0; p < n; ++p)
-                {
-                    per_lane[p] = recs[p];
-                    for (size_t g = first(p); g < first(p + 1); ++g) per_lane[n + g] = recs[p];
-                }
+                owner[p] = (uint32_t) p;
+                for (size_t g = first(p); g < first(p + 1); ++g) owner[n + g] = (uint32_t) p;
             }
-            const std::vector<ConstraintDev> &up = CP.shared ? recs : per_lane;
+            const std::vector<ConstraintDev> up = CP.shared ? recs : constraint_band_expand(recs.data(), owner);
             VMV_LOCKSTEP_HIP(mem.alloc(&d_q, lanes * (size_t) dim));
-            VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, up.size()));
+            if (int rc = upload_records(mem, up.data(), up.size(), &d_recs); rc != VMV_OK) return rc;
             VMV_LOCKSTEP_HIP(mem.alloc(&d_bits, bits.size()));
             VMV_LOCKSTEP_HIP(hipMemcpy(d_q, starts, n * (size_t) dim * 4, hipMemcpyHostToDevice));
             VMV_LOCKSTEP_HIP(hipMemcpy(d_q + n * (size_t) dim, goals, G * (size_t) dim * 4, hipMemcpyHostToDevice));
-            VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, up.data(), up.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
             if (int rc = L.constraint_check(CP, d_recs, d_q, lanes, d_bits, nullptr, stream); rc != VMV_OK) return rc;
             VMV_LOCKSTEP_HIP(hipMemcpy(bits.data(), d_bits, bits.size() * 8, hipMemcpyDeviceToHost));
         }
@@ -522,11 +516,10 @@ namespace vmv
 
         // ---- the problems that take part, with their in-band goals (goal_of: the goal's index within its own set)
         std::vector<size_t> kept, offsets(1, 0);
-        std::vector<uint32_t> goal_of;
+        std::vector<uint32_t> goal_of, kept_owner;
         std::vector<float> k_starts, k_goals;
         std::vector<uint64_t> k_skips;
         std::vector<const vmv_env *> k_envs;
-        std::vector<ConstraintDev> k_recs;
         for (size_t p = 0; p < n; ++p)
         {
             const size_t before = goal_of.size();
@@ -540,7 +533,7 @@ namespace vmv
             kept.push_back(p), offsets.push_back(goal_of.size()), k_envs.push_back(envs[p]);
             k_starts.insert(k_starts.end(), starts + p * (size_t) dim, starts + (p + 1) * (size_t) dim);
             if (skips) k_skips.push_back(skips[p]);
-            if (!CP.shared) k_recs.push_back(recs[p]);
+            kept_owner.push_back((uint32_t) p);
         }
         plans->n = n, plans->dim = dim, plans->rounds = 0, plans->questions = 0;
         plans->status.assign(n, (uint8_t) VMV_PLAN_INVALID_ENDPOINT), plans->iterations.assign(n, 0u), plans->sizes2.assign(2 * n, 0u);
@@ -550,9 +543,8 @@ namespace vmv
 
         DeviceBuffers mem;
         ConstraintDev *d_recs = nullptr;
-        const std::vector<ConstraintDev> &up = CP.shared ? recs : k_recs;
-        VMV_LOCKSTEP_HIP(mem.alloc(&d_recs, up.size()));
-        VMV_LOCKSTEP_HIP(hipMemcpy(d_recs, up.data(), up.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+        const std::vector<ConstraintDev> up = CP.shared ? recs : constraint_band_expand(recs.data(), kept_owner);
+        if (int rc = upload_records(mem, up.data(), up.size(), &d_recs); rc != VMV_OK) return rc;
         const ConstraintRound cr{CP, d_recs, max_stretch * GS.base.range};
         vmv_plans sub;
         if (int rc = rrtc_multi_run(robot, dim, lower, span, k_envs.data(), kept.size(), k_starts.data(), k_goals.data(), offsets.data(),
@@ -622,18 +614,15 @@ extern "C"
         int dim = 0;
         if (int rc = vmv::check_goals_call(robot, envs, n_problems, starts, goals, goal_offsets, halton_skips, settings, out, &dim); rc != VMV_OK)
             return rc;
-        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
-        if (n_constraints != 1 && n_constraints != n_problems) return vmv::refuse_argument("n_constraints must be 1 or n_problems");
-        vmv::ConstraintParams CP{};
-        if (const char *err = vmv::constraint_settings(constraint_settings->base, CP)) return vmv::refuse_argument(err);
-        const float ms = constraint_settings->max_stretch;
-        if (!(std::isfinite(ms) && ms >= 0.f)) return vmv::refuse_argument("max_stretch must be finite and not negative (0 = default)");
-        for (size_t k = 0; k < n_constraints; ++k)
-            if (const char *err = vmv::constraint_refusal(constraints[k]))
-                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
+        const float ms = constraint_settings ? constraint_settings->max_stretch : 0.f;
+        vmv::ConstraintBand band{};
+        const std::string err = vmv::constraint_band_checks(
+            constraints, n_constraints, constraint_settings ? &constraint_settings->base : nullptr, n_problems, "n_problems",
+            std::isfinite(ms) && ms >= 0.f ? nullptr : "max_stretch must be finite and not negative (0 = default)", band);
+        if (!err.empty()) return vmv::refuse_argument(err.c_str());
         const int rc = vmv::lockstep_call(robot, envs, n_problems, dim, out, [&](vmv_plans *plans) {
-            return vmv::rrtc_constrained_run(robot, dim, envs, n_problems, starts, goals, goal_offsets, halton_skips, *settings, constraints,
-                                             n_constraints, CP, ms > 0.f ? ms : 2.f, plans);
+            return vmv::rrtc_constrained_run(robot, dim, envs, n_problems, starts, goals, goal_offsets, halton_skips, *settings, band,
+                                             ms > 0.f ? ms : 2.f, plans);
         });
         if (rc == VMV_OK) (*out)->rrtc_goals = (*out)->constrained = true, (*out)->band_refused.resize(n_problems);
         return rc;

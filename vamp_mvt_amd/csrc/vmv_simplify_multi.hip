@@ -488,27 +488,19 @@ namespace vmv
             return sat_add(sat_mul(P.max_iterations, per_iteration), 2ull + check_every);
         }
 
-        struct SimplifyConstraints  // vmv_simplify_multi_constrained: the caller's constraints (1 or n_paths), the resolved settings
-        {
-            ConstraintParams P;
-            const vmv_ee_constraint *constraints;
-            size_t count;
-        };
-
         // The constrained call's look at its input, before the rounds: ONE band test over the first waypoint of every path
         // and ONE edge band test over every consecutive pair of the packed input (the pairs that straddle two paths are
         // asked too and not looked at), each with its path's record.  out_of_band[p] = 1: a path of 3 waypoints or more
         // with its first waypoint or an edge out of band.  d_recs: one record (shared) or one per path, for the rounds.
-        int simplify_band_input(int robot, const SimplifyConstraints &cb, DeviceBuffers &mem, size_t n, const float *points,
+        int simplify_band_input(int robot, const ConstraintBand &cb, DeviceBuffers &mem, size_t n, const float *points,
                                 const float *d_points, const size_t *offsets, size_t dim, hipStream_t stream, ConstraintDev **d_recs,
                                 std::vector<uint8_t> &out_of_band)
         {
             const RobotLaunchers &L = robot_launchers(robot);
             const size_t total = offsets[n], n_edges = total > 0 ? total - 1 : 0;
             std::vector<ConstraintDev> recs(cb.count);
-            for (size_t k = 0; k < cb.count; ++k) constraint_record(cb.constraints[k], (double) cb.P.pos_tol, (double) cb.P.rot_tol, recs[k]);
-            VMV_LOCKSTEP_HIP(mem.alloc(d_recs, cb.count));
-            VMV_LOCKSTEP_HIP(hipMemcpy(*d_recs, recs.data(), cb.count * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+            constraint_band_records(cb, recs.data());
+            if (int rc = upload_records(mem, recs.data(), cb.count, d_recs); rc != VMV_OK) return rc;
             out_of_band.assign(n, 0);
 
             std::vector<float> firsts(n * dim, 0.0f);
@@ -525,12 +517,11 @@ namespace vmv
             VMV_LOCKSTEP_HIP(hipMemcpyAsync(d_firsts, firsts.data(), n * dim * 4, hipMemcpyHostToDevice, stream));
             if (!cb.P.shared && n_edges)  // edge e begins at packed waypoint e: its path's record
             {
-                std::vector<ConstraintDev> per_edge(n_edges);
+                std::vector<uint32_t> owner(n_edges);
                 for (size_t p = 0; p < n; ++p)
-                    for (size_t e = offsets[p]; e < offsets[p + 1] && e < n_edges; ++e) per_edge[e] = recs[p];
+                    for (size_t e = offsets[p]; e < offsets[p + 1] && e < n_edges; ++e) owner[e] = (uint32_t) p;
                 ConstraintDev *d = nullptr;
-                VMV_LOCKSTEP_HIP(tmp.alloc(&d, n_edges));
-                VMV_LOCKSTEP_HIP(hipMemcpy(d, per_edge.data(), n_edges * sizeof(ConstraintDev), hipMemcpyHostToDevice));
+                if (int rc = upload_records(tmp, constraint_band_expand(recs.data(), owner).data(), n_edges, &d); rc != VMV_OK) return rc;
                 d_edge_recs = d;
             }
             if (int rc = L.constraint_check(cb.P, *d_recs, d_firsts, n, d_bits, nullptr, stream); rc != VMV_OK) return rc;
@@ -555,7 +546,7 @@ namespace vmv
         // robot's part built.
         // cb: vmv_simplify_multi_constrained's constraints and resolved settings (NULL: vmv_simplify_multi).
         int simplify_multi_run(int robot, const vmv_env *const *envs, size_t n, const float *points, const size_t *offsets,
-                               const SimplifyParams &P, uint32_t check_every, vmv_paths *paths, const SimplifyConstraints *cb = nullptr)
+                               const SimplifyParams &P, uint32_t check_every, vmv_paths *paths, const ConstraintBand *cb = nullptr)
         {
             const size_t dim = P.dim, W = P.w, total_in = offsets[n];
             hipStream_t stream = nullptr;
@@ -723,18 +714,13 @@ extern "C"
         vmv::SimplifyParams P{};
         uint32_t check_every = 0;
         if (int rc = vmv::simplify_checks(robot, envs, n_paths, points, offsets, settings, out, P, check_every); rc != VMV_OK) return rc;
-        if (!constraints || !constraint_settings) return vmv::refuse_argument("null pointer");
-        if (n_constraints != 1 && n_constraints != n_paths) return vmv::refuse_argument("n_constraints must be 1 or n_paths");
-        vmv::SimplifyConstraints cb{};
-        if (const char *err = vmv::constraint_settings(*constraint_settings, cb.P)) return vmv::refuse_argument(err);
-        for (size_t k = 0; k < n_constraints; ++k)
-            if (const char *err = vmv::constraint_refusal(constraints[k]))
-                return vmv::refuse_argument(("constraints[" + std::to_string(k) + "]: " + err).c_str());
-        cb.constraints = constraints, cb.count = n_constraints, cb.P.shared = n_constraints == 1 ? 1u : 0u;
+        vmv::ConstraintBand cb{};
+        const std::string err = vmv::constraint_band_checks(constraints, n_constraints, constraint_settings, n_paths, "n_paths", nullptr, cb);
+        if (!err.empty()) return vmv::refuse_argument(err.c_str());
         const int rc = vmv::lockstep_call(robot, envs, n_paths, (int) P.dim, out, [&](vmv_paths *paths) {
             float lower[16], span[16], descale[16];
             if (int rb = vmv_robot_bounds(robot, lower, span, descale); rb != VMV_OK) return rb;
-            for (uint32_t j = 0; j < 16; ++j) cb.P.lower[j] = j < P.dim ? lower[j] : 0.f, cb.P.upper[j] = j < P.dim ? lower[j] + span[j] : 0.f;
+            vmv::constraint_band_bounds(cb, lower, span, (int) P.dim);
             return vmv::simplify_multi_run(robot, envs, n_paths, points, offsets, P, check_every, paths, &cb);
         });
         if (rc == VMV_OK) (*out)->constrained = true, (*out)->band_refused.resize(n_paths);
