@@ -588,7 +588,8 @@ int vmv_rrtc_multi_constrained(int robot, const vmv_env *const *envs, size_t n_p
                                const vmv_ee_constraint *constraints /* host, [n_constraints] */, size_t n_constraints,
                                const vmv_constraint_plan_settings *constraint_settings, vmv_plans **out);
 /* refused [n_problems]: per problem the questions the constraint answered 0 (a failed or overstretched projection, an edge
- * out of band), whatever validity said.  VMV_ERR_INVALID_ARGUMENT on plans not made by vmv_rrtc_multi_constrained. */
+ * out of band), whatever validity said.  VMV_ERR_INVALID_ARGUMENT on plans made by neither vmv_rrtc_multi_constrained nor
+ * vmv_aorrtc_multi_constrained (which adds its searches' and its simplifications' counts, see there). */
 int vmv_plans_band_refused(const vmv_plans *plans, uint32_t *refused);
 int vmv_plans_goal_indices(const vmv_plans *plans, uint32_t *goal_index);
 
@@ -1218,10 +1219,48 @@ typedef struct
 } vmv_aorrtc_settings;
 int vmv_aorrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
                      const uint64_t *halton_skips, const vmv_aorrtc_settings *settings, vmv_plans **out);
-/* Per problem of a vmv_aorrtc_multi result (arrays of n_problems, any may be NULL): the cost after the first stage, the
+/* Per problem of a vmv_aorrtc_multi or vmv_aorrtc_multi_constrained result (arrays of n_problems, any may be NULL): the cost after the first stage, the
  * cost of the returned path (+inf = unsolved), the cost-bounded searches run, those that gave a cheaper path.
  * VMV_ERR_INVALID_ARGUMENT on the plans of another call. */
 int vmv_plans_costs(const vmv_plans *plans, float *first_costs, float *costs, uint32_t *searches, uint32_t *improvements);
+
+/* ---- lockstep AORRTC under end-effector constraints ----------------------------------------- */
+/* vmv_aorrtc_multi inside the band of an end-effector constraint: its arguments, then one constraint for every problem or
+ * one per problem (n_constraints = 1 or n_problems) and vmv_rrtc_multi_constrained's plan settings.  The contract per
+ * problem is vmv_aorrtc_multi's meta loop with these substitutions and nothing else:
+ *   1. The first solution is vmv_rrtc_multi_constrained's with one goal, dynamic domain and start_tree_first off and the
+ *      two maxima of these settings.  A start or goal out of band: VMV_PLAN_INVALID_ENDPOINT, no question, no path,
+ *      first_cost = cost = +inf, searches = 0.
+ *   2. Every simplification is vmv_simplify_multi_constrained's under the same constraint and constraint_settings->base.
+ *      A path longer than simplify.max_waypoints stays as it is; so does one that comes back VMV_SIMPLIFY_OUT_OF_BAND,
+ *      whose cost is then that of the unsimplified path.
+ *   3. A search is vmv_aorrtc_multi's with three kinds of question.  An extension near -> new and a march step from -> w
+ *      end in a NEW node, which gets vmv_rrtc_multi_constrained's treatment: it is projected
+ *      (vmv_constraint_project_batch's lane, bit for bit), accepted only if the projection converged and lies within
+ *      max_stretch * range of the question's near end, written back to the tree and to the question, and then the edge's
+ *      band test (vmv_constraint_check_motion_batch's) is ANDed into validity; refused, the node stays as written and the
+ *      answer is 0.  A re-parent question A[mi] -> new has no new node - `new` is projected already - and is band-checked
+ *      only: the stretch rule does not apply to it (its near end is a nearest node in cost space).  The null questions are
+ *      band-checked only (start -> start).  The closing step of a march is not asked, as in vmv_rrtc_multi.
+ *      Whatever is derived from a new node - new_cost, g2, a march node's cost = cost[prev] + dist(w, prev) - is computed
+ *      after the answer, from the projected point.  The PHS sample itself is never projected.
+ * The result is a vmv_plans as vmv_aorrtc_multi's; vmv_plans_costs reads it, and vmv_plans_band_refused gives per problem
+ * the first stage's count + the searches' questions the constraint answered 0 + every simplification's
+ * vmv_paths_band_refused.  rounds and questions count every stage.  A problem's result is its own, bit for bit, whatever
+ * the batch, its order and check_every.  With a constraint that restricts nothing the result is vmv_aorrtc_multi's byte for
+ * byte, rounds and questions included, while every node lies inside the joint bounds.
+ * NOT promised: as in vmv_simplify_multi_constrained the halves of a subdivided edge are not asked again, so a returned
+ * path lies on asked in-band edges or on halves of them, and a fresh sampling of its edges
+ * (vmv_constraint_check_motion_batch over the returned waypoints) may still answer 0 for some.  Only the end-effector
+ * frame can be constrained.
+ * Checks, all before any device call: vmv_aorrtc_multi's in its order, then vmv_rrtc_multi's remaining ones and the
+ * constraint's own as vmv_rrtc_multi_constrained makes them ("null pointer", n_constraints, the settings, max_stretch, every
+ * constraint; vmv_last_error() names the check); then the environments' checks.  A call that fails leaves *out untouched.
+ * Per round of a search one more launch than vmv_aorrtc_multi: one wave per question. */
+int vmv_aorrtc_multi_constrained(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                                 const uint64_t *halton_skips, const vmv_aorrtc_settings *settings,
+                                 const vmv_ee_constraint *constraints /* host, [n_constraints] */, size_t n_constraints,
+                                 const vmv_constraint_plan_settings *constraint_settings, vmv_plans **out);
 
 /* ---- lazy complete-graph search: many independent problems in one call ----------------------------------- */
 /* A* over the complete graph of a problem's valid samples with every unchecked edge taken as free, for n_problems problems

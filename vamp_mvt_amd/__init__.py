@@ -1348,7 +1348,16 @@ class _Robot(types.ModuleType):
 
         return _read_plans(plans, n, self._dim, goal_indices)
 
-    def aorrtc_multi_raw(self, starts, goals, environments, settings, skips=None):
+    def aorrtc_multi_constrained_raw(self, starts, goals, environments, constraints, settings, constraint_settings=None,
+                                     max_stretch=2.0, skips=None):
+        """vmv_aorrtc_multi_constrained: aorrtc_multi_raw under end-effector constraints - one EEConstraint for all problems
+        or one per problem; constraint_settings: a ConstraintSettings (None = defaults); max_stretch as in
+        rrtc_multi_constrained_raw.  -> aorrtc_multi_raw's dict plus band_refused per problem (the questions of every stage
+        the constraint answered 0); status 4 (invalid_endpoint) where the start or the goal is out of band."""
+        return self.aorrtc_multi_raw(starts, goals, environments, settings, skips,
+                                     constrained=(constraints, constraint_settings, float(max_stretch)))
+
+    def aorrtc_multi_raw(self, starts, goals, environments, settings, skips=None, constrained=None):
         """vmv_aorrtc_multi: AORRTC for many problems (a first solution by rrtc_multi's contract, simplified by
         simplify_multi's, then cost-bounded RRT-Connect searches in lockstep), the arguments those of rrtc_multi_raw.
         settings: range, balance, tree_ratio, check_every, optimize, cost_bound_resample, simplify_intermediate,
@@ -1369,10 +1378,19 @@ class _Robot(types.ModuleType):
         cs = _lib.AorrtcSettings(base, _simplify_settings_struct(settings.simplify), int(bool(settings.optimize)),
                                  int(bool(settings.cost_bound_resample)), int(bool(settings.simplify_intermediate)),
                                  base.max_iterations, max_in, base.max_samples, resamples, int(settings.max_searches))
+        if constrained is not None:  # (every Python-side check before any library call)
+            records, count = _constraint_records(constrained[0], n)
+            if not (math.isfinite(constrained[2]) and constrained[2] >= 0):
+                raise ValueError("max_stretch must be finite and not negative")
+            ps = _lib.ConstraintPlanSettings((constrained[1] or ConstraintSettings()).struct(), constrained[2])
         envs, handles = _env_handles(environments)  # `envs` stays referenced until the call returns
         plans = ctypes.c_void_p()
-        check(lib.vmv_aorrtc_multi(self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), ctypes.byref(cs),
-                                   ctypes.byref(plans)), "vmv_aorrtc_multi")
+        given = (self._id, handles, n, _fp(a), _fp(b), _ptr(sk, _lib.c_u64_p), ctypes.byref(cs))
+        if constrained is not None:
+            check(lib.vmv_aorrtc_multi_constrained(*given, records, count, ctypes.byref(ps), ctypes.byref(plans)),
+                  "vmv_aorrtc_multi_constrained")
+        else:
+            check(lib.vmv_aorrtc_multi(*given, ctypes.byref(plans)), "vmv_aorrtc_multi")
 
         def search_costs(plans, out):
             first, costs = np.zeros(n, np.float32), np.zeros(n, np.float32)
@@ -1380,6 +1398,10 @@ class _Robot(types.ModuleType):
             check(lib.vmv_plans_costs(plans, _fp(first), _fp(costs), n_searches.ctypes.data_as(_lib.c_u32_p),
                                       improvements.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_costs")
             out.update(first_costs=first, costs=costs, searches=n_searches, improvements=improvements)
+            if constrained is not None:
+                refused = np.zeros(n, np.uint32)
+                check(lib.vmv_plans_band_refused(plans, refused.ctypes.data_as(_lib.c_u32_p)), "vmv_plans_band_refused")
+                out["band_refused"] = refused
 
         return _read_plans(plans, n, self._dim, search_costs)
 

@@ -271,6 +271,9 @@ def _load():
         "vmv_roadmaps_destroy": (I, [V]),
         "vmv_aorrtc_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
                                  ctypes.POINTER(V)]),
+        "vmv_aorrtc_multi_constrained": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, ctypes.POINTER(AorrtcSettings),
+                                             ctypes.POINTER(EeConstraint), S, ctypes.POINTER(ConstraintPlanSettings),
+                                             ctypes.POINTER(V)]),
         "vmv_plans_costs": (I, [V, c_float_p, c_float_p, c_u32_p, c_u32_p]),
         "vmv_fcit_multi": (I, [I, ctypes.POINTER(V), S, c_float_p, c_float_p, c_u64_p, c_float_p, ctypes.POINTER(FcitSettings),
                                ctypes.POINTER(V)]),

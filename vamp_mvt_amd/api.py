@@ -345,6 +345,19 @@ def install(robot):
         with `status`, `first_cost`, `searches`, `improvements`; nanoseconds is the whole call's time divided by the
         problems).  A planning.AORRTCMultiSettings is taken as it is."""
         t0 = time.perf_counter_ns()
+        return aorrtc_results(planning.aorrtc_multi(robot, starts, goals, environments, aorrtc_settings(settings), skips), t0)
+
+    def aorrtc_multi_constrained(starts, goals, environments, constraints, settings, constraint_settings=None, skips=None,
+                                 max_stretch=2.0):
+        """planning.aorrtc_multi_constrained with this robot: aorrtc_multi under end-effector constraints ->
+        list[PlanningResult] as aorrtc_multi's, each with `band_refused` too.  The settings are taken as aorrtc_multi takes
+        them."""
+        t0 = time.perf_counter_ns()
+        return aorrtc_results(planning.aorrtc_multi_constrained(robot, starts, goals, environments, constraints,
+                                                                aorrtc_settings(settings), constraint_settings, skips, max_stretch), t0)
+
+    def aorrtc_settings(settings):
+        """planning.AORRTCMultiSettings from the reference-shaped AORRTCSettings; one of the former is taken as it is"""
         if isinstance(settings, planning.AORRTCMultiSettings):
             s = settings
         else:
@@ -362,7 +375,9 @@ def install(robot):
                 max_cost_bound_resamples=min(int(settings.max_cost_bound_resamples), 64),
                 max_searches=int(getattr(settings, "max_searches", 0)), simplify=settings.simplify,
                 check_every=int(getattr(settings, "check_every", 0)))
-        results = planning.aorrtc_multi(robot, starts, goals, environments, s, skips)
+        return s
+
+    def aorrtc_results(results, t0):
         each = (time.perf_counter_ns() - t0) // max(len(results), 1)
         out = []
         for r in results:
@@ -371,6 +386,8 @@ def install(robot):
                 path.append(q)
             res = PlanningResult(path, each, r.iterations, r.size, r.cost)
             res.status, res.first_cost, res.searches, res.improvements = r.status, r.first_cost, r.searches, r.improvements
+            if hasattr(r, "band_refused"):
+                res.band_refused = r.band_refused
             out.append(res)
         return out
 
@@ -558,6 +575,7 @@ def install(robot):
     robot.simplify_multi_constrained = simplify_multi_constrained
     robot.optimize_multi_constrained = optimize_multi_constrained
     robot.aorrtc, robot.aorrtc_multi = aorrtc, aorrtc_multi
+    robot.aorrtc_multi_constrained = aorrtc_multi_constrained
     robot.fcit_multi, robot.build_roadmaps = fcit_multi, build_roadmaps
     robot.roadmap = lambda start, goal, environment, settings, rng: roadmap(start, goal, environment, settings, rng)[0]
 

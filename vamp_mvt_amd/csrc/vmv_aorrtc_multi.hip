@@ -48,6 +48,11 @@
 // pool of max_samples nodes, the start tree from the front, the goal tree from the back (vmv_two_trees.h), with parent and
 // cost arrays.
 // Every store is a plain vector store by the owning workgroup; no atomics.
+//
+// vmv_aorrtc_multi_constrained is the same loop inside the band of an end-effector constraint: the first
+// solution by vmv_rrtc_multi_constrained, every simplification by vmv_simplify_multi_constrained, and the searches by
+// aox_step_constrained_kernel - the same body, which names each question's new node for the robot's
+// constraint_round_kernel (vmv_rrtc_multi_constrained's, launched right behind it) and ANDs that kernel's answer in.
 #include "../../include/vamp_mvt_amd.h"
 
 #include "vmv_lockstep.h"
@@ -112,6 +117,12 @@ namespace vmv
             float *q_start, *q_goal;      // [n_active][dim] the round's questions
             const uint64_t *bits;         // answers of the previous round
             uint8_t *done;                // [n_problems]
+            // vmv_aorrtc_multi_constrained only (aox_step<true>; not read otherwise): pending[a] = the pool element, over
+            // all problems, of the new node the question's far end was written to - A's next slot for an extension, B's
+            // next slot for a march step - or kNoPending for a re-parent, the null question and finished problems;
+            // c_ok[slot] = the constraint round's answer to the previous question, ANDed into the validity bit
+            uint64_t *pending;            // [n_active]
+            const uint8_t *c_ok;          // [n_active]
         };
 
         struct PhsFrame
@@ -244,7 +255,11 @@ namespace vmv
 
         // One workgroup per active problem; every branch below is taken by the whole workgroup (its conditions are
         // values every thread holds alike), so the barriers and cross-lane reads inside nearest() are safe.
-        __global__ __launch_bounds__(kAoxBlock) void aox_step_kernel(const AoxParams P, const AoxArrays D)
+        // kConstrained (vmv_aorrtc_multi_constrained): every question names its pending node for
+        // constraint_round_kernel, which runs between this kernel and the round's validation, projects that node in the
+        // pool and in q_goal and answers c_ok; what is derived from a pending node is computed after the answer.
+        template <bool kConstrained>
+        __device__ __forceinline__ void aox_step(const AoxParams &P, const AoxArrays &D)
         {
             __shared__ float s_t[kPlanMaxDim];
             __shared__ float s_g[kPlanMaxDim + 2];
@@ -271,6 +286,10 @@ namespace vmv
                     D.state[p] = st;
                 }
             };
+            const auto pend = [&](uint64_t element) {  // the question just written: its new node, or kNoPending
+                if constexpr (kConstrained)
+                    if (tid == 0) D.pending[a] = element;
+            };
 
             // the contract's nearest(T, s_t, c): T's first admissible node of the least key, and its distance to s_t
             const auto search = [&](uint32_t side, float c, float &out_d, uint32_t &out_i) {
@@ -289,7 +308,8 @@ namespace vmv
                 act = kFinish;
             else if (st.phase != kAoxFresh && st.phase != kAoxIdle)
             {
-                const bool ans = (D.bits[st.slot >> 6] >> (st.slot & 63u)) & 1ull;
+                bool ans = (D.bits[st.slot >> 6] >> (st.slot & 63u)) & 1ull;
+                if constexpr (kConstrained) ans = ans && D.c_ok[st.slot] != 0;
                 const uint32_t sa = st.a_side, sb = sa ^ 1u;
                 if (st.phase == kAoxExtend)
                 {
@@ -313,6 +333,13 @@ namespace vmv
                 {
                     if (ans)
                     {
+                        if constexpr (kConstrained)
+                        {
+                            // w was projected in place: its cost is that of the projected point.  Lane 0 alone reads it
+                            // before the barriers of the loop below, which every other reader of cost[] lies behind.
+                            const size_t w_at = node_at(sb, count_of(st.n, sb), M), prev_at = node_at(sb, st.prev, M);
+                            if (tid == 0) cost[w_at] = cost[prev_at] + tree_dist(pool + w_at * dim, pool + prev_at * dim, dim);
+                        }
                         st.prev = grow(st.n, sb);
                         if (++st.k == st.n_steps)
                             st.status = VMV_PLAN_SOLVED, act = kFinish;
@@ -345,6 +372,7 @@ namespace vmv
                         if (tid < dim) qs[tid] = pool[node_at(sa, mi, M) * dim + tid], qg[tid] = s_t[tid];
                         st.mi = mi, st.cand_cost = cand;
                         st.phase = kAoxReparent, st.slot = a, ++st.questions;
+                        pend(kNoPending);  // `new` is projected already: the edge is band-checked only
                         save();
                         return;
                     }
@@ -391,6 +419,7 @@ namespace vmv
                     }
                     st.phase = kAoxMarch, st.slot = a, ++st.questions;
                     if (tid == 0) parent[w_at] = st.prev, cost[w_at] = cost[node_at(sb, st.prev, M)] + sqrtf(sum);
+                    pend((uint64_t) p * M + w_at);
                     save();
                     return;
                 }
@@ -416,6 +445,7 @@ namespace vmv
                     {
                         ask_nothing(qs, qg, start, dim);
                         st.phase = kAoxIdle, st.slot = a;
+                        pend(kNoPending);
                         save();
                         return;
                     }
@@ -447,6 +477,7 @@ namespace vmv
                     ask_extension(pool, node_at(sa, ni, M), node_at(sa, count_of(st.n, sa), M), dim, s_t, d, R, qs, qg);
                     st.ni = ni;
                     st.phase = kAoxExtend, st.slot = a, ++st.questions;
+                    pend((uint64_t) p * M + node_at(sa, count_of(st.n, sa), M));
                     save();
                     return;
                 }
@@ -454,6 +485,7 @@ namespace vmv
 
             // finished (now or in an earlier round)
             ask_nothing(qs, qg, start, dim);
+            pend(kNoPending);
             if (st.phase != kAoxDone && tid == 0)
             {
                 st.phase = kAoxDone, st.slot = a;
@@ -463,6 +495,8 @@ namespace vmv
                 D.done[p] = 1;
             }
         }
+
+        __global__ __launch_bounds__(kAoxBlock) void aox_step_kernel(const AoxParams P, const AoxArrays D) { aox_step<false>(P, D); }
 
         __global__ __launch_bounds__(kAoxBlock) void aox_paths_kernel(const AoxParams P, const AoxArrays D, const uint32_t n_active,
                                                                        const uint64_t *__restrict__ offsets, float *__restrict__ paths)
@@ -497,6 +531,12 @@ namespace vmv
             *out_counter = c;
         }
 
+        // vmv_aorrtc_multi_constrained's step kernel: behind the others, so that none of them moves in the code object
+        __global__ __launch_bounds__(kAoxBlock) void aox_step_constrained_kernel(const AoxParams P, const AoxArrays D)
+        {
+            aox_step<true>(P, D);
+        }
+
         float host_dist(const float *a, const float *b, int dim)
         {
             float sum = 0.f;
@@ -518,11 +558,30 @@ namespace vmv
             return acc;
         }
 
+        // vmv_aorrtc_multi_constrained's own part of a call, NULL throughout for vmv_aorrtc_multi: the caller's constraints
+        // and plan settings (what every simplification is called with), the searches' constraint round - the launcher's
+        // resolved settings with the robot's bounds, max_stretch * range - and its device side, which AoxSearches::setup
+        // allocates: the records (one, or one per problem: a round picks by problem), the round's answers and, per
+        // problem, the questions of all searches it answered 0.
+        struct AoxConstrained
+        {
+            const vmv_ee_constraint *constraints;
+            size_t n_constraints;
+            const vmv_constraint_plan_settings *settings;
+            ConstraintParams P;
+            float stretch;
+            ConstraintDev *d_cons = nullptr;
+            uint8_t *d_c_ok = nullptr;
+            uint32_t *d_refused = nullptr;
+        };
+
         // vmv_simplify_multi over paths[idx[...]] in their environments, in place; a path longer than the simplifier's
         // max_waypoints stays as it is.  The call's rounds and questions are added to the totals.
+        // con: vmv_simplify_multi_constrained with each path's constraint instead; a path that comes back
+        // VMV_SIMPLIFY_OUT_OF_BAND stays as it is too, and each path's vmv_paths_band_refused is added to band_refused.
         int simplify_some(int robot, const vmv_env *const *envs, int dim, const std::vector<uint32_t> &idx,
                           std::vector<std::vector<float>> &paths, const vmv_simplify_settings &S, uint64_t &rounds,
-                          uint64_t &questions)
+                          uint64_t &questions, const AoxConstrained *con = nullptr, std::vector<uint32_t> *band_refused = nullptr)
         {
             const size_t max_waypoints = S.max_waypoints ? S.max_waypoints : 2048;  // the simplifier's default
             std::vector<uint32_t> which;
@@ -539,11 +598,26 @@ namespace vmv
             }
             if (which.empty()) return VMV_OK;
             vmv_paths *out = nullptr;
-            if (int rc = vmv_simplify_multi(robot, sub_envs.data(), which.size(), points.data(), offsets.data(), &S, &out); rc != VMV_OK)
-                return rc;
-            std::vector<uint32_t> lengths(which.size());
+            if (!con)
+            {
+                if (int rc = vmv_simplify_multi(robot, sub_envs.data(), which.size(), points.data(), offsets.data(), &S, &out); rc != VMV_OK)
+                    return rc;
+            }
+            else
+            {
+                std::vector<vmv_ee_constraint> sub_cons;  // one per path of the call, unless one serves all
+                for (size_t k = 0; con->n_constraints != 1 && k < which.size(); ++k) sub_cons.push_back(con->constraints[which[k]]);
+                if (int rc = vmv_simplify_multi_constrained(robot, sub_envs.data(), which.size(), points.data(), offsets.data(), &S,
+                                                            con->n_constraints == 1 ? con->constraints : sub_cons.data(),
+                                                            con->n_constraints == 1 ? 1 : which.size(), &con->settings->base, &out);
+                    rc != VMV_OK)
+                    return rc;
+            }
+            std::vector<uint32_t> lengths(which.size()), refused(which.size(), 0u);
+            std::vector<uint8_t> status(which.size());
             uint64_t r = 0, q = 0;
-            int rc = vmv_paths_summary(out, nullptr, nullptr, lengths.data(), nullptr, &r, &q);
+            int rc = vmv_paths_summary(out, status.data(), nullptr, lengths.data(), nullptr, &r, &q);
+            if (rc == VMV_OK && con) rc = vmv_paths_band_refused(out, refused.data());
             size_t total = 0;
             for (const uint32_t len : lengths) total += len;
             std::vector<float> simplified(total * (size_t) dim);
@@ -554,7 +628,8 @@ namespace vmv
             for (size_t k = 0; k < which.size(); ++k)
             {
                 const size_t count = (size_t) lengths[k] * (size_t) dim;
-                paths[which[k]].assign(simplified.begin() + at, simplified.begin() + at + count);
+                if (status[k] != VMV_SIMPLIFY_OUT_OF_BAND) paths[which[k]].assign(simplified.begin() + at, simplified.begin() + at + count);
+                if (con) (*band_refused)[which[k]] += refused[k];
                 at += count;
             }
             rounds += r, questions += q;
@@ -577,6 +652,7 @@ namespace vmv
             float *d_paths = nullptr;  // the traced paths of one generation, packed
             uint64_t paths_capacity = 0;  // in waypoints
             hipStream_t stream = nullptr;
+            AoxConstrained *con = nullptr;  // vmv_aorrtc_multi_constrained: the constraint round after every step kernel
             ~AoxSearches()
             {
                 if (d_paths) (void) hipFree(d_paths);
@@ -595,6 +671,18 @@ namespace vmv
                     return rc;
                 D.active = B.active, D.q_start = B.q_start, D.q_goal = B.q_goal, D.bits = B.bits, D.done = B.done;
                 D.max_cost = d_max_cost, D.budget = d_budget;
+                if (con)
+                {
+                    std::vector<ConstraintDev> recs(con->n_constraints);
+                    for (size_t k = 0; k < recs.size(); ++k)
+                        constraint_record(con->constraints[k], (double) con->P.pos_tol, (double) con->P.rot_tol, recs[k]);
+                    if (int rc = upload_records(mem, recs.data(), recs.size(), &con->d_cons); rc != VMV_OK) return rc;
+                    VMV_LOCKSTEP_HIP(mem.alloc(&D.pending, n));
+                    VMV_LOCKSTEP_HIP(mem.alloc(&con->d_c_ok, n));
+                    VMV_LOCKSTEP_HIP(mem.alloc(&con->d_refused, n));
+                    VMV_LOCKSTEP_HIP(hipMemsetAsync(con->d_refused, 0, std::max<size_t>(n * 4, 16), stream));
+                    D.c_ok = con->d_c_ok;
+                }
                 VMV_LOCKSTEP_HIP(hipMemsetAsync(D.state, 0, n * sizeof(AoxState), stream));  // every counter starts at 0
                 VMV_LOCKSTEP_HIP(hipStreamSynchronize(stream));
                 return VMV_OK;
@@ -623,9 +711,20 @@ namespace vmv
                 // for kAoxSpinCap iterations that asked nothing: a bound on the rounds that does not depend on the device's answers
                 const uint64_t max_rounds = (uint64_t) max_budget * (1ull + max_resamples) + max_samples + check_every + 2ull;
                 uint64_t rounds = 0;
-                const auto step = [&](uint32_t count) { hipLaunchKernelGGL(aox_step_kernel, dim3(count), dim3(kAoxBlock), 0, stream, P, D); };
-                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(), "vmv_aorrtc_multi",
-                                             "aox_step_kernel", step, rounds);
+                const auto step = [&](uint32_t count) {
+                    if (!con)
+                    {
+                        hipLaunchKernelGGL(aox_step_kernel, dim3(count), dim3(kAoxBlock), 0, stream, P, D);
+                        return;
+                    }
+                    // the pending node projected and written back, the edge's band test: before the round's validation
+                    hipLaunchKernelGGL(aox_step_constrained_kernel, dim3(count), dim3(kAoxBlock), 0, stream, P, D);
+                    (void) robot_launchers(robot).constraint_round(con->P, con->d_cons, B.active, B.q_start, B.q_goal, D.pending, D.pool,
+                                                                   con->stretch, con->d_c_ok, con->d_refused, count, stream);
+                };
+                if (int rc = lockstep_rounds(robot, stream, check_every, max_rounds, 1, active, active_envs, B.arrays(),
+                                             con ? "vmv_aorrtc_multi_constrained" : "vmv_aorrtc_multi",
+                                             con ? "aox_step_constrained_kernel" : "aox_step_kernel", step, rounds);
                     rc != VMV_OK)
                     return rc;
                 rounds_total += rounds;
@@ -667,7 +766,7 @@ namespace vmv
         // After the first stage: `plans` is vmv_rrtc_multi's result for the n > 0 problems and becomes the call's result.
         int aorrtc_after_first(int robot, int dim, const float *lower, const float *span, const vmv_env *const *envs, size_t n,
                                const float *starts, const float *goals, const uint64_t *skips, const vmv_aorrtc_settings &S,
-                               vmv_plans *plans)
+                               vmv_plans *plans, AoxConstrained *con = nullptr)
         {
             const float inf = std::numeric_limits<float>::infinity();
             plans->first_costs.assign(n, inf), plans->final_costs.assign(n, inf);
@@ -683,7 +782,9 @@ namespace vmv
                 if (plans->status[p] == VMV_PLAN_SOLVED) solved.push_back((uint32_t) p);
             }
             if (S.simplify_intermediate)
-                if (int rc = simplify_some(robot, envs, dim, solved, best, S.simplify, plans->rounds, plans->questions); rc != VMV_OK)
+                if (int rc = simplify_some(robot, envs, dim, solved, best, S.simplify, plans->rounds, plans->questions, con,
+                                           &plans->band_refused);
+                    rc != VMV_OK)
                     return rc;
             std::vector<uint32_t> optimising;
             std::vector<float> dmin(n, 0.f);
@@ -697,7 +798,7 @@ namespace vmv
             if (!optimising.empty())
             {
                 AoxSearches X;
-                X.robot = robot, X.dim = dim, X.n = n;
+                X.robot = robot, X.dim = dim, X.n = n, X.con = con;
                 X.check_every = S.rrtc.check_every ? S.rrtc.check_every : kAoxDefaultCheckEvery;
                 X.max_resamples = S.cost_bound_resample ? S.max_cost_bound_resamples : 0u, X.max_samples = S.max_samples;
                 X.P.dim = (uint32_t) dim, X.P.max_samples = S.max_samples, X.P.balance = S.rrtc.balance ? 1u : 0u;
@@ -733,7 +834,8 @@ namespace vmv
                         if (st.status == VMV_PLAN_SOLVED) improved.push_back(p);
                     }
                     if (S.simplify_intermediate)
-                        if (int rc = simplify_some(robot, envs, dim, improved, found, S.simplify, plans->rounds, plans->questions);
+                        if (int rc = simplify_some(robot, envs, dim, improved, found, S.simplify, plans->rounds, plans->questions, con,
+                                                   &plans->band_refused);
                             rc != VMV_OK)
                             return rc;
                     for (const uint32_t p : improved)
@@ -747,6 +849,12 @@ namespace vmv
                         }
                     }
                 }
+                if (con)  // the questions of all searches the constraint round answered 0
+                {
+                    std::vector<uint32_t> refused(n);
+                    VMV_LOCKSTEP_HIP(hipMemcpy(refused.data(), con->d_refused, n * 4, hipMemcpyDeviceToHost));
+                    for (size_t p = 0; p < n; ++p) plans->band_refused[p] += refused[p];
+                }
             }
 
             plans->aorrtc = true;
@@ -756,6 +864,53 @@ namespace vmv
                 plans->path_lengths[p] = (uint32_t) (best[p].size() / (size_t) dim);
                 plans->paths.insert(plans->paths.end(), best[p].begin(), best[p].end());
             }
+            return VMV_OK;
+        }
+
+        // vmv_aorrtc_multi's own checks, device-free and in the header's order; those of vmv_rrtc_multi follow in the
+        // first stage's call.  The simplifier's settings are checked by an empty call of the simplifier.
+        int aorrtc_checks(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                          const vmv_aorrtc_settings *settings, vmv_plans *const *out, int *dim)
+        {
+            *dim = vmv_robot_dimension(robot);
+            if (robot < 0 || robot >= vmv_num_robots() || *dim <= 0 || *dim > (int) kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
+            if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
+            if (n_problems >= kMultiMaxConfigs / 64) return VMV_ERR_INVALID_ARGUMENT;  // (64 questions per path per round)
+            const vmv_aorrtc_settings &S = *settings;
+            if (S.max_internal_iterations == 0 || S.max_cost_bound_resamples > kAoxMaxResamples) return VMV_ERR_INVALID_ARGUMENT;
+            vmv_paths *none = nullptr;
+            if (int rc = vmv_simplify_multi(robot, nullptr, 0, nullptr, nullptr, &S.simplify, &none); rc != VMV_OK) return rc;
+            (void) vmv_paths_destroy(none);
+            return VMV_OK;
+        }
+
+        // the first stage's settings: rrtc's own with the two maxima of the AORRTC settings (aorrtc.hh:384-386)
+        vmv_rrtc_settings aorrtc_first_stage(const vmv_aorrtc_settings &S)
+        {
+            vmv_rrtc_settings first = S.rrtc;
+            first.max_iterations = S.max_iterations, first.max_samples = S.max_samples;
+            return first;
+        }
+
+        // `plans`: the first stage's result, owned from here on: it becomes the call's result in *out, or is deleted
+        int aorrtc_finish(int robot, int dim, const vmv_env *const *envs, size_t n, const float *starts, const float *goals,
+                          const uint64_t *skips, const vmv_aorrtc_settings &S, vmv_plans *plans, AoxConstrained *con, vmv_plans **out)
+        {
+            int rc = VMV_OK;
+            if (n > 0)
+            {
+                float lower[16], span[16], descale[16];
+                rc = vmv_robot_bounds(robot, lower, span, descale);
+                if (rc == VMV_OK) rc = aorrtc_after_first(robot, dim, lower, span, envs, n, starts, goals, skips, S, plans, con);
+            }
+            else
+                plans->aorrtc = true;
+            if (rc != VMV_OK)
+            {
+                delete plans;
+                return rc;
+            }
+            *out = plans;
             return VMV_OK;
         }
 
@@ -796,39 +951,47 @@ extern "C"
     int vmv_aorrtc_multi(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
                          const uint64_t *halton_skips, const vmv_aorrtc_settings *settings, vmv_plans **out)
     {
-        // device-free checks first, in vmv_rrtc_multi's order; the simplifier's settings by an empty call of the simplifier
-        const int dim = vmv_robot_dimension(robot);
-        if (robot < 0 || robot >= vmv_num_robots() || dim <= 0 || dim > (int) vmv::kPlanMaxDim) return VMV_ERR_UNKNOWN_ROBOT;
-        if (!settings || !out || (n_problems > 0 && (!envs || !starts || !goals))) return VMV_ERR_INVALID_ARGUMENT;
-        if (n_problems >= vmv::kMultiMaxConfigs / 64) return VMV_ERR_INVALID_ARGUMENT;  // (64 questions per path per round)
-        const vmv_aorrtc_settings &S = *settings;
-        if (S.max_internal_iterations == 0 || S.max_cost_bound_resamples > vmv::kAoxMaxResamples) return VMV_ERR_INVALID_ARGUMENT;
-        {
-            vmv_paths *none = nullptr;
-            if (int rc = vmv_simplify_multi(robot, nullptr, 0, nullptr, nullptr, &S.simplify, &none); rc != VMV_OK) return rc;
-            (void) vmv_paths_destroy(none);
-        }
-        vmv_rrtc_settings first = S.rrtc;
-        first.max_iterations = S.max_iterations, first.max_samples = S.max_samples;  // aorrtc.hh:384-386
+        int dim = 0;
+        if (int rc = vmv::aorrtc_checks(robot, envs, n_problems, starts, goals, settings, out, &dim); rc != VMV_OK) return rc;
+        const vmv_rrtc_settings first = vmv::aorrtc_first_stage(*settings);
         vmv_plans *plans = nullptr;
         if (int rc = vmv_rrtc_multi(robot, envs, n_problems, starts, goals, halton_skips, &first, &plans); rc != VMV_OK) return rc;
-        int rc = VMV_OK;
-        if (n_problems > 0)
-        {
-            float lower[16], span[16], descale[16];
-            rc = vmv_robot_bounds(robot, lower, span, descale);
-            if (rc == VMV_OK)
-                rc = vmv::aorrtc_after_first(robot, dim, lower, span, envs, n_problems, starts, goals, halton_skips, S, plans);
-        }
-        else
-            plans->aorrtc = true;
+        return vmv::aorrtc_finish(robot, dim, envs, n_problems, starts, goals, halton_skips, *settings, plans, nullptr, out);
+    }
+
+    int vmv_aorrtc_multi_constrained(int robot, const vmv_env *const *envs, size_t n_problems, const float *starts, const float *goals,
+                                     const uint64_t *halton_skips, const vmv_aorrtc_settings *settings,
+                                     const vmv_ee_constraint *constraints, size_t n_constraints,
+                                     const vmv_constraint_plan_settings *constraint_settings, vmv_plans **out)
+    {
+        // vmv_aorrtc_multi's checks in its order; then the first stage's call makes vmv_rrtc_multi's and the constraint's own
+        // in vmv_rrtc_multi_constrained's order, all of them before it touches a device
+        int dim = 0;
+        if (int rc = vmv::aorrtc_checks(robot, envs, n_problems, starts, goals, settings, out, &dim); rc != VMV_OK) return rc;
+        vmv_rrtc_goals_settings first{};  // one goal per problem, dynamic domain and start_tree_first off
+        first.base = vmv::aorrtc_first_stage(*settings);
+        vmv_plans *plans = nullptr;
+        if (int rc = vmv_rrtc_multi_constrained(robot, envs, n_problems, starts, goals, nullptr, halton_skips, &first, constraints,
+                                                n_constraints, constraint_settings, &plans);
+            rc != VMV_OK)
+            return rc;
+        plans->rrtc_goals = false;  // (one goal per problem: there is no goal index to read)
+        // the band once more for the searches: the checks passed above, so this cannot refuse
+        vmv::AoxConstrained con{constraints, n_constraints, constraint_settings};
+        vmv::ConstraintBand band{};
+        float lower[16], span[16], descale[16];
+        int rc = vmv_robot_bounds(robot, lower, span, descale);
+        if (rc == VMV_OK && !vmv::constraint_band_resolve(constraints, n_constraints, constraint_settings->base, nullptr, band).empty())
+            rc = VMV_ERR_INVALID_ARGUMENT;
         if (rc != VMV_OK)
         {
             delete plans;
             return rc;
         }
-        *out = plans;
-        return VMV_OK;
+        vmv::constraint_band_bounds(band, lower, span, dim);
+        con.P = band.P;
+        con.stretch = (constraint_settings->max_stretch > 0.f ? constraint_settings->max_stretch : 2.f) * settings->rrtc.range;
+        return vmv::aorrtc_finish(robot, dim, envs, n_problems, starts, goals, halton_skips, *settings, plans, &con, out);
     }
 
     int vmv_plans_costs(const vmv_plans *plans, float *first_costs, float *costs, uint32_t *searches, uint32_t *improvements)

@@ -1,5 +1,5 @@
 // vmv_lockstep.h — the host side the lockstep calls share (vmv_rrtc_multi, vmv_rrtc_multi_goals, vmv_simplify_multi,
-// vmv_aorrtc_multi, vmv_fcit_multi and the _constrained forms of the first three; DESIGN §5c "A round"), and the host steps
+// vmv_aorrtc_multi, vmv_fcit_multi and the _constrained forms of the first four; DESIGN §5c "A round"), and the host steps
 // every planner and path call has around its kernels: the device-free argument checks, the problem uploads and the packed
 // paths of a result (vmv_prm_multi and vmv_roadmaps_* as well), the result object's life cycle (lockstep_call: those, and
 // vmv_optimize_multi, vmv_cartesian_multi, vmv_retime_multi with their _constrained forms), the refusal of the

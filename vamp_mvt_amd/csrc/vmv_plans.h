@@ -20,9 +20,9 @@ struct vmv_plans
     bool rrtc_goals = false;
     std::vector<uint32_t> goal_indices;  // [n] the goal, within its own set, a solved path ends in; UINT32_MAX = unsolved
 
-    // vmv_rrtc_multi_constrained only (vmv_plans_band_refused)
+    // vmv_rrtc_multi_constrained and vmv_aorrtc_multi_constrained only (vmv_plans_band_refused)
     bool constrained = false;
-    std::vector<uint32_t> band_refused;  // [n] questions the constraint's round answered 0 (projection or band test)
+    std::vector<uint32_t> band_refused;  // [n] questions the constraint answered 0 (projection or band test), all stages
 
     // vmv_prm_multi only (vmv_plans_roadmap_*)
     bool prm = false, kept = false;  // made by vmv_prm_multi; with keep_roadmaps
@@ -34,7 +34,7 @@ struct vmv_plans
     std::vector<uint32_t> edge_pairs;       // kept: [edges][2] vertex ids a < b, in candidate order
     std::vector<uint8_t> edge_valid;        // kept: [edges]
 
-    // vmv_aorrtc_multi only (vmv_plans_costs)
+    // vmv_aorrtc_multi and vmv_aorrtc_multi_constrained only (vmv_plans_costs)
     bool aorrtc = false;
     std::vector<float> first_costs, final_costs;  // [n] after the first stage; of the returned path (+inf = unsolved)
     std::vector<uint32_t> searches, improvements; // [n] cost-bounded searches run; those that gave a cheaper path

@@ -88,7 +88,6 @@ namespace vmv
             uint64_t *pending;         // [n_active]
             const uint8_t *c_ok;       // [n_active]
         };
-        constexpr uint64_t kNoPending = ~0ull;
 
         __device__ __forceinline__ uint32_t first_goal(const RrtcArrays &D, uint32_t p) { return D.goal_offsets ? D.goal_offsets[p] : p; }
         __device__ __forceinline__ uint32_t goal_count(const RrtcArrays &D, uint32_t p)

@@ -17,6 +17,9 @@ namespace vmv
     {
         constexpr uint32_t kTreeBlock = 256;  // threads of a step kernel's workgroup
         constexpr uint32_t kTreeWaves = kTreeBlock / kWave;
+        // the _constrained planners: what a step kernel stores in pending[a] where its question's far end is no new node
+        // (else the node's pool element over all problems, p * max_samples + node_at(...)); constraint_round_kernel reads it
+        constexpr uint64_t kNoPending = ~0ull;
 
         __device__ __forceinline__ size_t node_at(uint32_t side, uint32_t i, uint32_t max_samples)
         {

@@ -397,8 +397,9 @@ def rrtc_multi_constrained(robot, starts, goal_sets, environments, constraints, 
     ConstraintSettings (its check_step spaces the band samples of an edge); max_stretch: a projected node farther than
     max_stretch * range from the edge's near end is refused.  -> list[PlanningResult] as `rrtc_multi_goals`'s.  The path's
     edges pass `constraint_check_motion_batch`; `simplify_multi_constrained` simplifies it and
-    `optimize_multi_constrained` optimises it inside the band, while `simplify_multi`, `optimize_multi` and
-    `aorrtc_multi` do not know the constraint - ask `validate_paths_constrained` of what they return.  Each result also carries `band_refused`: the questions the constraint answered 0."""
+    `optimize_multi_constrained` optimises it inside the band and `aorrtc_multi_constrained` searches for a cheaper one
+    there, while `simplify_multi`, `optimize_multi` and `aorrtc_multi` do not know the constraint - ask
+    `validate_paths_constrained` of what they return.  Each result also carries `band_refused`: the questions the constraint answered 0."""
     s = settings or RRTCMultiSettings()
     sets = []
     for g in goal_sets:
@@ -559,15 +560,40 @@ def aorrtc_multi(robot, starts, goals, environments, settings: AORRTCMultiSettin
     ln, Marsaglia's polar method, a Householder reflection: + - * / sqrt and integer operations only), so a problem's
     result is defined bit for bit and does not depend on the other problems of the call or on check_every.  Agreement
     with the reference's own random stream is not claimed."""
+    return _aorrtc_results(robot.aorrtc_multi_raw(starts, goals, environments, _aorrtc_settings(settings), skips))
+
+
+def _aorrtc_settings(settings) -> AORRTCMultiSettings:
     s = settings or AORRTCMultiSettings()
     if not isinstance(s.simplify, SimplifyMultiSettings):
         s = replace(s, simplify=_as_simplify_multi_settings(s.simplify))
-    raw = robot.aorrtc_multi_raw(starts, goals, environments, s, skips)
+    return s
+
+
+def _aorrtc_results(raw):
     out = _planning_results(raw, cost=("costs", float), first_cost=("first_costs", float), searches=("searches", int),
-                            improvements=("improvements", int))
+                            improvements=("improvements", int), band_refused=("band_refused", int))  # (the last: the constrained call)
     if out:  # the call's totals over all stages ride on the first result
         out[0].validity_calls, out[0].edges_checked = raw["rounds"], raw["questions"]
     return out
+
+
+def aorrtc_multi_constrained(robot, starts, goals, environments, constraints, settings: AORRTCMultiSettings | None = None,
+                             constraint_settings=None, skips=None, max_stretch=2.0):
+    """`aorrtc_multi` under end-effector constraints (vmv_aorrtc_multi_constrained): constraints is one
+    EEConstraint for all problems or one per problem.  The first solution is `rrtc_multi_constrained`'s (one goal; a problem
+    whose start or goal is out of band ends "invalid_endpoint" with no path, infinite costs and no search), every
+    simplification `simplify_multi_constrained`'s (a path it reports "out_of_band" stays as it is), and in every
+    cost-bounded search each new node - an extension's, a march step's - is projected into the band, refused beyond
+    max_stretch * range, and each edge band-checked, one extra launch per round; a re-parent edge is band-checked only.
+    -> list[PlanningResult] as `aorrtc_multi`'s, each with `band_refused`: the questions of all stages the constraint
+    answered 0.  A problem's result is its own, bit for bit; with a constraint that restricts nothing it is `aorrtc_multi`'s.
+
+    Not promised: the halves of an edge the simplifier subdivides are not asked again, so `validate_paths_constrained`,
+    which samples every returned edge anew, may still answer False for some paths; only the end-effector frame can be
+    constrained."""
+    return _aorrtc_results(robot.aorrtc_multi_constrained_raw(starts, goals, environments, constraints, _aorrtc_settings(settings),
+                                                              constraint_settings, max_stretch, skips))
 
 
 def _as_simplify_multi_settings(settings) -> SimplifyMultiSettings:
@@ -1233,7 +1259,8 @@ def retime_multi_constrained(robot, paths, vel_limits, acc_limits, environments=
     polyline itself - ends the path at once, "collision" where validate_motion refused it and "out_of_band" otherwise, as
     does round max_rounds.  Where `retime_multi` is complete and no constraint restricts, the result is `retime_multi`'s
     byte for byte, in one round.  Corners are repaired, edges are not; a blend at a lower level is not proven faster than a
-    stop (tools/bench_retime_constrained.py measures it); `aorrtc_multi` still does not know the constraint."""
+    stop (tools/bench_retime_constrained.py measures it); `aorrtc_multi` does not know the constraint,
+    `aorrtc_multi_constrained` does."""
     s = settings if settings is not None else RetimeConstrainedSettings()
     raw = robot.retime_multi_constrained_raw(paths, vel_limits, acc_limits, environments, constraints, s, constraint_settings)
     off, lev = raw["offsets"].tolist(), raw["level_offsets"].tolist()
